@@ -462,6 +462,45 @@ WORKLOADS = {
 }
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6      # all files of one dump, .npy headers included
+NPY_HEADER_BYTES = 128
+DUMP_SEED = 20240601
+
+
+def _host(a):
+    """float64 ndarray of a host array, a scipy sparse matrix, a DeviceFactor or a (CUDA) torch tensor."""
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    elif hasattr(a, "toarray"):
+        a = a.toarray()
+    return np.asarray(a, dtype=np.float64)
+
+
+def dump_outputs(dirpath, arrays):
+    """`--dump-outputs DIR`: write the arrays the timed path returned in its last step as DIR/<name>.npy (float64),
+    DUMP_LIMIT_BYTES in all.  Smallest first, each array gets an equal share of what is left; one larger than its
+    share is replaced by a sample of its rows (axis 0) drawn with DUMP_SEED, in ascending row order, and the row
+    indices go to DIR/<name>_rows.npy.  Returns {name: description} for the JSON line."""
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = sorted(((name, _host(a)) for name, a in arrays), key=lambda na: na[1].nbytes)
+    left, info = DUMP_LIMIT_BYTES - 2 * NPY_HEADER_BYTES * len(arrays), {}    # room for a rows file per array
+    for i, (name, a) in enumerate(arrays):
+        share = left // (len(arrays) - i)
+        desc = dict(shape=list(a.shape), dtype="float64")
+        if a.nbytes > share:
+            row_bytes = a.nbytes // max(a.shape[0], 1) + 8
+            k = max(1, min(a.shape[0], share // row_bytes))
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], size=k, replace=False))
+            a = np.ascontiguousarray(a[rows])
+            np.save(os.path.join(dirpath, name + "_rows.npy"), rows.astype(np.float64))
+            left -= rows.size * 8
+            desc.update(sampled_rows=int(k), rows_file=name + "_rows.npy", seed=DUMP_SEED)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        left -= a.nbytes
+        info[name] = desc
+    return info
+
+
 def _xopts():
     """Developer hook for option sweeps: RICADI_OPTS="gmres_restart=40,agg_v=24"."""
     xopts = {}
@@ -472,11 +511,12 @@ def _xopts():
 
 
 def cycle_workload(name, world, rank, local, steps, warmup, col_split, barrier_fn, python_driver=False,
-                   with_cpu_baseline=True, interleave=True):
+                   with_cpu_baseline=True, interleave=True, outputs=None):
     """Times `steps` passes over the shift list of a WORKLOADS entry.  Default: through the boundary call
     pru.solve_proj_lyap_stein (C++ sweep driver; under torch.distributed the library shards the sweeps by shift
     over the ranks, RCCL all-gather on its stream) -- the same call at every rank count.  `python_driver`:
-    the Python sweep driver (shift_parallel.py; supports column parts).  Returns the result dict (rank 0)."""
+    the Python sweep driver (shift_parallel.py; supports column parts).  Returns the result dict (rank 0);
+    `outputs` (a dict) receives the factor Z of the last timed step as a host array."""
     import torch
     import torch.distributed as dist
     from optconpy_amd import _lib, backend, problems as pb
@@ -504,6 +544,7 @@ def cycle_workload(name, world, rank, local, steps, warmup, col_split, barrier_f
     n = pr.NV + pr.NP
     G = min(16, len(ms))
     parts = plan_items(G, world, col_split)
+    last = {}
     if python_driver:
         ops = HipOps(ctx)
         W = ops.to_panel(Wh)
@@ -514,6 +555,8 @@ def cycle_workload(name, world, rank, local, steps, warmup, col_split, barrier_f
             ops.worst_relres = 0.0
             blocks, info = lyap_adi_shift_parallel(ops, ms, W, adi_max_steps=len(ms), adi_newZ_reltol=0.0,
                                                    width=G, col_parts=parts)
+            if outputs is not None:
+                last["Z"] = blocks
             info["gmres_iters"] = ops.gmres_iters
             info["shift_solves"] = ops.shift_solves
             return info
@@ -524,6 +567,8 @@ def cycle_workload(name, world, rank, local, steps, warmup, col_split, barrier_f
         def step():
             ctx.clear_cache()
             o = pru.solve_proj_lyap_stein(amat=calA, mmat=MT, jmat=pr.J, wmat=Wh, transposed=True, adi_dict=dd)
+            if outputs is not None:
+                last["Z"] = o["zfac"]
             return dict(adi_steps=o["adi_steps"], gmres_iters=o["gmres_iters"], shift_solves=o["shift_solves"],
                         gmres_nonconverged=o["gmres_nonconverged"], gmres_worst_relres=o["gmres_worst_relres"],
                         res_fro=o["res_fro"])
@@ -543,6 +588,9 @@ def cycle_workload(name, world, rank, local, steps, warmup, col_split, barrier_f
         t = torch.tensor([el], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if outputs is not None and "Z" in last:          # after the timed region: the factor comes to the host here
+        Z = last["Z"]
+        outputs["Z"] = _host(torch.cat(Z, dim=1) if isinstance(Z, list) else Z)
     sinfo = ctx.setup_info()
     res = dict(workload="%s: driven-cavity pattern N=%d (%s), nu=%g; one step = one pass over the %d-shift list of "
                         "the open-loop Lyapunov ADI, panel m=%d, GMRES tol 1e-10, per-shift setup inside the step; %s"
@@ -572,14 +620,15 @@ def cycle_workload(name, world, rank, local, steps, warmup, col_split, barrier_f
     return res
 
 
-def dre_workload(args, rank):
+def dre_workload(args, rank, outputs=None):
     """`--workload cfg4-dre`: BASELINE cfg4 as what it is -- the time-varying differential Riccati loop at
     n ~ 1e5 (solve_dae_ric.py:121-211 through optconpy_amd.dae_ric.solve_flow_daeric, the boundary calls
     of every backward time step: Newton-ADI with z0 / w_mat = [M^T Z_c, sqrt(tau) C~^T] (m <= comprz_maxc +
     NY' + NU = 66), compression to comprz_maxc = 50, gain, feed-forward saddle solve), on the sine-squeezed
     time mesh get_tint(0, 1, Nts) (optcont_main.py:141-150) with a NEW operator per step
     (-(M^T/2 + tau_k (A + N(t_k))^T), N(t) = (1 + 0.5 sin(2 pi t)) N(vortex)).  One step = one whole
-    backward sweep; per time step wall-clock, Newton / ADI steps and shift-solves are reported."""
+    backward sweep; per time step wall-clock, Newton / ADI steps and shift-solves are reported.  `outputs` (a
+    dict) receives the gains and feed-forward terms of the last timed sweep."""
     import sadptprj_riclyap_adi.lin_alg_utils as lau
     import sadptprj_riclyap_adi.proj_ric_utils as pru
     from optconpy_amd import backend, problems as pb
@@ -634,14 +683,23 @@ def dre_workload(args, rank):
         fb = solve_flow_daeric(store=store, pru=Timed(), lau=lau, **kw)
         el = time.perf_counter() - t0
         K0 = store.load(fb[tmesh[0]]["mtxtb"])
+        if outputs is not None:
+            last.update(store=store, fb=fb)
         return el, list(rec), float(np.linalg.norm(K0))
 
+    last = {}
     for _ in range(args.warmup):
         one()
     tot, steps_rec, k0 = 0.0, None, None
     for _ in range(args.steps):
         el, steps_rec, k0 = one()
         tot += el
+    if outputs is not None:
+        # what solve_flow_daeric hands its caller, per time of the mesh: the gain M^T Z Z^T B~ and the feed-forward w
+        ts = sorted(last["fb"])
+        outputs["tmesh"] = np.asarray(ts, dtype=np.float64)
+        for key in ("mtxtb", "w"):
+            outputs[key] = np.stack([_host(last["store"].load(last["fb"][t][key])) for t in ts])
     units = sum(r["shift_solves"] for r in steps_rec)
     info = backend.context().setup_info()
     cpu = None
@@ -707,7 +765,12 @@ def main():
     ap.add_argument("--no-large-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="headline only (no second figures, no kernel rooflines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path returned in its last step as "
+                         "DIR/<name>.npy (float64, at most 64 MB in all; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # start the N ranks ourselves: a CHILD torchrun (never an exec), decided before torch or the HIP
@@ -759,9 +822,12 @@ def main():
         torch.cuda.synchronize()
         cx.synchronize()
 
+    outputs = {} if args.dump_outputs else None
     if args.workload == "cfg4-dre":
-        line = dre_workload(args, rank)
+        line = dre_workload(args, rank, outputs=outputs)
         if rank == 0:
+            if outputs is not None:
+                line["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs.items())
             print(json.dumps(line), flush=True)
         backend.reset()
         if world > 1:
@@ -770,7 +836,7 @@ def main():
     if args.workload in WORKLOADS:
         res = cycle_workload(args.workload, world, rank, local, args.steps, args.warmup, args.col_split, bar,
                              python_driver=args.python_driver, with_cpu_baseline=not args.no_cpu_baseline,
-                             interleave=not args.sorted_shifts)
+                             interleave=not args.sorted_shifts, outputs=outputs)
         if rank == 0:
             line = {
                 "metric": "ADI shift-solves/sec", "value": res["value"], "unit": "shift-solves/s",
@@ -779,6 +845,8 @@ def main():
                 "data": "synthetic", "config": res}
             if "cpu_baseline" in res:
                 line["cpu_baseline"] = res.pop("cpu_baseline")
+            if outputs is not None:
+                line["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs.items())
             print(json.dumps(line), flush=True)
         if world > 1:
             dist.destroy_process_group()
@@ -821,11 +889,14 @@ def main():
     # the step's input panels B~, C~^T, Z_k staged in HBM once, before any timed region (`value` is measured with
     # the inputs resident in HBM; the same step fed with host arrays is reported as value_pcie_inclusive)
     tb_d, trct_d, Zk_d = pru.to_device(tb), pru.to_device(trct), pru.to_device(Zk)
+    last = {}                  # --dump-outputs: the new factor of the latest step (downloaded after the timed region)
 
     def _dropin(bm, wm, z0):
         ctx.clear_cache()
         out = pru.proj_alg_ric_newtonadi(mmat=pr.M, amat=F, jmat=pr.J, bmat=bm, wmat=wm, z0=z0,
                                          nwtn_adi_dict=d1)
+        if outputs is not None:
+            last["Z"] = out["zfac"]
         K = -pru.get_mTzzTtb(MT, out["zfac"], bm)
         if out["gmres_nonconverged"]:
             raise RuntimeError("bench: %d timed shift-solves missed gmres_tol (worst %.2e)"
@@ -877,6 +948,8 @@ def main():
             raise RuntimeError("bench: %d timed shift-solves missed gmres_tol (worst %.2e)"
                                % (info["gmres_nonconverged"], info["gmres_worst_relres"]))
         Z = torch.cat(blocks, dim=1).contiguous()
+        if outputs is not None:
+            last["Z"] = Z
         Kt = ops.gain(-1.0, Z, sp["tbd"])                    # gain on the replicated factor
         return info["adi_steps"], ops.gmres_iters, Kt.cpu().numpy(), ops.shift_solves
 
@@ -918,6 +991,10 @@ def main():
 
     units, iters, local_solves, K, elapsed = timed(one_step, args.steps, args.warmup)
     main_step_ms = list(step_ms)
+    dumped = None
+    if outputs is not None and rank == 0:
+        # what the caller of the timed step receives: the gain K and the new low-rank factor Z of the last step
+        dumped = dump_outputs(args.dump_outputs, [("K", K), ("Z", last["Z"])])
     k_conv = float(np.linalg.norm(K - K_conv) / np.linalg.norm(K_conv))
     k_orc = None if K_oracle is None else float(np.linalg.norm(K - K_oracle) / np.linalg.norm(K_oracle))
 
@@ -978,6 +1055,8 @@ def main():
                               "FP32" if prec == "FP32" and os.environ.get("RICADI_MID32", "1") != "0" else "FP64"),
             },
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if k_orc is not None and k_orc > 1e-6:
             out["config"]["PARITY_VIOLATION"] = "K differs from the oracle fixture by %.2e > 1e-6" % k_orc
 

@@ -73,3 +73,24 @@ def test_cpu_baseline_leg_runs_on_a_tiny_problem():
     assert np.isfinite(out["value"]) and out["value"] > 0 and one["cores"] == 1
     assert "n = %d" % (pr.NV + pr.J.shape[0]) in one["sample"]
     assert one["step_seconds"] == pytest.approx(4 * one["lu_seconds"] + 8 * one["solve_seconds"], rel=0.05, abs=0.02)
+
+
+def test_dump_outputs_budget_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy per array, small ones whole, one over its share replaced by a seeded row sample
+    (with its row indices) so that the total stays within the limit; the same arrays give the same files."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    K = np.arange(12.0).reshape(6, 2).astype(np.float32)
+    Z = np.random.default_rng(0).standard_normal((20000, 16))            # 2.5 MB > 1 MB
+    info = bench.dump_outputs(str(tmp_path / "a"), [("Z", Z), ("K", K)])
+    bench.dump_outputs(str(tmp_path / "b"), [("Z", Z), ("K", K)])
+    k = np.load(tmp_path / "a" / "K.npy")
+    assert k.dtype == np.float64 and np.array_equal(k, K) and info["K"] == {"shape": [6, 2], "dtype": "float64"}
+    z, rows = np.load(tmp_path / "a" / "Z.npy"), np.load(tmp_path / "a" / "Z_rows.npy")
+    assert info["Z"]["shape"] == [20000, 16] and info["Z"]["sampled_rows"] == z.shape[0] == rows.size > 0
+    assert np.all(np.diff(rows) > 0) and np.array_equal(z, Z[rows.astype(int)])
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 1 << 20
+    for name in ("K.npy", "Z.npy", "Z_rows.npy"):
+        assert (tmp_path / "a" / name).read_bytes() == (tmp_path / "b" / name).read_bytes()

@@ -228,6 +228,28 @@ struct Exec {
   int* info = nullptr;
 };
 
+// The library's switches: environment variables RICADI_*, read once when a context is created (read_switches in
+// solver_capi.inl); a child level copies its parent's.  Each holds what the caller asked for -- whether the operator
+// allows a form is decided at set_operator (e.g. ricadi_ctx::ms_ok).
+struct Switches {
+  bool precond64 = false;     // RICADI_PRECOND64: the preconditioner applies the FP64 inverses
+  bool basis64 = false;       // RICADI_BASIS64: FP64-stored Krylov basis
+  bool basis32 = false;       // RICADI_BASIS32: FP32-stored Krylov basis (default: FP16 up to n = 2^21)
+  bool timing = false;        // RICADI_TIMING: wall-clock split of the drivers per Newton step
+  bool debug_sweeps = false;  // RICADI_DEBUG_SWEEPS: per-sweep report of the ADI drivers
+  bool smw = true;            // RICADI_SMW=0: keep the low-rank term inside the Krylov operator
+  bool wide_split = true;     // RICADI_WIDE_SPLIT=0: wide panels stay whole (gmres_core_any)
+  double sa_omega = 0.5;      // RICADI_SA=<omega>: damping of the smoothed aggregation (0: plain aggregation)
+  bool sweep_meta = true;     // RICADI_SWEEP_META=0: the generic sweep kernels instead of the record-driven ones
+  bool ms_spmm = true;        // RICADI_MS_SPMM=0: one assembled value array per shift instead
+  bool ms_force = false;      // RICADI_MS_SPMM=2: multi-shift kernel for every launch it can serve
+  bool w32 = true;            // RICADI_W32=0: the operator's output inside the Arnoldi iteration stays an FP64 panel
+  bool x32_always = true;     // RICADI_X32=0: the operator reads the FP32 Z_j only where the multi-shift SpMM runs
+  bool blocks16 = true;       // RICADI_BLOCKS16=0: the sweeps apply the FP32 copies of the per-shift blocks
+  bool rowwave = true;        // RICADI_ROWWAVE=0: the restriction through the 16-lanes-per-row CSR kernel
+  bool mid32 = true;          // RICADI_MID32=0: the velocity part between the sweeps of a cycle stays an FP64 panel
+};
+
 }  // namespace ricadi
 
 using namespace ricadi;
@@ -242,8 +264,9 @@ struct ricadi_ctx {
   // coarse correction, again dense or through a grandchild -- replaces the dense coarse apply.
   std::unique_ptr<ricadi_ctx> child;
   bool borrowed = false;      // st / rb belong to the parent level
-  int levels = 2;             // levels this context may use (RICADI_LEVELS; 2 = two-level only)
+  int levels = 2;             // levels this context may use (2 = two-level only)
   ricadi_opts opts;
+  Switches sw;
   bool has_op = false;
   int nv = 0, np = 0, n = 0;
   int bs = 32, nbv = 0, nbp = 0, kc = 0;
@@ -253,8 +276,8 @@ struct ricadi_ctx {
   DArr<double> srcA, srcE, srcJ;
   DevCsr A, E, J, JT;
   DArr<int> bv_ptr, bv_rows, bp_ptr, bp_rows, jd_ptr, jd_vblk;
-  DArr<int> ps_meta;          // fused pressure step: {row, J range, (S Y) range} per (Schur block, row), stride 5
-  // velocity sweeps: fixed-stride record per block (layout: ProlongArgs::bmeta); offsets of the two input lists
+  DArr<int> ps_meta;          // fused pressure step: one record per (Schur block, row) (layout: PSREC_*)
+  // velocity sweeps: fixed-stride record per block (layout: SWREC_*); offsets of the two input lists
   DArr<int> sw_meta;
   int sw_stride = 0, sw_in_rect = 0, sw_in_two = 0;
   DArr<double> bvA, bvE, jd_val;
@@ -298,22 +321,13 @@ struct ricadi_ctx {
   // from ONE read): saddle operator and prolongated operator
   DArr<double> sbAJ, sbE, sybAJ, sybE;
   DArr<uint16_t> sb_lidx_ms, syb_lidx_ms;
-  bool ms_spmm = true;        // RICADI_MS_SPMM=0: one assembled value array per shift instead
-  int ms_force = 0;           // RICADI_MS_SPMM=2: multi-shift kernel for every launch it can serve
-  bool w32 = true;            // RICADI_W32=0: the operator's output inside the Arnoldi iteration stays an FP64 panel
-  bool x32_always = true;     // RICADI_X32=0: the operator reads the FP32 Z_j only where the multi-shift SpMM runs
-  bool blocks16 = true;       // RICADI_BLOCKS16=0: the sweeps apply the FP32 copies of the per-shift blocks
-  bool rowwave = true;        // RICADI_ROWWAVE=0: the restriction through the 16-lanes-per-row CSR kernel
-  bool mid32 = true;          // RICADI_MID32=0: the velocity part between the sweeps of a cycle stays an FP64 panel
-  bool sweep_mfma32 = false;  // RICADI_SWEEP32=1: first velocity sweep on the FP32 matrix cores (experimental, unmeasured: DESIGN 10a)
-  bool coarse_mfma32 = false; // RICADI_COARSE32=1: coarse apply on the FP32 matrix cores (experimental, unmeasured: DESIGN 10a)
+  bool ms_ok = false;         // the operator's tiles allow the multi-shift kernel (its value arrays exist)
   int w32_last = -1;          // the last operator launch of an iteration / timing class wrote the FP32 panel (1) or FP64 (0)
   int mid32_last = -1;        // what the last preconditioner application did (1 FP32 panel, 0 FP64; -1 none yet)
   // low rank
   int q = 0;
   DArr<double> U, V, lrc, scratch;
   long lr_epoch = 0;          // bumped whenever U / V change
-  bool smw = true;            // RICADI_SMW=0: keep the low-rank term inside the Krylov operator
   DArr<double> smw_rhs, smw_x, smw_cap;
   DArr<double> split_b, split_x;   // wide panels as sixteen-column groups (gmres_core_any)
   DArr<double> sweep_u, sweep_t, sweep_coef, sweep_part;   // ADI sweeps: the G solutions, a panel, coefficients, norm partials
@@ -324,9 +338,9 @@ struct ricadi_ctx {
   DArr<double> basis, vcur, wv, zv, r2, tp, rc, ec, xs, bvec, pw1, pw2;
   DArr<float> basisf, zbasisf;   // zbasisf: Z_j = P^-1 v_j of the flexible GMRES, FP32
   DArr<float> wv32;              // w = S z_j of the hot path as an FP32 panel (round 4; the FP64 wv serves the restarts)
-  bool flex = true;              // RICADI_FGMRES=0: plain right preconditioning (x += P^-1 (V y) per cycle)
+  // storage in force (the switches' choice; a solve that misses its tolerance repeats with wider storage: StorageScope)
   bool basis32 = true;
-  bool basis16 = true;        // FP16-stored Krylov basis (default for n <= 2^21)
+  bool basis16 = true;        // FP16-stored Krylov basis (default for n <= 2^21: basis16_default)
   bool precond32 = true;
   DArr<double> partial, h1, h2, H, cs, sn, g, scale, resid, yv, bnorm2, nrm2;
   DArr<int> flag, ipiv, info;
@@ -384,9 +398,8 @@ struct ricadi_ctx {
   long total_iters = 0, total_solves = 0;
   long escalations = 0;       // solves repeated with wider storage of basis / preconditioner (safety net)
   int pc_stage = -1;          // >= 0: precond_apply issues only that stage (ricadi_time_kernel_dev)
-  // wall-clock split of the drivers (RICADI_TIMING=1 prints it per Newton step; the stream is
+  // wall-clock split of the drivers (sw.timing prints it per Newton step; the stream is
   // drained at the section ends only in that mode)
-  bool timing = false;
   double t_setup = 0, t_solve = 0, t_recomb = 0, t_compress = 0, t_updnorm = 0, t_proj = 0, t_gain = 0;
   double t_cyc = 0, t_iter = 0, t_guess = 0, t_smw = 0;   // inside t_solve: restart-cycle bookkeeping, Arnoldi iterations, recycling, SMW + checks
 
@@ -403,4 +416,7 @@ struct ricadi_ctx {
     if (st && !borrowed) (void)hipStreamDestroy(st);
   }
 };
+
+// The Krylov basis is stored in FP16 unless a switch asks for wider storage or n > 2^21 (ensure_work)
+inline bool basis16_default(const ricadi_ctx* c) { return !c->sw.basis64 && !c->sw.basis32 && c->n <= (1 << 21); }
 

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
+#include <stdexcept>
 
 #include "ricadi_internal.h"
 
@@ -861,6 +862,226 @@ int cauchy_data(const double* shifts, int g, double* rinv, double* cinv1) {
     cinv1[i] = (double)v;
   }
   return RICADI_OK;
+}
+
+// ---- device records of the preconditioner (uploaded by ricadi_set_operator) ---------------------------------------
+// Sorted distinct columns that the rows of every velocity block touch in the CSR matrix (rp, ci): the lists one after
+// the other in cols, block b's at [ptr[b], ptr[b + 1]); returns the length of the longest list.
+static int block_columns(const HostSetup& hs, const std::vector<int>& rp, const std::vector<int>& ci,
+                         std::vector<int>& ptr, std::vector<int>& cols) {
+  ptr.assign(hs.nbv + 1, 0);
+  cols.clear();
+  int kmax = 0;
+  std::vector<int> tmp;
+  for (int b = 0; b < hs.nbv; ++b) {
+    tmp.clear();
+    for (int q = hs.bv_ptr[b]; q < hs.bv_ptr[b + 1]; ++q)
+      for (int k = rp[hs.bv_rows[q]]; k < rp[hs.bv_rows[q] + 1]; ++k) tmp.push_back(ci[k]);
+    std::sort(tmp.begin(), tmp.end());
+    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+    cols.insert(cols.end(), tmp.begin(), tmp.end());
+    ptr[b + 1] = (int)cols.size();
+    kmax = std::max(kmax, (int)tmp.size());
+  }
+  return kmax;
+}
+
+// Dense bs x ks slice per velocity block of the CSR matrix (rp, ci, v) over the block's column list (ptr, cols of
+// block_columns): out[(b bs + row of the block) ks + position of the column in the list] += value.
+static std::vector<double> block_slices(const HostSetup& hs, const std::vector<int>& rp, const std::vector<int>& ci,
+                                        const std::vector<double>& v, const std::vector<int>& ptr,
+                                        const std::vector<int>& cols, int ks) {
+  std::vector<double> out((size_t)hs.nbv * hs.bs * ks, 0.0);
+  for (int b = 0; b < hs.nbv; ++b) {
+    const int* cb = cols.data() + ptr[b];
+    const int nc = ptr[b + 1] - ptr[b];
+    for (int q = hs.bv_ptr[b]; q < hs.bv_ptr[b + 1]; ++q) {
+      const int row = hs.bv_rows[q], il = q - hs.bv_ptr[b];
+      for (int k = rp[row]; k < rp[row + 1]; ++k) {
+        const int* f = std::lower_bound(cb, cb + nc, ci[k]);
+        if (f == cb + nc || *f != ci[k]) throw std::runtime_error("dense block slice: column outside the block's list");
+        out[((size_t)b * hs.bs + il) * ks + (int)(f - cb)] += v[k];
+      }
+    }
+  }
+  return out;
+}
+
+void build_setup_checked(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ricadi_opts& o,
+                         HostSetup& hs, int max_levels, double sa_omega) {
+  build_setup(A, E, J, o, hs, max_levels, sa_omega);
+  if (!hs.sa) return;
+  // the folded first sweep takes per-block dense slices of S*P of at most 64 columns
+  std::vector<int> ptr, cols;
+  const int kmax = block_columns(hs, hs.sy_rp, hs.sy_ci, ptr, cols);
+  if (kmax > 64 || !block_apply2_ok(hs.bs, 64)) {
+    if (o.verbose)
+      fprintf(stderr, "[ricadi] smoothed aggregation off: a velocity block touches %d coarse columns\n", kmax);
+    hs = HostSetup();
+    build_setup(A, E, J, o, hs, max_levels, 0.0);
+  }
+}
+
+// Multi-shift operands of a CSR matrix with three value sources (a, e, j) in the tile order perm; ncol_v: columns
+// below it are velocity columns
+static void ms_arrays(const HostSetup& hs, const std::vector<int>& rp, const std::vector<int>& ci,
+                      const std::vector<double>& a, const std::vector<double>& e, const std::vector<double>& j,
+                      const std::vector<int>& perm, const std::vector<uint16_t>& lidx, int ncol_v,
+                      std::vector<double>& aj, std::vector<double>& ee, std::vector<uint16_t>& lm) {
+  const size_t nnz = perm.size();
+  std::vector<int> rowof(ci.size());
+  for (int i = 0; i + 1 < (int)rp.size(); ++i)
+    for (int k = rp[i]; k < rp[i + 1]; ++k) rowof[k] = i;
+  aj.resize(nnz);
+  ee.resize(nnz);
+  lm.resize(nnz);
+  for (size_t kb = 0; kb < nnz; ++kb) {
+    const int k = perm[kb];
+    aj[kb] = a[k] + j[k];
+    ee[kb] = e[k];
+    const bool vv = rowof[k] < hs.nv && ci[k] < ncol_v;
+    lm[kb] = (uint16_t)(lidx[kb] | (vv ? 0x8000 : 0));
+  }
+}
+
+// Row block b of a tile format: its row pointers padded to 33 (rp2) and its column list to mc entries (cols2)
+static void pad_tile_block(const std::vector<int>& rowptr, const std::vector<int>& rp, const std::vector<int>& cptr,
+                           const std::vector<int>& colsrc, int b, int mc, std::vector<int>& rp2,
+                           std::vector<int>& cols2) {
+  const int q0 = rowptr[b], nr = rowptr[b + 1] - q0;
+  for (int q = 0; q <= 32; ++q) rp2[(size_t)b * 33 + q] = rp[q0 + std::min(q, nr)];
+  const int c0 = cptr[b], nc = cptr[b + 1] - c0;
+  for (int k = 0; k < nc; ++k) cols2[(size_t)b * mc + k] = colsrc[c0 + k];
+}
+
+PrecondRecords build_records(const HostSetup& hs, const HostCsr& J, const HostCsr& JT, bool sweep_meta,
+                             bool ms_spmm) {
+  PrecondRecords r;
+  const int np = hs.np;
+  // rectangular last sweep: pressure dofs touched by every velocity block, dense J^T slices
+  if (np > 0 && hs.nbv > 0) {
+    std::vector<int> ptr, cols;
+    const int kmax = block_columns(hs, JT.rp, JT.ci, ptr, cols);
+    const int ks = kmax <= 32 ? 32 : (kmax <= 64 ? 64 : (kmax <= 128 ? 128 : 0));
+    if (ks > 0 && block_apply_rect_ok(hs.bs, ks)) {
+      r.jtd = block_slices(hs, JT.rp, JT.ci, JT.v, ptr, cols, ks);
+      r.gt_ptr = std::move(ptr);
+      r.gt_cols = std::move(cols);
+      r.gt_ks = ks;
+      r.gt_kmax = kmax;
+      r.gt_ok = true;
+    }
+  }
+  // records of the fused pressure step (pressure_step_kernel): one load per (block, row) instead of the chain
+  // block list -> row index -> row pointers
+  r.ps_meta.assign((size_t)std::max(hs.nbp, 0) * 32 * PSREC_WIDTH, 0);
+  const bool with_sy = hs.kc > 0 && (int)hs.sy_rp.size() == hs.n + 1;
+  for (int b = 0; b < hs.nbp; ++b)
+    for (int il = 0; il < 32; ++il) {
+      int* mt = &r.ps_meta[((size_t)b * 32 + il) * PSREC_WIDTH];
+      const int cnt = hs.bp_ptr[b + 1] - hs.bp_ptr[b];
+      if (il >= cnt || cnt > 32) {
+        mt[PSREC_ROW] = -1;
+        continue;
+      }
+      const int prow = hs.bp_rows[hs.bp_ptr[b] + il];
+      mt[PSREC_ROW] = prow;
+      mt[PSREC_J0] = J.rp[prow];
+      mt[PSREC_J1] = J.rp[prow + 1];
+      mt[PSREC_SY0] = with_sy ? hs.sy_rp[hs.nv + prow] : 0;
+      mt[PSREC_SY1] = with_sy ? hs.sy_rp[hs.nv + prow + 1] : 0;
+      // (the kernel clamps its index loads to the row's last entry: an empty row must not point behind the arrays)
+      if (mt[PSREC_J1] == mt[PSREC_J0]) mt[PSREC_J0] = mt[PSREC_J1] = 0;
+      if (mt[PSREC_SY1] == mt[PSREC_SY0]) mt[PSREC_SY0] = mt[PSREC_SY1] = 0;
+    }
+  // dense slices of S*Y per velocity block (first sweep with the coarse residual folded in)
+  if (hs.kc > 0 && np > 0 && hs.nbv > 0 && !hs.sy_rp.empty()) {
+    std::vector<int> ptr, cols;
+    const int kmax = block_columns(hs, hs.sy_rp, hs.sy_ci, ptr, cols);
+    const int ks = kmax <= 32 ? 32 : (kmax <= 64 ? 64 : 0);
+    if (ks > 0 && block_apply2_ok(hs.bs, ks)) {
+      r.dA = block_slices(hs, hs.sy_rp, hs.sy_ci, hs.sy_A, ptr, cols, ks);
+      r.dE = block_slices(hs, hs.sy_rp, hs.sy_ci, hs.sy_E, ptr, cols, ks);
+      r.dJ = block_slices(hs, hs.sy_rp, hs.sy_ci, hs.sy_J, ptr, cols, ks);
+      // (P - Y)[row, :]: its columns are among those of (S P)[row, :] (S has a diagonal)
+      if (hs.sa) r.dT = block_slices(hs, hs.pd_rp, hs.pd_ci, hs.pd_v, ptr, cols, ks);
+      r.cy_ptr = std::move(ptr);
+      r.cy_cols = std::move(cols);
+      r.ady_ks = ks;
+      r.ady_ok = true;
+    }
+  }
+  // fixed-stride records of the velocity sweeps (block_rect32_kernel, block_two32_kernel; ProlongArgs::bmeta)
+  if (sweep_meta && hs.bs == 32 && hs.nbv > 0 && (r.gt_ok || r.ady_ok)) {
+    const int kr = r.gt_ok ? r.gt_ks : 0, k2 = r.ady_ok ? r.ady_ks : 0;
+    const int stride = swrec_stride(kr, k2);
+    std::vector<int> meta((size_t)hs.nbv * stride, 0);
+    bool ok = true;
+    for (int b = 0; b < hs.nbv && ok; ++b) {
+      int* mt = &meta[(size_t)b * stride];
+      const int b0 = hs.bv_ptr[b], nb = hs.bv_ptr[b + 1] - b0;
+      if (nb > 32 || nb <= 0) { ok = false; break; }
+      mt[SWREC_NB] = nb;
+      for (int i = 0; i < 32; ++i) {
+        const int row = hs.bv_rows[b0 + std::min(i, nb - 1)];
+        mt[SWREC_ROWS + i] = row;
+        mt[SWREC_AGG + i] = hs.kc > 0 ? hs.aggof[row] : 0;
+      }
+      if (r.gt_ok) {
+        const int i0 = r.gt_ptr[b], ni = r.gt_ptr[b + 1] - i0;
+        mt[SWREC_NI_RECT] = ni;
+        for (int i = 0; i < kr; ++i) mt[SWREC_IN + i] = ni > 0 ? r.gt_cols[i0 + std::min(i, ni - 1)] : 0;
+      }
+      if (r.ady_ok) {
+        const int i0 = r.cy_ptr[b], ni = r.cy_ptr[b + 1] - i0;
+        mt[SWREC_NI_TWO] = ni;
+        for (int i = 0; i < k2; ++i) mt[SWREC_IN + kr + i] = ni > 0 ? r.cy_cols[i0 + std::min(i, ni - 1)] : 0;
+      }
+    }
+    if (ok) {
+      r.sw_meta = std::move(meta);
+      r.sw_stride = stride;
+      r.sw_in_rect = SWREC_IN;
+      r.sw_in_two = SWREC_IN + kr;
+    }
+  }
+  // tile formats padded to fixed strides: rows2 [nblk][32], rp2 [nblk][33], cols2 [nblk][max cols], colsm2 = cols2
+  // through the aggregate map
+  const int nb = hs.sb_nblk;
+  r.syb_ok = hs.kc > 0 && nb > 0 && hs.syb_max_cols > 0;
+  if (r.syb_ok) {
+    const int mc = hs.syb_max_cols;
+    r.syb_rp2.assign((size_t)nb * 33, 0);
+    r.syb_cols2.assign((size_t)nb * mc, -1);
+    for (int b = 0; b < nb; ++b)
+      pad_tile_block(hs.sb_rowptr, hs.syb_rp, hs.syb_cptr, hs.syb_cols, b, mc, r.syb_rp2, r.syb_cols2);
+  }
+  {
+    const int mc = std::max(hs.sb_max_cols, 1);
+    r.sb_rows2.assign((size_t)nb * 32, -1);
+    r.sb_rp2.assign((size_t)nb * 33, 0);
+    r.sb_cols2.assign((size_t)nb * mc, -1);
+    r.sb_colsm2.assign((size_t)nb * mc, -1);
+    for (int b = 0; b < nb; ++b) {
+      const int q0 = hs.sb_rowptr[b], nr = hs.sb_rowptr[b + 1] - q0;
+      for (int q = 0; q < nr; ++q) r.sb_rows2[(size_t)b * 32 + q] = hs.sb_rows[q0 + q];
+      pad_tile_block(hs.sb_rowptr, hs.sb_rp, hs.sb_cptr, hs.sb_cols, b, mc, r.sb_rp2, r.sb_cols2);
+      for (int k = hs.sb_cptr[b]; k < hs.sb_cptr[b + 1]; ++k)
+        r.sb_colsm2[(size_t)b * mc + (k - hs.sb_cptr[b])] = hs.kc > 0 ? hs.aggof[hs.sb_cols[k]] : -1;
+    }
+  }
+  r.sb_ok = nb > 0 && hs.sb_max_cols < 65536;
+  // multi-shift operands: those of the saddle operator whenever its tiles are narrow enough, those of S*Y only when
+  // the multi-shift kernel is switched on as well
+  r.ms_ok = r.sb_ok && hs.sb_max_cols <= 160;
+  if (r.ms_ok)
+    ms_arrays(hs, hs.s_rp, hs.s_ci, hs.s_srcA, hs.s_srcE, hs.s_srcJ, hs.sb_perm, hs.sb_lidx, hs.nv, r.sbAJ, r.sbE,
+              r.sb_lidx_ms);
+  if (r.syb_ok && hs.syb_max_cols <= 160 && r.ms_ok && ms_spmm)
+    ms_arrays(hs, hs.sy_rp, hs.sy_ci, hs.sy_A, hs.sy_E, hs.sy_J, hs.syb_perm, hs.syb_lidx, hs.kcv, r.sybAJ, r.sybE,
+              r.syb_lidx_ms);
+  r.sy_chunk = (hs.sy_ci.size() <= (size_t)10 * std::max(hs.n, 1)) ? 8 : 16;
+  return r;
 }
 
 }  // namespace ricadi

@@ -85,6 +85,59 @@ struct HostSetup {
 };
 void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ricadi_opts& o,
                  HostSetup& hs, int max_levels = 2, double sa_omega = 0.0);
+// build_setup, rebuilt without smoothed aggregation when the smoothed prolongation does not fit the folded first
+// sweep (a velocity block touching more than 64 coarse columns)
+void build_setup_checked(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ricadi_opts& o,
+                         HostSetup& hs, int max_levels, double sa_omega);
+
+// ---- device records of the preconditioner ------------------------------------------
+// Fixed-stride record of a 32-row velocity block (ricadi_ctx::sw_meta, ProlongArgs::bmeta): a header of
+// SWREC_ROWS words {nb, ni of the rectangle sweep, ni of the two-term sweep, 0}, then the block's rows [32], the
+// aggregate of every row [32], the input rows of the rectangle sweep [kr] and of the two-term sweep [k2]; every list
+// is padded with its last entry.  kr / k2: padded slice widths of the two sweeps (0: sweep not in that form).
+constexpr int SWREC_NB = 0, SWREC_NI_RECT = 1, SWREC_NI_TWO = 2;
+constexpr int SWREC_ROWS = 4;
+constexpr int SWREC_AGG = SWREC_ROWS + 32;
+constexpr int SWREC_IN = SWREC_AGG + 32;
+constexpr int swrec_stride(int kr, int k2) { return SWREC_IN + kr + k2; }
+// Record of one (Schur block, row of the block) of the fused pressure step (ricadi_ctx::ps_meta), PSREC_WIDTH words:
+// {pressure-local row or -1, J row range [j0, j1), (S Y) pressure-row range [sy0, sy1)}; an empty range is [0, 0)
+constexpr int PSREC_ROW = 0, PSREC_J0 = 1, PSREC_J1 = 2, PSREC_SY0 = 3, PSREC_SY1 = 4, PSREC_WIDTH = 5;
+
+// Everything the preconditioner uploads beyond the HostSetup arrays themselves, derived on the host from the setup,
+// J and J^T.  sweep_meta: build the fixed-stride sweep records (RICADI_SWEEP_META); ms_spmm: the multi-shift value
+// arrays of S*Y (RICADI_MS_SPMM; those of the saddle operator are built whenever its tiles allow them).
+struct PrecondRecords {
+  // last velocity sweep in rectangular form: per velocity block the pressure dofs its rows touch (gt_ptr / gt_cols)
+  // and the dense bs x gt_ks slices of J^T over them; gt_kmax = longest list
+  bool gt_ok = false;
+  int gt_ks = 0, gt_kmax = 0;
+  std::vector<int> gt_ptr, gt_cols;
+  std::vector<double> jtd;
+  // first velocity sweep with the coarse residual folded in: per velocity block the coarse columns its S*Y rows
+  // touch and the dense bs x ady_ks slices of the three value sources (dT: of P - Y, smoothed aggregation only)
+  bool ady_ok = false;
+  int ady_ks = 0;
+  std::vector<int> cy_ptr, cy_cols;
+  std::vector<double> dA, dE, dJ, dT;
+  std::vector<int> ps_meta;                    // PSREC_WIDTH words per (Schur block, row)
+  std::vector<int> sw_meta;                    // swrec_stride words per velocity block; empty: sw_stride = 0
+  int sw_stride = 0, sw_in_rect = 0, sw_in_two = 0;
+  // tile format of the saddle operator padded to fixed strides (see spmm_blocked_kernel)
+  bool sb_ok = false;
+  std::vector<int> sb_rows2, sb_rp2, sb_cols2, sb_colsm2;
+  // ... and of S*Y
+  bool syb_ok = false;
+  std::vector<int> syb_rp2, syb_cols2;
+  // multi-shift kernel operands in tile order: AJ = A part + J part (disjoint supports), E, and the local index with
+  // the velocity-velocity flag in bit 15; ms_ok: those of the saddle operator were built
+  bool ms_ok = false;
+  std::vector<double> sbAJ, sbE, sybAJ, sybE;
+  std::vector<uint16_t> sb_lidx_ms, syb_lidx_ms;
+  int sy_chunk = 16;                           // row chunk of the S*Y CSR kernel: 8 when its rows are short
+};
+PrecondRecords build_records(const HostSetup& hs, const HostCsr& J, const HostCsr& JT, bool sweep_meta,
+                             bool ms_spmm);
 bool sa_criterion(const HostCsr& A, double& rs_out, double& gamma_out);
 int cauchy_data(const double* shifts, int g, double* rinv, double* cinv1);
 int deal_shifts(const double* shifts, int ns, int world, int32_t* owner);
@@ -146,10 +199,9 @@ struct ProlongArgs {
   size_t gs32 = 0;
   int only32 = 0;           // with out32: the FP64 result is not stored (the operator reads the FP32 copy)
   int old32 = 0;            // rectangle sweep: the rows it updates are read from out32 (FP32 intermediate of the cycle)
-  // Fixed-stride record per 32-row block (ricadi_ctx::sw_meta): {nb, ni of the rectangle sweep, ni of the two-term
-  // sweep, 0 | rows[32] | aggregate of every row [32] | input rows of the rectangle sweep | of the two-term sweep},
-  // lists padded with their last entry.  With it a wave has every index after ONE load round (block pointers ->
-  // row lists -> aggregate map were three dependent ones); bm_in = offset of the launched sweep's input list.
+  // Fixed-stride record per 32-row block (ricadi_ctx::sw_meta; layout: SWREC_* above).  With it a wave has every
+  // index after ONE load round (block pointers -> row lists -> aggregate map were three dependent ones); bm_in =
+  // offset of the launched sweep's input list (SWREC_IN for the rectangle sweep, SWREC_IN + kr for the two-term one).
   const int* bmeta = nullptr;
   int bm_stride = 0, bm_in = 0, bm_ni = 0;   // bm_ni: which header word holds ni (1 or 2)
 };
@@ -310,10 +362,8 @@ void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblock
 void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, const GroupPtrs& Einv,
                           const double* rc, double* ec);
 // FP32-stored inverses (leading dimension ldf = k rounded up to 4; bs x bs blocks)
-// f32_matrix_cores: the product on v_mfma_f32_16x16x4_f32 (coarse residual rounded to FP32, FP32 accumulation per K
-// slice) instead of v_mfma_f64_16x16x4_f64 -- experimental, see the kernel
 void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, const GroupPtrsF& Einv,
-                          int ldf, const double* rc, double* ec, bool f32_matrix_cores = false);
+                          int ldf, const double* rc, double* ec);
 void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
                           const int* rows, const GroupPtrsF& inv, const double* in, int ldi,
                           size_t gsi, double* out, int ldo, size_t gso, int m, int subtract,
@@ -410,8 +460,7 @@ void launch_to_bf16(hipStream_t st, size_t n, const double* src, uint16_t* dst);
 // contracts as launch_block_apply2_b / launch_block_apply_rect_b / launch_pressure_step_b with the FP32 panel; return
 // false (nothing launched) when the shape is not the hot one.
 bool launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const GroupPtrsH& m1, const Seg2& s1,
-                          const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa,
-                          bool f32_matrix_cores = false);
+                          const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa);
 bool launch_block_rect32_h(hipStream_t st, const GroupTab& gt, int ks, int nblocks, const GroupPtrsH& mats,
                            const double* in, size_t gsi, double* out, size_t gso, int subtract, const ProlongArgs& pa);
 void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
@@ -421,8 +470,8 @@ void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, con
 
 // K2p: the pressure step of the SIMPLE cycle fused into one launch (m = 16, 32 x 32 Schur blocks):
 //   out[rows_b] = inv_b (J z + (S Y)_p ec - r_p)[rows_b]  with the epilogue options of the Schur sweep (pa).
-// meta: per (block, row of the block) five ints {pressure-local row or -1, J row range [k0, k1), (S Y) pressure-row
-// range [s0, s1)} at stride 5 (ricadi_ctx::ps_meta); with_sy = false: no coarse term; z is the n x 16 panel whose
+// meta: per (block, row of the block) one PSREC_WIDTH-word record (layout: PSREC_* above; ricadi_ctx::ps_meta);
+// with_sy = false: no coarse term; z is the n x 16 panel whose
 // velocity rows are read, rp_ / rp16 the pressure rows of the residual (FP64 or FP16-stored), out the pressure rows of z.
 // zv32 (optional, group stride gsz32): the velocity rows as the FP32 panel the first sweep left (64-B row gathers).
 void launch_pressure_step_b(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,

@@ -235,8 +235,8 @@ void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblock
 // The generic kernels above spend their time in dependent load rounds, not in bytes: block pointers -> row / input
 // lists -> aggregate map -> gathers -> rows to update -> stores is five round trips per wave at 2-4 waves per SIMD
 // (with the FP32 intermediate the last sweep moved 40 % fewer bytes in the same 738 us at n = 5e5).  Here
-//   * every index of a block comes out of ONE fixed-stride record (ricadi_ctx::sw_meta, layout at
-//     ProlongArgs::bmeta: lists padded with their last entry, the aggregate of every row stored with it);
+//   * every index of a block comes out of ONE fixed-stride record (ricadi_ctx::sw_meta, layout SWREC_* in
+//     ricadi_internal.h: lists padded with their last entry, the aggregate of every row stored with it);
 //   * the gathers, the matrix tiles AND the rows the wave updates are requested together (the old rows do not
 //     depend on the products);
 //   * addresses are 32-bit byte offsets from uniform bases (one VGPR per load in flight instead of two), no column
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void block_rect32_kernel(
   const int* __restrict__ mt = meta + (size_t)wave * mstride;
   const T* __restrict__ Gi = mat + (size_t)wave * 32 * KS;
   // round 1: the record
-  const int nb = mt[0], ni = mt[1];
+  const int nb = mt[SWREC_NB], ni = mt[SWREC_NI_RECT];
   int xrow[NK][4], orow[2][4], oagg[2][4];
 #pragma unroll
   for (int kc = 0; kc < NK; ++kc)
@@ -285,8 +285,8 @@ __global__ __launch_bounds__(256) void block_rect32_kernel(
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      orow[t][e] = mt[4 + 16 * t + q + 4 * e];
-      oagg[t][e] = mt[36 + 16 * t + q + 4 * e];
+      orow[t][e] = mt[SWREC_ROWS + 16 * t + q + 4 * e];
+      oagg[t][e] = mt[SWREC_AGG + 16 * t + q + 4 * e];
     }
   // round 2: gathers, tiles, old rows, coarse part -- raw values, converted behind the barrier
   const double* __restrict__ ecp = ec ? ec : in;         // a readable dummy when there is no coarse part
@@ -371,12 +371,12 @@ __global__ __launch_bounds__(256) void block_two32_kernel(
   const double* __restrict__ in2 = s2.in + (size_t)grp * s2.gs;
   const int* __restrict__ mt = meta + (size_t)wave * mstride;
   // round 1: the record (lists padded with valid rows: no condition on any address)
-  const int nb = mt[0], ni = mt[2];
+  const int nb = mt[SWREC_NB], ni = mt[SWREC_NI_TWO];
   int r1[2][4], r2[N2][4], orow[2][4];
 #pragma unroll
   for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) r1[kc][s4] = mt[4 + kc * 16 + 4 * q + s4];
+    for (int s4 = 0; s4 < 4; ++s4) r1[kc][s4] = mt[SWREC_ROWS + kc * 16 + 4 * q + s4];
 #pragma unroll
   for (int kc = 0; kc < N2; ++kc)
 #pragma unroll
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(256) void block_two32_kernel(
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) orow[t][e] = mt[4 + 16 * t + q + 4 * e];
+    for (int e = 0; e < 4; ++e) orow[t][e] = mt[SWREC_ROWS + 16 * t + q + 4 * e];
   // round 2: both input panels and the four / six matrix tiles, raw
   _Float16 h1[2][4];
   double x1[2][4], x2[N2][4];
@@ -456,124 +456,6 @@ __global__ __launch_bounds__(256) void block_two32_kernel(
         if (pa.out2) pa.out2[(size_t)grp * pa.gs2 + at] = v;
         if (!(o32 && pa.only32)) out[at] = v;
         if (o32) o32[at] = (float)v;
-      }
-    }
-}
-
-// The first sweep on the FP32 matrix cores (v_mfma_f32_16x16x4_f32; BF16-stored blocks widened by a shift, the two
-// input panels rounded to FP32, FP32 accumulation over the block's <= 96 terms): block_two32_kernel above does 1.30
-// GFLOP per 16-group launch at cfg2 in 34 us = 0.49 of the FP64 matrix peak beside its 0.46 of HBM.  The arithmetic
-// was mirrored on scipy (tools/schur_lab.py `sa+b16+m32`: iteration counts identical).  As the coarse apply's FP32
-// form: WRITTEN IN THE LAST SESSION OF ROUND 4 WITHOUT GPU-MINUTES LEFT, never run on the device, off unless
-// RICADI_SWEEP32=1.  Differences from the kernel above: operand and accumulator types, and
-// the C/D map of the FP32 form -- row = 4 (l >> 4) + reg instead of (l >> 4) + 4 reg -- in the output rows.
-template <int K2, bool H1>
-__global__ __launch_bounds__(256) void block_two32_f32mfma_kernel(
-    GroupTab gt, int nblocks, const int* __restrict__ meta, int mstride, int in_off, GroupPtrsT<uint16_t> m1s, Seg2 s1,
-    GroupPtrsT<uint16_t> m2s, Seg2 s2, double* __restrict__ out, size_t gso, ProlongArgs pa) {
-  const int grp = gt.gid[blockIdx.z];
-  out += (size_t)grp * gso;
-  float* __restrict__ o32 = pa.out32 ? pa.out32 + (size_t)grp * pa.gs32 : nullptr;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (wave >= nblocks) return;
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 15, q = lane >> 4;
-  constexpr int N2 = K2 / 16;
-  const uint16_t* __restrict__ M1 = m1s.p[grp] + (size_t)wave * 32 * 32;
-  const uint16_t* __restrict__ M2 = m2s.p[grp] + (size_t)wave * 32 * K2;
-  const double* __restrict__ in1 = s1.in ? s1.in + (size_t)grp * s1.gs : nullptr;
-  const _Float16* __restrict__ in1h = s1.in16 ? s1.in16 + (size_t)grp * s1.gs : nullptr;
-  const double* __restrict__ in2 = s2.in + (size_t)grp * s2.gs;
-  const int* __restrict__ mt = meta + (size_t)wave * mstride;
-  const int nb = mt[0], ni = mt[2];
-  int r1[2][4], r2[N2][4], orow[2][4];
-#pragma unroll
-  for (int kc = 0; kc < 2; ++kc)
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) r1[kc][s4] = mt[4 + kc * 16 + 4 * q + s4];
-#pragma unroll
-  for (int kc = 0; kc < N2; ++kc)
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) r2[kc][s4] = mt[in_off + kc * 16 + 4 * q + s4];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) orow[t][e] = mt[4 + 16 * t + 4 * q + e];      // FP32 C/D map
-  _Float16 h1[2][4];
-  double x1[2][4], x2[N2][4];
-  uint2 a1[2][2], a2[2][N2];
-#pragma unroll
-  for (int kc = 0; kc < 2; ++kc)
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-      if (H1) h1[kc][s4] = ld_off(in1h, (unsigned)(r1[kc][s4] * 16 + r) * 2u);
-      else x1[kc][s4] = ld_off(in1, (unsigned)(r1[kc][s4] * 16 + r) * 8u);
-    }
-#pragma unroll
-  for (int kc = 0; kc < N2; ++kc)
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) x2[kc][s4] = ld_off(in2, (unsigned)(r2[kc][s4] * 16 + r) * 8u);
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-#pragma unroll
-    for (int kc = 0; kc < 2; ++kc) a1[t][kc] = Raw4<uint16_t>::load(M1 + (16 * t + r) * 32 + kc * 16 + 4 * q);
-#pragma unroll
-    for (int kc = 0; kc < N2; ++kc) a2[t][kc] = Raw4<uint16_t>::load(M2 + (16 * t + r) * K2 + kc * 16 + 4 * q);
-  }
-#pragma unroll
-  for (int kc = 0; kc < N2; ++kc)
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) asm volatile("" : "+v"(x2[kc][s4]));
-  __builtin_amdgcn_sched_barrier(0);
-  auto widen = [](const uint2& u, float (&a)[4]) {
-    a[0] = __uint_as_float(u.x << 16);
-    a[1] = __uint_as_float(u.x & 0xffff0000u);
-    a[2] = __uint_as_float(u.y << 16);
-    a[3] = __uint_as_float(u.y & 0xffff0000u);
-  };
-  f4v acc[2];
-  acc[0] = acc[1] = (f4v){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int kc = 0; kc < 2; ++kc) {
-    float xm[4];
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-      const float v = H1 ? (float)h1[kc][s4] : (float)x1[kc][s4];
-      xm[s4] = (kc * 16 + 4 * q + s4 < nb) ? v : 0.f;
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float a4[4];
-      widen(a1[t][kc], a4);
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4], xm[s4], acc[t], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int kc = 0; kc < N2; ++kc) {
-    if (kc * 16 >= ni) break;                 // wave-uniform
-    float xm[4];
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) xm[s4] = (kc * 16 + 4 * q + s4 < ni) ? -(float)x2[kc][s4] : 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float a4[4];
-      widen(a2[t][kc], a4);
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4], xm[s4], acc[t], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int il = 16 * t + 4 * q + e;
-      if (il < nb) {
-        const unsigned at = (unsigned)(orow[t][e] * 16 + r);
-        const double v = (double)acc[t][e];
-        if (pa.out2) pa.out2[(size_t)grp * pa.gs2 + at] = v;
-        if (!(o32 && pa.only32)) out[at] = v;
-        if (o32) o32[at] = acc[t][e];
       }
     }
 }
@@ -1338,77 +1220,6 @@ __global__ __launch_bounds__(512) void dense_apply_tiled_kernel(GroupTab gt, int
     if (row < k && c0 + cc < m) ec[(size_t)row * m + c0 + cc] = sum;
   }
 }
-// The same product on the FP32 matrix cores (v_mfma_f32_16x16x4_f32: twice the rate of the FP64 form, no
-// conversion of the FP32-stored inverse): the launch above is bound twice -- 0.53 of HBM on the inverses and 0.41 of
-// the FP64 matrix peak on their FP64 products.  The coarse residual is rounded to FP32 on load, a wave accumulates its
-// K slice (k / 8 terms) in FP32, the eight slices are summed in FP64.  Mirrored on scipy first (tools/schur_lab.py
-// `sa+c32h`: iteration counts identical to the FP64 product at N = 30 / 58, NSE and DRE operators) -- it is the
-// arithmetic of a flexible preconditioner whose inverse is FP32-stored already.  WRITTEN IN THE LAST SESSION OF ROUND 4
-// WITHOUT GPU-MINUTES LEFT: never run on the device, off unless RICADI_COARSE32=1; DESIGN.md section 10a.
-// Operand maps (cdna_hip_programming.md section 3): A[l & 15][k = l >> 4], B[k = l >> 4][l & 15] as in the FP64 form;
-// C/D col = l & 15, row = 4 (l >> 4) + reg (the FP64 form: row = (l >> 4) + 4 reg).
-__global__ __launch_bounds__(512) void dense_apply_tiled_f32mfma_kernel(GroupTab gt, int k, int m, GroupPtrsF Einvs,
-                                                                        const double* __restrict__ rc,
-                                                                        double* __restrict__ ec) {
-  __shared__ float red[8][16][17];
-  const int grp = gt.gid[blockIdx.z];
-  const float* __restrict__ Einv = Einvs.p[grp];
-  rc += (size_t)grp * k * m;
-  ec += (size_t)grp * k * m;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = lane & 15, q = lane >> 4;
-  const int it = blockIdx.x, c0 = blockIdx.y * 16;
-  const int kp = (k + 15) / 16;
-  const int per = (kp + 7) / 8;
-  const int ch0 = w * per, ch1 = min(kp, ch0 + per);
-  const int col = c0 + r;
-  f4v acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};   // one per chunk of a pass: no dependent MFMA pairs
-  const size_t lane_off = (size_t)r * 16 + 4 * q;
-  for (int ch = ch0; ch < ch1; ch += 2) {
-    const bool two = ch + 1 < ch1;               // wave-uniform
-    // all ten loads of a pass are requested before anything waits: the rc loads are unconditional on clamped
-    // addresses (k >= 1, m >= 1) and zeroed by selects afterwards -- behind per-lane branches hipcc put a
-    // vmcnt(0) after every one of them
-    double d0[4], d1[4];
-    const int colc = min(col, m - 1);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int j0 = ch * 16 + 4 * q + t, j1 = j0 + 16;
-      d0[t] = rc[(size_t)min(j0, k - 1) * m + colc];
-      d1[t] = rc[(size_t)min(j1, k - 1) * m + colc];
-    }
-    const float* __restrict__ trow = Einv + ((size_t)it * kp + ch) * 256 + lane_off;
-    const float4 a0 = *reinterpret_cast<const float4*>(trow);
-    float4 a1 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (two) a1 = *reinterpret_cast<const float4*>(trow + 256);
-    float b0[4], b1[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int j0 = ch * 16 + 4 * q + t, j1 = j0 + 16;
-      b0[t] = (j0 < k && col < m) ? (float)d0[t] : 0.f;
-      b1[t] = (two && j1 < k && col < m) ? (float)d1[t] : 0.f;
-    }
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b0[0], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b1[0], acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b0[1], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b1[1], acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b0[2], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b1[2], acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b0[3], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b1[3], acc1, 0, 0, 0);
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[w][4 * q + e][r] = acc0[e] + acc1[e];
-  __syncthreads();
-  if (threadIdx.x < 256) {
-    const int rr = threadIdx.x >> 4, cc = threadIdx.x & 15;
-    double sum = 0.0;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) sum += (double)red[t][rr][cc];
-    const int row = it * 16 + rr;
-    if (row < k && c0 + cc < m) ec[(size_t)row * m + c0 + cc] = sum;
-  }
-}
 template <class T>
 static void dense_apply_tiled_launch(hipStream_t st, const GroupTab& gt, int k, int m,
                                      const GroupPtrsT<T>& Einv, const double* rc, double* ec) {
@@ -1423,14 +1234,8 @@ static void dense_apply_tiled_launch(hipStream_t st, const GroupTab& gt, int k, 
   hipLaunchKernelGGL((dense_apply_tiled_kernel<T, 1>), grid, dim3(512), 0, st, gt, k, m, Einv, rc, ec);
 }
 void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, const GroupPtrsF& Einv,
-                          int ldf, const double* rc, double* ec, bool f32_matrix_cores) {
+                          int ldf, const double* rc, double* ec) {
   (void)ldf;   // tile-major storage (launch_to_f32_tiled)
-  if (f32_matrix_cores) {
-    if (k <= 0 || gt.ng <= 0) return;
-    dim3 grid((k + 15) / 16, (m + 15) / 16, gt.ng);
-    hipLaunchKernelGGL(dense_apply_tiled_f32mfma_kernel, grid, dim3(512), 0, st, gt, k, m, Einv, rc, ec);
-    return;
-  }
   dense_apply_tiled_launch(st, gt, k, m, Einv, rc, ec);
 }
 // dst = FP32 copy of the k x k row-major src in 16 x 16 tile-major layout, zero padded
@@ -1636,8 +1441,8 @@ void launch_to_f32(hipStream_t st, int nrows, int ncols, const double* src, int 
 // Round 4: the launch is a chain of dependent round trips per workgroup, not bytes (cfg2: 1 744 workgroups, all
 // resident at once, 41 us; the 151 KB of z rows a block gathers come out of L2), so the chain is what was cut:
 //   * 512 threads -- a 16-lane row per pressure row of the block, all 32 rows at once (two passes of 16 before);
-//   * per (block, row) ONE 5-word record {row, J row range, (S Y) row range} at a fixed stride (ps_meta, built at
-//     set_operator): block list -> row index -> row pointers were three dependent loads;
+//   * per (block, row) ONE record {row, J row range, (S Y) row range} at a fixed stride (ps_meta, layout PSREC_*,
+//     built by build_records): block list -> row index -> row pointers were three dependent loads;
 //   * the first (index, value) chunks of the J row and of the (S Y) row and r_p are requested together, the next
 //     J chunk while the 16 gathers of the current one are in flight.
 // Indices are loaded unconditionally (clamped to the row's last entry, the value zeroed instead): no exec-masked
@@ -1658,8 +1463,8 @@ __global__ __launch_bounds__(512) void pressure_step_kernel(
   const double* __restrict__ sval = with_sy ? syv.p[grp] : nullptr;
   const double* __restrict__ ecg = with_sy ? ec + (size_t)grp * gse : nullptr;
   const int g = threadIdx.x & 15, il = threadIdx.x >> 4;        // column, row of the block
-  const int* __restrict__ mt = meta + ((size_t)blockIdx.x * 32 + il) * 5;
-  const int prow_ = mt[0], k0 = mt[1], k1 = mt[2], s0 = mt[3], s1 = mt[4];
+  const int* __restrict__ mt = meta + ((size_t)blockIdx.x * 32 + il) * PSREC_WIDTH;
+  const int prow_ = mt[PSREC_ROW], k0 = mt[PSREC_J0], k1 = mt[PSREC_J1], s0 = mt[PSREC_SY0], s1 = mt[PSREC_SY1];
   const bool live = prow_ >= 0;
   const int prow = live ? prow_ : 0;
   // round 1 of loads, all independent: r_p, first J chunk, first (S Y) chunk
@@ -1739,7 +1544,7 @@ __global__ __launch_bounds__(512) void pressure_step_kernel(
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int ol = 16 * t + q + 4 * e;
-    const int row = meta[((size_t)blockIdx.x * 32 + ol) * 5];
+    const int row = meta[((size_t)blockIdx.x * 32 + ol) * PSREC_WIDTH + PSREC_ROW];
     if (row >= 0) {
       double v = acc4[e];
       if (pa.out2) pa.out2[(size_t)grp * pa.gs2 + (size_t)row * 16 + r] = v;
@@ -1799,22 +1604,12 @@ void launch_to_bf16(hipStream_t st, size_t n, const double* src, uint16_t* dst) 
   hipLaunchKernelGGL(to_bf16_kernel, dim3(grid), dim3(256), 0, st, n, src, dst);
 }
 bool launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const GroupPtrsH& m1, const Seg2& s1,
-                          const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa,
-                          bool f32_matrix_cores) {
+                          const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa) {
   if (nblocks <= 0 || gt.ng <= 0) return true;
   if (!(pa.bmeta && !pa.aggof && (s2.kstride == 32 || s2.kstride == 64) &&
         std::max(std::max(gso, s1.gs), s2.gs) * 8 < ((size_t)1 << 32)))
     return false;
   dim3 grid((nblocks + 3) / 4, 1, gt.ng), block(256);
-  if (f32_matrix_cores) {          // experimental (RICADI_SWEEP32=1), see block_two32_f32mfma_kernel
-#define RICADI_TWO32F(K, H)                                                                                       \
-  hipLaunchKernelGGL((block_two32_f32mfma_kernel<K, H>), grid, block, 0, st, gt, nblocks, pa.bmeta, pa.bm_stride, \
-                     pa.bm_in, m1, s1, m2, s2, out, gso, pa)
-    if (s2.kstride == 32) { if (s1.in16) RICADI_TWO32F(32, true); else RICADI_TWO32F(32, false); }
-    else { if (s1.in16) RICADI_TWO32F(64, true); else RICADI_TWO32F(64, false); }
-#undef RICADI_TWO32F
-    return true;
-  }
 #define RICADI_TWO32(K, H)                                                                                         \
   hipLaunchKernelGGL((block_two32_kernel<K, uint16_t, H>), grid, block, 0, st, gt, nblocks, pa.bmeta, pa.bm_stride, \
                      pa.bm_in, m1, s1, m2, s2, out, gso, pa)

@@ -126,7 +126,7 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
   ensure_work(c, m, G);
   Tick tk;
   auto lap = [&](double& acc) {
-    if (c->timing) {
+    if (c->sw.timing) {
       (void)hipStreamSynchronize(st);
       acc += tk.lap();
     }
@@ -378,7 +378,7 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
     stt.steps = steps;
     stt.sweeps = sw + 1;
     lap(c->t_recomb);
-    static const bool dbg = getenv("RICADI_DEBUG_SWEEPS") != nullptr;
+    const bool dbg = c->sw.debug_sweeps;
     if (prm.verbose || dbg) {
       int its = 0;
       for (int k = 0; k < nmine; ++k) its = std::max(its, res[k].iters);

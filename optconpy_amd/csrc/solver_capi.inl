@@ -67,6 +67,34 @@ void ricadi_default_adi_params(ricadi_adi_params* p) {
   p->sweep_width = 1;
 }
 
+// The only reading of the library's switches (ricadi_ctx::sw); RICADI_RECYCLE and RICADI_INJECT_SWEEP_FAILURE are
+// read per call instead (solver_adi.inl)
+static Switches read_switches() {
+  auto set = [](const char* name) { return getenv(name) != nullptr; };
+  auto off = [](const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '0';
+  };
+  Switches s;
+  s.precond64 = set("RICADI_PRECOND64");
+  s.basis64 = set("RICADI_BASIS64");
+  s.basis32 = set("RICADI_BASIS32");
+  s.timing = set("RICADI_TIMING");
+  s.debug_sweeps = set("RICADI_DEBUG_SWEEPS");
+  s.smw = !off("RICADI_SMW");
+  s.wide_split = !(getenv("RICADI_WIDE_SPLIT") && atoi(getenv("RICADI_WIDE_SPLIT")) == 0);
+  if (const char* e = getenv("RICADI_SA")) s.sa_omega = atof(e);
+  s.sweep_meta = !off("RICADI_SWEEP_META");
+  s.ms_spmm = !off("RICADI_MS_SPMM");
+  s.ms_force = getenv("RICADI_MS_SPMM") && getenv("RICADI_MS_SPMM")[0] == '2';
+  s.w32 = !off("RICADI_W32");
+  s.x32_always = !off("RICADI_X32");
+  s.blocks16 = !off("RICADI_BLOCKS16");
+  s.rowwave = !off("RICADI_ROWWAVE");
+  s.mid32 = !off("RICADI_MID32");
+  return s;
+}
+
 int ricadi_create(int device_id, ricadi_ctx** out) {
   REQUIRE(out, RICADI_EINVAL, "ricadi_create: ctx is NULL");
   *out = nullptr;
@@ -79,9 +107,8 @@ int ricadi_create(int device_id, ricadi_ctx** out) {
   std::unique_ptr<ricadi_ctx> c(new ricadi_ctx);
   c->dev = device_id;
   ricadi_default_opts(&c->opts);
-  c->precond32 = getenv("RICADI_PRECOND64") == nullptr;
-  c->timing = getenv("RICADI_TIMING") != nullptr;
-  if (const char* e = getenv("RICADI_SMW")) c->smw = e[0] != '0';
+  c->sw = read_switches();
+  c->precond32 = !c->sw.precond64;
   HIPCHK(hipStreamCreate(&c->st));
   RBCHK(rocblas_create_handle(&c->rb));
   RBCHK(rocblas_set_stream(c->rb, c->st));
@@ -151,33 +178,16 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
     if (E.ci[k] < 0 || E.ci[k] >= nv) throw ricadi::HipError{"E: column index out of range"};
   for (size_t k = 0; k < J.nnz(); ++k)
     if (J.ci[k] < 0 || J.ci[k] >= nv) throw ricadi::HipError{"J: column index out of range"};
-  HostSetup hs;
+  // everything shift independent, on the host
   if (!c->borrowed)
     c->levels = std::max(2, c->opts.max_levels);
-  // smoothed aggregation of the velocity prolongation (two-level setups, folded preconditioner cycle only);
-  // RICADI_SA=0 switches it off, RICADI_SA=<omega> sets the damping
-  double sa_omega = getenv("RICADI_SA") ? atof(getenv("RICADI_SA")) : 0.5;
-  if (c->borrowed || np == 0 || c->opts.bj_block != 32) sa_omega = 0.0;
-  build_setup(A, E, J, c->opts, hs, c->levels, sa_omega);
-  if (hs.sa) {
-    // the folded first sweep takes per-block dense slices of S*P of at most 64 columns
-    int kmax = 0;
-    std::vector<int> tmp;
-    for (int b = 0; b < hs.nbv; ++b) {
-      tmp.clear();
-      for (int q = hs.bv_ptr[b]; q < hs.bv_ptr[b + 1]; ++q)
-        for (int kk = hs.sy_rp[hs.bv_rows[q]]; kk < hs.sy_rp[hs.bv_rows[q] + 1]; ++kk) tmp.push_back(hs.sy_ci[kk]);
-      std::sort(tmp.begin(), tmp.end());
-      kmax = std::max(kmax, (int)(std::unique(tmp.begin(), tmp.end()) - tmp.begin()));
-    }
-    if (kmax > 64 || !block_apply2_ok(hs.bs, 64)) {
-      if (c->opts.verbose)
-        fprintf(stderr, "[ricadi] smoothed aggregation off: a velocity block touches %d coarse columns\n", kmax);
-      hs = HostSetup();
-      build_setup(A, E, J, c->opts, hs, c->levels, 0.0);
-    }
-  }
-  c->sa = hs.sa;
+  // smoothed aggregation of the velocity prolongation: two-level setups, folded preconditioner cycle only
+  const double sa_omega = (c->borrowed || np == 0 || c->opts.bj_block != 32) ? 0.0 : c->sw.sa_omega;
+  HostSetup hs;
+  build_setup_checked(A, E, J, c->opts, hs, c->levels, sa_omega);
+  const HostCsr JT = transpose(J);
+  const PrecondRecords pr = build_records(hs, J, JT, c->sw.sweep_meta, c->sw.ms_spmm);
+  // the child level (same stream and rocBLAS handle) takes the coarse problem
   c->cache.clear();
   c->child.reset();
   if (hs.multilevel) {
@@ -193,8 +203,9 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
     ch->opts.agg_p = 1;
     ch->opts.coarse_max = c->opts.coarse_max + c->opts.coarse_max / 8;   // pairs do not always pair up
     ch->levels = 2;
+    ch->sw = c->sw;
+    ch->sw.timing = false;              // the parent times the child's setup as one phase
     ch->precond32 = c->precond32;
-    ch->smw = c->smw;
     ch->flag.alloc(4);
     ch->info.alloc(4);
     const int rc = ricadi_set_operator(ch.get(), hs.kcv, hs.kcp, hs.l1A.rp.data(), hs.l1A.ci.data(), hs.l1A.v.data(),
@@ -203,6 +214,7 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
     if (rc != RICADI_OK) throw ricadi::HipError{std::string("child level: ") + ricadi_last_error()};
     c->child = std::move(ch);
   }
+  // upload
   c->nv = nv;
   c->np = np;
   c->n = nv + np;
@@ -210,6 +222,7 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   c->nbv = hs.nbv;
   c->nbp = hs.nbp;
   c->kc = hs.kc;
+  c->sa = hs.sa;
   c->snnz = hs.s_ci.size();
   c->s_rp.upload(hs.s_rp, st);
   c->s_ci.upload(hs.s_ci, st);
@@ -219,55 +232,12 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   c->A.upload(A, st);
   c->E.upload(E, st);
   c->J.upload(J, st);
-  HostCsr JT = transpose(J);
   c->JT.upload(JT, st);
-  std::vector<int> sw_gptr, sw_gcols, sw_cptr, sw_ccols;      // host copies for the sweeps' fixed-stride records
-  {
-    // rectangular last sweep: pressure dofs touched by every velocity block, dense J^T slices
-    c->gt_ok = false;
-    if (np > 0 && hs.nbv > 0) {
-      std::vector<int> gptr(hs.nbv + 1, 0), gcols;
-      int kmax = 0;
-      std::vector<int> tmp;
-      for (int b = 0; b < hs.nbv; ++b) {
-        tmp.clear();
-        for (int q = hs.bv_ptr[b]; q < hs.bv_ptr[b + 1]; ++q) {
-          const int row = hs.bv_rows[q];
-          for (int k = JT.rp[row]; k < JT.rp[row + 1]; ++k) tmp.push_back(JT.ci[k]);
-        }
-        std::sort(tmp.begin(), tmp.end());
-        tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-        gcols.insert(gcols.end(), tmp.begin(), tmp.end());
-        gptr[b + 1] = (int)gcols.size();
-        kmax = std::max(kmax, (int)tmp.size());
-      }
-      const int ks = kmax <= 32 ? 32 : (kmax <= 64 ? 64 : (kmax <= 128 ? 128 : 0));
-      if (ks > 0 && block_apply_rect_ok(hs.bs, ks)) {
-        std::vector<double> jtd((size_t)hs.nbv * hs.bs * ks, 0.0);
-        for (int b = 0; b < hs.nbv; ++b) {
-          const int* cb = gcols.data() + gptr[b];
-          const int nc = gptr[b + 1] - gptr[b];
-          for (int q = hs.bv_ptr[b]; q < hs.bv_ptr[b + 1]; ++q) {
-            const int row = hs.bv_rows[q], il = q - hs.bv_ptr[b];
-            for (int k = JT.rp[row]; k < JT.rp[row + 1]; ++k) {
-              const int jl = (int)(std::lower_bound(cb, cb + nc, JT.ci[k]) - cb);
-              jtd[((size_t)b * hs.bs + il) * ks + jl] += JT.v[k];
-            }
-          }
-        }
-        c->gt_ptr.upload(gptr, st);
-        c->gt_cols.upload(gcols, st);
-        sw_gptr = gptr;
-        sw_gcols = gcols;
-        c->gt_jtd.upload(jtd, st);
-        c->gt_ks = ks;
-        c->gt_ok = true;
-        if (c->opts.verbose)
-          fprintf(stderr, "[ricadi] last velocity sweep in rectangular form: <= %d pressure dofs per block (slice width %d)\n",
-                  kmax, ks);
-      }
-    }
-  }
+  c->gt_ok = pr.gt_ok;
+  c->gt_ks = pr.gt_ks;
+  c->gt_ptr.upload(pr.gt_ptr, st);
+  c->gt_cols.upload(pr.gt_cols, st);
+  c->gt_jtd.upload(pr.jtd, st);
   c->bv_ptr.upload(hs.bv_ptr, st);
   c->bv_rows.upload(hs.bv_rows, st);
   c->bp_ptr.upload(hs.bp_ptr, st);
@@ -280,153 +250,34 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   c->agg_ptr.upload(hs.agg_ptr, st);
   c->agg_rows.upload(hs.agg_rows, st);
   c->aggof.upload(hs.aggof, st);
-  if (hs.sa) {
-    c->pt_rp.upload(hs.pt_rp, st);
-    c->pt_ci.upload(hs.pt_ci, st);
-    c->pt_v.upload(hs.pt_v, st);
-  }
+  c->pt_rp.upload(hs.pt_rp, st);
+  c->pt_ci.upload(hs.pt_ci, st);
+  c->pt_v.upload(hs.pt_v, st);
   c->synnz = hs.sy_ci.size();
-  c->sy_chunk = (c->synnz <= (size_t)10 * std::max(c->n, 1)) ? 8 : 16;
-  if (c->opts.verbose)
-    fprintf(stderr, "[ricadi] prolongated operator S*Y: %.1f entries per row\n",
-            (double)c->synnz / std::max(c->n, 1));
+  c->sy_chunk = pr.sy_chunk;
   c->sy_rp.upload(hs.sy_rp, st);
   c->sy_ci.upload(hs.sy_ci, st);
-  {
-    // records of the fused pressure step (pressure_step_kernel): one load per (block, row) instead of the chain
-    // block list -> row index -> row pointers
-    std::vector<int> meta((size_t)std::max(hs.nbp, 0) * 32 * 5, 0);
-    const bool with_sy = hs.kc > 0 && (int)hs.sy_rp.size() == hs.n + 1;
-    for (int b = 0; b < hs.nbp; ++b)
-      for (int il = 0; il < 32; ++il) {
-        int* mt = &meta[((size_t)b * 32 + il) * 5];
-        const int cnt = hs.bp_ptr[b + 1] - hs.bp_ptr[b];
-        if (il >= cnt || cnt > 32) {
-          mt[0] = -1;
-          continue;
-        }
-        const int prow = hs.bp_rows[hs.bp_ptr[b] + il];
-        mt[0] = prow;
-        mt[1] = J.rp[prow];
-        mt[2] = J.rp[prow + 1];
-        mt[3] = with_sy ? hs.sy_rp[hs.nv + prow] : 0;
-        mt[4] = with_sy ? hs.sy_rp[hs.nv + prow + 1] : 0;
-        // (the kernel clamps its index loads to the row's last entry: an empty row must not point behind the arrays)
-        if (mt[2] == mt[1]) mt[1] = mt[2] = 0;
-        if (mt[4] == mt[3]) mt[3] = mt[4] = 0;
-      }
-    c->ps_meta.upload(meta, st);
-  }
+  c->ps_meta.upload(pr.ps_meta, st);
   c->sy_A.upload(hs.sy_A, st);
   c->sy_E.upload(hs.sy_E, st);
   c->sy_J.upload(hs.sy_J, st);
-  {
-    // dense slices of S*Y per velocity block (first sweep with the coarse residual folded in)
-    c->ady_ok = false;
-    if (hs.kc > 0 && np > 0 && hs.nbv > 0 && !hs.sy_rp.empty()) {
-      std::vector<int> cptr(hs.nbv + 1, 0), ccols, tmp;
-      int kmax = 0;
-      for (int b = 0; b < hs.nbv; ++b) {
-        tmp.clear();
-        for (int q = hs.bv_ptr[b]; q < hs.bv_ptr[b + 1]; ++q) {
-          const int row = hs.bv_rows[q];
-          for (int kk = hs.sy_rp[row]; kk < hs.sy_rp[row + 1]; ++kk) tmp.push_back(hs.sy_ci[kk]);
-        }
-        std::sort(tmp.begin(), tmp.end());
-        tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-        ccols.insert(ccols.end(), tmp.begin(), tmp.end());
-        cptr[b + 1] = (int)ccols.size();
-        kmax = std::max(kmax, (int)tmp.size());
-      }
-      const int ks = kmax <= 32 ? 32 : (kmax <= 64 ? 64 : 0);
-      if (ks > 0 && block_apply2_ok(hs.bs, ks)) {
-        const size_t tot = (size_t)hs.nbv * hs.bs * ks;
-        std::vector<double> dA(tot, 0.0), dE(tot, 0.0), dJ(tot, 0.0), dT(hs.sa ? tot : 0, 0.0);
-        for (int b = 0; b < hs.nbv; ++b) {
-          const int* cb = ccols.data() + cptr[b];
-          const int nc = cptr[b + 1] - cptr[b];
-          for (int q = hs.bv_ptr[b]; q < hs.bv_ptr[b + 1]; ++q) {
-            const int row = hs.bv_rows[q], il = q - hs.bv_ptr[b];
-            for (int kk = hs.sy_rp[row]; kk < hs.sy_rp[row + 1]; ++kk) {
-              const int jl = (int)(std::lower_bound(cb, cb + nc, hs.sy_ci[kk]) - cb);
-              const size_t at = ((size_t)b * hs.bs + il) * ks + jl;
-              dA[at] += hs.sy_A[kk];
-              dE[at] += hs.sy_E[kk];
-              dJ[at] += hs.sy_J[kk];
-            }
-            if (hs.sa)       // (P - Y)[row, :]: its columns are among those of (S P)[row, :] (S has a diagonal)
-              for (int kk = hs.pd_rp[row]; kk < hs.pd_rp[row + 1]; ++kk) {
-                const int* f = std::lower_bound(cb, cb + nc, hs.pd_ci[kk]);
-                if (f == cb + nc || *f != hs.pd_ci[kk]) throw ricadi::HipError{"smoothed prolongation: column outside the block's list"};
-                dT[((size_t)b * hs.bs + il) * ks + (int)(f - cb)] += hs.pd_v[kk];
-              }
-          }
-        }
-        if (hs.sa) c->cy_dT.upload(dT, st);
-        c->cy_ptr.upload(cptr, st);
-        c->cy_cols.upload(ccols, st);
-        sw_cptr = cptr;
-        sw_ccols = ccols;
-        c->cy_dA.upload(dA, st);
-        c->cy_dE.upload(dE, st);
-        c->cy_dJ.upload(dJ, st);
-        c->ady_ks = ks;
-        c->ady_ok = true;
-      }
-    }
-  }
-  {
-    // fixed-stride records of the velocity sweeps (block_apply2_kernel, block_apply_rect_kernel; ProlongArgs::bmeta)
-    c->sw_stride = 0;
-    if (hs.bs == 32 && hs.nbv > 0 && (c->gt_ok || c->ady_ok)) {
-      const int kr = c->gt_ok ? c->gt_ks : 0, k2 = c->ady_ok ? c->ady_ks : 0;
-      const int stride = 68 + kr + k2;
-      const std::vector<int>&gptr = sw_gptr, &gcols = sw_gcols, &cptr = sw_cptr, &ccols = sw_ccols;
-      std::vector<int> meta((size_t)hs.nbv * stride, 0);
-      bool ok = true;
-      for (int b = 0; b < hs.nbv && ok; ++b) {
-        int* mt = &meta[(size_t)b * stride];
-        const int b0 = hs.bv_ptr[b], nb = hs.bv_ptr[b + 1] - b0;
-        if (nb > 32 || nb <= 0) { ok = false; break; }
-        mt[0] = nb;
-        for (int i = 0; i < 32; ++i) {
-          const int row = hs.bv_rows[b0 + std::min(i, nb - 1)];
-          mt[4 + i] = row;
-          mt[36 + i] = hs.kc > 0 ? hs.aggof[row] : 0;
-        }
-        if (c->gt_ok) {
-          const int i0 = gptr[b], ni = gptr[b + 1] - i0;
-          mt[1] = ni;
-          for (int i = 0; i < kr; ++i) mt[68 + i] = ni > 0 ? gcols[i0 + std::min(i, ni - 1)] : 0;
-        }
-        if (c->ady_ok) {
-          const int i0 = cptr[b], ni = cptr[b + 1] - i0;
-          mt[2] = ni;
-          for (int i = 0; i < k2; ++i) mt[68 + kr + i] = ni > 0 ? ccols[i0 + std::min(i, ni - 1)] : 0;
-        }
-      }
-      const char* swe = getenv("RICADI_SWEEP_META");        // =0: the generic sweep kernels
-      if (ok && !(swe && swe[0] == '0')) {
-        c->sw_meta.upload(meta, st);
-        c->sw_stride = stride;
-        c->sw_in_rect = 68;
-        c->sw_in_two = 68 + kr;
-      }
-    }
-  }
-  c->syb_ok = hs.kc > 0 && hs.sb_nblk > 0 && hs.syb_max_cols > 0;
+  c->ady_ok = pr.ady_ok;
+  c->ady_ks = pr.ady_ks;
+  c->cy_ptr.upload(pr.cy_ptr, st);
+  c->cy_cols.upload(pr.cy_cols, st);
+  c->cy_dA.upload(pr.dA, st);
+  c->cy_dE.upload(pr.dE, st);
+  c->cy_dJ.upload(pr.dJ, st);
+  c->cy_dT.upload(pr.dT, st);
+  c->sw_meta.upload(pr.sw_meta, st);
+  c->sw_stride = pr.sw_stride;
+  c->sw_in_rect = pr.sw_in_rect;
+  c->sw_in_two = pr.sw_in_two;
+  c->syb_ok = pr.syb_ok;
   c->syb_max_cols = hs.syb_max_cols;
   if (c->syb_ok) {
-    const int nb = hs.sb_nblk, mc = hs.syb_max_cols;
-    std::vector<int> rp2((size_t)nb * 33, 0), cols2((size_t)nb * mc, -1);
-    for (int b = 0; b < nb; ++b) {
-      const int q0 = hs.sb_rowptr[b], nr = hs.sb_rowptr[b + 1] - q0;
-      for (int q = 0; q <= 32; ++q) rp2[(size_t)b * 33 + q] = hs.syb_rp[q0 + std::min(q, nr)];
-      const int c0 = hs.syb_cptr[b], nc = hs.syb_cptr[b + 1] - c0;
-      for (int j = 0; j < nc; ++j) cols2[(size_t)b * mc + j] = hs.syb_cols[c0 + j];
-    }
-    c->syb_rp2.upload(rp2, st);
-    c->syb_cols2.upload(cols2, st);
+    c->syb_rp2.upload(pr.syb_rp2, st);
+    c->syb_cols2.upload(pr.syb_cols2, st);
     c->syb_perm.upload(hs.syb_perm, st);
     c->syb_lidx.upload(hs.syb_lidx, st);
   }
@@ -437,80 +288,35 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   c->sb_nblk = hs.sb_nblk;
   c->sb_max_cols = hs.sb_max_cols;
   c->sb_max_nnz = hs.sb_max_nnz;
-  {
-    const int nb = hs.sb_nblk, mc = std::max(hs.sb_max_cols, 1);
-    std::vector<int> rows2((size_t)nb * 32, -1), rp2((size_t)nb * 33, 0), cols2((size_t)nb * mc, -1),
-        colsm2((size_t)nb * mc, -1);
-    for (int b = 0; b < nb; ++b) {
-      const int q0 = hs.sb_rowptr[b], nr = hs.sb_rowptr[b + 1] - q0;
-      for (int q = 0; q <= 32; ++q) rp2[(size_t)b * 33 + q] = hs.sb_rp[q0 + std::min(q, nr)];
-      for (int q = 0; q < nr; ++q) rows2[(size_t)b * 32 + q] = hs.sb_rows[q0 + q];
-      const int c0 = hs.sb_cptr[b], nc = hs.sb_cptr[b + 1] - c0;
-      for (int j = 0; j < nc; ++j) {
-        cols2[(size_t)b * mc + j] = hs.sb_cols[c0 + j];
-        colsm2[(size_t)b * mc + j] = hs.kc > 0 ? hs.aggof[hs.sb_cols[c0 + j]] : -1;
-      }
-    }
-    c->sb_rows2.upload(rows2, st);
-    c->sb_rp2.upload(rp2, st);
-    c->sb_cols2.upload(cols2, st);
-    c->sb_colsm2.upload(colsm2, st);
-  }
+  c->sb_rows2.upload(pr.sb_rows2, st);
+  c->sb_rp2.upload(pr.sb_rp2, st);
+  c->sb_cols2.upload(pr.sb_cols2, st);
+  c->sb_colsm2.upload(pr.sb_colsm2, st);
   c->sb_perm.upload(hs.sb_perm, st);
   c->sb_lidx.upload(hs.sb_lidx, st);
-  c->sb_ok = hs.sb_nblk > 0 && hs.sb_max_cols < 65536;
-  if (const char* e = getenv("RICADI_MS_SPMM")) {
-    c->ms_spmm = e[0] != '0';
-    c->ms_force = e[0] == '2';
-  }
-  if (const char* e = getenv("RICADI_MID32")) c->mid32 = e[0] != '0';
-  if (const char* e = getenv("RICADI_ROWWAVE")) c->rowwave = e[0] != '0';
-  if (const char* e = getenv("RICADI_COARSE32")) c->coarse_mfma32 = e[0] == '1';
-  if (const char* e = getenv("RICADI_SWEEP32")) c->sweep_mfma32 = e[0] == '1';
-  if (const char* e = getenv("RICADI_BLOCKS16")) c->blocks16 = e[0] != '0';
-  if (const char* e = getenv("RICADI_X32")) c->x32_always = e[0] != '0';
-  if (const char* e = getenv("RICADI_W32")) c->w32 = e[0] != '0';
-  // multi-shift kernel operands: vAJ = A part + J part (disjoint supports) and vE in tile
-  // order; velocity-velocity flag in bit 15 of the local index
-  auto ms_arrays = [&](const std::vector<int>& rp, const std::vector<int>& ci, const std::vector<double>& a,
-                       const std::vector<double>& e, const std::vector<double>& j, const std::vector<int>& perm,
-                       const std::vector<uint16_t>& lidx, int ncol_v, DArr<double>& dAJ, DArr<double>& dE,
-                       DArr<uint16_t>& dl) {
-    const size_t nnz = perm.size();
-    std::vector<int> rowof(ci.size());
-    for (int i = 0; i + 1 < (int)rp.size(); ++i)
-      for (int k = rp[i]; k < rp[i + 1]; ++k) rowof[k] = i;
-    std::vector<double> aj(nnz), ee(nnz);
-    std::vector<uint16_t> lm(nnz);
-    for (size_t kb = 0; kb < nnz; ++kb) {
-      const int k = perm[kb];
-      aj[kb] = a[k] + j[k];
-      ee[kb] = e[k];
-      const bool vv = rowof[k] < nv && ci[k] < ncol_v;
-      lm[kb] = (uint16_t)(lidx[kb] | (vv ? 0x8000 : 0));
-    }
-    dAJ.upload(aj, st);
-    dE.upload(ee, st);
-    dl.upload(lm, st);
-  };
-  if (c->sb_ok && hs.sb_max_cols <= 160)
-    ms_arrays(hs.s_rp, hs.s_ci, hs.s_srcA, hs.s_srcE, hs.s_srcJ, hs.sb_perm, hs.sb_lidx, nv, c->sbAJ, c->sbE,
-              c->sb_lidx_ms);
-  else
-    c->ms_spmm = false;
-  if (c->syb_ok && hs.syb_max_cols <= 160 && c->ms_spmm)
-    ms_arrays(hs.sy_rp, hs.sy_ci, hs.sy_A, hs.sy_E, hs.sy_J, hs.syb_perm, hs.syb_lidx, hs.kcv, c->sybAJ, c->sybE,
-              c->syb_lidx_ms);
+  c->sb_ok = pr.sb_ok;
+  c->ms_ok = pr.ms_ok;
+  c->sbAJ.upload(pr.sbAJ, st);
+  c->sbE.upload(pr.sbE, st);
+  c->sb_lidx_ms.upload(pr.sb_lidx_ms, st);
+  c->sybAJ.upload(pr.sybAJ, st);
+  c->sybE.upload(pr.sybE, st);
+  c->syb_lidx_ms.upload(pr.syb_lidx_ms, st);
   HIPCHK(hipStreamSynchronize(st));
   c->q = 0;
   c->wcols = 0;  // workspaces depend on n
   c->zc = 0;
   c->has_op = true;
-  if (c->opts.verbose)
+  if (c->opts.verbose) {
+    if (pr.gt_ok)
+      fprintf(stderr, "[ricadi] last velocity sweep in rectangular form: <= %d pressure dofs per block (slice width %d)\n",
+              pr.gt_kmax, pr.gt_ks);
+    fprintf(stderr, "[ricadi] prolongated operator S*Y: %.1f entries per row\n", (double)c->synnz / std::max(c->n, 1));
     fprintf(stderr, "[ricadi] operator nv=%d np=%d nnz(S)=%zu | BJ blocks %d+%d (bs=%d) | coarse %d (%d+%d) | "
             "SpMM row blocks %d (max %d distinct cols, %d nnz; mean %.0f cols)\n",
             nv, np, c->snnz, c->nbv, c->nbp, c->bs, c->kc, hs.kcv, hs.kcp, hs.sb_nblk,
             hs.sb_max_cols, hs.sb_max_nnz, hs.sb_nblk ? (double)hs.sb_cols.size() / hs.sb_nblk : 0.0);
+  }
   API_END
 }
 
@@ -954,7 +760,7 @@ int ricadi_time_spmm_batch_dev(ricadi_ctx* c, int ng, const double* alphas, cons
   }
   // ... and into an FP32 panel when the iteration's Arnoldi passes read one (dY is then left alone)
   DArr<float> y32;
-  const bool b16t = getenv("RICADI_BASIS64") == nullptr && getenv("RICADI_BASIS32") == nullptr && c->n <= (1 << 21);
+  const bool b16t = basis16_default(c);
   if (x32.p && iteration_w32(c, m, ng, b16t, update_hess_fused_ok(m, b16t),
                              update_dots_keeps_w(m, b16t, c->opts.gmres_restart), c->opts.gmres_restart))
     y32.alloc(bt.gs * ng);
@@ -1065,7 +871,7 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
             lc = lc->child.get();
           }
           if (c->precond32)
-            launch_dense_apply_b(st, gt, lc->kc, m, lb.einvf, (lc->kc + 3) & ~3, lc->rc.p, lc->ec.p, c->coarse_mfma32);
+            launch_dense_apply_b(st, gt, lc->kc, m, lb.einvf, (lc->kc + 3) & ~3, lc->rc.p, lc->ec.p);
           else
             launch_dense_apply_b(st, gt, lc->kc, m, lb.einv, lc->rc.p, lc->ec.p);
         }
@@ -1182,8 +988,7 @@ int ricadi_setup_info(ricadi_ctx* c, int* out, int nout) {
   if (nout > 8) out[8] = lv;
   if (nout > 9) out[9] = lc->kc;
   // [10]: 1 if the iteration reads the current vector from the FP16 basis (no FP64 copy written), 16-column panels
-  if (nout > 10) out[10] = (c->has_op && (getenv("RICADI_BASIS64") == nullptr) && (getenv("RICADI_BASIS32") == nullptr) &&
-                            c->n <= (1 << 21) && precond_reads_h16_static(c)) ? 1 : 0;
+  if (nout > 10) out[10] = (c->has_op && basis16_default(c) && precond_folds(c)) ? 1 : 0;
   // [11], [12]: padded widths of the dense rectangles of the last / first velocity sweep (0: sweep not in that form);
   // [13]: pressure dofs per Schur block list entry count (np), [14]: nnz(J), [15]: nnz of the pressure rows of S*Y
   if (nout > 11) out[11] = c->gt_ok ? c->gt_ks : 0;
@@ -1288,10 +1093,10 @@ int ricadi_lyap_adi(ricadi_ctx* c, const double* shifts, int ns, const double* W
   DArr<double> dW;
   dW.alloc((size_t)c->nv * m);
   HIPCHK(hipMemcpyAsync(dW.p, W, sizeof(double) * c->nv * m, hipMemcpyHostToDevice, c->st));
-  if (c->timing) c->t_setup = c->t_solve = c->t_recomb = c->t_compress = c->t_proj = c->t_cyc = c->t_iter = c->t_guess = 0;
+  if (c->sw.timing) c->t_setup = c->t_solve = c->t_recomb = c->t_compress = c->t_proj = c->t_cyc = c->t_iter = c->t_guess = 0;
   Tick tka;
   AdiStats s = lyap_adi_dev(c, shifts, ns, dW.p, m, *prm);
-  if (c->timing) {
+  if (c->sw.timing) {
     (void)hipStreamSynchronize(c->st);
     fprintf(stderr, "[ricadi timing] lyap_adi: total %.1f ms = setup %.1f + projection %.1f + solves %.1f (Arnoldi iterations %.1f, "
             "restart-cycle bookkeeping %.1f, recycled guesses %.1f) + recombination %.1f + recompression %.1f (+ rest)\n",

@@ -38,7 +38,6 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
   float* Vf = c->basisf.p;         // ... or the FP32-stored one
   const bool b16 = c->basis16;
   const bool b32 = c->basis32 && !b16;
-  const bool flex = c->flex;
   // (only where the launches are bandwidth bound -- the multi-shift SpMM regime: cfg5 K1 1252 -> 1150 us per
   // launch, cycle +2 %; at cfg2 the FP32 gathers are no faster and the step was 1.4 % slower)
   // the preconditioner reads the current vector from the FP16 basis itself; its FP64 copy is then not written
@@ -101,7 +100,7 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
   std::vector<double> rstart(GM, 0.0);
   Tick tkc;
   auto lapc = [&](double& acc) {
-    if (c->timing) {
+    if (c->sw.timing) {
       (void)hipStreamSynchronize(st);
       acc += tkc.lap();
     }
@@ -177,7 +176,7 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
       // preconditioner application at the cycle end, and P may differ from step to step
       // ... and the operator reads that stored FP32 copy (half the bytes of the x gathers; S Z_j = V H then
       // holds for exactly the vectors the correction uses), so the sweeps need not store the FP64 z at all
-      float* zj = flex ? c->zbasisf.p + (size_t)j * vs : nullptr;
+      float* zj = c->zbasisf.p + (size_t)j * vs;
       precond_apply(c, bt, vj, nm, c->zv.p, zj, nm, x32, h16 ? Vh + (size_t)j * vs : nullptr);
       op_apply(c, bt, c->zv.p, nm, c->wv.p, lowrank, x32 ? zj : nullptr, w32 ? c->wv32.p : nullptr);
       double* h2cur = c->h2.p;
@@ -246,27 +245,14 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
       live.swap(still);
     }
     lapc(c->t_iter);
-    // corrections: x_g += P^-1 (V_g y_g) with the k_g basis vectors group g built
+    // corrections: x_g += Z_g y_g with the k_g preconditioned vectors group g built
     // (one launch each for all groups of the cycle, k_g per group by value)
     bt.set(act);
     {
       GroupInts ks = same_int(0);
       for (int g : act) ks.v[g] = kk[g];
       launch_gmres_backsolve_b(st, bt.tab, m, ks, restart, c->H.p, c->g.p, c->yv.p);
-      if (flex)      // x += Z y in one launch
-        launch_cols_update_bk(st, bt.tab, n, m, ks, c->zbasisf.p, vs, nm, c->yv.p, (size_t)restart * m, x, nm, x, nm);
-      else if (b16)
-        launch_cols_update_bk(st, bt.tab, n, m, ks, Vh, vs, nm, c->yv.p, (size_t)restart * m, c->wv.p, nm);
-      else if (b32)
-        launch_cols_update_bk(st, bt.tab, n, m, ks, Vf, vs, nm, c->yv.p, (size_t)restart * m, c->wv.p, nm);
-      else
-        launch_cols_update_bk(st, bt.tab, n, m, ks, V, vs, nm, c->yv.p, (size_t)restart * m, c->wv.p, nm);
-    }
-    bt.set(act);
-    if (flex) {
-    } else {
-      precond_apply(c, bt, c->wv.p, nm, c->zv.p);
-      launch_axpby_b(st, bt.tab, nm, 1.0, c->zv.p, nm, 1.0, x, nm);
+      launch_cols_update_bk(st, bt.tab, n, m, ks, c->zbasisf.p, vs, nm, c->yv.p, (size_t)restart * m, x, nm, x, nm);
     }
     lapc(c->t_cyc);
   }
@@ -549,7 +535,7 @@ static void gmres_solve_batch(ricadi_ctx* c, ShiftData* const* sds, int G, const
   const bool shared = (gsb == 0 || G == 1) && plain && c->rec_depth > 0;
   Tick tkg;
   const bool guess = shared && recycle_guess(c, sds, G, b, m, x);
-  if (c->timing) {
+  if (c->sw.timing) {
     (void)hipStreamSynchronize(st);
     c->t_guess += tkg.lap();
   }
@@ -671,7 +657,7 @@ static void true_relres(ricadi_ctx* c, ShiftData* const* sds, int G, const doubl
 static void solve_batch(ricadi_ctx* c, ShiftData* const* sds, int G, const double* b, size_t gsb,
                         double* x, int m, bool lowrank, double* relres_host, GmresResult* res) {
   const int q = c->q;
-  if (!lowrank || q <= 0 || !c->smw || m + q > RICADI_MAX_M) {
+  if (!lowrank || q <= 0 || !c->sw.smw || m + q > RICADI_MAX_M) {
     gmres_solve_batch(c, sds, G, b, gsb, x, m, lowrank && q > 0, relres_host, res);
     return;
   }

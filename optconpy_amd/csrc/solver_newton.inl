@@ -33,9 +33,9 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
   ricadi_adi_params p2 = *prm;
   Tick tk0;
   prefetch_setup(c, shifts, std::min(ns, prm->adi_max_steps), prm->project_w != 0);
-  const double t_pre = c->timing ? ((void)hipStreamSynchronize(st), tk0.lap()) : 0.0;
+  const double t_pre = c->sw.timing ? ((void)hipStreamSynchronize(st), tk0.lap()) : 0.0;
   if (prm->project_w) project_panel(c, dWm.p, mw);
-  if (c->timing) {
+  if (c->sw.timing) {
     (void)hipStreamSynchronize(st);
     fprintf(stderr, "[ricadi timing] per-shift setup of %d shifts + projection operator %.1f ms, projection solve %.1f ms\n",
             std::min(ns, prm->adi_max_steps), 1e3 * t_pre, 1e3 * tk0.lap());
@@ -54,10 +54,10 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
   for (steps = 1; steps <= prm->nwtn_max_steps; ++steps) {
     int m = mw;
     Tick tkn;
-    if (c->timing) c->t_setup = c->t_solve = c->t_recomb = c->t_compress = c->t_updnorm = c->t_proj = c->t_gain = c->t_cyc = c->t_iter = c->t_guess = 0;
+    if (c->sw.timing) c->t_setup = c->t_solve = c->t_recomb = c->t_compress = c->t_updnorm = c->t_proj = c->t_gain = c->t_cyc = c->t_iter = c->t_guess = 0;
     if (kk > 0) {
       gain_dev(c, c->E, zk, kk, kk, dB, nb, dK.p);
-      if (c->timing) c->t_gain += tkn.lap();
+      if (c->sw.timing) c->t_gain += tkn.lap();
       m = mfull;
     } else {
       HIPCHK(hipMemsetAsync(dK.p, 0, sizeof(double) * nv * nb, st));
@@ -94,7 +94,7 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
     const int zraw = c->zc;
     Tick tkc;
     factor_recompress(c);
-    if (c->timing) c->t_compress += tkc.lap();
+    if (c->sw.timing) c->t_compress += tkc.lap();
     Znew.alloc((size_t)nv * c->zc);
     const int knew = c->zc;
     launch_copy_cols(st, nv, knew, c->Z.p, c->zld, 0, Znew.p, knew, 0, 1.0);
@@ -107,7 +107,7 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
       upd = dec[0];
       updrel = dec[1];
     }
-    if (c->timing) {
+    if (c->sw.timing) {
       c->t_updnorm += tkc.lap();
       fprintf(stderr, "[ricadi timing] inside the solves: Arnoldi iterations %.1f ms, restart-cycle bookkeeping %.1f, recycled guesses %.1f\n",
               1e3 * c->t_iter, 1e3 * c->t_cyc, 1e3 * c->t_guess);

@@ -43,7 +43,7 @@ static Batch make_batch(ricadi_ctx* c, ShiftData* const* sds, int G, int m) {
   bt.gtm = bt.adym = same_ptr((const double*)nullptr);
   bt.gtmf = bt.adymf = same_ptr((const float*)nullptr);
   bt.bvinvh = bt.bpinvh = bt.gtmh = bt.adymh = same_ptr((const uint16_t*)nullptr);
-  bt.blocks16 = c->blocks16 && G > 0;
+  bt.blocks16 = c->sw.blocks16 && G > 0;
   for (int g = 0; g < RICADI_MAX_GROUPS; ++g) bt.alpha[g] = bt.beta[g] = 0.0;
   for (int g = 0; g < G; ++g) {
     bt.alpha[g] = sds[g]->alpha;
@@ -88,8 +88,8 @@ static Batch make_batch(ricadi_ctx* c, ShiftData* sd, int m) { return make_batch
 // pays where the per-shift value arrays of the active groups no longer fit the caches
 // (measured: n = 5e5, 16 groups: 1.53 -> 1.25 ms per launch; n = 3e4: 83 -> 87 us).
 static bool ms_pays(const ricadi_ctx* c, int ng, size_t nnz) {
-  if (!c->ms_spmm) return false;
-  if (c->ms_force) return true;
+  if (!c->sw.ms_spmm || !c->ms_ok) return false;
+  if (c->sw.ms_force) return true;
   // per-shift value arrays of the active groups near or beyond the 256 MB infinity cache (measured with the FP32
   // operator input that follows this switch: cfg3, 227 MB: 197 -> 205 shift-solves/s; cfg2, 136 MB: 1.4 % slower)
   return ng >= 4 && (double)nnz * 10.0 * ng > 200e6;
@@ -144,13 +144,13 @@ static void saddle_spmm(ricadi_ctx* c, const Batch& bt, const double* x, size_t 
 
 // Does the GMRES iteration apply the operator to the FP32-stored Z_j?
 static bool operator_reads_x32(const ricadi_ctx* c, int m) {
-  return c->flex && saddle_tiled(c, m);
+  return saddle_tiled(c, m);
 }
 // ... for a batch of ng groups: always with the multi-shift kernel; with one workgroup per (row block, group) the FP32
 // input by itself measured 1.4 % slower at cfg2 in round 3, but it is what lets the cycle keep its velocity part in
 // FP32 and its blocks in BF16 (round 4), which more than pays for it (RICADI_X32=0: only with the multi-shift kernel)
 static bool iteration_reads_x32(const ricadi_ctx* c, int m, int ng) {
-  return operator_reads_x32(c, m) && (c->x32_always || ms_pays(c, ng, c->snnz));
+  return operator_reads_x32(c, m) && (c->sw.x32_always || ms_pays(c, ng, c->snnz));
 }
 
 // y = S(alpha,beta) x for every active group (n x m panels, ld = m, group stride gsx /
@@ -176,7 +176,7 @@ static void op_apply(ricadi_ctx* c, const Batch& bt, const double* x, size_t gsx
 // Does the Arnoldi iteration of a batch keep w = S z_j as an FP32 panel?  (the tile kernels with FP32 input write it,
 // the three 16-column passes on the FP16-stored basis read it; RICADI_W32=0: FP64 panel)
 static bool iteration_w32(const ricadi_ctx* c, int m, int ng, bool b16, bool fuseh, bool keepw, int restart) {
-  return c->w32 && m == 16 && b16 && fuseh && keepw && iteration_reads_x32(c, m, ng) && arnoldi16_w32_ok(restart);
+  return c->sw.w32 && m == 16 && b16 && fuseh && keepw && iteration_reads_x32(c, m, ng) && arnoldi16_w32_ok(restart);
 }
 
 // z = P^-1 r for every active group: multiplicative two-level, coarse correction
@@ -189,10 +189,7 @@ static bool iteration_w32(const ricadi_ctx* c, int m, int ng, bool b16, bool fus
 static bool precond_folds(const ricadi_ctx* c) {
   return c->kc > 0 && c->ady_ok && c->np > 0;
 }
-static bool precond_reads_h16_static(const ricadi_ctx* c) {
-  return precond_folds(c);
-}
-// Does the GMRES iteration hand the preconditioner the FP16-stored vector (RICADI_H16=0: the FP64 copy)?
+// Does the GMRES iteration hand the preconditioner the FP16-stored vector (else: the FP64 copy)?
 static bool precond_reads_h16(const ricadi_ctx* c, int m) {
   return c->basis16 && m <= 16 && precond_folds(c);
 }
@@ -210,14 +207,14 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
   // ricadi_time_kernel_dev times one stage at a time through exactly these launchers (c->pc_stage >= 0)
   auto on = [&](int stage) { return c->pc_stage < 0 || c->pc_stage == stage; };
   // the pressure step -- pressure rows of r - (S Y) e, J product, Schur sweep -- as ONE launch (K2p) for
-  // 16-column panels (RICADI_PFUSE=0: the three launches of round 2)
+  // 16-column panels (other widths: three launches)
   const bool fusedp = np > 0 && m == 16 && c->bs == 32;
   // The velocity part between the three sweeps (first sweep -> pressure step's J product -> last sweep) as an FP32
   // panel: where only the FP32 copy of z is wanted anyway (the operator reads Z_j as stored), the first sweep writes
   // the velocity rows of z32 itself, the pressure step gathers 64-B instead of 128-B rows and the last sweep updates
   // them in place.  Rounding the intermediate to FP32 perturbs the (flexible) preconditioner by what its FP32
   // inverses and the FP32-stored Z_j already do.
-  const bool mid32 = c->mid32 && z32 && only32 && fusedp && precond_folds(c) && c->gt_ok && c->precond32;
+  const bool mid32 = c->sw.mid32 && z32 && only32 && fusedp && precond_folds(c) && c->gt_ok && c->precond32;
   c->mid32_last = mid32 ? 1 : 0;
   // ... and on BF16-stored blocks where every shift of the batch has them (record-driven sweeps only)
   const bool b16 = mid32 && bt.blocks16 && c->sw_stride > 0 && c->bs == 32;
@@ -232,7 +229,7 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
     if (c->sa && !folded) throw HipError{"smoothed aggregation needs the folded preconditioner cycle"};
     const size_t rnnz = c->sa ? c->pt_ci.n : (size_t)c->n;
     if (!on(0)) {
-    } else if (m == 16 && c->rowwave && spmm_rowwave_pays(c->kc, rnnz))
+    } else if (m == 16 && c->sw.rowwave && spmm_rowwave_pays(c->kc, rnnz))
       launch_spmm_rowwave(st, gt, c->kc, rrp, rci, rvals, r16 ? nullptr : r, r16, gsr, c->rc.p, bt.gsc, m);
     else if (r16)
       launch_spmm_h(st, gt, c->kc, rrp, rci, rvals, nullptr, r16, m, gsr, c->rc.p, m, bt.gsc,
@@ -247,7 +244,7 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
       cb.tab = gt;
       precond_apply(c->child.get(), cb, c->rc.p, bt.gsc, c->ec.p);
     } else if (c->precond32)
-      launch_dense_apply_b(st, gt, c->kc, m, bt.einvf, (c->kc + 3) & ~3, c->rc.p, c->ec.p, c->coarse_mfma32);
+      launch_dense_apply_b(st, gt, c->kc, m, bt.einvf, (c->kc + 3) & ~3, c->rc.p, c->ec.p);
     else
       launch_dense_apply_b(st, gt, c->kc, m, bt.einv, c->rc.p, c->ec.p);
     if (!on(2) || (fusedp && folded)) {
@@ -331,7 +328,7 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
       fpa.bm_in = c->sw_in_two;
       fpa.bm_ni = 2;
     }
-    if (b16 && launch_block_two32_h(st, gt, c->nbv, bt.bvinvh, s1, bt.adymh, s2, z, bt.gs, fpa, c->sweep_mfma32)) {
+    if (b16 && launch_block_two32_h(st, gt, c->nbv, bt.bvinvh, s1, bt.adymh, s2, z, bt.gs, fpa)) {
     } else if (c->precond32)
       launch_block_apply2_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinvf, s1, bt.adymf, s2, z, m,
                             bt.gs, m, fpa);

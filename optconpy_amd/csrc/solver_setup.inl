@@ -4,9 +4,7 @@
 
 // Width of the column groups a wide panel is solved in (0: the panel stays whole); see gmres_core_any.
 static int wide_split_width(const ricadi_ctx* c, int m) {
-  static const int off = getenv("RICADI_WIDE_SPLIT") && atoi(getenv("RICADI_WIDE_SPLIT")) == 0 ? 1 : 0;
-  (void)c;
-  return (!off && m > 32) ? 16 : 0;
+  return (c->sw.wide_split && m > 32) ? 16 : 0;
 }
 
 // Workspace for batches of up to `groups` panels of width m (group-major: every
@@ -30,8 +28,8 @@ static void ensure_work(ricadi_ctx* c, int m, int groups = 1, int extra = -1) {
   if (want <= c->wcols && restart == c->wrestart) return;
   const size_t gm = (size_t)std::max(want, c->wcols);
   const size_t nm = (size_t)c->n * gm;
-  // Krylov basis: stored in FP16 by default (FP32 with RICADI_BASIS32=1, FP64 with
-  // RICADI_BASIS64=1); ALL arithmetic stays FP64 -- the three passes over the basis per
+  // Krylov basis: stored in FP16 by default (FP32 with RICADI_BASIS32, FP64 with
+  // RICADI_BASIS64); ALL arithmetic stays FP64 -- the three passes over the basis per
   // iteration are the largest share of the HBM traffic.  The current vector is also
   // kept in FP64 (vcur, holding the same rounded values) for the operator /
   // preconditioner application, so the Arnoldi relation holds exactly for the stored
@@ -39,8 +37,8 @@ static void ensure_work(ricadi_ctx* c, int m, int groups = 1, int extra = -1) {
   // cycle can deliver (~1e-3 for FP16, cycles gain ~1e-2), and every cycle starts from
   // the true FP64 residual.  Unit vectors of dimension n have entries ~ n^-1/2: FP16
   // (normal range from 6e-5) is used up to n = 2^21, FP32 beyond.
-  c->basis32 = getenv("RICADI_BASIS64") == nullptr;
-  c->basis16 = c->basis32 && getenv("RICADI_BASIS32") == nullptr && c->n <= (1 << 21);
+  c->basis32 = !c->sw.basis64;
+  c->basis16 = basis16_default(c);
   if (c->basis32) {
     c->basisf.alloc((size_t)(restart + 1) * nm);
     c->vcur.alloc(nm);
@@ -49,9 +47,7 @@ static void ensure_work(ricadi_ctx* c, int m, int groups = 1, int extra = -1) {
     c->basis.alloc((size_t)(restart + 1) * nm);
     c->basisf.release();
   }
-  c->flex = true;      // flexible GMRES: Z_j = P^-1 v_j kept (FP32), x += Z y at the cycle end
-  if (c->flex) c->zbasisf.alloc((size_t)restart * nm);
-  else c->zbasisf.release();
+  c->zbasisf.alloc((size_t)restart * nm);      // flexible GMRES: Z_j = P^-1 v_j kept (FP32), x += Z y at the cycle end
   c->wv.alloc(nm);
   c->wv32.alloc(nm);
   c->zv.alloc(nm);
@@ -200,7 +196,7 @@ static void get_shifts(ricadi_ctx* c, const double* alphas, const double* betas,
   Tick tks;
   double tph[6] = {0, 0, 0, 0, 0, 0};
   auto lapS = [&](int i) {
-    if (c->timing) {
+    if (c->sw.timing) {
       (void)hipStreamSynchronize(st);
       tph[i] += tks.lap();
     }
@@ -323,7 +319,7 @@ static void get_shifts(ricadi_ctx* c, const double* alphas, const double* betas,
         if (sd->einvf.n != kp * kp * 256) sd->einvf.alloc(kp * kp * 256);
         launch_to_f32_tiled(st, k, sd->einv.p, sd->einvf.p);
       }
-      if (c->blocks16 && c->sw_stride > 0 && c->gt_ok && c->ady_ok && k > 0 && c->nbp > 0) {
+      if (c->sw.blocks16 && c->sw_stride > 0 && c->gt_ok && c->ady_ok && k > 0 && c->nbp > 0) {
         // BF16 copies for the record-driven sweeps (all four or none: the cycle switches as a whole)
         if (sd->bvinvh.n != sd->bvinv.n) sd->bvinvh.alloc(sd->bvinv.n);
         if (sd->bpinvh.n != sd->bpinv.n) sd->bpinvh.alloc(sd->bpinv.n);
@@ -338,7 +334,7 @@ static void get_shifts(ricadi_ctx* c, const double* alphas, const double* betas,
     HIPCHK(hipStreamSynchronize(st));
   }
   lapS(4);
-  if (c->timing && !c->borrowed)
+  if (c->sw.timing && !c->borrowed)
     fprintf(stderr, "[ricadi timing] setup of %d shifts: child %.1f ms, per-shift assembly %.1f, block inverses + Schur blocks %.1f, coarse inverses %.1f, FP32 copies %.1f\n",
             (int)todo.size(), 1e3 * tph[0], 1e3 * tph[1], 1e3 * tph[2], 1e3 * tph[3], 1e3 * tph[4]);
   for (ShiftData* sd : todo) sd->valid = true;

@@ -353,39 +353,3 @@ def test_cycle_forms_of_round4_against_sparse_lu(cfg1, monkeypatch):
         iters[name] = np.asarray(its, dtype=float)
     for name, _ in forms[1:]:
         assert np.abs(iters[name] - iters["default"]).max() <= 3, iters
-
-
-@pytest.mark.skipif(os.environ.get("RICADI_EXPERIMENTAL") != "1",
-                    reason="kernel written without GPU-minutes left (round 4): run with RICADI_EXPERIMENTAL=1 first")
-@pytest.mark.parametrize("switch", ["RICADI_COARSE32", "RICADI_SWEEP32"])
-def test_experimental_fp32_matrix_core_forms(cfg1, monkeypatch, switch):
-    """RICADI_COARSE32=1: the coarse apply, RICADI_SWEEP32=1: the first velocity sweep on v_mfma_f32_16x16x4_f32
-    (operands rounded to FP32, FP32 accumulation) instead of the FP64 matrix cores.  Mirrored on scipy
-    (tools/schur_lab.py sa+c32h, sa+b16+m32: iteration counts unchanged); on the device each has to solve to the
-    tolerance, agree with the sparse LU and keep the default's iteration counts within a few before it may become
-    the default."""
-    import torch
-    pr = cfg1[0]
-    calA = (-pr.A - pr.Nc).T.tocsr()
-    MT = pr.M.T.tocsr()
-    R = np.random.default_rng(33).standard_normal((pr.NV, 16))
-    ps = [-1.0, -40.0, -1500.0]
-    refs = [olau.SaddleLU(calA + p * MT, pr.J).solve(R) for p in ps]
-    iters = {}
-    for name, val in (("default", None), (switch, "1")):
-        if val is not None:
-            monkeypatch.setenv(name, val)
-        with _lib.Context(0) as ctx:
-            ctx.set_operator(calA, MT, pr.J)
-            Rd = torch.from_numpy(R).cuda()
-            Xd = torch.empty((len(ps), pr.NV + pr.NP, 16), dtype=torch.float64, device="cuda")
-            its, rr = ctx.shift_solve_batch_dev(ps, [1.0] * len(ps), Rd.data_ptr(), 0, 16, Xd.data_ptr())
-            ctx.synchronize()
-            X = Xd.cpu().numpy()
-        if val is not None:
-            monkeypatch.delenv(name)
-        assert np.asarray(rr).max() <= 1e-10, name
-        for g in range(len(ps)):
-            assert rel(X[g][:pr.NV], refs[g][:pr.NV]) < 1e-8, (name, g)
-        iters[name] = np.asarray(its, dtype=float)
-    assert np.abs(iters[switch] - iters["default"]).max() <= 3, iters

@@ -745,14 +745,10 @@ class Context:
                                             C.byref(ms)))
         return ms.value
 
-
-def _time_gram_dev(self, z_ptr, c, g_ptr, reps):
-    ms = C.c_double(0.0)
-    _chk(self._lib.ricadi_time_gram_dev(self._h, z_ptr, c, g_ptr, reps, C.byref(ms)))
-    return ms.value
-
-
-Context.time_gram_dev = _time_gram_dev
+    def time_gram_dev(self, z_ptr, c, g_ptr, reps):
+        ms = C.c_double(0.0)
+        _chk(self._lib.ricadi_time_gram_dev(self._h, z_ptr, c, g_ptr, reps, C.byref(ms)))
+        return ms.value
 
 
 def _qr(self, Z, want_q=True):

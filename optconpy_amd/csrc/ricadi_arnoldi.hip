@@ -145,7 +145,6 @@ __device__ __forceinline__ double dpp_row_sum(double v) {
 constexpr int WLS = 18;
 // dot products of the chunk held in wl (DOT_ROWS rows of 16 doubles, stride WLS; rows >= nr zeroed) against the
 // basis vectors [0, nvec) and, if want_self, against itself (output row nvec)
-template <bool ATOMIC = false>
 __device__ __forceinline__ void chunk_dots16(const _Float16* __restrict__ basis, size_t vstride, int r0, int nr,
                                              int nvec, int want_self, const double* wl,
                                              double* __restrict__ pout) {
@@ -183,26 +182,19 @@ __device__ __forceinline__ void chunk_dots16(const _Float16* __restrict__ basis,
 #pragma unroll
     for (int t = 0; t < 8; ++t) acc[t] = dpp_row_sum(acc[t]);
     if (s == 0 && i < ntot) {
-      if (ATOMIC) {
-        // straight into the (pre-zeroed) result: no partial rows, no reduce launch
-#pragma unroll
-        for (int t = 0; t < 8; ++t) atomicAdd(pout + (size_t)i * 16 + half * 8 + t, acc[t]);
-      } else {
-        double2* o = reinterpret_cast<double2*>(pout + (size_t)i * 16 + half * 8);
-        o[0] = make_double2(acc[0], acc[1]);
-        o[1] = make_double2(acc[2], acc[3]);
-        o[2] = make_double2(acc[4], acc[5]);
-        o[3] = make_double2(acc[6], acc[7]);
-      }
+      double2* o = reinterpret_cast<double2*>(pout + (size_t)i * 16 + half * 8);
+      o[0] = make_double2(acc[0], acc[1]);
+      o[1] = make_double2(acc[2], acc[3]);
+      o[2] = make_double2(acc[4], acc[5]);
+      o[3] = make_double2(acc[6], acc[7]);
     }
   }
 }
 
-// ATOMIC: `partial` is the result array itself (group stride gsp), zeroed beforehand
 // WT: storage type of the panel w (round 4: the operator's output of the hot path is an FP32 panel -- the basis it is
 // orthogonalised against is FP16-stored, so its rounding of 6e-8 is far inside what the iteration already carries;
 // the arithmetic stays FP64)
-template <bool ATOMIC = false, class WT = double>
+template <class WT = double>
 __global__ __launch_bounds__(256) void cols_dots16_kernel(
     GroupTab gt, int nrows, int nvec, const _Float16* __restrict__ basis, size_t vstride, size_t gsb,
     const WT* __restrict__ w, size_t gsw, int want_self, double* __restrict__ partial, size_t gsp) {
@@ -234,14 +226,14 @@ __global__ __launch_bounds__(256) void cols_dots16_kernel(
   }
   __syncthreads();
   const int nout = (nvec + (want_self ? 1 : 0)) * 16;
-  chunk_dots16<ATOMIC>(basis, vstride, r0, nr, nvec, want_self, wl, ATOMIC ? partial : partial + (size_t)blockIdx.x * nout);
+  chunk_dots16(basis, vstride, r0, nr, nvec, want_self, wl, partial + (size_t)blockIdx.x * nout);
 }
 
 // w' = w - V h (written back), then the dots of w' against V and itself (chunk_dots16; the basis chunk
 // is cache resident by then, so the LDS side decides: with unpadded rows this phase was 2x slower)
 // STORE = false: w' is only staged in LDS for the dots, the panel w keeps the vector BEFORE the first projection (the
 // final update then subtracts the basis with the SUM of both passes' coefficients: one 8-byte store per element less)
-template <bool ATOMIC = false, bool STORE = true, class WT = double>
+template <bool STORE = true, class WT = double>
 __global__ __launch_bounds__(256) void cols_update_dots16_kernel(
     GroupTab gt, int nrows, int nvec, const _Float16* __restrict__ basis, size_t vstride, size_t gsb,
     const double* __restrict__ h, size_t gsh, WT* __restrict__ w, size_t gsw,
@@ -309,8 +301,7 @@ __global__ __launch_bounds__(256) void cols_update_dots16_kernel(
     }
   }
   __syncthreads();
-  chunk_dots16<ATOMIC>(basis, vstride, r0, nr, nvec, 1, wl,
-                       ATOMIC ? partial : partial + (size_t)blockIdx.x * (nvec + 1) * 16);
+  chunk_dots16(basis, vstride, r0, nr, nvec, 1, wl, partial + (size_t)blockIdx.x * (nvec + 1) * 16);
 }
 
 // ---- the same two dot kernels for panels of 8 * NOCT columns (NOCT = 1, 3, 4: the projection solve, the
@@ -576,18 +567,15 @@ __global__ __launch_bounds__(256) void cols_update_f4_kernel(
     op[1] = make_double2(a[2], a[3]);
   }
 }
-// the launch classes that use these kernels (1 dots, 2 update+dots, 4 update; 8: also for panels of 8, 24 and 32 columns)
-static bool arnoldi16(int) { return true; }
-
 template <class BT>
-static void cols_dots_impl(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                           const BT* basis, size_t vstride, size_t gsb, const double* w, size_t gsw,
-                           int want_self, double* partial, size_t gsp, double* out, size_t gso) {
+void launch_cols_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
+                        const BT* basis, size_t vstride, size_t gsb, const double* w, size_t gsw,
+                        int want_self, double* partial, size_t gsp, double* out, size_t gso) {
   const int nblk = dots_num_blocks(nrows);
   const int nout = (nvec + (want_self ? 1 : 0)) * m;
   if (nout == 0 || gt.ng <= 0) return;
   if constexpr (std::is_same<BT, _Float16>::value) {
-    if ((m == 8 || m == 24 || m == 32) && arnoldi16(1) && arnoldi16(8)) {
+    if (m == 8 || m == 24 || m == 32) {
       const dim3 grid(nblk, 1, gt.ng);
       if (m == 8)
         hipLaunchKernelGGL((cols_dots8x_kernel<1>), grid, dim3(256), 0, st, gt, nrows, nvec, basis, vstride, gsb, w, gsw,
@@ -602,8 +590,8 @@ static void cols_dots_impl(hipStream_t st, const GroupTab& gt, int nrows, int m,
                          nblk, nout, partial, gsp, out, gso, 0);
       return;
     }
-    if (m == 16 && arnoldi16(1)) {
-      hipLaunchKernelGGL((cols_dots16_kernel<false, double>), dim3(nblk, 1, gt.ng), dim3(256), 0, st, gt, nrows, nvec, basis,
+    if (m == 16) {
+      hipLaunchKernelGGL(cols_dots16_kernel<double>, dim3(nblk, 1, gt.ng), dim3(256), 0, st, gt, nrows, nvec, basis,
                          vstride, gsb, w, gsw, want_self, partial, gsp);
       hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt,
                          nblk, nout, partial, gsp, out, gso, 0);
@@ -616,29 +604,6 @@ static void cols_dots_impl(hipStream_t st, const GroupTab& gt, int nrows, int m,
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt,
                      nblk, nout, partial, gsp, out, gso, 0);
 }
-void launch_cols_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                        const double* basis, size_t vstride, size_t gsb, const double* w, size_t gsw,
-                        int want_self, double* partial, size_t gsp, double* out, size_t gso) {
-  cols_dots_impl(st, gt, nrows, m, nvec, basis, vstride, gsb, w, gsw, want_self, partial, gsp, out,
-                 gso);
-}
-void launch_cols_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                        const float* basis, size_t vstride, size_t gsb, const double* w, size_t gsw,
-                        int want_self, double* partial, size_t gsp, double* out, size_t gso) {
-  cols_dots_impl(st, gt, nrows, m, nvec, basis, vstride, gsb, w, gsw, want_self, partial, gsp, out,
-                 gso);
-}
-void launch_cols_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                        const _Float16* basis, size_t vstride, size_t gsb, const double* w,
-                        size_t gsw, int want_self, double* partial, size_t gsp, double* out,
-                        size_t gso) {
-  cols_dots_impl(st, gt, nrows, m, nvec, basis, vstride, gsb, w, gsw, want_self, partial, gsp, out,
-                 gso);
-}
-// (The two dot passes with FP64 atomic accumulation instead of partial rows + reduce launches -- two launches fewer per
-// iteration -- were measured in round 3: 468 workgroups per group add to the same 112-192 addresses, contended FP64 atomics
-// serialise at the memory side, cfg2 step 393 -> 741 ms.  The launchers are gone; the kernels keep their ATOMIC template
-// parameter at false.)
 void launch_cols_dots(hipStream_t st, int nrows, int m, int nvec, const double* basis,
                       size_t vstride, const double* w, int want_self, double* partial,
                       double* out) {
@@ -706,23 +671,21 @@ __global__ __launch_bounds__(256) void cols_update_dots_kernel(
     partial[(size_t)blockIdx.x * nout + o] = s0 + s1;
   }
 }
-// set by update_dots_keeps_w(): the 16-column FP16 launch leaves w untouched (see cols_update_dots16_kernel)
-static thread_local bool g_update_dots_nostore = false;
+// Can the 16-column FP16 launch leave w untouched (keep_w; see cols_update_dots16_kernel)?
 bool update_dots_keeps_w(int m, bool fp16_basis, int nvec_max) {
-  return fp16_basis && m == 16 && arnoldi16(2) && arnoldi16(4) &&
+  return fp16_basis && m == 16 &&
          (size_t)(DOT_ROWS * 18 + nvec_max * 16) * sizeof(double) <= 48 * 1024;
 }
-void set_update_dots_nostore(bool v) { g_update_dots_nostore = v; }
 template <class BT>
-static void cols_update_dots_impl(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                                  const BT* basis, size_t vstride, size_t gsb, const double* h,
-                                  size_t gsh, double* w, size_t gsw, double* partial, size_t gsp,
-                                  double* out, size_t gso) {
+void launch_cols_update_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
+                               const BT* basis, size_t vstride, size_t gsb, const double* h,
+                               size_t gsh, double* w, size_t gsw, bool keep_w, double* partial, size_t gsp,
+                               double* out, size_t gso) {
   if (gt.ng <= 0) return;
   const int nblk = dots_num_blocks(nrows);
   const int nout = (nvec + 1) * m;
   if constexpr (std::is_same<BT, _Float16>::value) {
-    if ((m == 8 || m == 24 || m == 32) && arnoldi16(2) && arnoldi16(8) &&
+    if ((m == 8 || m == 24 || m == 32) &&
         (size_t)(DOT_ROWS * (m + 2) + nvec * m) * sizeof(double) <= 48 * 1024) {
       const dim3 grid(nblk, 1, gt.ng);
       const size_t lds = (size_t)(DOT_ROWS * (m + 2) + nvec * m) * sizeof(double);
@@ -739,13 +702,13 @@ static void cols_update_dots_impl(hipStream_t st, const GroupTab& gt, int nrows,
                          nblk, nout, partial, gsp, out, gso, 0);
       return;
     }
-    if (m == 16 && arnoldi16(2) && (size_t)(DOT_ROWS * 18 + nvec * 16) * sizeof(double) <= 48 * 1024) {
-      if (g_update_dots_nostore)
-        hipLaunchKernelGGL((cols_update_dots16_kernel<false, false, double>), dim3(nblk, 1, gt.ng), dim3(256),
+    if (m == 16 && (size_t)(DOT_ROWS * 18 + nvec * 16) * sizeof(double) <= 48 * 1024) {
+      if (keep_w)
+        hipLaunchKernelGGL((cols_update_dots16_kernel<false, double>), dim3(nblk, 1, gt.ng), dim3(256),
                            (size_t)(DOT_ROWS * 18 + nvec * 16) * sizeof(double), st, gt, nrows, nvec, basis, vstride,
                            gsb, h, gsh, w, gsw, partial, gsp);
       else
-        hipLaunchKernelGGL((cols_update_dots16_kernel<false, true, double>), dim3(nblk, 1, gt.ng), dim3(256),
+        hipLaunchKernelGGL((cols_update_dots16_kernel<true, double>), dim3(nblk, 1, gt.ng), dim3(256),
                            (size_t)(DOT_ROWS * 18 + nvec * 16) * sizeof(double), st, gt, nrows, nvec, basis, vstride,
                            gsb, h, gsh, w, gsw, partial, gsp);
       hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt,
@@ -758,27 +721,6 @@ static void cols_update_dots_impl(hipStream_t st, const GroupTab& gt, int nrows,
                      gsh, w, gsw, partial, gsp);
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt,
                      nblk, nout, partial, gsp, out, gso, 0);
-}
-void launch_cols_update_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                               const double* basis, size_t vstride, size_t gsb, const double* h,
-                               size_t gsh, double* w, size_t gsw, double* partial, size_t gsp,
-                               double* out, size_t gso) {
-  cols_update_dots_impl(st, gt, nrows, m, nvec, basis, vstride, gsb, h, gsh, w, gsw, partial, gsp, out,
-                        gso);
-}
-void launch_cols_update_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                               const float* basis, size_t vstride, size_t gsb, const double* h,
-                               size_t gsh, double* w, size_t gsw, double* partial, size_t gsp,
-                               double* out, size_t gso) {
-  cols_update_dots_impl(st, gt, nrows, m, nvec, basis, vstride, gsb, h, gsh, w, gsw, partial, gsp, out,
-                        gso);
-}
-void launch_cols_update_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                               const _Float16* basis, size_t vstride, size_t gsb, const double* h,
-                               size_t gsh, double* w, size_t gsw, double* partial, size_t gsp,
-                               double* out, size_t gso) {
-  cols_update_dots_impl(st, gt, nrows, m, nvec, basis, vstride, gsb, h, gsh, w, gsw, partial, gsp, out,
-                        gso);
 }
 
 // out[r,c] = scale[c] * ( w[r,c] + sign * sum_{i<nvec} h[i*m+c] * V_i[r,c] )
@@ -831,7 +773,7 @@ static void cols_update_impl(hipStream_t st, const GroupTab& gt, int nrows, int 
   if constexpr (std::is_same<BT, _Float16>::value) {
     int nmax = 0;
     for (int i = 0; i < gt.ng; ++i) nmax = std::max(nmax, nvec.v[gt.gid[i]]);
-    if ((m == 16 || ((m & 7) == 0 && m <= 32 && arnoldi16(8))) && arnoldi16(4) &&
+    if ((m == 16 || ((m & 7) == 0 && m <= 32)) &&
         (size_t)nmax * m * sizeof(double) <= 48 * 1024) {
       const size_t nhalf = (size_t)nrows * (m / 8);       // 8-column pieces
       const int grid16 = (int)std::min<size_t>((nhalf + 255) / 256, 8192);
@@ -844,7 +786,7 @@ static void cols_update_impl(hipStream_t st, const GroupTab& gt, int nrows, int 
   if constexpr (std::is_same<BT, float>::value) {
     int nmax = 0;
     for (int i = 0; i < gt.ng; ++i) nmax = std::max(nmax, nvec.v[gt.gid[i]]);
-    if ((m & 3) == 0 && !outf && out && arnoldi16(4) && (size_t)nmax * m * sizeof(double) <= 48 * 1024) {
+    if ((m & 3) == 0 && !outf && out && (size_t)nmax * m * sizeof(double) <= 48 * 1024) {
       const size_t nquad = nelem / 4;
       const int gridq = (int)std::min<size_t>((nquad + 255) / 256, 8192);
       hipLaunchKernelGGL(cols_update_f4_kernel, dim3(gridq, 1, gt.ng), dim3(256),
@@ -857,48 +799,22 @@ static void cols_update_impl(hipStream_t st, const GroupTab& gt, int nrows, int 
   hipLaunchKernelGGL(cols_update_kernel<BT>, dim3(grid, 1, gt.ng), dim3(256), 0, st, gt, nelem, m,
                      nvec, basis, vstride, gsb, h, gsh, sign, w, gsw, scale, out, gso, outf, gsf);
 }
+template <class BT>
 void launch_cols_update_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                          const double* basis, size_t vstride, size_t gsb, const double* h,
+                          const BT* basis, size_t vstride, size_t gsb, const double* h,
                           size_t gsh, double sign, const double* w, size_t gsw, const double* scale,
-                          double* out, size_t gso) {
-  cols_update_impl(st, gt, nrows, m, same_int(nvec), basis, vstride, gsb, h, gsh, sign, w, gsw, scale,
-                   out, gso, (double*)nullptr, 0);
-}
-void launch_cols_update_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                          const float* basis, size_t vstride, size_t gsb, const double* h,
-                          size_t gsh, double sign, const double* w, size_t gsw, const double* scale,
-                          double* out, size_t gso, float* outf, size_t gsf) {
-  cols_update_impl(st, gt, nrows, m, same_int(nvec), basis, vstride, gsb, h, gsh, sign, w, gsw, scale,
-                   out, gso, outf, gsf);
-}
-void launch_cols_update_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                          const _Float16* basis, size_t vstride, size_t gsb, const double* h,
-                          size_t gsh, double sign, const double* w, size_t gsw, const double* scale,
-                          double* out, size_t gso, _Float16* outf, size_t gsf) {
+                          double* out, size_t gso, BT* outf, size_t gsf) {
   cols_update_impl(st, gt, nrows, m, same_int(nvec), basis, vstride, gsb, h, gsh, sign, w, gsw, scale,
                    out, gso, outf, gsf);
 }
 // correction step of a restart cycle: group g combines its first nvec.v[g] vectors
+// acc (optional): out = acc + sum; acc may be `out` itself (every thread reads its elements before it writes them)
+template <class BT>
 void launch_cols_update_bk(hipStream_t st, const GroupTab& gt, int nrows, int m, const GroupInts& nvec,
-                           const double* basis, size_t vstride, size_t gsb, const double* h, size_t gsh,
+                           const BT* basis, size_t vstride, size_t gsb, const double* h, size_t gsh,
                            double* out, size_t gso, const double* acc, size_t gsa) {
-  // acc (optional): out = acc + sum; acc may be `out` itself (every thread reads its elements before it writes them)
   cols_update_impl(st, gt, nrows, m, nvec, basis, vstride, gsb, h, gsh, 1.0, acc, gsa,
-                   (const double*)nullptr, out, gso, (double*)nullptr, 0);
-}
-void launch_cols_update_bk(hipStream_t st, const GroupTab& gt, int nrows, int m, const GroupInts& nvec,
-                           const _Float16* basis, size_t vstride, size_t gsb, const double* h, size_t gsh,
-                           double* out, size_t gso, const double* acc, size_t gsa) {
-  // acc (optional): out = acc + sum; acc may be `out` itself (every thread reads its elements before it writes them)
-  cols_update_impl(st, gt, nrows, m, nvec, basis, vstride, gsb, h, gsh, 1.0, acc, gsa,
-                   (const double*)nullptr, out, gso, (_Float16*)nullptr, 0);
-}
-void launch_cols_update_bk(hipStream_t st, const GroupTab& gt, int nrows, int m, const GroupInts& nvec,
-                           const float* basis, size_t vstride, size_t gsb, const double* h, size_t gsh,
-                           double* out, size_t gso, const double* acc, size_t gsa) {
-  // acc (optional): out = acc + sum; acc may be `out` itself (every thread reads its elements before it writes them)
-  cols_update_impl(st, gt, nrows, m, nvec, basis, vstride, gsb, h, gsh, 1.0, acc, gsa,
-                   (const double*)nullptr, out, gso, (float*)nullptr, 0);
+                   (const double*)nullptr, out, gso, (BT*)nullptr, 0);
 }
 void launch_cols_update(hipStream_t st, int nrows, int m, int nvec, const double* basis,
                         size_t vstride, const double* h, double sign, const double* w,
@@ -906,6 +822,22 @@ void launch_cols_update(hipStream_t st, int nrows, int m, int nvec, const double
   launch_cols_update_b(st, single_group(), nrows, m, nvec, basis, vstride, 0, h, 0, sign, w, 0, scale,
                        out, 0);
 }
+// the Krylov basis stored in FP64, FP32 or FP16 (the arithmetic is FP64 throughout)
+#define RICADI_BASIS_LAUNCHERS(BT)                                                                                    \
+  template void launch_cols_dots_b(hipStream_t, const GroupTab&, int, int, int, const BT*, size_t, size_t, const double*, \
+                                   size_t, int, double*, size_t, double*, size_t);                                    \
+  template void launch_cols_update_dots_b(hipStream_t, const GroupTab&, int, int, int, const BT*, size_t, size_t,      \
+                                          const double*, size_t, double*, size_t, bool, double*, size_t, double*,     \
+                                          size_t);                                                                    \
+  template void launch_cols_update_b(hipStream_t, const GroupTab&, int, int, int, const BT*, size_t, size_t,           \
+                                     const double*, size_t, double, const double*, size_t, const double*, double*,    \
+                                     size_t, BT*, size_t);                                                            \
+  template void launch_cols_update_bk(hipStream_t, const GroupTab&, int, int, const GroupInts&, const BT*, size_t,     \
+                                      size_t, const double*, size_t, double*, size_t, const double*, size_t);
+RICADI_BASIS_LAUNCHERS(double)
+RICADI_BASIS_LAUNCHERS(float)
+RICADI_BASIS_LAUNCHERS(_Float16)
+#undef RICADI_BASIS_LAUNCHERS
 
 // ---------------------------------------------------------------------------
 // GMRES small per-column kernels (one thread per panel column).
@@ -1247,10 +1179,7 @@ __global__ __launch_bounds__(256) void cols_update16_hess_kernel(
     }
   }
 }
-bool update_hess_fused_ok(int m, bool fp16_basis) {
-  static const bool on = true;
-  return on && fp16_basis && m == 16 && arnoldi16(4);
-}
+bool update_hess_fused_ok(int m, bool fp16_basis) { return fp16_basis && m == 16; }
 void launch_cols_update16_hess_b(hipStream_t st, const GroupTab& gt, int nrows, int nvec, const _Float16* basis,
                                  size_t vstride, size_t gsb, const double* h1, const double* h2, size_t gsh, int use_sum,
                                  const double* w, size_t gsw, double* out, size_t gso, _Float16* outf, size_t gsf, int j,
@@ -1275,14 +1204,14 @@ void launch_cols_update16_hess_b(hipStream_t st, const GroupTab& gt, int nrows, 
 // The first two Arnoldi passes on an FP32 panel w (16 columns, FP16-stored basis; the second pass in its
 // "w kept" form: nothing is written back): same partial / reduce structure as the FP64-panel launches.
 bool arnoldi16_w32_ok(int nvec_max) {
-  return arnoldi16(1) && arnoldi16(2) && (size_t)(DOT_ROWS * 18 + nvec_max * 16) * sizeof(double) <= 48 * 1024;
+  return (size_t)(DOT_ROWS * 18 + nvec_max * 16) * sizeof(double) <= 48 * 1024;
 }
 void launch_cols_dots16_w32(hipStream_t st, const GroupTab& gt, int nrows, int nvec, const _Float16* basis,
                             size_t vstride, size_t gsb, const float* w32, size_t gsw, double* partial, size_t gsp,
                             double* out, size_t gso) {
   if (gt.ng <= 0 || nvec <= 0) return;
   const int nblk = dots_num_blocks(nrows), nout = nvec * 16;
-  hipLaunchKernelGGL((cols_dots16_kernel<false, float>), dim3(nblk, 1, gt.ng), dim3(256), 0, st, gt, nrows, nvec, basis,
+  hipLaunchKernelGGL(cols_dots16_kernel<float>, dim3(nblk, 1, gt.ng), dim3(256), 0, st, gt, nrows, nvec, basis,
                      vstride, gsb, w32, gsw, 0, partial, gsp);
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt, nblk, nout, partial,
                      gsp, out, gso, 0);
@@ -1292,7 +1221,7 @@ void launch_cols_update_dots16_w32(hipStream_t st, const GroupTab& gt, int nrows
                                    double* partial, size_t gsp, double* out, size_t gso) {
   if (gt.ng <= 0) return;
   const int nblk = dots_num_blocks(nrows), nout = (nvec + 1) * 16;
-  hipLaunchKernelGGL((cols_update_dots16_kernel<false, false, float>), dim3(nblk, 1, gt.ng), dim3(256),
+  hipLaunchKernelGGL((cols_update_dots16_kernel<false, float>), dim3(nblk, 1, gt.ng), dim3(256),
                      (size_t)(DOT_ROWS * 18 + nvec * 16) * sizeof(double), st, gt, nrows, nvec, basis, vstride, gsb, h,
                      gsh, w32, gsw, partial, gsp);
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt, nblk, nout, partial,

@@ -250,14 +250,9 @@ void launch_gemm_nn_bp(hipStream_t st, const GroupTab& gt, int n, int p, int q, 
   hipLaunchKernelGGL((gemm_nn_kernel<2>), grid, block, 0, st, gt, n, p, q, A, lda, C, ldc, gsC, Y,
                      ldy, gsY, alpha, beta);
 }
-void launch_gemm_nn_b(hipStream_t st, const GroupTab& gt, int n, int p, int q, const double* A,
-                      int lda, const double* C, int ldc, size_t gsC, double* Y, int ldy, size_t gsY,
-                      double alpha, double beta) {
-  launch_gemm_nn_bp(st, gt, n, p, q, same_ptr(A), lda, C, ldc, gsC, Y, ldy, gsY, alpha, beta);
-}
 void launch_gemm_nn(hipStream_t st, int n, int p, int q, const double* A, int lda, const double* C,
                     int ldc, double* Y, int ldy, double alpha, double beta) {
-  launch_gemm_nn_b(st, single_group(), n, p, q, A, lda, C, ldc, 0, Y, ldy, 0, alpha, beta);
+  launch_gemm_nn_bp(st, single_group(), n, p, q, same_ptr(A), lda, C, ldc, 0, Y, ldy, 0, alpha, beta);
 }
 
 // ---------------------------------------------------------------------------

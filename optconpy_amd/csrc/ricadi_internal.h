@@ -298,65 +298,41 @@ void launch_colscale_b(hipStream_t st, const GroupTab& gt, size_t nrows, int m, 
 void launch_colscale_b(hipStream_t st, const GroupTab& gt, size_t nrows, int m, const double* a,
                        const double* x, size_t gsx, double b, double* y, size_t gsy, _Float16* yf,
                        size_t gsf);
+// Arnoldi passes on the Krylov basis stored as BT = double, float or _Float16 (the arithmetic is FP64 throughout)
+template <class BT>
 void launch_cols_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                        const _Float16* basis, size_t vstride, size_t gsb, const double* w,
-                        size_t gsw, int want_self, double* partial, size_t gsp, double* out,
-                        size_t gso);
+                        const BT* basis, size_t vstride, size_t gsb, const double* w, size_t gsw,
+                        int want_self, double* partial, size_t gsp, double* out, size_t gso);
+// keep_w (FP16 basis, 16 columns, update_dots_keeps_w): w is left as it was BEFORE the first projection (no 8-byte
+// store per element); the Hessenberg kernel then writes h1 + h2 to `hsum` and the final update uses those on w
+template <class BT>
 void launch_cols_update_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                               const _Float16* basis, size_t vstride, size_t gsb, const double* h,
-                               size_t gsh, double* w, size_t gsw, double* partial, size_t gsp,
+                               const BT* basis, size_t vstride, size_t gsb, const double* h,
+                               size_t gsh, double* w, size_t gsw, bool keep_w, double* partial, size_t gsp,
                                double* out, size_t gso);
+template <class BT>
 void launch_cols_update_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                          const _Float16* basis, size_t vstride, size_t gsb, const double* h,
+                          const BT* basis, size_t vstride, size_t gsb, const double* h,
                           size_t gsh, double sign, const double* w, size_t gsw, const double* scale,
-                          double* out, size_t gso, _Float16* outf, size_t gsf);
+                          double* out, size_t gso, BT* outf = nullptr, size_t gsf = 0);
+template <class BT>
 void launch_cols_update_bk(hipStream_t st, const GroupTab& gt, int nrows, int m, const GroupInts& nvec,
-                           const _Float16* basis, size_t vstride, size_t gsb, const double* h, size_t gsh,
+                           const BT* basis, size_t vstride, size_t gsb, const double* h, size_t gsh,
                            double* out, size_t gso, const double* acc = nullptr, size_t gsa = 0);
-// FP32-stored Krylov basis (arithmetic stays FP64): overloads reading `const float* basis`
-void launch_cols_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                        const float* basis, size_t vstride, size_t gsb, const double* w, size_t gsw,
-                        int want_self, double* partial, size_t gsp, double* out, size_t gso);
-void launch_cols_update_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                               const float* basis, size_t vstride, size_t gsb, const double* h,
-                               size_t gsh, double* w, size_t gsw, double* partial, size_t gsp,
-                               double* out, size_t gso);
-void launch_cols_update_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                          const float* basis, size_t vstride, size_t gsb, const double* h,
-                          size_t gsh, double sign, const double* w, size_t gsw, const double* scale,
-                          double* out, size_t gso, float* outf, size_t gsf);
-void launch_cols_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                        const double* basis, size_t vstride, size_t gsb, const double* w, size_t gsw,
-                        int want_self, double* partial, size_t gsp, double* out, size_t gso);
-void launch_cols_update_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                               const double* basis, size_t vstride, size_t gsb, const double* h,
-                               size_t gsh, double* w, size_t gsw, double* partial, size_t gsp,
-                               double* out, size_t gso);
-void launch_cols_update_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                          const double* basis, size_t vstride, size_t gsb, const double* h,
-                          size_t gsh, double sign, const double* w, size_t gsw, const double* scale,
-                          double* out, size_t gso);
 void launch_gmres_hess_b(hipStream_t st, const GroupTab& gt, int m, int j, int restart,
                          const double* h1, const double* h2, double* H, double* cs, double* sn,
                          double* g, double* scale, double* resid, const double* bnorm, double tol,
                          double* host_resid = nullptr, double* zero_h1 = nullptr, double* zero_h2 = nullptr,
                          double* hsum = nullptr);
-// 16-column FP16 Arnoldi path: the update+dots launch may leave w as it was BEFORE the first projection (no 8-byte
-// store per element); the Hessenberg kernel then writes h1 + h2 to `hsum` and the final update uses those on w
 bool update_dots_keeps_w(int m, bool fp16_basis, int nvec_max);
-void set_update_dots_nostore(bool v);
 void launch_gmres_backsolve_b(hipStream_t st, const GroupTab& gt, int m, const GroupInts& k,
                               int restart, const double* H, const double* g, double* y);
-void launch_cols_update_bk(hipStream_t st, const GroupTab& gt, int nrows, int m, const GroupInts& nvec,
-                           const double* basis, size_t vstride, size_t gsb, const double* h, size_t gsh,
-                           double* out, size_t gso, const double* acc = nullptr, size_t gsa = 0);
-void launch_cols_update_bk(hipStream_t st, const GroupTab& gt, int nrows, int m, const GroupInts& nvec,
-                           const float* basis, size_t vstride, size_t gsb, const double* h, size_t gsh,
-                           double* out, size_t gso, const double* acc = nullptr, size_t gsa = 0);
 void launch_gmres_start_b(hipStream_t st, const GroupTab& gt, int m, int restart,
                           const double* nrm2, double* g, double* scale, double* resid);
+// The preconditioner sweeps take their operands stored in FP64 (T = double: GroupPtrs) or FP32 (T = float: GroupPtrsF).
+template <class T>
 void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
-                          const int* rows, const GroupPtrs& inv, const double* in, int ldi,
+                          const int* rows, const GroupPtrsT<T>& inv, const double* in, int ldi,
                           size_t gsi, double* out, int ldo, size_t gso, int m, int subtract,
                           const ProlongArgs& pa = ProlongArgs(), const CsrInArgs& ci = CsrInArgs());
 void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, const GroupPtrs& Einv,
@@ -364,28 +340,19 @@ void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, cons
 // FP32-stored inverses (leading dimension ldf = k rounded up to 4; bs x bs blocks)
 void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, const GroupPtrsF& Einv,
                           int ldf, const double* rc, double* ec);
-void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
-                          const int* rows, const GroupPtrsF& inv, const double* in, int ldi,
-                          size_t gsi, double* out, int ldo, size_t gso, int m, int subtract,
-                          const ProlongArgs& pa = ProlongArgs(), const CsrInArgs& ci = CsrInArgs());
 // rectangular block sweep  out[rows_b] (-)= mats[b] (bs x ks) * in[irows_b]  (+ fused prolongation)
 bool block_apply_rect_ok(int bs, int ks);
+template <class T>
 void launch_block_apply_rect_b(hipStream_t st, const GroupTab& gt, int bs, int ks, int nblocks,
                                const int* bptr, const int* rows, const int* iptr, const int* irows,
-                               const GroupPtrs& mats, const double* in, int ldi, size_t gsi, double* out,
-                               int ldo, size_t gso, int m, int subtract, const ProlongArgs& pa);
-void launch_block_apply_rect_b(hipStream_t st, const GroupTab& gt, int bs, int ks, int nblocks,
-                               const int* bptr, const int* rows, const int* iptr, const int* irows,
-                               const GroupPtrsF& mats, const double* in, int ldi, size_t gsi, double* out,
+                               const GroupPtrsT<T>& mats, const double* in, int ldi, size_t gsi, double* out,
                                int ldo, size_t gso, int m, int subtract, const ProlongArgs& pa);
 // out[rows_b] = M1_b in1[rows_b] - M2_b in2[list2_b]  (+ fused prolongation / plain copy via pa);
 // segment 1: the block's own rows, bs x bs matrices; segment 2: list + bs x kstride (32 | 64) matrices
 bool block_apply2_ok(int bs, int k2);
+template <class T>
 void launch_block_apply2_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
-                           const int* rows, const GroupPtrs& m1, const Seg2& s1, const GroupPtrs& m2,
-                           const Seg2& s2, double* out, int ldo, size_t gso, int m, const ProlongArgs& pa);
-void launch_block_apply2_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
-                           const int* rows, const GroupPtrsF& m1, const Seg2& s1, const GroupPtrsF& m2,
+                           const int* rows, const GroupPtrsT<T>& m1, const Seg2& s1, const GroupPtrsT<T>& m2,
                            const Seg2& s2, double* out, int ldo, size_t gso, int m, const ProlongArgs& pa);
 // per shift:  out[b] = Ainv[b] * (alpha dE[b] + beta dA[b] + dJ[b])   (dense slices of S*Y, bs x ks)
 void launch_ady_blocks(hipStream_t st, int nshift, int nblocks, int bs, int ks, const double* dA,
@@ -402,9 +369,6 @@ void launch_gemm_tn_b(hipStream_t st, const GroupTab& gt, int n, int p, int q, c
 void launch_gemm_nn_bp(hipStream_t st, const GroupTab& gt, int n, int p, int q, const GroupPtrs& A,
                        int lda, const double* C, int ldc, size_t gsC, double* Y, int ldy, size_t gsY,
                        double alpha, double beta);
-void launch_gemm_nn_b(hipStream_t st, const GroupTab& gt, int n, int p, int q, const double* A,
-                      int lda, const double* C, int ldc, size_t gsC, double* Y, int ldy, size_t gsY,
-                      double alpha, double beta);
 void launch_spmm(hipStream_t st, int nrows, const int* rp, const int* ci, const double* val,
                  const double* x, int ldx, const int* xmap, double* y, int ldy, const double* r,
                  int ldr, double alpha, double beta_r, const double* rowscale, int m);
@@ -474,13 +438,9 @@ void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, con
 // with_sy = false: no coarse term; z is the n x 16 panel whose
 // velocity rows are read, rp_ / rp16 the pressure rows of the residual (FP64 or FP16-stored), out the pressure rows of z.
 // zv32 (optional, group stride gsz32): the velocity rows as the FP32 panel the first sweep left (64-B row gathers).
+template <class T>
 void launch_pressure_step_b(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
-                            const GroupPtrsF& inv, const int* jci, const double* jv, const double* z,
-                            size_t gsz, bool with_sy, const int* syci, const GroupPtrs& syv, const double* ec, size_t gse,
-                            const double* rp_, const _Float16* rp16, size_t gsr, double* out, size_t gso,
-                            const ProlongArgs& pa, const float* zv32 = nullptr, size_t gsz32 = 0);
-void launch_pressure_step_b(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
-                            const GroupPtrs& inv, const int* jci, const double* jv, const double* z,
+                            const GroupPtrsT<T>& inv, const int* jci, const double* jv, const double* z,
                             size_t gsz, bool with_sy, const int* syci, const GroupPtrs& syv, const double* ec, size_t gse,
                             const double* rp_, const _Float16* rp16, size_t gsr, double* out, size_t gso,
                             const ProlongArgs& pa, const float* zv32 = nullptr, size_t gsz32 = 0);

@@ -176,15 +176,10 @@ __global__ __launch_bounds__(256) void block_apply_kernel(
   }
 }
 template <class T>
-static void block_apply_rect_impl(hipStream_t st, const GroupTab& gt, int bs, int ks, int nblocks,
-                                  const int* bptr, const int* rows, const int* iptr, const int* irows,
-                                  const GroupPtrsT<T>& mats, const double* in, int ldi, size_t gsi, double* out,
-                                  int ldo, size_t gso, int m, int subtract, const ProlongArgs& pa);
-template <class T>
-static void block_apply_impl(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
-                             const int* rows, const GroupPtrsT<T>& inv, const double* in, int ldi,
-                             size_t gsi, double* out, int ldo, size_t gso, int m, int subtract,
-                             const ProlongArgs& pa, const CsrInArgs& ci) {
+void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
+                          const int* rows, const GroupPtrsT<T>& inv, const double* in, int ldi,
+                          size_t gsi, double* out, int ldo, size_t gso, int m, int subtract,
+                          const ProlongArgs& pa, const CsrInArgs& ci) {
   if (nblocks <= 0 || gt.ng <= 0) return;
   // plain panel input, 32 x 32 blocks: the rectangle kernel with the block's own rows as its input list (its loads
   // are issued in groups; this kernel's index -> gather pairs are a chain of dependent round trips).
@@ -194,7 +189,7 @@ static void block_apply_impl(hipStream_t st, const GroupTab& gt, int bs, int nbl
   // 43 vs 33 us).
   static const bool via_rect = true;
   if (via_rect && !ci.rp && bs == 32 && (long)nblocks * gt.ng <= 8192) {
-    block_apply_rect_impl(st, gt, 32, 32, nblocks, bptr, rows, bptr, rows, inv, in, ldi, gsi, out, ldo, gso, m,
+    launch_block_apply_rect_b(st, gt, 32, 32, nblocks, bptr, rows, bptr, rows, inv, in, ldi, gsi, out, ldo, gso, m,
                           subtract, pa);
     return;
   }
@@ -214,20 +209,6 @@ static void block_apply_impl(hipStream_t st, const GroupTab& gt, int bs, int nbl
                          inv, in, ldi, gsi, out, ldo, gso, m, subtract, pa, ci);
       break;
   }
-}
-void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
-                          const int* rows, const GroupPtrs& inv, const double* in, int ldi,
-                          size_t gsi, double* out, int ldo, size_t gso, int m, int subtract,
-                          const ProlongArgs& pa, const CsrInArgs& ci) {
-  block_apply_impl(st, gt, bs, nblocks, bptr, rows, inv, in, ldi, gsi, out, ldo, gso, m, subtract, pa,
-                   ci);
-}
-void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
-                          const int* rows, const GroupPtrsF& inv, const double* in, int ldi,
-                          size_t gsi, double* out, int ldo, size_t gso, int m, int subtract,
-                          const ProlongArgs& pa, const CsrInArgs& ci) {
-  block_apply_impl(st, gt, bs, nblocks, bptr, rows, inv, in, ldi, gsi, out, ldo, gso, m, subtract, pa,
-                   ci);
 }
 
 // ---------------------------------------------------------------------------
@@ -601,10 +582,10 @@ __global__ __launch_bounds__(256) void block_apply_rect_kernel(
   }
 }
 template <class T>
-static void block_apply_rect_impl(hipStream_t st, const GroupTab& gt, int bs, int ks, int nblocks,
-                                  const int* bptr, const int* rows, const int* iptr, const int* irows,
-                                  const GroupPtrsT<T>& mats, const double* in, int ldi, size_t gsi, double* out,
-                                  int ldo, size_t gso, int m, int subtract, const ProlongArgs& pa) {
+void launch_block_apply_rect_b(hipStream_t st, const GroupTab& gt, int bs, int ks, int nblocks,
+                               const int* bptr, const int* rows, const int* iptr, const int* irows,
+                               const GroupPtrsT<T>& mats, const double* in, int ldi, size_t gsi, double* out,
+                               int ldo, size_t gso, int m, int subtract, const ProlongArgs& pa) {
   if (nblocks <= 0 || gt.ng <= 0) return;
   const int nwaves = nblocks + (pa.aggof ? (pa.nextra + 31) / 32 : 0);
   dim3 grid((nwaves + 3) / 4, 1, gt.ng), block(256);
@@ -632,20 +613,6 @@ static void block_apply_rect_impl(hipStream_t st, const GroupTab& gt, int bs, in
 bool block_apply_rect_ok(int bs, int ks) {
   return (bs == 32 && (ks == 32 || ks == 64)) || (bs == 16 && (ks == 32 || ks == 64)) ||
          (bs == 64 && (ks == 64 || ks == 128));
-}
-void launch_block_apply_rect_b(hipStream_t st, const GroupTab& gt, int bs, int ks, int nblocks,
-                               const int* bptr, const int* rows, const int* iptr, const int* irows,
-                               const GroupPtrs& mats, const double* in, int ldi, size_t gsi, double* out,
-                               int ldo, size_t gso, int m, int subtract, const ProlongArgs& pa) {
-  block_apply_rect_impl(st, gt, bs, ks, nblocks, bptr, rows, iptr, irows, mats, in, ldi, gsi, out, ldo, gso, m,
-                        subtract, pa);
-}
-void launch_block_apply_rect_b(hipStream_t st, const GroupTab& gt, int bs, int ks, int nblocks,
-                               const int* bptr, const int* rows, const int* iptr, const int* irows,
-                               const GroupPtrsF& mats, const double* in, int ldi, size_t gsi, double* out,
-                               int ldo, size_t gso, int m, int subtract, const ProlongArgs& pa) {
-  block_apply_rect_impl(st, gt, bs, ks, nblocks, bptr, rows, iptr, irows, mats, in, ldi, gsi, out, ldo, gso, m,
-                        subtract, pa);
 }
 
 // ---------------------------------------------------------------------------
@@ -786,10 +753,9 @@ __global__ __launch_bounds__(256) void block_apply2_kernel(
 }
 bool block_apply2_ok(int bs, int k2) { return (bs == 32 || bs == 16) && (k2 == 32 || k2 == 64); }
 template <class T>
-static void block_apply2_impl(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
-                              const int* rows, const GroupPtrsT<T>& m1, const Seg2& s1,
-                              const GroupPtrsT<T>& m2, const Seg2& s2, double* out, int ldo, size_t gso, int m,
-                              const ProlongArgs& pa) {
+void launch_block_apply2_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
+                           const int* rows, const GroupPtrsT<T>& m1, const Seg2& s1, const GroupPtrsT<T>& m2,
+                           const Seg2& s2, double* out, int ldo, size_t gso, int m, const ProlongArgs& pa) {
   if (nblocks <= 0 || gt.ng <= 0) return;
   const int nwaves = nblocks + (pa.aggof ? (pa.nextra + 31) / 32 : 0);
   dim3 grid((nwaves + 3) / 4, 1, gt.ng), block(256);
@@ -820,16 +786,6 @@ static void block_apply2_impl(hipStream_t st, const GroupTab& gt, int bs, int nb
     else RICADI_BA2(16, 64, false);
   }
 #undef RICADI_BA2
-}
-void launch_block_apply2_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
-                           const int* rows, const GroupPtrs& m1, const Seg2& s1, const GroupPtrs& m2,
-                           const Seg2& s2, double* out, int ldo, size_t gso, int m, const ProlongArgs& pa) {
-  block_apply2_impl(st, gt, bs, nblocks, bptr, rows, m1, s1, m2, s2, out, ldo, gso, m, pa);
-}
-void launch_block_apply2_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
-                           const int* rows, const GroupPtrsF& m1, const Seg2& s1, const GroupPtrsF& m2,
-                           const Seg2& s2, double* out, int ldo, size_t gso, int m, const ProlongArgs& pa) {
-  block_apply2_impl(st, gt, bs, nblocks, bptr, rows, m1, s1, m2, s2, out, ldo, gso, m, pa);
 }
 
 // out[b] = Ainv[b] (bs x bs) * (alpha_s dE[b] + beta_s dA[b] + dJ[b]) (bs x ks)  for every velocity block
@@ -1555,11 +1511,11 @@ __global__ __launch_bounds__(512) void pressure_step_kernel(
   }
 }
 template <class T>
-static void pressure_step_impl(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
-                               const GroupPtrsT<T>& inv, const int* jci, const double* jv, const double* z,
-                               size_t gsz, bool with_sy, const int* syci, const GroupPtrs& syv, const double* ec,
-                               size_t gse, const double* rp_, const _Float16* rp16, size_t gsr, double* out, size_t gso,
-                               const ProlongArgs& pa, const float* zv32, size_t gsz32) {
+void launch_pressure_step_b(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
+                            const GroupPtrsT<T>& inv, const int* jci, const double* jv, const double* z,
+                            size_t gsz, bool with_sy, const int* syci, const GroupPtrs& syv, const double* ec, size_t gse,
+                            const double* rp_, const _Float16* rp16, size_t gsr, double* out, size_t gso,
+                            const ProlongArgs& pa, const float* zv32, size_t gsz32) {
   if (nblocks <= 0 || gt.ng <= 0) return;
   dim3 grid(nblocks, 1, gt.ng), block(512);
 #define RICADI_PS(RT, ZT, rp, zp, gz)                                                                              \
@@ -1570,22 +1526,6 @@ static void pressure_step_impl(hipStream_t st, const GroupTab& gt, int nblocks, 
   else if (zv32) RICADI_PS(double, float, rp_, zv32, gsz32);
   else RICADI_PS(double, double, rp_, z, gsz);
 #undef RICADI_PS
-}
-void launch_pressure_step_b(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
-                            const GroupPtrsF& inv, const int* jci, const double* jv, const double* z,
-                            size_t gsz, bool with_sy, const int* syci, const GroupPtrs& syv, const double* ec, size_t gse,
-                            const double* rp_, const _Float16* rp16, size_t gsr, double* out, size_t gso,
-                            const ProlongArgs& pa, const float* zv32, size_t gsz32) {
-  pressure_step_impl(st, gt, nblocks, meta, inv, jci, jv, z, gsz, with_sy, syci, syv, ec, gse, rp_, rp16, gsr, out, gso,
-                     pa, zv32, gsz32);
-}
-void launch_pressure_step_b(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
-                            const GroupPtrs& inv, const int* jci, const double* jv, const double* z,
-                            size_t gsz, bool with_sy, const int* syci, const GroupPtrs& syv, const double* ec, size_t gse,
-                            const double* rp_, const _Float16* rp16, size_t gsr, double* out, size_t gso,
-                            const ProlongArgs& pa, const float* zv32, size_t gsz32) {
-  pressure_step_impl(st, gt, nblocks, meta, inv, jci, jv, z, gsz, with_sy, syci, syv, ec, gse, rp_, rp16, gsr, out, gso,
-                     pa, zv32, gsz32);
 }
 
 // ---- BF16 copies of the per-shift blocks (round 4): the two velocity sweeps are bandwidth bound on exactly these
@@ -1637,8 +1577,27 @@ void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, con
                             const GroupPtrsH& inv, const int* jci, const double* jv, bool with_sy, const int* syci,
                             const GroupPtrs& syv, const double* ec, size_t gse, const double* rp_, const _Float16* rp16,
                             size_t gsr, double* out, size_t gso, const ProlongArgs& pa, const float* zv32, size_t gsz32) {
-  pressure_step_impl(st, gt, nblocks, meta, inv, jci, jv, (const double*)nullptr, 0, with_sy, syci, syv, ec, gse, rp_,
+  launch_pressure_step_b(st, gt, nblocks, meta, inv, jci, jv, (const double*)nullptr, 0, with_sy, syci, syv, ec, gse, rp_,
                      rp16, gsr, out, gso, pa, zv32, gsz32);
 }
+
+// the preconditioner's operands stored in FP64 (GroupPtrs) or FP32 (GroupPtrsF)
+#define RICADI_PRECOND_LAUNCHERS(T)                                                                                   \
+  template void launch_block_apply_b(hipStream_t, const GroupTab&, int, int, const int*, const int*,                  \
+                                     const GroupPtrsT<T>&, const double*, int, size_t, double*, int, size_t, int, int, \
+                                     const ProlongArgs&, const CsrInArgs&);                                           \
+  template void launch_block_apply_rect_b(hipStream_t, const GroupTab&, int, int, int, const int*, const int*,        \
+                                          const int*, const int*, const GroupPtrsT<T>&, const double*, int, size_t,   \
+                                          double*, int, size_t, int, int, const ProlongArgs&);                        \
+  template void launch_block_apply2_b(hipStream_t, const GroupTab&, int, int, const int*, const int*,                 \
+                                      const GroupPtrsT<T>&, const Seg2&, const GroupPtrsT<T>&, const Seg2&, double*,  \
+                                      int, size_t, int, const ProlongArgs&);                                          \
+  template void launch_pressure_step_b(hipStream_t, const GroupTab&, int, const int*, const GroupPtrsT<T>&,          \
+                                       const int*, const double*, const double*, size_t, bool, const int*,            \
+                                       const GroupPtrs&, const double*, size_t, const double*, const _Float16*,       \
+                                       size_t, double*, size_t, const ProlongArgs&, const float*, size_t);
+RICADI_PRECOND_LAUNCHERS(double)
+RICADI_PRECOND_LAUNCHERS(float)
+#undef RICADI_PRECOND_LAUNCHERS
 
 }  // namespace ricadi

@@ -35,70 +35,10 @@ __device__ __forceinline__ double lowrank_term(const LowRankArgs& lr, const doub
   return s;
 }
 
-template <int CPL>
-__global__ __launch_bounds__(256) void spmm_kernel(
-    GroupTab gt, int nrows, const int* __restrict__ rp, const int* __restrict__ ci,
-    GroupPtrs vals, const double* __restrict__ x, int ldx, size_t gsx,
-    const int* __restrict__ xmap, double* __restrict__ y, int ldy, size_t gsy,
-    const double* __restrict__ r, int ldr, size_t gsr, double alpha, double beta_r,
-    const double* __restrict__ rowscale, int m, LowRankArgs lr) {
-  const int grp = gt.gid[blockIdx.z];
-  const double* __restrict__ val = vals.p[grp];
-  x += (size_t)grp * gsx;
-  y += (size_t)grp * gsy;
-  if (r) r += (size_t)grp * gsr;
-  const double* __restrict__ lrc = lr.c + (size_t)grp * lr.gsc;
-  const int g = threadIdx.x & 15;
-  const int row = blockIdx.x * 16 + (threadIdx.x >> 4);
-  if (row >= nrows) return;
-  double acc[CPL];
-#pragma unroll
-  for (int c = 0; c < CPL; ++c) acc[c] = 0.0;
-  const int k0 = rp[row], k1 = rp[row + 1];
-  int k = k0;
-  for (; k + 1 < k1; k += 2) {
-    int c0 = ci[k], c1 = ci[k + 1];
-    const double v0 = val[k], v1 = val[k + 1];
-    if (xmap) { c0 = xmap[c0]; c1 = xmap[c1]; }
-    const double* x0 = x + (size_t)c0 * ldx;
-    const double* x1 = x + (size_t)c1 * ldx;
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-      const int col = g + 16 * c;
-      if (col < m) {
-        acc[c] = fma(v0, x0[col], acc[c]);
-        acc[c] = fma(v1, x1[col], acc[c]);
-      }
-    }
-  }
-  if (k < k1) {
-    int c0 = ci[k];
-    const double v0 = val[k];
-    if (xmap) c0 = xmap[c0];
-    const double* x0 = x + (size_t)c0 * ldx;
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-      const int col = g + 16 * c;
-      if (col < m) acc[c] = fma(v0, x0[col], acc[c]);
-    }
-  }
-  const double sc = alpha * (rowscale ? rowscale[row] : 1.0);
-#pragma unroll
-  for (int c = 0; c < CPL; ++c) {
-    const int col = g + 16 * c;
-    if (col < m) {
-      double out = sc * acc[c];
-      if (r) out += beta_r * r[(size_t)row * ldr + col];
-      if (row < lr.nrows) out -= lowrank_term(lr, lrc, row, col, m);
-      y[(size_t)row * ldy + col] = out;
-    }
-  }
-}
-
-// Variant 2 (default).  The 16 lanes of a row group load 16 consecutive
+// The 16 lanes of a row group load 16 consecutive
 // (col, val) pairs with ONE coalesced load each and broadcast them with
 // width-16 shuffles, so the 16 x-row gathers of a chunk are independent and all
-// in flight together (the variant above serialises col -> gather per entry).
+// in flight together (one entry at a time would serialise col -> gather).
 // Padding entries use val = 0 / col = 0, i.e. a harmless cached gather,
 // so the inner loop is branch free.  Row blocks are dealt to the 8 XCDs in
 // contiguous ranges (blockIdx % 8 selects the range), which keeps the gathered
@@ -177,8 +117,6 @@ __global__ __launch_bounds__(256) void spmm_kernel_v2(
   }
 }
 
-static int spmm_variant() { return 2; }
-
 static void spmm_dispatch(hipStream_t st, const GroupTab& gt, int nrows, const int* rp,
                           const int* ci, const GroupPtrs& vals, const double* x, int ldx,
                           size_t gsx, const int* xmap, double* y, int ldy, size_t gsy,
@@ -188,8 +126,7 @@ static void spmm_dispatch(hipStream_t st, const GroupTab& gt, int nrows, const i
   if (nrows <= 0 || m <= 0 || gt.ng <= 0) return;
   dim3 grid((nrows + 15) / 16, 1, gt.ng), block(256);
   const int cpl = (m + 15) / 16;
-  const bool v2 = spmm_variant() == 2;
-  if (v2 && chunk == 8 && cpl <= 2) {
+  if (chunk == 8 && cpl <= 2) {
     if (cpl == 1)
       hipLaunchKernelGGL((spmm_kernel_v2<1, 8>), grid, block, 0, st, gt, nrows, rp, ci, vals, x, ldx,
                          gsx, xmap, y, ldy, gsy, r, ldr, gsr, alpha, beta_r, rowscale, m, lr);
@@ -198,16 +135,10 @@ static void spmm_dispatch(hipStream_t st, const GroupTab& gt, int nrows, const i
                          gsx, xmap, y, ldy, gsy, r, ldr, gsr, alpha, beta_r, rowscale, m, lr);
     return;
   }
-#define RICADI_SPMM_CASE(C)                                                              \
-  case C:                                                                                \
-    if (v2)                                                                              \
-      hipLaunchKernelGGL((spmm_kernel_v2<C, 16>), grid, block, 0, st, gt, nrows, rp, ci, vals, \
-                         x, ldx, gsx, xmap, y, ldy, gsy, r, ldr, gsr, alpha, beta_r,     \
-                         rowscale, m, lr);                                               \
-    else                                                                                 \
-      hipLaunchKernelGGL(spmm_kernel<C>, grid, block, 0, st, gt, nrows, rp, ci, vals, x, \
-                         ldx, gsx, xmap, y, ldy, gsy, r, ldr, gsr, alpha, beta_r,        \
-                         rowscale, m, lr);                                               \
+#define RICADI_SPMM_CASE(C)                                                                    \
+  case C:                                                                                      \
+    hipLaunchKernelGGL((spmm_kernel_v2<C, 16>), grid, block, 0, st, gt, nrows, rp, ci, vals, x, ldx, gsx, \
+                       xmap, y, ldy, gsy, r, ldr, gsr, alpha, beta_r, rowscale, m, lr);       \
     break;
   switch (cpl) {
     RICADI_SPMM_CASE(1)

@@ -29,6 +29,27 @@
     }                                \
   } while (0)
 
+// Milliseconds per call of fn() over reps calls on stream st, timed with HIP events (destroyed on every path)
+template <class Fn>
+static double timed_ms(hipStream_t st, int reps, Fn&& fn) {
+  struct Events {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  HIPCHK(hipEventCreate(&ev.e[0]));
+  HIPCHK(hipEventCreate(&ev.e[1]));
+  HIPCHK(hipEventRecord(ev.e[0], st));
+  for (int i = 0; i < reps; ++i) fn();
+  HIPCHK(hipEventRecord(ev.e[1], st));
+  HIPCHK(hipEventSynchronize(ev.e[1]));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  return (double)ms / reps;
+}
+
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
@@ -721,20 +742,10 @@ int ricadi_time_spmm_dev(ricadi_ctx* c, double alpha, double beta, const double*
   REQUIRE(dX && dY && reps > 0 && ms_per_launch, RICADI_EINVAL, "bad argument");
   API_BEGIN
   ShiftData* sd = get_shift(c, alpha, beta);
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
   // plain assembled-CSR saddle SpMM only (no low-rank term): the roofline kernel
-  HIPCHK(hipEventRecord(e0, c->st));
   const Batch bt = make_batch(c, sd, m);
-  for (int i = 0; i < reps; ++i) saddle_spmm(c, bt, dX, bt.gs, nullptr, dY, bt.gs, nullptr, 0, 1.0, 0.0);
-  HIPCHK(hipEventRecord(e1, c->st));
-  HIPCHK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *ms_per_launch = (double)ms / reps;
+  *ms_per_launch =
+      timed_ms(c->st, reps, [&] { saddle_spmm(c, bt, dX, bt.gs, nullptr, dY, bt.gs, nullptr, 0, 1.0, 0.0); });
   API_END
 }
 
@@ -747,35 +758,23 @@ int ricadi_time_spmm_batch_dev(ricadi_ctx* c, int ng, const double* alphas, cons
   std::vector<ShiftData*> sds(ng);
   get_shifts(c, alphas, betas, ng, sds.data());
   const Batch bt = make_batch(c, sds.data(), ng, m);
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
   // the saddle SpMM exactly as the batched GMRES launches it (no low-rank term; on the FP32-stored vector
-  // when the iteration does so)
-  DArr<float> x32;
-  if (iteration_reads_x32(c, m, ng)) {
+  // when the iteration does so, and into an FP32 panel when its Arnoldi passes read one: dY is then left alone).
+  // The basis storage is the one the solver's workspace will have (no workspace may exist yet).
+  Restore<bool> keep16(c->basis16);
+  c->basis16 = basis16_default(c);
+  const IterationForm f = iteration_form(c, m, ng, false);
+  DArr<float> x32, y32;
+  if (f.x32) {
     x32.alloc(bt.gs * ng);
     for (int g = 0; g < ng; ++g)
       launch_to_f32(c->st, c->n, m, dX + (size_t)g * bt.gs, m, x32.p + (size_t)g * bt.gs, m);
   }
-  // ... and into an FP32 panel when the iteration's Arnoldi passes read one (dY is then left alone)
-  DArr<float> y32;
-  const bool b16t = basis16_default(c);
-  if (x32.p && iteration_w32(c, m, ng, b16t, update_hess_fused_ok(m, b16t),
-                             update_dots_keeps_w(m, b16t, c->opts.gmres_restart), c->opts.gmres_restart))
-    y32.alloc(bt.gs * ng);
-  c->w32_last = y32.p ? 1 : 0;
-  saddle_spmm(c, bt, dX, bt.gs, nullptr, dY, bt.gs, nullptr, 0, 1.0, 0.0, LowRankArgs(), x32.p, y32.p);
-  HIPCHK(hipEventRecord(e0, c->st));
-  for (int i = 0; i < reps; ++i)
-    saddle_spmm(c, bt, dX, bt.gs, nullptr, dY, bt.gs, nullptr, 0, 1.0, 0.0, LowRankArgs(), x32.p, y32.p);
-  HIPCHK(hipEventRecord(e1, c->st));
-  HIPCHK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *ms_per_launch = (double)ms / reps;
+  if (f.w32) y32.alloc(bt.gs * ng);
+  c->w32_last = f.w32 ? 1 : 0;
+  auto spmm = [&] { op_apply(c, bt, dX, bt.gs, dY, false, x32.p, y32.p); };
+  spmm();   // warm-up
+  *ms_per_launch = timed_ms(c->st, reps, spmm);
   API_END
 }
 
@@ -796,10 +795,9 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
   get_shifts(c, alphas, betas, ng, sds.data());
   ensure_work(c, m, ng, 0);
   Batch bt = make_batch(c, sds.data(), ng, m);
-  const int n = c->n, restart = c->opts.gmres_restart;
+  const int restart = c->opts.gmres_restart;
   const size_t nm = bt.gs, vs = nm * ng;
   const size_t gsh = (size_t)(restart + 2) * m;
-  const size_t gspart = (size_t)dots_num_blocks(n) * (restart + 2) * m;
   // finite fill: byte 0x3C -> 1.5e-18 (FP64), 1.06 (FP16), 0.0115 (FP32)
   HIPCHK(hipMemsetAsync(c->wv.p, 0x3C, sizeof(double) * vs, st));
   HIPCHK(hipMemsetAsync(c->zv.p, 0x3C, sizeof(double) * vs, st));
@@ -818,45 +816,28 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
     HIPCHK(hipMemsetAsync(c->ec.p, 0x3C, sizeof(double) * bt.gsc * ng, st));
   }
   if (c->np > 0) HIPCHK(hipMemsetAsync(c->tp.p, 0x3C, sizeof(double) * bt.gsp * ng, st));
-  const bool b16 = c->basis16, b32 = c->basis32 && !b16;
-  const size_t basis_bytes = (size_t)(nvec + 1) * vs * (b16 ? 2 : b32 ? 4 : 8);
+  const IterationForm f = iteration_form(c, m, ng, false);
+  const size_t basis_bytes = (size_t)(nvec + 1) * vs * (f.b16 ? 2 : f.b32 ? 4 : 8);
   if (c->basis32) {
     HIPCHK(hipMemsetAsync(c->basisf.p, 0x3C, basis_bytes, st));
     HIPCHK(hipMemsetAsync(c->vcur.p, 0x3C, sizeof(double) * vs, st));
   } else {
     HIPCHK(hipMemsetAsync(c->basis.p, 0x3C, basis_bytes, st));
   }
-  _Float16* Vh = reinterpret_cast<_Float16*>(c->basisf.p);
-  float* Vf = c->basisf.p;
-  double* V = c->basis.p;
-  const GroupTab& gt = bt.tab;
-  const GroupPtrs ones = same_ptr(c->ones.p);
+  const _Float16* Vh = f.h16 ? reinterpret_cast<_Float16*>(c->basisf.p) : nullptr;
   // the operator's output and the Arnoldi passes on the FP32 panel where the iteration uses it
-  const bool tw32 = b16 && c->zbasisf.p &&
-                    iteration_w32(c, m, ng, b16, update_hess_fused_ok(m, b16), update_dots_keeps_w(m, b16, restart), restart);
-  c->w32_last = tw32 ? 1 : 0;
+  c->w32_last = f.w32 ? 1 : 0;
   auto launch = [&]() {
     switch (which) {
       case 0:
-        saddle_spmm(c, bt, c->zv.p, nm, nullptr, c->wv.p, nm, nullptr, 0, 1.0, 0.0, LowRankArgs(),
-                    iteration_reads_x32(c, m, ng) && c->zbasisf.p ? c->zbasisf.p : nullptr, tw32 ? c->wv32.p : nullptr);
+        op_apply(c, bt, c->zv.p, nm, c->wv.p, false, f.x32 ? c->zbasisf.p : nullptr, f.w32 ? c->wv32.p : nullptr);
         break;
       case 1:
-        if (c->precond32)
-          launch_block_apply_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinvf, c->r2.p, m, nm,
-                               c->zv.p, m, nm, m, 0);
-        else
-          launch_block_apply_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinv, c->r2.p, m, nm,
-                               c->zv.p, m, nm, m, 0);
+        block_sweep(c, bt, false, c->r2.p, nm, c->zv.p, 0);
         break;
       case 2:
         if (c->nbp <= 0) throw HipError{"no pressure block"};
-        if (c->precond32)
-          launch_block_apply_b(st, gt, c->bs, c->nbp, c->bp_ptr.p, c->bp_rows.p, bt.bpinvf, c->tp.p, m,
-                               bt.gsp, c->zv.p + (size_t)c->nv * m, m, nm, m, 0);
-        else
-          launch_block_apply_b(st, gt, c->bs, c->nbp, c->bp_ptr.p, c->bp_rows.p, bt.bpinv, c->tp.p, m,
-                               bt.gsp, c->zv.p + (size_t)c->nv * m, m, nm, m, 0);
+        block_sweep(c, bt, true, c->tp.p, bt.gsp, c->zv.p + (size_t)c->nv * m, 0);
         break;
       case 3:
         if (c->kc <= 0) throw HipError{"no coarse level"};
@@ -866,89 +847,46 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
           Batch lb = bt;
           while (lc->child) {
             Batch t = *lb.sub;
-            t.tab = gt;
+            t.tab = bt.tab;
             lb = t;
             lc = lc->child.get();
           }
-          if (c->precond32)
-            launch_dense_apply_b(st, gt, lc->kc, m, lb.einvf, (lc->kc + 3) & ~3, lc->rc.p, lc->ec.p);
-          else
-            launch_dense_apply_b(st, gt, lc->kc, m, lb.einv, lc->rc.p, lc->ec.p);
+          coarse_dense(lc, lb);
         }
         break;
       case 4:
         if (!c->syb_ok) throw HipError{"no tiled S*Y"};
-        if (ms_pays(c, gt.ng, c->snnz) && spmm_blocked_ms_ok(m, c->syb_max_cols, (size_t)c->kc))
-          launch_spmm_blocked_ms(st, gt, bt.alpha, bt.beta, c->sb_nblk, c->sb_rows2.p, c->syb_rp2.p,
-                                 c->syb_cols2.p, c->syb_lidx_ms.p, c->sybAJ.p, c->sybE.p, c->ec.p,
-                                 m, bt.gsc, c->r2.p, m, nm, c->wv.p, m, nm, -1.0, 1.0, m, c->syb_max_cols);
-        else
-        launch_spmm_blocked_b(st, gt, c->sb_nblk, c->sb_rows2.p, c->syb_rp2.p, c->syb_cols2.p,
-                              c->syb_lidx.p, bt.syvalb, c->ec.p, m, bt.gsc, c->r2.p, m, nm, c->wv.p, m, nm,
-                              -1.0, 1.0, m, c->syb_max_cols);
+        sy_residual_tiled(c, bt, c->wv.p, nm);
         break;
       case 5:
-        if (tw32) launch_cols_dots16_w32(st, gt, n, nvec, Vh, vs, nm, c->wv32.p, nm, c->partial.p, gspart, c->h1.p, gsh);
-        else if (b16) launch_cols_dots_b(st, gt, n, m, nvec, Vh, vs, nm, c->wv.p, nm, 0, c->partial.p, gspart, c->h1.p, gsh);
-        else if (b32) launch_cols_dots_b(st, gt, n, m, nvec, Vf, vs, nm, c->wv.p, nm, 0, c->partial.p, gspart, c->h1.p, gsh);
-        else launch_cols_dots_b(st, gt, n, m, nvec, V, vs, nm, c->wv.p, nm, 0, c->partial.p, gspart, c->h1.p, gsh);
+        arnoldi_dots(c, f, bt, nvec);
         break;
       case 6:
-        set_update_dots_nostore(update_dots_keeps_w(m, b16, restart));   // as the iteration launches it
-        if (tw32) launch_cols_update_dots16_w32(st, gt, n, nvec, Vh, vs, nm, c->h1.p, gsh, c->wv32.p, nm, c->partial.p, gspart, c->h2.p, gsh);
-        else if (b16) launch_cols_update_dots_b(st, gt, n, m, nvec, Vh, vs, nm, c->h1.p, gsh, c->wv.p, nm, c->partial.p, gspart, c->h2.p, gsh);
-        else if (b32) launch_cols_update_dots_b(st, gt, n, m, nvec, Vf, vs, nm, c->h1.p, gsh, c->wv.p, nm, c->partial.p, gspart, c->h2.p, gsh);
-        else launch_cols_update_dots_b(st, gt, n, m, nvec, V, vs, nm, c->h1.p, gsh, c->wv.p, nm, c->partial.p, gspart, c->h2.p, gsh);
-        set_update_dots_nostore(false);
+        arnoldi_update_dots(c, f, bt, nvec);
         break;
       case 7:
-        if (b16 && update_hess_fused_ok(m, b16))     // as the iteration launches it: with the Hessenberg update
-          launch_cols_update16_hess_b(st, gt, n, nvec, Vh, vs, nm, c->h1.p, c->h2.p, gsh, update_dots_keeps_w(m, b16, restart) ? 1 : 0,
-                                      c->wv.p, nm, precond_reads_h16(c, m) ? nullptr : c->vcur.p, nm, Vh + (size_t)nvec * vs, nm,
-                                      nvec - 1, restart, c->H.p, c->cs.p, c->sn.p, c->g.p, c->resid.p, c->resid.p + c->wcols,
-                                      c->bnorm2.p, c->opts.gmres_tol, nullptr, tw32 ? c->wv32.p : nullptr);
-        else if (b16) launch_cols_update_b(st, gt, n, m, nvec, Vh, vs, nm, c->h2.p, gsh, -1.0, c->wv.p, nm, c->scale.p, precond_reads_h16(c, m) ? nullptr : c->vcur.p, nm, Vh + (size_t)nvec * vs, nm);
-        else if (b32) launch_cols_update_b(st, gt, n, m, nvec, Vf, vs, nm, c->h2.p, gsh, -1.0, c->wv.p, nm, c->scale.p, c->vcur.p, nm, Vf + (size_t)nvec * vs, nm);
-        else launch_cols_update_b(st, gt, n, m, nvec, V, vs, nm, c->h2.p, gsh, -1.0, c->wv.p, nm, c->scale.p, V + (size_t)nvec * vs, nm);
+        arnoldi_update(c, f, bt, nvec, nullptr);
         break;
       case 8:
-        if (b16 && precond_reads_h16(c, m))
-          precond_apply(c, bt, c->wv.p, nm, c->zv.p, c->zbasisf.p, nm, iteration_reads_x32(c, m, ng), Vh);
-        else
-          precond_apply(c, bt, c->wv.p, nm, c->zv.p, c->zbasisf.p, nm, iteration_reads_x32(c, m, ng));
+        precond_apply(c, bt, c->wv.p, nm, c->zv.p, c->zbasisf.p, nm, f.x32, Vh);
         break;
       case 9:
         if (c->kc <= 0) throw HipError{"no coarse level"};
-        launch_spmm_b(st, gt, c->kc, c->agg_ptr.p, c->agg_rows.p, ones, c->wv.p, m, nm, nullptr, c->rc.p, m,
-                      bt.gsc, nullptr, 0, 0, 1.0, 0.0, m);
+        restrict_csr(c, bt, c->wv.p, nm);
         break;
       case 10: case 11: case 12: case 13: case 14: case 15: case 16: {
         // ONE stage of the preconditioner application, through the launcher precond_apply itself uses
         Restore<int> keep(c->pc_stage);
         c->pc_stage = which - 10;
-        if (b16 && precond_reads_h16(c, m))
-          precond_apply(c, bt, c->wv.p, nm, c->zv.p, c->zbasisf.p, nm, iteration_reads_x32(c, m, ng), Vh);
-        else
-          precond_apply(c, bt, c->wv.p, nm, c->zv.p, c->zbasisf.p, nm, iteration_reads_x32(c, m, ng));
+        precond_apply(c, bt, c->wv.p, nm, c->zv.p, c->zbasisf.p, nm, f.x32, Vh);
         break;
       }
       default:
         throw HipError{"unknown kernel class"};
     }
   };
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
   launch();   // warm-up (code object load, caches)
-  HIPCHK(hipEventRecord(e0, st));
-  for (int i = 0; i < reps; ++i) launch();
-  HIPCHK(hipEventRecord(e1, st));
-  HIPCHK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *ms_per_launch = (double)ms / reps;
+  *ms_per_launch = timed_ms(st, reps, launch);
   API_END
 }
 
@@ -1043,18 +981,7 @@ int ricadi_time_qr_dev(ricadi_ctx* c, const double* dZ, int cz, int reps, double
   DArr<double> Q, R;
   Q.alloc((size_t)c->nv * cz);
   R.alloc((size_t)cz * cz);
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
-  HIPCHK(hipEventRecord(e0, c->st));
-  for (int i = 0; i < reps; ++i) block_qr_dev(c, dZ, cz, c->nv, cz, Q.p, R.p);
-  HIPCHK(hipEventRecord(e1, c->st));
-  HIPCHK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *ms_per_call = (double)ms / reps;
+  *ms_per_call = timed_ms(c->st, reps, [&] { block_qr_dev(c, dZ, cz, c->nv, cz, Q.p, R.p); });
   API_END
 }
 
@@ -1064,19 +991,8 @@ int ricadi_time_gram_dev(ricadi_ctx* c, const double* dZ, int cz, double* dG, in
           "bad argument");
   API_BEGIN
   (void)hipSetDevice(c->dev);
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
   HIPCHK(hipMemsetAsync(dG, 0, sizeof(double) * cz * cz, c->st));
-  HIPCHK(hipEventRecord(e0, c->st));
-  for (int i = 0; i < reps; ++i) launch_gemm_tn(c->st, c->nv, cz, cz, dZ, cz, dZ, cz, dG, cz);
-  HIPCHK(hipEventRecord(e1, c->st));
-  HIPCHK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *ms_per_launch = (double)ms / reps;
+  *ms_per_launch = timed_ms(c->st, reps, [&] { launch_gemm_tn(c->st, c->nv, cz, cz, dZ, cz, dZ, cz, dG, cz); });
   API_END
 }
 

@@ -18,6 +18,104 @@ struct GmresResult {
   double max_relres = 0.0;
 };
 
+// What one lockstep GMRES iteration launches: the single place that decides it (gmres_core and the kernel
+// timers of solver_capi.inl both ask here).
+struct IterationForm {
+  bool b16 = false, b32 = false;   // Krylov basis stored in FP16 / FP32 (neither: FP64)
+  bool h16 = false;     // the preconditioner reads the current vector from the FP16 basis; its FP64 copy is not written
+  bool keepw = false;   // w is not rewritten between the two Gram-Schmidt passes: the final update subtracts
+                        // V (h1 + h2) from the original w
+  bool fuseh = false;   // last Arnoldi pass and Hessenberg update in ONE launch (K3h)
+  bool x32 = false;     // the operator reads the FP32-stored Z_j
+  bool w32 = false;     // ... and writes w = S z_j as an FP32 panel, which the three Arnoldi passes read
+};
+static IterationForm iteration_form(const ricadi_ctx* c, int m, int G, bool lowrank) {
+  const int restart = c->opts.gmres_restart;
+  IterationForm f;
+  f.b16 = c->basis16;
+  f.b32 = c->basis32 && !f.b16;
+  f.h16 = precond_reads_h16(c, m);
+  f.keepw = update_dots_keeps_w(m, f.b16, restart);
+  f.fuseh = update_hess_fused_ok(m, f.b16);
+  // FP32 operator input for a batch of G groups: always with the multi-shift kernel; with one workgroup per (row
+  // block, group) the FP32 input by itself measured 1.4 % slower at cfg2 in round 3, but it is what lets the cycle
+  // keep its velocity part in FP32 and its blocks in BF16 (round 4), which more than pays for it (RICADI_X32=0: only
+  // with the multi-shift kernel; there the launches are bandwidth bound: cfg5 K1 1252 -> 1150 us per launch, cycle
+  // +2 %).  Not with the low-rank term.
+  f.x32 = saddle_tiled(c, m) && (c->sw.x32_always || ms_pays(c, G, c->snnz)) && !(lowrank && c->q > 0);
+  // the tile kernels with FP32 input write the FP32 panel, the three 16-column passes on the FP16-stored basis read
+  // it (RICADI_W32=0: FP64 panel)
+  f.w32 = f.x32 && c->sw.w32 && m == 16 && f.b16 && f.fuseh && f.keepw && arnoldi16_w32_ok(restart);
+  return f;
+}
+// fn(basis) with the Krylov basis as stored: _Float16*, float* or double*
+template <class Fn>
+static void with_basis(ricadi_ctx* c, const IterationForm& f, Fn&& fn) {
+  if (f.b16) fn(reinterpret_cast<_Float16*>(c->basisf.p));
+  else if (f.b32) fn(c->basisf.p);
+  else fn(c->basis.p);
+}
+
+// The Arnoldi passes of iteration nvec - 1 on the workspace panels (w = S z_j in wv / wv32, coefficients in h1 / h2),
+// for the groups of bt.tab.  Strides as in gmres_core.
+struct ArnoldiStrides {
+  size_t nm, vs, gsh, gspart, h2buf;
+  ArnoldiStrides(const ricadi_ctx* c, const Batch& bt)
+      : nm(bt.gs), vs(bt.gs * bt.G), gsh((size_t)(c->opts.gmres_restart + 2) * bt.m),
+        gspart((size_t)dots_num_blocks(c->n) * (c->opts.gmres_restart + 2) * bt.m),
+        h2buf((size_t)(c->opts.gmres_restart + 2) * c->wcols) {}
+};
+// first pass: h1 = V^T w
+static void arnoldi_dots(ricadi_ctx* c, const IterationForm& f, const Batch& bt, int nvec) {
+  const ArnoldiStrides s(c, bt);
+  if (f.w32)
+    launch_cols_dots16_w32(c->st, bt.tab, c->n, nvec, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
+                           c->wv32.p, s.nm, c->partial.p, s.gspart, c->h1.p, s.gsh);
+  else
+    with_basis(c, f, [&](auto* V) {
+      launch_cols_dots_b(c->st, bt.tab, c->n, bt.m, nvec, V, s.vs, s.nm, c->wv.p, s.nm, 0, c->partial.p, s.gspart,
+                         c->h1.p, s.gsh);
+    });
+}
+// first update fused with the dot products of the second pass: w -= V h1, h2 = V^T w (and ||w||^2)
+static void arnoldi_update_dots(ricadi_ctx* c, const IterationForm& f, const Batch& bt, int nvec) {
+  const ArnoldiStrides s(c, bt);
+  if (f.w32)
+    launch_cols_update_dots16_w32(c->st, bt.tab, c->n, nvec, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
+                                  c->h1.p, s.gsh, c->wv32.p, s.nm, c->partial.p, s.gspart, c->h2.p, s.gsh);
+  else
+    with_basis(c, f, [&](auto* V) {
+      launch_cols_update_dots_b(c->st, bt.tab, c->n, bt.m, nvec, V, s.vs, s.nm, c->h1.p, s.gsh, c->wv.p, s.nm, f.keepw,
+                                c->partial.p, s.gspart, c->h2.p, s.gsh);
+    });
+}
+// last update: v_{j+1} = scale (w - V h2), stored in the basis (fuseh: with the Hessenberg / Givens update of
+// iteration j = nvec - 1 in the same launch; the residual estimates also go to host_resid)
+static void arnoldi_update(ricadi_ctx* c, const IterationForm& f, const Batch& bt, int nvec, double* host_resid) {
+  const ArnoldiStrides s(c, bt);
+  const int j = nvec - 1, m = bt.m;
+  const size_t resbuf = (size_t)c->wcols;                    // doubles between the two residual-estimate buffers
+  double* vcur = f.h16 ? nullptr : c->vcur.p;
+  if (f.fuseh) {
+    _Float16* Vh = reinterpret_cast<_Float16*>(c->basisf.p);
+    launch_cols_update16_hess_b(c->st, bt.tab, c->n, nvec, Vh, s.vs, s.nm, c->h1.p, c->h2.p, s.gsh, f.keepw ? 1 : 0,
+                                c->wv.p, s.nm, vcur, s.nm, Vh + (size_t)nvec * s.vs, s.nm, j, c->opts.gmres_restart,
+                                c->H.p, c->cs.p, c->sn.p, c->g.p, c->resid.p + (size_t)(j & 1) * resbuf,
+                                c->resid.p + (size_t)((j + 1) & 1) * resbuf, c->bnorm2.p, c->opts.gmres_tol,
+                                host_resid, f.w32 ? c->wv32.p : nullptr);
+    return;
+  }
+  const double* h = f.keepw ? c->h2.p + s.h2buf : c->h2.p;
+  with_basis(c, f, [&](auto* V) {
+    if constexpr (std::is_same<std::remove_pointer_t<decltype(V)>, double>::value)
+      launch_cols_update_b(c->st, bt.tab, c->n, m, nvec, V, s.vs, s.nm, h, s.gsh, -1.0, c->wv.p, s.nm, c->scale.p,
+                           V + (size_t)nvec * s.vs, s.nm);
+    else
+      launch_cols_update_b(c->st, bt.tab, c->n, m, nvec, V, s.vs, s.nm, h, s.gsh, -1.0, c->wv.p, s.nm, c->scale.p,
+                           vcur, s.nm, V + (size_t)nvec * s.vs, s.nm);
+  });
+}
+
 // have_x0: x holds an initial guess (else it is zeroed);  only: the groups to iterate on (NULL = all; the
 // panels of the other groups are not touched);  allow_stall: a group whose full-length restart cycles no
 // longer gain is given up early (the caller repeats it with wider storage).
@@ -31,31 +129,11 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
   Batch bt = make_batch(c, sds, G, m);
   const size_t nm = bt.gs;             // one panel
   const size_t vs = nm * G;            // one Krylov vector of all groups
-  const size_t gsh = (size_t)(restart + 2) * m;
   const size_t gspart = (size_t)dots_num_blocks(n) * (restart + 2) * m;
   const int GM = G * m;
-  double* V = c->basis.p;          // FP64 basis (RICADI_BASIS64) ...
-  float* Vf = c->basisf.p;         // ... or the FP32-stored one
-  const bool b16 = c->basis16;
-  const bool b32 = c->basis32 && !b16;
-  // (only where the launches are bandwidth bound -- the multi-shift SpMM regime: cfg5 K1 1252 -> 1150 us per
-  // launch, cycle +2 %; at cfg2 the FP32 gathers are no faster and the step was 1.4 % slower)
-  // the preconditioner reads the current vector from the FP16 basis itself; its FP64 copy is then not written
-  const bool h16 = precond_reads_h16(c, m);
-  // dot passes with atomic accumulation (no partial rows, no reduce launches): FP16 basis, 16 columns
-  // w is not rewritten between the two Gram-Schmidt passes: the final update subtracts V (h1 + h2) from the original w
-  const bool keepw = update_dots_keeps_w(m, b16, restart);
-  // last Arnoldi pass and Hessenberg update in ONE launch (K3h)
-  const bool fuseh = update_hess_fused_ok(m, b16);
-  const size_t resbuf = (size_t)c->wcols;                    // doubles between the two residual-estimate buffers
-  struct NoStoreScope {
-    explicit NoStoreScope(bool v) { set_update_dots_nostore(v); }
-    ~NoStoreScope() { set_update_dots_nostore(false); }
-  } nostore_scope(keepw);
+  const IterationForm f = iteration_form(c, m, G, lowrank);
   const size_t h2buf = (size_t)(restart + 2) * c->wcols;        // doubles between the two second-pass buffers
-  const bool x32 = iteration_reads_x32(c, m, G) && !(lowrank && c->q > 0);
-  const bool w32 = x32 && iteration_w32(c, m, G, b16, fuseh, keepw, restart);
-  c->w32_last = w32 ? 1 : 0;
+  c->w32_last = f.w32 ? 1 : 0;
   _Float16* Vh = reinterpret_cast<_Float16*>(c->basisf.p);   // FP16 storage shares the FP32 buffer
   double* hb = c->h_resid;
   const size_t slot = (size_t)RICADI_MAX_M * RICADI_MAX_GROUPS;
@@ -160,70 +238,35 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
     act.swap(next);
     if (act.empty()) break;
     bt.set(act);
-    if (b16)
-      launch_colscale_b(st, bt.tab, n, m, c->scale.p, c->wv.p, nm, 0.0, c->vcur.p, nm, Vh, nm);
-    else if (b32)
-      launch_colscale_b(st, bt.tab, n, m, c->scale.p, c->wv.p, nm, 0.0, c->vcur.p, nm, Vf, nm);
-    else
-      launch_colscale_b(st, bt.tab, n, m, c->scale.p, c->wv.p, nm, 0.0, V, nm);
+    with_basis(c, f, [&](auto* V) {
+      if constexpr (std::is_same<std::remove_pointer_t<decltype(V)>, double>::value)
+        launch_colscale_b(st, bt.tab, n, m, c->scale.p, c->wv.p, nm, 0.0, V, nm);
+      else
+        launch_colscale_b(st, bt.tab, n, m, c->scale.p, c->wv.p, nm, 0.0, c->vcur.p, nm, V, nm);
+    });
     live = act;
     for (int g : act) kk[g] = 0;
     lapc(c->t_cyc);
     for (int j = 0; j < cyc && !live.empty(); ++j) {
       bt.set(live);
-      const double* vj = (b32 || b16) ? c->vcur.p : V + (size_t)j * vs;
+      const double* vj = (f.b32 || f.b16) ? c->vcur.p : c->basis.p + (size_t)j * vs;
       // flexible form: Z_j = P^-1 v_j is kept (FP32), the cycle's correction is x += Z y -- no
       // preconditioner application at the cycle end, and P may differ from step to step
       // ... and the operator reads that stored FP32 copy (half the bytes of the x gathers; S Z_j = V H then
       // holds for exactly the vectors the correction uses), so the sweeps need not store the FP64 z at all
       float* zj = c->zbasisf.p + (size_t)j * vs;
-      precond_apply(c, bt, vj, nm, c->zv.p, zj, nm, x32, h16 ? Vh + (size_t)j * vs : nullptr);
-      op_apply(c, bt, c->zv.p, nm, c->wv.p, lowrank, x32 ? zj : nullptr, w32 ? c->wv32.p : nullptr);
-      double* h2cur = c->h2.p;
-      if (w32) {
-        launch_cols_dots16_w32(st, bt.tab, n, j + 1, Vh, vs, nm, c->wv32.p, nm, c->partial.p, gspart, c->h1.p, gsh);
-        launch_cols_update_dots16_w32(st, bt.tab, n, j + 1, Vh, vs, nm, c->h1.p, gsh, c->wv32.p, nm, c->partial.p,
-                                      gspart, c->h2.p, gsh);
-      } else if (b16) {
-        launch_cols_dots_b(st, bt.tab, n, m, j + 1, Vh, vs, nm, c->wv.p, nm, 0, c->partial.p, gspart,
-                           c->h1.p, gsh);
-        launch_cols_update_dots_b(st, bt.tab, n, m, j + 1, Vh, vs, nm, c->h1.p, gsh, c->wv.p, nm,
-                                  c->partial.p, gspart, c->h2.p, gsh);
-      } else if (b32) {
-        launch_cols_dots_b(st, bt.tab, n, m, j + 1, Vf, vs, nm, c->wv.p, nm, 0, c->partial.p, gspart,
-                           c->h1.p, gsh);
-        launch_cols_update_dots_b(st, bt.tab, n, m, j + 1, Vf, vs, nm, c->h1.p, gsh, c->wv.p, nm,
-                                  c->partial.p, gspart, c->h2.p, gsh);
-      } else {
-        launch_cols_dots_b(st, bt.tab, n, m, j + 1, V, vs, nm, c->wv.p, nm, 0, c->partial.p, gspart,
-                           c->h1.p, gsh);
-        // first update fused with the dot products of the second pass
-        launch_cols_update_dots_b(st, bt.tab, n, m, j + 1, V, vs, nm, c->h1.p, gsh, c->wv.p, nm,
-                                  c->partial.p, gspart, c->h2.p, gsh);
-      }
+      precond_apply(c, bt, vj, nm, c->zv.p, zj, nm, f.x32, f.h16 ? Vh + (size_t)j * vs : nullptr);
+      op_apply(c, bt, c->zv.p, nm, c->wv.p, lowrank, f.x32 ? zj : nullptr, f.w32 ? c->wv32.p : nullptr);
+      arnoldi_dots(c, f, bt, j + 1);
+      arnoldi_update_dots(c, f, bt, j + 1);
       // the residual estimates also go straight to a pinned host slot (read one
       // iteration later, behind the event below)
       double* cur = hb + 2 * slot + (size_t)(j & 1) * slot;
-      if (fuseh)
-        launch_cols_update16_hess_b(st, bt.tab, n, j + 1, Vh, vs, nm, c->h1.p, h2cur, gsh, keepw ? 1 : 0, c->wv.p, nm,
-                                    h16 ? nullptr : c->vcur.p, nm, Vh + (size_t)(j + 1) * vs, nm, j, restart, c->H.p,
-                                    c->cs.p, c->sn.p, c->g.p, c->resid.p + (size_t)(j & 1) * resbuf,
-                                    c->resid.p + (size_t)((j + 1) & 1) * resbuf, c->bnorm2.p, tol, cur,
-                                    w32 ? c->wv32.p : nullptr);
-      else
-        launch_gmres_hess_b(st, bt.tab, m, j, restart, c->h1.p, h2cur, c->H.p, c->cs.p, c->sn.p,
+      if (!f.fuseh)
+        launch_gmres_hess_b(st, bt.tab, m, j, restart, c->h1.p, c->h2.p, c->H.p, c->cs.p, c->sn.p,
                             c->g.p, c->scale.p, c->resid.p, c->bnorm2.p, tol, cur, nullptr, nullptr,
-                            keepw ? c->h2.p + h2buf : nullptr);
-      if (fuseh) {
-      } else if (b16)
-        launch_cols_update_b(st, bt.tab, n, m, j + 1, Vh, vs, nm, keepw ? c->h2.p + h2buf : h2cur, gsh, -1.0, c->wv.p, nm,
-                             c->scale.p, h16 ? nullptr : c->vcur.p, nm, Vh + (size_t)(j + 1) * vs, nm);
-      else if (b32)
-        launch_cols_update_b(st, bt.tab, n, m, j + 1, Vf, vs, nm, c->h2.p, gsh, -1.0, c->wv.p, nm,
-                             c->scale.p, c->vcur.p, nm, Vf + (size_t)(j + 1) * vs, nm);
-      else
-        launch_cols_update_b(st, bt.tab, n, m, j + 1, V, vs, nm, c->h2.p, gsh, -1.0, c->wv.p, nm,
-                             c->scale.p, V + (size_t)(j + 1) * vs, nm);
+                            f.keepw ? c->h2.p + h2buf : nullptr);
+      arnoldi_update(c, f, bt, j + 1, cur);
       // Residual estimates travel to a pinned slot behind an event; the host
       // looks at the PREVIOUS iteration's slot, so it never drains the stream
       // (one iteration of lag: at most one surplus Arnoldi step per group).

@@ -142,17 +142,6 @@ static void saddle_spmm(ricadi_ctx* c, const Batch& bt, const double* x, size_t 
                   m, gsr, alpha, beta_r, m, lr);
 }
 
-// Does the GMRES iteration apply the operator to the FP32-stored Z_j?
-static bool operator_reads_x32(const ricadi_ctx* c, int m) {
-  return saddle_tiled(c, m);
-}
-// ... for a batch of ng groups: always with the multi-shift kernel; with one workgroup per (row block, group) the FP32
-// input by itself measured 1.4 % slower at cfg2 in round 3, but it is what lets the cycle keep its velocity part in
-// FP32 and its blocks in BF16 (round 4), which more than pays for it (RICADI_X32=0: only with the multi-shift kernel)
-static bool iteration_reads_x32(const ricadi_ctx* c, int m, int ng) {
-  return operator_reads_x32(c, m) && (c->sw.x32_always || ms_pays(c, ng, c->snnz));
-}
-
 // y = S(alpha,beta) x for every active group (n x m panels, ld = m, group stride gsx /
 // bt.gs); optional low-rank  - U V^T x_v  (U, V shared by the groups)
 // y32 (optional, with x32 only): the product goes to this FP32 panel (stride bt.gs) and y is not written
@@ -173,10 +162,47 @@ static void op_apply(ricadi_ctx* c, const Batch& bt, const double* x, size_t gsx
   }
   saddle_spmm(c, bt, x, gsx, nullptr, y, bt.gs, nullptr, 0, 1.0, 0.0, lr, x32, y32);
 }
-// Does the Arnoldi iteration of a batch keep w = S z_j as an FP32 panel?  (the tile kernels with FP32 input write it,
-// the three 16-column passes on the FP16-stored basis read it; RICADI_W32=0: FP64 panel)
-static bool iteration_w32(const ricadi_ctx* c, int m, int ng, bool b16, bool fuseh, bool keepw, int restart) {
-  return c->sw.w32 && m == 16 && b16 && fuseh && keepw && iteration_reads_x32(c, m, ng) && arnoldi16_w32_ok(restart);
+// ---- stages of the preconditioner that ricadi_time_kernel_dev also launches on their own
+// block-Jacobi sweep over the velocity (or pressure) blocks:  out[rows_b] (-)= inv_b in[rows_b]  (+ epilogue pa / cin)
+static void block_sweep(ricadi_ctx* c, const Batch& bt, bool pressure, const double* in, size_t gsi, double* out,
+                        int subtract, const ProlongArgs& pa = ProlongArgs(), const CsrInArgs& cin = CsrInArgs()) {
+  const int nb = pressure ? c->nbp : c->nbv, m = bt.m;
+  const int* bptr = pressure ? c->bp_ptr.p : c->bv_ptr.p;
+  const int* rows = pressure ? c->bp_rows.p : c->bv_rows.p;
+  auto sweep = [&](const auto& inv) {
+    launch_block_apply_b(c->st, bt.tab, c->bs, nb, bptr, rows, inv, in, m, gsi, out, m, bt.gs, m, subtract, pa, cin);
+  };
+  if (c->precond32) sweep(pressure ? bt.bpinvf : bt.bvinvf);
+  else sweep(pressure ? bt.bpinv : bt.bvinv);
+}
+// ec = E^-1 rc by the dense inverse of the coarse matrix (the last level)
+static void coarse_dense(ricadi_ctx* c, const Batch& bt) {
+  if (c->precond32)
+    launch_dense_apply_b(c->st, bt.tab, c->kc, bt.m, bt.einvf, (c->kc + 3) & ~3, c->rc.p, c->ec.p);
+  else
+    launch_dense_apply_b(c->st, bt.tab, c->kc, bt.m, bt.einv, c->rc.p, c->ec.p);
+}
+// r2 = r - (S Y) ec through the tile kernels (c->syb_ok): the multi-shift one where it pays
+static bool sy_tiled_ms(const ricadi_ctx* c, const Batch& bt) {
+  return ms_pays(c, bt.tab.ng, c->snnz) && spmm_blocked_ms_ok(bt.m, c->syb_max_cols, (size_t)c->kc);
+}
+static void sy_residual_tiled(ricadi_ctx* c, const Batch& bt, const double* r, size_t gsr) {
+  const int m = bt.m;
+  if (sy_tiled_ms(c, bt))
+    launch_spmm_blocked_ms(c->st, bt.tab, bt.alpha, bt.beta, c->sb_nblk, c->sb_rows2.p, c->syb_rp2.p, c->syb_cols2.p,
+                           c->syb_lidx_ms.p, c->sybAJ.p, c->sybE.p, c->ec.p, m, bt.gsc, c->r2.p, m, bt.gs, r, m, gsr,
+                           -1.0, 1.0, m, c->syb_max_cols);
+  else
+    launch_spmm_blocked_b(c->st, bt.tab, c->sb_nblk, c->sb_rows2.p, c->syb_rp2.p, c->syb_cols2.p, c->syb_lidx.p,
+                          bt.syvalb, c->ec.p, m, bt.gsc, c->r2.p, m, bt.gs, r, m, gsr, -1.0, 1.0, m, c->syb_max_cols);
+}
+// rc = Y^T r (smoothed aggregation: P^T r) by the 16-lanes-per-row CSR kernel
+static void restrict_csr(ricadi_ctx* c, const Batch& bt, const double* r, size_t gsr) {
+  const int* rrp = c->sa ? c->pt_rp.p : c->agg_ptr.p;
+  const int* rci = c->sa ? c->pt_ci.p : c->agg_rows.p;
+  const GroupPtrs rvals = same_ptr(c->sa ? (const double*)c->pt_v.p : c->ones.p);
+  launch_spmm_b(c->st, bt.tab, c->kc, rrp, rci, rvals, r, bt.m, gsr, nullptr, c->rc.p, bt.m, bt.gsc, nullptr, 0, 0,
+                1.0, 0.0, bt.m);
 }
 
 // z = P^-1 r for every active group: multiplicative two-level, coarse correction
@@ -235,18 +261,16 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
       launch_spmm_h(st, gt, c->kc, rrp, rci, rvals, nullptr, r16, m, gsr, c->rc.p, m, bt.gsc,
                     nullptr, 0, 0, 1.0, 0.0, m, 16);
     else
-      launch_spmm_b(st, gt, c->kc, rrp, rci, rvals, r, m, gsr, nullptr, c->rc.p, m,
-                    bt.gsc, nullptr, 0, 0, 1.0, 0.0, m);
+      restrict_csr(c, bt, r, gsr);
     if (!on(1)) {
     } else if (c->child) {
       // coarse problem by one cycle of the child level's preconditioner (a fixed linear operator)
       Batch cb = *bt.sub;
       cb.tab = gt;
       precond_apply(c->child.get(), cb, c->rc.p, bt.gsc, c->ec.p);
-    } else if (c->precond32)
-      launch_dense_apply_b(st, gt, c->kc, m, bt.einvf, (c->kc + 3) & ~3, c->rc.p, c->ec.p);
-    else
-      launch_dense_apply_b(st, gt, c->kc, m, bt.einv, c->rc.p, c->ec.p);
+    } else {
+      coarse_dense(c, bt);
+    }
     if (!on(2) || (fusedp && folded)) {
     } else if (folded) {
       // only the PRESSURE rows of r - (S Y) ec are formed (short CSR product over np rows); the
@@ -265,16 +289,8 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
       // velocity sweep instead, like the J^T product below, was measured slower: 249 vs
       // 257 shift-solves/s -- 8 rows x 7.6 dependent gathers per lane.)
       // Tile form: the aggregates a row block touches (a few dozen coarse rows) go to LDS once.
-      if (c->syb_ok && ms_pays(c, gt.ng, c->snnz) &&
-          spmm_blocked_ms_ok(m, c->syb_max_cols, (size_t)c->kc))
-        launch_spmm_blocked_ms(st, gt, bt.alpha, bt.beta, c->sb_nblk, c->sb_rows2.p, c->syb_rp2.p,
-                               c->syb_cols2.p, c->syb_lidx_ms.p, c->sybAJ.p, c->sybE.p, c->ec.p, m,
-                               bt.gsc, c->r2.p, m, bt.gs, r, m, gsr, -1.0, 1.0, m, c->syb_max_cols);
-      else if (c->syb_ok &&
-          spmm_blocked_lds_bytes(m, c->syb_max_cols, 0) <= (size_t)40 * 1024)
-        launch_spmm_blocked_b(st, gt, c->sb_nblk, c->sb_rows2.p, c->syb_rp2.p, c->syb_cols2.p,
-                              c->syb_lidx.p, bt.syvalb, c->ec.p, m, bt.gsc, c->r2.p, m, bt.gs, r, m, gsr,
-                              -1.0, 1.0, m, c->syb_max_cols);
+      if (c->syb_ok && (sy_tiled_ms(c, bt) || spmm_blocked_lds_bytes(m, c->syb_max_cols, 0) <= (size_t)40 * 1024))
+        sy_residual_tiled(c, bt, r, gsr);
       else
         launch_spmm_b(st, gt, c->n, c->sy_rp.p, c->sy_ci.p, bt.syval, c->ec.p, m, bt.gsc, nullptr,
                       c->r2.p, m, bt.gs, r, m, gsr, -1.0, 1.0, m, LowRankArgs(), c->sy_chunk);
@@ -292,16 +308,6 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
     pro.row0 = nv;
     pro.nextra = np;
   }
-  auto vel_apply = [&](const double* in, size_t gsi, int subtract, bool last,
-                       const CsrInArgs& cin = CsrInArgs()) {
-    const ProlongArgs pa = last ? pro : ProlongArgs();
-    if (c->precond32)
-      launch_block_apply_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinvf, in, m, gsi, z,
-                           m, bt.gs, m, subtract, pa, cin);
-    else
-      launch_block_apply_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinv, in, m, gsi, z,
-                           m, bt.gs, m, subtract, pa, cin);
-  };
   if (!on(3)) {
   } else if (folded) {
     // z_v = Ahat^-1 r_v - (Ahat^-1 D) ec : first velocity sweep on the corrected residual without
@@ -336,7 +342,7 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
       launch_block_apply2_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinv, s1, bt.adym, s2, z, m,
                             bt.gs, m, fpa);
   } else {
-    vel_apply(rr, gsrr, 0, np == 0);
+    block_sweep(c, bt, false, rr, gsrr, z, 0, np == 0 ? pro : ProlongArgs());
   }
   if (np > 0) {
     // t = J z_v - r_p
@@ -380,12 +386,9 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
       else
         launch_pressure_step_b(st, gt, c->nbp, c->ps_meta.p, bt.bpinv, c->J.ci.p, c->J.v.p, z, bt.gs, sy, c->sy_ci.p,
                                bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, ppro);
-    } else if (c->precond32)
-      launch_block_apply_b(st, gt, c->bs, c->nbp, c->bp_ptr.p, c->bp_rows.p, bt.bpinvf, c->tp.p, m,
-                           bt.gsp, zp, m, bt.gs, m, 0, ppro);
-    else
-      launch_block_apply_b(st, gt, c->bs, c->nbp, c->bp_ptr.p, c->bp_rows.p, bt.bpinv, c->tp.p, m,
-                           bt.gsp, zp, m, bt.gs, m, 0, ppro);
+    } else {
+      block_sweep(c, bt, true, c->tp.p, bt.gsp, zp, 0, ppro);
+    }
     // z_v -= Ahat^-1 (J^T z_p): the same block-Jacobi inverse as in the Schur blocks; the
     // J^T product is formed inside the sweep, row by row as the blocks gather them
     // (z_p is small and L2 resident), instead of through an intermediate panel
@@ -421,7 +424,7 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
       cin.src = c->tp.p;
       cin.gss = bt.gsp;
       pro.nextra = 0;          // the pressure rows already carry their coarse part
-      vel_apply(nullptr, 0, 1, true, cin);
+      block_sweep(c, bt, false, nullptr, 0, z, 1, pro, cin);
     }
   }
   if (z32 && !mirrored && c->pc_stage < 0)

@@ -353,3 +353,38 @@ def test_cycle_forms_of_round4_against_sparse_lu(cfg1, monkeypatch):
         iters[name] = np.asarray(its, dtype=float)
     for name, _ in forms[1:]:
         assert np.abs(iters[name] - iters["default"]).max() <= 3, iters
+
+
+# ------------------------------------------------------------------ the kernel timer (Context.TK)
+def test_kernel_timer_launches_what_the_iteration_launches(cfg1):
+    """Every class of Context.TK runs once through time_kernel_dev at the hot width (16) and at a generic one (5)
+    for three shifts and returns a finite, positive time, or the library's own refusal for a part the cfg1 operator
+    lacks.  After the dots and precond classes, the FP32 operator-output and FP32 intermediate flags equal what a
+    batched solve with the same shifts and width left: the timer and the iteration choose the same kernels."""
+    pr = cfg1[0]
+    calA = (-pr.A - pr.Nc).T.tocsr()
+    MT = pr.M.T.tocsr()
+    ps = [-2.0, -30.0, -400.0]
+    ones = [1.0] * len(ps)
+    refusals = ("no coarse level", "no pressure block", "no tiled S*Y")
+    flags = ("fp32_operator_output", "fp32_intermediate")
+    rng = np.random.default_rng(5)
+    with _lib.Context(0) as ctx:
+        ctx.set_operator(calA, MT, pr.J)
+        import torch
+        for m in (16, 5):
+            Rd = torch.from_numpy(rng.standard_normal((pr.NV, m))).cuda()
+            Xd = torch.empty((len(ps), pr.NV + pr.NP, m), dtype=torch.float64, device="cuda")
+            ctx.shift_solve_batch_dev(ps, ones, Rd.data_ptr(), 0, m, Xd.data_ptr())
+            ctx.synchronize()
+            solved = ctx.setup_info()
+            for name in ctx.TK:
+                try:
+                    t = ctx.time_kernel_dev(name, ps, ones, m, nvec=3, reps=2)
+                except RuntimeError as e:
+                    assert any(r in str(e) for r in refusals), (name, m, str(e))
+                    continue
+                assert np.isfinite(t) and t > 0.0, (name, m, t)
+                if name in ("dots", "precond"):
+                    info = ctx.setup_info()
+                    assert [info[k] for k in flags] == [solved[k] for k in flags], (name, m)

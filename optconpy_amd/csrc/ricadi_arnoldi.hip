@@ -1229,4 +1229,360 @@ void launch_cols_update_dots16_w32(hipStream_t st, const GroupTab& gt, int nrows
 }
 
 
+// ---------------------------------------------------------------------------
+// K3L: the Arnoldi of the hot path (FP16-stored basis, 16 columns, FP32 panel w) in its one-reduction form: delayed
+// classical Gram-Schmidt run twice (DCGS2; Swirydowicz et al. 2020, Bielich et al. 2022), three launches per
+// iteration (dots, the partial-sum reduction, update) instead of five.  Per column, at iteration j:
+//   * V_{j-1} = [v_0 .. v_{j-1}] is orthonormal and final; slot j of the basis holds the candidate u_j, projected
+//     ONCE and scaled by a norm estimate 1 / rho_{j-1}; the preconditioner and the operator have made w = S P^-1 u_j;
+//   * dots (arnoldi16_lowsync_dots_kernel + reduce_partials_kernel): ONE pass over V_{j-1}, u_j and w gives
+//     s = V^T u_j, alpha = u_j^T u_j, t = V^T w, beta = u_j^T w and ||w||^2;
+//   * update (arnoldi16_lowsync_update_kernel): every workgroup derives from those sums
+//       r_j = sqrt(alpha - ||s||^2)            (the delayed re-orthogonalisation: u_j = V s + r_j v_j),
+//       h_jj = (beta - s^T t) / r_j,  rho_j^2 = ||w||^2 - ||t||^2 - h_jj^2,
+//     and streams V_{j-1}, u_j and w once, writing v_j = (u_j - V s) / r_j into slot j (in place: row-local) and
+//     u_{j+1} = (w - V t - v_j h_jj) / rho_j into slot j+1.  Its workgroup 0 also completes column j-1 of H~,
+//     p_{j-1} + rho_{j-1} [s; r_j], applies the stored and the new Givens rotation, updates g, keeps the pending
+//     column p_j = [t; h_jj] and rho_j for the next iteration (two buffers by the parity of j: the other workgroups
+//     read the previous one), and writes a PROVISIONAL residual estimate for column j (s' = 0, r' = 1 on a copy of the
+//     rotations) to the device and pinned host slots -- the host keeps its one-iteration lag; H~ and g only ever
+//     hold completed columns.
+// rho_j only sets the FP16 storage scale of u_{j+1}: whatever value is used, w = [V, v_j] p_j + rho_j u_{j+1} holds,
+// and u_{j+1} = V s' + r' v_{j+1} is measured exactly by the next reduction -- cancellation in the Pythagorean estimate
+// cannot corrupt H~, only mis-scale the stored vector, so its range is guarded (floor 1e-3 ||w||, where the estimate
+// is at the level of the FP16 basis' own loss of orthogonality).  The last column of a cycle is completed by a dots
+// pass without w and arnoldi16_lowsync_close_kernel (each group with its own k_g), so the back substitution only
+// sees completed columns.  Frozen columns (|g| <= 0.01 tol ||b|| before the column's rotation, or breakdown) get a
+// zero sub-diagonal as in gmres_hess_kernel; the column after a frozen one is made inert (v, u, coefficients zero).
+// (An in-launch reduction by the last-arriving workgroup was tried first: with one agent-scope release per
+// workgroup over 16 x 468 workgroups the dots launch took 244 us at cfg2, with 48 workgroups per group 62 us.)
+// ---------------------------------------------------------------------------
+size_t lowsync_partial_stride(int nrows, int restart) { return (size_t)dots_num_blocks(nrows) * 2 * (restart + 2) * 16; }
+// per group: the reduced sums [slot][s|t][16] (2 (restart + 2) rows), then two pending columns (p, rho, g before
+// the column's rotation: restart + 3 rows each)
+size_t lowsync_coef_stride(int restart) { return (size_t)(4 * restart + 10) * 16; }
+bool arnoldi16_lowsync_ok(int restart) { return (size_t)((restart + 2) * 32 + 48) * sizeof(double) <= 48 * 1024; }
+
+struct LsPend {
+  double *p, *rho, *gj;
+  __device__ LsPend(double* coef, int restart, int par)
+      : p(coef + 2 * (restart + 2) * 16 + (size_t)par * (restart + 3) * 16), rho(p + (restart + 1) * 16), gj(rho + 16) {}
+};
+
+// partial[blk][o], o < ldp: the sums of one 64-row chunk per workgroup for slots V_0 .. V_{j-1}, u_j, w (j = js[group];
+// HAS_W = false: the end-of-cycle pass, no w).  u_j and w are staged in LDS once (FP64, rows of stride WLS); lane =
+// (row slice sl, column half, slot) as in chunk_dots16: the 16 lanes of a DPP row hold the 16 row slices of ONE
+// (slot, half), and one load of a basis row feeds both sums.  (With u_j and w loaded into registers by every slot's
+// lanes instead -- eight times the cache traffic -- the launch took 37 us at cfg2 against 23 us.)
+template <bool HAS_W>
+__global__ __launch_bounds__(256) void arnoldi16_lowsync_dots_kernel(
+    GroupTab gt, GroupInts js, int nrows, int ldp, const _Float16* __restrict__ basis, size_t vstride, size_t gsb,
+    const float* __restrict__ w, size_t gsw, double* __restrict__ partial, size_t gsp) {
+  __shared__ __attribute__((aligned(16))) double lds[2 * DOT_ROWS * WLS];
+  double* ul = lds;
+  double* wl = lds + DOT_ROWS * WLS;
+  const int grp = gt.gid[blockIdx.z];
+  const int j = js.v[grp];
+  const int nslot = j + 2;
+  basis += (size_t)grp * gsb;
+  if (HAS_W) w += (size_t)grp * gsw;
+  double* prow = partial + (size_t)grp * gsp + (size_t)blockIdx.x * ldp;
+  if (j <= 0 && !HAS_W) return;
+  const _Float16* u = basis + (size_t)j * vstride;
+  const int r0 = blockIdx.x * DOT_ROWS, nr = min(DOT_ROWS, nrows - r0);
+  if (threadIdx.x < DOT_ROWS * 2) {
+    const int row = threadIdx.x >> 1, hf = threadIdx.x & 1;
+    half8_t x = (half8_t)(_Float16)0;
+    if (row < nr) x = *reinterpret_cast<const half8_t*>(u + (size_t)(r0 + row) * 16 + hf * 8);
+    double2* d = reinterpret_cast<double2*>(ul + row * WLS + hf * 8);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) d[t] = make_double2((double)x[2 * t], (double)x[2 * t + 1]);
+  }
+  {
+    const int row = threadIdx.x >> 2, q = threadIdx.x & 3;
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (HAS_W && row < nr) x = *reinterpret_cast<const float4*>(w + (size_t)(r0 + row) * 16 + q * 4);
+    double2* d = reinterpret_cast<double2*>(wl + row * WLS + q * 4);
+    d[0] = make_double2((double)x.x, (double)x.y);
+    d[1] = make_double2((double)x.z, (double)x.w);
+  }
+  for (int e = nslot * 32 + threadIdx.x; e < ldp; e += 256) prow[e] = 0.0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sl = lane & 15, half = (lane >> 4) & 1, vsub = lane >> 5;
+  for (int i0 = 0; i0 < nslot; i0 += 8) {
+    const int i = i0 + 2 * wave + vsub;
+    double as[8], at[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) as[t] = at[t] = 0.0;
+    if (i < j) {
+      const _Float16* v = basis + (size_t)i * vstride + (size_t)r0 * 16 + half * 8;
+      half8_t x[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int row = sl + 16 * k;
+        if (row < nr) x[k] = *reinterpret_cast<const half8_t*>(v + (size_t)row * 16);
+        else x[k] = (half8_t)(_Float16)0;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const double* ur = ul + (sl + 16 * k) * WLS + half * 8;
+        const double* wr = wl + (sl + 16 * k) * WLS + half * 8;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          const double xv = (double)x[k][t];
+          as[t] = fma(xv, ur[t], as[t]);
+          at[t] = fma(xv, wr[t], at[t]);
+        }
+      }
+    } else if (i == j) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const double* ur = ul + (sl + 16 * k) * WLS + half * 8;
+        const double* wr = wl + (sl + 16 * k) * WLS + half * 8;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          as[t] = fma(ur[t], ur[t], as[t]);
+          at[t] = fma(ur[t], wr[t], at[t]);
+        }
+      }
+    } else if (i == j + 1) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const double* wr = wl + (sl + 16 * k) * WLS + half * 8;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) as[t] = fma(wr[t], wr[t], as[t]);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      as[t] = dpp_row_sum(as[t]);
+      at[t] = dpp_row_sum(at[t]);
+    }
+    if (sl == 0 && i < nslot) {
+      double2* o = reinterpret_cast<double2*>(prow + (size_t)i * 32 + half * 8);
+      double2* o2 = reinterpret_cast<double2*>(prow + (size_t)i * 32 + 16 + half * 8);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        o[t] = make_double2(as[2 * t], as[2 * t + 1]);
+        o2[t] = make_double2(at[2 * t], at[2 * t + 1]);
+      }
+    }
+  }
+}
+
+// Column c of group grp, from the reduced sums: completes column j-1 of H~ (when `complete`), returns the update's
+// coefficients.  Every caller derives the same values from the same inputs.
+struct LsCoefs {
+  double invr, hjj, sig;
+  bool dead;
+};
+__device__ LsCoefs ls_column(const double* sums, int j, int c, int restart, double* coef, double thr, bool complete,
+                             bool with_w, double* Hcol, double* csc, double* snc, double* gc, double* resid_out,
+                             double* host_resid) {
+  const double tiny = 1e-300;
+  auto S = [&](int i) { return sums[i * 32 + c]; };
+  auto T = [&](int i) { return sums[i * 32 + 16 + c]; };
+  double r = 1.0;                           // v_0 = u_0 (the cycle start normalised it)
+  bool dead = false;                        // column j-1 frozen or broken down: column j is inert
+  if (j > 0) {
+    const LsPend pp(coef, restart, (j - 1) & 1);
+    double ssq = 0.0;
+    for (int i = 0; i < j; ++i) ssq = fma(S(i), S(i), ssq);
+    const double r2 = S(j) - ssq;
+    r = r2 > 0.0 ? sqrt(r2) : 0.0;
+    const double rho = pp.rho[c], gj = pp.gj[c];
+    double sub = rho * r;
+    dead = !(sub > tiny) || fabs(gj) <= thr;
+    if (complete) {
+      // column j-1:  p_{j-1} + rho_{j-1} [s; r]
+      if (dead) sub = 0.0;
+      double* Hc = Hcol + (size_t)(j - 1) * (restart + 1);
+      double cur = fma(rho, S(0), pp.p[c]);
+      for (int i = 0; i + 1 < j; ++i) {
+        const double nxt = fma(rho, S(i + 1), pp.p[(i + 1) * 16 + c]);
+        Hc[i] = csc[i] * cur + snc[i] * nxt;
+        cur = -snc[i] * cur + csc[i] * nxt;
+      }
+      const double d = hypot(cur, sub);
+      double cj = 1.0, sj = 0.0;
+      if (d > tiny) {
+        cj = cur / d;
+        sj = sub / d;
+      }
+      csc[j - 1] = cj;
+      snc[j - 1] = sj;
+      Hc[j - 1] = (d > tiny) ? d : 1.0;    // keep R non-singular for frozen columns
+      Hc[j] = 0.0;
+      gc[j] = (d > tiny) ? -sj * gj : 0.0;
+      gc[j - 1] = (d > tiny) ? cj * gj : 0.0;
+    }
+  }
+  LsCoefs o{0.0, 0.0, 0.0, dead};
+  if (!with_w) return o;
+  o.invr = (!dead && r > tiny) ? 1.0 / r : 0.0;
+  double st = 0.0, tsq = 0.0;
+  for (int i = 0; i < j; ++i) {
+    st = fma(S(i), T(i), st);
+    tsq = fma(T(i), T(i), tsq);
+  }
+  const double hjj = (T(j) - st) * o.invr;
+  const double ww = S(j + 1);
+  const double wn = sqrt(fmax(ww, 0.0));
+  const double rho2 = ww - tsq - hjj * hjj;
+  double rho = fmax(rho2 > 0.0 ? sqrt(rho2) : 0.0, 1e-3 * wn);
+  if (dead || !(rho > tiny)) rho = 0.0;
+  o.hjj = dead ? 0.0 : hjj;
+  o.sig = rho > 0.0 ? 1.0 / rho : 0.0;
+  if (complete) {
+    // pending column j, and the provisional residual estimate after it (s' = 0, r' = 1) on a copy of the rotations
+    const LsPend pn(coef, restart, j & 1);
+    for (int i = 0; i < j; ++i) pn.p[i * 16 + c] = dead ? 0.0 : T(i);
+    pn.p[j * 16 + c] = o.hjj;
+    pn.rho[c] = rho;
+    const double gj = gc[j];
+    pn.gj[c] = gj;
+    const double sub = (dead || fabs(gj) <= thr) ? 0.0 : rho;
+    double cur = dead ? 0.0 : (j > 0 ? T(0) : o.hjj);
+    for (int i = 0; i < j; ++i) {
+      const double nxt = dead ? 0.0 : (i + 1 < j ? T(i + 1) : o.hjj);
+      cur = -snc[i] * cur + csc[i] * nxt;
+    }
+    const double d = hypot(cur, sub);
+    const double rnew = (d > tiny) ? fabs(sub / d * gj) : 0.0;
+    resid_out[c] = rnew;
+    if (host_resid) host_resid[c] = rnew;
+  }
+  return o;
+}
+
+__global__ __launch_bounds__(256) void arnoldi16_lowsync_update_kernel(
+    GroupTab gt, size_t nhalf, int j, _Float16* __restrict__ basis, size_t vstride, size_t gsb,
+    const float* __restrict__ w, size_t gsw, double* __restrict__ coef, size_t gsc, int restart,
+    double* __restrict__ H, double* __restrict__ cs, double* __restrict__ sn, double* __restrict__ g,
+    const double* __restrict__ bnorm, double tol, double* __restrict__ resid_out, double* __restrict__ host_resid) {
+  extern __shared__ double cl[];           // the reduced sums [slot][s|t][16] (slots 0 .. j+1), then invr, hjj, sig
+  const int m = 16;
+  const int grp = gt.gid[blockIdx.z];
+  basis += (size_t)grp * gsb;
+  w += (size_t)grp * gsw;
+  coef += (size_t)grp * gsc;
+  const int nsum = (j + 2) * 32;
+  double* sums = cl;
+  double* il = cl + nsum;                  // invr, hjj, sig: 16 each
+  for (int e = threadIdx.x; e < nsum; e += 256) sums[e] = coef[e];
+  __syncthreads();
+  if (threadIdx.x < m) {
+    const int c = threadIdx.x;
+    const size_t gq = (size_t)grp;
+    const bool w0 = blockIdx.x == 0;
+    const LsCoefs k = ls_column(sums, j, c, restart, coef, 0.01 * tol * bnorm[gq * m + c], w0, true,
+                                H + gq * m * (restart + 1) * restart + (size_t)c * (restart + 1) * restart,
+                                cs + gq * m * restart + (size_t)c * restart, sn + gq * m * restart + (size_t)c * restart,
+                                g + gq * m * (restart + 1) + (size_t)c * (restart + 1), resid_out + gq * m,
+                                host_resid ? host_resid + gq * m : nullptr);
+    il[c] = k.invr;
+    il[m + c] = k.hjj;
+    il[2 * m + c] = k.sig;
+  }
+  __syncthreads();
+  _Float16* uj = basis + (size_t)j * vstride;
+  _Float16* un = uj + vstride;
+  for (size_t idx = blockIdx.x * (size_t)256 + threadIdx.x; idx < nhalf; idx += (size_t)gridDim.x * 256) {
+    const size_t e = idx * 8;
+    const int c0 = (int)(idx & 1) * 8;
+    double as[8], at[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) as[t] = at[t] = 0.0;
+    const _Float16* v = basis + e;
+    int i = 0;
+    for (; i + 3 < j; i += 4) {
+      half8_t x[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) x[q] = *reinterpret_cast<const half8_t*>(v + (size_t)(i + q) * vstride);
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          as[t] = fma(sums[(i + q) * 32 + c0 + t], (double)x[q][t], as[t]);
+          at[t] = fma(sums[(i + q) * 32 + 16 + c0 + t], (double)x[q][t], at[t]);
+        }
+    }
+    for (; i < j; ++i) {
+      const half8_t x = *reinterpret_cast<const half8_t*>(v + (size_t)i * vstride);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        as[t] = fma(sums[i * 32 + c0 + t], (double)x[t], as[t]);
+        at[t] = fma(sums[i * 32 + 16 + c0 + t], (double)x[t], at[t]);
+      }
+    }
+    const half8_t uu = *reinterpret_cast<const half8_t*>(uj + e);
+    const float4* wp = reinterpret_cast<const float4*>(w + e);
+    const float4 w0 = wp[0], w1 = wp[1];
+    const float wf[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+    half8_t fv, fu;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      fv[t] = (_Float16)(((double)uu[t] - as[t]) * il[c0 + t]);
+      // the stored (rounded) v_j: w = [V, v_j] p_j + rho_j u_{j+1} holds for the vectors as stored
+      fu[t] = (_Float16)(((double)wf[t] - at[t] - (double)fv[t] * il[m + c0 + t]) * il[2 * m + c0 + t]);
+    }
+    *reinterpret_cast<half8_t*>(uj + e) = fv;
+    *reinterpret_cast<half8_t*>(un + e) = fu;
+  }
+}
+
+// end of a cycle: completes column k_g - 1 of every group from the sums of the dots pass without w
+__global__ __launch_bounds__(64) void arnoldi16_lowsync_close_kernel(
+    GroupTab gt, GroupInts ks, double* __restrict__ coef, size_t gsc, int restart, double* __restrict__ H,
+    double* __restrict__ cs, double* __restrict__ sn, double* __restrict__ g, const double* __restrict__ bnorm,
+    double tol) {
+  const int m = 16;
+  const int grp = gt.gid[blockIdx.z];
+  const int k = ks.v[grp];
+  const int c = threadIdx.x;
+  if (k <= 0 || c >= m) return;
+  const size_t gq = (size_t)grp;
+  coef += gq * gsc;
+  (void)ls_column(coef, k, c, restart, coef, 0.01 * tol * bnorm[gq * m + c], true, false,
+                  H + gq * m * (restart + 1) * restart + (size_t)c * (restart + 1) * restart,
+                  cs + gq * m * restart + (size_t)c * restart, sn + gq * m * restart + (size_t)c * restart,
+                  g + gq * m * (restart + 1) + (size_t)c * (restart + 1), nullptr, nullptr);
+}
+
+void launch_arnoldi16_lowsync_dots(hipStream_t st, const GroupTab& gt, const GroupInts& js, int nrows,
+                                   const _Float16* basis, size_t vstride, size_t gsb, const float* w32, size_t gsw,
+                                   double* partial, size_t gsp, double* coef, size_t gsc) {
+  if (gt.ng <= 0) return;
+  int jmax = 0;
+  for (int z = 0; z < gt.ng; ++z) jmax = std::max(jmax, js.v[gt.gid[z]]);
+  const int nblk = dots_num_blocks(nrows), ldp = (jmax + 2) * 32;
+  if (w32)
+    hipLaunchKernelGGL(arnoldi16_lowsync_dots_kernel<true>, dim3(nblk, 1, gt.ng), dim3(256), 0, st, gt, js, nrows, ldp,
+                       basis, vstride, gsb, w32, gsw, partial, gsp);
+  else
+    hipLaunchKernelGGL(arnoldi16_lowsync_dots_kernel<false>, dim3(nblk, 1, gt.ng), dim3(256), 0, st, gt, js, nrows,
+                       ldp, basis, vstride, gsb, w32, gsw, partial, gsp);
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((ldp + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt, nblk, ldp, partial,
+                     gsp, coef, gsc, 0);
+}
+void launch_arnoldi16_lowsync_update(hipStream_t st, const GroupTab& gt, int nrows, int j, _Float16* basis,
+                                     size_t vstride, size_t gsb, const float* w32, size_t gsw, double* coef,
+                                     size_t gsc, int restart, double* H, double* cs, double* sn, double* g,
+                                     const double* bnorm, double tol, double* resid_out, double* host_resid) {
+  if (gt.ng <= 0) return;
+  const size_t nhalf = (size_t)nrows * 2;
+  const int grid = (int)std::min<size_t>((nhalf + 255) / 256, 8192);
+  hipLaunchKernelGGL(arnoldi16_lowsync_update_kernel, dim3(grid, 1, gt.ng), dim3(256),
+                     (size_t)((j + 2) * 32 + 48) * sizeof(double), st, gt, nhalf, j, basis, vstride, gsb, w32, gsw, coef,
+                     gsc, restart, H, cs, sn, g, bnorm, tol, resid_out, host_resid);
+}
+void launch_arnoldi16_lowsync_close(hipStream_t st, const GroupTab& gt, const GroupInts& ks, double* coef, size_t gsc,
+                                    int restart, double* H, double* cs, double* sn, double* g, const double* bnorm,
+                                    double tol) {
+  if (gt.ng <= 0) return;
+  hipLaunchKernelGGL(arnoldi16_lowsync_close_kernel, dim3(1, 1, gt.ng), dim3(64), 0, st, gt, ks, coef, gsc, restart, H,
+                     cs, sn, g, bnorm, tol);
+}
+
 }  // namespace ricadi

@@ -248,6 +248,8 @@ struct Switches {
   bool blocks16 = true;       // RICADI_BLOCKS16=0: the sweeps apply the FP32 copies of the per-shift blocks
   bool rowwave = true;        // RICADI_ROWWAVE=0: the restriction through the 16-lanes-per-row CSR kernel
   bool mid32 = true;          // RICADI_MID32=0: the velocity part between the sweeps of a cycle stays an FP64 panel
+  bool lowsync = true;        // RICADI_ARNOLDI=cgs2: the three-pass CGS2 Arnoldi on the hot path instead of the
+                              // one-reduction form
 };
 
 }  // namespace ricadi
@@ -343,6 +345,7 @@ struct ricadi_ctx {
   bool basis16 = true;        // FP16-stored Krylov basis (default for n <= 2^21: basis16_default)
   bool precond32 = true;
   DArr<double> partial, h1, h2, H, cs, sn, g, scale, resid, yv, bnorm2, nrm2;
+  DArr<double> ls_partial, ls_coef;   // one-reduction Arnoldi: partial sums; reduced sums and pending columns per group
   DArr<int> flag, ipiv, info;
   DArr<double*> eptrs;
   DArr<double> gj_cb, gj_rp, gj_rb, gj_d;   // block Gauss-Jordan inverse of the coarse matrices

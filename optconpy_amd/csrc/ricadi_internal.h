@@ -465,6 +465,25 @@ void launch_cols_update_dots16_w32(hipStream_t st, const GroupTab& gt, int nrows
                                    size_t vstride, size_t gsb, const double* h, size_t gsh, float* w32, size_t gsw,
                                    double* partial, size_t gsp, double* out, size_t gso);
 
+// K3L: the one-reduction (delayed CGS2) Arnoldi of the same hot path (ricadi_arnoldi.hip).  dots: one pass over V,
+// the candidate u_j (slot j) and w, reduced into the group's coefficient block (w32 = NULL: the end-of-cycle pass,
+// j = k_g per group); update: derives the coefficients from those sums, completes column j-1 of H~ (workgroup 0),
+// writes the provisional residual estimate of column j, v_j into slot j (in place) and the next candidate u_{j+1}
+// into slot j+1; close: completes column k_g - 1 after the end-of-cycle dots pass.
+bool arnoldi16_lowsync_ok(int restart);
+size_t lowsync_partial_stride(int nrows, int restart);   // doubles per group of the partial-sum buffer
+size_t lowsync_coef_stride(int restart);                 // doubles per group of the coefficient buffer
+void launch_arnoldi16_lowsync_dots(hipStream_t st, const GroupTab& gt, const GroupInts& js, int nrows,
+                                   const _Float16* basis, size_t vstride, size_t gsb, const float* w32, size_t gsw,
+                                   double* partial, size_t gsp, double* coef, size_t gsc);
+void launch_arnoldi16_lowsync_update(hipStream_t st, const GroupTab& gt, int nrows, int j, _Float16* basis,
+                                     size_t vstride, size_t gsb, const float* w32, size_t gsw, double* coef,
+                                     size_t gsc, int restart, double* H, double* cs, double* sn, double* g,
+                                     const double* bnorm, double tol, double* resid_out, double* host_resid);
+void launch_arnoldi16_lowsync_close(hipStream_t st, const GroupTab& gt, const GroupInts& ks, double* coef, size_t gsc,
+                                    int restart, double* H, double* cs, double* sn, double* g, const double* bnorm,
+                                    double tol);
+
 // K5c: pivoted Cholesky of a (possibly augmented) symmetric matrix, 8 / 16 / 32 pivots per launch pair --
 // the eigensolver-free recompression (ricadi_kernels.hip).  State lives on the device so that the host can
 // issue all blocks without a read-back: once `stop` is set the remaining launches return at once.

@@ -113,6 +113,7 @@ static Switches read_switches() {
   s.blocks16 = !off("RICADI_BLOCKS16");
   s.rowwave = !off("RICADI_ROWWAVE");
   s.mid32 = !off("RICADI_MID32");
+  if (const char* e = getenv("RICADI_ARNOLDI")) s.lowsync = strcmp(e, "cgs2") != 0;
   return s;
 }
 
@@ -811,6 +812,7 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
   HIPCHK(hipMemsetAsync(c->g.p, 0x3C, sizeof(double) * (size_t)ng * m * (restart + 1), st));
   HIPCHK(hipMemsetAsync(c->cs.p, 0x3C, sizeof(double) * (size_t)ng * m * restart, st));
   HIPCHK(hipMemsetAsync(c->sn.p, 0x3C, sizeof(double) * (size_t)ng * m * restart, st));
+  HIPCHK(hipMemsetAsync(c->ls_coef.p, 0x3C, sizeof(double) * c->ls_coef.n, st));
   if (c->kc > 0) {
     HIPCHK(hipMemsetAsync(c->rc.p, 0x3C, sizeof(double) * bt.gsc * ng, st));
     HIPCHK(hipMemsetAsync(c->ec.p, 0x3C, sizeof(double) * bt.gsc * ng, st));
@@ -858,14 +860,19 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
         if (!c->syb_ok) throw HipError{"no tiled S*Y"};
         sy_residual_tiled(c, bt, c->wv.p, nm);
         break;
+      // one-reduction form: 5 = its dots (with the reduction), 6 = the end-of-cycle pass, 7 = its update (iteration
+      // nvec - 1)
       case 5:
-        arnoldi_dots(c, f, bt, nvec);
+        if (f.lowsync) arnoldi_lowsync_dots(c, bt, same_int(nvec - 1), false);
+        else arnoldi_dots(c, f, bt, nvec);
         break;
       case 6:
-        arnoldi_update_dots(c, f, bt, nvec);
+        if (f.lowsync) arnoldi_lowsync_dots(c, bt, same_int(nvec), true);
+        else arnoldi_update_dots(c, f, bt, nvec);
         break;
       case 7:
-        arnoldi_update(c, f, bt, nvec, nullptr);
+        if (f.lowsync) arnoldi_lowsync_update(c, bt, nvec - 1, nullptr);
+        else arnoldi_update(c, f, bt, nvec, nullptr);
         break;
       case 8:
         precond_apply(c, bt, c->wv.p, nm, c->zv.p, c->zbasisf.p, nm, f.x32, Vh);

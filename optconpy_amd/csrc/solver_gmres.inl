@@ -6,9 +6,10 @@
 // one Arnoldi process per column, all groups in lockstep inside ONE sequence of
 // launches (grid.z = active groups).  At n ~ 3e4 a single panel leaves most of
 // the chip idle and the launch path dominates; batching the shifts of a sweep
-// fills it.  Right preconditioning, CGS2, per-column Givens QR.  A group whose
-// columns have all converged leaves the active table; its correction is formed
-// at the end of the restart cycle from the basis vectors it had by then.
+// fills it.  Right preconditioning, CGS2 (on the hot path in its one-reduction,
+// delayed form: DESIGN.md 3a), per-column Givens QR.  A group whose columns have
+// all converged leaves the active table; its correction is formed at the end of
+// the restart cycle from the basis vectors it had by then.
 //   b: group stride gsb (0 = one right-hand side shared by all groups);
 //   x: group stride n*m, overwritten.
 struct GmresResult {
@@ -28,6 +29,8 @@ struct IterationForm {
   bool fuseh = false;   // last Arnoldi pass and Hessenberg update in ONE launch (K3h)
   bool x32 = false;     // the operator reads the FP32-stored Z_j
   bool w32 = false;     // ... and writes w = S z_j as an FP32 panel, which the three Arnoldi passes read
+  bool lowsync = false; // one-reduction (delayed CGS2) Arnoldi: dots, reduction, update per iteration (three launches,
+                        // not five), three more at the end of a cycle
 };
 static IterationForm iteration_form(const ricadi_ctx* c, int m, int G, bool lowrank) {
   const int restart = c->opts.gmres_restart;
@@ -46,6 +49,8 @@ static IterationForm iteration_form(const ricadi_ctx* c, int m, int G, bool lowr
   // the tile kernels with FP32 input write the FP32 panel, the three 16-column passes on the FP16-stored basis read
   // it (RICADI_W32=0: FP64 panel)
   f.w32 = f.x32 && c->sw.w32 && m == 16 && f.b16 && f.fuseh && f.keepw && arnoldi16_w32_ok(restart);
+  // ... and there the one-reduction Arnoldi (RICADI_ARNOLDI=cgs2: the three passes)
+  f.lowsync = f.w32 && f.h16 && c->sw.lowsync && arnoldi16_lowsync_ok(restart);
   return f;
 }
 // fn(basis) with the Krylov basis as stored: _Float16*, float* or double*
@@ -114,6 +119,28 @@ static void arnoldi_update(ricadi_ctx* c, const IterationForm& f, const Batch& b
       launch_cols_update_b(c->st, bt.tab, c->n, m, nvec, V, s.vs, s.nm, h, s.gsh, -1.0, c->wv.p, s.nm, c->scale.p,
                            vcur, s.nm, V + (size_t)nvec * s.vs, s.nm);
   });
+}
+
+// One-reduction Arnoldi (f.lowsync).  dots of iteration j (end_of_cycle: without w, j = k_g per group, and the
+// completion of column k_g - 1), update of iteration j (completes column j-1, provisional residual estimate of
+// column j into host_resid, v_j into slot j, the next candidate u_{j+1} into slot j+1).
+static void arnoldi_lowsync_dots(ricadi_ctx* c, const Batch& bt, const GroupInts& js, bool end_of_cycle) {
+  const ArnoldiStrides s(c, bt);
+  const int restart = c->opts.gmres_restart;
+  launch_arnoldi16_lowsync_dots(c->st, bt.tab, js, c->n, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
+                                end_of_cycle ? nullptr : c->wv32.p, s.nm, c->ls_partial.p,
+                                lowsync_partial_stride(c->n, restart), c->ls_coef.p, lowsync_coef_stride(restart));
+  if (end_of_cycle)
+    launch_arnoldi16_lowsync_close(c->st, bt.tab, js, c->ls_coef.p, lowsync_coef_stride(restart), restart, c->H.p,
+                                   c->cs.p, c->sn.p, c->g.p, c->bnorm2.p, c->opts.gmres_tol);
+}
+static void arnoldi_lowsync_update(ricadi_ctx* c, const Batch& bt, int j, double* host_resid) {
+  const ArnoldiStrides s(c, bt);
+  const int restart = c->opts.gmres_restart;
+  launch_arnoldi16_lowsync_update(c->st, bt.tab, c->n, j, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
+                                  c->wv32.p, s.nm, c->ls_coef.p, lowsync_coef_stride(restart), restart, c->H.p,
+                                  c->cs.p, c->sn.p, c->g.p, c->bnorm2.p, c->opts.gmres_tol,
+                                  c->resid.p + (size_t)(j & 1) * c->wcols, host_resid);
 }
 
 // have_x0: x holds an initial guess (else it is zeroed);  only: the groups to iterate on (NULL = all; the
@@ -257,16 +284,22 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
       float* zj = c->zbasisf.p + (size_t)j * vs;
       precond_apply(c, bt, vj, nm, c->zv.p, zj, nm, f.x32, f.h16 ? Vh + (size_t)j * vs : nullptr);
       op_apply(c, bt, c->zv.p, nm, c->wv.p, lowrank, f.x32 ? zj : nullptr, f.w32 ? c->wv32.p : nullptr);
-      arnoldi_dots(c, f, bt, j + 1);
-      arnoldi_update_dots(c, f, bt, j + 1);
       // the residual estimates also go straight to a pinned host slot (read one
       // iteration later, behind the event below)
       double* cur = hb + 2 * slot + (size_t)(j & 1) * slot;
-      if (!f.fuseh)
-        launch_gmres_hess_b(st, bt.tab, m, j, restart, c->h1.p, c->h2.p, c->H.p, c->cs.p, c->sn.p,
-                            c->g.p, c->scale.p, c->resid.p, c->bnorm2.p, tol, cur, nullptr, nullptr,
-                            f.keepw ? c->h2.p + h2buf : nullptr);
-      arnoldi_update(c, f, bt, j + 1, cur);
+      if (f.lowsync) {
+        // slot j holds the candidate u_j the preconditioner read; v_j replaces it, u_{j+1} goes to slot j + 1
+        arnoldi_lowsync_dots(c, bt, same_int(j), false);
+        arnoldi_lowsync_update(c, bt, j, cur);
+      } else {
+        arnoldi_dots(c, f, bt, j + 1);
+        arnoldi_update_dots(c, f, bt, j + 1);
+        if (!f.fuseh)
+          launch_gmres_hess_b(st, bt.tab, m, j, restart, c->h1.p, c->h2.p, c->H.p, c->cs.p, c->sn.p,
+                              c->g.p, c->scale.p, c->resid.p, c->bnorm2.p, tol, cur, nullptr, nullptr,
+                              f.keepw ? c->h2.p + h2buf : nullptr);
+        arnoldi_update(c, f, bt, j + 1, cur);
+      }
       // Residual estimates travel to a pinned slot behind an event; the host
       // looks at the PREVIOUS iteration's slot, so it never drains the stream
       // (one iteration of lag: at most one surplus Arnoldi step per group).
@@ -294,6 +327,8 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
     {
       GroupInts ks = same_int(0);
       for (int g : act) ks.v[g] = kk[g];
+      // one-reduction form: the last column of every group still waits for the correction of its candidate u_{k_g}
+      if (f.lowsync) arnoldi_lowsync_dots(c, bt, ks, true);
       launch_gmres_backsolve_b(st, bt.tab, m, ks, restart, c->H.p, c->g.p, c->yv.p);
       launch_cols_update_bk(st, bt.tab, n, m, ks, c->zbasisf.p, vs, nm, c->yv.p, (size_t)restart * m, x, nm, x, nm);
     }

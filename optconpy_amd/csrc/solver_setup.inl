@@ -61,6 +61,8 @@ static void ensure_work(ricadi_ctx* c, int m, int groups = 1, int extra = -1) {
   c->ec.alloc((size_t)std::max(c->kc, 1) * gm);
   c->partial.alloc((size_t)dots_num_blocks(c->n) * (restart + 2) * gm);
   c->h1.alloc((size_t)(restart + 2) * gm);
+  c->ls_partial.alloc((gm + 15) / 16 * lowsync_partial_stride(c->n, restart));
+  c->ls_coef.alloc((gm + 15) / 16 * lowsync_coef_stride(restart));
   c->h2.alloc((size_t)2 * (restart + 2) * gm);      // two buffers (atomic dot passes alternate between them)
   c->H.alloc(gm * (restart + 1) * restart);
   c->cs.alloc(gm * restart);

@@ -165,6 +165,41 @@ int ricadi_spmm(ricadi_ctx* ctx, double alpha, double beta,
 int ricadi_precond_apply(ricadi_ctx* ctx, double alpha, double beta,
                          const double* R, int m, double* Z);
 
+/* Preconditioner as the lockstep GMRES iteration applies it, for tests (device panels).  ng shifts
+ * (alphas[g], betas[g]); R_g = dR + g*r_stride (n x m, r_stride >= n*m); Z_g = dZ + g*n*m (FP64).  The form
+ * is the iteration's for a batch of ng panels of width m: where it hands the preconditioner the FP16-stored
+ * Krylov vector, R is rounded to FP16 into that storage and the FP64 panel handed along holds NaN; where the
+ * operator reads the FP32-stored Z_j, Z is that FP32 panel (widened).  active (may be NULL = all): the nactive
+ * distinct group ids the application acts on; the other panels of dZ are not written.  form_out (may be NULL):
+ * the branch each stage took, RICADI_PCF_* bits below.  ng*m <= 2048.  No reference counterpart.            */
+#define RICADI_PCF_H16 (1 << 0)          /* input read from the FP16-stored vector                            */
+#define RICADI_PCF_X32 (1 << 1)          /* output: the FP32 panel only (the operator reads it)               */
+#define RICADI_PCF_MID32 (1 << 2)        /* velocity part between the sweeps as an FP32 panel                 */
+#define RICADI_PCF_B16 (1 << 3)          /* BF16-stored per-shift blocks                                      */
+#define RICADI_PCF_RESTRICT_SHIFT 4      /* 2 bits: restriction 1 one wave per row, 2 FP16 CSR, 3 FP64 CSR   */
+#define RICADI_PCF_COARSE_SHIFT 6        /* 2 bits: coarse problem 1 child level's cycle, 2 dense inverse     */
+#define RICADI_PCF_PFUSED (1 << 8)       /* pressure step in one launch                                       */
+#define RICADI_PCF_PSPLIT (1 << 9)       /* pressure step in three launches                                   */
+#define RICADI_PCF_FIRST_SHIFT 10        /* 2 bits: first velocity sweep 1 record-driven BF16 two-term,
+                                            2 generic two-term, 3 plain block sweep                           */
+#define RICADI_PCF_LAST_SHIFT 12         /* 2 bits: last velocity sweep 1 record-driven BF16 rectangle,
+                                            2 generic rectangle, 3 J^T product formed row by row (CSR in)    */
+#define RICADI_PCF_FOLDED (1 << 14)      /* folded cycle (coarse residual inside the first sweep)             */
+#define RICADI_PCF_TWO_KS_SHIFT 16       /* 8 bits: padded width of the two-term sweep's second block (0: none) */
+#define RICADI_PCF_RECT_KS_SHIFT 24      /* 8 bits: padded width of the rectangle sweep's blocks (0: none)    */
+int ricadi_precond_apply_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas, const double* betas,
+                                   const double* dR, int64_t r_stride, int m, const int32_t* active,
+                                   int nactive, double* dZ, int* form_out);
+
+/* Structure of the preconditioner cycle of level `level` (0: this context, 1: its child level, ...), for
+ * tests.  sizes_out[16] = [nv, np, nbv, nbp, bs, kc, kcv, kcp, smoothed aggregation, nnz(P), has a child level,
+ * folded cycle, rectangle last sweep, FP32-stored operands, 0, 0].  Call with the arrays NULL for the sizes,
+ * then again with bv_ptr[nbv+1], bv_rows[nv], bp_ptr[nbp+1], bp_rows[np], aggof[n] (dof -> coarse index),
+ * p_rp[n+1], p_ci[nnz(P)], p_v[nnz(P)] (the prolongation P, CSR over all n rows); any of them may be NULL. */
+int ricadi_precond_structure(ricadi_ctx* ctx, int level, int32_t* sizes_out, int32_t* bv_ptr, int32_t* bv_rows,
+                             int32_t* bp_ptr, int32_t* bp_rows, int32_t* aggof, int32_t* p_rp, int32_t* p_ci,
+                             double* p_v);
+
 /* ---- one shift-solve ---------------------------------------------------
  * Solve S(alpha,beta) [V; L] = [R; Rp] for an NV x m panel R (Rp may be
  * NULL = 0).  X_out is n x m (velocity rows first).  iters_out[1],

@@ -109,6 +109,9 @@ SIGNATURES = {
     "ricadi_set_exchange_rccl": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int64]),
     "ricadi_exchange_count": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "ricadi_dense_inverse_batch": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
+    "ricadi_precond_apply_batch_dev": (C.c_int, [_vp, C.c_int, _dp, _dp, _vp, C.c_int64, C.c_int, _ip, C.c_int,
+                                                 _vp, C.POINTER(C.c_int)]),
+    "ricadi_precond_structure": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _dp]),
     "ricadi_host_deal": (C.c_int, [_dp, C.c_int, C.c_int, _ip]),
     "ricadi_host_sa_criterion": (C.c_int, [C.c_int, _ip, _ip, _dp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_int)]),
@@ -695,6 +698,59 @@ class Context:
         route = C.c_int(-1)
         _chk(self._lib.ricadi_dense_inverse_batch(self._h, A.shape[1], A.shape[0], _d(A), C.byref(route)))
         return A, int(route.value)
+
+    # RICADI_PCF_* of include/ricadi.h: the branch each stage of a preconditioner application took
+    PCF_RESTRICT = {0: None, 1: "rowwave", 2: "csr16", 3: "csr64"}
+    PCF_COARSE = {0: None, 1: "child", 2: "dense"}
+    PCF_FIRST = {0: None, 1: "two32", 2: "two_term", 3: "plain"}
+    PCF_LAST = {0: None, 1: "rect32", 2: "rect", 3: "csr_in"}
+
+    @classmethod
+    def decode_precond_form(cls, w):
+        w &= 0xFFFFFFFF
+        return dict(h16=bool(w & 1), x32=bool(w & 2), mid32=bool(w & 4), b16=bool(w & 8),
+                    restrict=cls.PCF_RESTRICT[(w >> 4) & 3], coarse=cls.PCF_COARSE[(w >> 6) & 3],
+                    pfused=bool(w & (1 << 8)), psplit=bool(w & (1 << 9)), first=cls.PCF_FIRST[(w >> 10) & 3],
+                    last=cls.PCF_LAST[(w >> 12) & 3], folded=bool(w & (1 << 14)), two_term_ks=(w >> 16) & 255,
+                    rect_ks=(w >> 24) & 255)
+
+    def precond_apply_batch_dev(self, alphas, betas, r_ptr, r_stride, m, z_ptr, active=None):
+        """``Z_g = P(alphas[g], betas[g])^-1 R_g`` as the lockstep GMRES applies it to a batch of
+        ``len(alphas)`` panels of width ``m`` (``R_g = r_ptr + g*r_stride``, ``Z_g = z_ptr + g*n*m``, device
+        FP64); ``active``: the group ids to apply it to (the other panels of Z are not written).  Returns the
+        decoded ``form`` word (``decode_precond_form``): which branch every stage of the cycle took."""
+        al = np.ascontiguousarray(alphas, dtype=np.float64)
+        be = np.ascontiguousarray(betas, dtype=np.float64)
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        form = C.c_int(-1)
+        _chk(self._lib.ricadi_precond_apply_batch_dev(self._h, al.size, _d(al), _d(be), r_ptr, int(r_stride), int(m),
+                                                      None if act is None else _i(act),
+                                                      0 if act is None else act.size, z_ptr, C.byref(form)))
+        return self.decode_precond_form(form.value)
+
+    def precond_structure(self, level=0):
+        """Structure of the preconditioner cycle of ``level`` (0 this context, 1 its child level): dict with the
+        velocity / pressure block lists (``bv_ptr``, ``bv_rows``, ``bp_ptr``, ``bp_rows``), ``aggof`` (dof ->
+        coarse index), ``kc``, ``kcv``, ``kcp``, ``smoothed``, the prolongation ``P`` (scipy CSR, n x kc),
+        ``child``, ``folded``, ``rect`` and ``precond32``."""
+        sz = np.zeros(16, dtype=np.int32)
+        nul = [None] * 8
+        _chk(self._lib.ricadi_precond_structure(self._h, int(level), _i(sz), *nul))
+        nv, np_, nbv, nbp, bs, kc, kcv, kcp, sa, nnzp, child, folded, rect, p32 = (int(x) for x in sz[:14])
+        n = nv + np_
+        out = dict(bv_ptr=np.zeros(nbv + 1, np.int32), bv_rows=np.zeros(nv, np.int32),
+                   bp_ptr=np.zeros(nbp + 1, np.int32), bp_rows=np.zeros(np_, np.int32),
+                   aggof=np.zeros(n if kc > 0 else 0, np.int32), p_rp=np.zeros(n + 1, np.int32),
+                   p_ci=np.zeros(nnzp, np.int32), p_v=np.zeros(nnzp))
+        ptr = lambda a: _d(a) if a.dtype == np.float64 else _i(a)   # noqa: E731
+        _chk(self._lib.ricadi_precond_structure(self._h, int(level), _i(sz), *[ptr(out[k]) for k in (
+            "bv_ptr", "bv_rows", "bp_ptr", "bp_rows", "aggof", "p_rp", "p_ci", "p_v")]))
+        P = (sps.csr_matrix((out.pop("p_v"), out.pop("p_ci"), out.pop("p_rp")), shape=(n, kc)) if kc > 0 else None)
+        if nbp == 0:
+            out["bp_ptr"] = np.zeros(1, np.int32)
+        out.update(nv=nv, np=np_, nbv=nbv, nbp=nbp, bs=bs, kc=kc, kcv=kcv, kcp=kcp, smoothed=bool(sa), P=P,
+                   child=bool(child), folded=bool(folded), rect=bool(rect), precond32=bool(p32))
+        return out
 
     def time_qr_dev(self, z_ptr, c, reps):
         ms = C.c_double(0.0)

@@ -326,6 +326,7 @@ struct ricadi_ctx {
   bool ms_ok = false;         // the operator's tiles allow the multi-shift kernel (its value arrays exist)
   int w32_last = -1;          // the last operator launch of an iteration / timing class wrote the FP32 panel (1) or FP64 (0)
   int mid32_last = -1;        // what the last preconditioner application did (1 FP32 panel, 0 FP64; -1 none yet)
+  int pc_form_last = -1;      // ... and the branch each of its stages took (RICADI_PCF_* bits; -1 none yet)
   // low rank
   int q = 0;
   DArr<double> U, V, lrc, scratch;

@@ -530,6 +530,142 @@ int ricadi_precond_apply(ricadi_ctx* c, double alpha, double beta, const double*
   API_END
 }
 
+int ricadi_precond_apply_batch_dev(ricadi_ctx* c, int ng, const double* alphas, const double* betas,
+                                   const double* dR, int64_t r_stride, int m, const int32_t* active, int nactive,
+                                   double* dZ, int* form_out) {
+  if (int rc = check_panel(c, m)) return rc;
+  REQUIRE(dR && dZ && alphas && betas, RICADI_EINVAL, "NULL argument");
+  REQUIRE(ng >= 1 && ng <= RICADI_MAX_GROUPS && (size_t)ng * m <= 2048, RICADI_EINVAL,
+          "1 <= ng <= 16 and ng*m <= 2048 required");
+  REQUIRE(r_stride >= (int64_t)c->n * m, RICADI_EINVAL, "bad r_stride");
+  std::vector<int> ids;
+  if (active) {
+    for (int i = 0; i < nactive; ++i) {
+      REQUIRE(active[i] >= 0 && active[i] < ng && std::find(ids.begin(), ids.end(), active[i]) == ids.end(),
+              RICADI_EINVAL, "active: distinct group ids in [0, ng) required");
+      ids.push_back(active[i]);
+    }
+    REQUIRE(!ids.empty(), RICADI_EINVAL, "no active group");
+  }
+  API_BEGIN
+  hipStream_t st = c->st;
+  std::vector<ShiftData*> sds(ng);
+  get_shifts(c, alphas, betas, ng, sds.data());
+  ensure_work(c, m, ng, 0);
+  Batch bt = make_batch(c, sds.data(), ng, m);
+  if (active) bt.set(ids);
+  else bt.all();
+  const size_t nm = bt.gs, vs = nm * ng;
+  // the form gmres_core applies the preconditioner in (same question, same answer)
+  const IterationForm f = iteration_form(c, m, ng, false);
+  // input: the FP64 panel, or the FP16-stored Krylov vector (basis slot 0, rounded by the kernel that stores the
+  // basis) beside an FP64 panel of NaN -- the iteration does not write that copy then
+  const double* r = dR;
+  size_t gsr = (size_t)r_stride;
+  _Float16* r16 = nullptr;
+  std::vector<double> ones((size_t)ng * m, 1.0);
+  if (f.h16) {
+    r16 = reinterpret_cast<_Float16*>(c->basisf.p);
+    HIPCHK(hipMemcpyAsync(c->scale.p, ones.data(), sizeof(double) * ones.size(), hipMemcpyHostToDevice, st));
+    launch_colscale_b(st, bt.tab, c->n, m, c->scale.p, dR, gsr, 0.0, c->pw2.p, nm, r16, nm);
+    HIPCHK(hipMemsetAsync(c->pw1.p, 0xFF, sizeof(double) * vs, st));
+    r = c->pw1.p;
+    gsr = nm;
+  }
+  // output: z straight into dZ, or -- where the operator reads the FP32-stored Z_j -- that panel (slot 0 of the
+  // Z_j store) with the FP64 panel it must not need filled with NaN
+  float* z32 = c->zbasisf.p;
+  double* z = dZ;
+  if (f.x32) {
+    HIPCHK(hipMemsetAsync(c->zv.p, 0xFF, sizeof(double) * vs, st));
+    HIPCHK(hipMemsetAsync(z32, 0xFF, sizeof(float) * vs, st));
+    z = c->zv.p;
+  }
+  c->pc_form_last = -1;
+  precond_apply(c, bt, r, gsr, z, z32, nm, f.x32, r16);
+  if (f.x32) {
+    std::vector<float> h32(nm);
+    std::vector<double> h64(nm);
+    for (int i = 0; i < bt.tab.ng; ++i) {
+      const size_t g = (size_t)bt.tab.gid[i];
+      HIPCHK(hipMemcpyAsync(h32.data(), z32 + g * nm, sizeof(float) * nm, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (size_t k = 0; k < nm; ++k) h64[k] = h32[k];
+      HIPCHK(hipMemcpyAsync(dZ + g * nm, h64.data(), sizeof(double) * nm, hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  if (form_out) *form_out = c->pc_form_last;
+  API_END
+}
+
+int ricadi_precond_structure(ricadi_ctx* c, int level, int32_t* sizes_out, int32_t* bv_ptr, int32_t* bv_rows,
+                             int32_t* bp_ptr, int32_t* bp_rows, int32_t* aggof, int32_t* p_rp, int32_t* p_ci,
+                             double* p_v) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(sizes_out && level >= 0, RICADI_EINVAL, "bad argument");
+  const ricadi_ctx* l = c;
+  for (int i = 0; i < level && l; ++i) l = l->child.get();
+  REQUIRE(l, RICADI_EINVAL, "no such level");
+  API_BEGIN
+  (void)hipSetDevice(c->dev);
+  hipStream_t st = c->st;
+  const int n = l->n, kc = l->kc;
+  auto down = [&](auto* dst, const auto& src, size_t cnt) {
+    if (dst && cnt) HIPCHK(hipMemcpyAsync(dst, src.p, sizeof(*dst) * cnt, hipMemcpyDeviceToHost, st));
+  };
+  // dof -> coarse index (velocity aggregates first), and P^T by rows where the prolongation is smoothed
+  std::vector<int32_t> agg(kc > 0 ? n : 0), ptrp, ptci;
+  std::vector<double> ptv;
+  down(agg.data(), l->aggof, agg.size());
+  if (l->sa) {
+    ptrp.resize(kc + 1);
+    ptci.resize(l->pt_ci.n);
+    ptv.resize(l->pt_v.n);
+    down(ptrp.data(), l->pt_rp, ptrp.size());
+    down(ptci.data(), l->pt_ci, ptci.size());
+    down(ptv.data(), l->pt_v, ptv.size());
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  int kcv = 0;
+  for (int i = 0; i < l->nv && kc > 0; ++i) kcv = std::max(kcv, agg[i] + 1);
+  const int nnzp = kc <= 0 ? 0 : l->sa ? (int)ptci.size() : n;
+  const int32_t sz[16] = {l->nv, l->np, l->nbv, l->nbp, l->bs, kc, kcv, kc - kcv, l->sa ? 1 : 0, nnzp,
+                          l->child ? 1 : 0, precond_folds(l) ? 1 : 0, l->gt_ok ? 1 : 0, l->precond32 ? 1 : 0, 0, 0};
+  std::copy(sz, sz + 16, sizes_out);
+  down(bv_ptr, l->bv_ptr, (size_t)l->nbv + 1);
+  down(bv_rows, l->bv_rows, (size_t)l->nv);
+  down(bp_ptr, l->bp_ptr, l->nbp > 0 ? (size_t)l->nbp + 1 : 0);
+  down(bp_rows, l->bp_rows, (size_t)l->np);
+  if (aggof) std::copy(agg.begin(), agg.end(), aggof);
+  if (kc > 0 && (p_rp || p_ci || p_v)) {
+    // P by rows: P^T transposed, or one unit entry per row (plain aggregation)
+    std::vector<int32_t> rp(n + 1, 0), ci(nnzp);
+    std::vector<double> v(nnzp, 1.0);
+    if (l->sa) {
+      for (int32_t j : ptci) ++rp[j + 1];
+      for (int i = 0; i < n; ++i) rp[i + 1] += rp[i];
+      std::vector<int32_t> at(rp.begin(), rp.end() - 1);
+      for (int a = 0; a < kc; ++a)
+        for (int k = ptrp[a]; k < ptrp[a + 1]; ++k) {
+          ci[at[ptci[k]]] = a;
+          v[at[ptci[k]]++] = ptv[k];
+        }
+    } else {
+      for (int i = 0; i < n; ++i) {
+        rp[i + 1] = i + 1;
+        ci[i] = agg[i];
+      }
+    }
+    if (p_rp) std::copy(rp.begin(), rp.end(), p_rp);
+    if (p_ci) std::copy(ci.begin(), ci.end(), p_ci);
+    if (p_v) std::copy(v.begin(), v.end(), p_v);
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  API_END
+}
+
 int ricadi_shift_solve_dev(ricadi_ctx* c, double alpha, double beta, const double* dR, int m,
                            double* dX, int* iters_out, double* relres_out) {
   if (int rc = check_panel(c, m)) return rc;

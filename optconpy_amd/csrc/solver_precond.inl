@@ -244,6 +244,8 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
   c->mid32_last = mid32 ? 1 : 0;
   // ... and on BF16-stored blocks where every shift of the batch has them (record-driven sweeps only)
   const bool b16 = mid32 && bt.blocks16 && c->sw_stride > 0 && c->bs == 32;
+  // the branch every stage takes (RICADI_PCF_* bits, ricadi_precond_apply_batch_dev): a host-side record, no launch
+  unsigned form = (z32 && only32 ? RICADI_PCF_X32 : 0) | (mid32 ? RICADI_PCF_MID32 : 0) | (b16 ? RICADI_PCF_B16 : 0);
   if (c->kc > 0) {
     // restriction Y^T r = CSR product with unit values (aggregate lists as rows)
     folded = precond_folds(c);
@@ -254,8 +256,12 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
     const GroupPtrs rvals = c->sa ? same_ptr((const double*)c->pt_v.p) : ones;
     if (c->sa && !folded) throw HipError{"smoothed aggregation needs the folded preconditioner cycle"};
     const size_t rnnz = c->sa ? c->pt_ci.n : (size_t)c->n;
+    const bool rowwave = m == 16 && c->sw.rowwave && spmm_rowwave_pays(c->kc, rnnz);
+    form |= (r16 ? RICADI_PCF_H16 : 0) | (folded ? RICADI_PCF_FOLDED : 0) |
+            ((rowwave ? 1 : r16 ? 2 : 3) << RICADI_PCF_RESTRICT_SHIFT) |
+            ((c->child ? 1 : 2) << RICADI_PCF_COARSE_SHIFT);
     if (!on(0)) {
-    } else if (m == 16 && c->sw.rowwave && spmm_rowwave_pays(c->kc, rnnz))
+    } else if (rowwave)
       launch_spmm_rowwave(st, gt, c->kc, rrp, rci, rvals, r16 ? nullptr : r, r16, gsr, c->rc.p, bt.gsc, m);
     else if (r16)
       launch_spmm_h(st, gt, c->kc, rrp, rci, rvals, nullptr, r16, m, gsr, c->rc.p, m, bt.gsc,
@@ -334,17 +340,24 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
       fpa.bm_in = c->sw_in_two;
       fpa.bm_ni = 2;
     }
+    form |= (unsigned)c->ady_ks << RICADI_PCF_TWO_KS_SHIFT;
     if (b16 && launch_block_two32_h(st, gt, c->nbv, bt.bvinvh, s1, bt.adymh, s2, z, bt.gs, fpa)) {
-    } else if (c->precond32)
-      launch_block_apply2_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinvf, s1, bt.adymf, s2, z, m,
-                            bt.gs, m, fpa);
-    else
-      launch_block_apply2_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinv, s1, bt.adym, s2, z, m,
-                            bt.gs, m, fpa);
+      form |= 1 << RICADI_PCF_FIRST_SHIFT;
+    } else {
+      form |= 2 << RICADI_PCF_FIRST_SHIFT;
+      if (c->precond32)
+        launch_block_apply2_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinvf, s1, bt.adymf, s2, z, m,
+                              bt.gs, m, fpa);
+      else
+        launch_block_apply2_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinv, s1, bt.adym, s2, z, m,
+                              bt.gs, m, fpa);
+    }
   } else {
+    form |= 3 << RICADI_PCF_FIRST_SHIFT;
     block_sweep(c, bt, false, rr, gsrr, z, 0, np == 0 ? pro : ProlongArgs());
   }
   if (np > 0) {
+    form |= fusedp ? RICADI_PCF_PFUSED : RICADI_PCF_PSPLIT;
     // t = J z_v - r_p
     if (on(4) && !fusedp)
       launch_spmm_b(st, gt, np, c->J.rp.p, c->J.ci.p, jv, z, m, bt.gs, nullptr, c->tp.p, m, bt.gsp,
@@ -407,13 +420,18 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
         pro.bm_ni = 1;
       }
       mirrored = true;
+      form |= (unsigned)c->gt_ks << RICADI_PCF_RECT_KS_SHIFT;
       if (b16 && launch_block_rect32_h(st, gt, c->gt_ks, c->nbv, bt.gtmh, c->tp.p, bt.gsp, z, bt.gs, 1, pro)) {
-      } else if (c->precond32)
-        launch_block_apply_rect_b(st, gt, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
-                                  c->gt_cols.p, bt.gtmf, c->tp.p, m, bt.gsp, z, m, bt.gs, m, 1, pro);
-      else
-        launch_block_apply_rect_b(st, gt, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
-                                  c->gt_cols.p, bt.gtm, c->tp.p, m, bt.gsp, z, m, bt.gs, m, 1, pro);
+        form |= 1 << RICADI_PCF_LAST_SHIFT;
+      } else {
+        form |= 2 << RICADI_PCF_LAST_SHIFT;
+        if (c->precond32)
+          launch_block_apply_rect_b(st, gt, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
+                                    c->gt_cols.p, bt.gtmf, c->tp.p, m, bt.gsp, z, m, bt.gs, m, 1, pro);
+        else
+          launch_block_apply_rect_b(st, gt, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
+                                    c->gt_cols.p, bt.gtm, c->tp.p, m, bt.gsp, z, m, bt.gs, m, 1, pro);
+      }
     } else {
       // blocks that touch too many pressure dofs for the dense rectangles: the J^T product formed row by row inside
       // the sweep (CsrInArgs)
@@ -424,12 +442,14 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
       cin.src = c->tp.p;
       cin.gss = bt.gsp;
       pro.nextra = 0;          // the pressure rows already carry their coarse part
+      form |= 3 << RICADI_PCF_LAST_SHIFT;
       block_sweep(c, bt, false, nullptr, 0, z, 1, pro, cin);
     }
   }
   if (z32 && !mirrored && c->pc_stage < 0)
     for (int i = 0; i < gt.ng; ++i)
       launch_to_f32(st, c->n, m, z + (size_t)gt.gid[i] * bt.gs, m, z32 + (size_t)gt.gid[i] * gs32, m);
+  if (c->pc_stage < 0) c->pc_form_last = (int)form;
 }
 
 static void op_apply(ricadi_ctx* c, ShiftData* sd, const double* x, double* y, int m, bool lowrank) {

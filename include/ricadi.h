@@ -392,6 +392,14 @@ int ricadi_time_kernel_dev(ricadi_ctx* ctx, int which, int ng, const double* alp
  * (/root/reference/optcont_main.py:133-134) and of the Newton update norm.      */
 int ricadi_qr(ricadi_ctx* ctx, const double* Z, int c, double* Q_out, double* R_out);
 
+/* K7: the pencil of the operator projected onto a dense basis (the Ritz values behind ms='auto'):
+ * HA = Q^T (cal A - U V^T) Q,  HE = Q^T cal E Q  (k x k row-major; the low-rank term if one is set).
+ * Q: NV x k row-major, 1 <= k <= 128, any columns (orthonormal ones for Ritz values).  One pass over the
+ * velocity rows of the operator; per-workgroup partials summed in a fixed order, so the same inputs give
+ * bitwise the same HA / HE.  Host buffers; the _dev form takes device pointers.  No reference counterpart. */
+int ricadi_project_pencil(ricadi_ctx* ctx, const double* Q, int k, double* HA, double* HE);
+int ricadi_project_pencil_dev(ricadi_ctx* ctx, const double* dQ, int k, double* dHA, double* dHE);
+
 /* Structure of the preconditioner the context built for its operator:
  * out = [NV, NP, velocity blocks, Schur blocks, block size, coarse dimension,
  *        SpMM row blocks, max distinct columns per row block,

@@ -100,6 +100,8 @@ SIGNATURES = {
     "ricadi_time_kernel_dev": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(C.c_double)]),
     "ricadi_qr": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
+    "ricadi_project_pencil": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
+    "ricadi_project_pencil_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "ricadi_setup_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
     "ricadi_time_qr_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "ricadi_time_gram_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _dp]),
@@ -266,6 +268,8 @@ class Context:
         self._h = _vp()
         _chk(self._lib.ricadi_create(int(device), C.byref(self._h)))
         self.nv = self.np_ = self.n = 0
+        self._lowrank = None
+        self.diag_ratio = None
         if opts:
             self.set_opts(**opts)
 
@@ -322,6 +326,12 @@ class Context:
                                                _i(erp), _i(eci), _d(ev), None, None, None))
         self.nv, self.np_ = nv, np_
         self.n = nv + np_
+        self._lowrank = None
+        # |diag cal A / diag cal E| over the velocity dofs where both are nonzero: the initial shift estimate of
+        # adi_shifts.auto_shifts
+        da, de = sps.csr_matrix(calA).diagonal(), sps.csr_matrix(calE).diagonal()
+        ok = (da != 0) & (de != 0)
+        self.diag_ratio = np.abs(da[ok] / de[ok])
 
     def clear_cache(self):
         _chk(self._lib.ricadi_clear_cache(self._h))
@@ -336,12 +346,14 @@ class Context:
         """Operator becomes ``beta*A + alpha*E - U V^T`` (both NV x q)."""
         if U is None or V is None:
             _chk(self._lib.ricadi_set_lowrank(self._h, None, None, 0))
+            self._lowrank = None
             return
         U = as_panel(U, self.nv)
         V = as_panel(V, self.nv)
         if U.shape != V.shape:
             raise ValueError("U and V must have the same shape")
         _chk(self._lib.ricadi_set_lowrank(self._h, _d(U), _d(V), U.shape[1]))
+        self._lowrank = (U, V)
 
     def set_recycle(self, depth):
         """Depth of the recycling ring for DIRECT solve calls (the ADI drivers use their own, 3)."""
@@ -818,6 +830,27 @@ def _qr(self, Z, want_q=True):
 
 
 Context.qr = _qr
+
+
+def _project_pencil(self, Q):
+    """``(H_A, H_E) = (Q^T (cal A - U V^T) Q, Q^T cal E Q)`` for an NV x k panel ``Q`` (k <= 128), on the device
+    (K7); the low-rank term only if one is set.  Bitwise reproducible."""
+    self._need_op()
+    Q = as_panel(Q, self.nv)
+    k = Q.shape[1]
+    HA = np.empty((k, k))
+    HE = np.empty((k, k))
+    _chk(self._lib.ricadi_project_pencil(self._h, _d(Q), k, _d(HA), _d(HE)))
+    return HA, HE
+
+
+def _project_pencil_dev(self, q_ptr, k, ha_ptr, he_ptr):
+    """Device-pointer form of :meth:`project_pencil` (``Q`` NV x k, ``H_A`` / ``H_E`` k x k, row-major)."""
+    _chk(self._lib.ricadi_project_pencil_dev(self._h, q_ptr, int(k), ha_ptr, he_ptr))
+
+
+Context.project_pencil = _project_pencil
+Context.project_pencil_dev = _project_pencil_dev
 
 
 def host_aggregate(pattern, bsize):

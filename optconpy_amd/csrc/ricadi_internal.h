@@ -417,6 +417,13 @@ void launch_gj_diag(hipStream_t st, int nb, double* D, int nbe, int* flag);
 void launch_gj_rows(hipStream_t st, int nb, double* const* mats, int k, int k0, int nbe, const double* Rb);
 void launch_combine3(hipStream_t st, size_t n, const double* a0, const double* a1,
                      const double* a2, double alpha, double beta, double* out);
+// K7: projected pencil H_A = Q^T cal A Q, H_E = Q^T cal E Q (ricadi_project.hip).  With U != NULL the dense form:
+// HA = Q^T U, HE = Q^T V (k x q).  part: project_part_count(nv, k, k or q) doubles of scratch.
+size_t project_part_count(int nv, int k, int n2);
+void launch_project_pencil(hipStream_t st, int nv, int k, const int* rp, const int* ci, const double* vA,
+                           const double* vE, const double* Q, const double* U, const double* V, int q,
+                           double* part, double* HA, double* HE);
+void launch_project_lowrank(hipStream_t st, int k, int q, const double* QU, const double* QV, double* HA);
 
 // dst (BF16 bit patterns, round to nearest even) = src (FP64), n entries
 void launch_to_bf16(hipStream_t st, size_t n, const double* src, uint16_t* dst);

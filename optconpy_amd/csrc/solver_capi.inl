@@ -1051,6 +1051,49 @@ int ricadi_qr(ricadi_ctx* c, const double* Z, int cz, double* Q_out, double* R_o
   API_END
 }
 
+// H_A = Q^T (cal A - U V^T) Q, H_E = Q^T cal E Q on device panels; the low-rank term through the dense form of
+// the same kernel (Q^T U, Q^T V), so H is bitwise reproducible with it as well
+static void project_pencil_dev(ricadi_ctx* c, const double* dQ, int k, double* dHA, double* dHE) {
+  const int nv = c->nv, q = c->q;
+  size_t cnt = project_part_count(nv, k, k);
+  if (q > 0) cnt = std::max(cnt, project_part_count(nv, k, q));
+  TArr<double> part(c->pool, cnt);
+  launch_project_pencil(c->st, nv, k, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, dQ, nullptr, nullptr, 0, part.p,
+                        dHA, dHE);
+  if (q > 0) {
+    TArr<double> qu(c->pool, (size_t)k * q), qv(c->pool, (size_t)k * q);
+    launch_project_pencil(c->st, nv, k, nullptr, nullptr, nullptr, nullptr, dQ, c->U.p, c->V.p, q, part.p, qu.p,
+                          qv.p);
+    launch_project_lowrank(c->st, k, q, qu.p, qv.p, dHA);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->st));
+}
+
+int ricadi_project_pencil_dev(ricadi_ctx* c, const double* dQ, int k, double* dHA, double* dHE) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(dQ && dHA && dHE && k >= 1 && k <= RICADI_MAX_M && k <= c->nv, RICADI_EINVAL, "bad argument");
+  API_BEGIN
+  (void)hipSetDevice(c->dev);
+  project_pencil_dev(c, dQ, k, dHA, dHE);
+  API_END
+}
+
+int ricadi_project_pencil(ricadi_ctx* c, const double* Q, int k, double* HA, double* HE) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(Q && HA && HE && k >= 1 && k <= RICADI_MAX_M && k <= c->nv, RICADI_EINVAL, "bad argument");
+  API_BEGIN
+  (void)hipSetDevice(c->dev);
+  const size_t nq = (size_t)c->nv * k, nh = (size_t)k * k;
+  TArr<double> dQ(c->pool, nq), dH(c->pool, 2 * nh);
+  HIPCHK(hipMemcpyAsync(dQ.p, Q, sizeof(double) * nq, hipMemcpyHostToDevice, c->st));
+  project_pencil_dev(c, dQ.p, k, dH.p, dH.p + nh);
+  HIPCHK(hipMemcpyAsync(HA, dH.p, sizeof(double) * nh, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(HE, dH.p + nh, sizeof(double) * nh, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  API_END
+}
+
 int ricadi_setup_info(ricadi_ctx* c, int* out, int nout) {
   REQUIRE(c && out && nout >= 8, RICADI_EINVAL, "bad argument");
   out[0] = c->nv;

@@ -14,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 import scipy.sparse as sps
 
-from . import _lib, backend
+from . import _lib, adi_shifts, backend
 
 __all__ = [
     "solve_proj_lyap_stein", "proj_alg_ric_newtonadi", "compress_Zsvd",
@@ -132,11 +132,50 @@ def _orient(amat, mmat, transposed):
     return a, e
 
 
+def _is_auto(ms):
+    return isinstance(ms, str) and ms == "auto"
+
+
 def _shifts(d):
-    ms = list(d.get("ms", DEFAULT_MS))
+    """The shift list of an ``adi_dict``: ``DEFAULT_MS`` without ``'ms'``, the string ``'auto'`` as is (the
+    caller generates the list, :func:`_auto_shifts`), else a list of negative reals."""
+    ms = d.get("ms", DEFAULT_MS)
+    if _is_auto(ms):
+        return "auto"
+    ms = list(ms)
     if any((not np.isreal(p)) or p >= 0 for p in ms):
         raise ValueError("ADI shifts must be negative real numbers")
     return [float(p) for p in ms]
+
+
+def _broadcast_shifts(ms):
+    """Rank 0's list on every rank of the default ``torch.distributed`` group (all ranks must solve with the
+    same shifts; their Ritz values may differ in the last bits).  No-op in a single process."""
+    try:
+        import torch
+        import torch.distributed as dist
+    except ImportError:
+        return ms
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() <= 1:
+        return ms
+    dev = "cuda:%d" % backend.device_id() if dist.get_backend() == "nccl" else "cpu"
+    buf = torch.zeros(_lib.MAX_M + 1, dtype=torch.float64, device=dev)
+    if dist.get_rank() == 0:
+        buf[0] = len(ms)
+        buf[1:1 + len(ms)] = torch.tensor(list(ms), dtype=torch.float64)
+    dist.broadcast(buf, src=0)
+    h = buf.cpu().numpy()
+    out = adi_shifts.ShiftList(float(x) for x in h[1:1 + int(h[0])])
+    out.info = dict(getattr(ms, "info", {}), broadcast=True)
+    return out
+
+
+def _auto_shifts(ctx, d, W):
+    """``ms='auto'``: shifts from the operator of ``ctx`` as it stands (low-rank term included) and the
+    right-hand side factor ``W``; ``adi_dict['num_shifts']`` / ``['shift_warm_steps']``."""
+    ms = adi_shifts.auto_shifts(ctx, W, num=int(d.get("num_shifts", 8)),
+                                warm_steps=int(d.get("shift_warm_steps", 2)), default=DEFAULT_MS)
+    return _broadcast_shifts(ms)
 
 
 def solve_proj_lyap_stein(amat=None, mmat=None, jmat=None, wmat=None,
@@ -166,17 +205,21 @@ def solve_proj_lyap_stein(amat=None, mmat=None, jmat=None, wmat=None,
     try:
         if W.shape[1] > _lib.MAX_M:
             raise ValueError("right-hand side factor wider than {0} columns".format(_lib.MAX_M))
-        backend.ensure_exchange(ctx, W.shape[1], len(_shifts(d)))
+        ms = _shifts(d)
+        if _is_auto(ms):
+            ms = _auto_shifts(ctx, d, W)
+            out["ms"], out["shift_info"] = list(ms), dict(ms.info)
+        backend.ensure_exchange(ctx, W.shape[1], len(ms))
         if d.get("device_resident", False):
             # the factor stays in HBM (DeviceFactor): NV x (steps m) doubles need not cross PCIe to form a gain
             import torch
-            _, info = ctx.lyap_adi(_shifts(d), W, prm, fetch=False)
+            _, info = ctx.lyap_adi(ms, W, prm, fetch=False)
             Zt = torch.empty((ctx.nv, info["cols"]), dtype=torch.float64, device="cuda")
             if info["cols"] > 0:
                 ctx.factor_get_dev(Zt.data_ptr(), info["cols"])
             Z = DeviceFactor(Zt)
         else:
-            Z, info = ctx.lyap_adi(_shifts(d), W, prm)
+            Z, info = ctx.lyap_adi(ms, W, prm)
         if d.get("check_lyap_res", False):
             # optcont_main.py:130 -- the residual of the equation just solved, evaluated
             # independently of the ADI recurrence from the factors (a5, same context)
@@ -213,23 +256,30 @@ def proj_alg_ric_newtonadi(mmat=None, amat=None, jmat=None, bmat=None,
         # throughput of one shift-solve at a time on one GPU.  ``sweep_width=1`` in the
         # dict restores the step-by-step recurrence of the reference.
         prm.sweep_width = 16
+    ms = _shifts(d)
+    sinfo = None
+    if _is_auto(ms):
+        ms = _newton_auto_shifts(ctx, d, calE, bmat, wmat, z0, mtxoldb)
+        sinfo = dict(ms.info)
     if d.get("device_resident", False) or any(_on_device(x) for x in (bmat, wmat, z0, mtxoldb)):
         # every panel in HBM (uploaded here once if it came as an ndarray), the new factor returned as a
         # DeviceFactor: no PCIe traffic in the call when the caller keeps its panels on the device
         Bt, Wt = to_device(bmat).t, to_device(wmat).t
-        backend.ensure_exchange(ctx, Bt.shape[1] + Wt.shape[1], len(_shifts(d)))
-        Zt, info = ctx.ric_newtonadi_dev(_shifts(d), Bt, Wt, prm,
+        backend.ensure_exchange(ctx, Bt.shape[1] + Wt.shape[1], len(ms))
+        Zt, info = ctx.ric_newtonadi_dev(ms, Bt, Wt, prm,
                                          Z0_t=None if z0 is None else to_device(z0).t,
                                          old_t=None if mtxoldb is None else to_device(mtxoldb).t)
         out = dict(zfac=DeviceFactor(Zt))
     else:
         B, W = _dense(bmat), _dense(wmat)
-        backend.ensure_exchange(ctx, B.shape[1] + W.shape[1], len(_shifts(d)))
-        Z, info = ctx.ric_newtonadi(_shifts(d), B, W, prm,
+        backend.ensure_exchange(ctx, B.shape[1] + W.shape[1], len(ms))
+        Z, info = ctx.ric_newtonadi(ms, B, W, prm,
                                     Z0=None if z0 is None else _dense(z0),
                                     oldB=None if mtxoldb is None else _dense(mtxoldb))
         out = dict(zfac=Z)
     out.update(info)
+    if sinfo is not None:
+        out["ms"], out["shift_info"] = list(ms), sinfo
     if d.get("check_lyap_res", False):
         # optcont_main.py:130: residual of the last Newton step's Lyapunov equation --
         # in residual-form ADI it is W_end W_end^T, whose norm the driver returns
@@ -238,6 +288,27 @@ def proj_alg_ric_newtonadi(mmat=None, amat=None, jmat=None, bmat=None,
             print("last Newton step: projected Lyapunov residual {0:.3e} (rhs {1:.3e})"
                   .format(info["lyap_res_fro"], info["lyap_rhs_fro"]))
     return out
+
+
+def _newton_auto_shifts(ctx, d, calE, bmat, wmat, z0, mtxoldb):
+    """``ms='auto'`` of the Newton iteration: one list for every Newton step of the call, generated on the first
+    step's Lyapunov operator ``cal A - (K_0 - old) B^T`` with right-hand side ``[W, K_0]``, ``K_0 = cal E Z_0 Z_0^T B``
+    (just ``W`` and ``cal A + old B^T`` without ``z0``)."""
+    B, W = _dense(_host(bmat)), _dense(_host(wmat))
+    K0 = None if z0 is None else np.asarray(calE @ (_dense(_host(z0)) @ (_dense(_host(z0)).T @ B)))
+    U = None
+    if K0 is not None:
+        U = K0.copy()
+    if mtxoldb is not None:
+        old = _dense(_host(mtxoldb))
+        U = -old if U is None else U - old
+    rhs = W if K0 is None else np.hstack([W, K0])
+    if U is not None:
+        ctx.set_lowrank(U, B)
+    try:
+        return _auto_shifts(ctx, d, rhs)
+    finally:
+        ctx.set_lowrank(None, None)
 
 
 def compress_Zsvd(Z, thresh=None, k=None, shplot=False):

@@ -248,6 +248,8 @@ struct Switches {
   bool blocks16 = true;       // RICADI_BLOCKS16=0: the sweeps apply the FP32 copies of the per-shift blocks
   bool rowwave = true;        // RICADI_ROWWAVE=0: the restriction through the 16-lanes-per-row CSR kernel
   bool mid32 = true;          // RICADI_MID32=0: the velocity part between the sweeps of a cycle stays an FP64 panel
+  bool coarse_pipe = true;    // RICADI_COARSE_PIPE=0: the coarse apply on the row-major coarse residual and the first
+                              // sweep with its loads in one round (the forms before the pipelined kernels)
   bool lowsync = true;        // RICADI_ARNOLDI=cgs2: the three-pass CGS2 Arnoldi on the hot path instead of the
                               // one-reduction form
 };

@@ -249,10 +249,17 @@ struct Seg2 {
 // y = A x for a CSR matrix with LONG rows (the restriction: one row per aggregate), one wave per row
 // (spmm_rowwave_kernel); x FP64 or FP16-stored (x16), panels of m = 16 columns (leading dimension 16), group strides
 // gsx / gsy.  spmm_rowwave_pays: rows long enough on average (>= 32 entries) for it to beat the 16-lane-per-row kernel.
+// kb: y (the coarse residual) in the k-blocked layout of rckb_index, for launch_dense_apply_kb.
 bool spmm_rowwave_pays(int nrows, size_t nnz);
 void launch_spmm_rowwave(hipStream_t st, const GroupTab& gt, int nrows, const int* rp, const int* ci,
                          const GroupPtrs& vals, const double* x, const _Float16* x16, size_t gsx, double* y, size_t gsy,
-                         int m);
+                         int m, bool kb = false);
+// The k x 16 coarse residual in the k-blocked layout: the rows below k4 = k & ~3 in groups of four, entry (j, c) at
+// ((j >> 2) * 16 + c) * 4 + (j & 3), so that the four values a lane of the coarse apply feeds to four MFMAs are 32
+// contiguous bytes; the last k - k4 rows row-major where they always are.  Same k * 16 doubles.
+__host__ __device__ inline size_t rckb_index(int j, int c, int k) {
+  return j < (k & ~3) ? ((size_t)(j >> 2) * 16 + c) * 4 + (j & 3) : (size_t)j * 16 + c;
+}
 
 // ---- kernel launchers (ricadi_kernels.hip) ---------------------------------
 // The *_b launchers are the batched forms (GroupTab + group strides `gs*`, in
@@ -340,6 +347,10 @@ void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, cons
 // FP32-stored inverses (leading dimension ldf = k rounded up to 4; bs x bs blocks)
 void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, const GroupPtrsF& Einv,
                           int ldf, const double* rc, double* ec);
+// The same product on the FP32 tile-major inverse for m = 16 with rc in the k-blocked layout (rckb_index); ec
+// row-major as above.
+void launch_dense_apply_kb(hipStream_t st, const GroupTab& gt, int k, const GroupPtrsF& Einv, const double* rc,
+                           double* ec);
 // rectangular block sweep  out[rows_b] (-)= mats[b] (bs x ks) * in[irows_b]  (+ fused prolongation)
 bool block_apply_rect_ok(int bs, int ks);
 template <class T>
@@ -430,8 +441,10 @@ void launch_to_bf16(hipStream_t st, size_t n, const double* src, uint16_t* dst);
 // The hot-shape sweeps (32-row blocks, 16 columns, fixed-stride records in pa.bmeta) on BF16-stored blocks: same
 // contracts as launch_block_apply2_b / launch_block_apply_rect_b / launch_pressure_step_b with the FP32 panel; return
 // false (nothing launched) when the shape is not the hot one.
+// pipe: the first sweep with its second segment's loads in flight behind the first segment's MFMAs (block_two32_kernel)
 bool launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const GroupPtrsH& m1, const Seg2& s1,
-                          const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa);
+                          const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa,
+                          bool pipe = false);
 bool launch_block_rect32_h(hipStream_t st, const GroupTab& gt, int ks, int nblocks, const GroupPtrsH& mats,
                            const double* in, size_t gsi, double* out, size_t gso, int subtract, const ProlongArgs& pa);
 void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,

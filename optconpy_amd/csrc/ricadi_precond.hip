@@ -333,7 +333,10 @@ __global__ __launch_bounds__(256) void block_rect32_kernel(
 }
 
 // first sweep:  out[rows_b] = M1_b * in1[rows_b] - M2_b * in2[list2_b]   (block_apply2_kernel for the hot shape)
-template <int K2, class T, bool H1>
+// PIPE: the loads are issued segment by segment -- the first segment's gathers and tiles, then the second's -- and the
+// second segment's gathers are pinned only behind the first segment's MFMAs, so that those 16 MFMAs run while the
+// second segment's loads are in flight (else: the whole second segment lands before the first MFMA).
+template <int K2, class T, bool H1, bool PIPE = false>
 __global__ __launch_bounds__(256) void block_two32_kernel(
     GroupTab gt, int nblocks, const int* __restrict__ meta, int mstride, int in_off, GroupPtrsT<T> m1s, Seg2 s1,
     GroupPtrsT<T> m2s, Seg2 s2, double* __restrict__ out, size_t gso, ProlongArgs pa) {
@@ -377,22 +380,30 @@ __global__ __launch_bounds__(256) void block_two32_kernel(
       if (H1) h1[kc][s4] = ld_off(in1h, (unsigned)(r1[kc][s4] * 16 + r) * 2u);
       else x1[kc][s4] = ld_off(in1, (unsigned)(r1[kc][s4] * 16 + r) * 8u);
     }
+  auto load_seg2 = [&]() {
 #pragma unroll
-  for (int kc = 0; kc < N2; ++kc)
+    for (int kc = 0; kc < N2; ++kc)
 #pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) x2[kc][s4] = ld_off(in2, (unsigned)(r2[kc][s4] * 16 + r) * 8u);
+      for (int s4 = 0; s4 < 4; ++s4) x2[kc][s4] = ld_off(in2, (unsigned)(r2[kc][s4] * 16 + r) * 8u);
+  };
+  // pinned (see block_rect32_kernel): the second segment's gathers are used under a wave-uniform condition
+  auto pin_seg2 = [&]() {
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
+    for (int kc = 0; kc < N2; ++kc)
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) asm volatile("" : "+v"(x2[kc][s4]));
+  };
+  if (!PIPE) load_seg2();
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int kc = 0; kc < 2; ++kc) a1[t][kc] = Raw4<T>::load(M1 + (16 * t + r) * 32 + kc * 16 + 4 * q);
+  if (PIPE) load_seg2();
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int kc = 0; kc < N2; ++kc) a2[t][kc] = Raw4<T>::load(M2 + (16 * t + r) * K2 + kc * 16 + 4 * q);
-  }
-  // pinned (see block_rect32_kernel): the second segment's gathers are used under a wave-uniform condition
-#pragma unroll
-  for (int kc = 0; kc < N2; ++kc)
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) asm volatile("" : "+v"(x2[kc][s4]));
+  if (!PIPE) pin_seg2();
   __builtin_amdgcn_sched_barrier(0);
   d4 acc[2];
   acc[0] = acc[1] = (d4){0.0, 0.0, 0.0, 0.0};
@@ -411,6 +422,11 @@ __global__ __launch_bounds__(256) void block_two32_kernel(
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[s4], xm[s4], acc[t], 0, 0, 0);
     }
+  }
+  if (PIPE) {
+    __builtin_amdgcn_sched_barrier(0);
+    pin_seg2();
+    __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
   for (int kc = 0; kc < N2; ++kc) {
@@ -1194,6 +1210,91 @@ void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, cons
   (void)ldf;   // tile-major storage (launch_to_f32_tiled)
   dense_apply_tiled_launch(st, gt, k, m, Einv, rc, ec);
 }
+// The coarse apply for m = 16 on the k-blocked coarse residual (rckb_index), software-pipelined.  Per 16-row chunk
+// a lane needs one 16-byte load of the inverse tile and, from rc, the 32 contiguous bytes of its four k-values (two
+// 16-byte loads where the row-major panel took four 8-byte gathers 128 B apart).  The chunks of a wave alternate
+// between two register sets: the loads of chunk c + 1 are in flight while chunk c is converted and multiplied, and
+// the two sets feed two accumulators, so that the MFMA chains of consecutive chunks do not wait on each other.
+// Workgroups take (group, row tile) pairs in an XCD-contiguous order (speed only): the dispatcher deals consecutive
+// workgroups round-robin over the 8 XCDs, so in launch order every XCD's L2 re-read the residuals of all G groups;
+// here each XCD walks a contiguous run of about G / 8 groups.
+template <class T>
+__global__ __launch_bounds__(512) void dense_apply_pipe_kernel(GroupTab gt, int k, GroupPtrsT<T> Einvs,
+                                                               const double* __restrict__ rc,
+                                                               double* __restrict__ ec) {
+  __shared__ double red[8][16][17];
+  const int kp = (k + 15) / 16;
+  const int nwg = gridDim.x, L = blockIdx.x;
+  const int xcd = L & 7, base = nwg >> 3, extra = nwg & 7;
+  const int pair = xcd * base + min(xcd, extra) + (L >> 3);   // a bijection of [0, nwg)
+  const int it = pair % kp, grp = gt.gid[pair / kp];
+  const T* __restrict__ Einv = Einvs.p[grp];
+  rc += (size_t)grp * k * 16;
+  ec += (size_t)grp * k * 16;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const int per = (kp + 7) / 8;
+  const int ch0 = w * per, ch1 = min(kp, ch0 + per);
+  // chunks below cf lie inside the k-blocked rows (k4 = k & ~3): no masks, no tail rows
+  const int cf = min(ch1, (k & ~3) >> 4);
+  const T* __restrict__ tiles = Einv + (size_t)it * kp * 256 + (size_t)r * 16 + 4 * q;
+  const double* __restrict__ rcl = rc + ((size_t)q * 16 + r) * 4;
+  auto fetch = [&](int ch, float4& a, double2& b0, double2& b1) {
+    a = *reinterpret_cast<const float4*>(tiles + (size_t)ch * 256);
+    const double2* p = reinterpret_cast<const double2*>(rcl + (size_t)ch * 256);
+    b0 = p[0];
+    b1 = p[1];
+  };
+  auto mma = [&](const float4& a, const double2& b0, const double2& b1, d4v& acc) {
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.x, b0.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.y, b0.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.z, b1.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.w, b1.y, acc, 0, 0, 0);
+  };
+  d4v acc0 = (d4v){0.0, 0.0, 0.0, 0.0}, acc1 = acc0;
+  float4 aA, aB;
+  double2 bA0, bA1, bB0, bB1;
+  int ch = ch0;
+  if (ch < cf) fetch(ch, aA, bA0, bA1);
+  for (; ch + 1 < cf; ch += 2) {
+    fetch(ch + 1, aB, bB0, bB1);
+    __builtin_amdgcn_sched_barrier(0);
+    mma(aA, bA0, bA1, acc0);
+    fetch(min(ch + 2, cf - 1), aA, bA0, bA1);   // the last chunk once more where the wave has no next one
+    __builtin_amdgcn_sched_barrier(0);
+    mma(aB, bB0, bB1, acc1);
+  }
+  if (ch < cf) {
+    mma(aA, bA0, bA1, acc0);
+    ++ch;
+  }
+  if (ch < ch1) {
+    // the last chunk of the matrix, partly beyond k4: per-value addresses and masks
+    const int j0 = ch * 16 + 4 * q;
+    double b[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) b[t] = j0 + t < k ? rc[rckb_index(j0 + t, r, k)] : 0.0;
+    aA = *reinterpret_cast<const float4*>(tiles + (size_t)ch * 256);
+    mma(aA, make_double2(b[0], b[1]), make_double2(b[2], b[3]), acc1);
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) red[w][q + 4 * e][r] = acc0[e] + acc1[e];
+  __syncthreads();
+  if (threadIdx.x < 256) {
+    const int rr = threadIdx.x >> 4, cc = threadIdx.x & 15;
+    double sum = 0.0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) sum += red[t][rr][cc];
+    const int row = it * 16 + rr;
+    if (row < k) ec[(size_t)row * 16 + cc] = sum;
+  }
+}
+void launch_dense_apply_kb(hipStream_t st, const GroupTab& gt, int k, const GroupPtrsF& Einv, const double* rc,
+                           double* ec) {
+  if (k <= 0 || gt.ng <= 0) return;
+  const int kp = (k + 15) / 16;
+  hipLaunchKernelGGL((dense_apply_pipe_kernel<float>), dim3(kp * gt.ng), dim3(512), 0, st, gt, k, Einv, rc, ec);
+}
 // dst = FP32 copy of the k x k row-major src in 16 x 16 tile-major layout, zero padded
 __global__ void to_f32_tiled_kernel(int k, const double* __restrict__ src, float* __restrict__ dst) {
   const int kp = (k + 15) / 16;
@@ -1544,17 +1645,21 @@ void launch_to_bf16(hipStream_t st, size_t n, const double* src, uint16_t* dst) 
   hipLaunchKernelGGL(to_bf16_kernel, dim3(grid), dim3(256), 0, st, n, src, dst);
 }
 bool launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const GroupPtrsH& m1, const Seg2& s1,
-                          const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa) {
+                          const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa,
+                          bool pipe) {
   if (nblocks <= 0 || gt.ng <= 0) return true;
   if (!(pa.bmeta && !pa.aggof && (s2.kstride == 32 || s2.kstride == 64) &&
         std::max(std::max(gso, s1.gs), s2.gs) * 8 < ((size_t)1 << 32)))
     return false;
   dim3 grid((nblocks + 3) / 4, 1, gt.ng), block(256);
-#define RICADI_TWO32(K, H)                                                                                         \
-  hipLaunchKernelGGL((block_two32_kernel<K, uint16_t, H>), grid, block, 0, st, gt, nblocks, pa.bmeta, pa.bm_stride, \
+#define RICADI_TWO32(K, H, P)                                                                                         \
+  hipLaunchKernelGGL((block_two32_kernel<K, uint16_t, H, P>), grid, block, 0, st, gt, nblocks, pa.bmeta, pa.bm_stride, \
                      pa.bm_in, m1, s1, m2, s2, out, gso, pa)
-  if (s2.kstride == 32) { if (s1.in16) RICADI_TWO32(32, true); else RICADI_TWO32(32, false); }
-  else { if (s1.in16) RICADI_TWO32(64, true); else RICADI_TWO32(64, false); }
+#define RICADI_TWO32_H(K, P) \
+  if (s1.in16) RICADI_TWO32(K, true, P); else RICADI_TWO32(K, false, P)
+  if (pipe) { if (s2.kstride == 32) RICADI_TWO32_H(32, true); else RICADI_TWO32_H(64, true); }
+  else { if (s2.kstride == 32) RICADI_TWO32_H(32, false); else RICADI_TWO32_H(64, false); }
+#undef RICADI_TWO32_H
 #undef RICADI_TWO32
   return true;
 }

@@ -214,8 +214,8 @@ __device__ __forceinline__ double rw_dpp(double v) {
 // one or four gather instructions, where the 16-lanes-per-row form issues 16 two-byte gathers per 16 entries and runs
 // at the rate of the address path (20 cycles per gather instruction and CU at cfg2), not of the bytes.  The next step's
 // (index, value) pair travels during the current gather; the 32 slots of a half are summed by four DPP exchanges and
-// one cross-row shuffle.  m = 16 only.
-template <class XT>
+// one cross-row shuffle.  m = 16 only.  KB: y in the k-blocked layout of the coarse residual (rckb_index).
+template <class XT, bool KB>
 __global__ __launch_bounds__(256) void spmm_rowwave_kernel(
     GroupTab gt, int nrows, const int* __restrict__ rp, const int* __restrict__ ci, GroupPtrs vals,
     const XT* __restrict__ x, size_t gsx, double* __restrict__ y, size_t gsy) {
@@ -292,7 +292,13 @@ __global__ __launch_bounds__(256) void spmm_rowwave_kernel(
     v += __shfl_xor(v, 16, 64);
     acc[t] = v;
   }
-  if (e == 0) {
+  if (KB && row < (nrows & ~3)) {
+    // eight lanes of a half write one column each (8-byte stores 32 B apart)
+    double v = acc[0];
+#pragma unroll
+    for (int t = 1; t < 8; ++t) v = e == t ? acc[t] : v;
+    if (e < 8) y[rckb_index(row, h * 8 + e, nrows)] = v;
+  } else if (e == 0) {
     double2* o = reinterpret_cast<double2*>(y + (size_t)row * 16 + h * 8);
     o[0] = make_double2(acc[0], acc[1]);
     o[1] = make_double2(acc[2], acc[3]);
@@ -303,13 +309,16 @@ __global__ __launch_bounds__(256) void spmm_rowwave_kernel(
 bool spmm_rowwave_pays(int nrows, size_t nnz) { return nrows > 0 && nnz >= (size_t)32 * nrows; }
 void launch_spmm_rowwave(hipStream_t st, const GroupTab& gt, int nrows, const int* rp, const int* ci,
                          const GroupPtrs& vals, const double* x, const _Float16* x16, size_t gsx, double* y, size_t gsy,
-                         int m) {
+                         int m, bool kb) {
   if (nrows <= 0 || m != 16 || gt.ng <= 0) return;
   dim3 grid((nrows + 3) / 4, 1, gt.ng), block(256);
-  if (x16)
-    hipLaunchKernelGGL((spmm_rowwave_kernel<_Float16>), grid, block, 0, st, gt, nrows, rp, ci, vals, x16, gsx, y, gsy);
-  else
-    hipLaunchKernelGGL((spmm_rowwave_kernel<double>), grid, block, 0, st, gt, nrows, rp, ci, vals, x, gsx, y, gsy);
+#define RW_LAUNCH(XT, KB, X) \
+  hipLaunchKernelGGL((spmm_rowwave_kernel<XT, KB>), grid, block, 0, st, gt, nrows, rp, ci, vals, X, gsx, y, gsy)
+  if (x16 && kb) RW_LAUNCH(_Float16, true, x16);
+  else if (x16) RW_LAUNCH(_Float16, false, x16);
+  else if (kb) RW_LAUNCH(double, true, x);
+  else RW_LAUNCH(double, false, x);
+#undef RW_LAUNCH
 }
 
 // ---------------------------------------------------------------------------

@@ -113,6 +113,7 @@ static Switches read_switches() {
   s.blocks16 = !off("RICADI_BLOCKS16");
   s.rowwave = !off("RICADI_ROWWAVE");
   s.mid32 = !off("RICADI_MID32");
+  s.coarse_pipe = !off("RICADI_COARSE_PIPE");
   if (const char* e = getenv("RICADI_ARNOLDI")) s.lowsync = strcmp(e, "cgs2") != 0;
   return s;
 }

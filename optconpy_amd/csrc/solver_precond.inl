@@ -175,9 +175,21 @@ static void block_sweep(ricadi_ctx* c, const Batch& bt, bool pressure, const dou
   if (c->precond32) sweep(pressure ? bt.bpinvf : bt.bvinvf);
   else sweep(pressure ? bt.bpinv : bt.bvinv);
 }
+// Does the restriction run one wave per row (spmm_rowwave_kernel)?
+static bool restrict_rowwave(const ricadi_ctx* c, int m) {
+  const size_t rnnz = c->sa ? c->pt_ci.n : (size_t)c->n;
+  return m == 16 && c->sw.rowwave && spmm_rowwave_pays(c->kc, rnnz);
+}
+// ... and does it write rc k-blocked for the pipelined coarse apply (dense_apply_pipe_kernel)?  Only where the dense
+// inverse reads rc: a child level takes rc as its row-major input.
+static bool coarse_kb(const ricadi_ctx* c, int m) {
+  return c->sw.coarse_pipe && c->kc > 0 && !c->child && c->precond32 && restrict_rowwave(c, m);
+}
 // ec = E^-1 rc by the dense inverse of the coarse matrix (the last level)
 static void coarse_dense(ricadi_ctx* c, const Batch& bt) {
-  if (c->precond32)
+  if (coarse_kb(c, bt.m))
+    launch_dense_apply_kb(c->st, bt.tab, c->kc, bt.einvf, c->rc.p, c->ec.p);
+  else if (c->precond32)
     launch_dense_apply_b(c->st, bt.tab, c->kc, bt.m, bt.einvf, (c->kc + 3) & ~3, c->rc.p, c->ec.p);
   else
     launch_dense_apply_b(c->st, bt.tab, c->kc, bt.m, bt.einv, c->rc.p, c->ec.p);
@@ -255,14 +267,14 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
     const int* rci = c->sa ? c->pt_ci.p : c->agg_rows.p;
     const GroupPtrs rvals = c->sa ? same_ptr((const double*)c->pt_v.p) : ones;
     if (c->sa && !folded) throw HipError{"smoothed aggregation needs the folded preconditioner cycle"};
-    const size_t rnnz = c->sa ? c->pt_ci.n : (size_t)c->n;
-    const bool rowwave = m == 16 && c->sw.rowwave && spmm_rowwave_pays(c->kc, rnnz);
+    const bool rowwave = restrict_rowwave(c, m);
     form |= (r16 ? RICADI_PCF_H16 : 0) | (folded ? RICADI_PCF_FOLDED : 0) |
             ((rowwave ? 1 : r16 ? 2 : 3) << RICADI_PCF_RESTRICT_SHIFT) |
             ((c->child ? 1 : 2) << RICADI_PCF_COARSE_SHIFT);
     if (!on(0)) {
     } else if (rowwave)
-      launch_spmm_rowwave(st, gt, c->kc, rrp, rci, rvals, r16 ? nullptr : r, r16, gsr, c->rc.p, bt.gsc, m);
+      launch_spmm_rowwave(st, gt, c->kc, rrp, rci, rvals, r16 ? nullptr : r, r16, gsr, c->rc.p, bt.gsc, m,
+                          coarse_kb(c, m));
     else if (r16)
       launch_spmm_h(st, gt, c->kc, rrp, rci, rvals, nullptr, r16, m, gsr, c->rc.p, m, bt.gsc,
                     nullptr, 0, 0, 1.0, 0.0, m, 16);
@@ -341,7 +353,7 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_
       fpa.bm_ni = 2;
     }
     form |= (unsigned)c->ady_ks << RICADI_PCF_TWO_KS_SHIFT;
-    if (b16 && launch_block_two32_h(st, gt, c->nbv, bt.bvinvh, s1, bt.adymh, s2, z, bt.gs, fpa)) {
+    if (b16 && launch_block_two32_h(st, gt, c->nbv, bt.bvinvh, s1, bt.adymh, s2, z, bt.gs, fpa, c->sw.coarse_pipe)) {
       form |= 1 << RICADI_PCF_FIRST_SHIFT;
     } else {
       form |= 2 << RICADI_PCF_FIRST_SHIFT;

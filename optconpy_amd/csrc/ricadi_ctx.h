@@ -328,7 +328,6 @@ struct ricadi_ctx {
   bool ms_ok = false;         // the operator's tiles allow the multi-shift kernel (its value arrays exist)
   int w32_last = -1;          // the last operator launch of an iteration / timing class wrote the FP32 panel (1) or FP64 (0)
   int mid32_last = -1;        // what the last preconditioner application did (1 FP32 panel, 0 FP64; -1 none yet)
-  int pc_form_last = -1;      // ... and the branch each of its stages took (RICADI_PCF_* bits; -1 none yet)
   // low rank
   int q = 0;
   DArr<double> U, V, lrc, scratch;
@@ -403,7 +402,6 @@ struct ricadi_ctx {
   // stats
   long total_iters = 0, total_solves = 0;
   long escalations = 0;       // solves repeated with wider storage of basis / preconditioner (safety net)
-  int pc_stage = -1;          // >= 0: precond_apply issues only that stage (ricadi_time_kernel_dev)
   // wall-clock split of the drivers (sw.timing prints it per Newton step; the stream is
   // drained at the section ends only in that mode)
   double t_setup = 0, t_solve = 0, t_recomb = 0, t_compress = 0, t_updnorm = 0, t_proj = 0, t_gain = 0;

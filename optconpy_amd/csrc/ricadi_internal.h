@@ -439,13 +439,17 @@ void launch_project_lowrank(hipStream_t st, int k, int q, const double* QU, cons
 // dst (BF16 bit patterns, round to nearest even) = src (FP64), n entries
 void launch_to_bf16(hipStream_t st, size_t n, const double* src, uint16_t* dst);
 // The hot-shape sweeps (32-row blocks, 16 columns, fixed-stride records in pa.bmeta) on BF16-stored blocks: same
-// contracts as launch_block_apply2_b / launch_block_apply_rect_b / launch_pressure_step_b with the FP32 panel; return
-// false (nothing launched) when the shape is not the hot one.
+// contracts as launch_block_apply2_b / launch_block_apply_rect_b / launch_pressure_step_b with the FP32 panel.  The
+// two velocity sweeps take only the shapes their predicate admits: padded width ks (s2.kstride) of 32 or 64, group
+// strides that fit 32-bit byte offsets, and for the rectangles an FP32 intermediate (old32) only with its panel; the
+// two-term one adds no coarse correction (pa.aggof unset).
 // pipe: the first sweep with its second segment's loads in flight behind the first segment's MFMAs (block_two32_kernel)
-bool launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const GroupPtrsH& m1, const Seg2& s1,
+bool block_two32_h_ok(int ks, size_t gso, size_t gs1, size_t gs2);
+void launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const GroupPtrsH& m1, const Seg2& s1,
                           const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa,
                           bool pipe = false);
-bool launch_block_rect32_h(hipStream_t st, const GroupTab& gt, int ks, int nblocks, const GroupPtrsH& mats,
+bool block_rect32_h_ok(int ks, size_t gsi, size_t gso, bool old32, bool out32);
+void launch_block_rect32_h(hipStream_t st, const GroupTab& gt, int ks, int nblocks, const GroupPtrsH& mats,
                            const double* in, size_t gsi, double* out, size_t gso, int subtract, const ProlongArgs& pa);
 void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
                             const GroupPtrsH& inv, const int* jci, const double* jv, bool with_sy, const int* syci,

@@ -1644,13 +1644,13 @@ void launch_to_bf16(hipStream_t st, size_t n, const double* src, uint16_t* dst) 
   const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
   hipLaunchKernelGGL(to_bf16_kernel, dim3(grid), dim3(256), 0, st, n, src, dst);
 }
-bool launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const GroupPtrsH& m1, const Seg2& s1,
+bool block_two32_h_ok(int ks, size_t gso, size_t gs1, size_t gs2) {
+  return (ks == 32 || ks == 64) && std::max(std::max(gso, gs1), gs2) * 8 < ((size_t)1 << 32);
+}
+void launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const GroupPtrsH& m1, const Seg2& s1,
                           const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa,
                           bool pipe) {
-  if (nblocks <= 0 || gt.ng <= 0) return true;
-  if (!(pa.bmeta && !pa.aggof && (s2.kstride == 32 || s2.kstride == 64) &&
-        std::max(std::max(gso, s1.gs), s2.gs) * 8 < ((size_t)1 << 32)))
-    return false;
+  if (nblocks <= 0 || gt.ng <= 0) return;
   dim3 grid((nblocks + 3) / 4, 1, gt.ng), block(256);
 #define RICADI_TWO32(K, H, P)                                                                                         \
   hipLaunchKernelGGL((block_two32_kernel<K, uint16_t, H, P>), grid, block, 0, st, gt, nblocks, pa.bmeta, pa.bm_stride, \
@@ -1661,13 +1661,13 @@ bool launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const
   else { if (s2.kstride == 32) RICADI_TWO32_H(32, false); else RICADI_TWO32_H(64, false); }
 #undef RICADI_TWO32_H
 #undef RICADI_TWO32
-  return true;
 }
-bool launch_block_rect32_h(hipStream_t st, const GroupTab& gt, int ks, int nblocks, const GroupPtrsH& mats,
+bool block_rect32_h_ok(int ks, size_t gsi, size_t gso, bool old32, bool out32) {
+  return (ks == 32 || ks == 64) && std::max(gsi, gso) * 8 < ((size_t)1 << 32) && !(old32 && !out32);
+}
+void launch_block_rect32_h(hipStream_t st, const GroupTab& gt, int ks, int nblocks, const GroupPtrsH& mats,
                            const double* in, size_t gsi, double* out, size_t gso, int subtract, const ProlongArgs& pa) {
-  if (nblocks <= 0 || gt.ng <= 0) return true;
-  if (!(pa.bmeta && (ks == 32 || ks == 64) && std::max(gsi, gso) * 8 < ((size_t)1 << 32) && !(pa.old32 && !pa.out32)))
-    return false;
+  if (nblocks <= 0 || gt.ng <= 0) return;
   const int nwaves = nblocks + (pa.aggof ? (pa.nextra + 31) / 32 : 0);
   dim3 grid((nwaves + 3) / 4, 1, gt.ng), block(256);
 #define RICADI_RECT32(K, O)                                                                                         \
@@ -1676,7 +1676,6 @@ bool launch_block_rect32_h(hipStream_t st, const GroupTab& gt, int ks, int nbloc
   if (ks == 32) { if (pa.old32) RICADI_RECT32(32, true); else RICADI_RECT32(32, false); }
   else { if (pa.old32) RICADI_RECT32(64, true); else RICADI_RECT32(64, false); }
 #undef RICADI_RECT32
-  return true;
 }
 void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
                             const GroupPtrsH& inv, const int* jci, const double* jv, bool with_sy, const int* syci,

@@ -582,8 +582,8 @@ int ricadi_precond_apply_batch_dev(ricadi_ctx* c, int ng, const double* alphas, 
     HIPCHK(hipMemsetAsync(z32, 0xFF, sizeof(float) * vs, st));
     z = c->zv.p;
   }
-  c->pc_form_last = -1;
-  precond_apply(c, bt, r, gsr, z, z32, nm, f.x32, r16);
+  const CycleForm pf = cycle_form(c, m, bt.blocks16, gsr, f.x32, f.h16);
+  precond_apply(c, bt, pf, CycleIO{r, gsr, r16, z, z32, nm});
   if (f.x32) {
     std::vector<float> h32(nm);
     std::vector<double> h64(nm);
@@ -597,7 +597,7 @@ int ricadi_precond_apply_batch_dev(ricadi_ctx* c, int ng, const double* alphas, 
     }
   }
   HIPCHK(hipStreamSynchronize(st));
-  if (form_out) *form_out = c->pc_form_last;
+  if (form_out) *form_out = (int)pf.word();
   API_END
 }
 
@@ -632,8 +632,9 @@ int ricadi_precond_structure(ricadi_ctx* c, int level, int32_t* sizes_out, int32
   int kcv = 0;
   for (int i = 0; i < l->nv && kc > 0; ++i) kcv = std::max(kcv, agg[i] + 1);
   const int nnzp = kc <= 0 ? 0 : l->sa ? (int)ptci.size() : n;
+  const bool folds = cycle_form(l, 16, false, 0, false, false).folded;   // (whatever the panel width)
   const int32_t sz[16] = {l->nv, l->np, l->nbv, l->nbp, l->bs, kc, kcv, kc - kcv, l->sa ? 1 : 0, nnzp,
-                          l->child ? 1 : 0, precond_folds(l) ? 1 : 0, l->gt_ok ? 1 : 0, l->precond32 ? 1 : 0, 0, 0};
+                          l->child ? 1 : 0, folds ? 1 : 0, l->gt_ok ? 1 : 0, l->precond32 ? 1 : 0, 0, 0};
   std::copy(sz, sz + 16, sizes_out);
   down(bv_ptr, l->bv_ptr, (size_t)l->nbv + 1);
   down(bv_rows, l->bv_rows, (size_t)l->nv);
@@ -966,6 +967,9 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
   const _Float16* Vh = f.h16 ? reinterpret_cast<_Float16*>(c->basisf.p) : nullptr;
   // the operator's output and the Arnoldi passes on the FP32 panel where the iteration uses it
   c->w32_last = f.w32 ? 1 : 0;
+  // the preconditioner cycle on the workspace panels, in the form gmres_core decides
+  const CycleForm pf = cycle_form(c, m, bt.blocks16, nm, f.x32, f.h16);
+  const CycleIO io{c->wv.p, nm, Vh, c->zv.p, c->zbasisf.p, nm};
   auto launch = [&]() {
     switch (which) {
       case 0:
@@ -990,7 +994,7 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
             lb = t;
             lc = lc->child.get();
           }
-          coarse_dense(lc, lb);
+          pc_coarse(lc, lb, cycle_form(lc, m, lb.blocks16, 0, false, false), CycleIO());
         }
         break;
       case 4:
@@ -1012,19 +1016,17 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
         else arnoldi_update(c, f, bt, nvec, nullptr);
         break;
       case 8:
-        precond_apply(c, bt, c->wv.p, nm, c->zv.p, c->zbasisf.p, nm, f.x32, Vh);
+        precond_apply(c, bt, pf, io);
         break;
       case 9:
         if (c->kc <= 0) throw HipError{"no coarse level"};
         restrict_csr(c, bt, c->wv.p, nm);
         break;
-      case 10: case 11: case 12: case 13: case 14: case 15: case 16: {
-        // ONE stage of the preconditioner application, through the launcher precond_apply itself uses
-        Restore<int> keep(c->pc_stage);
-        c->pc_stage = which - 10;
-        precond_apply(c, bt, c->wv.p, nm, c->zv.p, c->zbasisf.p, nm, f.x32, Vh);
+      case 10: case 11: case 12: case 13: case 14: case 15: case 16:
+        // ONE stage of the preconditioner application, the function precond_apply itself calls
+        cycle_begin(c, pf, io);
+        cycle_stages[which - 10](c, bt, pf, io);
         break;
-      }
       default:
         throw HipError{"unknown kernel class"};
     }
@@ -1113,7 +1115,7 @@ int ricadi_setup_info(ricadi_ctx* c, int* out, int nout) {
   if (nout > 8) out[8] = lv;
   if (nout > 9) out[9] = lc->kc;
   // [10]: 1 if the iteration reads the current vector from the FP16 basis (no FP64 copy written), 16-column panels
-  if (nout > 10) out[10] = (c->has_op && basis16_default(c) && precond_folds(c)) ? 1 : 0;
+  if (nout > 10) out[10] = (c->has_op && cycle_form(c, 16, false, 0, false, basis16_default(c)).h16) ? 1 : 0;
   // [11], [12]: padded widths of the dense rectangles of the last / first velocity sweep (0: sweep not in that form);
   // [13]: pressure dofs per Schur block list entry count (np), [14]: nnz(J), [15]: nnz of the pressure rows of S*Y
   if (nout > 11) out[11] = c->gt_ok ? c->gt_ks : 0;

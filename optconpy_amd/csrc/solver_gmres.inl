@@ -159,6 +159,7 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
   const size_t gspart = (size_t)dots_num_blocks(n) * (restart + 2) * m;
   const int GM = G * m;
   const IterationForm f = iteration_form(c, m, G, lowrank);
+  const CycleForm pf = cycle_form(c, m, bt.blocks16, nm, f.x32, f.h16);
   const size_t h2buf = (size_t)(restart + 2) * c->wcols;        // doubles between the two second-pass buffers
   c->w32_last = f.w32 ? 1 : 0;
   _Float16* Vh = reinterpret_cast<_Float16*>(c->basisf.p);   // FP16 storage shares the FP32 buffer
@@ -282,7 +283,7 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
       // ... and the operator reads that stored FP32 copy (half the bytes of the x gathers; S Z_j = V H then
       // holds for exactly the vectors the correction uses), so the sweeps need not store the FP64 z at all
       float* zj = c->zbasisf.p + (size_t)j * vs;
-      precond_apply(c, bt, vj, nm, c->zv.p, zj, nm, f.x32, f.h16 ? Vh + (size_t)j * vs : nullptr);
+      precond_apply(c, bt, pf, CycleIO{vj, nm, f.h16 ? Vh + (size_t)j * vs : nullptr, c->zv.p, zj, nm});
       op_apply(c, bt, c->zv.p, nm, c->wv.p, lowrank, f.x32 ? zj : nullptr, f.w32 ? c->wv32.p : nullptr);
       // the residual estimates also go straight to a pinned host slot (read one
       // iteration later, behind the event below)

@@ -162,7 +162,7 @@ static void op_apply(ricadi_ctx* c, const Batch& bt, const double* x, size_t gsx
   }
   saddle_spmm(c, bt, x, gsx, nullptr, y, bt.gs, nullptr, 0, 1.0, 0.0, lr, x32, y32);
 }
-// ---- stages of the preconditioner that ricadi_time_kernel_dev also launches on their own
+// ---- kernels of the preconditioner that ricadi_time_kernel_dev also launches on their own
 // block-Jacobi sweep over the velocity (or pressure) blocks:  out[rows_b] (-)= inv_b in[rows_b]  (+ epilogue pa / cin)
 static void block_sweep(ricadi_ctx* c, const Batch& bt, bool pressure, const double* in, size_t gsi, double* out,
                         int subtract, const ProlongArgs& pa = ProlongArgs(), const CsrInArgs& cin = CsrInArgs()) {
@@ -174,25 +174,6 @@ static void block_sweep(ricadi_ctx* c, const Batch& bt, bool pressure, const dou
   };
   if (c->precond32) sweep(pressure ? bt.bpinvf : bt.bvinvf);
   else sweep(pressure ? bt.bpinv : bt.bvinv);
-}
-// Does the restriction run one wave per row (spmm_rowwave_kernel)?
-static bool restrict_rowwave(const ricadi_ctx* c, int m) {
-  const size_t rnnz = c->sa ? c->pt_ci.n : (size_t)c->n;
-  return m == 16 && c->sw.rowwave && spmm_rowwave_pays(c->kc, rnnz);
-}
-// ... and does it write rc k-blocked for the pipelined coarse apply (dense_apply_pipe_kernel)?  Only where the dense
-// inverse reads rc: a child level takes rc as its row-major input.
-static bool coarse_kb(const ricadi_ctx* c, int m) {
-  return c->sw.coarse_pipe && c->kc > 0 && !c->child && c->precond32 && restrict_rowwave(c, m);
-}
-// ec = E^-1 rc by the dense inverse of the coarse matrix (the last level)
-static void coarse_dense(ricadi_ctx* c, const Batch& bt) {
-  if (coarse_kb(c, bt.m))
-    launch_dense_apply_kb(c->st, bt.tab, c->kc, bt.einvf, c->rc.p, c->ec.p);
-  else if (c->precond32)
-    launch_dense_apply_b(c->st, bt.tab, c->kc, bt.m, bt.einvf, (c->kc + 3) & ~3, c->rc.p, c->ec.p);
-  else
-    launch_dense_apply_b(c->st, bt.tab, c->kc, bt.m, bt.einv, c->rc.p, c->ec.p);
 }
 // r2 = r - (S Y) ec through the tile kernels (c->syb_ok): the multi-shift one where it pays
 static bool sy_tiled_ms(const ricadi_ctx* c, const Batch& bt) {
@@ -217,251 +198,314 @@ static void restrict_csr(ricadi_ctx* c, const Batch& bt, const double* r, size_t
                 1.0, 0.0, bt.m);
 }
 
-// z = P^-1 r for every active group: multiplicative two-level, coarse correction
-// first, then one consistent SIMPLE block-Jacobi sweep on the updated residual.
-// r has group stride gsr; z lives in a workspace buffer (stride bt.gs).
-// z32 (optional, group stride gs32): FP32 copy of z, written by the sweeps that write z last.
-// only32: z itself need not be stored where the sweeps write the copy (the operator will read z32).
-// r16: the same residual panel as stored in FP16 (the current Krylov vector; group stride gsr); where the folded
-// path runs, its three readers of r take the 2-byte copy (exactly the same values) and r itself is not touched.
-static bool precond_folds(const ricadi_ctx* c) {
-  return c->kc > 0 && c->ady_ok && c->np > 0;
-}
-// Does the GMRES iteration hand the preconditioner the FP16-stored vector (else: the FP64 copy)?
-static bool precond_reads_h16(const ricadi_ctx* c, int m) {
-  return c->basis16 && m <= 16 && precond_folds(c);
-}
-static void precond_apply(ricadi_ctx* c, const Batch& bt, const double* r, size_t gsr, double* z,
-                          float* z32 = nullptr, size_t gs32 = 0, bool only32 = false,
-                          const _Float16* r16 = nullptr) {
-  hipStream_t st = c->st;
-  bool mirrored = false;
-  const int nv = c->nv, np = c->np, m = bt.m;
-  const GroupTab& gt = bt.tab;
-  const GroupPtrs ones = same_ptr(c->ones.p), jv = same_ptr(c->J.v.p), jtv = same_ptr(c->JT.v.p);
-  const double* rr = r;
-  size_t gsrr = gsr;
-  bool folded = false;
-  // ricadi_time_kernel_dev times one stage at a time through exactly these launchers (c->pc_stage >= 0)
-  auto on = [&](int stage) { return c->pc_stage < 0 || c->pc_stage == stage; };
-  // the pressure step -- pressure rows of r - (S Y) e, J product, Schur sweep -- as ONE launch (K2p) for
-  // 16-column panels (other widths: three launches)
-  const bool fusedp = np > 0 && m == 16 && c->bs == 32;
+// ---- the preconditioner cycle ------------------------------------------------------
+// z = P^-1 r for every active group: multiplicative two-level, coarse correction first, then one consistent SIMPLE
+// block-Jacobi sweep on the updated residual.
+// What one application launches, stage by stage: decided by cycle_form alone (gmres_core once per solve, beside its
+// IterationForm; ricadi_precond_apply_batch_dev, the kernel timers and setup_info ask it too).
+struct CycleForm {
+  // rc = Y^T r (P^T r): one wave per row (rc k-blocked for CO_DENSE_KB), 16-lane CSR on the FP16 / FP64 input
+  enum Restriction { RS_NONE, RS_ROWWAVE, RS_CSR16, RS_CSR64 } restriction = RS_NONE;
+  // ec = E^-1 rc: one cycle of the child level, or the last level's dense inverse (k-blocked pipelined, or tiled)
+  enum Coarse { CO_NONE, CO_CHILD, CO_DENSE_KB, CO_DENSE } coarse = CO_NONE;
+  // r2 = r - (S Y) ec before the sweeps: its pressure rows (folded cycle, split pressure step) or all of it (unfolded)
+  enum SyResidual { SY_NONE, SY_PROWS, SY_FULL } sy = SY_NONE;
+  // first velocity sweep: plain on r2, two-term with the coarse residual folded in, or that on BF16 blocks (pipe:
+  // its second segment's loads in flight behind the first segment's MFMAs)
+  enum First { FS_PLAIN, FS_TWO_TERM, FS_TWO32, FS_TWO32_PIPE } first = FS_PLAIN;
+  // pressure step: one launch (K2p) on BF16 / FP32-or-FP64 blocks, or J product and Schur sweep on their own
+  enum Pressure { PS_NONE, PS_FUSED16, PS_FUSED, PS_SPLIT } pressure = PS_NONE;
+  // last velocity sweep: dense rectangles on BF16 / FP32-or-FP64 blocks, or the J^T product formed row by row
+  enum Last { LS_NONE, LS_RECT32, LS_RECT, LS_CSR_IN } last = LS_NONE;
+  bool h16 = false;     // the input is read from the FP16-stored vector
+  bool x32 = false;     // only the FP32 copy of z is wanted (the operator reads it)
+  bool mid32 = false;   // the velocity part between the sweeps as an FP32 panel
+  bool b16 = false;     // BF16-stored per-shift blocks
+  bool folded = false;  // the coarse residual is formed inside the first sweep and the pressure step
+  int two_ks = 0, rect_ks = 0;   // padded widths of the two-term sweep's second block / of the rectangles (0: none)
+  // the form word of include/ricadi.h (restriction and last: their values are the 2-bit codes)
+  unsigned word() const {
+    unsigned w = (h16 ? RICADI_PCF_H16 : 0) | (x32 ? RICADI_PCF_X32 : 0) | (mid32 ? RICADI_PCF_MID32 : 0) |
+                 (b16 ? RICADI_PCF_B16 : 0) | (folded ? RICADI_PCF_FOLDED : 0);
+    w |= (unsigned)restriction << RICADI_PCF_RESTRICT_SHIFT | (unsigned)last << RICADI_PCF_LAST_SHIFT;
+    if (coarse != CO_NONE) w |= (coarse == CO_CHILD ? 1u : 2u) << RICADI_PCF_COARSE_SHIFT;
+    w |= (first == FS_PLAIN ? 3u : first == FS_TWO_TERM ? 2u : 1u) << RICADI_PCF_FIRST_SHIFT;
+    if (pressure != PS_NONE) w |= pressure == PS_SPLIT ? RICADI_PCF_PSPLIT : RICADI_PCF_PFUSED;
+    return w | (unsigned)two_ks << RICADI_PCF_TWO_KS_SHIFT | (unsigned)rect_ks << RICADI_PCF_RECT_KS_SHIFT;
+  }
+};
+// The cycle of level c on panels of width m.  blocks16: every group of the batch has BF16 blocks; gsr: group stride
+// of the input; out32: only the FP32 copy of z is wanted; in16: the input is the FP16-stored vector (read where the
+// cycle folds, on up to 16 columns).  The sweeps' operand precision is the level's (c->precond32).
+static CycleForm cycle_form(const ricadi_ctx* c, int m, bool blocks16, size_t gsr, bool out32, bool in16) {
+  CycleForm f;
+  const size_t gs = (size_t)c->n * m;
+  // the pressure step -- pressure rows of r - (S Y) e, J product, Schur sweep -- as ONE launch for 16-column panels
+  const bool fusedp = c->np > 0 && m == 16 && c->bs == 32;
+  f.folded = c->kc > 0 && c->ady_ok && c->np > 0;
+  f.h16 = in16 && f.folded && m <= 16;
+  f.x32 = out32;
   // The velocity part between the three sweeps (first sweep -> pressure step's J product -> last sweep) as an FP32
   // panel: where only the FP32 copy of z is wanted anyway (the operator reads Z_j as stored), the first sweep writes
   // the velocity rows of z32 itself, the pressure step gathers 64-B instead of 128-B rows and the last sweep updates
   // them in place.  Rounding the intermediate to FP32 perturbs the (flexible) preconditioner by what its FP32
   // inverses and the FP32-stored Z_j already do.
-  const bool mid32 = c->sw.mid32 && z32 && only32 && fusedp && precond_folds(c) && c->gt_ok && c->precond32;
-  c->mid32_last = mid32 ? 1 : 0;
+  f.mid32 = c->sw.mid32 && out32 && fusedp && f.folded && c->gt_ok && c->precond32;
   // ... and on BF16-stored blocks where every shift of the batch has them (record-driven sweeps only)
-  const bool b16 = mid32 && bt.blocks16 && c->sw_stride > 0 && c->bs == 32;
-  // the branch every stage takes (RICADI_PCF_* bits, ricadi_precond_apply_batch_dev): a host-side record, no launch
-  unsigned form = (z32 && only32 ? RICADI_PCF_X32 : 0) | (mid32 ? RICADI_PCF_MID32 : 0) | (b16 ? RICADI_PCF_B16 : 0);
+  f.b16 = f.mid32 && blocks16 && c->sw_stride > 0 && c->bs == 32;
   if (c->kc > 0) {
-    // restriction Y^T r = CSR product with unit values (aggregate lists as rows)
-    folded = precond_folds(c);
-    if (!folded || m > 16) r16 = nullptr;
-    // (smoothed aggregation: P^T r with the rows of P^T)
-    const int* rrp = c->sa ? c->pt_rp.p : c->agg_ptr.p;
-    const int* rci = c->sa ? c->pt_ci.p : c->agg_rows.p;
-    const GroupPtrs rvals = c->sa ? same_ptr((const double*)c->pt_v.p) : ones;
-    if (c->sa && !folded) throw HipError{"smoothed aggregation needs the folded preconditioner cycle"};
-    const bool rowwave = restrict_rowwave(c, m);
-    form |= (r16 ? RICADI_PCF_H16 : 0) | (folded ? RICADI_PCF_FOLDED : 0) |
-            ((rowwave ? 1 : r16 ? 2 : 3) << RICADI_PCF_RESTRICT_SHIFT) |
-            ((c->child ? 1 : 2) << RICADI_PCF_COARSE_SHIFT);
-    if (!on(0)) {
-    } else if (rowwave)
-      launch_spmm_rowwave(st, gt, c->kc, rrp, rci, rvals, r16 ? nullptr : r, r16, gsr, c->rc.p, bt.gsc, m,
-                          coarse_kb(c, m));
-    else if (r16)
-      launch_spmm_h(st, gt, c->kc, rrp, rci, rvals, nullptr, r16, m, gsr, c->rc.p, m, bt.gsc,
-                    nullptr, 0, 0, 1.0, 0.0, m, 16);
+    const bool rowwave = m == 16 && c->sw.rowwave && spmm_rowwave_pays(c->kc, c->sa ? c->pt_ci.n : (size_t)c->n);
+    f.restriction = rowwave ? f.RS_ROWWAVE : f.h16 ? f.RS_CSR16 : f.RS_CSR64;
+    // only where the dense inverse reads rc: a child level takes it as its row-major input
+    f.coarse = c->child ? f.CO_CHILD : c->sw.coarse_pipe && c->precond32 && rowwave ? f.CO_DENSE_KB : f.CO_DENSE;
+    f.sy = !f.folded ? f.SY_FULL : fusedp ? f.SY_NONE : f.SY_PROWS;
+  }
+  if (f.folded) {
+    f.two_ks = c->ady_ks;
+    f.first = !(f.b16 && block_two32_h_ok(c->ady_ks, gs, gsr, (size_t)c->kc * m)) ? f.FS_TWO_TERM
+              : c->sw.coarse_pipe ? f.FS_TWO32_PIPE : f.FS_TWO32;
+  }
+  if (c->np > 0) {
+    f.pressure = !fusedp ? f.PS_SPLIT : f.b16 ? f.PS_FUSED16 : f.PS_FUSED;
+    f.rect_ks = c->gt_ok ? c->gt_ks : 0;
+    f.last = !c->gt_ok ? f.LS_CSR_IN
+             : f.b16 && block_rect32_h_ok(c->gt_ks, (size_t)c->np * m, gs, f.mid32, out32) ? f.LS_RECT32 : f.LS_RECT;
+  }
+  return f;
+}
+// Does the GMRES iteration hand the preconditioner the FP16-stored vector (else: the FP64 copy)?
+static bool precond_reads_h16(const ricadi_ctx* c, int m) { return cycle_form(c, m, false, 0, false, c->basis16).h16; }
+
+// The panels of one application: input r (group stride gsr), or exactly where the form has h16 the same vector as
+// stored in FP16 (r16, same stride; r is then not touched); output z (stride bt.gs) and its optional FP32 copy z32
+// (stride gs32), written by the sweeps that write z last.
+struct CycleIO {
+  const double* r = nullptr;
+  size_t gsr = 0;
+  const _Float16* r16 = nullptr;
+  double* z = nullptr;
+  float* z32 = nullptr;
+  size_t gs32 = 0;
+};
+// the coarse correction Y ec, added to the velocity rows by the sweep that writes them last
+static ProlongArgs prolongation(const ricadi_ctx* c, const Batch& bt) {
+  ProlongArgs pa;
+  if (c->kc > 0) {
+    pa.aggof = c->aggof.p;
+    pa.ec = c->ec.p;
+    pa.gse = bt.gsc;
+  }
+  return pa;
+}
+// the fixed-stride records of the velocity sweeps, where there are
+static void sweep_records(const ricadi_ctx* c, int in, int ni, ProlongArgs& pa) {
+  if (c->sw_stride > 0 && c->bs == 32) {
+    pa.bmeta = c->sw_meta.p;
+    pa.bm_stride = c->sw_stride;
+    pa.bm_in = in;
+    pa.bm_ni = ni;
+  }
+}
+static void precond_apply(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io);
+
+// The stages in the order of the cycle and of the timer classes pc_restrict .. pc_rect (Context.TK 10 - 16).  A stage
+// the form does not have launches nothing.
+static void pc_restrict(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
+  const int* rrp = c->sa ? c->pt_rp.p : c->agg_ptr.p;
+  const int* rci = c->sa ? c->pt_ci.p : c->agg_rows.p;
+  const GroupPtrs rvals = same_ptr(c->sa ? (const double*)c->pt_v.p : c->ones.p);
+  if (f.restriction == f.RS_ROWWAVE)
+    launch_spmm_rowwave(c->st, bt.tab, c->kc, rrp, rci, rvals, io.r16 ? nullptr : io.r, io.r16, io.gsr, c->rc.p,
+                        bt.gsc, bt.m, f.coarse == f.CO_DENSE_KB);
+  else if (f.restriction == f.RS_CSR16)
+    launch_spmm_h(c->st, bt.tab, c->kc, rrp, rci, rvals, nullptr, io.r16, bt.m, io.gsr, c->rc.p, bt.m, bt.gsc,
+                  nullptr, 0, 0, 1.0, 0.0, bt.m, 16);
+  else if (f.restriction == f.RS_CSR64)
+    restrict_csr(c, bt, io.r, io.gsr);
+}
+static void pc_coarse(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO&) {
+  if (f.coarse == f.CO_CHILD) {
+    // coarse problem by one cycle of the child level's preconditioner (a fixed linear operator)
+    ricadi_ctx* ch = c->child.get();
+    Batch cb = *bt.sub;
+    cb.tab = bt.tab;
+    precond_apply(ch, cb, cycle_form(ch, cb.m, cb.blocks16, bt.gsc, false, false),
+                  CycleIO{c->rc.p, bt.gsc, nullptr, c->ec.p});
+  } else if (f.coarse == f.CO_DENSE_KB) {
+    launch_dense_apply_kb(c->st, bt.tab, c->kc, bt.einvf, c->rc.p, c->ec.p);
+  } else if (f.coarse == f.CO_DENSE && c->precond32) {
+    launch_dense_apply_b(c->st, bt.tab, c->kc, bt.m, bt.einvf, (c->kc + 3) & ~3, c->rc.p, c->ec.p);
+  } else if (f.coarse == f.CO_DENSE) {
+    launch_dense_apply_b(c->st, bt.tab, c->kc, bt.m, bt.einv, c->rc.p, c->ec.p);
+  }
+}
+static void pc_sy_prows(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
+  hipStream_t st = c->st;
+  const int nv = c->nv, m = bt.m;
+  if (f.sy == f.SY_PROWS) {
+    // only the PRESSURE rows of r - (S Y) ec are formed (short CSR product over np rows); the
+    // velocity rows ride inside the first velocity sweep (block_apply2_kernel)
+    if (io.r16)
+      launch_spmm_h(st, bt.tab, c->np, c->sy_rp.p + nv, c->sy_ci.p, bt.syval, c->ec.p, nullptr, m, bt.gsc,
+                    c->r2.p + (size_t)nv * m, m, bt.gs, io.r16 + (size_t)nv * m, m, io.gsr, -1.0, 1.0, m, c->sy_chunk);
     else
-      restrict_csr(c, bt, r, gsr);
-    if (!on(1)) {
-    } else if (c->child) {
-      // coarse problem by one cycle of the child level's preconditioner (a fixed linear operator)
-      Batch cb = *bt.sub;
-      cb.tab = gt;
-      precond_apply(c->child.get(), cb, c->rc.p, bt.gsc, c->ec.p);
-    } else {
-      coarse_dense(c, bt);
-    }
-    if (!on(2) || (fusedp && folded)) {
-    } else if (folded) {
-      // only the PRESSURE rows of r - (S Y) ec are formed (short CSR product over np rows); the
-      // velocity rows ride inside the first velocity sweep (block_apply2_kernel, below)
-      if (r16)
-        launch_spmm_h(st, gt, np, c->sy_rp.p + nv, c->sy_ci.p, bt.syval, c->ec.p, nullptr, m, bt.gsc,
-                      c->r2.p + (size_t)nv * m, m, bt.gs, r16 + (size_t)nv * m, m, gsr, -1.0, 1.0, m, c->sy_chunk);
-      else
-        launch_spmm_b(st, gt, np, c->sy_rp.p + nv, c->sy_ci.p, bt.syval, c->ec.p, m, bt.gsc, nullptr,
-                      c->r2.p + (size_t)nv * m, m, bt.gs, r + (size_t)nv * m, m, gsr, -1.0, 1.0, m, LowRankArgs(),
-                      c->sy_chunk);
-    } else {
-      // Residual after the coarse correction, r2 = r - (S Y) ec, with the prolongated
-      // operator (short rows over the L2-resident coarse vector) -- not a full saddle SpMM
-      // through the prolongation map.  (Forming the velocity rows of r2 inside the first
-      // velocity sweep instead, like the J^T product below, was measured slower: 249 vs
-      // 257 shift-solves/s -- 8 rows x 7.6 dependent gathers per lane.)
-      // Tile form: the aggregates a row block touches (a few dozen coarse rows) go to LDS once.
-      if (c->syb_ok && (sy_tiled_ms(c, bt) || spmm_blocked_lds_bytes(m, c->syb_max_cols, 0) <= (size_t)40 * 1024))
-        sy_residual_tiled(c, bt, r, gsr);
-      else
-        launch_spmm_b(st, gt, c->n, c->sy_rp.p, c->sy_ci.p, bt.syval, c->ec.p, m, bt.gsc, nullptr,
-                      c->r2.p, m, bt.gs, r, m, gsr, -1.0, 1.0, m, LowRankArgs(), c->sy_chunk);
-    }
-    rr = c->r2.p;
-    gsrr = bt.gs;
+      launch_spmm_b(st, bt.tab, c->np, c->sy_rp.p + nv, c->sy_ci.p, bt.syval, c->ec.p, m, bt.gsc, nullptr,
+                    c->r2.p + (size_t)nv * m, m, bt.gs, io.r + (size_t)nv * m, m, io.gsr, -1.0, 1.0, m, LowRankArgs(),
+                    c->sy_chunk);
+  } else if (f.sy == f.SY_FULL) {
+    // Residual after the coarse correction, r2 = r - (S Y) ec, with the prolongated
+    // operator (short rows over the L2-resident coarse vector) -- not a full saddle SpMM
+    // through the prolongation map.  (Forming the velocity rows of r2 inside the first
+    // velocity sweep instead, like the J^T product below, was measured slower: 249 vs
+    // 257 shift-solves/s -- 8 rows x 7.6 dependent gathers per lane.)
+    // Tile form: the aggregates a row block touches (a few dozen coarse rows) go to LDS once.
+    if (c->syb_ok && (sy_tiled_ms(c, bt) || spmm_blocked_lds_bytes(m, c->syb_max_cols, 0) <= (size_t)40 * 1024))
+      sy_residual_tiled(c, bt, io.r, io.gsr);
+    else
+      launch_spmm_b(st, bt.tab, c->n, c->sy_rp.p, c->sy_ci.p, bt.syval, c->ec.p, m, bt.gsc, nullptr, c->r2.p, m,
+                    bt.gs, io.r, m, io.gsr, -1.0, 1.0, m, LowRankArgs(), c->sy_chunk);
   }
-  // the LAST velocity sweep also adds the coarse correction Y ec to all of z
-  // (its surplus waves take the pressure rows)
-  ProlongArgs pro;
+}
+static void pc_two_term(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
+  const int m = bt.m;
+  if (f.first == f.FS_PLAIN) {
+    // on r2 (on r without a coarse level); without pressure rows this sweep writes z last
+    const bool r2 = c->kc > 0;
+    block_sweep(c, bt, false, r2 ? c->r2.p : io.r, r2 ? bt.gs : io.gsr, io.z, 0,
+                c->np == 0 ? prolongation(c, bt) : ProlongArgs());
+    return;
+  }
+  // z_v = Ahat^-1 r_v - (Ahat^-1 D) ec : first velocity sweep on the corrected residual without
+  // ever writing it
+  Seg2 s1, s2;
+  s1.kstride = c->bs;
+  s1.in = io.r16 ? nullptr : io.r;
+  s1.in16 = io.r16;
+  s1.gs = io.gsr;
+  s2.iptr = c->cy_ptr.p;
+  s2.irows = c->cy_cols.p;
+  s2.kstride = c->ady_ks;
+  s2.in = c->ec.p;
+  s2.gs = bt.gsc;
+  ProlongArgs pa;
+  if (f.mid32) {
+    pa.out32 = io.z32;
+    pa.gs32 = io.gs32;
+    pa.only32 = 1;
+  }
+  sweep_records(c, c->sw_in_two, 2, pa);
+  if (f.first == f.FS_TWO32 || f.first == f.FS_TWO32_PIPE)
+    launch_block_two32_h(c->st, bt.tab, c->nbv, bt.bvinvh, s1, bt.adymh, s2, io.z, bt.gs, pa,
+                         f.first == f.FS_TWO32_PIPE);
+  else if (c->precond32)
+    launch_block_apply2_b(c->st, bt.tab, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinvf, s1, bt.adymf, s2, io.z,
+                          m, bt.gs, m, pa);
+  else
+    launch_block_apply2_b(c->st, bt.tab, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinv, s1, bt.adym, s2, io.z,
+                          m, bt.gs, m, pa);
+}
+// t = J z_v - r_p (r_p of r2, or of r without a coarse level)
+static void pc_jprod(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
+  if (f.pressure != f.PS_SPLIT) return;
+  const int m = bt.m;
+  const bool r2 = c->kc > 0;
+  launch_spmm_b(c->st, bt.tab, c->np, c->J.rp.p, c->J.ci.p, same_ptr(c->J.v.p), io.z, m, bt.gs, nullptr, c->tp.p, m,
+                bt.gsp, (r2 ? c->r2.p : io.r) + (size_t)c->nv * m, m, r2 ? bt.gs : io.gsr, 1.0, -1.0, m);
+}
+static void pc_schur(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
+  if (f.pressure == f.PS_NONE) return;
+  const int nv = c->nv, m = bt.m;
+  const size_t off = (size_t)nv * m;
+  double* zp = io.z + off;
+  // Fused variant: the pressure sweep writes z_p already WITH its coarse part and keeps
+  // the plain z_p (the operand of the J^T product below) in tp -- in place: a wave
+  // reads its block's rows of tp before it writes them, blocks are disjoint.
+  ProlongArgs pa;
+  pa.out2 = c->tp.p;
+  pa.gs2 = bt.gsp;
+  if (io.z32) {
+    pa.out32 = io.z32 + off;
+    pa.gs32 = io.gs32;
+    pa.only32 = f.x32 && c->gt_ok;   // the rectangle sweep below completes the FP32 copy
+  }
   if (c->kc > 0) {
-    pro.aggof = c->aggof.p;
-    pro.ec = c->ec.p;
-    pro.gse = bt.gsc;
-    pro.row0 = nv;
-    pro.nextra = np;
+    pa.aggof = c->aggof.p + nv;
+    pa.ec = c->ec.p;
+    pa.gse = bt.gsc;
   }
-  if (!on(3)) {
-  } else if (folded) {
-    // z_v = Ahat^-1 r_v - (Ahat^-1 D) ec : first velocity sweep on the corrected residual without
-    // ever writing it
-    Seg2 s1, s2;
-    s1.kstride = c->bs;
-    s1.in = r16 ? nullptr : r;
-    s1.in16 = r16;
-    s1.gs = gsr;
-    s2.iptr = c->cy_ptr.p;
-    s2.irows = c->cy_cols.p;
-    s2.kstride = c->ady_ks;
-    s2.in = c->ec.p;
-    s2.gs = bt.gsc;
-    ProlongArgs fpa;
-    if (mid32) {
-      fpa.out32 = z32;
-      fpa.gs32 = gs32;
-      fpa.only32 = 1;
-    }
-    if (c->sw_stride > 0 && c->bs == 32) {
-      fpa.bmeta = c->sw_meta.p;
-      fpa.bm_stride = c->sw_stride;
-      fpa.bm_in = c->sw_in_two;
-      fpa.bm_ni = 2;
-    }
-    form |= (unsigned)c->ady_ks << RICADI_PCF_TWO_KS_SHIFT;
-    if (b16 && launch_block_two32_h(st, gt, c->nbv, bt.bvinvh, s1, bt.adymh, s2, z, bt.gs, fpa, c->sw.coarse_pipe)) {
-      form |= 1 << RICADI_PCF_FIRST_SHIFT;
-    } else {
-      form |= 2 << RICADI_PCF_FIRST_SHIFT;
-      if (c->precond32)
-        launch_block_apply2_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinvf, s1, bt.adymf, s2, z, m,
-                              bt.gs, m, fpa);
-      else
-        launch_block_apply2_b(st, gt, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinv, s1, bt.adym, s2, z, m,
-                              bt.gs, m, fpa);
-    }
-  } else {
-    form |= 3 << RICADI_PCF_FIRST_SHIFT;
-    block_sweep(c, bt, false, rr, gsrr, z, 0, np == 0 ? pro : ProlongArgs());
+  if (f.pressure == f.PS_SPLIT) {
+    block_sweep(c, bt, true, c->tp.p, bt.gsp, zp, 0, pa);
+    return;
   }
-  if (np > 0) {
-    form |= fusedp ? RICADI_PCF_PFUSED : RICADI_PCF_PSPLIT;
-    // t = J z_v - r_p
-    if (on(4) && !fusedp)
-      launch_spmm_b(st, gt, np, c->J.rp.p, c->J.ci.p, jv, z, m, bt.gs, nullptr, c->tp.p, m, bt.gsp,
-                    rr + (size_t)nv * m, m, gsrr, 1.0, -1.0, m);
-    double* zp = z + (size_t)nv * m;
-    // Fused variant: the pressure sweep writes z_p already WITH its coarse part and keeps
-    // the plain z_p (the operand of the J^T product below) in tp -- in place: a wave
-    // reads its block's rows of tp before it writes them, blocks are disjoint.
-    ProlongArgs ppro;
-    {
-      ppro.out2 = c->tp.p;
-      ppro.gs2 = bt.gsp;
-      if (z32) {
-        ppro.out32 = z32 + (size_t)nv * m;
-        ppro.gs32 = gs32;
-        ppro.only32 = only32 && c->gt_ok;   // the rectangle sweep below completes the FP32 copy
-      }
-      if (c->kc > 0) {
-        ppro.aggof = c->aggof.p + nv;
-        ppro.ec = c->ec.p;
-        ppro.gse = bt.gsc;
-      }
-    }
-    if (!on(5)) {
-    } else if (fusedp) {
-      // r_p: of the folded cycle the input vector itself (FP64 or FP16-stored) with the coarse term formed in
-      // the kernel; else the pressure rows of the corrected residual r2
-      const bool sy = folded;
-      const double* rp64 = sy ? (r16 ? nullptr : r + (size_t)nv * m) : rr + (size_t)nv * m;
-      const _Float16* rp16 = sy && r16 ? r16 + (size_t)nv * m : nullptr;
-      const size_t gsrp = sy ? gsr : gsrr;
-      if (b16)
-        launch_pressure_step_h(st, gt, c->nbp, c->ps_meta.p, bt.bpinvh, c->J.ci.p, c->J.v.p, sy, c->sy_ci.p, bt.syval,
-                               c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, ppro, z32, gs32);
-      else if (c->precond32)
-        launch_pressure_step_b(st, gt, c->nbp, c->ps_meta.p, bt.bpinvf, c->J.ci.p, c->J.v.p, z, bt.gs, sy, c->sy_ci.p,
-                               bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, ppro, mid32 ? z32 : nullptr,
-                               gs32);
-      else
-        launch_pressure_step_b(st, gt, c->nbp, c->ps_meta.p, bt.bpinv, c->J.ci.p, c->J.v.p, z, bt.gs, sy, c->sy_ci.p,
-                               bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, ppro);
-    } else {
-      block_sweep(c, bt, true, c->tp.p, bt.gsp, zp, 0, ppro);
-    }
-    // z_v -= Ahat^-1 (J^T z_p): the same block-Jacobi inverse as in the Schur blocks; the
-    // J^T product is formed inside the sweep, row by row as the blocks gather them
-    // (z_p is small and L2 resident), instead of through an intermediate panel
-    if (!on(6)) {
-    } else if (c->gt_ok) {
-      // z_v -= G z_p with the per-shift blocks G_b = Ahat_b^-1 J^T[rows_b, pcols_b] formed at setup
-      pro.nextra = 0;            // the pressure rows already carry their coarse part
-      pro.out32 = z32;
-      pro.gs32 = gs32;
-      pro.only32 = only32;
-      pro.old32 = mid32 ? 1 : 0;
-      if (c->sw_stride > 0 && c->bs == 32) {
-        pro.bmeta = c->sw_meta.p;
-        pro.bm_stride = c->sw_stride;
-        pro.bm_in = c->sw_in_rect;
-        pro.bm_ni = 1;
-      }
-      mirrored = true;
-      form |= (unsigned)c->gt_ks << RICADI_PCF_RECT_KS_SHIFT;
-      if (b16 && launch_block_rect32_h(st, gt, c->gt_ks, c->nbv, bt.gtmh, c->tp.p, bt.gsp, z, bt.gs, 1, pro)) {
-        form |= 1 << RICADI_PCF_LAST_SHIFT;
-      } else {
-        form |= 2 << RICADI_PCF_LAST_SHIFT;
-        if (c->precond32)
-          launch_block_apply_rect_b(st, gt, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
-                                    c->gt_cols.p, bt.gtmf, c->tp.p, m, bt.gsp, z, m, bt.gs, m, 1, pro);
-        else
-          launch_block_apply_rect_b(st, gt, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
-                                    c->gt_cols.p, bt.gtm, c->tp.p, m, bt.gsp, z, m, bt.gs, m, 1, pro);
-      }
-    } else {
-      // blocks that touch too many pressure dofs for the dense rectangles: the J^T product formed row by row inside
-      // the sweep (CsrInArgs)
-      CsrInArgs cin;
-      cin.rp = c->JT.rp.p;
-      cin.ci = c->JT.ci.p;
-      cin.v = jtv;
-      cin.src = c->tp.p;
-      cin.gss = bt.gsp;
-      pro.nextra = 0;          // the pressure rows already carry their coarse part
-      form |= 3 << RICADI_PCF_LAST_SHIFT;
-      block_sweep(c, bt, false, nullptr, 0, z, 1, pro, cin);
-    }
+  // r_p: of the folded cycle the input vector itself (FP64 or FP16-stored) with the coarse term formed in
+  // the kernel; else the pressure rows of the corrected residual r2 (of r without a coarse level)
+  const bool sy = f.folded, r2 = !sy && c->kc > 0;
+  const double* rp64 = io.r16 ? nullptr : (r2 ? c->r2.p : io.r) + off;
+  const _Float16* rp16 = io.r16 ? io.r16 + off : nullptr;
+  const size_t gsrp = r2 ? bt.gs : io.gsr;
+  if (f.pressure == f.PS_FUSED16)
+    launch_pressure_step_h(c->st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinvh, c->J.ci.p, c->J.v.p, sy, c->sy_ci.p,
+                           bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, pa, io.z32, io.gs32);
+  else if (c->precond32)
+    launch_pressure_step_b(c->st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinvf, c->J.ci.p, c->J.v.p, io.z, bt.gs, sy,
+                           c->sy_ci.p, bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, pa,
+                           f.mid32 ? io.z32 : nullptr, io.gs32);
+  else
+    launch_pressure_step_b(c->st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinv, c->J.ci.p, c->J.v.p, io.z, bt.gs, sy,
+                           c->sy_ci.p, bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, pa);
+}
+// z_v -= Ahat^-1 (J^T z_p): the same block-Jacobi inverse as in the Schur blocks; the
+// J^T product is formed inside the sweep, row by row as the blocks gather them
+// (z_p is small and L2 resident), instead of through an intermediate panel.  It adds the coarse correction Y ec
+// to the velocity rows of z (the pressure rows already carry theirs).
+static void pc_rect(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
+  if (f.last == f.LS_NONE) return;
+  const int m = bt.m;
+  ProlongArgs pa = prolongation(c, bt);
+  if (f.last == f.LS_CSR_IN) {
+    // blocks that touch too many pressure dofs for the dense rectangles: the J^T product formed row by row inside
+    // the sweep (CsrInArgs)
+    CsrInArgs cin;
+    cin.rp = c->JT.rp.p;
+    cin.ci = c->JT.ci.p;
+    cin.v = same_ptr(c->JT.v.p);
+    cin.src = c->tp.p;
+    cin.gss = bt.gsp;
+    block_sweep(c, bt, false, nullptr, 0, io.z, 1, pa, cin);
+    return;
   }
-  if (z32 && !mirrored && c->pc_stage < 0)
-    for (int i = 0; i < gt.ng; ++i)
-      launch_to_f32(st, c->n, m, z + (size_t)gt.gid[i] * bt.gs, m, z32 + (size_t)gt.gid[i] * gs32, m);
-  if (c->pc_stage < 0) c->pc_form_last = (int)form;
+  // z_v -= G z_p with the per-shift blocks G_b = Ahat_b^-1 J^T[rows_b, pcols_b] formed at setup
+  pa.out32 = io.z32;
+  pa.gs32 = io.gs32;
+  pa.only32 = f.x32;
+  pa.old32 = f.mid32 ? 1 : 0;
+  sweep_records(c, c->sw_in_rect, 1, pa);
+  if (f.last == f.LS_RECT32)
+    launch_block_rect32_h(c->st, bt.tab, c->gt_ks, c->nbv, bt.gtmh, c->tp.p, bt.gsp, io.z, bt.gs, 1, pa);
+  else if (c->precond32)
+    launch_block_apply_rect_b(c->st, bt.tab, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
+                              c->gt_cols.p, bt.gtmf, c->tp.p, m, bt.gsp, io.z, m, bt.gs, m, 1, pa);
+  else
+    launch_block_apply_rect_b(c->st, bt.tab, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
+                              c->gt_cols.p, bt.gtm, c->tp.p, m, bt.gsp, io.z, m, bt.gs, m, 1, pa);
+}
+using CycleStage = void (*)(ricadi_ctx*, const Batch&, const CycleForm&, const CycleIO&);
+static const CycleStage cycle_stages[] = {pc_restrict, pc_coarse, pc_sy_prows, pc_two_term,
+                                          pc_jprod,    pc_schur,  pc_rect};
+
+// what an application of the cycle, or of one of its stages, does first
+static void cycle_begin(ricadi_ctx* c, const CycleForm& f, const CycleIO& io) {
+  c->mid32_last = f.mid32 ? 1 : 0;
+  if (c->sa && !f.folded) throw HipError{"smoothed aggregation needs the folded preconditioner cycle"};
+  if (!io.r16 != !f.h16) throw HipError{"FP16-stored input where the cycle form does not read it, or none"};
+}
+static void precond_apply(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
+  cycle_begin(c, f, io);
+  for (CycleStage stage : cycle_stages) stage(c, bt, f, io);
+  if (io.z32 && f.last != f.LS_RECT32 && f.last != f.LS_RECT)   // (the rectangle sweeps write z32 themselves)
+    for (int i = 0; i < bt.tab.ng; ++i)
+      launch_to_f32(c->st, c->n, bt.m, io.z + (size_t)bt.tab.gid[i] * bt.gs, bt.m,
+                    io.z32 + (size_t)bt.tab.gid[i] * io.gs32, bt.m);
 }
 
 static void op_apply(ricadi_ctx* c, ShiftData* sd, const double* x, double* y, int m, bool lowrank) {
@@ -470,7 +514,7 @@ static void op_apply(ricadi_ctx* c, ShiftData* sd, const double* x, double* y, i
 }
 static void precond_apply(ricadi_ctx* c, ShiftData* sd, const double* r, double* z, int m) {
   const Batch bt = make_batch(c, sd, m);
-  precond_apply(c, bt, r, bt.gs, z);
+  precond_apply(c, bt, cycle_form(c, m, bt.blocks16, bt.gs, false, false), CycleIO{r, bt.gs, nullptr, z});
 }
 
 static void col_norms2(ricadi_ctx* c, const double* w, int nrows, int m, double* out) {

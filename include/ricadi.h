@@ -381,6 +381,13 @@ int ricadi_time_spmm_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas,
  * 3 first velocity sweep (two-term block sweep with the coarse residual folded in), 4 J product,
  * 5 Schur-complement sweep, 6 last velocity sweep (rectangle sweep with prolongation)             */
 #define RICADI_TK_PC_STAGE0 10
+/* One hot lockstep GMRES iteration (preconditioner, operator, Arnoldi passes of iteration nvec - 1; no convergence
+ * logic), averaged over `reps` iterations issued back to back: ITER all ng groups on the context stream, ITER_SPLIT
+ * the even and the odd group ids as two half-batches on two streams, forked from the context stream before the
+ * first iteration and joined back to it after the last (the solver's split, RICADI_SPLIT).  Result: wall time per
+ * iteration from HIP events.                                                                                     */
+#define RICADI_TK_ITER 17
+#define RICADI_TK_ITER_SPLIT 18
 int ricadi_time_kernel_dev(ricadi_ctx* ctx, int which, int ng, const double* alphas,
                            const double* betas, int m, int nvec, int reps,
                            double* ms_per_launch);

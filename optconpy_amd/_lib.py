@@ -681,7 +681,7 @@ class Context:
 
     TK = dict(spmm=0, block_v=1, block_p=2, coarse=3, spmm_sy=4, dots=5, update_dots=6, update=7,
               precond=8, restrict=9, pc_restrict=10, pc_coarse=11, pc_sy_prows=12, pc_two_term=13,
-              pc_jprod=14, pc_schur=15, pc_rect=16)
+              pc_jprod=14, pc_schur=15, pc_rect=16, iter=17, iter_split=18)
 
     def time_kernel_dev(self, which, alphas, betas, m, nvec=7, reps=100):
         """Milliseconds per launch of one hot-path kernel class (``Context.TK``) as the

@@ -194,6 +194,7 @@ struct ShiftData {
   // smw_w = S^-1 [U;0] (I - V^T S^-1 U)^-1, n x q
   DArr<double> smw_w;
   long smw_epoch = -1;
+  int last_iters = -1;        // iterations of this shift's last lockstep GMRES solve (gmres_core's split into halves)
   ShiftData* sub = nullptr;   // the same shift on the child level (multilevel preconditioner)
   // recycled solves (ricadi_set_recycle): y with S(alpha,beta) y = b for the right-hand side panels of
   // the context's ring that carry the same serial number; n x w each
@@ -252,6 +253,7 @@ struct Switches {
                               // sweep with its loads in one round (the forms before the pipelined kernels)
   bool lowsync = true;        // RICADI_ARNOLDI=cgs2: the three-pass CGS2 Arnoldi on the hot path instead of the
                               // one-reduction form
+  bool split = true;          // RICADI_SPLIT=0: the lockstep GMRES batch on one stream instead of two half-batches
 };
 
 }  // namespace ricadi
@@ -354,6 +356,11 @@ struct ricadi_ctx {
   DArr<double*> gj_ptrs;
   double* h_resid = nullptr;  // pinned, 4 slots of MAX_GROUPS*MAX_M: norms, rhs norms, two residual slots
   hipEvent_t ev_res[2] = {nullptr, nullptr};
+  // the second half-batch of the lockstep GMRES (half_stream; created on first use): its stream, the events of its
+  // one-iteration lag, and the fork / join with st
+  hipStream_t st_half = nullptr;
+  hipEvent_t ev_res_half[2] = {nullptr, nullptr};
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // factor
   DArr<double> Z;
   int zc = 0, zld = 0;
@@ -410,8 +417,13 @@ struct ricadi_ctx {
   ~ricadi_ctx() {
     if (h_resid) (void)hipHostFree(h_resid);
     if (xcomm && xcomm_owned) (void)ncclCommDestroy(xcomm);
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i) {
       if (ev_res[i]) (void)hipEventDestroy(ev_res[i]);
+      if (ev_res_half[i]) (void)hipEventDestroy(ev_res_half[i]);
+    }
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+    if (st_half) (void)hipStreamDestroy(st_half);
     child.reset();
     if (rb && !borrowed) rocblas_destroy_handle(rb);
     if (rb2) rocblas_destroy_handle(rb2);

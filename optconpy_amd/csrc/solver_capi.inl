@@ -115,6 +115,7 @@ static Switches read_switches() {
   s.mid32 = !off("RICADI_MID32");
   s.coarse_pipe = !off("RICADI_COARSE_PIPE");
   if (const char* e = getenv("RICADI_ARNOLDI")) s.lowsync = strcmp(e, "cgs2") != 0;
+  s.split = !off("RICADI_SPLIT");
   return s;
 }
 
@@ -1027,12 +1028,48 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
         cycle_begin(c, pf, io);
         cycle_stages[which - 10](c, bt, pf, io);
         break;
+      case RICADI_TK_ITER: case RICADI_TK_ITER_SPLIT:
+        break;   // (below)
       default:
         throw HipError{"unknown kernel class"};
     }
   };
-  launch();   // warm-up (code object load, caches)
-  *ms_per_launch = timed_ms(st, reps, launch);
+  if (which == RICADI_TK_ITER || which == RICADI_TK_ITER_SPLIT) {
+    // reps hot iterations j = nvec - 1 (no convergence logic): all groups on the context stream, or the even and the
+    // odd group ids as two halves on two streams, forked from it and joined back to it once around all reps
+    const bool two = which == RICADI_TK_ITER_SPLIT && ng >= 2;
+    Batch bh[2] = {bt, bt};
+    if (two) {
+      bh[1].st = half_stream(c);
+      std::vector<int> half[2];
+      for (int g = 0; g < ng; ++g) half[g & 1].push_back(g);
+      for (int h = 0; h < 2; ++h) {
+        bh[h].set(half[h]);
+        bh[h].ng_solve = ng;
+      }
+    }
+    auto iters = [&](int k) {
+      if (two) {
+        HIPCHK(hipEventRecord(c->ev_fork, st));
+        HIPCHK(hipStreamWaitEvent(bh[1].st, c->ev_fork, 0));
+      }
+      for (int i = 0; i < k; ++i) {
+        if (two)
+          for (int h = 0; h < 2; ++h) iteration_launches(c, f, pf, bh[h], nvec - 1, false, nullptr);
+        else
+          iteration_launches(c, f, pf, bt, nvec - 1, false, nullptr);
+      }
+      if (two) {
+        HIPCHK(hipEventRecord(c->ev_join, bh[1].st));
+        HIPCHK(hipStreamWaitEvent(st, c->ev_join, 0));
+      }
+    };
+    iters(1);   // warm-up
+    *ms_per_launch = timed_ms(st, 1, [&] { iters(reps); }) / reps;
+  } else {
+    launch();   // warm-up (code object load, caches)
+    *ms_per_launch = timed_ms(st, reps, launch);
+  }
   API_END
 }
 

@@ -74,11 +74,11 @@ struct ArnoldiStrides {
 static void arnoldi_dots(ricadi_ctx* c, const IterationForm& f, const Batch& bt, int nvec) {
   const ArnoldiStrides s(c, bt);
   if (f.w32)
-    launch_cols_dots16_w32(c->st, bt.tab, c->n, nvec, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
+    launch_cols_dots16_w32(bt.st, bt.tab, c->n, nvec, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
                            c->wv32.p, s.nm, c->partial.p, s.gspart, c->h1.p, s.gsh);
   else
     with_basis(c, f, [&](auto* V) {
-      launch_cols_dots_b(c->st, bt.tab, c->n, bt.m, nvec, V, s.vs, s.nm, c->wv.p, s.nm, 0, c->partial.p, s.gspart,
+      launch_cols_dots_b(bt.st, bt.tab, c->n, bt.m, nvec, V, s.vs, s.nm, c->wv.p, s.nm, 0, c->partial.p, s.gspart,
                          c->h1.p, s.gsh);
     });
 }
@@ -86,11 +86,11 @@ static void arnoldi_dots(ricadi_ctx* c, const IterationForm& f, const Batch& bt,
 static void arnoldi_update_dots(ricadi_ctx* c, const IterationForm& f, const Batch& bt, int nvec) {
   const ArnoldiStrides s(c, bt);
   if (f.w32)
-    launch_cols_update_dots16_w32(c->st, bt.tab, c->n, nvec, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
+    launch_cols_update_dots16_w32(bt.st, bt.tab, c->n, nvec, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
                                   c->h1.p, s.gsh, c->wv32.p, s.nm, c->partial.p, s.gspart, c->h2.p, s.gsh);
   else
     with_basis(c, f, [&](auto* V) {
-      launch_cols_update_dots_b(c->st, bt.tab, c->n, bt.m, nvec, V, s.vs, s.nm, c->h1.p, s.gsh, c->wv.p, s.nm, f.keepw,
+      launch_cols_update_dots_b(bt.st, bt.tab, c->n, bt.m, nvec, V, s.vs, s.nm, c->h1.p, s.gsh, c->wv.p, s.nm, f.keepw,
                                 c->partial.p, s.gspart, c->h2.p, s.gsh);
     });
 }
@@ -103,7 +103,7 @@ static void arnoldi_update(ricadi_ctx* c, const IterationForm& f, const Batch& b
   double* vcur = f.h16 ? nullptr : c->vcur.p;
   if (f.fuseh) {
     _Float16* Vh = reinterpret_cast<_Float16*>(c->basisf.p);
-    launch_cols_update16_hess_b(c->st, bt.tab, c->n, nvec, Vh, s.vs, s.nm, c->h1.p, c->h2.p, s.gsh, f.keepw ? 1 : 0,
+    launch_cols_update16_hess_b(bt.st, bt.tab, c->n, nvec, Vh, s.vs, s.nm, c->h1.p, c->h2.p, s.gsh, f.keepw ? 1 : 0,
                                 c->wv.p, s.nm, vcur, s.nm, Vh + (size_t)nvec * s.vs, s.nm, j, c->opts.gmres_restart,
                                 c->H.p, c->cs.p, c->sn.p, c->g.p, c->resid.p + (size_t)(j & 1) * resbuf,
                                 c->resid.p + (size_t)((j + 1) & 1) * resbuf, c->bnorm2.p, c->opts.gmres_tol,
@@ -113,10 +113,10 @@ static void arnoldi_update(ricadi_ctx* c, const IterationForm& f, const Batch& b
   const double* h = f.keepw ? c->h2.p + s.h2buf : c->h2.p;
   with_basis(c, f, [&](auto* V) {
     if constexpr (std::is_same<std::remove_pointer_t<decltype(V)>, double>::value)
-      launch_cols_update_b(c->st, bt.tab, c->n, m, nvec, V, s.vs, s.nm, h, s.gsh, -1.0, c->wv.p, s.nm, c->scale.p,
+      launch_cols_update_b(bt.st, bt.tab, c->n, m, nvec, V, s.vs, s.nm, h, s.gsh, -1.0, c->wv.p, s.nm, c->scale.p,
                            V + (size_t)nvec * s.vs, s.nm);
     else
-      launch_cols_update_b(c->st, bt.tab, c->n, m, nvec, V, s.vs, s.nm, h, s.gsh, -1.0, c->wv.p, s.nm, c->scale.p,
+      launch_cols_update_b(bt.st, bt.tab, c->n, m, nvec, V, s.vs, s.nm, h, s.gsh, -1.0, c->wv.p, s.nm, c->scale.p,
                            vcur, s.nm, V + (size_t)nvec * s.vs, s.nm);
   });
 }
@@ -127,20 +127,96 @@ static void arnoldi_update(ricadi_ctx* c, const IterationForm& f, const Batch& b
 static void arnoldi_lowsync_dots(ricadi_ctx* c, const Batch& bt, const GroupInts& js, bool end_of_cycle) {
   const ArnoldiStrides s(c, bt);
   const int restart = c->opts.gmres_restart;
-  launch_arnoldi16_lowsync_dots(c->st, bt.tab, js, c->n, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
+  launch_arnoldi16_lowsync_dots(bt.st, bt.tab, js, c->n, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
                                 end_of_cycle ? nullptr : c->wv32.p, s.nm, c->ls_partial.p,
                                 lowsync_partial_stride(c->n, restart), c->ls_coef.p, lowsync_coef_stride(restart));
   if (end_of_cycle)
-    launch_arnoldi16_lowsync_close(c->st, bt.tab, js, c->ls_coef.p, lowsync_coef_stride(restart), restart, c->H.p,
+    launch_arnoldi16_lowsync_close(bt.st, bt.tab, js, c->ls_coef.p, lowsync_coef_stride(restart), restart, c->H.p,
                                    c->cs.p, c->sn.p, c->g.p, c->bnorm2.p, c->opts.gmres_tol);
 }
 static void arnoldi_lowsync_update(ricadi_ctx* c, const Batch& bt, int j, double* host_resid) {
   const ArnoldiStrides s(c, bt);
   const int restart = c->opts.gmres_restart;
-  launch_arnoldi16_lowsync_update(c->st, bt.tab, c->n, j, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
+  launch_arnoldi16_lowsync_update(bt.st, bt.tab, c->n, j, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
                                   c->wv32.p, s.nm, c->ls_coef.p, lowsync_coef_stride(restart), restart, c->H.p,
                                   c->cs.p, c->sn.p, c->g.p, c->bnorm2.p, c->opts.gmres_tol,
                                   c->resid.p + (size_t)(j & 1) * c->wcols, host_resid);
+}
+
+// The launches of lockstep iteration j for the groups of bt.tab, on bt.st (gmres_core and the kernel timers):
+// preconditioner, operator, Arnoldi.  Residual estimates of the iteration also go to host_resid (may be null).
+static void iteration_launches(ricadi_ctx* c, const IterationForm& f, const CycleForm& pf, const Batch& bt, int j,
+                               bool lowrank, double* host_resid) {
+  const size_t nm = bt.gs, vs = nm * bt.G;
+  const double* vj = (f.b32 || f.b16) ? c->vcur.p : c->basis.p + (size_t)j * vs;
+  _Float16* Vh = reinterpret_cast<_Float16*>(c->basisf.p);   // FP16 storage shares the FP32 buffer
+  // flexible form: Z_j = P^-1 v_j is kept (FP32), the cycle's correction is x += Z y -- no
+  // preconditioner application at the cycle end, and P may differ from step to step
+  // ... and the operator reads that stored FP32 copy (half the bytes of the x gathers; S Z_j = V H then
+  // holds for exactly the vectors the correction uses), so the sweeps need not store the FP64 z at all
+  float* zj = c->zbasisf.p + (size_t)j * vs;
+  precond_apply(c, bt, pf, CycleIO{vj, nm, f.h16 ? Vh + (size_t)j * vs : nullptr, c->zv.p, zj, nm});
+  op_apply(c, bt, c->zv.p, nm, c->wv.p, lowrank, f.x32 ? zj : nullptr, f.w32 ? c->wv32.p : nullptr);
+  if (f.lowsync) {
+    // slot j holds the candidate u_j the preconditioner read; v_j replaces it, u_{j+1} goes to slot j + 1
+    arnoldi_lowsync_dots(c, bt, same_int(j), false);
+    arnoldi_lowsync_update(c, bt, j, host_resid);
+  } else {
+    const int restart = c->opts.gmres_restart;
+    arnoldi_dots(c, f, bt, j + 1);
+    arnoldi_update_dots(c, f, bt, j + 1);
+    if (!f.fuseh)
+      launch_gmres_hess_b(bt.st, bt.tab, bt.m, j, restart, c->h1.p, c->h2.p, c->H.p, c->cs.p, c->sn.p, c->g.p,
+                          c->scale.p, c->resid.p, c->bnorm2.p, c->opts.gmres_tol, host_resid, nullptr, nullptr,
+                          f.keepw ? c->h2.p + (size_t)(restart + 2) * c->wcols : nullptr);
+    arnoldi_update(c, f, bt, j + 1, host_resid);
+  }
+}
+
+// ---- two half-batches on two streams ----------------------------------------------------
+// The groups of a lockstep batch are independent Arnoldi processes and every buffer the iteration writes is indexed
+// by group id, so the batch can go through the same launch sequence as two halves on two streams: the GPU then runs
+// a VALU / LDS / gather bound launch of one half (saddle SpMM, restriction, pressure step) beside an FP64-MFMA bound
+// one of the other (coarse apply, first sweep), and each half's launch boundaries hide behind the other's kernels
+// (DESIGN.md 6a).  Every kernel sums a group in an order that does not depend on the other groups of its launch, so
+// the split changes no bit of the results.  The second stream (non-blocking) lives in the context.
+// Fewer live groups than this run on one stream: halves of 1 - 2 groups are latency-bound chains whose launches
+// measured slower side by side than as one table (cfg2: 4 groups +10 %, 2 groups +25 % per iteration; 8 groups -8 %).
+constexpr int kSplitMinGroups = 8;
+static hipStream_t half_stream(ricadi_ctx* c) {
+  if (!c->st_half) {
+    HIPCHK(hipStreamCreateWithFlags(&c->st_half, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&c->ev_res_half[i], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+  }
+  return c->st_half;
+}
+// Does the lockstep solve of G groups run as two halves?  Not with a child level (the child's cycle has not been
+// audited for scratch shared across groups), not with the low-rank operator term (its coefficient panel lrc is cleared
+// for all groups at once and summed with atomics), and only where it was measured to pay: up to n = 2e5 (cfg2, n = 3e4:
+// -9 % per 16-group iteration; cfg3, n = 5e4: -5 % per step; cfg5, n = 5e5: +1.1 .. +1.8 % per iteration at 4 - 16
+// groups, where every launch already fills the chip).
+static bool split_halves(const ricadi_ctx* c, int G, bool lowrank) {
+  return c->sw.split && G >= kSplitMinGroups && !c->child && !(lowrank && c->q > 0) && c->n <= 200000;
+}
+// The halves of the active groups: alternating positions in the order of the groups' iteration counts in their
+// previous solve (slowest first; every ADI sweep repeats the same shifts), else in the caller's order (a sorted shift
+// list: neighbours need similar counts).  Either way each half gets a mix of slow and fast shifts, and the two slowest
+// land in different halves.
+static void split_groups(ShiftData* const* sds, const std::vector<int>& act, std::vector<int> (&half)[2]) {
+  std::vector<int> ord = act;
+  bool known = true;
+  for (int g : act) known = known && sds[g]->last_iters >= 0;
+  if (known)
+    std::stable_sort(ord.begin(), ord.end(),
+                     [&](int a, int b) { return sds[a]->last_iters > sds[b]->last_iters; });
+  half[0].clear();
+  half[1].clear();
+  for (size_t i = 0; i < ord.size(); ++i) half[i & 1].push_back(ord[i]);
+  // group ids in increasing order within a half, as in the one-stream table
+  std::sort(half[0].begin(), half[0].end());
+  std::sort(half[1].begin(), half[1].end());
 }
 
 // have_x0: x holds an initial guess (else it is zeroed);  only: the groups to iterate on (NULL = all; the
@@ -160,12 +236,18 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
   const int GM = G * m;
   const IterationForm f = iteration_form(c, m, G, lowrank);
   const CycleForm pf = cycle_form(c, m, bt.blocks16, nm, f.x32, f.h16);
-  const size_t h2buf = (size_t)(restart + 2) * c->wcols;        // doubles between the two second-pass buffers
   c->w32_last = f.w32 ? 1 : 0;
-  _Float16* Vh = reinterpret_cast<_Float16*>(c->basisf.p);   // FP16 storage shares the FP32 buffer
   double* hb = c->h_resid;
   const size_t slot = (size_t)RICADI_MAX_M * RICADI_MAX_GROUPS;
   for (int g = 0; g < G; ++g) res[g] = GmresResult();
+  // the iterations of a cycle as two half-batches: half h on stream hs[h] (half 0 on the context's stream), its lag
+  // event pair evh[h]
+  const bool split = split_halves(c, G, lowrank);
+  const hipStream_t hs[2] = {st, split ? half_stream(c) : st};
+  hipEvent_t* const evh[2] = {c->ev_res, split ? c->ev_res_half : c->ev_res};
+  Batch bh[2] = {bt, bt};
+  bh[1].st = hs[1];
+  std::vector<int> half[2];
 
   auto norms2 = [&](const double* w, size_t gsw, double* out) {
     launch_cols_dots_b(st, bt.tab, n, m, 0, (const double*)nullptr, 0, 0, w, gsw, 1, c->partial.p, gspart, out,
@@ -208,6 +290,7 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
   auto lapc = [&](double& acc) {
     if (c->sw.timing) {
       (void)hipStreamSynchronize(st);
+      if (split) (void)hipStreamSynchronize(hs[1]);
       acc += tkc.lap();
     }
   };
@@ -274,37 +357,48 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
     });
     live = act;
     for (int g : act) kk[g] = 0;
+    // one cycle schedule for both halves; the second stream starts behind what the first has issued so far, and is
+    // joined back as soon as too few groups are left for two halves
+    bool two = split && act.size() >= (size_t)kSplitMinGroups;
+    bool joined = !two;
+    auto join = [&]() {
+      if (joined) return;
+      HIPCHK(hipEventRecord(c->ev_join, hs[1]));
+      HIPCHK(hipStreamWaitEvent(st, c->ev_join, 0));
+      joined = true;
+    };
+    if (two) {
+      split_groups(sds, act, half);
+      HIPCHK(hipEventRecord(c->ev_fork, st));
+      HIPCHK(hipStreamWaitEvent(hs[1], c->ev_fork, 0));
+    }
     lapc(c->t_cyc);
     for (int j = 0; j < cyc && !live.empty(); ++j) {
-      bt.set(live);
-      const double* vj = (f.b32 || f.b16) ? c->vcur.p : c->basis.p + (size_t)j * vs;
-      // flexible form: Z_j = P^-1 v_j is kept (FP32), the cycle's correction is x += Z y -- no
-      // preconditioner application at the cycle end, and P may differ from step to step
-      // ... and the operator reads that stored FP32 copy (half the bytes of the x gathers; S Z_j = V H then
-      // holds for exactly the vectors the correction uses), so the sweeps need not store the FP64 z at all
-      float* zj = c->zbasisf.p + (size_t)j * vs;
-      precond_apply(c, bt, pf, CycleIO{vj, nm, f.h16 ? Vh + (size_t)j * vs : nullptr, c->zv.p, zj, nm});
-      op_apply(c, bt, c->zv.p, nm, c->wv.p, lowrank, f.x32 ? zj : nullptr, f.w32 ? c->wv32.p : nullptr);
       // the residual estimates also go straight to a pinned host slot (read one
       // iteration later, behind the event below)
       double* cur = hb + 2 * slot + (size_t)(j & 1) * slot;
-      if (f.lowsync) {
-        // slot j holds the candidate u_j the preconditioner read; v_j replaces it, u_{j+1} goes to slot j + 1
-        arnoldi_lowsync_dots(c, bt, same_int(j), false);
-        arnoldi_lowsync_update(c, bt, j, cur);
+      if (two && live.size() < (size_t)kSplitMinGroups) join();
+      if (!joined) {
+        // the multi-shift kernels' choice follows the groups of the whole solve
+        for (int h = 0; h < 2; ++h) {
+          std::vector<int> lh;
+          for (int g : half[h])
+            if (std::find(live.begin(), live.end(), g) != live.end()) lh.push_back(g);
+          bh[h].set(lh);
+          bh[h].ng_solve = (int)live.size();
+        }
+        for (int h = 0; h < 2; ++h) {
+          if (bh[h].tab.ng > 0) iteration_launches(c, f, pf, bh[h], j, lowrank, cur);
+          HIPCHK(hipEventRecord(evh[h][j & 1], hs[h]));
+        }
       } else {
-        arnoldi_dots(c, f, bt, j + 1);
-        arnoldi_update_dots(c, f, bt, j + 1);
-        if (!f.fuseh)
-          launch_gmres_hess_b(st, bt.tab, m, j, restart, c->h1.p, c->h2.p, c->H.p, c->cs.p, c->sn.p,
-                              c->g.p, c->scale.p, c->resid.p, c->bnorm2.p, tol, cur, nullptr, nullptr,
-                              f.keepw ? c->h2.p + h2buf : nullptr);
-        arnoldi_update(c, f, bt, j + 1, cur);
+        bt.set(live);
+        iteration_launches(c, f, pf, bt, j, lowrank, cur);
+        // Residual estimates travel to a pinned slot behind an event; the host
+        // looks at the PREVIOUS iteration's slot, so it never drains the stream
+        // (one iteration of lag: at most one surplus Arnoldi step per group).
+        HIPCHK(hipEventRecord(c->ev_res[j & 1], st));
       }
-      // Residual estimates travel to a pinned slot behind an event; the host
-      // looks at the PREVIOUS iteration's slot, so it never drains the stream
-      // (one iteration of lag: at most one surplus Arnoldi step per group).
-      HIPCHK(hipEventRecord(c->ev_res[j & 1], st));
       for (int g : live) {
         ++res[g].iters;
         kk[g] = j + 1;
@@ -312,6 +406,7 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
       std::vector<int> still;
       if (j >= 1) {
         HIPCHK(hipEventSynchronize(c->ev_res[(j - 1) & 1]));
+        if (two) HIPCHK(hipEventSynchronize(evh[1][(j - 1) & 1]));   // (recorded up to the join; done since)
         const double* prev = hb + 2 * slot + (size_t)((j - 1) & 1) * slot;
         for (int g : live)
           if (!group_converged(prev, g) && res[g].iters < maxit) still.push_back(g);
@@ -321,6 +416,8 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
       }
       live.swap(still);
     }
+    // the second stream's iterations are complete before the corrections (and before anything after the solve)
+    join();
     lapc(c->t_iter);
     // corrections: x_g += Z_g y_g with the k_g preconditioned vectors group g built
     // (one launch each for all groups of the cycle, k_g per group by value)
@@ -336,6 +433,8 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
     lapc(c->t_cyc);
   }
   lapc(c->t_cyc);
+  for (int g = 0; g < G; ++g)
+    if (!only || std::find(only->begin(), only->end(), g) != only->end()) sds[g]->last_iters = res[g].iters;
 }
 
 // ---- wide panels as sixteen-column groups -------------------------------------------------------

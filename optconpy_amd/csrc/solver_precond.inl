@@ -18,6 +18,11 @@ struct Batch {
   bool blocks16 = false;                       // every group of the batch has them
   size_t gs = 0, gsp = 0, gsc = 0, gsq = 0;   // strides: n*m, np*m, kc*m, q*m
   std::shared_ptr<Batch> sub;                 // the same groups on the child level
+  hipStream_t st = nullptr;                   // stream of every launch for the batch (make_batch: the context's)
+  // groups active in the whole lockstep solve when this batch is one half of it (gmres_core's split): the choice of
+  // the multi-shift kernels follows the whole solve, so both halves launch what one stream would; 0: tab.ng
+  int ng_solve = 0;
+  int ms_groups() const { return ng_solve > 0 ? ng_solve : tab.ng; }
 
   void all() {
     tab.ng = G;
@@ -72,6 +77,7 @@ static Batch make_batch(ricadi_ctx* c, ShiftData* const* sds, int G, int m) {
   bt.gsp = (size_t)c->np * m;
   bt.gsc = (size_t)c->kc * m;
   bt.gsq = (size_t)std::max(c->q, 1) * m;
+  bt.st = c->st;
   bt.all();
   if (c->child) {
     ShiftData* subs[RICADI_MAX_GROUPS];
@@ -114,31 +120,31 @@ static void saddle_spmm(ricadi_ctx* c, const Batch& bt, const double* x, size_t 
   const bool fits = saddle_tiled(c, m);
   const bool has_lr = lr.q > 0 && lr.nrows > 0;
   if (x32 && fits && !r && !xmap && !has_lr) {
-    const bool ms = ms_pays(c, bt.tab.ng, c->snnz) && spmm_blocked_ms_ok(m, c->sb_max_cols, (size_t)c->n);
+    const bool ms = ms_pays(c, bt.ms_groups(), c->snnz) && spmm_blocked_ms_ok(m, c->sb_max_cols, (size_t)c->n);
     c->k1_variant = (ms ? 2 : 1) + 4;
     if (ms)
-      launch_spmm_blocked_ms_x32(c->st, bt.tab, bt.alpha, bt.beta, c->sb_nblk, c->sb_rows2.p, c->sb_rp2.p,
+      launch_spmm_blocked_ms_x32(bt.st, bt.tab, bt.alpha, bt.beta, c->sb_nblk, c->sb_rows2.p, c->sb_rp2.p,
                                  c->sb_cols2.p, c->sb_lidx_ms.p, c->sbAJ.p, c->sbE.p, x32, m, gsx, y, m, gsy, alpha,
                                  m, c->sb_max_cols, y32);
     else
-      launch_spmm_blocked_x32(c->st, bt.tab, c->sb_nblk, c->sb_rows2.p, c->sb_rp2.p, c->sb_cols2.p, c->sb_lidx.p,
+      launch_spmm_blocked_x32(bt.st, bt.tab, c->sb_nblk, c->sb_rows2.p, c->sb_rp2.p, c->sb_cols2.p, c->sb_lidx.p,
                               bt.svalb, x32, m, gsx, y, m, gsy, alpha, m, c->sb_max_cols, y32);
     return;
   }
   if (y32) throw HipError{"FP32 operator output asked for outside the FP32-input tile kernels"};
-  const bool ms = fits && ms_pays(c, bt.tab.ng, c->snnz) && !xmap && !has_lr &&
+  const bool ms = fits && ms_pays(c, bt.ms_groups(), c->snnz) && !xmap && !has_lr &&
                   spmm_blocked_ms_ok(m, c->sb_max_cols, (size_t)c->n);
   if (!xmap) c->k1_variant = ms ? 2 : fits ? 1 : 0;
   if (ms)
-    launch_spmm_blocked_ms(c->st, bt.tab, bt.alpha, bt.beta, c->sb_nblk, c->sb_rows2.p, c->sb_rp2.p,
+    launch_spmm_blocked_ms(bt.st, bt.tab, bt.alpha, bt.beta, c->sb_nblk, c->sb_rows2.p, c->sb_rp2.p,
                            c->sb_cols2.p, c->sb_lidx_ms.p, c->sbAJ.p, c->sbE.p, x, m, gsx, y, m, gsy,
                            r, m, gsr, alpha, beta_r, m, c->sb_max_cols);
   else if (fits)
-    launch_spmm_blocked_b(c->st, bt.tab, c->sb_nblk, c->sb_rows2.p, c->sb_rp2.p,
+    launch_spmm_blocked_b(bt.st, bt.tab, c->sb_nblk, c->sb_rows2.p, c->sb_rp2.p,
                           xmap ? c->sb_colsm2.p : c->sb_cols2.p, c->sb_lidx.p, bt.svalb, x, m, gsx, y,
                           m, gsy, r, m, gsr, alpha, beta_r, m, c->sb_max_cols, lr);
   else
-    launch_spmm_b(c->st, bt.tab, c->n, c->s_rp.p, c->s_ci.p, bt.sval, x, m, gsx, xmap, y, m, gsy, r,
+    launch_spmm_b(bt.st, bt.tab, c->n, c->s_rp.p, c->s_ci.p, bt.sval, x, m, gsx, xmap, y, m, gsy, r,
                   m, gsr, alpha, beta_r, m, lr);
 }
 
@@ -147,7 +153,7 @@ static void saddle_spmm(ricadi_ctx* c, const Batch& bt, const double* x, size_t 
 // y32 (optional, with x32 only): the product goes to this FP32 panel (stride bt.gs) and y is not written
 static void op_apply(ricadi_ctx* c, const Batch& bt, const double* x, size_t gsx, double* y,
                      bool lowrank, const float* x32 = nullptr, float* y32 = nullptr) {
-  hipStream_t st = c->st;
+  hipStream_t st = bt.st;
   const int m = bt.m;
   LowRankArgs lr;
   if (lowrank && c->q > 0) {
@@ -170,23 +176,23 @@ static void block_sweep(ricadi_ctx* c, const Batch& bt, bool pressure, const dou
   const int* bptr = pressure ? c->bp_ptr.p : c->bv_ptr.p;
   const int* rows = pressure ? c->bp_rows.p : c->bv_rows.p;
   auto sweep = [&](const auto& inv) {
-    launch_block_apply_b(c->st, bt.tab, c->bs, nb, bptr, rows, inv, in, m, gsi, out, m, bt.gs, m, subtract, pa, cin);
+    launch_block_apply_b(bt.st, bt.tab, c->bs, nb, bptr, rows, inv, in, m, gsi, out, m, bt.gs, m, subtract, pa, cin);
   };
   if (c->precond32) sweep(pressure ? bt.bpinvf : bt.bvinvf);
   else sweep(pressure ? bt.bpinv : bt.bvinv);
 }
 // r2 = r - (S Y) ec through the tile kernels (c->syb_ok): the multi-shift one where it pays
 static bool sy_tiled_ms(const ricadi_ctx* c, const Batch& bt) {
-  return ms_pays(c, bt.tab.ng, c->snnz) && spmm_blocked_ms_ok(bt.m, c->syb_max_cols, (size_t)c->kc);
+  return ms_pays(c, bt.ms_groups(), c->snnz) && spmm_blocked_ms_ok(bt.m, c->syb_max_cols, (size_t)c->kc);
 }
 static void sy_residual_tiled(ricadi_ctx* c, const Batch& bt, const double* r, size_t gsr) {
   const int m = bt.m;
   if (sy_tiled_ms(c, bt))
-    launch_spmm_blocked_ms(c->st, bt.tab, bt.alpha, bt.beta, c->sb_nblk, c->sb_rows2.p, c->syb_rp2.p, c->syb_cols2.p,
+    launch_spmm_blocked_ms(bt.st, bt.tab, bt.alpha, bt.beta, c->sb_nblk, c->sb_rows2.p, c->syb_rp2.p, c->syb_cols2.p,
                            c->syb_lidx_ms.p, c->sybAJ.p, c->sybE.p, c->ec.p, m, bt.gsc, c->r2.p, m, bt.gs, r, m, gsr,
                            -1.0, 1.0, m, c->syb_max_cols);
   else
-    launch_spmm_blocked_b(c->st, bt.tab, c->sb_nblk, c->sb_rows2.p, c->syb_rp2.p, c->syb_cols2.p, c->syb_lidx.p,
+    launch_spmm_blocked_b(bt.st, bt.tab, c->sb_nblk, c->sb_rows2.p, c->syb_rp2.p, c->syb_cols2.p, c->syb_lidx.p,
                           bt.syvalb, c->ec.p, m, bt.gsc, c->r2.p, m, bt.gs, r, m, gsr, -1.0, 1.0, m, c->syb_max_cols);
 }
 // rc = Y^T r (smoothed aggregation: P^T r) by the 16-lanes-per-row CSR kernel
@@ -194,7 +200,7 @@ static void restrict_csr(ricadi_ctx* c, const Batch& bt, const double* r, size_t
   const int* rrp = c->sa ? c->pt_rp.p : c->agg_ptr.p;
   const int* rci = c->sa ? c->pt_ci.p : c->agg_rows.p;
   const GroupPtrs rvals = same_ptr(c->sa ? (const double*)c->pt_v.p : c->ones.p);
-  launch_spmm_b(c->st, bt.tab, c->kc, rrp, rci, rvals, r, bt.m, gsr, nullptr, c->rc.p, bt.m, bt.gsc, nullptr, 0, 0,
+  launch_spmm_b(bt.st, bt.tab, c->kc, rrp, rci, rvals, r, bt.m, gsr, nullptr, c->rc.p, bt.m, bt.gsc, nullptr, 0, 0,
                 1.0, 0.0, bt.m);
 }
 
@@ -315,10 +321,10 @@ static void pc_restrict(ricadi_ctx* c, const Batch& bt, const CycleForm& f, cons
   const int* rci = c->sa ? c->pt_ci.p : c->agg_rows.p;
   const GroupPtrs rvals = same_ptr(c->sa ? (const double*)c->pt_v.p : c->ones.p);
   if (f.restriction == f.RS_ROWWAVE)
-    launch_spmm_rowwave(c->st, bt.tab, c->kc, rrp, rci, rvals, io.r16 ? nullptr : io.r, io.r16, io.gsr, c->rc.p,
+    launch_spmm_rowwave(bt.st, bt.tab, c->kc, rrp, rci, rvals, io.r16 ? nullptr : io.r, io.r16, io.gsr, c->rc.p,
                         bt.gsc, bt.m, f.coarse == f.CO_DENSE_KB);
   else if (f.restriction == f.RS_CSR16)
-    launch_spmm_h(c->st, bt.tab, c->kc, rrp, rci, rvals, nullptr, io.r16, bt.m, io.gsr, c->rc.p, bt.m, bt.gsc,
+    launch_spmm_h(bt.st, bt.tab, c->kc, rrp, rci, rvals, nullptr, io.r16, bt.m, io.gsr, c->rc.p, bt.m, bt.gsc,
                   nullptr, 0, 0, 1.0, 0.0, bt.m, 16);
   else if (f.restriction == f.RS_CSR64)
     restrict_csr(c, bt, io.r, io.gsr);
@@ -329,18 +335,20 @@ static void pc_coarse(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const 
     ricadi_ctx* ch = c->child.get();
     Batch cb = *bt.sub;
     cb.tab = bt.tab;
+    cb.st = bt.st;
+    cb.ng_solve = bt.ng_solve;
     precond_apply(ch, cb, cycle_form(ch, cb.m, cb.blocks16, bt.gsc, false, false),
                   CycleIO{c->rc.p, bt.gsc, nullptr, c->ec.p});
   } else if (f.coarse == f.CO_DENSE_KB) {
-    launch_dense_apply_kb(c->st, bt.tab, c->kc, bt.einvf, c->rc.p, c->ec.p);
+    launch_dense_apply_kb(bt.st, bt.tab, c->kc, bt.einvf, c->rc.p, c->ec.p);
   } else if (f.coarse == f.CO_DENSE && c->precond32) {
-    launch_dense_apply_b(c->st, bt.tab, c->kc, bt.m, bt.einvf, (c->kc + 3) & ~3, c->rc.p, c->ec.p);
+    launch_dense_apply_b(bt.st, bt.tab, c->kc, bt.m, bt.einvf, (c->kc + 3) & ~3, c->rc.p, c->ec.p);
   } else if (f.coarse == f.CO_DENSE) {
-    launch_dense_apply_b(c->st, bt.tab, c->kc, bt.m, bt.einv, c->rc.p, c->ec.p);
+    launch_dense_apply_b(bt.st, bt.tab, c->kc, bt.m, bt.einv, c->rc.p, c->ec.p);
   }
 }
 static void pc_sy_prows(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
-  hipStream_t st = c->st;
+  hipStream_t st = bt.st;
   const int nv = c->nv, m = bt.m;
   if (f.sy == f.SY_PROWS) {
     // only the PRESSURE rows of r - (S Y) ec are formed (short CSR product over np rows); the
@@ -395,13 +403,13 @@ static void pc_two_term(ricadi_ctx* c, const Batch& bt, const CycleForm& f, cons
   }
   sweep_records(c, c->sw_in_two, 2, pa);
   if (f.first == f.FS_TWO32 || f.first == f.FS_TWO32_PIPE)
-    launch_block_two32_h(c->st, bt.tab, c->nbv, bt.bvinvh, s1, bt.adymh, s2, io.z, bt.gs, pa,
+    launch_block_two32_h(bt.st, bt.tab, c->nbv, bt.bvinvh, s1, bt.adymh, s2, io.z, bt.gs, pa,
                          f.first == f.FS_TWO32_PIPE);
   else if (c->precond32)
-    launch_block_apply2_b(c->st, bt.tab, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinvf, s1, bt.adymf, s2, io.z,
+    launch_block_apply2_b(bt.st, bt.tab, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinvf, s1, bt.adymf, s2, io.z,
                           m, bt.gs, m, pa);
   else
-    launch_block_apply2_b(c->st, bt.tab, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinv, s1, bt.adym, s2, io.z,
+    launch_block_apply2_b(bt.st, bt.tab, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinv, s1, bt.adym, s2, io.z,
                           m, bt.gs, m, pa);
 }
 // t = J z_v - r_p (r_p of r2, or of r without a coarse level)
@@ -409,7 +417,7 @@ static void pc_jprod(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const C
   if (f.pressure != f.PS_SPLIT) return;
   const int m = bt.m;
   const bool r2 = c->kc > 0;
-  launch_spmm_b(c->st, bt.tab, c->np, c->J.rp.p, c->J.ci.p, same_ptr(c->J.v.p), io.z, m, bt.gs, nullptr, c->tp.p, m,
+  launch_spmm_b(bt.st, bt.tab, c->np, c->J.rp.p, c->J.ci.p, same_ptr(c->J.v.p), io.z, m, bt.gs, nullptr, c->tp.p, m,
                 bt.gsp, (r2 ? c->r2.p : io.r) + (size_t)c->nv * m, m, r2 ? bt.gs : io.gsr, 1.0, -1.0, m);
 }
 static void pc_schur(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
@@ -444,14 +452,14 @@ static void pc_schur(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const C
   const _Float16* rp16 = io.r16 ? io.r16 + off : nullptr;
   const size_t gsrp = r2 ? bt.gs : io.gsr;
   if (f.pressure == f.PS_FUSED16)
-    launch_pressure_step_h(c->st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinvh, c->J.ci.p, c->J.v.p, sy, c->sy_ci.p,
+    launch_pressure_step_h(bt.st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinvh, c->J.ci.p, c->J.v.p, sy, c->sy_ci.p,
                            bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, pa, io.z32, io.gs32);
   else if (c->precond32)
-    launch_pressure_step_b(c->st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinvf, c->J.ci.p, c->J.v.p, io.z, bt.gs, sy,
+    launch_pressure_step_b(bt.st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinvf, c->J.ci.p, c->J.v.p, io.z, bt.gs, sy,
                            c->sy_ci.p, bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, pa,
                            f.mid32 ? io.z32 : nullptr, io.gs32);
   else
-    launch_pressure_step_b(c->st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinv, c->J.ci.p, c->J.v.p, io.z, bt.gs, sy,
+    launch_pressure_step_b(bt.st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinv, c->J.ci.p, c->J.v.p, io.z, bt.gs, sy,
                            c->sy_ci.p, bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, pa);
 }
 // z_v -= Ahat^-1 (J^T z_p): the same block-Jacobi inverse as in the Schur blocks; the
@@ -481,12 +489,12 @@ static void pc_rect(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const Cy
   pa.old32 = f.mid32 ? 1 : 0;
   sweep_records(c, c->sw_in_rect, 1, pa);
   if (f.last == f.LS_RECT32)
-    launch_block_rect32_h(c->st, bt.tab, c->gt_ks, c->nbv, bt.gtmh, c->tp.p, bt.gsp, io.z, bt.gs, 1, pa);
+    launch_block_rect32_h(bt.st, bt.tab, c->gt_ks, c->nbv, bt.gtmh, c->tp.p, bt.gsp, io.z, bt.gs, 1, pa);
   else if (c->precond32)
-    launch_block_apply_rect_b(c->st, bt.tab, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
+    launch_block_apply_rect_b(bt.st, bt.tab, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
                               c->gt_cols.p, bt.gtmf, c->tp.p, m, bt.gsp, io.z, m, bt.gs, m, 1, pa);
   else
-    launch_block_apply_rect_b(c->st, bt.tab, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
+    launch_block_apply_rect_b(bt.st, bt.tab, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
                               c->gt_cols.p, bt.gtm, c->tp.p, m, bt.gsp, io.z, m, bt.gs, m, 1, pa);
 }
 using CycleStage = void (*)(ricadi_ctx*, const Batch&, const CycleForm&, const CycleIO&);
@@ -504,7 +512,7 @@ static void precond_apply(ricadi_ctx* c, const Batch& bt, const CycleForm& f, co
   for (CycleStage stage : cycle_stages) stage(c, bt, f, io);
   if (io.z32 && f.last != f.LS_RECT32 && f.last != f.LS_RECT)   // (the rectangle sweeps write z32 themselves)
     for (int i = 0; i < bt.tab.ng; ++i)
-      launch_to_f32(c->st, c->n, bt.m, io.z + (size_t)bt.tab.gid[i] * bt.gs, bt.m,
+      launch_to_f32(bt.st, c->n, bt.m, io.z + (size_t)bt.tab.gid[i] * bt.gs, bt.m,
                     io.z32 + (size_t)bt.tab.gid[i] * io.gs32, bt.m);
 }
 

@@ -191,6 +191,24 @@ int ricadi_precond_apply_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas
                                    const double* dR, int64_t r_stride, int m, const int32_t* active,
                                    int nactive, double* dZ, int* form_out);
 
+/* The saddle product y_g = beta_r r_g + alpha S(alphas[g], betas[g]) x_g as the lockstep GMRES launches it
+ * (the operator product of the iteration and the restart residual), for tests: a batch of ng panels of width m,
+ * x_g = dX + g*x_stride, y_g = dY + g*y_stride, r_g = dR + g*r_stride (device FP64, row-major, ld m; every stride
+ * >= n*m).  active (may be NULL = all ng): the group ids to apply it to; the other panels of dY are not written.
+ * flags: RICADI_OA_X32 the input is rounded to FP32 on the device first (as the iteration stores Z_j);
+ * RICADI_OA_Y32 the product goes to an FP32 panel, returned widened in dY; RICADI_OA_LOWRANK the term - U V^T x_v
+ * of ricadi_set_lowrank; RICADI_OA_RESIDUAL the term beta_r r_g (else dR is ignored).  The FP32 forms exist for
+ * the plain product where the tiles of the operator fit (else RICADI_EINVAL).  variant_out (may be NULL): the
+ * kernel form that ran, as ricadi_setup_info's k1_variant. */
+#define RICADI_OA_X32 1
+#define RICADI_OA_Y32 2
+#define RICADI_OA_LOWRANK 4
+#define RICADI_OA_RESIDUAL 8
+int ricadi_op_apply_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas, const double* betas, const double* dX,
+                              int64_t x_stride, int m, const int32_t* active, int nactive, int flags, double alpha,
+                              const double* dR, int64_t r_stride, double beta_r, double* dY, int64_t y_stride,
+                              int* variant_out);
+
 /* Structure of the preconditioner cycle of level `level` (0: this context, 1: its child level, ...), for
  * tests.  sizes_out[16] = [nv, np, nbv, nbp, bs, kc, kcv, kcp, smoothed aggregation, nnz(P), has a child level,
  * folded cycle, rectangle last sweep, FP32-stored operands, 0, 0].  Call with the arrays NULL for the sizes,
@@ -527,6 +545,20 @@ int ricadi_host_plan_levels(int nv, int np, const int32_t* a_rowptr, const int32
                             const int32_t* e_rowptr, const int32_t* e_col, const double* e_val,
                             const int32_t* j_rowptr, const int32_t* j_col, const double* j_val,
                             const ricadi_opts* opts, int32_t* out);
+/* The row-block tile format of the saddle SpMM that ricadi_set_operator would build (host only), for tests.
+ * sizes_out[8] = [n, nblk, max_cols, max_nnz, nnz(S), tiles usable, multi-shift form built, nv].  Call with
+ * the arrays NULL for the sizes, then again with rows2[nblk*32] (global row per local row, -1 = none),
+ * rp2[nblk*33] (entry range per local row, in tile order), cols2[nblk*max(max_cols,1)] (global column per tile
+ * slot, -1 = none), lidx[nnz] (tile slot per entry), perm[nnz] (index of the entry in the saddle CSR), the
+ * saddle CSR s_rp[n+1], s_ci[nnz] and its value sources s_src[3*nnz] (cal A, cal E, J / J^T parts, one array
+ * after the other); with the multi-shift form also lidx_ms[nnz] (tile slot | 0x8000 for velocity-velocity
+ * entries), vAJ[nnz] (cal A + J part) and vE[nnz] (cal E part), in tile order.  Any array may be NULL.  */
+int ricadi_host_saddle_tiles(int nv, int np, const int32_t* a_rowptr, const int32_t* a_col, const double* a_val,
+                             const int32_t* e_rowptr, const int32_t* e_col, const double* e_val,
+                             const int32_t* j_rowptr, const int32_t* j_col, const double* j_val,
+                             const ricadi_opts* opts, int32_t* sizes_out, int32_t* rows2, int32_t* rp2,
+                             int32_t* cols2, uint16_t* lidx, uint16_t* lidx_ms, double* vAJ, double* vE,
+                             int32_t* perm, int32_t* s_rp, int32_t* s_ci, double* s_src);
 /* Greedy BFS aggregation of the graph of a CSR pattern into blocks of at
  * most bsize rows; blk_out[n]; returns the number of blocks (or <0).        */
 int ricadi_host_aggregate(int n, const int32_t* rowptr, const int32_t* col,

@@ -40,6 +40,7 @@ class RicadiAdiParams(C.Structure):
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _vp = C.c_void_p
+_up = C.POINTER(C.c_uint16)
 
 # name -> (restype, argtypes); every symbol declared in include/ricadi.h
 SIGNATURES = {
@@ -114,6 +115,12 @@ SIGNATURES = {
     "ricadi_precond_apply_batch_dev": (C.c_int, [_vp, C.c_int, _dp, _dp, _vp, C.c_int64, C.c_int, _ip, C.c_int,
                                                  _vp, C.POINTER(C.c_int)]),
     "ricadi_precond_structure": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _dp]),
+    "ricadi_op_apply_batch_dev": (C.c_int, [_vp, C.c_int, _dp, _dp, _vp, C.c_int64, C.c_int, _ip, C.c_int, C.c_int,
+                                            C.c_double, _vp, C.c_int64, C.c_double, _vp, C.c_int64,
+                                            C.POINTER(C.c_int)]),
+    "ricadi_host_saddle_tiles": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp,
+                                           C.POINTER(RicadiOpts), _ip, _ip, _ip, _ip, _up, _up, _dp, _dp, _ip, _ip,
+                                           _ip, _dp]),
     "ricadi_host_deal": (C.c_int, [_dp, C.c_int, C.c_int, _ip]),
     "ricadi_host_sa_criterion": (C.c_int, [C.c_int, _ip, _ip, _dp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_int)]),
@@ -740,6 +747,25 @@ class Context:
                                                       0 if act is None else act.size, z_ptr, C.byref(form)))
         return self.decode_precond_form(form.value)
 
+    # flags of op_apply_batch_dev (RICADI_OA_* of include/ricadi.h)
+    OA_X32, OA_Y32, OA_LOWRANK, OA_RESIDUAL = 1, 2, 4, 8
+
+    def op_apply_batch_dev(self, alphas, betas, x_ptr, x_stride, m, y_ptr, y_stride, active=None, flags=0,
+                           alpha=1.0, r_ptr=None, r_stride=0, beta_r=0.0):
+        """``Y_g = beta_r R_g + alpha S(alphas[g], betas[g]) X_g`` as the lockstep GMRES launches the saddle product,
+        on ``len(alphas)`` device FP64 panels of width ``m`` (``X_g = x_ptr + g*x_stride`` and so on, strides in
+        elements); ``active``: the group ids to apply it to (the other panels of Y are not written); ``flags``:
+        ``OA_*``.  Returns the kernel form that ran (``k1_variant`` of ``setup_info``)."""
+        al = np.ascontiguousarray(alphas, dtype=np.float64)
+        be = np.ascontiguousarray(betas, dtype=np.float64)
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        var = C.c_int(-1)
+        _chk(self._lib.ricadi_op_apply_batch_dev(self._h, al.size, _d(al), _d(be), x_ptr, int(x_stride), int(m),
+                                                 None if act is None else _i(act), 0 if act is None else act.size,
+                                                 int(flags), float(alpha), r_ptr, int(r_stride), float(beta_r),
+                                                 y_ptr, int(y_stride), C.byref(var)))
+        return int(var.value)
+
     def precond_structure(self, level=0):
         """Structure of the preconditioner cycle of ``level`` (0 this context, 1 its child level): dict with the
         velocity / pressure block lists (``bv_ptr``, ``bv_rows``, ``bp_ptr``, ``bp_rows``), ``aggof`` (dof ->
@@ -890,6 +916,43 @@ def host_plan_levels(calA, calE, J, **opts):
     _chk(load().ricadi_host_plan_levels(a[3][0], j[3][0], _i(a[0]), _i(a[1]), _d(a[2]), _i(e[0]), _i(e[1]), _d(e[2]),
                                         _i(j[0]), _i(j[1]), _d(j[2]), C.byref(o), _i(out)))
     return dict(levels=int(out[0]), kc=int(out[1]), kcv=int(out[2]), kcp=int(out[3]), smoothed=bool(out[4]))
+
+
+def host_saddle_tiles(calA, calE, J, **opts):
+    """The row-block tile format of the saddle SpMM that ``set_operator`` would build
+    (``ricadi_host_saddle_tiles``; host only): dict with ``n``, ``nv``, ``nblk``, ``max_cols``, ``max_nnz``,
+    ``nnz``, ``sb_ok``, ``ms_ok``, the tile arrays ``rows2`` (nblk x 32), ``rp2`` (nblk x 33), ``cols2``
+    (nblk x max cols), ``lidx``, ``perm`` (tile order -> saddle CSR entry), the saddle CSR ``s_rp``, ``s_ci`` with
+    its value sources ``src_a``, ``src_e``, ``src_j``, and with ``ms_ok`` the multi-shift operands ``lidx_ms``,
+    ``vAJ``, ``vE`` (else None)."""
+    a, e = as_csr(calA), as_csr(calE)
+    nv = a[3][0]
+    j = as_csr(J) if J is not None and J.shape[0] > 0 else None
+    np_ = 0 if j is None else j[3][0]
+    jargs = (None, None, None) if j is None else (_i(j[0]), _i(j[1]), _d(j[2]))
+    o = default_opts(**opts)
+    lib = load()
+    sz = np.zeros(8, dtype=np.int32)
+
+    def call(*arrs):
+        _chk(lib.ricadi_host_saddle_tiles(nv, np_, _i(a[0]), _i(a[1]), _d(a[2]), _i(e[0]), _i(e[1]), _d(e[2]),
+                                          *jargs, C.byref(o), _i(sz), *arrs))
+
+    call(*[None] * 11)
+    n, nblk, max_cols, max_nnz, nnz, sb_ok, ms_ok, nv_ = (int(x) for x in sz)
+    out = dict(rows2=np.zeros((nblk, 32), np.int32), rp2=np.zeros((nblk, 33), np.int32),
+               cols2=np.zeros((nblk, max(max_cols, 1)), np.int32), lidx=np.zeros(nnz, np.uint16),
+               lidx_ms=np.zeros(nnz, np.uint16), vAJ=np.zeros(nnz), vE=np.zeros(nnz), perm=np.zeros(nnz, np.int32),
+               s_rp=np.zeros(n + 1, np.int32), s_ci=np.zeros(nnz, np.int32), s_src=np.zeros(3 * nnz))
+    u16 = lambda x: x.ctypes.data_as(_up)   # noqa: E731
+    call(_i(out["rows2"]), _i(out["rp2"]), _i(out["cols2"]), u16(out["lidx"]), u16(out["lidx_ms"]), _d(out["vAJ"]),
+         _d(out["vE"]), _i(out["perm"]), _i(out["s_rp"]), _i(out["s_ci"]), _d(out["s_src"]))
+    src = out.pop("s_src")
+    out.update(src_a=src[:nnz], src_e=src[nnz:2 * nnz], src_j=src[2 * nnz:], n=n, nv=nv_, nblk=nblk,
+               max_cols=max_cols, max_nnz=max_nnz, nnz=nnz, sb_ok=bool(sb_ok), ms_ok=bool(ms_ok))
+    if not ms_ok:
+        out.update(lidx_ms=None, vAJ=None, vE=None)
+    return out
 
 
 def host_sa_criterion(calA):

@@ -1143,6 +1143,56 @@ int ricadi_host_plan_levels(int nv, int np, const int32_t* a_rp, const int32_t* 
   return RICADI_OK;
 }
 
+int ricadi_host_saddle_tiles(int nv, int np, const int32_t* a_rp, const int32_t* a_ci, const double* a_v,
+                             const int32_t* e_rp, const int32_t* e_ci, const double* e_v, const int32_t* j_rp,
+                             const int32_t* j_ci, const double* j_v, const ricadi_opts* opts, int32_t* sizes_out,
+                             int32_t* rows2, int32_t* rp2, int32_t* cols2, uint16_t* lidx, uint16_t* lidx_ms,
+                             double* vAJ, double* vE, int32_t* perm, int32_t* s_rp, int32_t* s_ci, double* s_src) {
+  if (nv < 1 || np < 0 || !a_rp || !a_ci || !a_v || !e_rp || !e_ci || !e_v || (np > 0 && (!j_rp || !j_ci || !j_v)) ||
+      !opts || !sizes_out) {
+    ricadi::set_error("ricadi_host_saddle_tiles: bad argument");
+    return RICADI_EINVAL;
+  }
+  try {
+    const ricadi::HostCsr A = ricadi::make_csr(nv, nv, a_rp, a_ci, a_v), E = ricadi::make_csr(nv, nv, e_rp, e_ci, e_v);
+    const int32_t zero = 0;
+    const ricadi::HostCsr J = np > 0 ? ricadi::make_csr(np, nv, j_rp, j_ci, j_v) : ricadi::make_csr(0, nv, &zero, &zero, a_v);
+    ricadi::HostSetup hs;
+    const double sa_omega = (np == 0 || opts->bj_block != 32) ? 0.0 : 0.5;
+    ricadi::build_setup_checked(A, E, J, *opts, hs, std::max(2, opts->max_levels), sa_omega);
+    const ricadi::PrecondRecords r = ricadi::build_records(hs, J, ricadi::transpose(J), false, true);
+    const int nb = hs.sb_nblk, mc = std::max(hs.sb_max_cols, 1);
+    const size_t nnz = hs.s_ci.size();
+    const int32_t sz[8] = {hs.n, nb, hs.sb_max_cols, hs.sb_max_nnz, (int32_t)nnz, r.sb_ok ? 1 : 0, r.ms_ok ? 1 : 0,
+                           hs.nv};
+    std::copy(sz, sz + 8, sizes_out);
+    auto out = [](auto* dst, const auto& src, size_t cnt) {
+      if (dst) std::copy(src.begin(), src.begin() + cnt, dst);
+    };
+    out(rows2, r.sb_rows2, (size_t)nb * 32);
+    out(rp2, r.sb_rp2, (size_t)nb * 33);
+    out(cols2, r.sb_cols2, (size_t)nb * mc);
+    out(lidx, hs.sb_lidx, nnz);
+    out(perm, hs.sb_perm, nnz);
+    out(s_rp, hs.s_rp, (size_t)hs.n + 1);
+    out(s_ci, hs.s_ci, nnz);
+    if (s_src) {
+      out(s_src, hs.s_srcA, nnz);
+      out(s_src + nnz, hs.s_srcE, nnz);
+      out(s_src + 2 * nnz, hs.s_srcJ, nnz);
+    }
+    if (r.ms_ok) {
+      out(lidx_ms, r.sb_lidx_ms, nnz);
+      out(vAJ, r.sbAJ, nnz);
+      out(vE, r.sbE, nnz);
+    }
+  } catch (...) {
+    ricadi::set_error("ricadi_host_saddle_tiles: exception");
+    return RICADI_EINVAL;
+  }
+  return RICADI_OK;
+}
+
 int ricadi_host_deal(const double* shifts, int ns, int world, int32_t* owner_out) {
   if (!shifts || !owner_out || ns < 1 || world < 1) {
     ricadi::set_error("ricadi_host_deal: bad argument");

@@ -345,8 +345,9 @@ void launch_spmm_rowwave(hipStream_t st, const GroupTab& gt, int nrows, const in
 // the block index alone: the kernel is bound by the latency of its dependent
 // loads, and this removes one full round trip (block pointers -> row/column lists).
 // HAS_R / HAS_LR: compile the residual term / the low-rank epilogue in (the plain
-// operator launch of the GMRES iteration has neither).
-template <bool HAS_R, bool HAS_LR, class XT = double>
+// operator launch of the GMRES iteration has neither).  F4: the 16-byte tile fill of an
+// FP32 x (launcher: m = ldx = 16 and every group base 16-byte aligned, f4_fill_ok).
+template <bool HAS_R, bool HAS_LR, class XT = double, bool F4 = false>
 __global__ __launch_bounds__(256) void spmm_blocked_kernel(
     const int* __restrict__ rows2, const int* __restrict__ rp2, const int* __restrict__ cols2,
     const uint16_t* __restrict__ lidx, GroupTab gt, GroupPtrs vals,
@@ -399,7 +400,8 @@ __global__ __launch_bounds__(256) void spmm_blocked_kernel(
   // LDS stores -- so that the loads are in flight together (a load followed by
   // its own ds_write makes hipcc wait vmcnt(0) per row).
   constexpr int XJ = 5;                        // 16 groups x 5 = 80 tile rows per pass
-  if (sizeof(XT) == 4 && m == 16) {
+  if constexpr (F4) {
+    static_assert(sizeof(XT) == 4, "16-byte tile fill: FP32 x only");
     // FP32 rows of 16 columns are 64 B: a lane takes FOUR columns (16-byte load), a 16-lane group four rows per load
     // -- a quarter of the gather instructions of the one-column form.  (That form made the FP32-input kernel 10 %
     // slower than the FP64-input one -- same number of row requests, nothing gained from the smaller rows; two columns
@@ -559,6 +561,12 @@ void launch_spmm_blocked_b(hipStream_t st, const GroupTab& gt, int nblk, const i
 #undef RICADI_TILE_LAUNCH
 }
 
+// The 16-byte tile fill of an FP32 x reads a row as four float4 at a fixed stride of 16 floats from the group base:
+// only for packed 16-column panels whose group bases are 16-byte aligned (else the one-column fill)
+static bool f4_fill_ok(const float* x, int m, int ldx, size_t gsx) {
+  return m == 16 && ldx == 16 && gsx % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0;
+}
+
 // plain operator product with an FP32-stored x (the flexible GMRES applies S to the stored Z_j): the x tile
 // is converted while it is staged, the inner loop is the same
 void launch_spmm_blocked_x32(hipStream_t st, const GroupTab& gt, int nblk, const int* rows2, const int* rp2,
@@ -567,9 +575,14 @@ void launch_spmm_blocked_x32(hipStream_t st, const GroupTab& gt, int nblk, const
   if (nblk <= 0 || gt.ng <= 0) return;
   const dim3 grid(nblk, 1, gt.ng), block(256);
   const size_t lds = spmm_blocked_lds_bytes(m, max_cols, 0);
-  hipLaunchKernelGGL((spmm_blocked_kernel<false, false, float>), grid, block, lds, st, rows2, rp2, cols2, lidx, gt,
-                     vals, x, ldx, gsx, y, ldy, gsy, (const double*)nullptr, 0, (size_t)0, alpha, 0.0, m, max_cols,
-                     LowRankArgs(), y32);
+  if (f4_fill_ok(x, m, ldx, gsx))
+    hipLaunchKernelGGL((spmm_blocked_kernel<false, false, float, true>), grid, block, lds, st, rows2, rp2, cols2, lidx,
+                       gt, vals, x, ldx, gsx, y, ldy, gsy, (const double*)nullptr, 0, (size_t)0, alpha, 0.0, m,
+                       max_cols, LowRankArgs(), y32);
+  else
+    hipLaunchKernelGGL((spmm_blocked_kernel<false, false, float>), grid, block, lds, st, rows2, rp2, cols2, lidx, gt,
+                       vals, x, ldx, gsx, y, ldy, gsy, (const double*)nullptr, 0, (size_t)0, alpha, 0.0, m, max_cols,
+                       LowRankArgs(), y32);
 }
 
 // ---------------------------------------------------------------------------
@@ -652,7 +665,7 @@ __global__ __launch_bounds__(256) void spmm_blocked_ms_kernel(
   // FP32 rows of 16 columns (64 B): four columns per lane, 64 tile rows per pass of the workgroup -- three 16-byte
   // loads per thread and group instead of ten 4-byte ones (the per-group kernel gained 27 % from the same change)
   constexpr int XQ = 3;
-  constexpr bool f4 = F4;                    // launcher: XT = float, m = ldx = 16
+  constexpr bool f4 = F4;                    // launcher: XT = float, m = ldx = 16, aligned group bases (f4_fill_ok)
   const int j4 = threadIdx.x >> 2, c4 = (threadIdx.x & 3) * 4;
   int xoff4[XQ];
   float4 xv4[XQ];
@@ -806,7 +819,7 @@ void launch_spmm_blocked_ms_x32(hipStream_t st, const GroupTab& gt, const double
   while (ysplit < gt.ng && (long)nblk * ysplit < 900 && ysplit < 8) ysplit *= 2;
   ysplit = std::min(ysplit, gt.ng);
   const dim3 grid(nblk, ysplit, 1), block(256);
-  if (m == 16 && ldx == 16 && max_cols <= 192)
+  if (f4_fill_ok(x, m, ldx, gsx) && max_cols <= 192)
     hipLaunchKernelGGL((spmm_blocked_ms_kernel<false, float, true>), grid, block, spmm_blocked_ms_lds_bytes(max_cols), st,
                        rows2, rp2, cols2, lidx, gt, cf, vAJ, vE, x, ldx, gsx, y, ldy, gsy, (const double*)nullptr, 0,
                        (size_t)0, alpha, 0.0, m, max_cols, y32);

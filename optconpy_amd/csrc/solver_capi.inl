@@ -602,6 +602,72 @@ int ricadi_precond_apply_batch_dev(ricadi_ctx* c, int ng, const double* alphas, 
   API_END
 }
 
+int ricadi_op_apply_batch_dev(ricadi_ctx* c, int ng, const double* alphas, const double* betas, const double* dX,
+                              int64_t x_stride, int m, const int32_t* active, int nactive, int flags, double alpha,
+                              const double* dR, int64_t r_stride, double beta_r, double* dY, int64_t y_stride,
+                              int* variant_out) {
+  if (int rc = check_panel(c, m)) return rc;
+  REQUIRE(dX && dY && alphas && betas, RICADI_EINVAL, "NULL argument");
+  REQUIRE(ng >= 1 && ng <= RICADI_MAX_GROUPS && (size_t)ng * m <= 2048, RICADI_EINVAL,
+          "1 <= ng <= 16 and ng*m <= 2048 required");
+  REQUIRE((flags & ~(RICADI_OA_X32 | RICADI_OA_Y32 | RICADI_OA_LOWRANK | RICADI_OA_RESIDUAL)) == 0, RICADI_EINVAL,
+          "unknown flag");
+  const int64_t nm = (int64_t)c->n * m;
+  REQUIRE(x_stride >= nm && y_stride >= nm, RICADI_EINVAL, "bad x_stride / y_stride");
+  const bool res = flags & RICADI_OA_RESIDUAL, x32 = flags & RICADI_OA_X32, y32 = flags & RICADI_OA_Y32;
+  const bool lowrank = (flags & RICADI_OA_LOWRANK) && c->q > 0;
+  REQUIRE(!res || (dR && r_stride >= nm), RICADI_EINVAL, "residual form: r and r_stride >= n*m required");
+  // the FP32 operand forms exist in the tile kernels' plain product only (saddle_spmm)
+  REQUIRE(!x32 || (saddle_tiled(c, m) && !res && !lowrank), RICADI_EINVAL,
+          "FP32 input: only the plain product where the tiles fit");
+  REQUIRE(!y32 || x32, RICADI_EINVAL, "FP32 output: with the FP32 input only");
+  std::vector<int> ids;
+  if (active) {
+    for (int i = 0; i < nactive; ++i) {
+      REQUIRE(active[i] >= 0 && active[i] < ng && std::find(ids.begin(), ids.end(), active[i]) == ids.end(),
+              RICADI_EINVAL, "active: distinct group ids in [0, ng) required");
+      ids.push_back(active[i]);
+    }
+    REQUIRE(!ids.empty(), RICADI_EINVAL, "no active group");
+  }
+  API_BEGIN
+  hipStream_t st = c->st;
+  std::vector<ShiftData*> sds(ng);
+  get_shifts(c, alphas, betas, ng, sds.data());
+  ensure_work(c, m, ng, 0);
+  Batch bt = make_batch(c, sds.data(), ng, m);
+  if (active) bt.set(ids);
+  else bt.all();
+  // FP32 copies of x / y with the caller's group strides (as the iteration stores Z_j and w)
+  DArr<float> xf, yf;
+  if (x32) {
+    xf.alloc((size_t)x_stride * ng);
+    for (int i = 0; i < bt.tab.ng; ++i) {
+      const size_t g = (size_t)bt.tab.gid[i];
+      launch_to_f32(st, c->n, m, dX + g * x_stride, m, xf.p + g * x_stride, m);
+    }
+  }
+  if (y32) yf.alloc((size_t)y_stride * ng);
+  const LowRankArgs lr = lowrank ? lowrank_args(c, bt, dX, (size_t)x_stride) : LowRankArgs();
+  saddle_spmm(c, bt, dX, (size_t)x_stride, nullptr, dY, (size_t)y_stride, res ? dR : nullptr,
+              res ? (size_t)r_stride : 0, alpha, res ? beta_r : 0.0, lr, xf.p, yf.p);
+  if (y32) {
+    std::vector<float> h32((size_t)nm);
+    std::vector<double> h64((size_t)nm);
+    for (int i = 0; i < bt.tab.ng; ++i) {
+      const size_t g = (size_t)bt.tab.gid[i];
+      HIPCHK(hipMemcpyAsync(h32.data(), yf.p + g * y_stride, sizeof(float) * nm, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (int64_t k = 0; k < nm; ++k) h64[k] = h32[k];
+      HIPCHK(hipMemcpyAsync(dY + g * y_stride, h64.data(), sizeof(double) * nm, hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  if (variant_out) *variant_out = c->k1_variant;
+  API_END
+}
+
 int ricadi_precond_structure(ricadi_ctx* c, int level, int32_t* sizes_out, int32_t* bv_ptr, int32_t* bv_rows,
                              int32_t* bp_ptr, int32_t* bp_rows, int32_t* aggof, int32_t* p_rp, int32_t* p_ci,
                              double* p_v) {

@@ -151,21 +151,23 @@ static void saddle_spmm(ricadi_ctx* c, const Batch& bt, const double* x, size_t 
 // y = S(alpha,beta) x for every active group (n x m panels, ld = m, group stride gsx /
 // bt.gs); optional low-rank  - U V^T x_v  (U, V shared by the groups)
 // y32 (optional, with x32 only): the product goes to this FP32 panel (stride bt.gs) and y is not written
+// the low-rank term - U V^T x of the active groups (none without set_lowrank): the coefficients V^T x first; the
+// product with U rides in the SpMM's epilogue
+static LowRankArgs lowrank_args(ricadi_ctx* c, const Batch& bt, const double* x, size_t gsx) {
+  LowRankArgs lr;
+  if (c->q <= 0) return lr;
+  HIPCHK(hipMemsetAsync(c->lrc.p, 0, sizeof(double) * bt.gsq * bt.G, bt.st));
+  launch_gemm_tn_b(bt.st, bt.tab, c->nv, c->q, bt.m, c->V.p, c->q, x, bt.m, gsx, c->lrc.p, bt.m, bt.gsq);
+  lr.U = c->U.p;
+  lr.c = c->lrc.p;
+  lr.gsc = bt.gsq;
+  lr.q = c->q;
+  lr.nrows = c->nv;
+  return lr;
+}
 static void op_apply(ricadi_ctx* c, const Batch& bt, const double* x, size_t gsx, double* y,
                      bool lowrank, const float* x32 = nullptr, float* y32 = nullptr) {
-  hipStream_t st = bt.st;
-  const int m = bt.m;
-  LowRankArgs lr;
-  if (lowrank && c->q > 0) {
-    // coefficients V^T x first; the product with U rides in the SpMM's epilogue
-    HIPCHK(hipMemsetAsync(c->lrc.p, 0, sizeof(double) * bt.gsq * bt.G, st));
-    launch_gemm_tn_b(st, bt.tab, c->nv, c->q, m, c->V.p, c->q, x, m, gsx, c->lrc.p, m, bt.gsq);
-    lr.U = c->U.p;
-    lr.c = c->lrc.p;
-    lr.gsc = bt.gsq;
-    lr.q = c->q;
-    lr.nrows = c->nv;
-  }
+  const LowRankArgs lr = lowrank ? lowrank_args(c, bt, x, gsx) : LowRankArgs();
   saddle_spmm(c, bt, x, gsx, nullptr, y, bt.gs, nullptr, 0, 1.0, 0.0, lr, x32, y32);
 }
 // ---- kernels of the preconditioner that ricadi_time_kernel_dev also launches on their own

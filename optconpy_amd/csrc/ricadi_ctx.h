@@ -227,6 +227,7 @@ struct Exec {
   rocblas_handle rb = nullptr;
   DevPool* pool = nullptr;
   int* info = nullptr;
+  int* flag = nullptr;        // its own flag words; a setup raises [0] (singular block) and [2] (vanishing coarse pivot)
 };
 
 // The library's switches: environment variables RICADI_*, read once when a context is created (read_switches in
@@ -254,6 +255,8 @@ struct Switches {
   bool lowsync = true;        // RICADI_ARNOLDI=cgs2: the three-pass CGS2 Arnoldi on the hot path instead of the
                               // one-reduction form
   bool split = true;          // RICADI_SPLIT=0: the lockstep GMRES batch on one stream instead of two half-batches
+  bool setup_overlap = true;  // RICADI_SETUP_OVERLAP=0: the ADI shifts and the projection operator set up in one batch
+                              // before the projection solve, instead of the shifts' setup beside it (setup_overlap_begin)
 };
 
 }  // namespace ricadi
@@ -354,6 +357,9 @@ struct ricadi_ctx {
   DArr<double*> eptrs;
   DArr<double> gj_cb, gj_rp, gj_rb, gj_d;   // block Gauss-Jordan inverse of the coarse matrices
   DArr<double*> gj_ptrs;
+  double** gj_hptrs = nullptr;   // pinned host side of gj_ptrs: an upload reads it asynchronously (setup_issue)
+  size_t gj_hcap = 0;
+  DArr<int> flag2;               // flag words of the auxiliary Exec
   double* h_resid = nullptr;  // pinned, 4 slots of MAX_GROUPS*MAX_M: norms, rhs norms, two residual slots
   hipEvent_t ev_res[2] = {nullptr, nullptr};
   // the second half-batch of the lockstep GMRES (half_stream; created on first use): its stream, the events of its
@@ -416,6 +422,7 @@ struct ricadi_ctx {
 
   ~ricadi_ctx() {
     if (h_resid) (void)hipHostFree(h_resid);
+    if (gj_hptrs) (void)hipHostFree(gj_hptrs);
     if (xcomm && xcomm_owned) (void)ncclCommDestroy(xcomm);
     for (int i = 0; i < 2; ++i) {
       if (ev_res[i]) (void)hipEventDestroy(ev_res[i]);

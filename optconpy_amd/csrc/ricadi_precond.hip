@@ -894,128 +894,211 @@ void launch_block_combine(hipStream_t st, size_t n, const double* Ba, const doub
 // not its diagonal).  One workgroup per pressure block loops over the coupled
 // velocity blocks; both bs x bs products go through LDS.  Measured on the CPU
 // mirror (N = 58): GMRES iterations 170 / 115 / 61 -> 108 / 74 / 43.
+// The 256 threads form a 16 x 16 grid: thread (ty, tx) owns the R x R outputs at rows ty + 16 a, columns
+// tx + 16 b (R = bs / 16), so a k-step reads 2 R operands from LDS for R^2 FMAs.  The operands sit in LDS with
+// leading dimension bs + 1: the column reads of Jd in the second product (a 32-way bank conflict at stride bs in
+// the one-output-per-thread form, 1.6 ms per call at cfg2) are conflict-free.  The next pair's J slice and
+// velocity inverse are loaded into registers while the current pair is multiplied.  Every output is still a
+// chain of FMAs over the inner index added to its accumulator, in the same order: the result is bitwise that
+// of the one-output-per-thread form.
+template <int R>
 __global__ __launch_bounds__(256) void schur_blocks_bj_kernel(
-    int bs, const int* __restrict__ bptr, const int* __restrict__ jd_ptr,
+    const int* __restrict__ bptr, const int* __restrict__ jd_ptr,
     const int* __restrict__ jd_vblk, const double* __restrict__ jd_val,
     GroupPtrs bvinvs, GroupPtrs blockss) {
+  constexpr int BS = 16 * R, LD = BS + 1, NEL = BS * BS, PER = NEL / 256;
   // one launch serves all shifts being set up: blockIdx.y = shift
   const double* __restrict__ bvinv = bvinvs.p[blockIdx.y];
   double* __restrict__ blocks = const_cast<double*>(blockss.p[blockIdx.y]);
-  extern __shared__ double sm[];           // Jd, Ai, T : 3 x bs x bs
+  extern __shared__ double sm[];           // Jd, Ai, T : 3 x bs x (bs + 1)
   double* Jd = sm;
-  double* Ai = sm + bs * bs;
-  double* T = sm + 2 * bs * bs;
+  double* Ai = sm + BS * LD;
+  double* T = sm + 2 * BS * LD;
   const int b = blockIdx.x;
   const int nb = bptr[b + 1] - bptr[b];
-  const int nel = bs * bs;
-  double acc[16];                           // bs <= 64: at most 4096 / 256 outputs per thread
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  double acc[R][R];
 #pragma unroll
-  for (int t = 0; t < 16; ++t) acc[t] = 0.0;
-  for (int pr = jd_ptr[b]; pr < jd_ptr[b + 1]; ++pr) {
-    const double* jsrc = jd_val + (size_t)pr * nel;
-    const double* asrc = bvinv + (size_t)jd_vblk[pr] * nel;
-    for (int e = threadIdx.x; e < nel; e += 256) {
-      Jd[e] = jsrc[e];
-      Ai[e] = asrc[e];
+  for (int a = 0; a < R; ++a)
+#pragma unroll
+    for (int c = 0; c < R; ++c) acc[a][c] = 0.0;
+  const int p0 = jd_ptr[b], p1 = jd_ptr[b + 1];
+  double pj[PER], pa[PER];                  // the pair in flight (global -> registers -> LDS)
+  auto load = [&](int pr) {
+    const double* jsrc = jd_val + (size_t)pr * NEL;
+    const double* asrc = bvinv + (size_t)jd_vblk[pr] * NEL;
+#pragma unroll
+    for (int t = 0; t < PER; ++t) {
+      pj[t] = jsrc[threadIdx.x + 256 * t];
+      pa[t] = asrc[threadIdx.x + 256 * t];
+    }
+  };
+  if (p0 < p1) load(p0);
+  for (int pr = p0; pr < p1; ++pr) {
+#pragma unroll
+    for (int t = 0; t < PER; ++t) {
+      const int e = threadIdx.x + 256 * t, i = e / BS, c = e - i * BS;
+      Jd[i * LD + c] = pj[t];
+      Ai[i * LD + c] = pa[t];
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < nel; e += 256) {     // T = Jd * Ai
-      const int i = e / bs, c = e - i * bs;
-      double s = 0.0;
-      for (int j = 0; j < bs; ++j) s = fma(Jd[i * bs + j], Ai[j * bs + c], s);
-      T[e] = s;
+    if (pr + 1 < p1) load(pr + 1);
+    double s[R][R];                                      // T = Jd * Ai
+#pragma unroll
+    for (int a = 0; a < R; ++a)
+#pragma unroll
+      for (int c = 0; c < R; ++c) s[a][c] = 0.0;
+#pragma unroll 4
+    for (int j = 0; j < BS; ++j) {
+      double jv[R], av[R];
+#pragma unroll
+      for (int a = 0; a < R; ++a) jv[a] = Jd[(ty + 16 * a) * LD + j];
+#pragma unroll
+      for (int c = 0; c < R; ++c) av[c] = Ai[j * LD + tx + 16 * c];
+#pragma unroll
+      for (int a = 0; a < R; ++a)
+#pragma unroll
+        for (int c = 0; c < R; ++c) s[a][c] = fma(jv[a], av[c], s[a][c]);
     }
+#pragma unroll
+    for (int a = 0; a < R; ++a)
+#pragma unroll
+      for (int c = 0; c < R; ++c) T[(ty + 16 * a) * LD + tx + 16 * c] = s[a][c];
     __syncthreads();
-    for (int e = threadIdx.x, t = 0; e < nel; e += 256, ++t) {   // acc += T * Jd^T
-      const int i = e / bs, k = e - i * bs;
-      double s = 0.0;
-      for (int c = 0; c < bs; ++c) s = fma(T[i * bs + c], Jd[k * bs + c], s);
-      acc[t] += s;
+#pragma unroll
+    for (int a = 0; a < R; ++a)                          // acc += T * Jd^T
+#pragma unroll
+      for (int k = 0; k < R; ++k) s[a][k] = 0.0;
+#pragma unroll 4
+    for (int c = 0; c < BS; ++c) {
+      double tv[R], jk[R];
+#pragma unroll
+      for (int a = 0; a < R; ++a) tv[a] = T[(ty + 16 * a) * LD + c];
+#pragma unroll
+      for (int k = 0; k < R; ++k) jk[k] = Jd[(tx + 16 * k) * LD + c];
+#pragma unroll
+      for (int a = 0; a < R; ++a)
+#pragma unroll
+        for (int k = 0; k < R; ++k) s[a][k] = fma(tv[a], jk[k], s[a][k]);
     }
+#pragma unroll
+    for (int a = 0; a < R; ++a)
+#pragma unroll
+      for (int k = 0; k < R; ++k) acc[a][k] += s[a][k];
     __syncthreads();
   }
-  double* Bb = blocks + (size_t)b * nel;
-  for (int e = threadIdx.x, t = 0; e < nel; e += 256, ++t) {
-    const int i = e / bs, k = e - i * bs;
-    Bb[e] = (i < nb && k < nb) ? acc[t] : (i == k ? 1.0 : 0.0);
-  }
+  double* Bb = blocks + (size_t)b * NEL;
+#pragma unroll
+  for (int a = 0; a < R; ++a)
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = ty + 16 * a, kk = tx + 16 * k;
+      Bb[i * BS + kk] = (i < nb && kk < nb) ? acc[a][k] : (i == kk ? 1.0 : 0.0);
+    }
 }
 void launch_schur_blocks_bj(hipStream_t st, int nshift, int nblocks, int bs, const int* bptr,
                             const int* jd_ptr, const int* jd_vblk, const double* jd_val,
                             const GroupPtrs& bvinv, const GroupPtrs& blocks) {
   if (nblocks <= 0) return;
-  hipLaunchKernelGGL(schur_blocks_bj_kernel, dim3(nblocks, nshift), dim3(256),
-                     (size_t)3 * bs * bs * sizeof(double), st, bs, bptr, jd_ptr, jd_vblk, jd_val, bvinv,
-                     blocks);
+  const size_t lds = (size_t)3 * bs * (bs + 1) * sizeof(double);
+  const dim3 grid(nblocks, nshift);
+  if (bs == 16)
+    hipLaunchKernelGGL(schur_blocks_bj_kernel<1>, grid, dim3(256), lds, st, bptr, jd_ptr, jd_vblk, jd_val, bvinv, blocks);
+  else if (bs == 32)
+    hipLaunchKernelGGL(schur_blocks_bj_kernel<2>, grid, dim3(256), lds, st, bptr, jd_ptr, jd_vblk, jd_val, bvinv, blocks);
+  else   // 64: the block-Jacobi partition makes no other size (ricadi_host.cpp)
+    hipLaunchKernelGGL(schur_blocks_bj_kernel<4>, grid, dim3(256), lds, st, bptr, jd_ptr, jd_vblk, jd_val, bvinv, blocks);
 }
 
 // In-place inverse of dense bs x bs blocks by Gauss-Jordan with partial
 // pivoting in LDS; one workgroup per block.  flag[0] is set to 1 on a zero pivot.
-__global__ __launch_bounds__(256) void block_invert_kernel(int bs, const int* __restrict__ bptr,
-                                                           GroupPtrs blockss,
+// Per step every wave finds the pivot itself (one row per lane, a butterfly argmax that keeps the first of equal
+// magnitudes -- the row a serial scan with `>` picks), then every thread computes its entries of the swapped,
+// scaled and eliminated matrix into registers from the old one and writes them back after a barrier: two
+// barriers per step instead of a single-thread scan and five barriers.  Each entry gets the same operations as in
+// the swap / scale / update / zero sequence (a - a_ik * (a_pj * (1 / pivot))): the result is bitwise the same.
+template <int BS>
+__global__ __launch_bounds__(256) void block_invert_kernel(const int* __restrict__ bptr, GroupPtrs blockss,
                                                            int* __restrict__ flag) {
+  constexpr int W = 2 * BS, PER = BS * W / 256;
   double* __restrict__ blocks = const_cast<double*>(blockss.p[blockIdx.y]);   // blockIdx.y = shift
   extern __shared__ double sm[];  // bs x (2*bs) augmented matrix
-  __shared__ int piv;
-  __shared__ double pivval;
-  const int W = 2 * bs;
-  double* Bb = blocks + (size_t)blockIdx.x * bs * bs;
+  double* Bb = blocks + (size_t)blockIdx.x * BS * BS;
   // rows / columns beyond the block's true size are identity padding
-  const int nb = bptr ? bptr[blockIdx.x + 1] - bptr[blockIdx.x] : bs;
-  for (int e = threadIdx.x; e < bs * W; e += blockDim.x) {
-    const int i = e / W, j = e - i * W;
+  const int nb = bptr ? bptr[blockIdx.x + 1] - bptr[blockIdx.x] : BS;
+#pragma unroll
+  for (int t = 0; t < PER; ++t) {
+    const int e = threadIdx.x + 256 * t, i = e / W, j = e - i * W;
     double v;
-    if (j < bs)
-      v = (i < nb && j < nb) ? Bb[i * bs + j] : (i == j ? 1.0 : 0.0);
+    if (j < BS)
+      v = (i < nb && j < nb) ? Bb[i * BS + j] : (i == j ? 1.0 : 0.0);
     else
-      v = ((j - bs) == i) ? 1.0 : 0.0;
+      v = ((j - BS) == i) ? 1.0 : 0.0;
     sm[e] = v;
   }
   __syncthreads();
-  for (int k = 0; k < bs; ++k) {
-    if (threadIdx.x == 0) {
-      int p = k;
-      double best = fabs(sm[k * W + k]);
-      for (int i = k + 1; i < bs; ++i) {
-        const double v = fabs(sm[i * W + k]);
-        if (v > best) { best = v; p = i; }
-      }
-      piv = p;
-      pivval = sm[p * W + k];
-      if (!(best > 0.0)) { flag[0] = 1; pivval = 1.0; }
-    }
-    __syncthreads();
-    const int p = piv;
-    if (p != k) {
-      for (int j = threadIdx.x; j < W; j += blockDim.x) {
-        const double t = sm[k * W + j];
-        sm[k * W + j] = sm[p * W + j];
-        sm[p * W + j] = t;
+  const int lane = threadIdx.x & 63;
+  for (int k = 0; k < BS; ++k) {
+    // pivot: the first row of largest |a_ik|, i >= k; NaNs are never chosen unless on the diagonal (a serial
+    // scan starting there keeps a NaN best, and the step is flagged)
+    const int i = k + lane;
+    double v = i < BS ? fabs(sm[i * W + k]) : -1.0;
+    const double vk = __shfl(v, 0);
+    if (v != v) v = -1.0;
+    int p = i;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const double ov = __shfl_xor(v, off);
+      const int op = __shfl_xor(p, off);
+      if (ov > v || (ov == v && op < p)) {
+        v = ov;
+        p = op;
       }
     }
-    __syncthreads();
-    const double ipv = 1.0 / pivval;
-    for (int j = threadIdx.x; j < W; j += blockDim.x) sm[k * W + j] *= ipv;
-    __syncthreads();
-    for (int e = threadIdx.x; e < bs * W; e += blockDim.x) {
-      const int i = e / W, j = e - i * W;
-      if (i != k && j != k) sm[e] -= sm[i * W + k] * sm[k * W + j];
+    double best = v;
+    if (vk != vk) {
+      p = k;
+      best = vk;
+    }
+    const bool ok = best > 0.0;
+    if (!ok && threadIdx.x == 0) flag[0] = 1;
+    const double ipv = 1.0 / (ok ? sm[p * W + k] : 1.0);
+    double nv[PER];
+#pragma unroll
+    for (int t = 0; t < PER; ++t) {
+      const int e = threadIdx.x + 256 * t, r = e / W, j = e - r * W;
+      if (r == k) {
+        nv[t] = sm[p * W + j] * ipv;
+      } else if (j == k) {
+        nv[t] = 0.0;
+      } else {
+        const int src = r == p ? k : r;            // rows k and p trade places
+        const double rkj = sm[p * W + j] * ipv;
+        nv[t] = sm[src * W + j] - sm[src * W + k] * rkj;
+      }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < bs; i += blockDim.x)
-      if (i != k) sm[i * W + k] = 0.0;
+#pragma unroll
+    for (int t = 0; t < PER; ++t) sm[threadIdx.x + 256 * t] = nv[t];
     __syncthreads();
   }
-  for (int e = threadIdx.x; e < bs * bs; e += blockDim.x) {
-    const int i = e / bs, j = e - i * bs;
-    Bb[e] = sm[i * W + bs + j];
+#pragma unroll
+  for (int t = 0; t < BS * BS / 256; ++t) {
+    const int e = threadIdx.x + 256 * t, i = e / BS, j = e - i * BS;
+    Bb[e] = sm[i * W + BS + j];
   }
 }
 void launch_block_invert(hipStream_t st, int nshift, int nblocks, int bs, const int* bptr,
                          const GroupPtrs& blocks, int* flag) {
   if (nblocks <= 0 || nshift <= 0) return;
-  hipLaunchKernelGGL(block_invert_kernel, dim3(nblocks, nshift), dim3(256),
-                     (size_t)bs * 2 * bs * sizeof(double), st, bs, bptr, blocks, flag);
+  const size_t lds = (size_t)bs * 2 * bs * sizeof(double);
+  const dim3 grid(nblocks, nshift);
+  if (bs == 16)
+    hipLaunchKernelGGL(block_invert_kernel<16>, grid, dim3(256), lds, st, bptr, blocks, flag);
+  else if (bs == 32)
+    hipLaunchKernelGGL(block_invert_kernel<32>, grid, dim3(256), lds, st, bptr, blocks, flag);
+  else   // 64
+    hipLaunchKernelGGL(block_invert_kernel<64>, grid, dim3(256), lds, st, bptr, blocks, flag);
 }
 
 // ---------------------------------------------------------------------------
@@ -1367,10 +1450,15 @@ __global__ __launch_bounds__(256) void gj_cols_kernel(GjPtrs A, int k, int k0, i
 // sub-block at rows 4 bi, columns 4 bj), a Gauss-Jordan step only passes the pivot row and column through LDS
 // (double buffered: one barrier per step).  The first version kept the matrix in LDS and rewrote all of it
 // per step: bound by the LDS store rate, 260 us per call instead of ~25.
+// A wave owns an 8 x 8 patch of sub-blocks (a 32 x 32 square), so the pivot row and the pivot column each lie
+// in 4 of the 16 waves: only those take the branches that overwrite the pivot row and clear the pivot column,
+// the rest do the bare rank-1 update.  With per-entry selects on all waves (sub-blocks dealt lane by lane) a
+// step cost ~5 VALU instructions per entry: 155 us per call at cfg2.  Same operations per entry as before.
 __global__ __launch_bounds__(1024) void gj_diag_kernel(double* __restrict__ D, int nbe, int* __restrict__ flag) {
   __shared__ double rowb[2][GJ_NB], colb[2][GJ_NB];
   double* d = D + (size_t)blockIdx.x * GJ_NB * GJ_NB;
-  const int bi = threadIdx.x & 31, bj = threadIdx.x >> 5;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int bi = (w >> 2) * 8 + (lane >> 3), bj = (w & 3) * 8 + (lane & 7);
   const int i0 = 4 * bi, j0 = 4 * bj;
   double a[4][4];
 #pragma unroll
@@ -1390,27 +1478,27 @@ __global__ __launch_bounds__(1024) void gj_diag_kernel(double* __restrict__ D, i
     for (int tj = 0; tj < 4; ++tj)
       if (i0 + ti < nbe && j0 + tj < nbe) amax = fmax(amax, fabs(a[ti][tj]));
   for (int off = 32; off > 0; off >>= 1) amax = fmax(amax, __shfl_xor(amax, off));
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = amax;
+  if (lane == 0) wmax[w] = amax;
   __syncthreads();
   amax = 0.0;
 #pragma unroll
-  for (int w = 0; w < 16; ++w) amax = fmax(amax, wmax[w]);
+  for (int q = 0; q < 16; ++q) amax = fmax(amax, wmax[q]);
   const double ptol = 1e-12 * amax;
   bool bad = !(amax > 0.0) || !(amax < 1e300);
   for (int p = 0; p < nbe && !bad; ++p) {
-    const int buf = p & 1;
-    if ((p >> 2) == bi) {          // owners of the pivot row
+    const int buf = p & 1, pb = p >> 2, pt = p & 3;
+    if (pb == bi) {                // owners of the pivot row
 #pragma unroll
       for (int ti = 0; ti < 4; ++ti)
-        if (i0 + ti == p) {
+        if (ti == pt) {
 #pragma unroll
           for (int tj = 0; tj < 4; ++tj) rowb[buf][j0 + tj] = a[ti][tj];
         }
     }
-    if ((p >> 2) == bj) {          // owners of the pivot column
+    if (pb == bj) {                // owners of the pivot column
 #pragma unroll
       for (int tj = 0; tj < 4; ++tj)
-        if (j0 + tj == p) {
+        if (tj == pt) {
 #pragma unroll
           for (int ti = 0; ti < 4; ++ti) colb[buf][i0 + ti] = a[ti][tj];
         }
@@ -1424,16 +1512,30 @@ __global__ __launch_bounds__(1024) void gj_diag_kernel(double* __restrict__ D, i
     const double inv = 1.0 / piv;
     double rj[4], ci[4];
 #pragma unroll
-    for (int tj = 0; tj < 4; ++tj) rj[tj] = (j0 + tj == p) ? inv : rowb[buf][j0 + tj] * inv;
+    for (int tj = 0; tj < 4; ++tj) rj[tj] = rowb[buf][j0 + tj] * inv;
 #pragma unroll
     for (int ti = 0; ti < 4; ++ti) ci[ti] = colb[buf][i0 + ti];
+    if (pb == bj) {                // pivot column: a_ip is replaced by 0 - a_ip / piv
+#pragma unroll
+      for (int tj = 0; tj < 4; ++tj)
+        if (tj == pt) {
+          rj[tj] = inv;
+#pragma unroll
+          for (int ti = 0; ti < 4; ++ti) a[ti][tj] = 0.0;
+        }
+    }
 #pragma unroll
     for (int ti = 0; ti < 4; ++ti)
 #pragma unroll
-      for (int tj = 0; tj < 4; ++tj) {
-        if (i0 + ti == p) a[ti][tj] = rj[tj];
-        else a[ti][tj] = ((j0 + tj == p) ? 0.0 : a[ti][tj]) - ci[ti] * rj[tj];
-      }
+      for (int tj = 0; tj < 4; ++tj) a[ti][tj] = a[ti][tj] - ci[ti] * rj[tj];
+    if (pb == bi) {                // pivot row: the scaled row
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+        if (ti == pt) {
+#pragma unroll
+          for (int tj = 0; tj < 4; ++tj) a[ti][tj] = rj[tj];
+        }
+    }
   }
   if (bad && threadIdx.x == 0) atomicExch(flag, 1);
 #pragma unroll

@@ -53,6 +53,32 @@ static double* ctl_recv(ricadi_ctx* c) {
   return c->xrecv + (size_t)c->xworld * exchange_panel_capacity(c) / sizeof(double);
 }
 static bool sharded(const ricadi_ctx* c) { return (c->xworld > 1 || c->xforce) && (c->xfn != nullptr || c->xcomm != nullptr); }
+
+// Per-shift setup beside the projection solve.  The serial order (prefetch_setup, then project_panel) sets up the
+// ADI shifts and the projection operator (alpha, beta) = (1, 0) in one batch and then solves.  The overlapped order:
+//   1. the projection operator alone on the main stream (get_shift: issued and finished),
+//   2. the setup of the ADI shifts issued on the auxiliary stream (this function),
+//   3. the projection solve on the main stream (the caller: project_panel),
+//   4. setup_finish (the caller).
+// Returns false -- nothing done, the caller keeps the serial order -- without a projection, with a child level
+// (its setup runs on the parent's stream), when sharded (a rank's setup failure must reach the other ranks through
+// the sweep's status words, which the serial order reports from one place) and with RICADI_SETUP_OVERLAP=0.
+// Scratch that both streams touch between 2 and 4:
+//   * gj_cb / gj_rp / gj_rb / gj_d / gj_ptrs / gj_hptrs: used by setups only, and 1 is finished before 2 is issued;
+//   * flag words: the auxiliary Exec has its own (flag2); the solve uses none of c->flag;
+//   * pools: the setup takes nothing from a pool (ShiftData owns its buffers); the solve uses c->pool on the main
+//     stream only;
+//   * rc / ec and the rest of the GMRES workspace: not touched by the setup; ensure_work has sized them before;
+//   * ipiv / info / eptrs (pivoted route): used by setup_finish only, after the auxiliary stream has drained;
+//   * st2 / rb2 / ev_z: shared with the asynchronous recompression, which runs inside the sweeps, after 4.
+static bool setup_overlap_begin(ricadi_ctx* c, const double* shifts, int nuse, bool project, SetupJob& job) {
+  if (!project || c->np == 0 || c->child || sharded(c) || !c->sw.setup_overlap) return false;
+  get_shift(c, 1.0, 0.0);
+  std::vector<double> be(nuse, 1.0);
+  std::vector<ShiftData*> sds(nuse);
+  setup_issue(c, aux_exec(c), shifts, be.data(), nuse, sds.data(), job);
+  return true;
+}
 // v[0..n) <- rank 0's values (decisions must not differ between the ranks: the norms they rest on come
 // from kernels with atomic accumulation).  One tiny all-gather.
 static void values_of_rank0(ricadi_ctx* c, double* v, int n) {
@@ -151,18 +177,21 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
     }
   };
   const bool words_fit = (size_t)c->np * m >= 2;
-  guarded([&] {
-    std::vector<double> mine;
-    const int nuse = std::min(ns, prm.adi_max_steps);
-    for (int i = 0; i < nuse; ++i)
-      if (owner[i] == rank) mine.push_back(shifts[i]);
-    prefetch_setup(c, mine.data(), (int)mine.size(), prm.project_w != 0);
-  });
+  SetupJob sjob;
+  if (!setup_overlap_begin(c, shifts, std::min(ns, prm.adi_max_steps), prm.project_w != 0, sjob))
+    guarded([&] {
+      std::vector<double> mine;
+      const int nuse = std::min(ns, prm.adi_max_steps);
+      for (int i = 0; i < nuse; ++i)
+        if (owner[i] == rank) mine.push_back(shifts[i]);
+      prefetch_setup(c, mine.data(), (int)mine.size(), prm.project_w != 0);
+    });
   lap(c->t_setup);
   if (prm.project_w) {
     // (replicated: the projection operator is set up by every rank; a rank whose own setup failed skips it)
     if (fail.empty()) guarded([&] { project_panel(c, dW, m); });
   }
+  setup_finish(c, sjob);          // (overlapped order only: `projection` then includes the wait for the setup)
   lap(c->t_proj);
   const long it0 = c->total_iters;
   if (!shard) c->sweep_u.ensure(nm * G);
@@ -439,8 +468,11 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
   ensure_work(c, m);
   // per-shift data of the whole shift cycle (and of the projection) up front: the coarse
   // inverses then come out of one batched factorisation instead of one at a time
-  prefetch_setup(c, shifts, std::min(ns, prm.adi_max_steps), prm.project_w != 0);
+  SetupJob sjob;
+  if (!setup_overlap_begin(c, shifts, std::min(ns, prm.adi_max_steps), prm.project_w != 0, sjob))
+    prefetch_setup(c, shifts, std::min(ns, prm.adi_max_steps), prm.project_w != 0);
   if (prm.project_w) project_panel(c, dW, m);
+  setup_finish(c, sjob);
   const long it0 = c->total_iters;
   double znorm2 = 0.0;
   int zc_last = c->zc;

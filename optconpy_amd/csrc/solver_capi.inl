@@ -116,6 +116,7 @@ static Switches read_switches() {
   s.coarse_pipe = !off("RICADI_COARSE_PIPE");
   if (const char* e = getenv("RICADI_ARNOLDI")) s.lowsync = strcmp(e, "cgs2") != 0;
   s.split = !off("RICADI_SPLIT");
+  s.setup_overlap = !off("RICADI_SETUP_OVERLAP");
   return s;
 }
 

@@ -10,6 +10,7 @@ static Exec main_exec(ricadi_ctx* c) {
   ex.rb = c->rb;
   ex.pool = &c->pool;
   ex.info = c->info.p;
+  ex.flag = c->flag.p;
   return ex;
 }
 

@@ -1056,6 +1056,7 @@ static Exec aux_exec(ricadi_ctx* c) {
     RBCHK(rocblas_create_handle(&c->rb2));
     RBCHK(rocblas_set_stream(c->rb2, c->st2));
     c->info2.alloc(4);
+    c->flag2.alloc(4);
     HIPCHK(hipEventCreateWithFlags(&c->ev_z, hipEventDisableTiming));
   }
   Exec ex;
@@ -1063,6 +1064,7 @@ static Exec aux_exec(ricadi_ctx* c) {
   ex.rb = c->rb2;
   ex.pool = &c->pool2;
   ex.info = c->info2.p;
+  ex.flag = c->flag2.p;
   return ex;
 }
 

@@ -32,9 +32,12 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
   // the rhs factor W is projected once here; the K_k part is in range(P^T) already
   ricadi_adi_params p2 = *prm;
   Tick tk0;
-  prefetch_setup(c, shifts, std::min(ns, prm->adi_max_steps), prm->project_w != 0);
+  SetupJob sjob;       // overlapped order (setup_overlap_begin): the solve time below includes the setup's finish
+  if (!setup_overlap_begin(c, shifts, std::min(ns, prm->adi_max_steps), prm->project_w != 0, sjob))
+    prefetch_setup(c, shifts, std::min(ns, prm->adi_max_steps), prm->project_w != 0);
   const double t_pre = c->sw.timing ? ((void)hipStreamSynchronize(st), tk0.lap()) : 0.0;
   if (prm->project_w) project_panel(c, dWm.p, mw);
+  setup_finish(c, sjob);
   if (c->sw.timing) {
     (void)hipStreamSynchronize(st);
     fprintf(stderr, "[ricadi timing] per-shift setup of %d shifts + projection operator %.1f ms, projection solve %.1f ms\n",

@@ -84,36 +84,34 @@ static void ensure_work(ricadi_ctx* c, int m, int groups = 1, int extra = -1) {
 }
 
 // ---- per-shift setup ---------------------------------------------------------
+static Exec main_exec(ricadi_ctx* c);
+static void get_shifts(ricadi_ctx* c, const double* alphas, const double* betas, int ng, ShiftData** out);
+
 template <class T>
 static void stable_alloc(DArr<T>& a, size_t n) {
   if (a.n != n) a.alloc(n);
 }
 
-// In-place inverses of nb (<= RICADI_MAX_GROUPS) dense k x k matrices (row-major, device pointers in hmats) by
+// In-place inverses of nb (<= gj_max_batch()) dense k x k matrices (row-major, device pointers in hmats) by
 // block Gauss-Jordan elimination without pivoting: per 128-row block three small kernels and two batched
-// rocBLAS GEMMs (ricadi_kernels.hip).  Returns false if a diagonal block had a vanishing pivot (the matrices
-// are garbage then; the caller assembles them again and takes the pivoted rocSOLVER route).
-static bool gj_invert_batched(ricadi_ctx* c, double* const* hmats, int nb, int k) {
-  hipStream_t st = c->st;
+// rocBLAS GEMMs (ricadi_kernels.hip).  A diagonal block with a vanishing pivot raises *gjflag (the matrices are
+// garbage then; the caller assembles them again and takes the pivoted rocSOLVER route).  No host
+// synchronisation: the pointer arrays go up from hptrs (pinned, read by the copy when the stream reaches it) to
+// dptrs; the caller has sized the gj_* panels for the batch.
+static void gj_invert_batched(ricadi_ctx* c, const Exec& ex, int* gjflag, double* const* hmats, int nb, int k,
+                              double** hptrs, double** dptrs) {
+  hipStream_t st = ex.st;
   const int NB = gj_block();
   const size_t pan = (size_t)k * NB;
-  c->gj_cb.ensure(pan * nb);
-  c->gj_rp.ensure(pan * nb);
-  c->gj_rb.ensure(pan * nb);
-  c->gj_d.ensure((size_t)NB * NB * nb);
-  std::vector<double*> hp((size_t)5 * nb);
   for (int i = 0; i < nb; ++i) {
-    hp[i] = hmats[i];
-    hp[nb + i] = c->gj_cb.p + pan * i;
-    hp[2 * nb + i] = c->gj_rp.p + pan * i;
-    hp[3 * nb + i] = c->gj_rb.p + pan * i;
-    hp[4 * nb + i] = c->gj_d.p + (size_t)NB * NB * i;
+    hptrs[i] = hmats[i];
+    hptrs[nb + i] = c->gj_cb.p + pan * i;
+    hptrs[2 * nb + i] = c->gj_rp.p + pan * i;
+    hptrs[3 * nb + i] = c->gj_rb.p + pan * i;
+    hptrs[4 * nb + i] = c->gj_d.p + (size_t)NB * NB * i;
   }
-  c->gj_ptrs.ensure((size_t)5 * nb);
-  HIPCHK(hipMemcpyAsync(c->gj_ptrs.p, hp.data(), sizeof(double*) * hp.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(c->flag.p + 2, 0, sizeof(int), st));
-  HIPCHK(hipStreamSynchronize(st));   // hp is a stack object
-  double* const* dA = c->gj_ptrs.p;
+  HIPCHK(hipMemcpyAsync(dptrs, hptrs, sizeof(double*) * 5 * nb, hipMemcpyHostToDevice, st));
+  double* const* dA = dptrs;
   double* const* dCb = dA + nb;
   double* const* dRp = dA + 2 * nb;
   double* const* dRb = dA + 3 * nb;
@@ -122,39 +120,62 @@ static bool gj_invert_batched(ricadi_ctx* c, double* const* hmats, int nb, int k
   for (int k0 = 0; k0 < k; k0 += NB) {
     const int nbe = std::min(NB, k - k0);
     launch_gj_prep(st, nb, hmats, k, k0, nbe, c->gj_cb.p, c->gj_rp.p, c->gj_d.p);
-    launch_gj_diag(st, nb, c->gj_d.p, nbe, c->flag.p + 2);
+    launch_gj_diag(st, nb, c->gj_d.p, nbe, gjflag);
     // row-major Rb = D^-1 Rp  ==  column-major Rb^T = Rp^T (D^-1)^T
-    RBCHK(rocblas_dgemm_batched(c->rb, rocblas_operation_none, rocblas_operation_none, k, nbe, nbe, &one,
+    RBCHK(rocblas_dgemm_batched(ex.rb, rocblas_operation_none, rocblas_operation_none, k, nbe, nbe, &one,
                                 (const double* const*)dRp, k, (const double* const*)dD, NB, &zero, dRb, k, nb));
     // row-major A -= Cb Rb  ==  column-major A^T -= Rb^T Cb^T
-    RBCHK(rocblas_dgemm_batched(c->rb, rocblas_operation_none, rocblas_operation_none, k, k, nbe, &mone,
+    RBCHK(rocblas_dgemm_batched(ex.rb, rocblas_operation_none, rocblas_operation_none, k, k, nbe, &mone,
                                 (const double* const*)dRb, k, (const double* const*)dCb, NB, &one, dA, k, nb));
     launch_gj_rows(st, nb, hmats, k, k0, nbe, c->gj_rb.p);
   }
-  int flag = 0;
-  HIPCHK(hipMemcpyAsync(&flag, c->flag.p + 2, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return flag == 0;
 }
 
-// In-place inverses of nb dense k x k matrices (row major, device pointers in hp): the coarse matrices of a setup.
-// Route 0: block Gauss-Jordan WITHOUT pivoting on batched GEMMs (gj_invert_batched) -- with the velocity
-// aggregates ordered before the pressure aggregates that is block elimination of the coarse saddle matrix: the
-// velocity block has a definite symmetric part for ADI shifts (and is s.p.d. for the projection), the Schur
-// complement -B Av^-1 B^T inherits it.  A pivot that vanishes relative to its block's scale sends ALL matrices of
-// the call through route 1: rocSOLVER's getrf / getri with partial pivoting (its unpivoted routines, the step in
-// between until round 3, only notice an EXACTLY zero pivot -- a pivot of 1e-14 of the block's scale passed and left
-// a garbage inverse).  `reassemble` restores the matrices the first route has overwritten.  info (nb entries):
-// rocSOLVER's status.  Returns the route.
+// The gj_* panels and pointer arrays for a batch of nb matrices of size k.  Growing them may synchronise the device:
+// setup_issue calls this before its first launch.  The pinned pointer buffer holds a full batch from the start.
+static void gj_reserve(ricadi_ctx* c, int nb, int k) {
+  const int NB = gj_block(), chunk = std::min(gj_max_batch(), nb);
+  const size_t pan = (size_t)k * NB;
+  c->gj_cb.ensure(pan * chunk);
+  c->gj_rp.ensure(pan * chunk);
+  c->gj_rb.ensure(pan * chunk);
+  c->gj_d.ensure((size_t)NB * NB * chunk);
+  c->gj_ptrs.ensure((size_t)5 * nb);
+  if (c->gj_hcap < (size_t)5 * nb) {
+    if (c->gj_hptrs) {
+      HIPCHK(hipDeviceSynchronize());      // an earlier upload may still read the old buffer
+      HIPCHK(hipHostFree(c->gj_hptrs));
+      c->gj_hptrs = nullptr;
+    }
+    const size_t cap = (size_t)5 * std::max(nb, gj_max_batch());
+    HIPCHK(hipHostMalloc((void**)&c->gj_hptrs, sizeof(double*) * cap));
+    c->gj_hcap = cap;
+  }
+}
+
+// Issue half of the route-0 inverses of all matrices in hp (chunks of gj_max_batch() in stream order on ex); the
+// verdict is in ex.flag[2] once ex.st has got there (invert_dense_finish).  The gj_* panels and pointer arrays are
+// shared by every Exec: a setup issued on one must be finished before another is issued.
+static void invert_dense_issue(ricadi_ctx* c, const Exec& ex, const std::vector<double*>& hp, int k) {
+  const int nb = (int)hp.size();
+  gj_reserve(c, nb, k);
+  HIPCHK(hipMemsetAsync(ex.flag + 2, 0, sizeof(int), ex.st));
+  for (int i0 = 0; i0 < nb; i0 += gj_max_batch())
+    gj_invert_batched(c, ex, ex.flag + 2, hp.data() + i0, std::min(gj_max_batch(), nb - i0), k,
+                      c->gj_hptrs + 5 * i0, c->gj_ptrs.p + 5 * i0);
+}
+
+// Finish half: ex.st must have been synchronised.  A vanishing pivot in any matrix sends ALL of them through
+// route 1 on the main stream (`reassemble` restores what route 0 has overwritten).  Returns the route.
 template <class F>
-static int invert_dense_batch(ricadi_ctx* c, const std::vector<double*>& hp, int k, std::vector<int>& info,
-                              F&& reassemble) {
+static int invert_dense_finish(ricadi_ctx* c, const Exec& ex, const std::vector<double*>& hp, int k,
+                               std::vector<int>& info, F&& reassemble) {
   hipStream_t st = c->st;
   const int nb = (int)hp.size();
-  bool done = true;
-  for (int i0 = 0; i0 < nb && done; i0 += gj_max_batch())
-    done = gj_invert_batched(c, hp.data() + i0, std::min(gj_max_batch(), nb - i0), k);
-  if (done) {
+  int flag = 0;
+  HIPCHK(hipMemcpyAsync(&flag, ex.flag + 2, sizeof(int), hipMemcpyDeviceToHost, ex.st));
+  HIPCHK(hipStreamSynchronize(ex.st));
+  if (flag == 0) {
     std::fill(info.begin(), info.end(), 0);
     return 0;
   }
@@ -172,14 +193,53 @@ static int invert_dense_batch(ricadi_ctx* c, const std::vector<double*>& hp, int
   return 1;
 }
 
-// Per-shift data for the given (alpha, beta) pairs; whatever is missing is built for
-// all of them together: the element-wise / block kernels per shift, the dense coarse
-// inverses in ONE batched rocSOLVER factorisation + inversion (its many small
-// panel kernels then serve all shifts of a sweep per launch instead of one).
-static void get_shifts(ricadi_ctx* c, const double* alphas, const double* betas, int ng,
-                       ShiftData** out) {
-  hipStream_t st = c->st;
+// In-place inverses of nb dense k x k matrices (row major, device pointers in hp): the coarse matrices of a setup.
+// Route 0: block Gauss-Jordan WITHOUT pivoting on batched GEMMs (gj_invert_batched) -- with the velocity
+// aggregates ordered before the pressure aggregates that is block elimination of the coarse saddle matrix: the
+// velocity block has a definite symmetric part for ADI shifts (and is s.p.d. for the projection), the Schur
+// complement -B Av^-1 B^T inherits it.  A pivot that vanishes relative to its block's scale sends ALL matrices of
+// the call through route 1: rocSOLVER's getrf / getri with partial pivoting (its unpivoted routines, the step in
+// between until round 3, only notice an EXACTLY zero pivot -- a pivot of 1e-14 of the block's scale passed and left
+// a garbage inverse).  `reassemble` restores the matrices the first route has overwritten.  info (nb entries):
+// rocSOLVER's status.  Returns the route.
+template <class F>
+static int invert_dense_batch(ricadi_ctx* c, const std::vector<double*>& hp, int k, std::vector<int>& info,
+                              F&& reassemble) {
+  const Exec ex = main_exec(c);
+  invert_dense_issue(c, ex, hp, k);
+  HIPCHK(hipStreamSynchronize(ex.st));
+  return invert_dense_finish(c, ex, hp, k, info, reassemble);
+}
+
+// A per-shift setup between its two halves: setup_issue puts every launch on `ex` without synchronising the
+// host, setup_finish waits for them, checks the flags, takes the pivoted coarse route if needed and marks the data
+// valid.  An exception in between (the caller's own work) leaves the job to its destructor, which drains ex.st
+// before the half-built data can be built again elsewhere.
+struct SetupJob {
+  Exec ex;
   std::vector<ShiftData*> todo;
+  std::vector<double*> hp;      // the coarse matrices of todo (route 0 in flight on ex)
+  Tick tks;
+  double tph[6] = {0, 0, 0, 0, 0, 0};
+  bool open = false;
+  SetupJob() = default;
+  SetupJob(const SetupJob&) = delete;
+  SetupJob& operator=(const SetupJob&) = delete;
+  ~SetupJob() {
+    if (open) (void)hipStreamSynchronize(ex.st);
+  }
+};
+
+// Issue half of the per-shift data for the given (alpha, beta) pairs; whatever is missing is built for all of
+// them together: the element-wise / block kernels per shift, the dense coarse inverses in ONE batched block
+// Gauss-Jordan elimination (its launches then serve all shifts of a sweep at once).  With ex on the auxiliary
+// stream the work waits for what the main stream has issued so far.
+static void setup_issue(ricadi_ctx* c, const Exec& ex, const double* alphas, const double* betas, int ng,
+                        ShiftData** out, SetupJob& job) {
+  hipStream_t st = ex.st;
+  job.ex = ex;
+  std::vector<ShiftData*>& todo = job.todo;
+  todo.clear();
   for (int g = 0; g < ng; ++g) {
     auto key = std::make_pair(alphas[g], betas[g]);
     auto it = c->cache.find(key);
@@ -195,18 +255,53 @@ static void get_shifts(ricadi_ctx* c, const double* alphas, const double* betas,
     todo.push_back(sd);
   }
   if (todo.empty()) return;
-  Tick tks;
-  double tph[6] = {0, 0, 0, 0, 0, 0};
+  job.open = true;
+  job.tks = Tick();
+  double* tph = job.tph;
+  Tick& tks = job.tks;
   auto lapS = [&](int i) {
     if (c->sw.timing) {
       (void)hipStreamSynchronize(st);
       tph[i] += tks.lap();
     }
   };
-  HIPCHK(hipMemsetAsync(c->flag.p, 0, sizeof(int), st));
   const size_t bsz = (size_t)c->bs * c->bs;
   const int k = c->kc;
   const int kd = c->child ? 0 : c->kc;   // size of the dense coarse inverse (none with a child level)
+  const bool copies16 = c->sw.blocks16 && c->sw_stride > 0 && c->gt_ok && c->ady_ok && k > 0 && c->nbp > 0;
+  // Every buffer first, then the launches: an allocation may wait for the device (hipFree inside a growing
+  // DArr does), and the projection solve would then wait for the work already issued here.
+  for (ShiftData* sd : todo) {
+    stable_alloc(sd->sval, c->snnz);
+    if (c->sb_ok) stable_alloc(sd->svalb, c->snnz);
+    stable_alloc(sd->bvinv, (size_t)c->nbv * bsz);
+    if (c->nbp > 0) stable_alloc(sd->bpinv, (size_t)c->nbp * bsz);
+    if (c->gt_ok) stable_alloc(sd->gtm, (size_t)c->nbv * c->bs * c->gt_ks);
+    if (c->ady_ok && k > 0) stable_alloc(sd->adym, (size_t)c->nbv * c->bs * c->ady_ks);
+    if (kd > 0) stable_alloc(sd->einv, (size_t)k * k);
+    if (k > 0) {
+      stable_alloc(sd->syval, c->synnz);
+      if (c->syb_ok) stable_alloc(sd->syvalb, c->synnz);
+    }
+    if (c->precond32) {
+      stable_alloc(sd->bvinvf, sd->bvinv.n);
+      if (c->nbp > 0) stable_alloc(sd->bpinvf, sd->bpinv.n);
+      if (c->gt_ok) stable_alloc(sd->gtmf, sd->gtm.n);
+      if (c->ady_ok && k > 0) stable_alloc(sd->adymf, sd->adym.n);
+      if (copies16) {
+        stable_alloc(sd->bvinvh, sd->bvinv.n);
+        stable_alloc(sd->bpinvh, sd->bpinv.n);
+        stable_alloc(sd->gtmh, sd->gtm.n);
+        stable_alloc(sd->adymh, sd->adym.n);
+      }
+    }
+  }
+  if (kd > 0) gj_reserve(c, (int)todo.size(), k);
+  if (st != c->st) {
+    HIPCHK(hipEventRecord(c->ev_z, c->st));
+    HIPCHK(hipStreamWaitEvent(st, c->ev_z, 0));
+  }
+  HIPCHK(hipMemsetAsync(ex.flag, 0, sizeof(int), st));
   if (c->child) {
     std::vector<double> al(todo.size()), be(todo.size());
     std::vector<ShiftData*> subs(todo.size(), nullptr);
@@ -220,30 +315,15 @@ static void get_shifts(ricadi_ctx* c, const double* alphas, const double* betas,
   lapS(0);
   for (ShiftData* sd : todo) {
     const double alpha = sd->alpha, beta = sd->beta;
-    stable_alloc(sd->sval, c->snnz);
     launch_assemble_shift(st, (int)c->snnz, c->srcA.p, c->srcE.p, c->srcJ.p, alpha, beta,
                           sd->sval.p);
-    if (c->sb_ok) {
-      stable_alloc(sd->svalb, c->snnz);
-      launch_gather_vals(st, (int)c->snnz, c->sb_perm.p, sd->sval.p, sd->svalb.p);
-    }
-    stable_alloc(sd->bvinv, (size_t)c->nbv * bsz);
+    if (c->sb_ok) launch_gather_vals(st, (int)c->snnz, c->sb_perm.p, sd->sval.p, sd->svalb.p);
     launch_block_combine(st, (size_t)c->nbv * bsz, c->bvA.p, c->bvE.p, alpha, beta, sd->bvinv.p);
-    if (c->nbp > 0) stable_alloc(sd->bpinv, (size_t)c->nbp * bsz);
-    if (c->gt_ok) stable_alloc(sd->gtm, (size_t)c->nbv * c->bs * c->gt_ks);
-    if (c->ady_ok && k > 0) stable_alloc(sd->adym, (size_t)c->nbv * c->bs * c->ady_ks);
-    if (kd > 0) {
-      stable_alloc(sd->einv, (size_t)k * k);
-      launch_combine3(st, (size_t)k * k, c->E0.p, c->EM.p, c->EJ.p, alpha, beta, sd->einv.p);
-    }
+    if (kd > 0) launch_combine3(st, (size_t)k * k, c->E0.p, c->EM.p, c->EJ.p, alpha, beta, sd->einv.p);
     if (k > 0) {
-      stable_alloc(sd->syval, c->synnz);
       launch_assemble_shift(st, (int)c->synnz, c->sy_A.p, c->sy_E.p, c->sy_J.p, alpha, beta,
                             sd->syval.p);
-      if (c->syb_ok) {
-        stable_alloc(sd->syvalb, c->synnz);
-        launch_gather_vals(st, (int)c->synnz, c->syb_perm.p, sd->syval.p, sd->syvalb.p);
-      }
+      if (c->syb_ok) launch_gather_vals(st, (int)c->synnz, c->syb_perm.p, sd->syval.p, sd->syvalb.p);
     }
   }
   lapS(1);
@@ -255,7 +335,7 @@ static void get_shifts(ricadi_ctx* c, const double* alphas, const double* betas,
       pv.p[i] = todo[t0 + i]->bvinv.p;
       pp.p[i] = todo[t0 + i]->bpinv.p;
     }
-    launch_block_invert(st, cnt, c->nbv, c->bs, c->bv_ptr.p, pv, c->flag.p);
+    launch_block_invert(st, cnt, c->nbv, c->bs, c->bv_ptr.p, pv, ex.flag);
     if (c->gt_ok) {
       GroupPtrs pg = same_ptr((const double*)nullptr);
       for (int i = 0; i < cnt; ++i) pg.p[i] = todo[t0 + i]->gtm.p;
@@ -275,71 +355,94 @@ static void get_shifts(ricadi_ctx* c, const double* alphas, const double* betas,
     if (c->nbp > 0) {
       launch_schur_blocks_bj(st, cnt, c->nbp, c->bs, c->bp_ptr.p, c->jd_ptr.p, c->jd_vblk.p,
                              c->jd_val.p, pv, pp);
-      launch_block_invert(st, cnt, c->nbp, c->bs, c->bp_ptr.p, pp, c->flag.p);
+      launch_block_invert(st, cnt, c->nbp, c->bs, c->bp_ptr.p, pp, ex.flag);
     }
   }
   lapS(2);
-  const int nb = (int)todo.size();
-  std::vector<int> info(nb, 0);
   if (kd > 0) {
-    std::vector<double*> hp(nb);
-    for (int i = 0; i < nb; ++i) hp[i] = todo[i]->einv.p;
-    c->coarse_route = invert_dense_batch(c, hp, k, info, [&] {
-      for (ShiftData* sd : todo)
-        launch_combine3(st, (size_t)k * k, c->E0.p, c->EM.p, c->EJ.p, sd->alpha, sd->beta, sd->einv.p);
-    });
+    job.hp.resize(todo.size());
+    for (size_t i = 0; i < todo.size(); ++i) job.hp[i] = todo[i]->einv.p;
+    invert_dense_issue(c, ex, job.hp, k);
   }
   lapS(3);
-  int flag = 0;
-  HIPCHK(hipMemcpyAsync(&flag, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  for (int i = 0; i < nb; ++i)
-    if (info[i] != 0)
-      throw HipError{"coarse matrix singular (getrf/getri info " + std::to_string(info[i]) + ")"};
-  if (flag) throw HipError{"singular block-Jacobi block"};
   if (c->precond32) {
+    // the FP32 / BF16 copies of everything but the coarse inverses (those may still take route 1)
     const int bs2 = c->bs * c->bs;
     for (ShiftData* sd : todo) {
-      if (sd->bvinvf.n != sd->bvinv.n) sd->bvinvf.alloc(sd->bvinv.n);
       launch_to_f32(st, c->nbv, bs2, sd->bvinv.p, bs2, sd->bvinvf.p, bs2);
       if (c->nbp > 0) {
-        if (sd->bpinvf.n != sd->bpinv.n) sd->bpinvf.alloc(sd->bpinv.n);
         launch_to_f32(st, c->nbp, bs2, sd->bpinv.p, bs2, sd->bpinvf.p, bs2);
       }
       if (c->gt_ok) {
         const int gsz = c->bs * c->gt_ks;
-        if (sd->gtmf.n != sd->gtm.n) sd->gtmf.alloc(sd->gtm.n);
         launch_to_f32(st, c->nbv, gsz, sd->gtm.p, gsz, sd->gtmf.p, gsz);
       }
       if (c->ady_ok && k > 0) {
         const int gsz = c->bs * c->ady_ks;
-        if (sd->adymf.n != sd->adym.n) sd->adymf.alloc(sd->adym.n);
         launch_to_f32(st, c->nbv, gsz, sd->adym.p, gsz, sd->adymf.p, gsz);
       }
-      if (kd > 0) {
-        const size_t kp = (size_t)(k + 15) / 16;
-        if (sd->einvf.n != kp * kp * 256) sd->einvf.alloc(kp * kp * 256);
-        launch_to_f32_tiled(st, k, sd->einv.p, sd->einvf.p);
-      }
-      if (c->sw.blocks16 && c->sw_stride > 0 && c->gt_ok && c->ady_ok && k > 0 && c->nbp > 0) {
+      if (copies16) {
         // BF16 copies for the record-driven sweeps (all four or none: the cycle switches as a whole)
-        if (sd->bvinvh.n != sd->bvinv.n) sd->bvinvh.alloc(sd->bvinv.n);
-        if (sd->bpinvh.n != sd->bpinv.n) sd->bpinvh.alloc(sd->bpinv.n);
-        if (sd->gtmh.n != sd->gtm.n) sd->gtmh.alloc(sd->gtm.n);
-        if (sd->adymh.n != sd->adym.n) sd->adymh.alloc(sd->adym.n);
         launch_to_bf16(st, sd->bvinv.n, sd->bvinv.p, sd->bvinvh.p);
         launch_to_bf16(st, sd->bpinv.n, sd->bpinv.p, sd->bpinvh.p);
         launch_to_bf16(st, sd->gtm.n, sd->gtm.p, sd->gtmh.p);
         launch_to_bf16(st, sd->adym.n, sd->adym.p, sd->adymh.p);
       }
     }
-    HIPCHK(hipStreamSynchronize(st));
   }
   lapS(4);
+}
+
+// Finish half: waits for the issued work, reports a singular block or coarse matrix (same errors as ever), takes
+// the pivoted route for the whole batch where a coarse pivot vanished, makes the FP32 copies of the coarse
+// inverses on the main stream and marks the data valid.
+static void setup_finish(ricadi_ctx* c, SetupJob& job) {
+  if (!job.open) return;
+  hipStream_t st = c->st;
+  const Exec& ex = job.ex;
+  const std::vector<ShiftData*>& todo = job.todo;
+  double* tph = job.tph;
+  HIPCHK(hipStreamSynchronize(ex.st));
+  job.open = false;
+  Tick tf;                       // (RICADI_TIMING: the issued phases were timed in setup_issue)
+  const int k = c->kc;
+  const int kd = c->child ? 0 : c->kc;
+  const int nb = (int)todo.size();
+  std::vector<int> info(nb, 0);
+  if (kd > 0) {
+    c->coarse_route = invert_dense_finish(c, ex, job.hp, k, info, [&] {
+      for (ShiftData* sd : todo)
+        launch_combine3(st, (size_t)k * k, c->E0.p, c->EM.p, c->EJ.p, sd->alpha, sd->beta, sd->einv.p);
+    });
+  }
+  tph[3] += tf.lap();
+  int flag = 0;
+  HIPCHK(hipMemcpyAsync(&flag, ex.flag, sizeof(int), hipMemcpyDeviceToHost, ex.st));
+  HIPCHK(hipStreamSynchronize(ex.st));
+  for (int i = 0; i < nb; ++i)
+    if (info[i] != 0)
+      throw HipError{"coarse matrix singular (getrf/getri info " + std::to_string(info[i]) + ")"};
+  if (flag) throw HipError{"singular block-Jacobi block"};
+  if (c->precond32 && kd > 0) {
+    for (ShiftData* sd : todo) {
+      const size_t kp = (size_t)(k + 15) / 16;
+      if (sd->einvf.n != kp * kp * 256) sd->einvf.alloc(kp * kp * 256);
+      launch_to_f32_tiled(st, k, sd->einv.p, sd->einvf.p);
+    }
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  tph[4] += tf.lap();
   if (c->sw.timing && !c->borrowed)
     fprintf(stderr, "[ricadi timing] setup of %d shifts: child %.1f ms, per-shift assembly %.1f, block inverses + Schur blocks %.1f, coarse inverses %.1f, FP32 copies %.1f\n",
             (int)todo.size(), 1e3 * tph[0], 1e3 * tph[1], 1e3 * tph[2], 1e3 * tph[3], 1e3 * tph[4]);
   for (ShiftData* sd : todo) sd->valid = true;
+}
+
+// Per-shift data for the given (alpha, beta) pairs, built on the main stream (both halves at once).
+static void get_shifts(ricadi_ctx* c, const double* alphas, const double* betas, int ng, ShiftData** out) {
+  SetupJob job;
+  setup_issue(c, main_exec(c), alphas, betas, ng, out, job);
+  setup_finish(c, job);
 }
 
 static ShiftData* get_shift(ricadi_ctx* c, double alpha, double beta) {

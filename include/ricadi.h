@@ -78,6 +78,14 @@ typedef struct ricadi_opts {
                             "QR ... SVD" (singular values resolved to eps*s_1), for factors of up to
                             1024 columns -- wider ones take the Gram route;  0 = always Gram matrix +
                             eigendecomposition (resolves singular values down to sqrt(eps)*s_1)      */
+  int child_smoother;    /* smoother of a child level of the multilevel preconditioner (a hierarchy without a
+                            child level ignores it): 0 (default) one SIMPLE block sweep; 1 one coloured Vanka
+                            sweep -- per child pressure unknown the patch of itself and the velocity unknowns
+                            its row of J touches (at most 64 unknowns), local saddle systems inverted per
+                            shift, patches that share no unknown applied together, colour after colour on the
+                            updated residual.  Set before ricadi_set_operator                              */
+  double child_damping;  /* damping omega of the Vanka sweep (default 0.7); the SIMPLE sweep ignores it.  Set
+                            before ricadi_set_operator                                                      */
 } ricadi_opts;
 
 /* Parameters of the ADI / Newton loops; same meaning as the keys of the
@@ -185,6 +193,9 @@ int ricadi_precond_apply(ricadi_ctx* ctx, double alpha, double beta,
 #define RICADI_PCF_LAST_SHIFT 12         /* 2 bits: last velocity sweep 1 record-driven BF16 rectangle,
                                             2 generic rectangle, 3 J^T product formed row by row (CSR in)    */
 #define RICADI_PCF_FOLDED (1 << 14)      /* folded cycle (coarse residual inside the first sweep)             */
+#define RICADI_PCF_VANKA (1 << 15)       /* a child level's cycle with the coloured Vanka sweep: coarse correction,
+                                            then per colour the residual and the patch kernel (no SIMPLE sweeps:
+                                            first / last sweep and pressure step read 0)                       */
 #define RICADI_PCF_TWO_KS_SHIFT 16       /* 8 bits: padded width of the two-term sweep's second block (0: none) */
 #define RICADI_PCF_RECT_KS_SHIFT 24      /* 8 bits: padded width of the rectangle sweep's blocks (0: none)    */
 int ricadi_precond_apply_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas, const double* betas,
@@ -217,6 +228,12 @@ int ricadi_op_apply_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas, con
 int ricadi_precond_structure(ricadi_ctx* ctx, int level, int32_t* sizes_out, int32_t* bv_ptr, int32_t* bv_rows,
                              int32_t* bp_ptr, int32_t* bp_rows, int32_t* aggof, int32_t* p_rp, int32_t* p_ci,
                              double* p_v);
+
+/* The patches of the coloured Vanka sweep of level `level` (>= 1: a child level) as the device uses them, for
+ * tests; sizes_out and the records as ricadi_host_vanka_patches returns them (all sizes 0 where the level has no
+ * Vanka sweep).  Call with the arrays NULL for the sizes, then again with colour_ptr[colours + 1] and
+ * patch_idx[64 * patches]; either may be NULL.                                                                   */
+int ricadi_precond_vanka(ricadi_ctx* ctx, int level, int32_t* sizes_out, int32_t* colour_ptr, int32_t* patch_idx);
 
 /* ---- one shift-solve ---------------------------------------------------
  * Solve S(alpha,beta) [V; L] = [R; Rp] for an NV x m panel R (Rp may be
@@ -406,6 +423,10 @@ int ricadi_time_spmm_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas,
  * iteration from HIP events.                                                                                     */
 #define RICADI_TK_ITER 17
 #define RICADI_TK_ITER_SPLIT 18
+/* The coloured Vanka sweep of the first child level that has one (ricadi_opts::child_smoother = 1): all its colours,
+ * 2 launches each (residual of the child's operator, patch kernel), without the child's coarse correction.
+ * RICADI_EHIP ("no coarse level with a Vanka sweep") where no level has one.                                                                  */
+#define RICADI_TK_PC_VANKA 19
 int ricadi_time_kernel_dev(ricadi_ctx* ctx, int which, int ng, const double* alphas,
                            const double* betas, int m, int nvec, int reps,
                            double* ms_per_launch);
@@ -440,7 +461,11 @@ int ricadi_project_pencil_dev(ricadi_ctx* ctx, const double* dQ, int k, double* 
  *        1 if the last preconditioner application kept the velocity part between its sweeps as an FP32 panel
  *        (first sweep -> pressure step -> last sweep), 0 for an FP64 panel; -1 none yet,
  *        1 if the operator launch of the last iteration (or timing call) wrote w = S z as an FP32 panel for the
- *        Arnoldi passes, 0 for FP64; -1 none yet];
+ *        Arnoldi passes, 0 for FP64; -1 none yet,
+ *        [21] 1 if a child level smooths with the coloured Vanka sweep (0: SIMPLE sweep or no child level), and of
+ *        the first such level [22] its colours (the lone colour included), [23] its patches (one per pressure unknown of the
+ *        level), [24] its largest patch, [25] the entries of J the size cap of 64 unknowns dropped, [26] its lone
+ *        pseudo-patches];
  * nout >= 8; entries beyond nout are not written.                                   */
 int ricadi_setup_info(ricadi_ctx* ctx, int* out, int nout);
 
@@ -559,6 +584,20 @@ int ricadi_host_saddle_tiles(int nv, int np, const int32_t* a_rowptr, const int3
                              const ricadi_opts* opts, int32_t* sizes_out, int32_t* rows2, int32_t* rp2,
                              int32_t* cols2, uint16_t* lidx, uint16_t* lidx_ms, double* vAJ, double* vE,
                              int32_t* perm, int32_t* s_rp, int32_t* s_ci, double* s_src);
+/* The patches and colours of the coloured Vanka sweep for a level with nv velocity and np pressure unknowns, from
+ * its J (CSR, np x nv) alone; host only, deterministic.  One patch per pressure unknown i: the velocity unknowns
+ * with a stored entry in row i of J (ascending), then nv + i.  A record is 64 int32, -1 padded; a row with more
+ * than 63 entries keeps the 63 of largest |J_iv| (ties: the lower index) and the rest are counted as dropped.
+ * Colours: first fit in patch order; two patches share a colour only if they share no unknown.  Velocity
+ * unknowns in no patch ("lone") are packed in ascending order, 64 at a time, into pseudo-patches that form one
+ * last colour; the sweep applies the diagonal of the velocity block to them.  Patches are listed colour by
+ * colour, inside a colour by pressure unknown.
+ * sizes_out[8] = [colours (the lone colour included), patches (pseudo-patches included), pressure patches (= np),
+ * largest patch (unknowns), entries of J dropped by the size cap, lone velocity unknowns, lone pseudo-patches,
+ * 0].  Call with the arrays NULL for the sizes, then again with colour_ptr[colours + 1] (first patch of every
+ * colour) and patch_idx[64 * patches]; either may be NULL.                                                       */
+int ricadi_host_vanka_patches(int nv, int np, const int32_t* j_rowptr, const int32_t* j_col, const double* j_val,
+                              int32_t* sizes_out, int32_t* colour_ptr, int32_t* patch_idx);
 /* Greedy BFS aggregation of the graph of a CSR pattern into blocks of at
  * most bsize rows; blk_out[n]; returns the number of blocks (or <0).        */
 int ricadi_host_aggregate(int n, const int32_t* rowptr, const int32_t* col,

@@ -20,14 +20,15 @@ RICADI_ENOCONV = -3
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 401
+ABI_VERSION = 402
 
 
 class RicadiOpts(C.Structure):
     _fields_ = [("gmres_tol", C.c_double), ("gmres_restart", C.c_int),
                 ("gmres_maxit", C.c_int), ("bj_block", C.c_int), ("agg_v", C.c_int),
                 ("agg_p", C.c_int), ("coarse_max", C.c_int), ("use_coarse", C.c_int),
-                ("max_levels", C.c_int), ("verbose", C.c_int), ("compress_qr", C.c_int)]
+                ("max_levels", C.c_int), ("verbose", C.c_int), ("compress_qr", C.c_int),
+                ("child_smoother", C.c_int), ("child_damping", C.c_double)]
 
 
 class RicadiAdiParams(C.Structure):
@@ -127,6 +128,8 @@ SIGNATURES = {
     "ricadi_host_plan_levels": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp,
                                           C.POINTER(RicadiOpts), _ip]),
     "ricadi_host_aggregate": (C.c_int, [C.c_int, _ip, _ip, C.c_int, _ip]),
+    "ricadi_host_vanka_patches": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _ip]),
+    "ricadi_precond_vanka": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip]),
     "ricadi_host_cauchy": (C.c_int, [_dp, C.c_int, _dp, _dp]),
 }
 
@@ -688,7 +691,7 @@ class Context:
 
     TK = dict(spmm=0, block_v=1, block_p=2, coarse=3, spmm_sy=4, dots=5, update_dots=6, update=7,
               precond=8, restrict=9, pc_restrict=10, pc_coarse=11, pc_sy_prows=12, pc_two_term=13,
-              pc_jprod=14, pc_schur=15, pc_rect=16, iter=17, iter_split=18)
+              pc_jprod=14, pc_schur=15, pc_rect=16, iter=17, iter_split=18, pc_vanka=19)
 
     def time_kernel_dev(self, which, alphas, betas, m, nvec=7, reps=100):
         """Milliseconds per launch of one hot-path kernel class (``Context.TK``) as the
@@ -701,11 +704,13 @@ class Context:
         return ms.value
 
     def setup_info(self):
-        a = (C.c_int * 21)()
-        _chk(self._lib.ricadi_setup_info(self._h, a, 21))
+        a = (C.c_int * 27)()
+        _chk(self._lib.ricadi_setup_info(self._h, a, 27))
         return dict(zip(("nv", "np", "nbv", "nbp", "bs", "kc", "spmm_row_blocks", "spmm_max_cols", "levels",
                          "dense_coarse", "fp16_vector_input", "rect_ks", "two_term_ks", "np_", "nnz_j",
-                         "nnz_sy", "nnz_restriction", "coarse_route", "k1_variant", "fp32_intermediate", "fp32_operator_output"),
+                         "nnz_sy", "nnz_restriction", "coarse_route", "k1_variant", "fp32_intermediate", "fp32_operator_output",
+                         "child_smoother", "vanka_colours", "vanka_patches", "vanka_largest_patch", "vanka_dropped",
+                         "vanka_lone_patches"),
                         list(a)))
 
     def dense_inverse_batch(self, mats):
@@ -730,7 +735,8 @@ class Context:
         return dict(h16=bool(w & 1), x32=bool(w & 2), mid32=bool(w & 4), b16=bool(w & 8),
                     restrict=cls.PCF_RESTRICT[(w >> 4) & 3], coarse=cls.PCF_COARSE[(w >> 6) & 3],
                     pfused=bool(w & (1 << 8)), psplit=bool(w & (1 << 9)), first=cls.PCF_FIRST[(w >> 10) & 3],
-                    last=cls.PCF_LAST[(w >> 12) & 3], folded=bool(w & (1 << 14)), two_term_ks=(w >> 16) & 255,
+                    last=cls.PCF_LAST[(w >> 12) & 3], folded=bool(w & (1 << 14)), vanka=bool(w & (1 << 15)),
+                    two_term_ks=(w >> 16) & 255,
                     rect_ks=(w >> 24) & 255)
 
     def precond_apply_batch_dev(self, alphas, betas, r_ptr, r_stride, m, z_ptr, active=None):
@@ -789,6 +795,11 @@ class Context:
         out.update(nv=nv, np=np_, nbv=nbv, nbp=nbp, bs=bs, kc=kc, kcv=kcv, kcp=kcp, smoothed=bool(sa), P=P,
                    child=bool(child), folded=bool(folded), rect=bool(rect), precond32=bool(p32))
         return out
+
+    def precond_vanka(self, level=1):
+        """The patches of the coloured Vanka sweep of ``level`` (a child level) as the device uses them: the dict
+        of ``host_vanka_patches`` (every size 0 where the level has no Vanka sweep)."""
+        return _vanka_records(lambda sz, cp, pi: self._lib.ricadi_precond_vanka(self._h, int(level), sz, cp, pi))
 
     def time_qr_dev(self, z_ptr, c, reps):
         ms = C.c_double(0.0)
@@ -877,6 +888,34 @@ def _project_pencil_dev(self, q_ptr, k, ha_ptr, he_ptr):
 
 Context.project_pencil = _project_pencil
 Context.project_pencil_dev = _project_pencil_dev
+
+
+def _vanka_records(call):
+    sz = np.zeros(8, dtype=np.int32)
+    _chk(call(_i(sz), None, None))
+    ncol, npat = int(sz[0]), int(sz[1])
+    cp = np.zeros(ncol + 1, dtype=np.int32)
+    idx = np.full((npat, 64), -1, dtype=np.int32)
+    _chk(call(_i(sz), _i(cp), _i(idx)))
+    return dict(colours=ncol, patches=npat, pressure_patches=int(sz[2]), largest=int(sz[3]), dropped=int(sz[4]),
+                lone=int(sz[5]), lone_patches=int(sz[6]), colour_ptr=cp, patch_idx=idx)
+
+
+def host_vanka_patches(nv, J):
+    """Patches and colours of the coloured Vanka sweep for a level with ``nv`` velocity unknowns and the
+    constraint matrix ``J`` (np x nv; every STORED entry counts, also an explicit zero), computed on the host
+    (``ricadi_host_vanka_patches``; no GPU): dict with ``colours``, ``patches`` (lone pseudo-patches included),
+    ``pressure_patches``, ``largest``, ``dropped``, ``lone``, ``lone_patches``, ``colour_ptr`` (first patch of
+    every colour) and ``patch_idx`` (patches x 64, -1 padded, colour by colour)."""
+    J = sps.csr_matrix(J, dtype=np.float64)
+    if J.shape[1] != nv:
+        raise ValueError("J has the wrong number of columns")
+    rp = np.ascontiguousarray(J.indptr, dtype=np.int32)
+    ci = np.ascontiguousarray(J.indices, dtype=np.int32)
+    v = np.ascontiguousarray(J.data, dtype=np.float64)
+    lib = load()
+    return _vanka_records(lambda sz, cp, pi: lib.ricadi_host_vanka_patches(int(nv), J.shape[0], _i(rp), _i(ci),
+                                                                           _d(v), sz, cp, pi))
 
 
 def host_aggregate(pattern, bsize):

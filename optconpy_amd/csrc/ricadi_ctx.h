@@ -196,6 +196,10 @@ struct ShiftData {
   long smw_epoch = -1;
   int last_iters = -1;        // iterations of this shift's last lockstep GMRES solve (gmres_core's split into halves)
   ShiftData* sub = nullptr;   // the same shift on the child level (multilevel preconditioner)
+  // coloured Vanka sweep of a child level: the 64 x 64 patch inverses of this shift in patch order, as the level stores
+  // its operands (vkinv in FP64, always; vkinvf the FP32 copies the cycle applies unless RICADI_PRECOND64=1)
+  DArr<double> vkinv;
+  DArr<float> vkinvf;
   // recycled solves (ricadi_set_recycle): y with S(alpha,beta) y = b for the right-hand side panels of
   // the context's ring that carry the same serial number; n x w each
   struct RecY {
@@ -303,6 +307,11 @@ struct ricadi_ctx {
   bool sa = false;
   DArr<int> pt_rp, pt_ci;
   DArr<double> pt_v;
+  // coloured Vanka sweep (a child level with opts.child_smoother = 1; vanka_patches of ricadi_host.cpp): the records in
+  // colour order (device) and the first patch of every colour (host)
+  bool vanka = false;
+  VankaPatches vk;
+  DArr<int> vk_idx;
   bool gt_ok = false;
   int gt_ks = 0;
   DArr<int> gt_ptr, gt_cols;

@@ -1084,9 +1084,94 @@ PrecondRecords build_records(const HostSetup& hs, const HostCsr& J, const HostCs
   return r;
 }
 
+// ---- coloured Vanka sweep: patches and colours ----------------------------------------
+VankaPatches vanka_patches(int nv, const HostCsr& J) {
+  VankaPatches vp;
+  const int np = J.nrows;
+  vp.npress = np;
+  std::vector<std::vector<int>> pat(np);
+  std::vector<char> held(nv, 0);
+  for (int i = 0; i < np; ++i) {
+    std::vector<int> ks;
+    for (int k = J.rp[i]; k < J.rp[i + 1]; ++k) ks.push_back(k);
+    // duplicates of a column (none in a canonical CSR) count once: the first
+    std::sort(ks.begin(), ks.end(), [&](int a, int b) { return J.ci[a] != J.ci[b] ? J.ci[a] < J.ci[b] : a < b; });
+    ks.erase(std::unique(ks.begin(), ks.end(), [&](int a, int b) { return J.ci[a] == J.ci[b]; }), ks.end());
+    if ((int)ks.size() > VANKA_K - 1) {
+      // the size cap: the VANKA_K - 1 entries of largest |J_iv|, ties to the lower index
+      std::stable_sort(ks.begin(), ks.end(), [&](int a, int b) { return std::fabs(J.v[a]) > std::fabs(J.v[b]); });
+      vp.dropped += (int)ks.size() - (VANKA_K - 1);
+      ks.resize(VANKA_K - 1);
+    }
+    std::vector<int>& p = pat[i];
+    for (int k : ks) p.push_back(J.ci[k]);
+    std::sort(p.begin(), p.end());
+    for (int v : p) held[v] = 1;
+    p.push_back(nv + i);
+    vp.largest = std::max(vp.largest, (int)p.size());
+  }
+  // first-fit colouring in patch order: per unknown the colours of the patches that hold it so far
+  std::vector<std::vector<int>> used(nv);
+  std::vector<int> colour(np, 0), mark;
+  int ncol = 0;
+  for (int i = 0; i < np; ++i) {
+    mark.assign(ncol + 1, 0);
+    for (size_t q = 0; q + 1 < pat[i].size(); ++q)
+      for (int c : used[pat[i][q]]) mark[c] = 1;
+    int c = 0;
+    while (mark[c]) ++c;
+    colour[i] = c;
+    ncol = std::max(ncol, c + 1);
+    for (size_t q = 0; q + 1 < pat[i].size(); ++q) used[pat[i][q]].push_back(c);
+  }
+  std::vector<int> lone;
+  for (int v = 0; v < nv; ++v)
+    if (!held[v]) lone.push_back(v);
+  vp.nlone = (int)lone.size();
+  vp.nlone_patches = (vp.nlone + VANKA_K - 1) / VANKA_K;
+  vp.ncolours = ncol + (vp.nlone_patches > 0 ? 1 : 0);
+  vp.npatches = np + vp.nlone_patches;
+  vp.colour_ptr.assign(vp.ncolours + 1, 0);
+  for (int i = 0; i < np; ++i) ++vp.colour_ptr[colour[i] + 1];
+  if (vp.nlone_patches > 0) vp.colour_ptr[vp.ncolours] = vp.nlone_patches;
+  for (int c = 0; c < vp.ncolours; ++c) vp.colour_ptr[c + 1] += vp.colour_ptr[c];
+  vp.idx.assign((size_t)vp.npatches * VANKA_K, -1);
+  std::vector<int> at(vp.colour_ptr.begin(), vp.colour_ptr.end() - 1);
+  for (int i = 0; i < np; ++i) std::copy(pat[i].begin(), pat[i].end(), vp.idx.begin() + (size_t)at[colour[i]]++ * VANKA_K);
+  for (int q = 0; q < vp.nlone; ++q) vp.idx[(size_t)np * VANKA_K + q] = lone[q];
+  return vp;
+}
+
 }  // namespace ricadi
 
 extern "C" {
+
+int ricadi_host_vanka_patches(int nv, int np, const int32_t* j_rp, const int32_t* j_ci, const double* j_v,
+                              int32_t* sizes_out, int32_t* colour_ptr, int32_t* patch_idx) {
+  if (nv < 1 || np < 0 || !sizes_out || (np > 0 && (!j_rp || !j_ci || !j_v))) {
+    ricadi::set_error("ricadi_host_vanka_patches: bad argument");
+    return RICADI_EINVAL;
+  }
+  try {
+    const int32_t zero = 0;
+    const double dzero = 0.0;
+    const ricadi::HostCsr J = np > 0 ? ricadi::make_csr(np, nv, j_rp, j_ci, j_v) : ricadi::make_csr(0, nv, &zero, &zero, &dzero);
+    for (size_t k = 0; k < J.nnz(); ++k)
+      if (J.ci[k] < 0 || J.ci[k] >= nv) {
+        ricadi::set_error("ricadi_host_vanka_patches: column index out of range");
+        return RICADI_EINVAL;
+      }
+    const ricadi::VankaPatches vp = ricadi::vanka_patches(nv, J);
+    const int32_t sz[8] = {vp.ncolours, vp.npatches, vp.npress, vp.largest, vp.dropped, vp.nlone, vp.nlone_patches, 0};
+    std::copy(sz, sz + 8, sizes_out);
+    if (colour_ptr) std::copy(vp.colour_ptr.begin(), vp.colour_ptr.end(), colour_ptr);
+    if (patch_idx) std::copy(vp.idx.begin(), vp.idx.end(), patch_idx);
+  } catch (...) {
+    ricadi::set_error("ricadi_host_vanka_patches: exception");
+    return RICADI_EINVAL;
+  }
+  return RICADI_OK;
+}
 
 int ricadi_host_aggregate(int n, const int32_t* rowptr, const int32_t* col, int bsize,
                           int32_t* blk_out) {

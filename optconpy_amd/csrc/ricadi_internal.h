@@ -30,6 +30,15 @@ void sort_rows(HostCsr& a);
 
 int aggregate(int n, const int* rp, const int* ci, int bsize, int* blk);
 
+// Patches and colours of the coloured Vanka sweep of a level, from its J alone (ricadi_host_vanka_patches of
+// include/ricadi.h states the rule).  idx: VANKA_K indices per patch, -1 padded, colour by colour.
+constexpr int VANKA_K = 64;
+struct VankaPatches {
+  int ncolours = 0, npatches = 0, npress = 0, largest = 0, dropped = 0, nlone = 0, nlone_patches = 0;
+  std::vector<int> colour_ptr, idx;
+};
+VankaPatches vanka_patches(int nv, const HostCsr& J);
+
 // Host-built description of the saddle operator and the two-level
 // preconditioner's fixed (shift independent) parts.
 struct HostSetup {
@@ -436,6 +445,16 @@ void launch_project_pencil(hipStream_t st, int nv, int k, const int* rp, const i
                            double* part, double* HA, double* HE);
 void launch_project_lowrank(hipStream_t st, int k, int q, const double* QU, const double* QV, double* HA);
 
+// coloured Vanka sweep of a child level (ricadi_precond.hip): the patch matrices S[idx, idx] of up to RICADI_MAX_GROUPS
+// shifts per launch (mats[i]: npatches x 64 x 64 of shift i; patches from first_lone on: diagonal only); one colour
+// z[idx_b] += omega Inv_b rho[idx_b] over the patches [p0, p0 + count); z = Y ec (aggof == nullptr: z = 0)
+void launch_vanka_gather(hipStream_t st, int nshift, int npatches, int first_lone, const int* idx, const int* s_rp,
+                         const int* s_ci, const GroupPtrs& sval, double* const* mats);
+template <class T>
+void launch_vanka_patch(hipStream_t st, const GroupTab& gt, int p0, int count, const int* idx, const GroupPtrsT<T>& invs,
+                        const double* rho, size_t gsr, double* z, size_t gsz, int m, double omega);
+void launch_prolong_plain(hipStream_t st, const GroupTab& gt, int n, int m, const int* aggof, const double* ec,
+                          size_t gse, double* z, size_t gsz);
 // dst (BF16 bit patterns, round to nearest even) = src (FP64), n entries
 void launch_to_bf16(hipStream_t st, size_t n, const double* src, uint16_t* dst);
 // The hot-shape sweeps (32-row blocks, 16 columns, fixed-stride records in pa.bmeta) on BF16-stored blocks: same

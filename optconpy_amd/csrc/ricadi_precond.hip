@@ -1787,6 +1787,148 @@ void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, con
                      rp16, gsr, out, gso, pa, zv32, gsz32);
 }
 
+// ---------------------------------------------------------------------------
+// Coloured Vanka sweep of a child level (ricadi_opts::child_smoother = 1).  A patch is a record of VANKA_K = 64
+// unknowns of the level (ascending, -1 padded; ricadi_host_vanka_patches), its operand the 64 x 64 inverse of the
+// level's operator on those unknowns (row-major, padding rows / columns identity), one array of all patches per shift.
+// ---------------------------------------------------------------------------
+// Setup: M(patch) = S[idx, idx] from the level's assembled CSR values of one shift, for every (patch, shift).
+// One workgroup per (patch, shift); the matrix is built in LDS and written once.  Four threads walk a row of S; a
+// column is looked up in the sorted record by bisection.  Patches from first_lone on are the diagonal pseudo-patches
+// of the lone velocity unknowns: only S[i, i] is taken.
+struct VankaMats {
+  double* p[RICADI_MAX_GROUPS];
+};
+__global__ __launch_bounds__(256) void vanka_gather_kernel(int first_lone, const int* __restrict__ idx,
+                                                           const int* __restrict__ s_rp, const int* __restrict__ s_ci,
+                                                           GroupPtrs sval, VankaMats out) {
+  __shared__ int id[VANKA_K];
+  __shared__ double Ms[VANKA_K * VANKA_K];
+  const int pch = blockIdx.x;
+  const double* __restrict__ val = sval.p[blockIdx.y];
+  double* __restrict__ M = out.p[blockIdx.y] + (size_t)pch * VANKA_K * VANKA_K;
+  if (threadIdx.x < VANKA_K) id[threadIdx.x] = idx[(size_t)pch * VANKA_K + threadIdx.x];
+  __syncthreads();
+  int cnt = 0;
+  for (int i = 0; i < VANKA_K; ++i) cnt += id[i] >= 0 ? 1 : 0;
+  for (int e = threadIdx.x; e < VANKA_K * VANKA_K; e += 256) {
+    const int i = e / VANKA_K, j = e % VANKA_K;
+    Ms[e] = (i == j && i >= cnt) ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  const int i = threadIdx.x >> 2;
+  if (i < cnt) {
+    const int row = id[i];
+    for (int k = s_rp[row] + (threadIdx.x & 3); k < s_rp[row + 1]; k += 4) {
+      const int col = s_ci[k];
+      int lo = 0, hi = cnt;               // first position with id[pos] >= col
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (id[mid] < col) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo < cnt && id[lo] == col && (pch < first_lone || lo == i)) Ms[i * VANKA_K + lo] = val[k];
+    }
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < VANKA_K * VANKA_K; e += 256) M[e] = Ms[e];
+}
+void launch_vanka_gather(hipStream_t st, int nshift, int npatches, int first_lone, const int* idx, const int* s_rp,
+                         const int* s_ci, const GroupPtrs& sval, double* const* mats) {
+  if (npatches <= 0 || nshift <= 0) return;
+  VankaMats out;
+  for (int i = 0; i < RICADI_MAX_GROUPS; ++i) out.p[i] = i < nshift ? mats[i] : nullptr;
+  hipLaunchKernelGGL(vanka_gather_kernel, dim3(npatches, nshift), dim3(256), 0, st, first_lone, idx, s_rp, s_ci, sval,
+                     out);
+}
+
+// One colour:  z[idx_b] += omega * Inv_b * rho[idx_b]  for the patches [p0, p0 + gridDim.x) and every active group.
+// One workgroup of four waves per (patch, group); wave w owns the output rows 16 w .. 16 w + 15 of the patch and
+// gathers all 64 rows of the panel rho through the record (one row of a 16-column panel = one 128-B line; the other
+// three waves' copies hit the cache).  All index loads go out in one round (four 16-B loads and four words per lane),
+// the operand loads beside them, then the 16 row gathers in one round.  FP64 MFMA 16x16x4, the stored operand (FP32
+// or FP64) widened in registers.  Wider or narrower panels: the kernel loops over 16-column slices.  The patches of
+// a colour share no unknown, so the read-modify-write of z needs no atomics; rho and z are different panels.
+template <class T>
+__global__ __launch_bounds__(256) void vanka_patch_kernel(GroupTab gt, int p0, const int* __restrict__ idx,
+                                                          GroupPtrsT<T> invs, const double* __restrict__ rho, size_t gsr,
+                                                          double* __restrict__ z, size_t gsz, int m, double omega) {
+  const int grp = gt.gid[blockIdx.y];
+  const int pch = p0 + blockIdx.x;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const int* __restrict__ rec = idx + (size_t)pch * VANKA_K;
+  const T* __restrict__ inv = invs.p[grp] + (size_t)pch * VANKA_K * VANKA_K + (size_t)(16 * w + r) * VANKA_K + 4 * q;
+  rho += (size_t)grp * gsr;
+  z += (size_t)grp * gsz;
+  int4 ik[4];
+  int io[4];
+  typename Raw4<T>::type a[4];
+#pragma unroll
+  for (int kc = 0; kc < 4; ++kc) ik[kc] = *reinterpret_cast<const int4*>(rec + 16 * kc + 4 * q);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) io[e] = rec[16 * w + q + 4 * e];
+#pragma unroll
+  for (int kc = 0; kc < 4; ++kc) a[kc] = Raw4<T>::load(inv + 16 * kc);
+  for (int c0 = 0; c0 < m; c0 += 16) {
+    const bool ok = c0 + r < m;
+    const int col = ok ? c0 + r : m - 1;
+    double xb[4][4];
+#pragma unroll
+    for (int kc = 0; kc < 4; ++kc) {
+      const int rows[4] = {ik[kc].x, ik[kc].y, ik[kc].z, ik[kc].w};
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) xb[kc][s4] = rho[(size_t)max(rows[s4], 0) * m + col];
+    }
+    d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int kc = 0; kc < 4; ++kc) {
+      const int rows[4] = {ik[kc].x, ik[kc].y, ik[kc].z, ik[kc].w};
+      double a4[4];
+      Raw4<T>::unpack(a[kc], a4);
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[s4], (rows[s4] >= 0 && ok) ? xb[kc][s4] : 0.0, acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (io[e] >= 0 && ok) {
+        double* o = z + (size_t)io[e] * m + col;
+        *o = fma(omega, acc[e], *o);
+      }
+  }
+}
+template <class T>
+void launch_vanka_patch(hipStream_t st, const GroupTab& gt, int p0, int count, const int* idx, const GroupPtrsT<T>& invs,
+                        const double* rho, size_t gsr, double* z, size_t gsz, int m, double omega) {
+  if (count <= 0 || gt.ng <= 0) return;
+  hipLaunchKernelGGL((vanka_patch_kernel<T>), dim3(count, gt.ng), dim3(256), 0, st, gt, p0, idx, invs, rho, gsr, z, gsz,
+                     m, omega);
+}
+template void launch_vanka_patch(hipStream_t, const GroupTab&, int, int, const int*, const GroupPtrsT<double>&,
+                                 const double*, size_t, double*, size_t, int, double);
+template void launch_vanka_patch(hipStream_t, const GroupTab&, int, int, const int*, const GroupPtrsT<float>&,
+                                 const double*, size_t, double*, size_t, int, double);
+
+// z = Y ec on all n rows of every active group (plain aggregation; aggof == nullptr: z = 0): the start of a cycle
+// whose sweep adds to z instead of writing it
+__global__ __launch_bounds__(256) void prolong_plain_kernel(GroupTab gt, size_t nm, int m, const int* __restrict__ aggof,
+                                                            const double* __restrict__ ec, size_t gse,
+                                                            double* __restrict__ z, size_t gsz) {
+  const int grp = gt.gid[blockIdx.y];
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= nm) return;
+  const size_t row = e / m, col = e - row * m;
+  z[(size_t)grp * gsz + e] = aggof ? ec[(size_t)grp * gse + (size_t)aggof[row] * m + col] : 0.0;
+}
+void launch_prolong_plain(hipStream_t st, const GroupTab& gt, int n, int m, const int* aggof, const double* ec,
+                          size_t gse, double* z, size_t gsz) {
+  if (n <= 0 || gt.ng <= 0) return;
+  const size_t nm = (size_t)n * m;
+  hipLaunchKernelGGL(prolong_plain_kernel, dim3((unsigned)((nm + 255) / 256), gt.ng), dim3(256), 0, st, gt, nm, m,
+                     aggof, ec, gse, z, gsz);
+}
+
 // the preconditioner's operands stored in FP64 (GroupPtrs) or FP32 (GroupPtrsF)
 #define RICADI_PRECOND_LAUNCHERS(T)                                                                                   \
   template void launch_block_apply_b(hipStream_t, const GroupTab&, int, int, const int*, const int*,                  \

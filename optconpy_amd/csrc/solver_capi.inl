@@ -53,11 +53,11 @@ static double timed_ms(hipStream_t st, int reps, Fn&& fn) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 401; }
+int ricadi_version(void) { return 402; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
-const char* ricadi_struct_signature(void) { return "ricadi_opts:diiiiiiiiii;ricadi_adi_params:ididdiiii"; }
+const char* ricadi_struct_signature(void) { return "ricadi_opts:diiiiiiiiiiid;ricadi_adi_params:ididdiiii"; }
 
 void ricadi_default_opts(ricadi_opts* o) {
   if (!o) return;
@@ -72,6 +72,8 @@ void ricadi_default_opts(ricadi_opts* o) {
   o->max_levels = 3;
   o->verbose = 0;
   o->compress_qr = 1;
+  o->child_smoother = 0;
+  o->child_damping = 0.7;
 }
 
 void ricadi_default_adi_params(ricadi_adi_params* p) {
@@ -156,10 +158,14 @@ int ricadi_set_opts(ricadi_ctx* c, const ricadi_opts* o) {
   REQUIRE(c && o, RICADI_EINVAL, "ricadi_set_opts: NULL argument");
   REQUIRE(o->gmres_restart >= 2 && o->gmres_restart <= 400, RICADI_EINVAL, "gmres_restart out of range");
   REQUIRE(o->gmres_tol > 0 && o->gmres_maxit > 0, RICADI_EINVAL, "bad gmres_tol / gmres_maxit");
+  REQUIRE(o->child_smoother == 0 || o->child_smoother == 1, RICADI_EINVAL, "child_smoother must be 0 or 1");
+  REQUIRE(o->child_damping > 0 && o->child_damping <= 2, RICADI_EINVAL, "child_damping out of range");
   const bool structural = c->has_op && (o->bj_block != c->opts.bj_block || o->agg_v != c->opts.agg_v ||
                                         o->agg_p != c->opts.agg_p || o->coarse_max != c->opts.coarse_max ||
                                         o->max_levels != c->opts.max_levels ||
-                                        o->use_coarse != c->opts.use_coarse);
+                                        o->use_coarse != c->opts.use_coarse ||
+                                        o->child_smoother != c->opts.child_smoother ||
+                                        o->child_damping != c->opts.child_damping);
   REQUIRE(!structural, RICADI_ESTATE, "preconditioner options must be set before ricadi_set_operator");
   c->opts = *o;
   return RICADI_OK;
@@ -258,6 +264,10 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   c->E.upload(E, st);
   c->J.upload(J, st);
   c->JT.upload(JT, st);
+  // a child level's coloured Vanka sweep: patches and colours from its J (shift independent)
+  c->vanka = c->borrowed && c->opts.child_smoother == 1 && np > 0;
+  c->vk = c->vanka ? vanka_patches(nv, J) : VankaPatches();
+  c->vk_idx.upload(c->vk.idx, st);
   c->gt_ok = pr.gt_ok;
   c->gt_ks = pr.gt_ks;
   c->gt_ptr.upload(pr.gt_ptr, st);
@@ -736,6 +746,27 @@ int ricadi_precond_structure(ricadi_ctx* c, int level, int32_t* sizes_out, int32
   API_END
 }
 
+int ricadi_precond_vanka(ricadi_ctx* c, int level, int32_t* sizes_out, int32_t* colour_ptr, int32_t* patch_idx) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(sizes_out && level >= 0, RICADI_EINVAL, "bad argument");
+  const ricadi_ctx* l = c;
+  for (int i = 0; i < level && l; ++i) l = l->child.get();
+  REQUIRE(l, RICADI_EINVAL, "no such level");
+  API_BEGIN
+  (void)hipSetDevice(c->dev);
+  const VankaPatches& vp = l->vk;
+  const int32_t sz[8] = {vp.ncolours, vp.npatches, l->vanka ? vp.npress : 0, vp.largest, vp.dropped, vp.nlone,
+                         vp.nlone_patches, 0};
+  std::copy(sz, sz + 8, sizes_out);
+  if (colour_ptr) std::copy(vp.colour_ptr.begin(), vp.colour_ptr.end(), colour_ptr);
+  // the records as the device holds them
+  if (patch_idx && l->vk_idx.n) {
+    HIPCHK(hipMemcpyAsync(patch_idx, l->vk_idx.p, sizeof(int32_t) * l->vk_idx.n, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+  }
+  API_END
+}
+
 int ricadi_shift_solve_dev(ricadi_ctx* c, double alpha, double beta, const double* dR, int m,
                            double* dX, int* iters_out, double* relres_out) {
   if (int rc = check_panel(c, m)) return rc;
@@ -1095,6 +1126,20 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
         cycle_begin(c, pf, io);
         cycle_stages[which - 10](c, bt, pf, io);
         break;
+      case RICADI_TK_PC_VANKA: {
+        // the Vanka sweep lives on a child level: all its colours on that level's panels, as pc_vanka issues them
+        ricadi_ctx* lc = c;
+        Batch lb = bt;
+        while (lc && !lc->vanka) {
+          if (!lc->child) throw HipError{"no coarse level with a Vanka sweep"};
+          Batch t = *lb.sub;
+          t.tab = bt.tab;
+          lb = t;
+          lc = lc->child.get();
+        }
+        vanka_colours(lc, lb, CycleIO{lc->wv.p, lb.gs, nullptr, lc->zv.p});
+        break;
+      }
       case RICADI_TK_ITER: case RICADI_TK_ITER_SPLIT:
         break;   // (below)
       default:
@@ -1239,6 +1284,15 @@ int ricadi_setup_info(ricadi_ctx* c, int* out, int nout) {
   if (nout > 19) out[19] = c->mid32_last;
   // [20]: the operator launch of the last iteration / timing call wrote w as an FP32 panel (1) or FP64 (0); -1 none yet
   if (nout > 20) out[20] = c->w32_last;
+  // [21] .. [26]: the coloured Vanka sweep of the first child level that has one: in use, colours, patches (one per
+  // pressure unknown of that level), largest patch, entries of J dropped by the size cap, lone pseudo-patches
+  const ricadi_ctx* vc = c->child.get();
+  while (vc && !vc->vanka) vc = vc->child.get();
+  if (vc) {
+    const int v[6] = {1, vc->vk.ncolours, vc->vk.npress, vc->vk.largest, vc->vk.dropped, vc->vk.nlone_patches};
+    for (int i = 0; i < 6; ++i)
+      if (nout > 21 + i) out[21 + i] = v[i];
+  }
   return RICADI_OK;
 }
 

@@ -15,6 +15,8 @@ struct Batch {
   GroupPtrs gtm, adym;
   GroupPtrsF gtmf, adymf;
   GroupPtrsH bvinvh, bpinvh, gtmh, adymh;     // BF16 copies (null where a shift has none)
+  GroupPtrs vkinv;                            // patch inverses of the coloured Vanka sweep (a child level's batch)
+  GroupPtrsF vkinvf;
   bool blocks16 = false;                       // every group of the batch has them
   size_t gs = 0, gsp = 0, gsc = 0, gsq = 0;   // strides: n*m, np*m, kc*m, q*m
   std::shared_ptr<Batch> sub;                 // the same groups on the child level
@@ -48,6 +50,8 @@ static Batch make_batch(ricadi_ctx* c, ShiftData* const* sds, int G, int m) {
   bt.gtm = bt.adym = same_ptr((const double*)nullptr);
   bt.gtmf = bt.adymf = same_ptr((const float*)nullptr);
   bt.bvinvh = bt.bpinvh = bt.gtmh = bt.adymh = same_ptr((const uint16_t*)nullptr);
+  bt.vkinv = same_ptr((const double*)nullptr);
+  bt.vkinvf = same_ptr((const float*)nullptr);
   bt.blocks16 = c->sw.blocks16 && G > 0;
   for (int g = 0; g < RICADI_MAX_GROUPS; ++g) bt.alpha[g] = bt.beta[g] = 0.0;
   for (int g = 0; g < G; ++g) {
@@ -72,6 +76,8 @@ static Batch make_batch(ricadi_ctx* c, ShiftData* const* sds, int G, int m) {
     bt.bvinv.p[g] = sds[g]->bvinv.p;
     bt.bpinv.p[g] = sds[g]->bpinv.p;
     bt.einv.p[g] = sds[g]->einv.p;
+    bt.vkinv.p[g] = sds[g]->vkinv.p;
+    bt.vkinvf.p[g] = sds[g]->vkinvf.p;
   }
   bt.gs = (size_t)c->n * m;
   bt.gsp = (size_t)c->np * m;
@@ -220,7 +226,7 @@ struct CycleForm {
   enum SyResidual { SY_NONE, SY_PROWS, SY_FULL } sy = SY_NONE;
   // first velocity sweep: plain on r2, two-term with the coarse residual folded in, or that on BF16 blocks (pipe:
   // its second segment's loads in flight behind the first segment's MFMAs)
-  enum First { FS_PLAIN, FS_TWO_TERM, FS_TWO32, FS_TWO32_PIPE } first = FS_PLAIN;
+  enum First { FS_PLAIN, FS_TWO_TERM, FS_TWO32, FS_TWO32_PIPE, FS_NONE } first = FS_PLAIN;
   // pressure step: one launch (K2p) on BF16 / FP32-or-FP64 blocks, or J product and Schur sweep on their own
   enum Pressure { PS_NONE, PS_FUSED16, PS_FUSED, PS_SPLIT } pressure = PS_NONE;
   // last velocity sweep: dense rectangles on BF16 / FP32-or-FP64 blocks, or the J^T product formed row by row
@@ -230,14 +236,17 @@ struct CycleForm {
   bool mid32 = false;   // the velocity part between the sweeps as an FP32 panel
   bool b16 = false;     // BF16-stored per-shift blocks
   bool folded = false;  // the coarse residual is formed inside the first sweep and the pressure step
+  // a child level's coloured Vanka sweep in place of the SIMPLE sweeps: z = Y ec, then per colour the residual of the
+  // level's operator and the patch kernel (pc_vanka); first = FS_NONE, no pressure step, no last sweep
+  bool vanka = false;
   int two_ks = 0, rect_ks = 0;   // padded widths of the two-term sweep's second block / of the rectangles (0: none)
   // the form word of include/ricadi.h (restriction and last: their values are the 2-bit codes)
   unsigned word() const {
     unsigned w = (h16 ? RICADI_PCF_H16 : 0) | (x32 ? RICADI_PCF_X32 : 0) | (mid32 ? RICADI_PCF_MID32 : 0) |
-                 (b16 ? RICADI_PCF_B16 : 0) | (folded ? RICADI_PCF_FOLDED : 0);
+                 (b16 ? RICADI_PCF_B16 : 0) | (folded ? RICADI_PCF_FOLDED : 0) | (vanka ? RICADI_PCF_VANKA : 0);
     w |= (unsigned)restriction << RICADI_PCF_RESTRICT_SHIFT | (unsigned)last << RICADI_PCF_LAST_SHIFT;
     if (coarse != CO_NONE) w |= (coarse == CO_CHILD ? 1u : 2u) << RICADI_PCF_COARSE_SHIFT;
-    w |= (first == FS_PLAIN ? 3u : first == FS_TWO_TERM ? 2u : 1u) << RICADI_PCF_FIRST_SHIFT;
+    w |= (first == FS_NONE ? 0u : first == FS_PLAIN ? 3u : first == FS_TWO_TERM ? 2u : 1u) << RICADI_PCF_FIRST_SHIFT;
     if (pressure != PS_NONE) w |= pressure == PS_SPLIT ? RICADI_PCF_PSPLIT : RICADI_PCF_PFUSED;
     return w | (unsigned)two_ks << RICADI_PCF_TWO_KS_SHIFT | (unsigned)rect_ks << RICADI_PCF_RECT_KS_SHIFT;
   }
@@ -248,6 +257,18 @@ struct CycleForm {
 static CycleForm cycle_form(const ricadi_ctx* c, int m, bool blocks16, size_t gsr, bool out32, bool in16) {
   CycleForm f;
   const size_t gs = (size_t)c->n * m;
+  if (c->vanka) {
+    // the unfolded cycle with the Vanka sweep: restriction and coarse apply as ever, everything after them in pc_vanka
+    f.vanka = true;
+    f.x32 = out32;
+    f.first = f.FS_NONE;
+    if (c->kc > 0) {
+      const bool rowwave = m == 16 && c->sw.rowwave && spmm_rowwave_pays(c->kc, (size_t)c->n);
+      f.restriction = rowwave ? f.RS_ROWWAVE : f.RS_CSR64;
+      f.coarse = c->child ? f.CO_CHILD : c->sw.coarse_pipe && c->precond32 && rowwave ? f.CO_DENSE_KB : f.CO_DENSE;
+    }
+    return f;
+  }
   // the pressure step -- pressure rows of r - (S Y) e, J product, Schur sweep -- as ONE launch for 16-column panels
   const bool fusedp = c->np > 0 && m == 16 && c->bs == 32;
   f.folded = c->kc > 0 && c->ady_ok && c->np > 0;
@@ -378,6 +399,7 @@ static void pc_sy_prows(ricadi_ctx* c, const Batch& bt, const CycleForm& f, cons
 }
 static void pc_two_term(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
   const int m = bt.m;
+  if (f.first == f.FS_NONE) return;
   if (f.first == f.FS_PLAIN) {
     // on r2 (on r without a coarse level); without pressure rows this sweep writes z last
     const bool r2 = c->kc > 0;
@@ -499,9 +521,31 @@ static void pc_rect(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const Cy
     launch_block_apply_rect_b(bt.st, bt.tab, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
                               c->gt_cols.p, bt.gtm, c->tp.p, m, bt.gsp, io.z, m, bt.gs, m, 1, pa);
 }
+// The coloured Vanka sweep of a child level (CycleForm::vanka), colour after colour on the iterate as it stood
+// before the colour:  rho = r - S z (the level's saddle product in its residual form, tiled or CSR as the level
+// chooses), then z[idx_b] += omega Inv_b rho[idx_b] for every patch b of the colour -- two launches per colour.
+// (One in-place kernel that forms its own residual rows would race: a patch reads columns of z that another patch
+// of the same colour writes.)
+static void vanka_colours(ricadi_ctx* c, const Batch& bt, const CycleIO& io) {
+  const double omega = c->opts.child_damping;
+  for (int col = 0; col < c->vk.ncolours; ++col) {
+    const int p0 = c->vk.colour_ptr[col], cnt = c->vk.colour_ptr[col + 1] - p0;
+    saddle_spmm(c, bt, io.z, bt.gs, nullptr, c->r2.p, bt.gs, io.r, io.gsr, -1.0, 1.0);
+    if (c->precond32)
+      launch_vanka_patch(bt.st, bt.tab, p0, cnt, c->vk_idx.p, bt.vkinvf, c->r2.p, bt.gs, io.z, bt.gs, bt.m, omega);
+    else
+      launch_vanka_patch(bt.st, bt.tab, p0, cnt, c->vk_idx.p, bt.vkinv, c->r2.p, bt.gs, io.z, bt.gs, bt.m, omega);
+  }
+}
+static void pc_vanka(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
+  if (!f.vanka) return;
+  // z = Y ec: the sweep adds to it (plain aggregation on a child level)
+  launch_prolong_plain(bt.st, bt.tab, c->n, bt.m, c->kc > 0 ? c->aggof.p : nullptr, c->ec.p, bt.gsc, io.z, bt.gs);
+  vanka_colours(c, bt, io);
+}
 using CycleStage = void (*)(ricadi_ctx*, const Batch&, const CycleForm&, const CycleIO&);
 static const CycleStage cycle_stages[] = {pc_restrict, pc_coarse, pc_sy_prows, pc_two_term,
-                                          pc_jprod,    pc_schur,  pc_rect};
+                                          pc_jprod,    pc_schur,  pc_rect,     pc_vanka};
 
 // what an application of the cycle, or of one of its stages, does first
 static void cycle_begin(ricadi_ctx* c, const CycleForm& f, const CycleIO& io) {

@@ -283,6 +283,11 @@ static void setup_issue(ricadi_ctx* c, const Exec& ex, const double* alphas, con
       stable_alloc(sd->syval, c->synnz);
       if (c->syb_ok) stable_alloc(sd->syvalb, c->synnz);
     }
+    if (c->vanka) {
+      const size_t vn = (size_t)c->vk.npatches * VANKA_K * VANKA_K;
+      stable_alloc(sd->vkinv, vn);      // (the FP64 originals stay, like einv: a solve repeated with FP64 operands reads them)
+      if (c->precond32) stable_alloc(sd->vkinvf, vn);
+    }
     if (c->precond32) {
       stable_alloc(sd->bvinvf, sd->bvinv.n);
       if (c->nbp > 0) stable_alloc(sd->bpinvf, sd->bpinv.n);
@@ -393,6 +398,42 @@ static void setup_issue(ricadi_ctx* c, const Exec& ex, const double* alphas, con
   lapS(4);
 }
 
+// The patch inverses of the coloured Vanka sweep for the shifts of a setup (a child level; called from setup_finish,
+// when the level's assembled values sd->sval are complete and the route-0 panels of the coarse inverses are free
+// again): gather S[idx, idx] of every (shift, patch), invert the whole batch with the coarse matrices' routine
+// (block Gauss-Jordan, pivoted rocSOLVER route for all of them where a pivot vanishes), store as the level stores
+// its operands (in place in FP64; the FP32 copies beside them where the level's operands are FP32-stored).
+static void vanka_setup(ricadi_ctx* c, const Exec& ex, const std::vector<ShiftData*>& todo) {
+  hipStream_t st = ex.st;
+  const size_t np_ = (size_t)c->vk.npatches, kk = (size_t)VANKA_K * VANKA_K;
+  if (np_ == 0 || todo.empty()) return;
+  std::vector<double*> base(todo.size());
+  for (size_t i = 0; i < todo.size(); ++i) base[i] = todo[i]->vkinv.p;
+  auto gather = [&] {
+    for (size_t t0 = 0; t0 < todo.size(); t0 += RICADI_MAX_GROUPS) {
+      const int cnt = (int)std::min<size_t>(RICADI_MAX_GROUPS, todo.size() - t0);
+      GroupPtrs sv = same_ptr((const double*)nullptr);
+      for (int i = 0; i < cnt; ++i) sv.p[i] = todo[t0 + i]->sval.p;
+      launch_vanka_gather(st, cnt, (int)np_, c->vk.npress, c->vk_idx.p, c->s_rp.p, c->s_ci.p, sv, base.data() + t0);
+    }
+  };
+  gather();
+  std::vector<double*> hp(todo.size() * np_);
+  for (size_t i = 0; i < todo.size(); ++i)
+    for (size_t b = 0; b < np_; ++b) hp[i * np_ + b] = base[i] + kk * b;
+  std::vector<int> info(hp.size(), 0);
+  invert_dense_issue(c, ex, hp, VANKA_K);
+  HIPCHK(hipStreamSynchronize(st));
+  invert_dense_finish(c, ex, hp, VANKA_K, info, gather);
+  for (int v : info)
+    if (v != 0) throw HipError{"Vanka patch matrix singular (getrf/getri info " + std::to_string(v) + ")"};
+  if (c->precond32) {
+    for (size_t i = 0; i < todo.size(); ++i)
+      launch_to_f32(c->st, (int)np_, (int)kk, base[i], (int)kk, todo[i]->vkinvf.p, (int)kk);
+    HIPCHK(hipStreamSynchronize(c->st));
+  }
+}
+
 // Finish half: waits for the issued work, reports a singular block or coarse matrix (same errors as ever), takes
 // the pivoted route for the whole batch where a coarse pivot vanished, makes the FP32 copies of the coarse
 // inverses on the main stream and marks the data valid.
@@ -431,6 +472,7 @@ static void setup_finish(ricadi_ctx* c, SetupJob& job) {
     }
     HIPCHK(hipStreamSynchronize(st));
   }
+  if (c->vanka) vanka_setup(c, ex, todo);
   tph[4] += tf.lap();
   if (c->sw.timing && !c->borrowed)
     fprintf(stderr, "[ricadi timing] setup of %d shifts: child %.1f ms, per-shift assembly %.1f, block inverses + Schur blocks %.1f, coarse inverses %.1f, FP32 copies %.1f\n",

@@ -16,8 +16,8 @@ namespace ricadi {
 #include "solver_setup.inl"
 #include "solver_precond.inl"
 #include "solver_gmres.inl"
-#include "solver_adi.inl"
 #include "solver_dense.inl"
+#include "solver_adi.inl"
 }  // namespace ricadi
 #include "solver_newton.inl"
 #include "solver_capi.inl"

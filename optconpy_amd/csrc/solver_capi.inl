@@ -5,7 +5,8 @@
 //                                      C  A B I
 // =====================================================================================
 #define API_BEGIN try {
-#define API_END                                                   \
+// ... returning `status` where nothing was thrown
+#define API_END_STATUS(status)                                    \
   }                                                               \
   catch (const ricadi::HipError& e) {                             \
     ricadi::set_error(e.msg);                                     \
@@ -19,7 +20,8 @@
     ricadi::set_error("unknown C++ exception");                   \
     return RICADI_EHIP;                                           \
   }                                                               \
-  return RICADI_OK;
+  return (status);
+#define API_END API_END_STATUS(RICADI_OK)
 
 #define REQUIRE(cond, code, msg)     \
   do {                               \
@@ -48,6 +50,21 @@ static double timed_ms(hipStream_t st, int reps, Fn&& fn) {
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
   return (double)ms / reps;
+}
+
+// The first level from c downwards for which is(level) holds (NULL: none); lb, the batch of c on entry, becomes the
+// batch of that level with the same group table.
+template <class Pred>
+static ricadi_ctx* walk_levels(ricadi_ctx* c, Batch& lb, Pred&& is) {
+  const GroupTab tab = lb.tab;
+  ricadi_ctx* lc = c;
+  for (; lc && !is(lc); lc = lc->child.get()) {
+    if (!lc->child) continue;
+    Batch t = *lb.sub;
+    t.tab = tab;
+    lb = t;
+  }
+  return lc;
 }
 
 extern "C" {
@@ -543,6 +560,18 @@ int ricadi_precond_apply(ricadi_ctx* c, double alpha, double beta, const double*
   API_END
 }
 
+// The group ids of active[0 .. nactive) into ids, validated (active == NULL: all groups, ids stays empty)
+static int active_ids(const int32_t* active, int nactive, int ng, std::vector<int>& ids) {
+  if (!active) return RICADI_OK;
+  for (int i = 0; i < nactive; ++i) {
+    REQUIRE(active[i] >= 0 && active[i] < ng && std::find(ids.begin(), ids.end(), active[i]) == ids.end(),
+            RICADI_EINVAL, "active: distinct group ids in [0, ng) required");
+    ids.push_back(active[i]);
+  }
+  REQUIRE(!ids.empty(), RICADI_EINVAL, "no active group");
+  return RICADI_OK;
+}
+
 int ricadi_precond_apply_batch_dev(ricadi_ctx* c, int ng, const double* alphas, const double* betas,
                                    const double* dR, int64_t r_stride, int m, const int32_t* active, int nactive,
                                    double* dZ, int* form_out) {
@@ -552,14 +581,7 @@ int ricadi_precond_apply_batch_dev(ricadi_ctx* c, int ng, const double* alphas, 
           "1 <= ng <= 16 and ng*m <= 2048 required");
   REQUIRE(r_stride >= (int64_t)c->n * m, RICADI_EINVAL, "bad r_stride");
   std::vector<int> ids;
-  if (active) {
-    for (int i = 0; i < nactive; ++i) {
-      REQUIRE(active[i] >= 0 && active[i] < ng && std::find(ids.begin(), ids.end(), active[i]) == ids.end(),
-              RICADI_EINVAL, "active: distinct group ids in [0, ng) required");
-      ids.push_back(active[i]);
-    }
-    REQUIRE(!ids.empty(), RICADI_EINVAL, "no active group");
-  }
+  if (int rc = active_ids(active, nactive, ng, ids)) return rc;
   API_BEGIN
   hipStream_t st = c->st;
   std::vector<ShiftData*> sds(ng);
@@ -633,14 +655,7 @@ int ricadi_op_apply_batch_dev(ricadi_ctx* c, int ng, const double* alphas, const
           "FP32 input: only the plain product where the tiles fit");
   REQUIRE(!y32 || x32, RICADI_EINVAL, "FP32 output: with the FP32 input only");
   std::vector<int> ids;
-  if (active) {
-    for (int i = 0; i < nactive; ++i) {
-      REQUIRE(active[i] >= 0 && active[i] < ng && std::find(ids.begin(), ids.end(), active[i]) == ids.end(),
-              RICADI_EINVAL, "active: distinct group ids in [0, ng) required");
-      ids.push_back(active[i]);
-    }
-    REQUIRE(!ids.empty(), RICADI_EINVAL, "no active group");
-  }
+  if (int rc = active_ids(active, nactive, ng, ids)) return rc;
   API_BEGIN
   hipStream_t st = c->st;
   std::vector<ShiftData*> sds(ng);
@@ -767,32 +782,24 @@ int ricadi_precond_vanka(ricadi_ctx* c, int level, int32_t* sizes_out, int32_t* 
   API_END
 }
 
+static int solve_status(bool converged) {
+  if (!converged) ricadi::set_error("GMRES did not reach the tolerance");
+  return converged ? RICADI_OK : RICADI_ENOCONV;
+}
+
 int ricadi_shift_solve_dev(ricadi_ctx* c, double alpha, double beta, const double* dR, int m,
                            double* dX, int* iters_out, double* relres_out) {
   if (int rc = check_panel(c, m)) return rc;
   REQUIRE(dR && dX, RICADI_EINVAL, "NULL panel");
   int status = RICADI_OK;
-  try {
-    ShiftData* sd = get_shift(c, alpha, beta);
-    ensure_work(c, m);
-    load_rhs(c, dR, m, c->bvec.p);
-    GmresResult r = gmres_solve(c, sd, c->bvec.p, dX, m, true, relres_out);
-    if (iters_out) *iters_out = r.iters;
-    if (!r.converged) {
-      ricadi::set_error("GMRES did not reach the tolerance");
-      status = RICADI_ENOCONV;
-    }
-  } catch (const ricadi::HipError& e) {
-    ricadi::set_error(e.msg);
-    return RICADI_EHIP;
-  } catch (const std::exception& e) {
-    ricadi::set_error(e.what());
-    return RICADI_EHIP;
-  } catch (...) {
-    ricadi::set_error("unknown C++ exception");
-    return RICADI_EHIP;
-  }
-  return status;
+  API_BEGIN
+  ShiftData* sd = get_shift(c, alpha, beta);
+  ensure_work(c, m);
+  load_rhs(c, dR, m, c->bvec.p);
+  GmresResult r = gmres_solve(c, sd, c->bvec.p, dX, m, true, relres_out);
+  if (iters_out) *iters_out = r.iters;
+  status = solve_status(r.converged);
+  API_END_STATUS(status)
 }
 
 int ricadi_shift_solve_batch_dev(ricadi_ctx* c, int ng, const double* alphas, const double* betas,
@@ -804,34 +811,21 @@ int ricadi_shift_solve_batch_dev(ricadi_ctx* c, int ng, const double* alphas, co
           "1 <= ng <= 16 and ng*m <= 2048 required");
   REQUIRE(r_stride == 0 || r_stride >= (int64_t)c->nv * m, RICADI_EINVAL, "bad r_stride");
   int status = RICADI_OK;
-  try {
-    std::vector<ShiftData*> sds(ng);
-    get_shifts(c, alphas, betas, ng, sds.data());
-    ensure_work(c, m, ng);
-    const size_t nm = (size_t)c->n * m;
-    const int nload = r_stride == 0 ? 1 : ng;
-    for (int g = 0; g < nload; ++g) load_rhs(c, dR + (size_t)g * r_stride, m, c->bvec.p + (size_t)g * nm);
-    std::vector<GmresResult> res(ng);
-    solve_batch(c, sds.data(), ng, c->bvec.p, r_stride == 0 ? 0 : nm, dX, m, true, relres_out,
-                res.data());
-    for (int g = 0; g < ng; ++g) {
-      if (iters_out) iters_out[g] = res[g].iters;
-      if (!res[g].converged) {
-        ricadi::set_error("GMRES did not reach the tolerance");
-        status = RICADI_ENOCONV;
-      }
-    }
-  } catch (const ricadi::HipError& e) {
-    ricadi::set_error(e.msg);
-    return RICADI_EHIP;
-  } catch (const std::exception& e) {
-    ricadi::set_error(e.what());
-    return RICADI_EHIP;
-  } catch (...) {
-    ricadi::set_error("unknown C++ exception");
-    return RICADI_EHIP;
+  API_BEGIN
+  std::vector<ShiftData*> sds(ng);
+  get_shifts(c, alphas, betas, ng, sds.data());
+  ensure_work(c, m, ng);
+  const size_t nm = (size_t)c->n * m;
+  const int nload = r_stride == 0 ? 1 : ng;
+  for (int g = 0; g < nload; ++g) load_rhs(c, dR + (size_t)g * r_stride, m, c->bvec.p + (size_t)g * nm);
+  std::vector<GmresResult> res(ng);
+  solve_batch(c, sds.data(), ng, c->bvec.p, r_stride == 0 ? 0 : nm, dX, m, true, relres_out,
+              res.data());
+  for (int g = 0; g < ng; ++g) {
+    if (iters_out) iters_out[g] = res[g].iters;
+    if (!res[g].converged) status = solve_status(false);
   }
-  return status;
+  API_END_STATUS(status)
 }
 
 int ricadi_shift_solve(ricadi_ctx* c, double alpha, double beta, const double* R, const double* Rp,
@@ -839,36 +833,23 @@ int ricadi_shift_solve(ricadi_ctx* c, double alpha, double beta, const double* R
   if (int rc = check_panel(c, m)) return rc;
   REQUIRE(R && X_out, RICADI_EINVAL, "NULL panel");
   int status = RICADI_OK;
-  try {
-    const size_t nm = (size_t)c->n * m, nvm = (size_t)c->nv * m;
-    ShiftData* sd = get_shift(c, alpha, beta);
-    ensure_work(c, m);
-    HIPCHK(hipMemcpyAsync(c->bvec.p, R, nvm * sizeof(double), hipMemcpyHostToDevice, c->st));
-    if (c->np > 0) {
-      if (Rp)
-        HIPCHK(hipMemcpyAsync(c->bvec.p + nvm, Rp, (nm - nvm) * sizeof(double), hipMemcpyHostToDevice, c->st));
-      else
-        HIPCHK(hipMemsetAsync(c->bvec.p + nvm, 0, (nm - nvm) * sizeof(double), c->st));
-    }
-    GmresResult r = gmres_solve(c, sd, c->bvec.p, c->xs.p, m, true, relres_out);
-    HIPCHK(hipMemcpyAsync(X_out, c->xs.p, nm * sizeof(double), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    if (iters_out) *iters_out = r.iters;
-    if (!r.converged) {
-      ricadi::set_error("GMRES did not reach the tolerance");
-      status = RICADI_ENOCONV;
-    }
-  } catch (const ricadi::HipError& e) {
-    ricadi::set_error(e.msg);
-    return RICADI_EHIP;
-  } catch (const std::exception& e) {
-    ricadi::set_error(e.what());
-    return RICADI_EHIP;
-  } catch (...) {
-    ricadi::set_error("unknown C++ exception");
-    return RICADI_EHIP;
+  API_BEGIN
+  const size_t nm = (size_t)c->n * m, nvm = (size_t)c->nv * m;
+  ShiftData* sd = get_shift(c, alpha, beta);
+  ensure_work(c, m);
+  HIPCHK(hipMemcpyAsync(c->bvec.p, R, nvm * sizeof(double), hipMemcpyHostToDevice, c->st));
+  if (c->np > 0) {
+    if (Rp)
+      HIPCHK(hipMemcpyAsync(c->bvec.p + nvm, Rp, (nm - nvm) * sizeof(double), hipMemcpyHostToDevice, c->st));
+    else
+      HIPCHK(hipMemsetAsync(c->bvec.p + nvm, 0, (nm - nvm) * sizeof(double), c->st));
   }
-  return status;
+  GmresResult r = gmres_solve(c, sd, c->bvec.p, c->xs.p, m, true, relres_out);
+  HIPCHK(hipMemcpyAsync(X_out, c->xs.p, nm * sizeof(double), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  if (iters_out) *iters_out = r.iters;
+  status = solve_status(r.converged);
+  API_END_STATUS(status)
 }
 
 int ricadi_apply_e_dev(ricadi_ctx* c, double coef, const double* dV, int m, double* dW) {
@@ -970,7 +951,7 @@ int ricadi_panel_norms_dev(ricadi_ctx* c, const double* dW, int nrows, int m, do
   if (int rc = check_panel(c, m)) return rc;
   REQUIRE(dW && nrows > 0, RICADI_EINVAL, "bad panel");
   API_BEGIN
-  DScalar::gram_norms(c, dW, nrows, m, gram_fro, nrm2);
+  gram_norms(c, dW, nrows, m, gram_fro, nrm2);
   API_END
 }
 
@@ -1085,14 +1066,8 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
         if (c->kc <= 0) throw HipError{"no coarse level"};
         {
           // the dense inverse lives on the last level
-          ricadi_ctx* lc = c;
           Batch lb = bt;
-          while (lc->child) {
-            Batch t = *lb.sub;
-            t.tab = bt.tab;
-            lb = t;
-            lc = lc->child.get();
-          }
+          ricadi_ctx* lc = walk_levels(c, lb, [](const ricadi_ctx* l) { return !l->child; });
           pc_coarse(lc, lb, cycle_form(lc, m, lb.blocks16, 0, false, false), CycleIO());
         }
         break;
@@ -1128,15 +1103,9 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
         break;
       case RICADI_TK_PC_VANKA: {
         // the Vanka sweep lives on a child level: all its colours on that level's panels, as pc_vanka issues them
-        ricadi_ctx* lc = c;
         Batch lb = bt;
-        while (lc && !lc->vanka) {
-          if (!lc->child) throw HipError{"no coarse level with a Vanka sweep"};
-          Batch t = *lb.sub;
-          t.tab = bt.tab;
-          lb = t;
-          lc = lc->child.get();
-        }
+        ricadi_ctx* lc = walk_levels(c, lb, [](const ricadi_ctx* l) { return l->vanka; });
+        if (!lc) throw HipError{"no coarse level with a Vanka sweep"};
         vanka_colours(lc, lb, CycleIO{lc->wv.p, lb.gs, nullptr, lc->zv.p});
         break;
       }
@@ -1150,31 +1119,22 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
     // reps hot iterations j = nvec - 1 (no convergence logic): all groups on the context stream, or the even and the
     // odd group ids as two halves on two streams, forked from it and joined back to it once around all reps
     const bool two = which == RICADI_TK_ITER_SPLIT && ng >= 2;
-    Batch bh[2] = {bt, bt};
+    HalfSchedule halves(c, bt, two);
     if (two) {
-      bh[1].st = half_stream(c);
-      std::vector<int> half[2];
-      for (int g = 0; g < ng; ++g) half[g & 1].push_back(g);
-      for (int h = 0; h < 2; ++h) {
-        bh[h].set(half[h]);
-        bh[h].ng_solve = ng;
+      std::vector<int> all;
+      for (int g = 0; g < ng; ++g) {
+        halves.half[g & 1].push_back(g);
+        all.push_back(g);
       }
+      halves.set_live(all);
     }
     auto iters = [&](int k) {
-      if (two) {
-        HIPCHK(hipEventRecord(c->ev_fork, st));
-        HIPCHK(hipStreamWaitEvent(bh[1].st, c->ev_fork, 0));
-      }
+      if (two) halves.fork();
       for (int i = 0; i < k; ++i) {
-        if (two)
-          for (int h = 0; h < 2; ++h) iteration_launches(c, f, pf, bh[h], nvec - 1, false, nullptr);
-        else
-          iteration_launches(c, f, pf, bt, nvec - 1, false, nullptr);
+        if (two) halves.issue(f, pf, nvec - 1, false, nullptr);
+        else iteration_launches(c, f, pf, bt, nvec - 1, false, nullptr);
       }
-      if (two) {
-        HIPCHK(hipEventRecord(c->ev_join, bh[1].st));
-        HIPCHK(hipStreamWaitEvent(st, c->ev_join, 0));
-      }
+      halves.join();
     };
     iters(1);   // warm-up
     *ms_per_launch = timed_ms(st, 1, [&] { iters(reps); }) / reps;

@@ -1,4 +1,4 @@
-// solver_dense.inl -- compression, recompression by pivoted Cholesky, block QR / TSQR, gain.
+// solver_dense.inl -- main / auxiliary Exec, compression, recompression by pivoted Cholesky, block QR / TSQR, gain.
 // Part of ricadi_solver.hip (one translation unit; included there in order).
 
 // ---- compression: Gram matrix on the matrix cores, eigendecomposition, Z * V_k -----
@@ -11,6 +11,25 @@ static Exec main_exec(ricadi_ctx* c) {
   ex.pool = &c->pool;
   ex.info = c->info.p;
   ex.flag = c->flag.p;
+  return ex;
+}
+
+// Auxiliary stream + handle for work that runs beside the main stream (created on first use).
+static Exec aux_exec(ricadi_ctx* c) {
+  if (!c->st2) {
+    HIPCHK(hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking));
+    RBCHK(rocblas_create_handle(&c->rb2));
+    RBCHK(rocblas_set_stream(c->rb2, c->st2));
+    c->info2.alloc(4);
+    c->flag2.alloc(4);
+    HIPCHK(hipEventCreateWithFlags(&c->ev_z, hipEventDisableTiming));
+  }
+  Exec ex;
+  ex.st = c->st2;
+  ex.rb = c->rb2;
+  ex.pool = &c->pool2;
+  ex.info = c->info2.p;
+  ex.flag = c->flag2.p;
   return ex;
 }
 
@@ -128,44 +147,83 @@ static int recompress_exec(ricadi_ctx* c, const Exec& ex, const double* dZ, int 
   return compress_gram_exec(c, ex, dZ, cz, ldz, rel, 0, true, dOut, nullptr);
 }
 
-static int compress_dev(ricadi_ctx* c, const double* dZ, int cz, int ldz, double thresh, int kmax,
-                        bool thresh_relative, double* dOut, std::vector<double>* sv_host,
-                        bool use_qr) {
-  hipStream_t st = c->st;
-  if (cz == 0) return 0;
-  if (use_qr && cz <= c->nv) {
-    // Z = Q R (TSQR panels), R^T = U' S V'^T (rocSOLVER, column-major view of the
-    // row-major R), right singular vectors of R = U'; Zc = Z V_k.
-    TArr<double> Q(c->pool, (size_t)c->nv * cz), R(c->pool, (size_t)cz * cz), S(c->pool, cz),
-        U(c->pool, (size_t)cz * cz), E5(c->pool, cz);
-    block_qr_dev(c, dZ, ldz, c->nv, cz, Q.p, R.p);
-    RBCHK(rocsolver_dgesvd(c->rb, rocblas_svect_all, rocblas_svect_none, cz, cz, R.p, cz, S.p, U.p, cz,
-                           nullptr, 1, E5.p, rocblas_outofplace, c->info.p));
-    std::vector<double> sv(cz), Uh((size_t)cz * cz);
-    HIPCHK(hipMemcpyAsync(sv.data(), S.p, sizeof(double) * cz, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(Uh.data(), U.p, sizeof(double) * cz * cz, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int k = std::min(cz, c->nv);
-    if (thresh >= 0.0) {
-      const double t = thresh_relative ? thresh * sv[0] : thresh;
-      int cnt = 0;
-      while (cnt < cz && sv[cnt] > t) ++cnt;
-      k = std::min(k, cnt);
-    }
-    if (kmax > 0) k = std::min(k, kmax);
-    if (sv_host) *sv_host = sv;
-    if (k == 0) return 0;
-    // row jj of the row-major view of U' = right singular vector jj of R
-    std::vector<double> Ch((size_t)cz * k);
-    for (int jj = 0; jj < k; ++jj)
-      for (int i = 0; i < cz; ++i) Ch[(size_t)i * k + jj] = Uh[(size_t)jj * cz + i];
-    TArr<double> sel(c->pool, (size_t)cz * k);
-    HIPCHK(hipMemcpyAsync(sel.p, Ch.data(), sizeof(double) * cz * k, hipMemcpyHostToDevice, st));
-    launch_gemm_nn(st, c->nv, cz, k, dZ, ldz, sel.p, k, dOut, k, 1.0, 0.0);
-    HIPCHK(hipStreamSynchronize(st));
-    return k;
+// Truncation level of the internal recompressions: the Gram-matrix route
+// resolves singular values down to sqrt(eps)*sigma_1; dropping what lies below
+// changes Z Z^T by at most eps*||Z Z^T|| -- rounding level.
+static const double kInternalRelThresh = 3e-8;
+
+// Recompress the device factor in place (columns [0, zc) of c->Z).
+static void factor_recompress(ricadi_ctx* c) {
+  if (c->zc == 0) return;
+  TArr<double> tmp(c->pool, (size_t)c->nv * c->zc);
+  const int k = recompress_exec(c, main_exec(c), c->Z.p, c->zc, c->zld, kInternalRelThresh, tmp.p);
+  if (k > 0) launch_copy_cols(c->st, c->nv, k, tmp.p, k, 0, c->Z.p, c->zld, 0, 1.0);
+  HIPCHK(hipStreamSynchronize(c->st));
+  c->zc = k;
+}
+
+// In-ADI recompression that does not stall the sweeps: the columns [0, snap) of the factor are
+// compressed on the auxiliary stream by a helper thread (same arithmetic as
+// factor_recompress) while the main stream goes on appending columns behind them; finish()
+// splices the result in:  Z <- [compressed prefix | columns appended meanwhile].
+// Member order matters: `fut` is destroyed first and waits for the helper, then `out`.
+struct AsyncRecompress {
+  ricadi_ctx* c;
+  TArr<double> out;
+  int snap = 0;
+  bool active = false;
+  std::future<int> fut;
+  explicit AsyncRecompress(ricadi_ctx* ctx) : c(ctx), out(ctx->pool) {}
+  void start() {
+    if (active || c->zc == 0) return;
+    const Exec ex = aux_exec(c);
+    snap = c->zc;
+    out.alloc((size_t)c->nv * snap);
+    HIPCHK(hipEventRecord(c->ev_z, c->st));            // the prefix is complete on the main stream
+    HIPCHK(hipStreamWaitEvent(c->st2, c->ev_z, 0));
+    ricadi_ctx* cc = c;
+    const double* Zp = c->Z.p;
+    const int ld = c->zld, sn = snap, dev = c->dev;
+    double* op = out.p;
+    fut = std::async(std::launch::async, [cc, ex, Zp, ld, sn, dev, op]() {
+      (void)hipSetDevice(dev);
+      return recompress_exec(cc, ex, Zp, sn, ld, kInternalRelThresh, op);
+    });
+    active = true;
   }
-  return compress_gram_exec(c, main_exec(c), dZ, cz, ldz, thresh, kmax, thresh_relative, dOut, sv_host);
+  void finish() {
+    if (!active) return;
+    active = false;
+    const int k = fut.get();                            // the auxiliary stream is drained in there
+    hipStream_t st = c->st;
+    const int nv = c->nv, tail = c->zc - snap;
+    if (tail > 0) {
+      TArr<double> tmp(c->pool, (size_t)nv * tail);
+      launch_copy_cols(st, nv, tail, c->Z.p, c->zld, snap, tmp.p, tail, 0, 1.0);
+      launch_copy_cols(st, nv, tail, tmp.p, tail, 0, c->Z.p, c->zld, k, 1.0);
+    }
+    if (k > 0) launch_copy_cols(st, nv, k, out.p, k, 0, c->Z.p, c->zld, 0, 1.0);
+    c->zc = k + tail;
+    out.release();
+  }
+};
+
+// Frobenius norm of W^T W and ||W||_F^2 of a device panel
+static void gram_norms(ricadi_ctx* c, const double* dW, int nrows, int m, double* gram_fro, double* nrm2) {
+  DArr<double>& G = c->scratch;
+  G.ensure((size_t)m * m + 64);
+  HIPCHK(hipMemsetAsync(G.p, 0, sizeof(double) * m * m, c->st));
+  launch_gemm_tn(c->st, nrows, m, m, dW, m, dW, m, G.p, m);
+  std::vector<double> h((size_t)m * m);
+  HIPCHK(hipMemcpyAsync(h.data(), G.p, sizeof(double) * m * m, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  double f = 0.0, t = 0.0;
+  for (int i = 0; i < m; ++i) {
+    t += h[(size_t)i * m + i];
+    for (int j = 0; j < m; ++j) f += h[(size_t)i * m + j] * h[(size_t)i * m + j];
+  }
+  if (gram_fro) *gram_fro = std::sqrt(f);
+  if (nrm2) *nrm2 = t;
 }
 
 // ---- K5: Householder TSQR tree and block QR ----------------------------------------
@@ -263,7 +321,7 @@ static void panel_cholqr2_wide(ricadi_ctx* c, const double* P, int ldp, int n, i
 // ADI blocks; RICADI_TSQR_HOUSEHOLDER=1 forces it).  Q: n x kk (ld kk), R: kk x kk
 // row-major upper triangular.  No panel straddles column `split` (the update norm factorises [Z_new, Z_old]).
 static void block_qr_dev(ricadi_ctx* c, const double* D, int ldd, int n, int kk, double* Q,
-                         double* R, int split) {
+                         double* R, int split = 0) {
   hipStream_t st = c->st;
   const int PWF = 128;                              // panel width of the fast path
   TArr<double> P(c->pool, (size_t)n * PWF), C1(c->pool, (size_t)kk * PWF), C2(c->pool, (size_t)kk * PWF);
@@ -309,6 +367,46 @@ static void block_qr_dev(ricadi_ctx* c, const double* D, int ldd, int n, int kk,
     if (!flag) break;
     if (c->opts.verbose) fprintf(stderr, "[ricadi] block QR: ill-conditioned panel, Householder TSQR instead\n");
   }
+}
+
+static int compress_dev(ricadi_ctx* c, const double* dZ, int cz, int ldz, double thresh, int kmax,
+                        bool thresh_relative, double* dOut, std::vector<double>* sv_host,
+                        bool use_qr = false) {
+  hipStream_t st = c->st;
+  if (cz == 0) return 0;
+  if (use_qr && cz <= c->nv) {
+    // Z = Q R (TSQR panels), R^T = U' S V'^T (rocSOLVER, column-major view of the
+    // row-major R), right singular vectors of R = U'; Zc = Z V_k.
+    TArr<double> Q(c->pool, (size_t)c->nv * cz), R(c->pool, (size_t)cz * cz), S(c->pool, cz),
+        U(c->pool, (size_t)cz * cz), E5(c->pool, cz);
+    block_qr_dev(c, dZ, ldz, c->nv, cz, Q.p, R.p);
+    RBCHK(rocsolver_dgesvd(c->rb, rocblas_svect_all, rocblas_svect_none, cz, cz, R.p, cz, S.p, U.p, cz,
+                           nullptr, 1, E5.p, rocblas_outofplace, c->info.p));
+    std::vector<double> sv(cz), Uh((size_t)cz * cz);
+    HIPCHK(hipMemcpyAsync(sv.data(), S.p, sizeof(double) * cz, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(Uh.data(), U.p, sizeof(double) * cz * cz, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int k = std::min(cz, c->nv);
+    if (thresh >= 0.0) {
+      const double t = thresh_relative ? thresh * sv[0] : thresh;
+      int cnt = 0;
+      while (cnt < cz && sv[cnt] > t) ++cnt;
+      k = std::min(k, cnt);
+    }
+    if (kmax > 0) k = std::min(k, kmax);
+    if (sv_host) *sv_host = sv;
+    if (k == 0) return 0;
+    // row jj of the row-major view of U' = right singular vector jj of R
+    std::vector<double> Ch((size_t)cz * k);
+    for (int jj = 0; jj < k; ++jj)
+      for (int i = 0; i < cz; ++i) Ch[(size_t)i * k + jj] = Uh[(size_t)jj * cz + i];
+    TArr<double> sel(c->pool, (size_t)cz * k);
+    HIPCHK(hipMemcpyAsync(sel.p, Ch.data(), sizeof(double) * cz * k, hipMemcpyHostToDevice, st));
+    launch_gemm_nn(st, c->nv, cz, k, dZ, ldz, sel.p, k, dOut, k, 1.0, 0.0);
+    HIPCHK(hipStreamSynchronize(st));
+    return k;
+  }
+  return compress_gram_exec(c, main_exec(c), dZ, cz, ldz, thresh, kmax, thresh_relative, dOut, sv_host);
 }
 
 // || Z1 Z1^T - Z0 Z0^T ||_F  via an LQ factorisation of [Z1, Z0]^T (Householder,

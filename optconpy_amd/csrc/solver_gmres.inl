@@ -70,6 +70,11 @@ struct ArnoldiStrides {
         gspart((size_t)dots_num_blocks(c->n) * (c->opts.gmres_restart + 2) * bt.m),
         h2buf((size_t)(c->opts.gmres_restart + 2) * c->wcols) {}
 };
+// column norms squared of a panel (group stride gsw) for the groups of bt.tab: out[g * m + j]
+static void panel_norms2(ricadi_ctx* c, const Batch& bt, const double* w, size_t gsw, double* out) {
+  launch_cols_dots_b(bt.st, bt.tab, c->n, bt.m, 0, (const double*)nullptr, 0, 0, w, gsw, 1, c->partial.p,
+                     ArnoldiStrides(c, bt).gspart, out, (size_t)bt.m);
+}
 // first pass: h1 = V^T w
 static void arnoldi_dots(ricadi_ctx* c, const IterationForm& f, const Batch& bt, int nvec) {
   const ArnoldiStrides s(c, bt);
@@ -218,52 +223,135 @@ static void split_groups(ShiftData* const* sds, const std::vector<int>& act, std
   std::sort(half[0].begin(), half[0].end());
   std::sort(half[1].begin(), half[1].end());
 }
+namespace {   // (file-local types: no symbols of theirs leave the library)
+// The schedule of the two halves (gmres_core and the split-iteration timer): half h on bh[h].st -- half 0 on the
+// context's stream -- with the lag event pair lag_events(h).  The caller fills half[] (split_groups, or lists of its
+// own), forks, sets the tables for the groups that are live, issues iterations and joins; between a join and the next
+// fork everything runs on the context's stream.  With enabled == false (split_halves said no) nothing of the second
+// stream is created or touched.
+struct HalfSchedule {
+  ricadi_ctx* c;
+  const bool enabled;
+  std::vector<int> half[2];    // group ids of the halves
+  Batch bh[2];                 // the solve's batch on the stream of half h, table: the live groups of the half
+  bool forked = false;
 
-// have_x0: x holds an initial guess (else it is zeroed);  only: the groups to iterate on (NULL = all; the
-// panels of the other groups are not touched);  allow_stall: a group whose full-length restart cycles no
-// longer gain is given up early (the caller repeats it with wider storage).
-static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double* b, size_t gsb, double* x,
-                       int m, bool lowrank, GmresResult* res, bool have_x0, const std::vector<int>* only,
-                       bool allow_stall) {
-  ensure_work(c, m, G, 0);
-  hipStream_t st = c->st;
-  const int n = c->n, restart = c->opts.gmres_restart, maxit = c->opts.gmres_maxit;
-  const double tol = c->opts.gmres_tol;
-  Batch bt = make_batch(c, sds, G, m);
-  const size_t nm = bt.gs;             // one panel
-  const size_t vs = nm * G;            // one Krylov vector of all groups
-  const size_t gspart = (size_t)dots_num_blocks(n) * (restart + 2) * m;
-  const int GM = G * m;
-  const IterationForm f = iteration_form(c, m, G, lowrank);
-  const CycleForm pf = cycle_form(c, m, bt.blocks16, nm, f.x32, f.h16);
-  c->w32_last = f.w32 ? 1 : 0;
-  double* hb = c->h_resid;
+  HalfSchedule(ricadi_ctx* ctx, const Batch& bt, bool enable) : c(ctx), enabled(enable), bh{bt, bt} {
+    if (enabled) bh[1].st = half_stream(c);
+  }
+  hipEvent_t* lag_events(int h) const { return h == 1 && enabled ? c->ev_res_half : c->ev_res; }
+  // two halves for this many groups?
+  bool pays(size_t ngroups) const { return enabled && ngroups >= (size_t)kSplitMinGroups; }
+  // the second stream starts behind what the context's stream has been given so far
+  void fork() {
+    HIPCHK(hipEventRecord(c->ev_fork, bh[0].st));
+    HIPCHK(hipStreamWaitEvent(bh[1].st, c->ev_fork, 0));
+    forked = true;
+  }
+  // tables of the halves: their groups that are in `live`; the multi-shift kernels' choice follows the groups of
+  // the whole solve
+  void set_live(const std::vector<int>& live) {
+    for (int h = 0; h < 2; ++h) {
+      std::vector<int> lh;
+      for (int g : half[h])
+        if (std::find(live.begin(), live.end(), g) != live.end()) lh.push_back(g);
+      bh[h].set(lh);
+      bh[h].ng_solve = (int)live.size();
+    }
+  }
+  // iteration j on both halves; lag >= 0: that event of each half's pair is recorded behind the half's launches
+  void issue(const IterationForm& f, const CycleForm& pf, int j, bool lowrank, double* host_resid, int lag = -1) {
+    for (int h = 0; h < 2; ++h) {
+      if (bh[h].tab.ng > 0) iteration_launches(c, f, pf, bh[h], j, lowrank, host_resid);
+      if (lag >= 0) HIPCHK(hipEventRecord(lag_events(h)[lag], bh[h].st));
+    }
+  }
+  // the context's stream goes on behind what the second stream has been given (no-op unless forked)
+  void join() {
+    if (!forked) return;
+    HIPCHK(hipEventRecord(c->ev_join, bh[1].st));
+    HIPCHK(hipStreamWaitEvent(bh[0].st, c->ev_join, 0));
+    forked = false;
+  }
+};
+
+// The lockstep solve as restart cycles (gmres_core drives the phases):  begin_cycle -- true residual of the iterates,
+// who converged / hit maxit / stalled, the next cycle's length, first Krylov vector of the groups that go on;
+// iterate_cycle -- up to cyc lockstep iterations, the host looking at the residual estimates one iteration late;
+// end_cycle -- x += Z y.
+struct LockstepSolve {
+  ricadi_ctx* const c;
+  ShiftData* const* const sds;
+  const int G, m;
+  const double* const b;
+  const size_t gsb;
+  double* const x;
+  const bool lowrank, allow_stall;
+  GmresResult* const res;
+  const std::vector<int>* const only;
+  const hipStream_t st;
+  const int restart, maxit;
+  const double tol;
+  Batch bt;
+  const size_t nm, vs;           // one panel; one Krylov vector of all groups
+  const int GM;
+  const IterationForm f;
+  const CycleForm pf;
+  HalfSchedule halves;
+  // pinned host slots: [0] true residuals, [1] right-hand side norms, [2], [3] the iterations' residual estimates
+  double* const hb;
   const size_t slot = (size_t)RICADI_MAX_M * RICADI_MAX_GROUPS;
-  for (int g = 0; g < G; ++g) res[g] = GmresResult();
-  // the iterations of a cycle as two half-batches: half h on stream hs[h] (half 0 on the context's stream), its lag
-  // event pair evh[h]
-  const bool split = split_halves(c, G, lowrank);
-  const hipStream_t hs[2] = {st, split ? half_stream(c) : st};
-  hipEvent_t* const evh[2] = {c->ev_res, split ? c->ev_res_half : c->ev_res};
-  Batch bh[2] = {bt, bt};
-  bh[1].st = hs[1];
-  std::vector<int> half[2];
+  std::vector<double> bn;        // ||b|| per column
+  std::vector<double> rstart;    // residual per column at the start of the previous cycle
+  std::vector<int> act;          // groups of the current cycle
+  std::vector<int> live;         // ... of them, still iterating
+  GroupInts kk;                  // Krylov vectors group g built in the current cycle (by value to the cycle's close)
+  std::vector<int> nstall;       // full-length cycles in a row that gained < 30 % on some column of group g
+  bool first;                    // the iterates are zero: the first residual is b
+  // Cycle length: short cycles keep the Krylov basis (the dominant HBM traffic of an
+  // iteration: three passes over it) small; a cycle that gains less than a factor 10
+  // on some column lengthens the following ones, up to gmres_restart.
+  int cyc;
+  Tick tick;
 
-  auto norms2 = [&](const double* w, size_t gsw, double* out) {
-    launch_cols_dots_b(st, bt.tab, n, m, 0, (const double*)nullptr, 0, 0, w, gsw, 1, c->partial.p, gspart, out,
-                       (size_t)m);
-  };
-  bt.all();
-  norms2(b, gsb, c->bnorm2.p);
-  HIPCHK(hipMemcpyAsync(hb + slot, c->bnorm2.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  std::vector<double> bn(GM);
-  for (int j = 0; j < GM; ++j) bn[j] = std::sqrt(std::max(hb[slot + j], 0.0));
-  // device copy of the norms (not squared) for the hess kernel
-  HIPCHK(hipMemcpyAsync(c->bnorm2.p, bn.data(), sizeof(double) * GM, hipMemcpyHostToDevice, st));
-  if (!have_x0) HIPCHK(hipMemsetAsync(x, 0, sizeof(double) * vs, st));
+  // (after ensure_work, which decides the storage of the basis)
+  LockstepSolve(ricadi_ctx* ctx, ShiftData* const* sds_, int G_, const double* b_, size_t gsb_, double* x_, int m_,
+                bool lowrank_, GmresResult* res_, bool have_x0, const std::vector<int>* only_, bool allow_stall_)
+      : c(ctx), sds(sds_), G(G_), m(m_), b(b_), gsb(gsb_), x(x_), lowrank(lowrank_), allow_stall(allow_stall_),
+        res(res_), only(only_), st(ctx->st), restart(ctx->opts.gmres_restart), maxit(ctx->opts.gmres_maxit),
+        tol(ctx->opts.gmres_tol), bt(make_batch(ctx, sds_, G_, m_)), nm(bt.gs), vs(nm * G_), GM(G_ * m_),
+        f(iteration_form(ctx, m_, G_, lowrank_)), pf(cycle_form(ctx, m_, bt.blocks16, nm, f.x32, f.h16)),
+        halves(ctx, bt, split_halves(ctx, G_, lowrank_)), hb(ctx->h_resid), bn(GM), rstart(GM, 0.0), nstall(G_, 0), first(!have_x0), cyc(std::min(restart, 10)) {
+    c->w32_last = f.w32 ? 1 : 0;
+    for (int g = 0; g < G; ++g) res[g] = GmresResult();
+    if (only) act = *only;
+    else
+      for (int g = 0; g < G; ++g) act.push_back(g);
+  }
 
-  auto group_converged = [&](const double* r, int g) {
+  void lap(double& acc) {
+    if (c->sw.timing) {
+      (void)hipStreamSynchronize(st);
+      if (halves.enabled) (void)hipStreamSynchronize(halves.bh[1].st);
+      acc += tick.lap();
+    }
+  }
+
+  // norms of the right-hand sides: host (bn) and device (bnorm2, not squared, for the Hessenberg kernels); x = 0
+  // without an initial guess
+  void rhs_norms() {
+    bt.all();
+    panel_norms2(c, bt, b, gsb, c->bnorm2.p);
+    HIPCHK(hipMemcpyAsync(hb + slot, c->bnorm2.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int j = 0; j < GM; ++j) bn[j] = std::sqrt(std::max(hb[slot + j], 0.0));
+    HIPCHK(hipMemcpyAsync(c->bnorm2.p, bn.data(), sizeof(double) * GM, hipMemcpyHostToDevice, st));
+    if (first) HIPCHK(hipMemsetAsync(x, 0, sizeof(double) * vs, st));
+    tick = Tick();
+  }
+
+  // all columns of group g at the tolerance in the residuals r?  (records the group's worst relative residual)
+  bool group_converged(const double* r, int g) {
     double worst = 0.0;
     bool ok = true;
     for (int j = g * m; j < (g + 1) * m; ++j) {
@@ -273,31 +361,36 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
     }
     res[g].max_relres = worst;
     return ok;
-  };
+  }
 
-  std::vector<char> done(G, 0);
-  std::vector<int> act, live, kk(G, 0), nstall(G, 0);
-  if (only) act = *only;
-  else
-    for (int g = 0; g < G; ++g) act.push_back(g);
-  bool first = !have_x0;
-  // Cycle length: short cycles keep the Krylov basis (the dominant HBM traffic of an
-  // iteration: three passes over it) small; a cycle that gains less than a factor 10
-  // on some column lengthens the following ones, up to gmres_restart.
-  int cyc = std::min(restart, 10);
-  std::vector<double> rstart(GM, 0.0);
-  Tick tkc;
-  auto lapc = [&](double& acc) {
-    if (c->sw.timing) {
-      (void)hipStreamSynchronize(st);
-      if (split) (void)hipStreamSynchronize(hs[1]);
-      acc += tkc.lap();
+  // The decision at a cycle start, from the true residuals r of the groups of act (host): a group is done when it
+  // has converged, has used maxit iterations, or -- allow_stall -- three full-length cycles in a row gained less
+  // than 30 % on one of its columns.  Returns the groups that go on; a column that gained less than a factor 10
+  // lengthens the cycles from here on.  Launches nothing.
+  std::vector<int> next_active(const double* r) {
+    std::vector<int> next;
+    bool slow = false;
+    for (int g : act) {
+      if (group_converged(r, g)) {
+        res[g].converged = true;
+      } else if (res[g].iters < maxit) {
+        bool flat = false;
+        for (int j = g * m; j < (g + 1) * m; ++j) {
+          if (rstart[j] > 0.0 && r[j] > tol * bn[j] && r[j] > 0.1 * rstart[j]) slow = true;
+          if (rstart[j] > 0.0 && r[j] > tol * bn[j] && r[j] > 0.7 * rstart[j]) flat = true;
+          rstart[j] = r[j];
+        }
+        nstall[g] = (flat && cyc >= restart) ? nstall[g] + 1 : 0;
+        if (allow_stall && nstall[g] >= 3) res[g].stalled = true;
+        else next.push_back(g);
+      }
     }
-  };
-  while (!act.empty()) {
-    lapc(c->t_iter);
-    bt.set(act);
-    // residual of the current iterates
+    if (slow) cyc = std::min(restart, cyc + (cyc + 1) / 2);
+    return next;
+  }
+
+  // r = b - S x of the groups of bt.tab into wv (the first time without an initial guess: r = b, all groups)
+  void residual() {
     if (first) {
       if (gsb == nm) {
         HIPCHK(hipMemcpyAsync(c->wv.p, b, sizeof(double) * vs, hipMemcpyDeviceToDevice, st));
@@ -314,99 +407,66 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
       saddle_spmm(c, bt, x, nm, nullptr, c->wv.p, nm, b, gsb, -1.0, 1.0);
     }
     first = false;
-    norms2(c->wv.p, nm, c->nrm2.p);
+  }
+
+  // false: no group goes on
+  bool begin_cycle() {
+    if (act.empty()) return false;
+    lap(c->t_iter);
+    bt.set(act);
+    residual();
+    panel_norms2(c, bt, c->wv.p, nm, c->nrm2.p);
     launch_gmres_start_b(st, bt.tab, m, restart, c->nrm2.p, c->g.p, c->scale.p, c->resid.p);
     HIPCHK(hipMemcpyAsync(hb, c->resid.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    std::vector<int> next;
-    bool slow = false;
-    for (int g : act) {
-      if (group_converged(hb, g)) {
-        res[g].converged = true;
-        done[g] = 1;
-      } else if (res[g].iters >= maxit) {
-        done[g] = 1;
-      } else {
-        bool flat = false;
-        for (int j = g * m; j < (g + 1) * m; ++j) {
-          if (rstart[j] > 0.0 && hb[j] > tol * bn[j] && hb[j] > 0.1 * rstart[j]) slow = true;
-          if (rstart[j] > 0.0 && hb[j] > tol * bn[j] && hb[j] > 0.7 * rstart[j]) flat = true;
-          rstart[j] = hb[j];
-        }
-        nstall[g] = (flat && cyc >= restart) ? nstall[g] + 1 : 0;
-        if (allow_stall && nstall[g] >= 3) {
-          res[g].stalled = true;
-          done[g] = 1;
-        } else {
-          next.push_back(g);
-        }
-      }
-    }
-    if (slow) cyc = std::min(restart, cyc + (cyc + 1) / 2);
-    // Few groups left (the stragglers of the sweep): the launches are latency bound then and
-    // the traffic of a longer Krylov basis costs nothing -- let the cycles run to the full
-    // restart length instead of throwing the subspace away every `cyc` vectors.
-    act.swap(next);
-    if (act.empty()) break;
+    act = next_active(hb);
+    if (act.empty()) return false;
+    // first Krylov vector: the scaled residual
     bt.set(act);
     with_basis(c, f, [&](auto* V) {
       if constexpr (std::is_same<std::remove_pointer_t<decltype(V)>, double>::value)
-        launch_colscale_b(st, bt.tab, n, m, c->scale.p, c->wv.p, nm, 0.0, V, nm);
+        launch_colscale_b(st, bt.tab, c->n, m, c->scale.p, c->wv.p, nm, 0.0, V, nm);
       else
-        launch_colscale_b(st, bt.tab, n, m, c->scale.p, c->wv.p, nm, 0.0, c->vcur.p, nm, V, nm);
+        launch_colscale_b(st, bt.tab, c->n, m, c->scale.p, c->wv.p, nm, 0.0, c->vcur.p, nm, V, nm);
     });
     live = act;
-    for (int g : act) kk[g] = 0;
+    kk = same_int(0);
+    return true;
+  }
+
+  void iterate_cycle() {
     // one cycle schedule for both halves; the second stream starts behind what the first has issued so far, and is
     // joined back as soon as too few groups are left for two halves
-    bool two = split && act.size() >= (size_t)kSplitMinGroups;
-    bool joined = !two;
-    auto join = [&]() {
-      if (joined) return;
-      HIPCHK(hipEventRecord(c->ev_join, hs[1]));
-      HIPCHK(hipStreamWaitEvent(st, c->ev_join, 0));
-      joined = true;
-    };
+    const bool two = halves.pays(act.size());
     if (two) {
-      split_groups(sds, act, half);
-      HIPCHK(hipEventRecord(c->ev_fork, st));
-      HIPCHK(hipStreamWaitEvent(hs[1], c->ev_fork, 0));
+      split_groups(sds, act, halves.half);
+      halves.fork();
     }
-    lapc(c->t_cyc);
+    lap(c->t_cyc);
     for (int j = 0; j < cyc && !live.empty(); ++j) {
-      // the residual estimates also go straight to a pinned host slot (read one
-      // iteration later, behind the event below)
+      // The residual estimates also go straight to a pinned host slot behind a lag event; the host looks at the
+      // PREVIOUS iteration's slot, so it never drains the streams (at most one surplus Arnoldi step per group).
       double* cur = hb + 2 * slot + (size_t)(j & 1) * slot;
-      if (two && live.size() < (size_t)kSplitMinGroups) join();
-      if (!joined) {
-        // the multi-shift kernels' choice follows the groups of the whole solve
-        for (int h = 0; h < 2; ++h) {
-          std::vector<int> lh;
-          for (int g : half[h])
-            if (std::find(live.begin(), live.end(), g) != live.end()) lh.push_back(g);
-          bh[h].set(lh);
-          bh[h].ng_solve = (int)live.size();
-        }
-        for (int h = 0; h < 2; ++h) {
-          if (bh[h].tab.ng > 0) iteration_launches(c, f, pf, bh[h], j, lowrank, cur);
-          HIPCHK(hipEventRecord(evh[h][j & 1], hs[h]));
-        }
+      if (!halves.pays(live.size())) halves.join();
+      if (halves.forked) {
+        halves.set_live(live);
+        halves.issue(f, pf, j, lowrank, cur, j & 1);
       } else {
         bt.set(live);
         iteration_launches(c, f, pf, bt, j, lowrank, cur);
-        // Residual estimates travel to a pinned slot behind an event; the host
-        // looks at the PREVIOUS iteration's slot, so it never drains the stream
-        // (one iteration of lag: at most one surplus Arnoldi step per group).
         HIPCHK(hipEventRecord(c->ev_res[j & 1], st));
       }
       for (int g : live) {
         ++res[g].iters;
-        kk[g] = j + 1;
+        kk.v[g] = j + 1;
       }
+      // who iterates on: not at maxit, and -- by the estimates of iteration j - 1, which have arrived behind their
+      // lag events -- not converged
       std::vector<int> still;
       if (j >= 1) {
         HIPCHK(hipEventSynchronize(c->ev_res[(j - 1) & 1]));
-        if (two) HIPCHK(hipEventSynchronize(evh[1][(j - 1) & 1]));   // (recorded up to the join; done since)
+        // (the second half's: recorded up to the join; done since)
+        if (two) HIPCHK(hipEventSynchronize(halves.lag_events(1)[(j - 1) & 1]));
         const double* prev = hb + 2 * slot + (size_t)((j - 1) & 1) * slot;
         for (int g : live)
           if (!group_converged(prev, g) && res[g].iters < maxit) still.push_back(g);
@@ -417,30 +477,50 @@ static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double
       live.swap(still);
     }
     // the second stream's iterations are complete before the corrections (and before anything after the solve)
-    join();
-    lapc(c->t_iter);
-    // corrections: x_g += Z_g y_g with the k_g preconditioned vectors group g built
-    // (one launch each for all groups of the cycle, k_g per group by value)
-    bt.set(act);
-    {
-      GroupInts ks = same_int(0);
-      for (int g : act) ks.v[g] = kk[g];
-      // one-reduction form: the last column of every group still waits for the correction of its candidate u_{k_g}
-      if (f.lowsync) arnoldi_lowsync_dots(c, bt, ks, true);
-      launch_gmres_backsolve_b(st, bt.tab, m, ks, restart, c->H.p, c->g.p, c->yv.p);
-      launch_cols_update_bk(st, bt.tab, n, m, ks, c->zbasisf.p, vs, nm, c->yv.p, (size_t)restart * m, x, nm, x, nm);
-    }
-    lapc(c->t_cyc);
+    halves.join();
+    lap(c->t_iter);
   }
-  lapc(c->t_cyc);
-  for (int g = 0; g < G; ++g)
-    if (!only || std::find(only->begin(), only->end(), g) != only->end()) sds[g]->last_iters = res[g].iters;
+
+  // corrections: x_g += Z_g y_g with the k_g preconditioned vectors group g built
+  // (one launch each for all groups of the cycle, k_g per group by value)
+  void end_cycle() {
+    bt.set(act);
+    // one-reduction form: the last column of every group still waits for the correction of its candidate u_{k_g}
+    if (f.lowsync) arnoldi_lowsync_dots(c, bt, kk, true);
+    launch_gmres_backsolve_b(st, bt.tab, m, kk, restart, c->H.p, c->g.p, c->yv.p);
+    launch_cols_update_bk(st, bt.tab, c->n, m, kk, c->zbasisf.p, vs, nm, c->yv.p, (size_t)restart * m, x, nm, x, nm);
+    lap(c->t_cyc);
+  }
+
+  void finish() {
+    lap(c->t_cyc);
+    for (int g = 0; g < G; ++g)
+      if (!only || std::find(only->begin(), only->end(), g) != only->end()) sds[g]->last_iters = res[g].iters;
+  }
+};
+
+}  // namespace
+
+// have_x0: x holds an initial guess (else it is zeroed);  only: the groups to iterate on (NULL = all; the
+// panels of the other groups are not touched);  allow_stall: a group whose full-length restart cycles no
+// longer gain is given up early (the caller repeats it with wider storage).
+static void gmres_core(ricadi_ctx* c, ShiftData* const* sds, int G, const double* b, size_t gsb, double* x,
+                       int m, bool lowrank, GmresResult* res, bool have_x0, const std::vector<int>* only,
+                       bool allow_stall) {
+  ensure_work(c, m, G, 0);
+  LockstepSolve s(c, sds, G, b, gsb, x, m, lowrank, res, have_x0, only, allow_stall);
+  s.rhs_norms();
+  while (s.begin_cycle()) {
+    s.iterate_cycle();
+    s.end_cycle();
+  }
+  s.finish();
 }
 
 // ---- wide panels as sixteen-column groups -------------------------------------------------------
 // The columns of a panel are independent Arnoldi processes (per-column Givens), so an n x m panel with
 // m > 32 -- the time-varying Riccati loop's [M^T Z_c, sqrt(tau) C~^T, K_k] of up to comprz_maxc + NY' + NU
-// columns, /root/reference/solve_dae_ric.py:149 -- is solved as groups of 16 columns of the SAME shift in
+// columns, solve_dae_ric.py:149 of the reference -- is solved as groups of 16 columns of the SAME shift in
 // the lockstep batch: every kernel tuned for the 16-column case (LDS-tiled SpMM, 16-byte Arnoldi kernels,
 // fused pressure step, FP16 vector input) then carries the iteration instead of the generic-width ones.
 // The shifts of the call are walked in chunks of floor(RICADI_MAX_GROUPS / groups per shift); the column
@@ -597,9 +677,7 @@ static bool recycle_guess(ricadi_ctx* c, ShiftData* const* sds, int G, const dou
   const int rank = gram_lstsq_scaled(h, m, Ghh, Ghb, 1e-11, Y);
   if (rank == 0) return false;
   HIPCHK(hipMemcpyAsync(Yd.p, Y.data(), sizeof(double) * h * m, hipMemcpyHostToDevice, st));
-  GroupTab all{};
-  all.ng = G;
-  for (int g = 0; g < G; ++g) all.gid[g] = g;
+  const GroupTab all = all_groups(G);
   r0 = 0;
   for (size_t i = 0; i < ent.size(); ++i) {
     GroupPtrs A = same_ptr((const double*)nullptr);
@@ -701,6 +779,26 @@ static int storage_level(const ricadi_ctx* c) {
   return 0;
 }
 
+// Relative true residuals ||b - (S - U V^T) x|| / ||b|| per column (G*m values, host);
+// the residual panels are left in c->wv.
+static void true_relres(ricadi_ctx* c, ShiftData* const* sds, int G, const double* b, size_t gsb,
+                        const double* x, int m, bool lowrank, double* out) {
+  hipStream_t st = c->st;
+  Batch bt = make_batch(c, sds, G, m);
+  const size_t nm = bt.gs;
+  const int GM = G * m;
+  double* hb = c->h_resid;
+  op_apply(c, bt, x, nm, c->wv.p, lowrank);
+  launch_axpby_b(st, bt.tab, nm, 1.0, b, gsb, -1.0, c->wv.p, nm);
+  panel_norms2(c, bt, c->wv.p, nm, c->nrm2.p);
+  panel_norms2(c, bt, b, gsb, c->bnorm2.p);
+  HIPCHK(hipMemcpyAsync(hb, c->nrm2.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hb + GM, c->bnorm2.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int j = 0; j < GM; ++j)
+    out[j] = hb[GM + j] > 0.0 ? std::sqrt(std::max(hb[j], 0.0) / hb[GM + j]) : 0.0;
+}
+
 // The batched solve as the drivers call it: recycled initial guess (shared right-hand side, plain
 // operator), the lockstep GMRES, the storage safety net -- a group that stops at gmres_maxit or
 // stagnates is continued from its iterate with the FP32- and then the FP64-stored basis and FP64
@@ -741,25 +839,7 @@ static void gmres_solve_batch(ricadi_ctx* c, ShiftData* const* sds, int G, const
     }
     bad.swap(still);
   }
-  if (relres_host) {
-    // true residuals
-    Batch bt = make_batch(c, sds, G, m);
-    const size_t nm = bt.gs;
-    const size_t gspart = (size_t)dots_num_blocks(c->n) * (c->opts.gmres_restart + 2) * m;
-    const int GM = G * m;
-    double* hb = c->h_resid;
-    op_apply(c, bt, x, nm, c->wv.p, lowrank);
-    launch_axpby_b(st, bt.tab, nm, 1.0, b, gsb, -1.0, c->wv.p, nm);
-    launch_cols_dots_b(st, bt.tab, c->n, m, 0, (const double*)nullptr, 0, 0, c->wv.p, nm, 1, c->partial.p,
-                       gspart, c->nrm2.p, (size_t)m);
-    launch_cols_dots_b(st, bt.tab, c->n, m, 0, (const double*)nullptr, 0, 0, b, gsb, 1, c->partial.p,
-                       gspart, c->bnorm2.p, (size_t)m);
-    HIPCHK(hipMemcpyAsync(hb, c->nrm2.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hb + GM, c->bnorm2.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int j = 0; j < GM; ++j)
-      relres_host[j] = hb[GM + j] > 0.0 ? std::sqrt(std::max(hb[j], 0.0) / hb[GM + j]) : 0.0;
-  }
+  if (relres_host) true_relres(c, sds, G, b, gsb, x, m, lowrank, relres_host);
   if (shared) recycle_store(c, sds, G, b, m, x);
   for (int g = 0; g < G; ++g) c->total_iters += res[g].iters;
   c->total_solves += G;
@@ -800,29 +880,6 @@ static bool host_invert(std::vector<double>& a, int q) {
   return true;
 }
 
-// Relative true residuals ||b - (S - U V^T) x|| / ||b|| per column (G*m values, host);
-// the residual panels are left in c->wv.
-static void true_relres(ricadi_ctx* c, ShiftData* const* sds, int G, const double* b, size_t gsb,
-                        const double* x, int m, bool lowrank, double* out) {
-  hipStream_t st = c->st;
-  Batch bt = make_batch(c, sds, G, m);
-  const size_t nm = bt.gs;
-  const size_t gspart = (size_t)dots_num_blocks(c->n) * (c->opts.gmres_restart + 2) * m;
-  const int GM = G * m;
-  double* hb = c->h_resid;
-  op_apply(c, bt, x, nm, c->wv.p, lowrank);
-  launch_axpby_b(st, bt.tab, nm, 1.0, b, gsb, -1.0, c->wv.p, nm);
-  launch_cols_dots_b(st, bt.tab, c->n, m, 0, (const double*)nullptr, 0, 0, c->wv.p, nm, 1, c->partial.p,
-                     gspart, c->nrm2.p, (size_t)m);
-  launch_cols_dots_b(st, bt.tab, c->n, m, 0, (const double*)nullptr, 0, 0, b, gsb, 1, c->partial.p,
-                     gspart, c->bnorm2.p, (size_t)m);
-  HIPCHK(hipMemcpyAsync(hb, c->nrm2.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(hb + GM, c->bnorm2.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  for (int j = 0; j < GM; ++j)
-    out[j] = hb[GM + j] > 0.0 ? std::sqrt(std::max(hb[j], 0.0) / hb[GM + j]) : 0.0;
-}
-
 // Batched solve with the low-rank term  (S_g - U V^T) x_g = b_g.
 //
 // Default: Sherman-Morrison-Woodbury, as the reference's lau.solve_sadpnt_smw does --
@@ -845,9 +902,7 @@ static void solve_batch(ricadi_ctx* c, ShiftData* const* sds, int G, const doubl
   const double tol = c->opts.gmres_tol;
   bool need = false;
   for (int g = 0; g < G; ++g) need = need || sds[g]->smw_epoch != c->lr_epoch;
-  GroupTab all{};
-  all.ng = G;
-  for (int g = 0; g < G; ++g) all.gid[g] = g;
+  const GroupTab all = all_groups(G);
   bool bad = false;
   // U = columns [ucol, ucol + q) of the (shared) right-hand side: S^-1 U is part of the plain solution,
   // no augmented columns needed (first sweep of a Newton step without mtxoldb: rhs = [W, K_k], U = K_k)
@@ -965,152 +1020,3 @@ static void load_rhs(ricadi_ctx* c, const double* dR, int m, double* b) {
   if (c->np > 0)
     HIPCHK(hipMemsetAsync(b + (size_t)c->nv * m, 0, sizeof(double) * (size_t)c->np * m, c->st));
 }
-
-// Per-shift data of the ADI shifts an iteration is about to use -- and of the projection
-// operator (alpha, beta) = (1, 0) when `with_projection` -- built in ONE setup pass: the
-// coarse matrices of all of them go through the same batched factorisation (a matrix set
-// up alone costs ~8x its share of a batch of 16).
-static void prefetch_setup(ricadi_ctx* c, const double* shifts, int nuse, bool with_projection) {
-  std::vector<double> al, be;
-  if (with_projection && c->np > 0) {
-    al.push_back(1.0);
-    be.push_back(0.0);
-  }
-  for (int i = 0; i < nuse; ++i) {
-    al.push_back(shifts[i]);
-    be.push_back(1.0);
-  }
-  if (al.empty()) return;
-  std::vector<ShiftData*> sds(al.size());
-  get_shifts(c, al.data(), be.data(), (int)al.size(), sds.data());
-}
-
-// W (NV x m, device, in place) <- P^T W  through one saddle solve with cal E
-static void project_panel(ricadi_ctx* c, double* dW, int m) {
-  if (c->np == 0) return;
-  ShiftData* sd = get_shift(c, 1.0, 0.0);
-  ensure_work(c, m);
-  load_rhs(c, dW, m, c->bvec.p);
-  GmresResult r = gmres_solve(c, sd, c->bvec.p, c->xs.p, m, false, nullptr);
-  if (!r.converged) throw HipError{"projection solve did not converge"};
-  launch_spmm(c->st, c->nv, c->E.rp.p, c->E.ci.p, c->E.v.p, c->xs.p, m, nullptr, dW, m, nullptr, 0,
-              1.0, 0.0, nullptr, m);
-}
-
-struct DScalar {
-  // tiny helper: Frobenius norm of W^T W and ||W||_F^2 of a device panel
-  static void gram_norms(ricadi_ctx* c, const double* dW, int nrows, int m, double* gram_fro,
-                         double* nrm2) {
-    DArr<double>& G = c->scratch;
-    G.ensure((size_t)m * m + 64);
-    HIPCHK(hipMemsetAsync(G.p, 0, sizeof(double) * m * m, c->st));
-    launch_gemm_tn(c->st, nrows, m, m, dW, m, dW, m, G.p, m);
-    std::vector<double> h((size_t)m * m);
-    HIPCHK(hipMemcpyAsync(h.data(), G.p, sizeof(double) * m * m, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    double f = 0.0, t = 0.0;
-    for (int i = 0; i < m; ++i) {
-      t += h[(size_t)i * m + i];
-      for (int j = 0; j < m; ++j) f += h[(size_t)i * m + j] * h[(size_t)i * m + j];
-    }
-    if (gram_fro) *gram_fro = std::sqrt(f);
-    if (nrm2) *nrm2 = t;
-  }
-};
-
-static int compress_dev(ricadi_ctx* c, const double* dZ, int cz, int ldz, double thresh, int kmax,
-                        bool thresh_relative, double* dOut, std::vector<double>* sv_host,
-                        bool use_qr = false);
-static void block_qr_dev(ricadi_ctx* c, const double* D, int ldd, int n, int kk, double* Q,
-                         double* R, int split = 0);
-
-// Truncation level of the internal recompressions: the Gram-matrix route
-// resolves singular values down to sqrt(eps)*sigma_1; dropping what lies below
-// changes Z Z^T by at most eps*||Z Z^T|| -- rounding level.
-static const double kInternalRelThresh = 3e-8;
-
-static Exec main_exec(ricadi_ctx* c);
-static int recompress_exec(ricadi_ctx* c, const Exec& ex, const double* dZ, int cz, int ldz, double rel,
-                           double* dOut);
-
-// Recompress the device factor in place (columns [0, zc) of c->Z).
-static void factor_recompress(ricadi_ctx* c) {
-  if (c->zc == 0) return;
-  TArr<double> tmp(c->pool, (size_t)c->nv * c->zc);
-  const int k = recompress_exec(c, main_exec(c), c->Z.p, c->zc, c->zld, kInternalRelThresh, tmp.p);
-  if (k > 0) launch_copy_cols(c->st, c->nv, k, tmp.p, k, 0, c->Z.p, c->zld, 0, 1.0);
-  HIPCHK(hipStreamSynchronize(c->st));
-  c->zc = k;
-}
-
-static int compress_gram_exec(ricadi_ctx* c, const Exec& ex, const double* dZ, int cz, int ldz,
-                              double thresh, int kmax, bool thresh_relative, double* dOut,
-                              std::vector<double>* sv_host);
-static int recompress_exec(ricadi_ctx* c, const Exec& ex, const double* dZ, int cz, int ldz, double rel,
-                           double* dOut);
-
-// Auxiliary stream + handle for work that runs beside the main stream (created on first use).
-static Exec aux_exec(ricadi_ctx* c) {
-  if (!c->st2) {
-    HIPCHK(hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking));
-    RBCHK(rocblas_create_handle(&c->rb2));
-    RBCHK(rocblas_set_stream(c->rb2, c->st2));
-    c->info2.alloc(4);
-    c->flag2.alloc(4);
-    HIPCHK(hipEventCreateWithFlags(&c->ev_z, hipEventDisableTiming));
-  }
-  Exec ex;
-  ex.st = c->st2;
-  ex.rb = c->rb2;
-  ex.pool = &c->pool2;
-  ex.info = c->info2.p;
-  ex.flag = c->flag2.p;
-  return ex;
-}
-
-// In-ADI recompression that does not stall the sweeps: the columns [0, snap) of the factor are
-// compressed on the auxiliary stream by a helper thread (same arithmetic as
-// factor_recompress) while the main stream goes on appending columns behind them; finish()
-// splices the result in:  Z <- [compressed prefix | columns appended meanwhile].
-// Member order matters: `fut` is destroyed first and waits for the helper, then `out`.
-struct AsyncRecompress {
-  ricadi_ctx* c;
-  TArr<double> out;
-  int snap = 0;
-  bool active = false;
-  std::future<int> fut;
-  explicit AsyncRecompress(ricadi_ctx* ctx) : c(ctx), out(ctx->pool) {}
-  void start() {
-    if (active || c->zc == 0) return;
-    const Exec ex = aux_exec(c);
-    snap = c->zc;
-    out.alloc((size_t)c->nv * snap);
-    HIPCHK(hipEventRecord(c->ev_z, c->st));            // the prefix is complete on the main stream
-    HIPCHK(hipStreamWaitEvent(c->st2, c->ev_z, 0));
-    ricadi_ctx* cc = c;
-    const double* Zp = c->Z.p;
-    const int ld = c->zld, sn = snap, dev = c->dev;
-    double* op = out.p;
-    fut = std::async(std::launch::async, [cc, ex, Zp, ld, sn, dev, op]() {
-      (void)hipSetDevice(dev);
-      return recompress_exec(cc, ex, Zp, sn, ld, kInternalRelThresh, op);
-    });
-    active = true;
-  }
-  void finish() {
-    if (!active) return;
-    active = false;
-    const int k = fut.get();                            // the auxiliary stream is drained in there
-    hipStream_t st = c->st;
-    const int nv = c->nv, tail = c->zc - snap;
-    if (tail > 0) {
-      TArr<double> tmp(c->pool, (size_t)nv * tail);
-      launch_copy_cols(st, nv, tail, c->Z.p, c->zld, snap, tmp.p, tail, 0, 1.0);
-      launch_copy_cols(st, nv, tail, tmp.p, tail, 0, c->Z.p, c->zld, k, 1.0);
-    }
-    if (k > 0) launch_copy_cols(st, nv, k, out.p, k, 0, c->Z.p, c->zld, 0, 1.0);
-    c->zc = k + tail;
-    out.release();
-  }
-};
-

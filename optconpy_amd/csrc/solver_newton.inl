@@ -81,7 +81,7 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
     launch_copy_cols(st, nv, mw, dWm.p, mw, 0, dRhs.p, m, 0, 1.0);
     if (m > mw) launch_copy_cols(st, nv, nb, dK.p, nb, 0, dRhs.p, m, mw, 1.0);
     factor_reserve(c, prm->adi_max_steps * m);
-    DScalar::gram_norms(c, dRhs.p, nv, m, &last_rhs, nullptr);
+    gram_norms(c, dRhs.p, nv, m, &last_rhs, nullptr);
     // without mtxoldb the low-rank factor U = K_k is the last nb columns of the rhs itself
     c->lr_ucol = (lr && !oldB && m > mw) ? mw : -1;
     AdiStats s = lyap_adi_dev(c, shifts, ns, dRhs.p, m, p2);

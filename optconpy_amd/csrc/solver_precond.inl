@@ -5,6 +5,12 @@
 // The shifts of one batched solve: per group id the shift-dependent operands, and
 // the table of groups a launch works on (ricadi_internal.h).  All workspace
 // buffers are group-major with the strides below.
+static GroupTab all_groups(int G) {
+  GroupTab t{};
+  t.ng = G;
+  for (int g = 0; g < G; ++g) t.gid[g] = g;
+  return t;
+}
 struct Batch {
   int G = 0;                 // groups in the solve (ids 0 .. G-1)
   int m = 0;                 // panel width of every group
@@ -26,10 +32,7 @@ struct Batch {
   int ng_solve = 0;
   int ms_groups() const { return ng_solve > 0 ? ng_solve : tab.ng; }
 
-  void all() {
-    tab.ng = G;
-    for (int g = 0; g < G; ++g) tab.gid[g] = g;
-  }
+  void all() { tab = all_groups(G); }
   void only(int g) {
     tab.ng = 1;
     tab.gid[0] = g;

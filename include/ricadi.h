@@ -188,10 +188,13 @@ int ricadi_precond_apply(ricadi_ctx* ctx, double alpha, double beta,
 #define RICADI_PCF_COARSE_SHIFT 6        /* 2 bits: coarse problem 1 child level's cycle, 2 dense inverse     */
 #define RICADI_PCF_PFUSED (1 << 8)       /* pressure step in one launch                                       */
 #define RICADI_PCF_PSPLIT (1 << 9)       /* pressure step in three launches                                   */
-#define RICADI_PCF_FIRST_SHIFT 10        /* 2 bits: first velocity sweep 1 record-driven BF16 two-term,
-                                            2 generic two-term, 3 plain block sweep                           */
-#define RICADI_PCF_LAST_SHIFT 12         /* 2 bits: last velocity sweep 1 record-driven BF16 rectangle,
-                                            2 generic rectangle, 3 J^T product formed row by row (CSR in)    */
+#define RICADI_PCF_FIRST_SHIFT 10        /* 2 bits: first velocity sweep 1 record-driven two-term on BF16 blocks,
+                                            2 two-term on FP32- or FP64-stored blocks (record-driven kernel where
+                                            the level has records and the shape admits it, generic kernel
+                                            otherwise), 3 plain block sweep                                   */
+#define RICADI_PCF_LAST_SHIFT 12         /* 2 bits: last velocity sweep 1 record-driven rectangle on BF16 blocks,
+                                            2 rectangle on FP32- or FP64-stored blocks (record-driven or generic
+                                            kernel, as above), 3 J^T product formed row by row (CSR in)       */
 #define RICADI_PCF_FOLDED (1 << 14)      /* folded cycle (coarse residual inside the first sweep)             */
 #define RICADI_PCF_VANKA (1 << 15)       /* a child level's cycle with the coloured Vanka sweep: coarse correction,
                                             then per colour the residual and the patch kernel (no SIMPLE sweeps:

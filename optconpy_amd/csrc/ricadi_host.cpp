@@ -1011,7 +1011,7 @@ PrecondRecords build_records(const HostSetup& hs, const HostCsr& J, const HostCs
       r.ady_ok = true;
     }
   }
-  // fixed-stride records of the velocity sweeps (block_rect32_kernel, block_two32_kernel; ProlongArgs::bmeta)
+  // fixed-stride records of the velocity sweeps (block_rect32_kernel, block_two32_kernel; SweepRecs)
   if (sweep_meta && hs.bs == 32 && hs.nbv > 0 && (r.gt_ok || r.ady_ok)) {
     const int kr = r.gt_ok ? r.gt_ks : 0, k2 = r.ady_ok ? r.ady_ks : 0;
     const int stride = swrec_stride(kr, k2);

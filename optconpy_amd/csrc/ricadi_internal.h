@@ -100,7 +100,7 @@ void build_setup_checked(const HostCsr& A, const HostCsr& E, const HostCsr& J, c
                          HostSetup& hs, int max_levels, double sa_omega);
 
 // ---- device records of the preconditioner ------------------------------------------
-// Fixed-stride record of a 32-row velocity block (ricadi_ctx::sw_meta, ProlongArgs::bmeta): a header of
+// Fixed-stride record of a 32-row velocity block (ricadi_ctx::sw_meta, SweepRecs::meta): a header of
 // SWREC_ROWS words {nb, ni of the rectangle sweep, ni of the two-term sweep, 0}, then the block's rows [32], the
 // aggregate of every row [32], the input rows of the rectangle sweep [kr] and of the two-term sweep [k2]; every list
 // is padded with its last entry.  kr / k2: padded slice widths of the two sweeps (0: sweep not in that form).
@@ -194,25 +194,26 @@ inline GroupPtrsT<T> same_ptr(const T* q) {
   return g;
 }
 
-// Coarse-level prolongation fused into a block-Jacobi sweep: every row the sweep
-// writes gets  + ec[aggof[row], :]  (ec: kc x m per group, stride gse), and surplus
-// waves do the same for rows [row0, row0 + nextra) outside the blocks.
+// The epilogue of a block-Jacobi sweep.  Coarse-level prolongation fused into it: every row the sweep
+// writes gets  + ec[aggof[row], :]  (ec: kc x m per group, stride gse); and the copies of the result.
 struct ProlongArgs {
   const int* aggof = nullptr;
   const double* ec = nullptr;
   size_t gse = 0;
-  int row0 = 0, nextra = 0;
   double* out2 = nullptr;   // if set: the sweep's result before the coarse part is added
   size_t gs2 = 0;
   float* out32 = nullptr;   // if set: FP32 copy of what the sweep writes (flexible GMRES keeps Z_j = P^-1 v_j)
   size_t gs32 = 0;
   int only32 = 0;           // with out32: the FP64 result is not stored (the operator reads the FP32 copy)
   int old32 = 0;            // rectangle sweep: the rows it updates are read from out32 (FP32 intermediate of the cycle)
-  // Fixed-stride record per 32-row block (ricadi_ctx::sw_meta; layout: SWREC_* above).  With it a wave has every
-  // index after ONE load round (block pointers -> row lists -> aggregate map were three dependent ones); bm_in =
-  // offset of the launched sweep's input list (SWREC_IN for the rectangle sweep, SWREC_IN + kr for the two-term one).
-  const int* bmeta = nullptr;
-  int bm_stride = 0, bm_in = 0, bm_ni = 0;   // bm_ni: which header word holds ni (1 or 2)
+};
+// The fixed-stride records of the 32-row velocity blocks (ricadi_ctx::sw_meta; layout: SWREC_* above), for the two
+// record-driven sweeps.  With them a wave has every index after ONE load round (block pointers -> row lists ->
+// aggregate map were three dependent ones).  in_off: offset of the launched sweep's input list in a record (SWREC_IN
+// for the rectangle sweep, SWREC_IN + kr for the two-term one).
+struct SweepRecs {
+  const int* meta = nullptr;
+  int stride = 0, in_off = 0;
 };
 
 // Low-rank term fused into an SpMM epilogue:  y[row, :] -= U[row, :] * c  for
@@ -270,7 +271,7 @@ __host__ __device__ inline size_t rckb_index(int j, int c, int k) {
   return j < (k & ~3) ? ((size_t)(j >> 2) * 16 + c) * 4 + (j & 3) : (size_t)j * 16 + c;
 }
 
-// ---- kernel launchers (ricadi_kernels.hip) ---------------------------------
+// ---- kernel launchers (ricadi_spmm.hip, ricadi_arnoldi.hip, ricadi_precond.hip, ricadi_dense.hip) -----
 // The *_b launchers are the batched forms (GroupTab + group strides `gs*`, in
 // doubles); the plain ones run a single panel.
 void launch_spmm_h(hipStream_t st, const GroupTab& gt, int nrows, const int* rp, const int* ci,
@@ -345,7 +346,8 @@ void launch_gmres_backsolve_b(hipStream_t st, const GroupTab& gt, int m, const G
                               int restart, const double* H, const double* g, double* y);
 void launch_gmres_start_b(hipStream_t st, const GroupTab& gt, int m, int restart,
                           const double* nrm2, double* g, double* scale, double* resid);
-// The preconditioner sweeps take their operands stored in FP64 (T = double: GroupPtrs) or FP32 (T = float: GroupPtrsF).
+// The generic preconditioner sweeps take their operands stored in FP64 (T = double: GroupPtrs) or FP32 (T = float:
+// GroupPtrsF).
 template <class T>
 void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblocks, const int* bptr,
                           const int* rows, const GroupPtrsT<T>& inv, const double* in, int ldi,
@@ -353,9 +355,9 @@ void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblock
                           const ProlongArgs& pa = ProlongArgs(), const CsrInArgs& ci = CsrInArgs());
 void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, const GroupPtrs& Einv,
                           const double* rc, double* ec);
-// FP32-stored inverses (leading dimension ldf = k rounded up to 4; bs x bs blocks)
+// FP32-stored inverses: tile-major (launch_to_f32_tiled)
 void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, const GroupPtrsF& Einv,
-                          int ldf, const double* rc, double* ec);
+                          const double* rc, double* ec);
 // The same product on the FP32 tile-major inverse for m = 16 with rc in the k-blocked layout (rckb_index); ec
 // row-major as above.
 void launch_dense_apply_kb(hipStream_t st, const GroupTab& gt, int k, const GroupPtrsF& Einv, const double* rc,
@@ -392,7 +394,7 @@ void launch_gemm_nn_bp(hipStream_t st, const GroupTab& gt, int n, int p, int q, 
 void launch_spmm(hipStream_t st, int nrows, const int* rp, const int* ci, const double* val,
                  const double* x, int ldx, const int* xmap, double* y, int ldy, const double* r,
                  int ldr, double alpha, double beta_r, const double* rowscale, int m);
-size_t spmm_blocked_lds_bytes(int m, int max_cols, int max_nnz);
+size_t spmm_blocked_lds_bytes(int m, int max_cols);
 void launch_gather_vals(hipStream_t st, int nnz, const int* perm, const double* src, double* dst);
 void launch_assemble_shift(hipStream_t st, int nnz, const double* srcA, const double* srcE,
                            const double* srcJ, double alpha, double beta, double* out);
@@ -428,7 +430,7 @@ void launch_cholqr_small(hipStream_t st, int w, const double* G, const double* R
 void launch_cholqr_wide(hipStream_t st, int w, const double* G, int ldg, double* T, double* R, int* flag);
 void launch_select_evecs(hipStream_t st, int c, int k, const double* evec, double* sel);
 void launch_transpose_sign(hipStream_t st, int k, int k1, double sneg, const double* in, double* out);
-// batched block Gauss-Jordan inverse of the coarse matrices (ricadi_kernels.hip); nb <= RICADI_MAX_GROUPS matrices
+// batched block Gauss-Jordan inverse of the coarse matrices (ricadi_precond.hip); nb <= RICADI_MAX_GROUPS matrices
 int gj_block();
 int gj_max_batch();
 void launch_gj_prep(hipStream_t st, int nb, double* const* mats, int k, int k0, int nbe, double* Cb, double* Rp,
@@ -457,23 +459,23 @@ void launch_prolong_plain(hipStream_t st, const GroupTab& gt, int n, int m, cons
                           size_t gse, double* z, size_t gsz);
 // dst (BF16 bit patterns, round to nearest even) = src (FP64), n entries
 void launch_to_bf16(hipStream_t st, size_t n, const double* src, uint16_t* dst);
-// The hot-shape sweeps (32-row blocks, 16 columns, fixed-stride records in pa.bmeta) on BF16-stored blocks: same
-// contracts as launch_block_apply2_b / launch_block_apply_rect_b / launch_pressure_step_b with the FP32 panel.  The
-// two velocity sweeps take only the shapes their predicate admits: padded width ks (s2.kstride) of 32 or 64, group
-// strides that fit 32-bit byte offsets, and for the rectangles an FP32 intermediate (old32) only with its panel; the
-// two-term one adds no coarse correction (pa.aggof unset).
-// pipe: the first sweep with its second segment's loads in flight behind the first segment's MFMAs (block_two32_kernel)
-bool block_two32_h_ok(int ks, size_t gso, size_t gs1, size_t gs2);
-void launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const GroupPtrsH& m1, const Seg2& s1,
-                          const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa,
-                          bool pipe = false);
-bool block_rect32_h_ok(int ks, size_t gsi, size_t gso, bool old32, bool out32);
-void launch_block_rect32_h(hipStream_t st, const GroupTab& gt, int ks, int nblocks, const GroupPtrsH& mats,
-                           const double* in, size_t gsi, double* out, size_t gso, int subtract, const ProlongArgs& pa);
-void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
-                            const GroupPtrsH& inv, const int* jci, const double* jv, bool with_sy, const int* syci,
-                            const GroupPtrs& syv, const double* ec, size_t gse, const double* rp_, const _Float16* rp16,
-                            size_t gsr, double* out, size_t gso, const ProlongArgs& pa, const float* zv32, size_t gsz32);
+// The two velocity sweeps of the hot shape driven by the fixed-stride records (block_two32_kernel, block_rect32_kernel):
+// same contracts as launch_block_apply2_b / launch_block_apply_rect_b on packed 16-column panels (leading dimension
+// 16), for blocks stored as T = double, float or uint16_t (BF16).  Each takes exactly what its predicate admits:
+// 32-row blocks, m == 16, a padded width ks (s2.kstride) of 32 or 64, records (recs), group strides whose byte offsets
+// fit 32 bits; the rectangles an FP32 intermediate (old32) only with its panel (out32); the two-term sweep no fused
+// prolongation (prolong: pa.aggof set).
+// pipe (BF16 blocks only): the second segment's loads in flight behind the first segment's MFMAs
+bool block_two32_ok(int bs, int m, int ks, bool recs, bool prolong, size_t gso, size_t gs1, size_t gs2);
+template <class T>
+void launch_block_two32(hipStream_t st, const GroupTab& gt, int nblocks, const SweepRecs& rec, const GroupPtrsT<T>& m1,
+                        const Seg2& s1, const GroupPtrsT<T>& m2, const Seg2& s2, double* out, size_t gso,
+                        const ProlongArgs& pa, bool pipe = false);
+bool block_rect32_ok(int bs, int m, int ks, bool recs, size_t gsi, size_t gso, bool old32, bool out32);
+template <class T>
+void launch_block_rect32(hipStream_t st, const GroupTab& gt, int ks, int nblocks, const SweepRecs& rec,
+                         const GroupPtrsT<T>& mats, const double* in, size_t gsi, double* out, size_t gso, int subtract,
+                         const ProlongArgs& pa);
 
 // K2p: the pressure step of the SIMPLE cycle fused into one launch (m = 16, 32 x 32 Schur blocks):
 //   out[rows_b] = inv_b (J z + (S Y)_p ec - r_p)[rows_b]  with the epilogue options of the Schur sweep (pa).
@@ -481,6 +483,7 @@ void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, con
 // with_sy = false: no coarse term; z is the n x 16 panel whose
 // velocity rows are read, rp_ / rp16 the pressure rows of the residual (FP64 or FP16-stored), out the pressure rows of z.
 // zv32 (optional, group stride gsz32): the velocity rows as the FP32 panel the first sweep left (64-B row gathers).
+// T = double, float or uint16_t (BF16-stored inverses).
 template <class T>
 void launch_pressure_step_b(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
                             const GroupPtrsT<T>& inv, const int* jci, const double* jv, const double* z,
@@ -528,7 +531,7 @@ void launch_arnoldi16_lowsync_close(hipStream_t st, const GroupTab& gt, const Gr
                                     double tol);
 
 // K5c: pivoted Cholesky of a (possibly augmented) symmetric matrix, 8 / 16 / 32 pivots per launch pair --
-// the eigensolver-free recompression (ricadi_kernels.hip).  State lives on the device so that the host can
+// the eigensolver-free recompression (ricadi_dense.hip).  State lives on the device so that the host can
 // issue all blocks without a read-back: once `stop` is set the remaining launches return at once.
 struct PcholState {
   double d0;     // first pivot (scale of the tolerance)

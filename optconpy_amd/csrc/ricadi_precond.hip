@@ -98,20 +98,7 @@ __global__ __launch_bounds__(256) void block_apply_kernel(
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, q = lane >> 4;
-  if (wave >= nblocks) {
-    // surplus waves: coarse-level prolongation of the rows outside the blocks
-    // (the pressure rows when this is the last velocity sweep), 32 rows per wave
-    const int e0 = (wave - nblocks) * 32;
-    for (int rr = e0 + q; rr < min(e0 + 32, pa.nextra); rr += 4) {
-      const int row = pa.row0 + rr;
-      for (int col = r; col < m; col += 16) {
-        const double v = out[(size_t)row * ldo + col] + ec[(size_t)pa.aggof[row] * m + col];
-        out[(size_t)row * ldo + col] = v;
-        if (pa.out32) pa.out32[(size_t)grp * pa.gs32 + (size_t)row * ldo + col] = (float)v;
-      }
-    }
-    return;
-  }
+  if (wave >= nblocks) return;          // (the grid is rounded up to four waves)
   const int b0 = bptr[wave], nb = bptr[wave + 1] - b0;
   const T* Bi = inv + (size_t)wave * BS * BS;
   constexpr int NT = BS / 16;
@@ -181,20 +168,7 @@ void launch_block_apply_b(hipStream_t st, const GroupTab& gt, int bs, int nblock
                           size_t gsi, double* out, int ldo, size_t gso, int m, int subtract,
                           const ProlongArgs& pa, const CsrInArgs& ci) {
   if (nblocks <= 0 || gt.ng <= 0) return;
-  // plain panel input, 32 x 32 blocks: the rectangle kernel with the block's own rows as its input list (its loads
-  // are issued in groups; this kernel's index -> gather pairs are a chain of dependent round trips).
-  // RICADI_BA_PLAIN=1 keeps this kernel.
-  // Only where the launch is latency bound (few waves: the Schur sweep of cfg2 has 110 blocks x 16 groups): with many
-  // waves the rectangle kernel's 152 VGPRs cost more than its grouped loads gain (velocity-sized sweep at cfg2:
-  // 43 vs 33 us).
-  static const bool via_rect = true;
-  if (via_rect && !ci.rp && bs == 32 && (long)nblocks * gt.ng <= 8192) {
-    launch_block_apply_rect_b(st, gt, 32, 32, nblocks, bptr, rows, bptr, rows, inv, in, ldi, gsi, out, ldo, gso, m,
-                          subtract, pa);
-    return;
-  }
-  const int nwaves = nblocks + (pa.aggof ? (pa.nextra + 31) / 32 : 0);
-  dim3 grid((nwaves + 3) / 4, 1, gt.ng), block(256);
+  dim3 grid((nblocks + 3) / 4, 1, gt.ng), block(256);
   switch (bs) {
     case 16:
       hipLaunchKernelGGL((block_apply_kernel<16, T>), grid, block, 0, st, gt, nblocks, bptr, rows,
@@ -241,17 +215,7 @@ __global__ __launch_bounds__(256) void block_rect32_kernel(
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, q = lane >> 4;
-  if (wave >= nblocks) {
-    // surplus waves: coarse-level prolongation of the rows outside the blocks
-    const int e0 = (wave - nblocks) * 32;
-    for (int rr = e0 + q; rr < min(e0 + 32, pa.nextra); rr += 4) {
-      const int row = pa.row0 + rr;
-      const double v = out[(size_t)row * 16 + r] + ec[(size_t)pa.aggof[row] * 16 + r];
-      out[(size_t)row * 16 + r] = v;
-      if (o32) o32[(size_t)row * 16 + r] = (float)v;
-    }
-    return;
-  }
+  if (wave >= nblocks) return;          // (the grid is rounded up to four waves)
   constexpr int NK = KS / 16;
   const int* __restrict__ mt = meta + (size_t)wave * mstride;
   const T* __restrict__ Gi = mat + (size_t)wave * 32 * KS;
@@ -457,6 +421,50 @@ __global__ __launch_bounds__(256) void block_two32_kernel(
     }
 }
 
+// The one launcher and the one predicate of each of the two kernels (what the predicates ask: ricadi_internal.h).
+static bool offsets_fit32(size_t gs) { return gs * 8 < ((size_t)1 << 32); }   // byte offsets within a group's panel
+bool block_rect32_ok(int bs, int m, int ks, bool recs, size_t gsi, size_t gso, bool old32, bool out32) {
+  return recs && bs == 32 && m == 16 && (ks == 32 || ks == 64) && offsets_fit32(std::max(gsi, gso)) &&
+         !(old32 && !out32);
+}
+template <class T>
+void launch_block_rect32(hipStream_t st, const GroupTab& gt, int ks, int nblocks, const SweepRecs& rec,
+                         const GroupPtrsT<T>& mats, const double* in, size_t gsi, double* out, size_t gso, int subtract,
+                         const ProlongArgs& pa) {
+  if (nblocks <= 0 || gt.ng <= 0) return;
+  dim3 grid((nblocks + 3) / 4, 1, gt.ng), block(256);
+#define RICADI_RECT32(K, O)                                                                                 \
+  hipLaunchKernelGGL((block_rect32_kernel<K, T, O>), grid, block, 0, st, gt, nblocks, rec.meta, rec.stride, \
+                     rec.in_off, mats, in, gsi, out, gso, subtract, pa)
+  if (ks == 32) { if (pa.old32) RICADI_RECT32(32, true); else RICADI_RECT32(32, false); }
+  else { if (pa.old32) RICADI_RECT32(64, true); else RICADI_RECT32(64, false); }
+#undef RICADI_RECT32
+}
+bool block_two32_ok(int bs, int m, int ks, bool recs, bool prolong, size_t gso, size_t gs1, size_t gs2) {
+  return recs && bs == 32 && m == 16 && (ks == 32 || ks == 64) && offsets_fit32(std::max({gso, gs1, gs2})) && !prolong;
+}
+template <class T>
+void launch_block_two32(hipStream_t st, const GroupTab& gt, int nblocks, const SweepRecs& rec, const GroupPtrsT<T>& m1,
+                        const Seg2& s1, const GroupPtrsT<T>& m2, const Seg2& s2, double* out, size_t gso,
+                        const ProlongArgs& pa, bool pipe) {
+  if (nblocks <= 0 || gt.ng <= 0) return;
+  dim3 grid((nblocks + 3) / 4, 1, gt.ng), block(256);
+#define RICADI_TWO32(K, H, P)                                                                                 \
+  hipLaunchKernelGGL((block_two32_kernel<K, T, H, P>), grid, block, 0, st, gt, nblocks, rec.meta, rec.stride, \
+                     rec.in_off, m1, s1, m2, s2, out, gso, pa)
+#define RICADI_TWO32_H(K, P) \
+  if (s1.in16) RICADI_TWO32(K, true, P); else RICADI_TWO32(K, false, P)
+  if constexpr (std::is_same<T, uint16_t>::value) {      // the only blocks the pipelined form is built for
+    if (pipe) {
+      if (s2.kstride == 32) RICADI_TWO32_H(32, true); else RICADI_TWO32_H(64, true);
+      return;
+    }
+  }
+  if (s2.kstride == 32) RICADI_TWO32_H(32, false); else RICADI_TWO32_H(64, false);
+#undef RICADI_TWO32_H
+#undef RICADI_TWO32
+}
+
 // ---------------------------------------------------------------------------
 // K2, rectangular form: the last velocity sweep of the SIMPLE cycle,
 //     z_v[rows_b] -= G_b * z_p[pcols_b],      G_b = Ahat_b^-1 * J^T[rows_b, pcols_b]   (BS x KS)
@@ -481,19 +489,7 @@ __global__ __launch_bounds__(256) void block_apply_rect_kernel(
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, q = lane >> 4;
-  if (wave >= nblocks) {
-    // surplus waves: coarse-level prolongation of the rows outside the blocks
-    const int e0 = (wave - nblocks) * 32;
-    for (int rr = e0 + q; rr < min(e0 + 32, pa.nextra); rr += 4) {
-      const int row = pa.row0 + rr;
-      for (int col = r; col < m; col += 16) {
-        const double v = out[(size_t)row * ldo + col] + ec[(size_t)pa.aggof[row] * m + col];
-        out[(size_t)row * ldo + col] = v;
-        if (pa.out32) pa.out32[(size_t)grp * pa.gs32 + (size_t)row * ldo + col] = (float)v;
-      }
-    }
-    return;
-  }
+  if (wave >= nblocks) return;          // (the grid is rounded up to four waves)
   const int b0 = bptr[wave], nb = bptr[wave + 1] - b0;
   const int i0 = iptr[wave], ni = iptr[wave + 1] - i0;
   const T* Gi = mat + (size_t)wave * BS * KS;
@@ -603,18 +599,7 @@ void launch_block_apply_rect_b(hipStream_t st, const GroupTab& gt, int bs, int k
                                const GroupPtrsT<T>& mats, const double* in, int ldi, size_t gsi, double* out,
                                int ldo, size_t gso, int m, int subtract, const ProlongArgs& pa) {
   if (nblocks <= 0 || gt.ng <= 0) return;
-  const int nwaves = nblocks + (pa.aggof ? (pa.nextra + 31) / 32 : 0);
-  dim3 grid((nwaves + 3) / 4, 1, gt.ng), block(256);
-  if (pa.bmeta && bs == 32 && m == 16 && ldi == 16 && ldo == 16 && (ks == 32 || ks == 64) &&
-      std::max(gsi, gso) * 8 < ((size_t)1 << 32) && !(pa.old32 && !pa.out32)) {
-#define RICADI_RECT32(K, O)                                                                                  \
-  hipLaunchKernelGGL((block_rect32_kernel<K, T, O>), grid, block, 0, st, gt, nblocks, pa.bmeta, pa.bm_stride, \
-                     pa.bm_in, mats, in, gsi, out, gso, subtract, pa)
-    if (ks == 32) { if (pa.old32) RICADI_RECT32(32, true); else RICADI_RECT32(32, false); }
-    else { if (pa.old32) RICADI_RECT32(64, true); else RICADI_RECT32(64, false); }
-#undef RICADI_RECT32
-    return;
-  }
+  dim3 grid((nblocks + 3) / 4, 1, gt.ng), block(256);
 #define RICADI_RECT(B, K)                                                                           \
   hipLaunchKernelGGL((block_apply_rect_kernel<B, K, T>), grid, block, 0, st, gt, nblocks, bptr, rows, \
                      iptr, irows, mats, in, ldi, gsi, out, ldo, gso, m, subtract, pa)
@@ -656,18 +641,7 @@ __global__ __launch_bounds__(256) void block_apply2_kernel(
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, q = lane >> 4;
-  if (wave >= nblocks) {
-    const int e0 = (wave - nblocks) * 32;
-    for (int rr = e0 + q; rr < min(e0 + 32, pa.nextra); rr += 4) {
-      const int row = pa.row0 + rr;
-      for (int col = r; col < m; col += 16) {
-        const double v = out[(size_t)row * ldo + col] + ec[(size_t)pa.aggof[row] * m + col];
-        out[(size_t)row * ldo + col] = v;
-        if (pa.out32) pa.out32[(size_t)grp * pa.gs32 + (size_t)row * ldo + col] = (float)v;
-      }
-    }
-    return;
-  }
+  if (wave >= nblocks) return;          // (the grid is rounded up to four waves)
   const int b0 = bptr[wave], nb = bptr[wave + 1] - b0;
   const int i0 = s2.iptr[wave], ni = s2.iptr[wave + 1] - i0;
   constexpr int NT = BS / 16, N1 = BS / 16, N2 = K2 / 16;
@@ -773,18 +747,7 @@ void launch_block_apply2_b(hipStream_t st, const GroupTab& gt, int bs, int nbloc
                            const int* rows, const GroupPtrsT<T>& m1, const Seg2& s1, const GroupPtrsT<T>& m2,
                            const Seg2& s2, double* out, int ldo, size_t gso, int m, const ProlongArgs& pa) {
   if (nblocks <= 0 || gt.ng <= 0) return;
-  const int nwaves = nblocks + (pa.aggof ? (pa.nextra + 31) / 32 : 0);
-  dim3 grid((nwaves + 3) / 4, 1, gt.ng), block(256);
-  if (pa.bmeta && bs == 32 && m == 16 && ldo == 16 && !pa.aggof && (s2.kstride == 32 || s2.kstride == 64) &&
-      std::max(std::max(gso, s1.gs), s2.gs) * 8 < ((size_t)1 << 32)) {
-#define RICADI_TWO32(K, H)                                                                                  \
-  hipLaunchKernelGGL((block_two32_kernel<K, T, H>), grid, block, 0, st, gt, nblocks, pa.bmeta, pa.bm_stride, \
-                     pa.bm_in, m1, s1, m2, s2, out, gso, pa)
-    if (s2.kstride == 32) { if (s1.in16) RICADI_TWO32(32, true); else RICADI_TWO32(32, false); }
-    else { if (s1.in16) RICADI_TWO32(64, true); else RICADI_TWO32(64, false); }
-#undef RICADI_TWO32
-    return;
-  }
+  dim3 grid((nblocks + 3) / 4, 1, gt.ng), block(256);
   // H = first-segment rows read from an FP16 panel (s1.in16): its own instantiation -- both paths in one
   // kernel cost 148 instead of 128 VGPRs, i.e. one wave per SIMD less
 #define RICADI_BA2(B, K, H)                                                                              \
@@ -1289,8 +1252,7 @@ static void dense_apply_tiled_launch(hipStream_t st, const GroupTab& gt, int k, 
   hipLaunchKernelGGL((dense_apply_tiled_kernel<T, 1>), grid, dim3(512), 0, st, gt, k, m, Einv, rc, ec);
 }
 void launch_dense_apply_b(hipStream_t st, const GroupTab& gt, int k, int m, const GroupPtrsF& Einv,
-                          int ldf, const double* rc, double* ec) {
-  (void)ldf;   // tile-major storage (launch_to_f32_tiled)
+                          const double* rc, double* ec) {
   dense_apply_tiled_launch(st, gt, k, m, Einv, rc, ec);
 }
 // The coarse apply for m = 16 on the k-blocked coarse residual (rckb_index), software-pipelined.  Per 16-row chunk
@@ -1746,46 +1708,6 @@ void launch_to_bf16(hipStream_t st, size_t n, const double* src, uint16_t* dst) 
   const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
   hipLaunchKernelGGL(to_bf16_kernel, dim3(grid), dim3(256), 0, st, n, src, dst);
 }
-bool block_two32_h_ok(int ks, size_t gso, size_t gs1, size_t gs2) {
-  return (ks == 32 || ks == 64) && std::max(std::max(gso, gs1), gs2) * 8 < ((size_t)1 << 32);
-}
-void launch_block_two32_h(hipStream_t st, const GroupTab& gt, int nblocks, const GroupPtrsH& m1, const Seg2& s1,
-                          const GroupPtrsH& m2, const Seg2& s2, double* out, size_t gso, const ProlongArgs& pa,
-                          bool pipe) {
-  if (nblocks <= 0 || gt.ng <= 0) return;
-  dim3 grid((nblocks + 3) / 4, 1, gt.ng), block(256);
-#define RICADI_TWO32(K, H, P)                                                                                         \
-  hipLaunchKernelGGL((block_two32_kernel<K, uint16_t, H, P>), grid, block, 0, st, gt, nblocks, pa.bmeta, pa.bm_stride, \
-                     pa.bm_in, m1, s1, m2, s2, out, gso, pa)
-#define RICADI_TWO32_H(K, P) \
-  if (s1.in16) RICADI_TWO32(K, true, P); else RICADI_TWO32(K, false, P)
-  if (pipe) { if (s2.kstride == 32) RICADI_TWO32_H(32, true); else RICADI_TWO32_H(64, true); }
-  else { if (s2.kstride == 32) RICADI_TWO32_H(32, false); else RICADI_TWO32_H(64, false); }
-#undef RICADI_TWO32_H
-#undef RICADI_TWO32
-}
-bool block_rect32_h_ok(int ks, size_t gsi, size_t gso, bool old32, bool out32) {
-  return (ks == 32 || ks == 64) && std::max(gsi, gso) * 8 < ((size_t)1 << 32) && !(old32 && !out32);
-}
-void launch_block_rect32_h(hipStream_t st, const GroupTab& gt, int ks, int nblocks, const GroupPtrsH& mats,
-                           const double* in, size_t gsi, double* out, size_t gso, int subtract, const ProlongArgs& pa) {
-  if (nblocks <= 0 || gt.ng <= 0) return;
-  const int nwaves = nblocks + (pa.aggof ? (pa.nextra + 31) / 32 : 0);
-  dim3 grid((nwaves + 3) / 4, 1, gt.ng), block(256);
-#define RICADI_RECT32(K, O)                                                                                         \
-  hipLaunchKernelGGL((block_rect32_kernel<K, uint16_t, O>), grid, block, 0, st, gt, nblocks, pa.bmeta, pa.bm_stride, \
-                     pa.bm_in, mats, in, gsi, out, gso, subtract, pa)
-  if (ks == 32) { if (pa.old32) RICADI_RECT32(32, true); else RICADI_RECT32(32, false); }
-  else { if (pa.old32) RICADI_RECT32(64, true); else RICADI_RECT32(64, false); }
-#undef RICADI_RECT32
-}
-void launch_pressure_step_h(hipStream_t st, const GroupTab& gt, int nblocks, const int* meta,
-                            const GroupPtrsH& inv, const int* jci, const double* jv, bool with_sy, const int* syci,
-                            const GroupPtrs& syv, const double* ec, size_t gse, const double* rp_, const _Float16* rp16,
-                            size_t gsr, double* out, size_t gso, const ProlongArgs& pa, const float* zv32, size_t gsz32) {
-  launch_pressure_step_b(st, gt, nblocks, meta, inv, jci, jv, (const double*)nullptr, 0, with_sy, syci, syv, ec, gse, rp_,
-                     rp16, gsr, out, gso, pa, zv32, gsz32);
-}
 
 // ---------------------------------------------------------------------------
 // Coloured Vanka sweep of a child level (ricadi_opts::child_smoother = 1).  A patch is a record of VANKA_K = 64
@@ -1929,7 +1851,22 @@ void launch_prolong_plain(hipStream_t st, const GroupTab& gt, int n, int m, cons
                      aggof, ec, gse, z, gsz);
 }
 
-// the preconditioner's operands stored in FP64 (GroupPtrs) or FP32 (GroupPtrsF)
+// the record-driven sweeps and the pressure step: blocks stored in FP64, FP32 or BF16
+#define RICADI_PRECOND_LAUNCHERS16(T)                                                                                 \
+  template void launch_block_two32(hipStream_t, const GroupTab&, int, const SweepRecs&, const GroupPtrsT<T>&,         \
+                                   const Seg2&, const GroupPtrsT<T>&, const Seg2&, double*, size_t,                   \
+                                   const ProlongArgs&, bool);                                                         \
+  template void launch_block_rect32(hipStream_t, const GroupTab&, int, int, const SweepRecs&, const GroupPtrsT<T>&,   \
+                                    const double*, size_t, double*, size_t, int, const ProlongArgs&);                 \
+  template void launch_pressure_step_b(hipStream_t, const GroupTab&, int, const int*, const GroupPtrsT<T>&,          \
+                                       const int*, const double*, const double*, size_t, bool, const int*,            \
+                                       const GroupPtrs&, const double*, size_t, const double*, const _Float16*,       \
+                                       size_t, double*, size_t, const ProlongArgs&, const float*, size_t);
+RICADI_PRECOND_LAUNCHERS16(double)
+RICADI_PRECOND_LAUNCHERS16(float)
+RICADI_PRECOND_LAUNCHERS16(uint16_t)
+#undef RICADI_PRECOND_LAUNCHERS16
+// the generic sweeps: FP64 (GroupPtrs) or FP32 (GroupPtrsF)
 #define RICADI_PRECOND_LAUNCHERS(T)                                                                                   \
   template void launch_block_apply_b(hipStream_t, const GroupTab&, int, int, const int*, const int*,                  \
                                      const GroupPtrsT<T>&, const double*, int, size_t, double*, int, size_t, int, int, \
@@ -1939,11 +1876,7 @@ void launch_prolong_plain(hipStream_t st, const GroupTab& gt, int n, int m, cons
                                           double*, int, size_t, int, int, const ProlongArgs&);                        \
   template void launch_block_apply2_b(hipStream_t, const GroupTab&, int, int, const int*, const int*,                 \
                                       const GroupPtrsT<T>&, const Seg2&, const GroupPtrsT<T>&, const Seg2&, double*,  \
-                                      int, size_t, int, const ProlongArgs&);                                          \
-  template void launch_pressure_step_b(hipStream_t, const GroupTab&, int, const int*, const GroupPtrsT<T>&,          \
-                                       const int*, const double*, const double*, size_t, bool, const int*,            \
-                                       const GroupPtrs&, const double*, size_t, const double*, const _Float16*,       \
-                                       size_t, double*, size_t, const ProlongArgs&, const float*, size_t);
+                                      int, size_t, int, const ProlongArgs&);
 RICADI_PRECOND_LAUNCHERS(double)
 RICADI_PRECOND_LAUNCHERS(float)
 #undef RICADI_PRECOND_LAUNCHERS

@@ -538,8 +538,7 @@ __global__ __launch_bounds__(256) void spmm_blocked_kernel(
   }
 #undef RICADI_TILE_STEP
 }
-size_t spmm_blocked_lds_bytes(int m, int max_cols, int max_nnz) {
-  (void)max_nnz;
+size_t spmm_blocked_lds_bytes(int m, int max_cols) {
   return (size_t)max_cols * m * sizeof(double) + 16;
 }
 void launch_spmm_blocked_b(hipStream_t st, const GroupTab& gt, int nblk, const int* rows2,
@@ -549,7 +548,7 @@ void launch_spmm_blocked_b(hipStream_t st, const GroupTab& gt, int nblk, const i
                            double beta_r, int m, int max_cols, const LowRankArgs& lr) {
   if (nblk <= 0 || gt.ng <= 0) return;
   const dim3 grid(nblk, 1, gt.ng), block(256);
-  const size_t lds = spmm_blocked_lds_bytes(m, max_cols, 0);
+  const size_t lds = spmm_blocked_lds_bytes(m, max_cols);
 #define RICADI_TILE_LAUNCH(R, L)                                                                  \
   hipLaunchKernelGGL((spmm_blocked_kernel<R, L>), grid, block, lds, st, rows2, rp2, cols2, lidx, gt, \
                      vals, x, ldx, gsx, y, ldy, gsy, r, ldr, gsr, alpha, beta_r, m, max_cols, lr, (float*)nullptr)
@@ -574,7 +573,7 @@ void launch_spmm_blocked_x32(hipStream_t st, const GroupTab& gt, int nblk, const
                              size_t gsx, double* y, int ldy, size_t gsy, double alpha, int m, int max_cols, float* y32) {
   if (nblk <= 0 || gt.ng <= 0) return;
   const dim3 grid(nblk, 1, gt.ng), block(256);
-  const size_t lds = spmm_blocked_lds_bytes(m, max_cols, 0);
+  const size_t lds = spmm_blocked_lds_bytes(m, max_cols);
   if (f4_fill_ok(x, m, ldx, gsx))
     hipLaunchKernelGGL((spmm_blocked_kernel<false, false, float, true>), grid, block, lds, st, rows2, rp2, cols2, lidx,
                        gt, vals, x, ldx, gsx, y, ldy, gsy, (const double*)nullptr, 0, (size_t)0, alpha, 0.0, m,
@@ -805,27 +804,37 @@ __global__ __launch_bounds__(256) void spmm_blocked_ms_kernel(
 #undef RICADI_MS_STEP
 }
 size_t spmm_blocked_ms_lds_bytes(int max_cols) { return (size_t)2 * max_cols * 16 * sizeof(double) + 16; }
+// What both multi-shift launchers pass besides the panels: the shifts' coefficients by value, and the grid -- enough
+// workgroups for ~4 per CU (1024): the groups are split over grid.y when the row blocks alone do not fill the chip
+struct MsLaunch {
+  GroupCoefs cf;
+  dim3 grid;
+};
+static MsLaunch ms_launch(const GroupTab& gt, const double* alphas, const double* betas, int nblk) {
+  MsLaunch l;
+  for (int i = 0; i < RICADI_MAX_GROUPS; ++i) {
+    l.cf.alpha[i] = alphas[i];
+    l.cf.beta[i] = betas[i];
+  }
+  int ysplit = 1;
+  while (ysplit < gt.ng && (long)nblk * ysplit < 900 && ysplit < 8) ysplit *= 2;
+  l.grid = dim3(nblk, std::min(ysplit, gt.ng), 1);
+  return l;
+}
 void launch_spmm_blocked_ms_x32(hipStream_t st, const GroupTab& gt, const double* alphas, const double* betas,
                                 int nblk, const int* rows2, const int* rp2, const int* cols2, const uint16_t* lidx,
                                 const double* vAJ, const double* vE, const float* x, int ldx, size_t gsx, double* y,
                                 int ldy, size_t gsy, double alpha, int m, int max_cols, float* y32) {
   if (nblk <= 0 || gt.ng <= 0) return;
-  GroupCoefs cf;
-  for (int i = 0; i < RICADI_MAX_GROUPS; ++i) {
-    cf.alpha[i] = alphas[i];
-    cf.beta[i] = betas[i];
-  }
-  int ysplit = 1;
-  while (ysplit < gt.ng && (long)nblk * ysplit < 900 && ysplit < 8) ysplit *= 2;
-  ysplit = std::min(ysplit, gt.ng);
-  const dim3 grid(nblk, ysplit, 1), block(256);
+  const MsLaunch l = ms_launch(gt, alphas, betas, nblk);
+  const dim3 block(256);
   if (f4_fill_ok(x, m, ldx, gsx) && max_cols <= 192)
-    hipLaunchKernelGGL((spmm_blocked_ms_kernel<false, float, true>), grid, block, spmm_blocked_ms_lds_bytes(max_cols), st,
-                       rows2, rp2, cols2, lidx, gt, cf, vAJ, vE, x, ldx, gsx, y, ldy, gsy, (const double*)nullptr, 0,
+    hipLaunchKernelGGL((spmm_blocked_ms_kernel<false, float, true>), l.grid, block, spmm_blocked_ms_lds_bytes(max_cols), st,
+                       rows2, rp2, cols2, lidx, gt, l.cf, vAJ, vE, x, ldx, gsx, y, ldy, gsy, (const double*)nullptr, 0,
                        (size_t)0, alpha, 0.0, m, max_cols, y32);
   else
-    hipLaunchKernelGGL((spmm_blocked_ms_kernel<false, float, false>), grid, block, spmm_blocked_ms_lds_bytes(max_cols), st,
-                       rows2, rp2, cols2, lidx, gt, cf, vAJ, vE, x, ldx, gsx, y, ldy, gsy, (const double*)nullptr, 0,
+    hipLaunchKernelGGL((spmm_blocked_ms_kernel<false, float, false>), l.grid, block, spmm_blocked_ms_lds_bytes(max_cols), st,
+                       rows2, rp2, cols2, lidx, gt, l.cf, vAJ, vE, x, ldx, gsx, y, ldy, gsy, (const double*)nullptr, 0,
                        (size_t)0, alpha, 0.0, m, max_cols, y32);
 }
 // max_cols <= 160 (tile slots per thread: 16 x XP x XJ), m <= 16, panel offsets in 31 bits
@@ -839,26 +848,15 @@ void launch_spmm_blocked_ms(hipStream_t st, const GroupTab& gt, const double* al
                             const double* r, int ldr, size_t gsr, double alpha, double beta_r, int m,
                             int max_cols) {
   if (nblk <= 0 || gt.ng <= 0) return;
-  GroupCoefs cf;
-  for (int i = 0; i < RICADI_MAX_GROUPS; ++i) {
-    cf.alpha[i] = alphas[i];
-    cf.beta[i] = betas[i];
-  }
-  // enough workgroups for ~4 per CU (1024): split the groups over grid.y when the row
-  // blocks alone do not fill the chip
-  int ysplit = 1;
-  while (ysplit < gt.ng && (long)nblk * ysplit < 900 && ysplit < 8) ysplit *= 2;
-  static const int ys_env = 0;
-  if (ys_env > 0) ysplit = ys_env;
-  ysplit = std::min(ysplit, gt.ng);
-  const dim3 grid(nblk, ysplit, 1), block(256);
+  const MsLaunch l = ms_launch(gt, alphas, betas, nblk);
+  const dim3 block(256);
   const size_t lds = spmm_blocked_ms_lds_bytes(max_cols);
   if (r)
-    hipLaunchKernelGGL((spmm_blocked_ms_kernel<true>), grid, block, lds, st, rows2, rp2, cols2, lidx, gt,
-                       cf, vAJ, vE, x, ldx, gsx, y, ldy, gsy, r, ldr, gsr, alpha, beta_r, m, max_cols, (float*)nullptr);
+    hipLaunchKernelGGL((spmm_blocked_ms_kernel<true>), l.grid, block, lds, st, rows2, rp2, cols2, lidx, gt,
+                       l.cf, vAJ, vE, x, ldx, gsx, y, ldy, gsy, r, ldr, gsr, alpha, beta_r, m, max_cols, (float*)nullptr);
   else
-    hipLaunchKernelGGL((spmm_blocked_ms_kernel<false>), grid, block, lds, st, rows2, rp2, cols2, lidx, gt,
-                       cf, vAJ, vE, x, ldx, gsx, y, ldy, gsy, r, ldr, gsr, alpha, beta_r, m, max_cols, (float*)nullptr);
+    hipLaunchKernelGGL((spmm_blocked_ms_kernel<false>), l.grid, block, lds, st, rows2, rp2, cols2, lidx, gt,
+                       l.cf, vAJ, vE, x, ldx, gsx, y, ldy, gsy, r, ldr, gsr, alpha, beta_r, m, max_cols, (float*)nullptr);
 }
 
 // dst[k] = src[perm[k]]  (assembled CSR values -> block order)

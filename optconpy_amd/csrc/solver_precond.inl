@@ -5,6 +5,18 @@
 // The shifts of one batched solve: per group id the shift-dependent operands, and
 // the table of groups a launch works on (ricadi_internal.h).  All workspace
 // buffers are group-major with the strides below.
+// A per-shift block operand of the preconditioner as stored: its pointer table in every precision (null where a shift
+// has no copy in it)
+struct BlockOperand {
+  GroupPtrs d = {};
+  GroupPtrsF f = {};
+  GroupPtrsH h = {};    // BF16
+  void set(int g, const double* pd, const float* pf, const uint16_t* ph = nullptr) {
+    d.p[g] = pd;
+    f.p[g] = pf;
+    h.p[g] = ph;
+  }
+};
 static GroupTab all_groups(int G) {
   GroupTab t{};
   t.ng = G;
@@ -16,14 +28,11 @@ struct Batch {
   int m = 0;                 // panel width of every group
   GroupTab tab;              // groups the next launches act on
   double alpha[RICADI_MAX_GROUPS], beta[RICADI_MAX_GROUPS];   // shift of every group id
-  GroupPtrs sval, svalb, syval, syvalb, bvinv, bpinv, einv;
-  GroupPtrsF bvinvf, bpinvf, einvf;
-  GroupPtrs gtm, adym;
-  GroupPtrsF gtmf, adymf;
-  GroupPtrsH bvinvh, bpinvh, gtmh, adymh;     // BF16 copies (null where a shift has none)
-  GroupPtrs vkinv;                            // patch inverses of the coloured Vanka sweep (a child level's batch)
-  GroupPtrsF vkinvf;
-  bool blocks16 = false;                       // every group of the batch has them
+  GroupPtrs sval = {}, svalb = {}, syval = {}, syvalb = {};
+  BlockOperand bvinv, bpinv, gtm, adym;       // blocks of the sweeps
+  BlockOperand einv;                          // the last level's dense inverse (no BF16 copy)
+  BlockOperand vkinv;                         // patch inverses of the coloured Vanka sweep (a child level's batch)
+  bool blocks16 = false;                      // every group of the batch has the BF16 copies of the sweeps' blocks
   size_t gs = 0, gsp = 0, gsc = 0, gsq = 0;   // strides: n*m, np*m, kc*m, q*m
   std::shared_ptr<Batch> sub;                 // the same groups on the child level
   hipStream_t st = nullptr;                   // stream of every launch for the batch (make_batch: the context's)
@@ -48,39 +57,23 @@ static Batch make_batch(ricadi_ctx* c, ShiftData* const* sds, int G, int m) {
   bt.G = G;
   bt.m = m;
   bt.tab = GroupTab{};
-  bt.sval = bt.svalb = bt.syval = bt.syvalb = bt.bvinv = bt.bpinv = bt.einv = same_ptr((const double*)nullptr);
-  bt.bvinvf = bt.bpinvf = bt.einvf = same_ptr((const float*)nullptr);
-  bt.gtm = bt.adym = same_ptr((const double*)nullptr);
-  bt.gtmf = bt.adymf = same_ptr((const float*)nullptr);
-  bt.bvinvh = bt.bpinvh = bt.gtmh = bt.adymh = same_ptr((const uint16_t*)nullptr);
-  bt.vkinv = same_ptr((const double*)nullptr);
-  bt.vkinvf = same_ptr((const float*)nullptr);
   bt.blocks16 = c->sw.blocks16 && G > 0;
   for (int g = 0; g < RICADI_MAX_GROUPS; ++g) bt.alpha[g] = bt.beta[g] = 0.0;
   for (int g = 0; g < G; ++g) {
-    bt.alpha[g] = sds[g]->alpha;
-    bt.beta[g] = sds[g]->beta;
-    bt.bvinvf.p[g] = sds[g]->bvinvf.p;
-    bt.bpinvf.p[g] = sds[g]->bpinvf.p;
-    bt.einvf.p[g] = sds[g]->einvf.p;
-    bt.bvinvh.p[g] = sds[g]->bvinvh.p;
-    bt.bpinvh.p[g] = sds[g]->bpinvh.p;
-    bt.gtmh.p[g] = sds[g]->gtmh.p;
-    bt.adymh.p[g] = sds[g]->adymh.p;
-    if (!sds[g]->bvinvh.p || !sds[g]->bpinvh.p || !sds[g]->gtmh.p || !sds[g]->adymh.p) bt.blocks16 = false;
-    bt.gtm.p[g] = sds[g]->gtm.p;
-    bt.gtmf.p[g] = sds[g]->gtmf.p;
-    bt.adym.p[g] = sds[g]->adym.p;
-    bt.adymf.p[g] = sds[g]->adymf.p;
-    bt.sval.p[g] = sds[g]->sval.p;
-    bt.syval.p[g] = sds[g]->syval.p;
-    bt.syvalb.p[g] = sds[g]->syvalb.p;
-    bt.svalb.p[g] = sds[g]->svalb.p;
-    bt.bvinv.p[g] = sds[g]->bvinv.p;
-    bt.bpinv.p[g] = sds[g]->bpinv.p;
-    bt.einv.p[g] = sds[g]->einv.p;
-    bt.vkinv.p[g] = sds[g]->vkinv.p;
-    bt.vkinvf.p[g] = sds[g]->vkinvf.p;
+    const ShiftData& s = *sds[g];
+    bt.alpha[g] = s.alpha;
+    bt.beta[g] = s.beta;
+    bt.sval.p[g] = s.sval.p;
+    bt.svalb.p[g] = s.svalb.p;
+    bt.syval.p[g] = s.syval.p;
+    bt.syvalb.p[g] = s.syvalb.p;
+    bt.bvinv.set(g, s.bvinv.p, s.bvinvf.p, s.bvinvh.p);
+    bt.bpinv.set(g, s.bpinv.p, s.bpinvf.p, s.bpinvh.p);
+    bt.gtm.set(g, s.gtm.p, s.gtmf.p, s.gtmh.p);
+    bt.adym.set(g, s.adym.p, s.adymf.p, s.adymh.p);
+    bt.einv.set(g, s.einv.p, s.einvf.p);
+    bt.vkinv.set(g, s.vkinv.p, s.vkinvf.p);
+    if (!s.bvinvh.p || !s.bpinvh.p || !s.gtmh.p || !s.adymh.p) bt.blocks16 = false;
   }
   bt.gs = (size_t)c->n * m;
   bt.gsp = (size_t)c->np * m;
@@ -117,7 +110,7 @@ static bool ms_pays(const ricadi_ctx* c, int ng, size_t nnz) {
 // The LDS-tiled kernels serve panels of width m (else the CSR kernel runs)
 static bool saddle_tiled(const ricadi_ctx* c, int m) {
   return c->sb_ok &&
-         spmm_blocked_lds_bytes(m, c->sb_max_cols, c->sb_max_nnz) <= (size_t)40 * 1024;
+         spmm_blocked_lds_bytes(m, c->sb_max_cols) <= (size_t)40 * 1024;
 }
 // x32 (optional): FP32 copy of x with the same leading dimension and group stride; the tiled kernels read it
 // instead of x (plain products only: no residual term, no low-rank epilogue, no prolongation map)
@@ -179,6 +172,17 @@ static void op_apply(ricadi_ctx* c, const Batch& bt, const double* x, size_t gsx
   const LowRankArgs lr = lowrank ? lowrank_args(c, bt, x, gsx) : LowRankArgs();
   saddle_spmm(c, bt, x, gsx, nullptr, y, bt.gs, nullptr, 0, 1.0, 0.0, lr, x32, y32);
 }
+// fn(tables ...) with the tables of the operands ops in the precision a stage reads its blocks in: the level's (FP32,
+// or FP64 with RICADI_PRECOND64=1); H: a stage whose launcher also takes BF16 blocks reads those where the cycle form
+// puts it on them (b16)
+template <bool H = false, class Fn, class... Op>
+static void with_stored(const ricadi_ctx* c, bool b16, Fn&& fn, const Op&... ops) {
+  if constexpr (H) {
+    if (b16) return fn(ops.h...);
+  }
+  if (c->precond32) fn(ops.f...);
+  else fn(ops.d...);
+}
 // ---- kernels of the preconditioner that ricadi_time_kernel_dev also launches on their own
 // block-Jacobi sweep over the velocity (or pressure) blocks:  out[rows_b] (-)= inv_b in[rows_b]  (+ epilogue pa / cin)
 static void block_sweep(ricadi_ctx* c, const Batch& bt, bool pressure, const double* in, size_t gsi, double* out,
@@ -186,11 +190,18 @@ static void block_sweep(ricadi_ctx* c, const Batch& bt, bool pressure, const dou
   const int nb = pressure ? c->nbp : c->nbv, m = bt.m;
   const int* bptr = pressure ? c->bp_ptr.p : c->bv_ptr.p;
   const int* rows = pressure ? c->bp_rows.p : c->bv_rows.p;
-  auto sweep = [&](const auto& inv) {
-    launch_block_apply_b(bt.st, bt.tab, c->bs, nb, bptr, rows, inv, in, m, gsi, out, m, bt.gs, m, subtract, pa, cin);
-  };
-  if (c->precond32) sweep(pressure ? bt.bpinvf : bt.bvinvf);
-  else sweep(pressure ? bt.bpinv : bt.bvinv);
+  // Plain panel input, 32 x 32 blocks, a latency-bound launch (few waves: the Schur sweep of cfg2 has 110 blocks x 16
+  // groups): the rectangle kernel with the block's own rows as its input list -- its loads are issued in groups, the
+  // plain kernel's index -> gather pairs are a chain of dependent round trips.  With many waves the rectangle kernel's
+  // 152 VGPRs cost more than its grouped loads gain (velocity-sized sweep at cfg2: 43 vs 33 us).
+  const bool as_rect = !cin.rp && c->bs == 32 && (long)nb * bt.tab.ng <= 8192;
+  with_stored(c, false, [&](const auto& inv) {
+    if (as_rect)
+      launch_block_apply_rect_b(bt.st, bt.tab, 32, 32, nb, bptr, rows, bptr, rows, inv, in, m, gsi, out, m, bt.gs, m,
+                                subtract, pa);
+    else
+      launch_block_apply_b(bt.st, bt.tab, c->bs, nb, bptr, rows, inv, in, m, gsi, out, m, bt.gs, m, subtract, pa, cin);
+  }, pressure ? bt.bpinv : bt.bvinv);
 }
 // r2 = r - (S Y) ec through the tile kernels (c->syb_ok): the multi-shift one where it pays
 static bool sy_tiled_ms(const ricadi_ctx* c, const Batch& bt) {
@@ -227,29 +238,35 @@ struct CycleForm {
   enum Coarse { CO_NONE, CO_CHILD, CO_DENSE_KB, CO_DENSE } coarse = CO_NONE;
   // r2 = r - (S Y) ec before the sweeps: its pressure rows (folded cycle, split pressure step) or all of it (unfolded)
   enum SyResidual { SY_NONE, SY_PROWS, SY_FULL } sy = SY_NONE;
-  // first velocity sweep: plain on r2, two-term with the coarse residual folded in, or that on BF16 blocks (pipe:
-  // its second segment's loads in flight behind the first segment's MFMAs)
+  // first velocity sweep: plain on r2; two-term with the coarse residual folded in, by the generic kernel or the
+  // record-driven one (pipe: on BF16 blocks, its second segment's loads in flight behind the first segment's MFMAs)
   enum First { FS_PLAIN, FS_TWO_TERM, FS_TWO32, FS_TWO32_PIPE, FS_NONE } first = FS_PLAIN;
   // pressure step: one launch (K2p) on BF16 / FP32-or-FP64 blocks, or J product and Schur sweep on their own
   enum Pressure { PS_NONE, PS_FUSED16, PS_FUSED, PS_SPLIT } pressure = PS_NONE;
-  // last velocity sweep: dense rectangles on BF16 / FP32-or-FP64 blocks, or the J^T product formed row by row
+  // last velocity sweep: dense rectangles by the record-driven / the generic kernel, or the J^T product formed row by
+  // row
   enum Last { LS_NONE, LS_RECT32, LS_RECT, LS_CSR_IN } last = LS_NONE;
   bool h16 = false;     // the input is read from the FP16-stored vector
   bool x32 = false;     // only the FP32 copy of z is wanted (the operator reads it)
   bool mid32 = false;   // the velocity part between the sweeps as an FP32 panel
-  bool b16 = false;     // BF16-stored per-shift blocks
+  bool b16 = false;     // BF16-stored per-shift blocks: read by the pressure step and the record-driven sweeps
   bool folded = false;  // the coarse residual is formed inside the first sweep and the pressure step
   // a child level's coloured Vanka sweep in place of the SIMPLE sweeps: z = Y ec, then per colour the residual of the
   // level's operator and the patch kernel (pc_vanka); first = FS_NONE, no pressure step, no last sweep
   bool vanka = false;
   int two_ks = 0, rect_ks = 0;   // padded widths of the two-term sweep's second block / of the rectangles (0: none)
-  // the form word of include/ricadi.h (restriction and last: their values are the 2-bit codes)
+  // the sweeps that read BF16 blocks (a record-driven kernel runs on the level's FP32 / FP64 blocks as well)
+  bool first16() const { return b16 && (first == FS_TWO32 || first == FS_TWO32_PIPE); }
+  bool last16() const { return b16 && last == LS_RECT32; }
+  // the form word of include/ricadi.h (restriction: its value is the 2-bit code; first and last: 1 = on BF16 blocks,
+  // 2 = on FP32 / FP64 blocks by either kernel)
   unsigned word() const {
     unsigned w = (h16 ? RICADI_PCF_H16 : 0) | (x32 ? RICADI_PCF_X32 : 0) | (mid32 ? RICADI_PCF_MID32 : 0) |
                  (b16 ? RICADI_PCF_B16 : 0) | (folded ? RICADI_PCF_FOLDED : 0) | (vanka ? RICADI_PCF_VANKA : 0);
-    w |= (unsigned)restriction << RICADI_PCF_RESTRICT_SHIFT | (unsigned)last << RICADI_PCF_LAST_SHIFT;
+    w |= (unsigned)restriction << RICADI_PCF_RESTRICT_SHIFT;
+    w |= (last == LS_NONE ? 0u : last == LS_CSR_IN ? 3u : last16() ? 1u : 2u) << RICADI_PCF_LAST_SHIFT;
     if (coarse != CO_NONE) w |= (coarse == CO_CHILD ? 1u : 2u) << RICADI_PCF_COARSE_SHIFT;
-    w |= (first == FS_NONE ? 0u : first == FS_PLAIN ? 3u : first == FS_TWO_TERM ? 2u : 1u) << RICADI_PCF_FIRST_SHIFT;
+    w |= (first == FS_NONE ? 0u : first == FS_PLAIN ? 3u : first16() ? 1u : 2u) << RICADI_PCF_FIRST_SHIFT;
     if (pressure != PS_NONE) w |= pressure == PS_SPLIT ? RICADI_PCF_PSPLIT : RICADI_PCF_PFUSED;
     return w | (unsigned)two_ks << RICADI_PCF_TWO_KS_SHIFT | (unsigned)rect_ks << RICADI_PCF_RECT_KS_SHIFT;
   }
@@ -284,7 +301,8 @@ static CycleForm cycle_form(const ricadi_ctx* c, int m, bool blocks16, size_t gs
   // inverses and the FP32-stored Z_j already do.
   f.mid32 = c->sw.mid32 && out32 && fusedp && f.folded && c->gt_ok && c->precond32;
   // ... and on BF16-stored blocks where every shift of the batch has them (record-driven sweeps only)
-  f.b16 = f.mid32 && blocks16 && c->sw_stride > 0 && c->bs == 32;
+  const bool recs = c->sw_stride > 0;   // the level has the sweeps' fixed-stride records
+  f.b16 = f.mid32 && blocks16 && recs && c->bs == 32;
   if (c->kc > 0) {
     const bool rowwave = m == 16 && c->sw.rowwave && spmm_rowwave_pays(c->kc, c->sa ? c->pt_ci.n : (size_t)c->n);
     f.restriction = rowwave ? f.RS_ROWWAVE : f.h16 ? f.RS_CSR16 : f.RS_CSR64;
@@ -294,14 +312,16 @@ static CycleForm cycle_form(const ricadi_ctx* c, int m, bool blocks16, size_t gs
   }
   if (f.folded) {
     f.two_ks = c->ady_ks;
-    f.first = !(f.b16 && block_two32_h_ok(c->ady_ks, gs, gsr, (size_t)c->kc * m)) ? f.FS_TWO_TERM
-              : c->sw.coarse_pipe ? f.FS_TWO32_PIPE : f.FS_TWO32;
+    // (the sweep adds no coarse part: the last sweep does)
+    f.first = !block_two32_ok(c->bs, m, c->ady_ks, recs, false, gs, gsr, (size_t)c->kc * m) ? f.FS_TWO_TERM
+              : f.b16 && c->sw.coarse_pipe ? f.FS_TWO32_PIPE : f.FS_TWO32;
   }
   if (c->np > 0) {
     f.pressure = !fusedp ? f.PS_SPLIT : f.b16 ? f.PS_FUSED16 : f.PS_FUSED;
     f.rect_ks = c->gt_ok ? c->gt_ks : 0;
     f.last = !c->gt_ok ? f.LS_CSR_IN
-             : f.b16 && block_rect32_h_ok(c->gt_ks, (size_t)c->np * m, gs, f.mid32, out32) ? f.LS_RECT32 : f.LS_RECT;
+             : block_rect32_ok(c->bs, m, c->gt_ks, recs, (size_t)c->np * m, gs, f.mid32, out32) ? f.LS_RECT32
+                                                                                                : f.LS_RECT;
   }
   return f;
 }
@@ -329,14 +349,10 @@ static ProlongArgs prolongation(const ricadi_ctx* c, const Batch& bt) {
   }
   return pa;
 }
-// the fixed-stride records of the velocity sweeps, where there are
-static void sweep_records(const ricadi_ctx* c, int in, int ni, ProlongArgs& pa) {
-  if (c->sw_stride > 0 && c->bs == 32) {
-    pa.bmeta = c->sw_meta.p;
-    pa.bm_stride = c->sw_stride;
-    pa.bm_in = in;
-    pa.bm_ni = ni;
-  }
+// the fixed-stride records of the velocity sweeps (of a level that has them: the form says so) with the input list at
+// in_off
+static SweepRecs sweep_records(const ricadi_ctx* c, int in_off) {
+  return SweepRecs{c->sw_meta.p, c->sw_stride, in_off};
 }
 static void precond_apply(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io);
 
@@ -366,11 +382,11 @@ static void pc_coarse(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const 
     precond_apply(ch, cb, cycle_form(ch, cb.m, cb.blocks16, bt.gsc, false, false),
                   CycleIO{c->rc.p, bt.gsc, nullptr, c->ec.p});
   } else if (f.coarse == f.CO_DENSE_KB) {
-    launch_dense_apply_kb(bt.st, bt.tab, c->kc, bt.einvf, c->rc.p, c->ec.p);
-  } else if (f.coarse == f.CO_DENSE && c->precond32) {
-    launch_dense_apply_b(bt.st, bt.tab, c->kc, bt.m, bt.einvf, (c->kc + 3) & ~3, c->rc.p, c->ec.p);
+    launch_dense_apply_kb(bt.st, bt.tab, c->kc, bt.einv.f, c->rc.p, c->ec.p);
   } else if (f.coarse == f.CO_DENSE) {
-    launch_dense_apply_b(bt.st, bt.tab, c->kc, bt.m, bt.einv, c->rc.p, c->ec.p);
+    with_stored(c, false, [&](const auto& einv) {
+      launch_dense_apply_b(bt.st, bt.tab, c->kc, bt.m, einv, c->rc.p, c->ec.p);
+    }, bt.einv);
   }
 }
 static void pc_sy_prows(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
@@ -393,7 +409,7 @@ static void pc_sy_prows(ricadi_ctx* c, const Batch& bt, const CycleForm& f, cons
     // velocity sweep instead, like the J^T product below, was measured slower: 249 vs
     // 257 shift-solves/s -- 8 rows x 7.6 dependent gathers per lane.)
     // Tile form: the aggregates a row block touches (a few dozen coarse rows) go to LDS once.
-    if (c->syb_ok && (sy_tiled_ms(c, bt) || spmm_blocked_lds_bytes(m, c->syb_max_cols, 0) <= (size_t)40 * 1024))
+    if (c->syb_ok && (sy_tiled_ms(c, bt) || spmm_blocked_lds_bytes(m, c->syb_max_cols) <= (size_t)40 * 1024))
       sy_residual_tiled(c, bt, io.r, io.gsr);
     else
       launch_spmm_b(st, bt.tab, c->n, c->sy_rp.p, c->sy_ci.p, bt.syval, c->ec.p, m, bt.gsc, nullptr, c->r2.p, m,
@@ -428,16 +444,16 @@ static void pc_two_term(ricadi_ctx* c, const Batch& bt, const CycleForm& f, cons
     pa.gs32 = io.gs32;
     pa.only32 = 1;
   }
-  sweep_records(c, c->sw_in_two, 2, pa);
-  if (f.first == f.FS_TWO32 || f.first == f.FS_TWO32_PIPE)
-    launch_block_two32_h(bt.st, bt.tab, c->nbv, bt.bvinvh, s1, bt.adymh, s2, io.z, bt.gs, pa,
-                         f.first == f.FS_TWO32_PIPE);
-  else if (c->precond32)
-    launch_block_apply2_b(bt.st, bt.tab, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinvf, s1, bt.adymf, s2, io.z,
-                          m, bt.gs, m, pa);
+  if (f.first == f.FS_TWO_TERM)
+    with_stored(c, false, [&](const auto& m1, const auto& m2) {
+      launch_block_apply2_b(bt.st, bt.tab, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, m1, s1, m2, s2, io.z, m, bt.gs, m,
+                            pa);
+    }, bt.bvinv, bt.adym);
   else
-    launch_block_apply2_b(bt.st, bt.tab, c->bs, c->nbv, c->bv_ptr.p, c->bv_rows.p, bt.bvinv, s1, bt.adym, s2, io.z,
-                          m, bt.gs, m, pa);
+    with_stored<true>(c, f.first16(), [&](const auto& m1, const auto& m2) {
+      launch_block_two32(bt.st, bt.tab, c->nbv, sweep_records(c, c->sw_in_two), m1, s1, m2, s2, io.z, bt.gs, pa,
+                         f.first == f.FS_TWO32_PIPE);
+    }, bt.bvinv, bt.adym);
 }
 // t = J z_v - r_p (r_p of r2, or of r without a coarse level)
 static void pc_jprod(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {
@@ -478,16 +494,12 @@ static void pc_schur(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const C
   const double* rp64 = io.r16 ? nullptr : (r2 ? c->r2.p : io.r) + off;
   const _Float16* rp16 = io.r16 ? io.r16 + off : nullptr;
   const size_t gsrp = r2 ? bt.gs : io.gsr;
-  if (f.pressure == f.PS_FUSED16)
-    launch_pressure_step_h(bt.st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinvh, c->J.ci.p, c->J.v.p, sy, c->sy_ci.p,
-                           bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, pa, io.z32, io.gs32);
-  else if (c->precond32)
-    launch_pressure_step_b(bt.st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinvf, c->J.ci.p, c->J.v.p, io.z, bt.gs, sy,
-                           c->sy_ci.p, bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, pa,
-                           f.mid32 ? io.z32 : nullptr, io.gs32);
-  else
-    launch_pressure_step_b(bt.st, bt.tab, c->nbp, c->ps_meta.p, bt.bpinv, c->J.ci.p, c->J.v.p, io.z, bt.gs, sy,
-                           c->sy_ci.p, bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, pa);
+  // z_v: the FP32 panel where the first sweep left that (mid32; BF16 blocks come with it), else the rows of z
+  with_stored<true>(c, f.pressure == f.PS_FUSED16, [&](const auto& inv) {
+    launch_pressure_step_b(bt.st, bt.tab, c->nbp, c->ps_meta.p, inv, c->J.ci.p, c->J.v.p, io.z, bt.gs, sy, c->sy_ci.p,
+                           bt.syval, c->ec.p, bt.gsc, rp64, rp16, gsrp, zp, bt.gs, pa, f.mid32 ? io.z32 : nullptr,
+                           io.gs32);
+  }, bt.bpinv);
 }
 // z_v -= Ahat^-1 (J^T z_p): the same block-Jacobi inverse as in the Schur blocks; the
 // J^T product is formed inside the sweep, row by row as the blocks gather them
@@ -514,15 +526,16 @@ static void pc_rect(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const Cy
   pa.gs32 = io.gs32;
   pa.only32 = f.x32;
   pa.old32 = f.mid32 ? 1 : 0;
-  sweep_records(c, c->sw_in_rect, 1, pa);
   if (f.last == f.LS_RECT32)
-    launch_block_rect32_h(bt.st, bt.tab, c->gt_ks, c->nbv, bt.gtmh, c->tp.p, bt.gsp, io.z, bt.gs, 1, pa);
-  else if (c->precond32)
-    launch_block_apply_rect_b(bt.st, bt.tab, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
-                              c->gt_cols.p, bt.gtmf, c->tp.p, m, bt.gsp, io.z, m, bt.gs, m, 1, pa);
+    with_stored<true>(c, f.last16(), [&](const auto& g) {
+      launch_block_rect32(bt.st, bt.tab, c->gt_ks, c->nbv, sweep_records(c, c->sw_in_rect), g, c->tp.p, bt.gsp, io.z,
+                          bt.gs, 1, pa);
+    }, bt.gtm);
   else
-    launch_block_apply_rect_b(bt.st, bt.tab, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
-                              c->gt_cols.p, bt.gtm, c->tp.p, m, bt.gsp, io.z, m, bt.gs, m, 1, pa);
+    with_stored(c, false, [&](const auto& g) {
+      launch_block_apply_rect_b(bt.st, bt.tab, c->bs, c->gt_ks, c->nbv, c->bv_ptr.p, c->bv_rows.p, c->gt_ptr.p,
+                                c->gt_cols.p, g, c->tp.p, m, bt.gsp, io.z, m, bt.gs, m, 1, pa);
+    }, bt.gtm);
 }
 // The coloured Vanka sweep of a child level (CycleForm::vanka), colour after colour on the iterate as it stood
 // before the colour:  rho = r - S z (the level's saddle product in its residual form, tiled or CSR as the level
@@ -534,10 +547,9 @@ static void vanka_colours(ricadi_ctx* c, const Batch& bt, const CycleIO& io) {
   for (int col = 0; col < c->vk.ncolours; ++col) {
     const int p0 = c->vk.colour_ptr[col], cnt = c->vk.colour_ptr[col + 1] - p0;
     saddle_spmm(c, bt, io.z, bt.gs, nullptr, c->r2.p, bt.gs, io.r, io.gsr, -1.0, 1.0);
-    if (c->precond32)
-      launch_vanka_patch(bt.st, bt.tab, p0, cnt, c->vk_idx.p, bt.vkinvf, c->r2.p, bt.gs, io.z, bt.gs, bt.m, omega);
-    else
-      launch_vanka_patch(bt.st, bt.tab, p0, cnt, c->vk_idx.p, bt.vkinv, c->r2.p, bt.gs, io.z, bt.gs, bt.m, omega);
+    with_stored(c, false, [&](const auto& inv) {
+      launch_vanka_patch(bt.st, bt.tab, p0, cnt, c->vk_idx.p, inv, c->r2.p, bt.gs, io.z, bt.gs, bt.m, omega);
+    }, bt.vkinv);
   }
 }
 static void pc_vanka(ricadi_ctx* c, const Batch& bt, const CycleForm& f, const CycleIO& io) {

@@ -94,7 +94,7 @@ static void stable_alloc(DArr<T>& a, size_t n) {
 
 // In-place inverses of nb (<= gj_max_batch()) dense k x k matrices (row-major, device pointers in hmats) by
 // block Gauss-Jordan elimination without pivoting: per 128-row block three small kernels and two batched
-// rocBLAS GEMMs (ricadi_kernels.hip).  A diagonal block with a vanishing pivot raises *gjflag (the matrices are
+// rocBLAS GEMMs (ricadi_precond.hip).  A diagonal block with a vanishing pivot raises *gjflag (the matrices are
 // garbage then; the caller assembles them again and takes the pivoted rocSOLVER route).  No host
 // synchronisation: the pointer arrays go up from hptrs (pinned, read by the copy when the stream reaches it) to
 // dptrs; the caller has sized the gj_* panels for the batch.

@@ -13,6 +13,8 @@
 //     matrix row and its lanes own the panel columns g, g+16, ...;
 //   * reductions over rows are two-stage (per-workgroup partials, then a small
 //     reduce kernel), so results are bitwise reproducible run to run.
+#include <stdexcept>
+
 #include "ricadi_device.h"
 
 namespace ricadi {
@@ -29,28 +31,18 @@ namespace ricadi {
 // ---------------------------------------------------------------------------
 constexpr int DOT_ROWS = 64;
 
+// the dot phase on a staged chunk: wl holds nr rows of m doubles (the chunk starts at element `base` of every basis
+// vector); pout[i * m + c], i < nvec (and row nvec = the chunk's own column norms squared, if want_self)
 template <class BT>
-__global__ __launch_bounds__(256) void cols_dots_kernel(
-    GroupTab gt, int nrows, int m, int nvec, const BT* __restrict__ basis, size_t vstride,
-    size_t gsb, const double* __restrict__ w, size_t gsw, int want_self,
-    double* __restrict__ partial, size_t gsp) {
-  extern __shared__ double wl[];  // DOT_ROWS x m
-  const int grp = gt.gid[blockIdx.z];
-  basis += (size_t)grp * gsb;
-  w += (size_t)grp * gsw;
-  partial += (size_t)grp * gsp;
-  const int r0 = blockIdx.x * DOT_ROWS;
-  const int nr = min(DOT_ROWS, nrows - r0);
-  for (int e = threadIdx.x; e < nr * m; e += blockDim.x) wl[e] = w[(size_t)r0 * m + e];
-  __syncthreads();
-  const int ntot = nvec + (want_self ? 1 : 0);
-  const int nout = ntot * m;
+__device__ __forceinline__ void chunk_dots(const BT* __restrict__ basis, size_t vstride, size_t base, int nr, int m,
+                                           int nvec, int want_self, const double* wl, double* __restrict__ pout) {
+  const int nout = (nvec + (want_self ? 1 : 0)) * m;
   for (int o = threadIdx.x; o < nout; o += blockDim.x) {
     const int i = o / m, c = o - i * m;
     double s0 = 0.0, s1 = 0.0;
     int r = 0;
     if (i < nvec) {
-      const BT* v = basis + (size_t)i * vstride + (size_t)r0 * m + c;
+      const BT* v = basis + (size_t)i * vstride + base + c;
       double s2 = 0.0, s3 = 0.0;
       for (; r + 3 < nr; r += 4) {       // four independent row loads in flight
         const double v0 = (double)v[(size_t)r * m], v1 = (double)v[(size_t)(r + 1) * m];
@@ -66,8 +58,24 @@ __global__ __launch_bounds__(256) void cols_dots_kernel(
     } else {
       for (; r < nr; ++r) s0 = fma(wl[r * m + c], wl[r * m + c], s0);
     }
-    partial[(size_t)blockIdx.x * nout + o] = s0 + s1;
+    pout[o] = s0 + s1;
   }
+}
+template <class BT>
+__global__ __launch_bounds__(256) void cols_dots_kernel(
+    GroupTab gt, int nrows, int m, int nvec, const BT* __restrict__ basis, size_t vstride, size_t gsb,
+    const double* __restrict__ w, size_t gsw, int want_self, double* __restrict__ partial, size_t gsp) {
+  extern __shared__ double wl[];  // DOT_ROWS x m
+  const int grp = gt.gid[blockIdx.z];
+  basis += (size_t)grp * gsb;
+  w += (size_t)grp * gsw;
+  partial += (size_t)grp * gsp;
+  const int r0 = blockIdx.x * DOT_ROWS;
+  const int nr = min(DOT_ROWS, nrows - r0);
+  for (int e = threadIdx.x; e < nr * m; e += blockDim.x) wl[e] = w[(size_t)r0 * m + e];
+  __syncthreads();
+  const int nout = (nvec + (want_self ? 1 : 0)) * m;
+  chunk_dots(basis, vstride, (size_t)r0 * m, nr, m, nvec, want_self, wl, partial + (size_t)blockIdx.x * nout);
 }
 
 // out[o] (+)= sum_b partial[b][o].  256 threads = 16 outputs x 16 block-slices:
@@ -113,13 +121,14 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(GroupTab gt, int n
 int dots_num_blocks(int nrows) { return (nrows + DOT_ROWS - 1) / DOT_ROWS; }
 
 // ---------------------------------------------------------------------------
-// K3, FP16-stored basis with 16-column panels (the hot case): the same three Arnoldi passes
-// with 16-byte (8 x FP16) basis loads.  The generic kernels above read 2 bytes per lane and
-// load, which is fine while the launches are latency bound (n ~ 3e4) and leaves them at
-// 0.34-0.46 of the HBM roofline at n = 5e5.
-//   dots: lane = (row slice s = lane & 15, column half, vector) -- the 16 lanes of a DPP row
-//   hold the 16 row slices of ONE (vector, half), each lane runs over rows s, s+16, s+32, s+48
-//   of the 64-row chunk with its 4 loads in flight, and the row sum is 4 DPP exchanges.
+// K3, FP16-stored basis with panels of M = 8 * NOCT columns (NOCT = 2, 16 columns: the hot case; 1, 3, 4: the
+// projection solve, the augmented Sherman-Morrison-Woodbury sweep [b, U] of the Newton step and wider panels): the
+// same three Arnoldi passes with 16-byte (8 x FP16) basis loads.  The generic kernels above read 2 bytes per lane
+// and load, which is fine while the launches are latency bound (n ~ 3e4) and leaves them at 0.34-0.46 of the HBM
+// roofline at n = 5e5.
+//   dots: lane = (row slice s = lane & 15, (vector, column octet) pair) -- the 16 lanes of a DPP row hold the 16 row
+//   slices of ONE pair, each lane runs over rows s, s+16, s+32, s+48 of the 64-row chunk with its 4 loads in flight,
+//   and the row sum is 4 DPP exchanges.
 // ---------------------------------------------------------------------------
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
@@ -140,173 +149,11 @@ __device__ __forceinline__ double dpp_row_sum(double v) {
   return v;
 }
 
-// LDS row stride of the staged chunk: 18 doubles (144 B) -- with 16 the lanes of a DPP row (rows s, s+1, ...
-// 128 B apart) fall on two banks sets and every read is an 8-way conflict
+// LDS row stride of a staged chunk: M + 2 doubles (16 columns: 18 doubles, 144 B) -- with M the lanes of a DPP row
+// (rows s, s+1, ... 128 B apart) fall on two banks sets and every read is an 8-way conflict
 constexpr int WLS = 18;
-// dot products of the chunk held in wl (DOT_ROWS rows of 16 doubles, stride WLS; rows >= nr zeroed) against the
+// dot products of the chunk held in wl (DOT_ROWS rows of M doubles, stride M + 2; rows >= nr zeroed) against the
 // basis vectors [0, nvec) and, if want_self, against itself (output row nvec)
-__device__ __forceinline__ void chunk_dots16(const _Float16* __restrict__ basis, size_t vstride, int r0, int nr,
-                                             int nvec, int want_self, const double* wl,
-                                             double* __restrict__ pout) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int s = lane & 15, half = (lane >> 4) & 1, vsub = lane >> 5;
-  const int ntot = nvec + (want_self ? 1 : 0);
-  for (int i0 = 0; i0 < ntot; i0 += 8) {
-    const int i = i0 + 2 * wave + vsub;
-    double acc[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) acc[t] = 0.0;
-    if (i < nvec) {
-      const _Float16* v = basis + (size_t)i * vstride + (size_t)r0 * 16 + half * 8;
-      half8_t x[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int row = s + 16 * k;
-        if (row < nr) x[k] = *reinterpret_cast<const half8_t*>(v + (size_t)row * 16);
-        else x[k] = (half8_t)(_Float16)0;
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const double* wr = wl + (s + 16 * k) * WLS + half * 8;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) acc[t] = fma((double)x[k][t], wr[t], acc[t]);
-      }
-    } else if (i == nvec && want_self) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const double* wr = wl + (s + 16 * k) * WLS + half * 8;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) acc[t] = fma(wr[t], wr[t], acc[t]);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) acc[t] = dpp_row_sum(acc[t]);
-    if (s == 0 && i < ntot) {
-      double2* o = reinterpret_cast<double2*>(pout + (size_t)i * 16 + half * 8);
-      o[0] = make_double2(acc[0], acc[1]);
-      o[1] = make_double2(acc[2], acc[3]);
-      o[2] = make_double2(acc[4], acc[5]);
-      o[3] = make_double2(acc[6], acc[7]);
-    }
-  }
-}
-
-// WT: storage type of the panel w (round 4: the operator's output of the hot path is an FP32 panel -- the basis it is
-// orthogonalised against is FP16-stored, so its rounding of 6e-8 is far inside what the iteration already carries;
-// the arithmetic stays FP64)
-template <class WT = double>
-__global__ __launch_bounds__(256) void cols_dots16_kernel(
-    GroupTab gt, int nrows, int nvec, const _Float16* __restrict__ basis, size_t vstride, size_t gsb,
-    const WT* __restrict__ w, size_t gsw, int want_self, double* __restrict__ partial, size_t gsp) {
-  __shared__ __attribute__((aligned(16))) double wl[DOT_ROWS * WLS];
-  const int grp = gt.gid[blockIdx.z];
-  basis += (size_t)grp * gsb;
-  w += (size_t)grp * gsw;
-  partial += (size_t)grp * gsp;
-  const int r0 = blockIdx.x * DOT_ROWS;
-  const int nr = min(DOT_ROWS, nrows - r0);
-  if constexpr (sizeof(WT) == 4) {
-    const float2* src = reinterpret_cast<const float2*>(w + (size_t)r0 * 16);
-    float2 raw[DOT_ROWS * 8 / 256];
-#pragma unroll
-    for (int k = 0; k < DOT_ROWS * 8 / 256; ++k) {
-      const int e = threadIdx.x + 256 * k;
-      raw[k] = src[e < nr * 8 ? e : 0];
-    }
-#pragma unroll
-    for (int k = 0; k < DOT_ROWS * 8 / 256; ++k) {
-      const int e = threadIdx.x + 256 * k;
-      *reinterpret_cast<double2*>(wl + (e >> 3) * WLS + (e & 7) * 2) =
-          e < nr * 8 ? make_double2((double)raw[k].x, (double)raw[k].y) : make_double2(0.0, 0.0);
-    }
-  } else {
-    const double2* src = reinterpret_cast<const double2*>(w + (size_t)r0 * 16);
-    for (int e = threadIdx.x; e < DOT_ROWS * 8; e += 256)
-      *reinterpret_cast<double2*>(wl + (e >> 3) * WLS + (e & 7) * 2) = e < nr * 8 ? src[e] : make_double2(0.0, 0.0);
-  }
-  __syncthreads();
-  const int nout = (nvec + (want_self ? 1 : 0)) * 16;
-  chunk_dots16(basis, vstride, r0, nr, nvec, want_self, wl, partial + (size_t)blockIdx.x * nout);
-}
-
-// w' = w - V h (written back), then the dots of w' against V and itself (chunk_dots16; the basis chunk
-// is cache resident by then, so the LDS side decides: with unpadded rows this phase was 2x slower)
-// STORE = false: w' is only staged in LDS for the dots, the panel w keeps the vector BEFORE the first projection (the
-// final update then subtracts the basis with the SUM of both passes' coefficients: one 8-byte store per element less)
-template <bool STORE = true, class WT = double>
-__global__ __launch_bounds__(256) void cols_update_dots16_kernel(
-    GroupTab gt, int nrows, int nvec, const _Float16* __restrict__ basis, size_t vstride, size_t gsb,
-    const double* __restrict__ h, size_t gsh, WT* __restrict__ w, size_t gsw,
-    double* __restrict__ partial, size_t gsp) {
-  extern __shared__ __attribute__((aligned(16))) double sm16[];
-  double* wl = sm16;                       // DOT_ROWS rows, stride WLS
-  double* hl = sm16 + DOT_ROWS * WLS;      // nvec x 16
-  const int grp = gt.gid[blockIdx.z];
-  basis += (size_t)grp * gsb;
-  h += (size_t)grp * gsh;
-  w += (size_t)grp * gsw;
-  partial += (size_t)grp * gsp;
-  const int r0 = blockIdx.x * DOT_ROWS;
-  const int nr = min(DOT_ROWS, nrows - r0);
-  for (int e = threadIdx.x; e < nvec * 16; e += 256) hl[e] = h[e];
-  __syncthreads();
-  {
-    // update: a thread owns the elements tid, tid + 256, ... of the chunk (one column c = tid & 15, four rows);
-    // per pair of basis vectors its 8 two-byte loads are issued together and the two coefficients come from
-    // LDS once.  (The 16-byte form with the vectors split over lane pairs was slower at every basis size:
-    // 1.69 vs 1.02 ms at n = 5e5, 7 vectors.)
-    const size_t base = (size_t)r0 * 16;
-    const int c = threadIdx.x & 15;
-    constexpr int NE = DOT_ROWS * 16 / 256;          // 4
-    int e[NE];
-    bool ok[NE];
-    double sacc[NE];
-#pragma unroll
-    for (int k = 0; k < NE; ++k) {
-      e[k] = threadIdx.x + 256 * k;
-      ok[k] = e[k] < nr * 16;
-      sacc[k] = 0.0;
-    }
-    int i = 0;
-    for (; i + 1 < nvec; i += 2) {
-      _Float16 b0[NE], b1[NE];
-      const _Float16* v0 = basis + (size_t)i * vstride + base;
-      const _Float16* v1 = v0 + vstride;
-#pragma unroll
-      for (int k = 0; k < NE; ++k) {
-        b0[k] = v0[ok[k] ? e[k] : 0];               // unconditional loads (row 0 of the chunk is always valid)
-        b1[k] = v1[ok[k] ? e[k] : 0];
-      }
-      const double h0 = hl[i * 16 + c], h1 = hl[(i + 1) * 16 + c];
-#pragma unroll
-      for (int k = 0; k < NE; ++k) sacc[k] = fma(h1, (double)b1[k], fma(h0, (double)b0[k], sacc[k]));
-    }
-    if (i < nvec) {
-      _Float16 b0[NE];
-      const _Float16* v0 = basis + (size_t)i * vstride + base;
-#pragma unroll
-      for (int k = 0; k < NE; ++k) b0[k] = v0[ok[k] ? e[k] : 0];
-      const double h0 = hl[i * 16 + c];
-#pragma unroll
-      for (int k = 0; k < NE; ++k) sacc[k] = fma(h0, (double)b0[k], sacc[k]);
-    }
-    WT wv[NE];
-#pragma unroll
-    for (int k = 0; k < NE; ++k) wv[k] = w[base + (ok[k] ? e[k] : 0)];
-#pragma unroll
-    for (int k = 0; k < NE; ++k) {
-      const double v = ok[k] ? (double)wv[k] - sacc[k] : 0.0;
-      if (STORE && ok[k]) w[base + e[k]] = (WT)v;
-      wl[(e[k] >> 4) * WLS + c] = v;
-    }
-  }
-  __syncthreads();
-  chunk_dots16(basis, vstride, r0, nr, nvec, 1, wl, partial + (size_t)blockIdx.x * (nvec + 1) * 16);
-}
-
-// ---- the same two dot kernels for panels of 8 * NOCT columns (NOCT = 1, 3, 4: the projection solve, the
-// augmented Sherman-Morrison-Woodbury sweep [b, U] of the Newton step and wider panels): a DPP row holds the 16 row
-// slices of one (vector, column octet) pair.
 template <int NOCT>
 __device__ __forceinline__ void chunk_dots8x(const _Float16* __restrict__ basis, size_t vstride, int r0, int nr,
                                              int nvec, int want_self, const double* wl, double* __restrict__ pout) {
@@ -355,11 +202,15 @@ __device__ __forceinline__ void chunk_dots8x(const _Float16* __restrict__ basis,
     }
   }
 }
-template <int NOCT>
+
+// WT: storage type of the panel w.  float: the operator's output of the hot path is an FP32 panel -- the basis it is
+// orthogonalised against is FP16-stored, so its rounding of 6e-8 is far inside what the iteration already carries;
+// the arithmetic stays FP64.  Its chunk is staged with all loads issued before the first conversion.
+template <int NOCT, class WT>
 __global__ __launch_bounds__(256) void cols_dots8x_kernel(
     GroupTab gt, int nrows, int nvec, const _Float16* __restrict__ basis, size_t vstride, size_t gsb,
-    const double* __restrict__ w, size_t gsw, int want_self, double* __restrict__ partial, size_t gsp) {
-  constexpr int M = 8 * NOCT, WS = M + 2;
+    const WT* __restrict__ w, size_t gsw, int want_self, double* __restrict__ partial, size_t gsp) {
+  constexpr int M = 8 * NOCT, WS = M + 2, M2 = M / 2;     // a thread stages two-column pieces, M2 per row
   __shared__ __attribute__((aligned(16))) double wl[DOT_ROWS * WS];
   const int grp = gt.gid[blockIdx.z];
   basis += (size_t)grp * gsb;
@@ -367,21 +218,41 @@ __global__ __launch_bounds__(256) void cols_dots8x_kernel(
   partial += (size_t)grp * gsp;
   const int r0 = blockIdx.x * DOT_ROWS;
   const int nr = min(DOT_ROWS, nrows - r0);
-  {
-    const double2* src = reinterpret_cast<const double2*>(w + (size_t)r0 * M);
-    for (int e = threadIdx.x; e < DOT_ROWS * (M / 2); e += 256) {
-      const int row = e / (M / 2), c2 = e - row * (M / 2);
-      *reinterpret_cast<double2*>(wl + row * WS + 2 * c2) = row < nr ? src[e] : make_double2(0.0, 0.0);
+  auto piece = [&](int e) {
+    const int row = e / M2;
+    return reinterpret_cast<double2*>(wl + row * WS + 2 * (e - row * M2));
+  };
+  if constexpr (sizeof(WT) == 4) {
+    constexpr int NL = DOT_ROWS * M2 / 256;
+    const float2* src = reinterpret_cast<const float2*>(w + (size_t)r0 * M);
+    float2 raw[NL];
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {
+      const int e = threadIdx.x + 256 * k;
+      raw[k] = src[e < nr * M2 ? e : 0];
     }
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {
+      const int e = threadIdx.x + 256 * k;
+      *piece(e) = e < nr * M2 ? make_double2((double)raw[k].x, (double)raw[k].y) : make_double2(0.0, 0.0);
+    }
+  } else {
+    const double2* src = reinterpret_cast<const double2*>(w + (size_t)r0 * M);
+    for (int e = threadIdx.x; e < DOT_ROWS * M2; e += 256) *piece(e) = e < nr * M2 ? src[e] : make_double2(0.0, 0.0);
   }
   __syncthreads();
   const int nout = (nvec + (want_self ? 1 : 0)) * M;
   chunk_dots8x<NOCT>(basis, vstride, r0, nr, nvec, want_self, wl, partial + (size_t)blockIdx.x * nout);
 }
-template <int NOCT>
+
+// w' = w - V h (written back), then the dots of w' against V and itself (chunk_dots8x; the basis chunk
+// is cache resident by then, so the LDS side decides: with unpadded rows this phase was 2x slower)
+// STORE = false: w' is only staged in LDS for the dots, the panel w keeps the vector BEFORE the first projection (the
+// final update then subtracts the basis with the SUM of both passes' coefficients: one 8-byte store per element less)
+template <int NOCT, bool STORE, class WT>
 __global__ __launch_bounds__(256) void cols_update_dots8x_kernel(
     GroupTab gt, int nrows, int nvec, const _Float16* __restrict__ basis, size_t vstride, size_t gsb,
-    const double* __restrict__ h, size_t gsh, double* __restrict__ w, size_t gsw,
+    const double* __restrict__ h, size_t gsh, WT* __restrict__ w, size_t gsw,
     double* __restrict__ partial, size_t gsp) {
   constexpr int M = 8 * NOCT, WS = M + 2;
   extern __shared__ __attribute__((aligned(16))) double sm8x[];
@@ -397,6 +268,10 @@ __global__ __launch_bounds__(256) void cols_update_dots8x_kernel(
   for (int e = threadIdx.x; e < nvec * M; e += 256) hl[e] = h[e];
   __syncthreads();
   {
+    // update: a thread owns the elements tid, tid + 256, ... of the chunk (for M = 8, 16, 32 all in one column);
+    // per pair of basis vectors its two-byte loads are issued together and the coefficients come from LDS once.
+    // (The 16-byte form with the vectors split over lane pairs was slower at every basis size: 1.69 vs 1.02 ms at
+    // n = 5e5, 16 columns, 7 vectors.)
     const size_t base = (size_t)r0 * M;
     constexpr int NE = DOT_ROWS * M / 256;           // 2 * NOCT
     int e[NE], c[NE];
@@ -409,26 +284,63 @@ __global__ __launch_bounds__(256) void cols_update_dots8x_kernel(
       ok[k] = e[k] < nr * M;
       sacc[k] = 0.0;
     }
-    for (int i = 0; i < nvec; ++i) {
+    int i = 0;
+    for (; i + 1 < nvec; i += 2) {
+      _Float16 b0[NE], b1[NE];
+      const _Float16* v0 = basis + (size_t)i * vstride + base;
+      const _Float16* v1 = v0 + vstride;
+#pragma unroll
+      for (int k = 0; k < NE; ++k) {
+        b0[k] = v0[ok[k] ? e[k] : 0];               // unconditional loads (row 0 of the chunk is always valid)
+        b1[k] = v1[ok[k] ? e[k] : 0];
+      }
+      const double* h0 = hl + i * M;
+      const double* h1 = h0 + M;
+#pragma unroll
+      for (int k = 0; k < NE; ++k) sacc[k] = fma(h1[c[k]], (double)b1[k], fma(h0[c[k]], (double)b0[k], sacc[k]));
+    }
+    if (i < nvec) {
       _Float16 b0[NE];
       const _Float16* v0 = basis + (size_t)i * vstride + base;
 #pragma unroll
       for (int k = 0; k < NE; ++k) b0[k] = v0[ok[k] ? e[k] : 0];
+      const double* h0 = hl + i * M;
 #pragma unroll
-      for (int k = 0; k < NE; ++k) sacc[k] = fma(hl[i * M + c[k]], (double)b0[k], sacc[k]);
+      for (int k = 0; k < NE; ++k) sacc[k] = fma(h0[c[k]], (double)b0[k], sacc[k]);
     }
-    double wv[NE];
+    WT wv[NE];
 #pragma unroll
     for (int k = 0; k < NE; ++k) wv[k] = w[base + (ok[k] ? e[k] : 0)];
 #pragma unroll
     for (int k = 0; k < NE; ++k) {
-      const double v = ok[k] ? wv[k] - sacc[k] : 0.0;
-      if (ok[k]) w[base + e[k]] = v;
+      const double v = ok[k] ? (double)wv[k] - sacc[k] : 0.0;
+      if (STORE && ok[k]) w[base + e[k]] = (WT)v;
       wl[(e[k] / M) * WS + c[k]] = v;
     }
   }
   __syncthreads();
   chunk_dots8x<NOCT>(basis, vstride, r0, nr, nvec, 1, wl, partial + (size_t)blockIdx.x * (nvec + 1) * M);
+}
+
+// a[t] += sum_{i < nvec} hc[i * ldh + t] * V_i[t], t < 8: the eight FP16 columns at v of nvec vectors vstride apart
+// (hc: the coefficients of those columns, rows of ldh doubles); 16-byte loads, four vectors in flight
+__device__ __forceinline__ void accum_octet(const _Float16* v, size_t vstride, int nvec, const double* hc,
+                                            int ldh, double (&a)[8]) {
+  int i = 0;
+  for (; i + 3 < nvec; i += 4) {
+    half8_t x[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) x[u] = *reinterpret_cast<const half8_t*>(v + (size_t)(i + u) * vstride);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int t = 0; t < 8; ++t) a[t] = fma(hc[(i + u) * ldh + t], (double)x[u][t], a[t]);
+  }
+  for (; i < nvec; ++i) {
+    const half8_t x = *reinterpret_cast<const half8_t*>(v + (size_t)i * vstride);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) a[t] = fma(hc[i * ldh + t], (double)x[t], a[t]);
+  }
 }
 
 // out = scale * (w + sign * V h), stored in FP16 (outf) and, rounded identically, in FP64 (out):
@@ -456,22 +368,7 @@ __global__ __launch_bounds__(256) void cols_update16_kernel(
     double a[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) a[t] = 0.0;
-    const _Float16* v = basis + e;
-    int i = 0;
-    for (; i + 3 < nvec; i += 4) {
-      half8_t x[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) x[u] = *reinterpret_cast<const half8_t*>(v + (size_t)(i + u) * vstride);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) a[t] = fma(hl[(i + u) * m + c0 + t], (double)x[u][t], a[t]);
-    }
-    for (; i < nvec; ++i) {
-      const half8_t x = *reinterpret_cast<const half8_t*>(v + (size_t)i * vstride);
-#pragma unroll
-      for (int t = 0; t < 8; ++t) a[t] = fma(hl[i * m + c0 + t], (double)x[t], a[t]);
-    }
+    accum_octet(basis + e, vstride, nvec, hl + c0, m, a);
     if (w) {
       const double2* wp = reinterpret_cast<const double2*>(w + e);
 #pragma unroll
@@ -567,42 +464,56 @@ __global__ __launch_bounds__(256) void cols_update_f4_kernel(
     op[1] = make_double2(a[2], a[3]);
   }
 }
-template <class BT>
+// ---- launch helpers shared by the dot launchers ----
+static void reduce_partials(hipStream_t st, const GroupTab& gt, int nblk, int nout, const double* partial, size_t gsp,
+                            double* out, size_t gso) {
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt, nblk, nout,
+                     partial, gsp, out, gso, 0);
+}
+constexpr size_t kLdsLimit = 48 * 1024;
+// LDS bytes of cols_update_dots8x_kernel: the staged chunk and nvec rows of coefficients
+static size_t update_dots_lds_bytes(int m, int nvec) { return (size_t)(DOT_ROWS * (m + 2) + nvec * m) * sizeof(double); }
+// fn(integral constant NOCT) for the panel widths the 8x kernels serve; false: another width
+template <class Fn>
+static bool with_noct(int m, Fn&& fn) {
+  switch (m) {
+    case 8: fn(std::integral_constant<int, 1>()); return true;
+    case 16: fn(std::integral_constant<int, 2>()); return true;
+    case 24: fn(std::integral_constant<int, 3>()); return true;
+    case 32: fn(std::integral_constant<int, 4>()); return true;
+    default: return false;
+  }
+}
+// The FP32 panel exists only on the hot path (iteration_form: FP16 basis, 16 columns, w kept): anything else is a
+// dispatch error, never a quiet detour through a generic kernel.
+template <class BT, class WT>
+static void require_panel_form(int m, bool keep_w) {
+  if (std::is_same<WT, float>::value && !(std::is_same<BT, _Float16>::value && m == 16 && keep_w))
+    throw std::logic_error("FP32 panel w: only with the FP16-stored basis, 16 columns and w kept");
+}
+
+template <class BT, class WT>
 void launch_cols_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                        const BT* basis, size_t vstride, size_t gsb, const double* w, size_t gsw,
+                        const BT* basis, size_t vstride, size_t gsb, const WT* w, size_t gsw,
                         int want_self, double* partial, size_t gsp, double* out, size_t gso) {
+  require_panel_form<BT, WT>(m, true);
   const int nblk = dots_num_blocks(nrows);
   const int nout = (nvec + (want_self ? 1 : 0)) * m;
   if (nout == 0 || gt.ng <= 0) return;
-  if constexpr (std::is_same<BT, _Float16>::value) {
-    if (m == 8 || m == 24 || m == 32) {
-      const dim3 grid(nblk, 1, gt.ng);
-      if (m == 8)
-        hipLaunchKernelGGL((cols_dots8x_kernel<1>), grid, dim3(256), 0, st, gt, nrows, nvec, basis, vstride, gsb, w, gsw,
-                           want_self, partial, gsp);
-      else if (m == 24)
-        hipLaunchKernelGGL((cols_dots8x_kernel<3>), grid, dim3(256), 0, st, gt, nrows, nvec, basis, vstride, gsb, w, gsw,
-                           want_self, partial, gsp);
-      else
-        hipLaunchKernelGGL((cols_dots8x_kernel<4>), grid, dim3(256), 0, st, gt, nrows, nvec, basis, vstride, gsb, w, gsw,
-                           want_self, partial, gsp);
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt,
-                         nblk, nout, partial, gsp, out, gso, 0);
-      return;
-    }
-    if (m == 16) {
-      hipLaunchKernelGGL(cols_dots16_kernel<double>, dim3(nblk, 1, gt.ng), dim3(256), 0, st, gt, nrows, nvec, basis,
-                         vstride, gsb, w, gsw, want_self, partial, gsp);
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt,
-                         nblk, nout, partial, gsp, out, gso, 0);
-      return;
-    }
-  }
-  hipLaunchKernelGGL(cols_dots_kernel<BT>, dim3(nblk, 1, gt.ng), dim3(256),
-                     DOT_ROWS * m * sizeof(double), st, gt, nrows, m, nvec, basis, vstride, gsb, w,
-                     gsw, want_self, partial, gsp);
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt,
-                     nblk, nout, partial, gsp, out, gso, 0);
+  const dim3 grid(nblk, 1, gt.ng);
+  bool done = false;
+  if constexpr (std::is_same<BT, _Float16>::value)
+    done = with_noct(m, [&](auto noct) {
+      constexpr int NOCT = decltype(noct)::value;
+      if constexpr (NOCT == 2 || std::is_same<WT, double>::value)
+        hipLaunchKernelGGL((cols_dots8x_kernel<NOCT, WT>), grid, dim3(256), 0, st, gt, nrows, nvec, basis, vstride, gsb,
+                           w, gsw, want_self, partial, gsp);
+    });
+  if constexpr (std::is_same<WT, double>::value)
+    if (!done)
+      hipLaunchKernelGGL(cols_dots_kernel<BT>, grid, dim3(256), DOT_ROWS * m * sizeof(double), st, gt, nrows, m, nvec,
+                         basis, vstride, gsb, w, gsw, want_self, partial, gsp);
+  reduce_partials(st, gt, nblk, nout, partial, gsp, out, gso);
 }
 void launch_cols_dots(hipStream_t st, int nrows, int m, int nvec, const double* basis,
                       size_t vstride, const double* w, int want_self, double* partial,
@@ -646,86 +557,53 @@ __global__ __launch_bounds__(256) void cols_update_dots_kernel(
     w[base + e] = v;
   }
   __syncthreads();
-  const int nout = (nvec + 1) * m;
-  for (int o = threadIdx.x; o < nout; o += blockDim.x) {
-    const int i = o / m, c = o - i * m;
-    double s0 = 0.0, s1 = 0.0;
-    if (i < nvec) {
-      const BT* v = basis + (size_t)i * vstride + base + c;
-      int r = 0;
-      double s2 = 0.0, s3 = 0.0;
-      for (; r + 3 < nr; r += 4) {
-        const double v0 = (double)v[(size_t)r * m], v1 = (double)v[(size_t)(r + 1) * m];
-        const double v2 = (double)v[(size_t)(r + 2) * m], v3 = (double)v[(size_t)(r + 3) * m];
-        s0 = fma(v0, wl[r * m + c], s0);
-        s1 = fma(v1, wl[(r + 1) * m + c], s1);
-        s2 = fma(v2, wl[(r + 2) * m + c], s2);
-        s3 = fma(v3, wl[(r + 3) * m + c], s3);
-      }
-      for (; r < nr; ++r) s0 = fma((double)v[(size_t)r * m], wl[r * m + c], s0);
-      s0 += s2;
-      s1 += s3;
-    } else {
-      for (int r = 0; r < nr; ++r) s0 = fma(wl[r * m + c], wl[r * m + c], s0);
-    }
-    partial[(size_t)blockIdx.x * nout + o] = s0 + s1;
-  }
+  chunk_dots(basis, vstride, base, nr, m, nvec, 1, wl, partial + (size_t)blockIdx.x * (nvec + 1) * m);
 }
-// Can the 16-column FP16 launch leave w untouched (keep_w; see cols_update_dots16_kernel)?
+// Can the 16-column FP16 launch leave w untouched (keep_w; see cols_update_dots8x_kernel)?
 bool update_dots_keeps_w(int m, bool fp16_basis, int nvec_max) {
-  return fp16_basis && m == 16 &&
-         (size_t)(DOT_ROWS * 18 + nvec_max * 16) * sizeof(double) <= 48 * 1024;
+  return fp16_basis && m == 16 && update_dots_lds_bytes(16, nvec_max) <= kLdsLimit;
 }
-template <class BT>
+bool arnoldi16_w32_ok(int nvec_max) { return update_dots_lds_bytes(16, nvec_max) <= kLdsLimit; }
+template <class BT, class WT>
 void launch_cols_update_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
                                const BT* basis, size_t vstride, size_t gsb, const double* h,
-                               size_t gsh, double* w, size_t gsw, bool keep_w, double* partial, size_t gsp,
+                               size_t gsh, WT* w, size_t gsw, bool keep_w, double* partial, size_t gsp,
                                double* out, size_t gso) {
+  require_panel_form<BT, WT>(m, keep_w);
   if (gt.ng <= 0) return;
   const int nblk = dots_num_blocks(nrows);
   const int nout = (nvec + 1) * m;
-  if constexpr (std::is_same<BT, _Float16>::value) {
-    if ((m == 8 || m == 24 || m == 32) &&
-        (size_t)(DOT_ROWS * (m + 2) + nvec * m) * sizeof(double) <= 48 * 1024) {
-      const dim3 grid(nblk, 1, gt.ng);
-      const size_t lds = (size_t)(DOT_ROWS * (m + 2) + nvec * m) * sizeof(double);
-      if (m == 8)
-        hipLaunchKernelGGL((cols_update_dots8x_kernel<1>), grid, dim3(256), lds, st, gt, nrows, nvec, basis, vstride,
-                           gsb, h, gsh, w, gsw, partial, gsp);
-      else if (m == 24)
-        hipLaunchKernelGGL((cols_update_dots8x_kernel<3>), grid, dim3(256), lds, st, gt, nrows, nvec, basis, vstride,
-                           gsb, h, gsh, w, gsw, partial, gsp);
-      else
-        hipLaunchKernelGGL((cols_update_dots8x_kernel<4>), grid, dim3(256), lds, st, gt, nrows, nvec, basis, vstride,
-                           gsb, h, gsh, w, gsw, partial, gsp);
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt,
-                         nblk, nout, partial, gsp, out, gso, 0);
-      return;
-    }
-    if (m == 16 && (size_t)(DOT_ROWS * 18 + nvec * 16) * sizeof(double) <= 48 * 1024) {
-      if (keep_w)
-        hipLaunchKernelGGL((cols_update_dots16_kernel<false, double>), dim3(nblk, 1, gt.ng), dim3(256),
-                           (size_t)(DOT_ROWS * 18 + nvec * 16) * sizeof(double), st, gt, nrows, nvec, basis, vstride,
-                           gsb, h, gsh, w, gsw, partial, gsp);
-      else
-        hipLaunchKernelGGL((cols_update_dots16_kernel<true, double>), dim3(nblk, 1, gt.ng), dim3(256),
-                           (size_t)(DOT_ROWS * 18 + nvec * 16) * sizeof(double), st, gt, nrows, nvec, basis, vstride,
-                           gsb, h, gsh, w, gsw, partial, gsp);
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt,
-                         nblk, nout, partial, gsp, out, gso, 0);
-      return;
-    }
+  const dim3 grid(nblk, 1, gt.ng);
+  const size_t lds = update_dots_lds_bytes(m, nvec);
+  bool done = false;
+  if constexpr (std::is_same<BT, _Float16>::value)
+    done = lds <= kLdsLimit && with_noct(m, [&](auto noct) {
+      constexpr int NOCT = decltype(noct)::value;
+      // (w is kept at 16 columns only: update_dots_keeps_w)
+      if constexpr (NOCT == 2) {
+        if (keep_w) {
+          hipLaunchKernelGGL((cols_update_dots8x_kernel<2, false, WT>), grid, dim3(256), lds, st, gt, nrows, nvec, basis,
+                             vstride, gsb, h, gsh, w, gsw, partial, gsp);
+          return;
+        }
+      }
+      if constexpr (std::is_same<WT, double>::value)
+        hipLaunchKernelGGL((cols_update_dots8x_kernel<NOCT, true, WT>), grid, dim3(256), lds, st, gt, nrows, nvec, basis,
+                           vstride, gsb, h, gsh, w, gsw, partial, gsp);
+    });
+  if (!done) {
+    if constexpr (std::is_same<WT, double>::value)
+      hipLaunchKernelGGL(cols_update_dots_kernel<BT>, grid, dim3(256), DOT_ROWS * m * sizeof(double), st, gt, nrows, m,
+                         nvec, basis, vstride, gsb, h, gsh, w, gsw, partial, gsp);
+    else
+      throw std::logic_error("FP32 panel w: the coefficients do not fit the update-and-dots kernel's LDS");
   }
-  hipLaunchKernelGGL(cols_update_dots_kernel<BT>, dim3(nblk, 1, gt.ng), dim3(256),
-                     DOT_ROWS * m * sizeof(double), st, gt, nrows, m, nvec, basis, vstride, gsb, h,
-                     gsh, w, gsw, partial, gsp);
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt,
-                     nblk, nout, partial, gsp, out, gso, 0);
+  reduce_partials(st, gt, nblk, nout, partial, gsp, out, gso);
 }
 
 // out[r,c] = scale[c] * ( w[r,c] + sign * sum_{i<nvec} h[i*m+c] * V_i[r,c] )
 // (scale may be NULL = 1; w may be NULL = 0).  Streams nvec panels once.
-// outf (optional): FP32 copy of the result (the stored Krylov vector); out then
+// outf (optional): the result as stored in the basis (BT: the stored Krylov vector); out then
 // holds the same rounded values, so the vector the next operator application
 // sees IS the stored one.
 template <class BT>
@@ -773,8 +651,7 @@ static void cols_update_impl(hipStream_t st, const GroupTab& gt, int nrows, int 
   if constexpr (std::is_same<BT, _Float16>::value) {
     int nmax = 0;
     for (int i = 0; i < gt.ng; ++i) nmax = std::max(nmax, nvec.v[gt.gid[i]]);
-    if ((m == 16 || ((m & 7) == 0 && m <= 32)) &&
-        (size_t)nmax * m * sizeof(double) <= 48 * 1024) {
+    if ((m & 7) == 0 && m <= 32 && (size_t)nmax * m * sizeof(double) <= kLdsLimit) {
       const size_t nhalf = (size_t)nrows * (m / 8);       // 8-column pieces
       const int grid16 = (int)std::min<size_t>((nhalf + 255) / 256, 8192);
       hipLaunchKernelGGL(cols_update16_kernel, dim3(grid16, 1, gt.ng), dim3(256),
@@ -786,7 +663,7 @@ static void cols_update_impl(hipStream_t st, const GroupTab& gt, int nrows, int 
   if constexpr (std::is_same<BT, float>::value) {
     int nmax = 0;
     for (int i = 0; i < gt.ng; ++i) nmax = std::max(nmax, nvec.v[gt.gid[i]]);
-    if ((m & 3) == 0 && !outf && out && (size_t)nmax * m * sizeof(double) <= 48 * 1024) {
+    if ((m & 3) == 0 && !outf && out && (size_t)nmax * m * sizeof(double) <= kLdsLimit) {
       const size_t nquad = nelem / 4;
       const int gridq = (int)std::min<size_t>((nquad + 255) / 256, 8192);
       hipLaunchKernelGGL(cols_update_f4_kernel, dim3(gridq, 1, gt.ng), dim3(256),
@@ -823,12 +700,15 @@ void launch_cols_update(hipStream_t st, int nrows, int m, int nvec, const double
                        out, 0);
 }
 // the Krylov basis stored in FP64, FP32 or FP16 (the arithmetic is FP64 throughout)
-#define RICADI_BASIS_LAUNCHERS(BT)                                                                                    \
-  template void launch_cols_dots_b(hipStream_t, const GroupTab&, int, int, int, const BT*, size_t, size_t, const double*, \
+// ... and the panel w in FP64 or FP32 (FP32: hot path only, require_panel_form)
+#define RICADI_PANEL_LAUNCHERS(BT, WT)                                                                                \
+  template void launch_cols_dots_b(hipStream_t, const GroupTab&, int, int, int, const BT*, size_t, size_t, const WT*, \
                                    size_t, int, double*, size_t, double*, size_t);                                    \
   template void launch_cols_update_dots_b(hipStream_t, const GroupTab&, int, int, int, const BT*, size_t, size_t,      \
-                                          const double*, size_t, double*, size_t, bool, double*, size_t, double*,     \
-                                          size_t);                                                                    \
+                                          const double*, size_t, WT*, size_t, bool, double*, size_t, double*, size_t);
+#define RICADI_BASIS_LAUNCHERS(BT)                                                                                    \
+  RICADI_PANEL_LAUNCHERS(BT, double)                                                                                  \
+  RICADI_PANEL_LAUNCHERS(BT, float)                                                                                   \
   template void launch_cols_update_b(hipStream_t, const GroupTab&, int, int, int, const BT*, size_t, size_t,           \
                                      const double*, size_t, double, const double*, size_t, const double*, double*,    \
                                      size_t, BT*, size_t);                                                            \
@@ -838,6 +718,7 @@ RICADI_BASIS_LAUNCHERS(double)
 RICADI_BASIS_LAUNCHERS(float)
 RICADI_BASIS_LAUNCHERS(_Float16)
 #undef RICADI_BASIS_LAUNCHERS
+#undef RICADI_PANEL_LAUNCHERS
 
 // ---------------------------------------------------------------------------
 // GMRES small per-column kernels (one thread per panel column).
@@ -848,6 +729,31 @@ RICADI_BASIS_LAUNCHERS(_Float16)
 // applies the stored rotations, creates the new one, writes scale = 1/h_{j+1,j}
 // (0 on breakdown / frozen column) and the residual estimate |g_{j+1}|.
 // ---------------------------------------------------------------------------
+constexpr double kTiny = 1e-300;
+// frozen column (already converged: |g_j| at or below thr; or exact breakdown: no sub-diagonal): it is kept inert
+__device__ __forceinline__ bool column_frozen(double sub, double gabs, double thr) {
+  return !(sub > kTiny) || gabs <= thr;
+}
+// The new rotation of column j of one panel column: from `cur` (the diagonal entry after the stored rotations) and
+// the sub-diagonal `sub` it writes cs[j], sn[j], the rotated Hc[j], Hc[j + 1] and g[j], g[j + 1] (gj: g[j] before);
+// returns the residual estimate |g[j + 1]|.
+__device__ __forceinline__ double givens_tail(double cur, double sub, double gj, int j, double* Hc, double* cs,
+                                              double* sn, double* g) {
+  const double d = hypot(cur, sub);
+  double cj = 1.0, sj = 0.0;
+  if (d > kTiny) {
+    cj = cur / d;
+    sj = sub / d;
+  }
+  cs[j] = cj;
+  sn[j] = sj;
+  Hc[j] = (d > kTiny) ? d : 1.0;           // keep R non-singular for frozen columns
+  Hc[j + 1] = 0.0;
+  g[j + 1] = (d > kTiny) ? -sj * gj : 0.0;
+  g[j] = (d > kTiny) ? cj * gj : 0.0;
+  return (d > kTiny) ? fabs(sj * gj) : 0.0;
+}
+
 // One 64-lane workgroup per panel column: the lanes stage h1+h2, cs, sn in LDS
 // with independent loads (and reduce ||h2||^2 with shuffles); lane 0 then runs
 // the sequential rotation chain out of LDS instead of a chain of dependent
@@ -857,8 +763,7 @@ __global__ __launch_bounds__(64) void gmres_hess_kernel(
     const double* __restrict__ h2, double* __restrict__ H, double* __restrict__ cs,
     double* __restrict__ sn, double* __restrict__ g, double* __restrict__ scale,
     double* __restrict__ resid, const double* __restrict__ bnorm, double tol,
-    double* __restrict__ host_resid, double* __restrict__ zero_h1, double* __restrict__ zero_h2,
-    double* __restrict__ hsum) {
+    double* __restrict__ host_resid, double* __restrict__ hsum) {
   extern __shared__ double sh[];       // hcol[restart+2], csl[restart], snl[restart]
   if (host_resid) host_resid += (size_t)gt.gid[blockIdx.z] * m;
   {
@@ -866,9 +771,7 @@ __global__ __launch_bounds__(64) void gmres_hess_kernel(
     const size_t grp = (size_t)gt.gid[blockIdx.z];
     h1 += grp * (restart + 2) * m;
     h2 += grp * (restart + 2) * m;
-    if (zero_h1) zero_h1 += grp * (restart + 2) * m;
     if (hsum) hsum += grp * (restart + 2) * m;
-    if (zero_h2) zero_h2 += grp * (restart + 2) * m;
     H += grp * m * (restart + 1) * restart;
     cs += grp * m * restart;
     sn += grp * m * restart;
@@ -894,12 +797,6 @@ __global__ __launch_bounds__(64) void gmres_hess_kernel(
     hcol[i] = h1[i * m + c] + b;
     if (hsum) hsum[i * m + c] = hcol[i];       // coefficients of BOTH passes, for an update that starts from the unprojected w
   }
-  // atomic dot passes (launch_cols_dots16_atomic): clear what has been consumed -- this column of the first-pass
-  // sums, and of the second-pass buffer of the NEXT iteration (last read by the update of the previous one)
-  if (zero_h1)
-    for (int i = lane; i < nv; i += 64) zero_h1[i * m + c] = 0.0;
-  if (zero_h2)
-    for (int i = lane; i <= nv + 1 && i < restart + 2; i += 64) zero_h2[i * m + c] = 0.0;
   for (int i = lane; i < j; i += 64) {
     csl[i] = csc[i];
     snl[i] = snc[i];
@@ -912,10 +809,7 @@ __global__ __launch_bounds__(64) void gmres_hess_kernel(
   const double gj = gc[j];
   double hn2 = ww - h2sq;
   double hnext = hn2 > 0.0 ? sqrt(hn2) : 0.0;
-  // frozen column (already converged, or exact breakdown): keep it inert
-  const double tiny = 1e-300;
-  const bool dead = !(hnext > tiny) || (fabs(gj) <= 0.01 * tol * bnorm[c]);
-  if (dead) hnext = 0.0;
+  if (column_frozen(hnext, fabs(gj), 0.01 * tol * bnorm[c])) hnext = 0.0;
   double cur = hcol[0];
   for (int i = 0; i < j; ++i) {
     const double nxt = hcol[i + 1];
@@ -924,22 +818,8 @@ __global__ __launch_bounds__(64) void gmres_hess_kernel(
     Hc[i] = t;
     cur = u;
   }
-  const double d = hypot(cur, hnext);
-  double cj = 1.0, sj = 0.0;
-  if (d > tiny) { cj = cur / d; sj = hnext / d; }
-  csc[j] = cj;
-  snc[j] = sj;
-  Hc[j] = (d > tiny) ? d : 1.0;  // keep R non-singular for frozen columns
-  Hc[j + 1] = 0.0;
-  if (d > tiny) {
-    gc[j + 1] = -sj * gj;
-    gc[j] = cj * gj;
-  } else {
-    gc[j + 1] = 0.0;
-    gc[j] = 0.0;
-  }
-  scale[c] = (hnext > tiny) ? 1.0 / hnext : 0.0;
-  const double rnew = (d > tiny) ? fabs(sj * gj) : 0.0;
+  const double rnew = givens_tail(cur, hnext, gj, j, Hc, csc, snc, gc);
+  scale[c] = (hnext > kTiny) ? 1.0 / hnext : 0.0;
   resid[c] = rnew;
   // pinned host copy for the (lagged) convergence check: saves a D2H copy per iteration
   if (host_resid) host_resid[c] = rnew;
@@ -947,11 +827,11 @@ __global__ __launch_bounds__(64) void gmres_hess_kernel(
 void launch_gmres_hess_b(hipStream_t st, const GroupTab& gt, int m, int j, int restart,
                          const double* h1, const double* h2, double* H, double* cs, double* sn,
                          double* g, double* scale, double* resid, const double* bnorm, double tol,
-                         double* host_resid, double* zero_h1, double* zero_h2, double* hsum) {
+                         double* host_resid, double* hsum) {
   if (gt.ng <= 0) return;
   hipLaunchKernelGGL(gmres_hess_kernel, dim3(m, 1, gt.ng), dim3(64),
                      (3 * restart + 4) * sizeof(double), st, gt, m, j, restart, h1, h2, H, cs, sn, g,
-                     scale, resid, bnorm, tol, host_resid, zero_h1, zero_h2, hsum);
+                     scale, resid, bnorm, tol, host_resid, hsum);
 }
 
 // y[i*m + c] solves R y = g for the k x k triangle of column c.  One wave per (column, group): lane l first
@@ -1057,11 +937,13 @@ void launch_gmres_start_b(hipStream_t st, const GroupTab& gt, int m, int restart
 // gmres_hess_kernel did (column of H through the stored rotations, new rotation, g, residual estimate into
 // pinned host memory).  The residual estimates are double buffered (resid_in read by everybody, resid_out
 // written by workgroup 0): a value that decides "frozen" must not change under the other workgroups' feet.
-//   use_sum = 1: w is the vector BEFORE the first projection, coefficients h1 + h2 (cols_update_dots16<.., false>);
+//   use_sum = 1: w is the vector BEFORE the first projection, coefficients h1 + h2 (cols_update_dots8x_kernel<2, false, .>);
 //   use_sum = 0: w has been projected once, coefficients h2.
 // ---------------------------------------------------------------------------
-template <class WT = double>
-__global__ __launch_bounds__(256) void cols_update16_hess_kernel(
+// (launch bounds: eight waves per SIMD, what the kernel has always run at -- left alone the allocator lands one VGPR
+// above the 64 that takes)
+template <class WT>
+__global__ __launch_bounds__(256, 8) void cols_update16_hess_kernel(
     GroupTab gt, size_t nhalf, int nvec, const _Float16* __restrict__ basis, size_t vstride, size_t gsb,
     const double* __restrict__ h1, const double* __restrict__ h2, size_t gsh, int use_sum,
     const WT* __restrict__ w, size_t gsw, double* __restrict__ out, size_t gso, _Float16* __restrict__ outf,
@@ -1078,7 +960,6 @@ __global__ __launch_bounds__(256) void cols_update16_hess_kernel(
   if (out) out += (size_t)grp * gso;
   outf += (size_t)grp * gsf;
   double* scl = hl + nvec * m;
-  const double tiny = 1e-300;
   for (int e = threadIdx.x; e < nvec * m; e += 256) hl[e] = use_sum ? h1[e] + h2[e] : h2[e];
   double hnext = 0.0;
   if (threadIdx.x < m) {
@@ -1091,8 +972,8 @@ __global__ __launch_bounds__(256) void cols_update16_hess_kernel(
     const double hn2 = h2[nvec * m + c] - h2sq;          // ||w'||^2 before the second projection, minus it
     hnext = hn2 > 0.0 ? sqrt(hn2) : 0.0;
     const double rprev = resid_in[(size_t)grp * m + c];  // |g_j|
-    if (!(hnext > tiny) || rprev <= 0.01 * tol * bnorm[(size_t)grp * m + c]) hnext = 0.0;   // frozen column
-    scl[c] = hnext > tiny ? 1.0 / hnext : 0.0;
+    if (column_frozen(hnext, rprev, 0.01 * tol * bnorm[(size_t)grp * m + c])) hnext = 0.0;
+    scl[c] = hnext > kTiny ? 1.0 / hnext : 0.0;
   }
   __syncthreads();
   if (blockIdx.x == 0 && threadIdx.x < m) {
@@ -1112,19 +993,7 @@ __global__ __launch_bounds__(256) void cols_update16_hess_kernel(
       Hc[i] = t;
       cur = u;
     }
-    const double d = hypot(cur, hnext);
-    double cj = 1.0, sj = 0.0;
-    if (d > tiny) {
-      cj = cur / d;
-      sj = hnext / d;
-    }
-    csc[j] = cj;
-    snc[j] = sj;
-    Hc[j] = (d > tiny) ? d : 1.0;          // keep R non-singular for frozen columns
-    Hc[j + 1] = 0.0;
-    gc[j + 1] = (d > tiny) ? -sj * gj : 0.0;
-    gc[j] = (d > tiny) ? cj * gj : 0.0;
-    const double rnew = (d > tiny) ? fabs(sj * gj) : 0.0;
+    const double rnew = givens_tail(cur, hnext, gj, j, Hc, csc, snc, gc);
     resid_out[gq * m + c] = rnew;
     if (host_resid) host_resid[gq * m + c] = rnew;
   }
@@ -1134,22 +1003,7 @@ __global__ __launch_bounds__(256) void cols_update16_hess_kernel(
     double a[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) a[t] = 0.0;
-    const _Float16* v = basis + e;
-    int i = 0;
-    for (; i + 3 < nvec; i += 4) {
-      half8_t x[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) x[u] = *reinterpret_cast<const half8_t*>(v + (size_t)(i + u) * vstride);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) a[t] = fma(hl[(i + u) * m + c0 + t], (double)x[u][t], a[t]);
-    }
-    for (; i < nvec; ++i) {
-      const half8_t x = *reinterpret_cast<const half8_t*>(v + (size_t)i * vstride);
-#pragma unroll
-      for (int t = 0; t < 8; ++t) a[t] = fma(hl[i * m + c0 + t], (double)x[t], a[t]);
-    }
+    accum_octet(basis + e, vstride, nvec, hl + c0, m, a);
     if constexpr (sizeof(WT) == 4) {
       const float4* wp = reinterpret_cast<const float4*>(w + e);
       const float4 w0 = wp[0], w1 = wp[1];
@@ -1180,54 +1034,29 @@ __global__ __launch_bounds__(256) void cols_update16_hess_kernel(
   }
 }
 bool update_hess_fused_ok(int m, bool fp16_basis) { return fp16_basis && m == 16; }
+template <class WT>
 void launch_cols_update16_hess_b(hipStream_t st, const GroupTab& gt, int nrows, int nvec, const _Float16* basis,
                                  size_t vstride, size_t gsb, const double* h1, const double* h2, size_t gsh, int use_sum,
-                                 const double* w, size_t gsw, double* out, size_t gso, _Float16* outf, size_t gsf, int j,
+                                 const WT* w, size_t gsw, double* out, size_t gso, _Float16* outf, size_t gsf, int j,
                                  int restart, double* H, double* cs, double* sn, double* g, const double* resid_in,
-                                 double* resid_out, const double* bnorm, double tol, double* host_resid,
-                                 const float* w32) {
+                                 double* resid_out, const double* bnorm, double tol, double* host_resid) {
   if (gt.ng <= 0) return;
   const size_t nhalf = (size_t)nrows * 2;
   const int grid = (int)std::min<size_t>((nhalf + 255) / 256, 8192);
-  if (w32)
-    hipLaunchKernelGGL(cols_update16_hess_kernel<float>, dim3(grid, 1, gt.ng), dim3(256),
-                       (size_t)(nvec * 16 + 16) * sizeof(double), st, gt, nhalf, nvec, basis, vstride, gsb, h1, h2, gsh,
-                       use_sum, w32, gsw, out, gso, outf, gsf, j, restart, H, cs, sn, g, resid_in, resid_out, bnorm, tol,
-                       host_resid);
-  else
-    hipLaunchKernelGGL(cols_update16_hess_kernel<double>, dim3(grid, 1, gt.ng), dim3(256),
-                       (size_t)(nvec * 16 + 16) * sizeof(double), st, gt, nhalf, nvec, basis, vstride, gsb, h1, h2, gsh,
-                       use_sum, w, gsw, out, gso, outf, gsf, j, restart, H, cs, sn, g, resid_in, resid_out, bnorm, tol,
-                       host_resid);
+  hipLaunchKernelGGL(cols_update16_hess_kernel<WT>, dim3(grid, 1, gt.ng), dim3(256),
+                     (size_t)(nvec * 16 + 16) * sizeof(double), st, gt, nhalf, nvec, basis, vstride, gsb, h1, h2, gsh,
+                     use_sum, w, gsw, out, gso, outf, gsf, j, restart, H, cs, sn, g, resid_in, resid_out, bnorm, tol,
+                     host_resid);
 }
-
-// The first two Arnoldi passes on an FP32 panel w (16 columns, FP16-stored basis; the second pass in its
-// "w kept" form: nothing is written back): same partial / reduce structure as the FP64-panel launches.
-bool arnoldi16_w32_ok(int nvec_max) {
-  return (size_t)(DOT_ROWS * 18 + nvec_max * 16) * sizeof(double) <= 48 * 1024;
-}
-void launch_cols_dots16_w32(hipStream_t st, const GroupTab& gt, int nrows, int nvec, const _Float16* basis,
-                            size_t vstride, size_t gsb, const float* w32, size_t gsw, double* partial, size_t gsp,
-                            double* out, size_t gso) {
-  if (gt.ng <= 0 || nvec <= 0) return;
-  const int nblk = dots_num_blocks(nrows), nout = nvec * 16;
-  hipLaunchKernelGGL(cols_dots16_kernel<float>, dim3(nblk, 1, gt.ng), dim3(256), 0, st, gt, nrows, nvec, basis,
-                     vstride, gsb, w32, gsw, 0, partial, gsp);
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt, nblk, nout, partial,
-                     gsp, out, gso, 0);
-}
-void launch_cols_update_dots16_w32(hipStream_t st, const GroupTab& gt, int nrows, int nvec, const _Float16* basis,
-                                   size_t vstride, size_t gsb, const double* h, size_t gsh, float* w32, size_t gsw,
-                                   double* partial, size_t gsp, double* out, size_t gso) {
-  if (gt.ng <= 0) return;
-  const int nblk = dots_num_blocks(nrows), nout = (nvec + 1) * 16;
-  hipLaunchKernelGGL((cols_update_dots16_kernel<false, float>), dim3(nblk, 1, gt.ng), dim3(256),
-                     (size_t)(DOT_ROWS * 18 + nvec * 16) * sizeof(double), st, gt, nrows, nvec, basis, vstride, gsb, h,
-                     gsh, w32, gsw, partial, gsp);
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((nout + 15) / 16, 1, gt.ng), dim3(256), 0, st, gt, nblk, nout, partial,
-                     gsp, out, gso, 0);
-}
-
+// the panel w in FP64 or FP32
+#define RICADI_UPDATE16_HESS(WT)                                                                                      \
+  template void launch_cols_update16_hess_b(hipStream_t, const GroupTab&, int, int, const _Float16*, size_t, size_t,  \
+                                            const double*, const double*, size_t, int, const WT*, size_t, double*,    \
+                                            size_t, _Float16*, size_t, int, int, double*, double*, double*, double*,  \
+                                            const double*, double*, const double*, double, double*);
+RICADI_UPDATE16_HESS(double)
+RICADI_UPDATE16_HESS(float)
+#undef RICADI_UPDATE16_HESS
 
 // ---------------------------------------------------------------------------
 // K3L: the Arnoldi of the hot path (FP16-stored basis, 16 columns, FP32 panel w) in its one-reduction form: delayed
@@ -1271,7 +1100,7 @@ struct LsPend {
 
 // partial[blk][o], o < ldp: the sums of one 64-row chunk per workgroup for slots V_0 .. V_{j-1}, u_j, w (j = js[group];
 // HAS_W = false: the end-of-cycle pass, no w).  u_j and w are staged in LDS once (FP64, rows of stride WLS); lane =
-// (row slice sl, column half, slot) as in chunk_dots16: the 16 lanes of a DPP row hold the 16 row slices of ONE
+// (row slice sl, column half, slot) as in chunk_dots8x<2>: the 16 lanes of a DPP row hold the 16 row slices of ONE
 // (slot, half), and one load of a basis row feeds both sums.  (With u_j and w loaded into registers by every slot's
 // lanes instead -- eight times the cache traffic -- the launch took 37 us at cfg2 against 23 us.)
 template <bool HAS_W>
@@ -1393,7 +1222,7 @@ __device__ LsCoefs ls_column(const double* sums, int j, int c, int restart, doub
     r = r2 > 0.0 ? sqrt(r2) : 0.0;
     const double rho = pp.rho[c], gj = pp.gj[c];
     double sub = rho * r;
-    dead = !(sub > tiny) || fabs(gj) <= thr;
+    dead = column_frozen(sub, fabs(gj), thr);
     if (complete) {
       // column j-1:  p_{j-1} + rho_{j-1} [s; r]
       if (dead) sub = 0.0;
@@ -1404,18 +1233,7 @@ __device__ LsCoefs ls_column(const double* sums, int j, int c, int restart, doub
         Hc[i] = csc[i] * cur + snc[i] * nxt;
         cur = -snc[i] * cur + csc[i] * nxt;
       }
-      const double d = hypot(cur, sub);
-      double cj = 1.0, sj = 0.0;
-      if (d > tiny) {
-        cj = cur / d;
-        sj = sub / d;
-      }
-      csc[j - 1] = cj;
-      snc[j - 1] = sj;
-      Hc[j - 1] = (d > tiny) ? d : 1.0;    // keep R non-singular for frozen columns
-      Hc[j] = 0.0;
-      gc[j] = (d > tiny) ? -sj * gj : 0.0;
-      gc[j - 1] = (d > tiny) ? cj * gj : 0.0;
+      (void)givens_tail(cur, sub, gj, j - 1, Hc, csc, snc, gc);
     }
   }
   LsCoefs o{0.0, 0.0, 0.0, dead};

@@ -315,17 +315,19 @@ void launch_colscale_b(hipStream_t st, const GroupTab& gt, size_t nrows, int m, 
 void launch_colscale_b(hipStream_t st, const GroupTab& gt, size_t nrows, int m, const double* a,
                        const double* x, size_t gsx, double b, double* y, size_t gsy, _Float16* yf,
                        size_t gsf);
-// Arnoldi passes on the Krylov basis stored as BT = double, float or _Float16 (the arithmetic is FP64 throughout)
-template <class BT>
+// Arnoldi passes on the Krylov basis stored as BT = double, float or _Float16 (the arithmetic is FP64 throughout).
+// The panel w is stored as WT = double, or float: the operator's FP32 output on the hot path, admitted exactly where
+// iteration_form admits it (FP16 basis, 16 columns, keep_w, arnoldi16_w32_ok); any other use throws.
+template <class BT, class WT>
 void launch_cols_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
-                        const BT* basis, size_t vstride, size_t gsb, const double* w, size_t gsw,
+                        const BT* basis, size_t vstride, size_t gsb, const WT* w, size_t gsw,
                         int want_self, double* partial, size_t gsp, double* out, size_t gso);
-// keep_w (FP16 basis, 16 columns, update_dots_keeps_w): w is left as it was BEFORE the first projection (no 8-byte
-// store per element); the Hessenberg kernel then writes h1 + h2 to `hsum` and the final update uses those on w
-template <class BT>
+// keep_w (FP16 basis, 16 columns, update_dots_keeps_w): w is left as it was BEFORE the first projection (no store per
+// element); the Hessenberg kernel then writes h1 + h2 to `hsum` and the final update uses those on w
+template <class BT, class WT>
 void launch_cols_update_dots_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
                                const BT* basis, size_t vstride, size_t gsb, const double* h,
-                               size_t gsh, double* w, size_t gsw, bool keep_w, double* partial, size_t gsp,
+                               size_t gsh, WT* w, size_t gsw, bool keep_w, double* partial, size_t gsp,
                                double* out, size_t gso);
 template <class BT>
 void launch_cols_update_b(hipStream_t st, const GroupTab& gt, int nrows, int m, int nvec,
@@ -339,9 +341,9 @@ void launch_cols_update_bk(hipStream_t st, const GroupTab& gt, int nrows, int m,
 void launch_gmres_hess_b(hipStream_t st, const GroupTab& gt, int m, int j, int restart,
                          const double* h1, const double* h2, double* H, double* cs, double* sn,
                          double* g, double* scale, double* resid, const double* bnorm, double tol,
-                         double* host_resid = nullptr, double* zero_h1 = nullptr, double* zero_h2 = nullptr,
-                         double* hsum = nullptr);
+                         double* host_resid = nullptr, double* hsum = nullptr);
 bool update_dots_keeps_w(int m, bool fp16_basis, int nvec_max);
+bool arnoldi16_w32_ok(int nvec_max);   // do the coefficients of nvec_max vectors fit beside the FP32 panel's chunk?
 void launch_gmres_backsolve_b(hipStream_t st, const GroupTab& gt, int m, const GroupInts& k,
                               int restart, const double* H, const double* g, double* y);
 void launch_gmres_start_b(hipStream_t st, const GroupTab& gt, int m, int restart,
@@ -491,25 +493,14 @@ void launch_pressure_step_b(hipStream_t st, const GroupTab& gt, int nblocks, con
                             const double* rp_, const _Float16* rp16, size_t gsr, double* out, size_t gso,
                             const ProlongArgs& pa, const float* zv32 = nullptr, size_t gsz32 = 0);
 
-// K3h: last Arnoldi pass + Hessenberg / Givens update in one launch (FP16 basis, m = 16)
+// K3h: last Arnoldi pass + Hessenberg / Givens update in one launch (FP16 basis, m = 16; the panel w in FP64 or FP32)
 bool update_hess_fused_ok(int m, bool fp16_basis);
+template <class WT>
 void launch_cols_update16_hess_b(hipStream_t st, const GroupTab& gt, int nrows, int nvec, const _Float16* basis,
                                  size_t vstride, size_t gsb, const double* h1, const double* h2, size_t gsh, int use_sum,
-                                 const double* w, size_t gsw, double* out, size_t gso, _Float16* outf, size_t gsf, int j,
+                                 const WT* w, size_t gsw, double* out, size_t gso, _Float16* outf, size_t gsf, int j,
                                  int restart, double* H, double* cs, double* sn, double* g, const double* resid_in,
-                                 double* resid_out, const double* bnorm, double tol, double* host_resid,
-                                 const float* w32 = nullptr);
-
-// First two Arnoldi passes of a 16-column panel against the FP16-stored basis with the panel w stored in FP32 (the
-// operator's output on the hot path, round 4); the second pass leaves w as it is ("w kept" form).  launch_cols_update16_
-// hess_b takes the same panel through its w32 argument.
-bool arnoldi16_w32_ok(int nvec_max);
-void launch_cols_dots16_w32(hipStream_t st, const GroupTab& gt, int nrows, int nvec, const _Float16* basis,
-                            size_t vstride, size_t gsb, const float* w32, size_t gsw, double* partial, size_t gsp,
-                            double* out, size_t gso);
-void launch_cols_update_dots16_w32(hipStream_t st, const GroupTab& gt, int nrows, int nvec, const _Float16* basis,
-                                   size_t vstride, size_t gsb, const double* h, size_t gsh, float* w32, size_t gsw,
-                                   double* partial, size_t gsp, double* out, size_t gso);
+                                 double* resid_out, const double* bnorm, double tol, double* host_resid);
 
 // K3L: the one-reduction (delayed CGS2) Arnoldi of the same hot path (ricadi_arnoldi.hip).  dots: one pass over V,
 // the candidate u_j (slot j) and w, reduced into the group's coefficient block (w32 = NULL: the end-of-cycle pass,

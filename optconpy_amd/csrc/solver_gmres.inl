@@ -61,6 +61,13 @@ static void with_basis(ricadi_ctx* c, const IterationForm& f, Fn&& fn) {
   else fn(c->basis.p);
 }
 
+// fn(w) with the operator's output panel as stored: float* (f.w32) or double*
+template <class Fn>
+static void with_panel(ricadi_ctx* c, const IterationForm& f, Fn&& fn) {
+  if (f.w32) fn(c->wv32.p);
+  else fn(c->wv.p);
+}
+
 // The Arnoldi passes of iteration nvec - 1 on the workspace panels (w = S z_j in wv / wv32, coefficients in h1 / h2),
 // for the groups of bt.tab.  Strides as in gmres_core.
 struct ArnoldiStrides {
@@ -78,26 +85,22 @@ static void panel_norms2(ricadi_ctx* c, const Batch& bt, const double* w, size_t
 // first pass: h1 = V^T w
 static void arnoldi_dots(ricadi_ctx* c, const IterationForm& f, const Batch& bt, int nvec) {
   const ArnoldiStrides s(c, bt);
-  if (f.w32)
-    launch_cols_dots16_w32(bt.st, bt.tab, c->n, nvec, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
-                           c->wv32.p, s.nm, c->partial.p, s.gspart, c->h1.p, s.gsh);
-  else
-    with_basis(c, f, [&](auto* V) {
-      launch_cols_dots_b(bt.st, bt.tab, c->n, bt.m, nvec, V, s.vs, s.nm, c->wv.p, s.nm, 0, c->partial.p, s.gspart,
-                         c->h1.p, s.gsh);
+  with_basis(c, f, [&](auto* V) {
+    with_panel(c, f, [&](auto* w) {
+      launch_cols_dots_b(bt.st, bt.tab, c->n, bt.m, nvec, V, s.vs, s.nm, w, s.nm, 0, c->partial.p, s.gspart, c->h1.p,
+                         s.gsh);
     });
+  });
 }
 // first update fused with the dot products of the second pass: w -= V h1, h2 = V^T w (and ||w||^2)
 static void arnoldi_update_dots(ricadi_ctx* c, const IterationForm& f, const Batch& bt, int nvec) {
   const ArnoldiStrides s(c, bt);
-  if (f.w32)
-    launch_cols_update_dots16_w32(bt.st, bt.tab, c->n, nvec, reinterpret_cast<_Float16*>(c->basisf.p), s.vs, s.nm,
-                                  c->h1.p, s.gsh, c->wv32.p, s.nm, c->partial.p, s.gspart, c->h2.p, s.gsh);
-  else
-    with_basis(c, f, [&](auto* V) {
-      launch_cols_update_dots_b(bt.st, bt.tab, c->n, bt.m, nvec, V, s.vs, s.nm, c->h1.p, s.gsh, c->wv.p, s.nm, f.keepw,
+  with_basis(c, f, [&](auto* V) {
+    with_panel(c, f, [&](auto* w) {
+      launch_cols_update_dots_b(bt.st, bt.tab, c->n, bt.m, nvec, V, s.vs, s.nm, c->h1.p, s.gsh, w, s.nm, f.keepw,
                                 c->partial.p, s.gspart, c->h2.p, s.gsh);
     });
+  });
 }
 // last update: v_{j+1} = scale (w - V h2), stored in the basis (fuseh: with the Hessenberg / Givens update of
 // iteration j = nvec - 1 in the same launch; the residual estimates also go to host_resid)
@@ -108,11 +111,13 @@ static void arnoldi_update(ricadi_ctx* c, const IterationForm& f, const Batch& b
   double* vcur = f.h16 ? nullptr : c->vcur.p;
   if (f.fuseh) {
     _Float16* Vh = reinterpret_cast<_Float16*>(c->basisf.p);
-    launch_cols_update16_hess_b(bt.st, bt.tab, c->n, nvec, Vh, s.vs, s.nm, c->h1.p, c->h2.p, s.gsh, f.keepw ? 1 : 0,
-                                c->wv.p, s.nm, vcur, s.nm, Vh + (size_t)nvec * s.vs, s.nm, j, c->opts.gmres_restart,
-                                c->H.p, c->cs.p, c->sn.p, c->g.p, c->resid.p + (size_t)(j & 1) * resbuf,
-                                c->resid.p + (size_t)((j + 1) & 1) * resbuf, c->bnorm2.p, c->opts.gmres_tol,
-                                host_resid, f.w32 ? c->wv32.p : nullptr);
+    with_panel(c, f, [&](auto* w) {
+      launch_cols_update16_hess_b(bt.st, bt.tab, c->n, nvec, Vh, s.vs, s.nm, c->h1.p, c->h2.p, s.gsh, f.keepw ? 1 : 0,
+                                  w, s.nm, vcur, s.nm, Vh + (size_t)nvec * s.vs, s.nm, j, c->opts.gmres_restart, c->H.p,
+                                  c->cs.p, c->sn.p, c->g.p, c->resid.p + (size_t)(j & 1) * resbuf,
+                                  c->resid.p + (size_t)((j + 1) & 1) * resbuf, c->bnorm2.p, c->opts.gmres_tol,
+                                  host_resid);
+    });
     return;
   }
   const double* h = f.keepw ? c->h2.p + s.h2buf : c->h2.p;
@@ -172,7 +177,7 @@ static void iteration_launches(ricadi_ctx* c, const IterationForm& f, const Cycl
     arnoldi_update_dots(c, f, bt, j + 1);
     if (!f.fuseh)
       launch_gmres_hess_b(bt.st, bt.tab, bt.m, j, restart, c->h1.p, c->h2.p, c->H.p, c->cs.p, c->sn.p, c->g.p,
-                          c->scale.p, c->resid.p, c->bnorm2.p, c->opts.gmres_tol, host_resid, nullptr, nullptr,
+                          c->scale.p, c->resid.p, c->bnorm2.p, c->opts.gmres_tol, host_resid,
                           f.keepw ? c->h2.p + (size_t)(restart + 2) * c->wcols : nullptr);
     arnoldi_update(c, f, bt, j + 1, host_resid);
   }

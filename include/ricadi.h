@@ -45,6 +45,10 @@ extern "C" {
 
 typedef struct ricadi_ctx ricadi_ctx;
 
+/* most levels of a hierarchy under ricadi_opts::hierarchy = 1 (a level: a grid with its own sweep; the dense inverse
+ * of the last level's coarse problem is not counted) */
+#define RICADI_MAX_HIERARCHY_LEVELS 6
+
 /* Options of the inner solver (block-Jacobi + coarse-level preconditioned
  * GMRES).  Zero-initialise and call ricadi_default_opts() first.            */
 typedef struct ricadi_opts {
@@ -78,6 +82,18 @@ typedef struct ricadi_opts {
                             "QR ... SVD" (singular values resolved to eps*s_1), for factors of up to
                             1024 columns -- wider ones take the Gram route;  0 = always Gram matrix +
                             eigendecomposition (resolves singular values down to sqrt(eps)*s_1)      */
+  int hierarchy;         /* rule of the multilevel hierarchy.  0 (default): the rule of max_levels above.  1 ("fine"):
+                            level 0 keeps agg_v / agg_p and never grows them; where its coarse problem exceeds
+                            coarse_max it goes to a child level (pairs of velocity aggregates, single pressure
+                            aggregates, dense inverse <= coarse_max*9/8), which hands ITS coarse problem to a child
+                            in the same way -- at most RICADI_MAX_HIERARCHY_LEVELS levels, one V-cycle visit per
+                            level, the last one holds the dense inverse; only if that many levels do not reach the
+                            cap does the LAST level grow its aggregates (x1.5 per step); a level whose velocity aggregates
+                            would not outnumber its pressure aggregates by a quarter coarsens its pressure further
+                            (else the coarse saddle matrix of a deep chain is singular).  Every level with a child
+                            uses plain aggregation; the two-level rule for stiffness-dominated operators
+                            (ricadi_host_sa_criterion) is not applied; max_levels is ignored.
+                            ricadi_host_plan_hierarchy returns the levels.  Set before ricadi_set_operator       */
   int child_smoother;    /* smoother of a child level of the multilevel preconditioner (a hierarchy without a
                             child level ignores it): 0 (default) one SIMPLE block sweep; 1 one coloured Vanka
                             sweep -- per child pressure unknown the patch of itself and the velocity unknowns
@@ -468,7 +484,10 @@ int ricadi_project_pencil_dev(ricadi_ctx* ctx, const double* dQ, int k, double* 
  *        [21] 1 if a child level smooths with the coloured Vanka sweep (0: SIMPLE sweep or no child level), and of
  *        the first such level [22] its colours (the lone colour included), [23] its patches (one per pressure unknown of the
  *        level), [24] its largest patch, [25] the entries of J the size cap of 64 unknowns dropped, [26] its lone
- *        pseudo-patches];
+ *        pseudo-patches,
+ *        [27] ricadi_opts::hierarchy in force, [28] the levels of the hierarchy as ricadi_host_plan_hierarchy counts
+ *        them (grids with a sweep of their own: entry 8 counts the dense coarse problem as one level more), [29] the
+ *        dimension of the dense inverse of the last level (entry 9 again; 0 without a coarse space)];
  * nout >= 8; entries beyond nout are not written.                                   */
 int ricadi_setup_info(ricadi_ctx* ctx, int* out, int nout);
 
@@ -573,6 +592,22 @@ int ricadi_host_plan_levels(int nv, int np, const int32_t* a_rowptr, const int32
                             const int32_t* e_rowptr, const int32_t* e_col, const double* e_val,
                             const int32_t* j_rowptr, const int32_t* j_col, const double* j_val,
                             const ricadi_opts* opts, int32_t* out);
+/* The whole hierarchy ricadi_set_operator would build for (cal A, cal E, J) with these options, level by level, on the
+ * host: the same rule and the same child options as the setup, with the switch RICADI_SA at its default.  A level is
+ * a grid with a sweep of its own; level l + 1 works on the aggregates of level l (plain aggregation, Galerkin
+ * matrices), the last level inverts its coarse matrix densely.  *nlevels_out = number of levels (at most
+ * RICADI_MAX_HIERARCHY_LEVELS; ricadi_host_plan_levels' out[0] counts the dense coarse problem as one more where
+ * there is a coarse space).  levels_out: 8 entries per level, RICADI_MAX_HIERARCHY_LEVELS * 8 in all,
+ *   [nv, np, kv, kp, agg_v, agg_p, has_child, dense_dim]
+ * -- the level's size, its velocity / pressure aggregates, the aggregate sizes it ended with (the caller's on level 0
+ * under hierarchy = 1; (2, 1) on a child unless it is the last level and had to grow them), whether its coarse problem
+ * goes to a child, and kv + kp where it is inverted densely (0 on every level with a child).  smoothed_out (may be
+ * NULL): per level 1 where its prolongation is smoothed.  Deterministic; no GPU needed.                             */
+int ricadi_host_plan_hierarchy(int nv, int np, const int32_t* a_rowptr, const int32_t* a_col, const double* a_val,
+                               const int32_t* e_rowptr, const int32_t* e_col, const double* e_val,
+                               const int32_t* j_rowptr, const int32_t* j_col, const double* j_val,
+                               const ricadi_opts* opts, int32_t* nlevels_out, int32_t* levels_out,
+                               int32_t* smoothed_out);
 /* The row-block tile format of the saddle SpMM that ricadi_set_operator would build (host only), for tests.
  * sizes_out[8] = [n, nblk, max_cols, max_nnz, nnz(S), tiles usable, multi-shift form built, nv].  Call with
  * the arrays NULL for the sizes, then again with rows2[nblk*32] (global row per local row, -1 = none),

@@ -20,7 +20,7 @@ RICADI_ENOCONV = -3
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 402
+ABI_VERSION = 403
 
 
 class RicadiOpts(C.Structure):
@@ -28,7 +28,7 @@ class RicadiOpts(C.Structure):
                 ("gmres_maxit", C.c_int), ("bj_block", C.c_int), ("agg_v", C.c_int),
                 ("agg_p", C.c_int), ("coarse_max", C.c_int), ("use_coarse", C.c_int),
                 ("max_levels", C.c_int), ("verbose", C.c_int), ("compress_qr", C.c_int),
-                ("child_smoother", C.c_int), ("child_damping", C.c_double)]
+                ("hierarchy", C.c_int), ("child_smoother", C.c_int), ("child_damping", C.c_double)]
 
 
 class RicadiAdiParams(C.Structure):
@@ -127,6 +127,8 @@ SIGNATURES = {
                                            C.POINTER(C.c_int)]),
     "ricadi_host_plan_levels": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp,
                                           C.POINTER(RicadiOpts), _ip]),
+    "ricadi_host_plan_hierarchy": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp,
+                                             C.POINTER(RicadiOpts), _ip, _ip, _ip]),
     "ricadi_host_aggregate": (C.c_int, [C.c_int, _ip, _ip, C.c_int, _ip]),
     "ricadi_host_vanka_patches": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _ip]),
     "ricadi_precond_vanka": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip]),
@@ -704,13 +706,13 @@ class Context:
         return ms.value
 
     def setup_info(self):
-        a = (C.c_int * 27)()
-        _chk(self._lib.ricadi_setup_info(self._h, a, 27))
+        a = (C.c_int * 30)()
+        _chk(self._lib.ricadi_setup_info(self._h, a, 30))
         return dict(zip(("nv", "np", "nbv", "nbp", "bs", "kc", "spmm_row_blocks", "spmm_max_cols", "levels",
                          "dense_coarse", "fp16_vector_input", "rect_ks", "two_term_ks", "np_", "nnz_j",
                          "nnz_sy", "nnz_restriction", "coarse_route", "k1_variant", "fp32_intermediate", "fp32_operator_output",
                          "child_smoother", "vanka_colours", "vanka_patches", "vanka_largest_patch", "vanka_dropped",
-                         "vanka_lone_patches"),
+                         "vanka_lone_patches", "hierarchy", "hierarchy_levels", "hierarchy_dense"),
                         list(a)))
 
     def dense_inverse_batch(self, mats):
@@ -773,14 +775,16 @@ class Context:
         return int(var.value)
 
     def precond_structure(self, level=0):
-        """Structure of the preconditioner cycle of ``level`` (0 this context, 1 its child level): dict with the
+        """Structure of the preconditioner cycle of ``level`` (0 this context, 1 its child level, 2 that level's
+        child, ...: ``ValueError`` below the last one): dict with the
         velocity / pressure block lists (``bv_ptr``, ``bv_rows``, ``bp_ptr``, ``bp_rows``), ``aggof`` (dof ->
         coarse index), ``kc``, ``kcv``, ``kcp``, ``smoothed``, the prolongation ``P`` (scipy CSR, n x kc),
-        ``child``, ``folded``, ``rect`` and ``precond32``."""
+        ``child``, ``folded``, ``rect``, ``precond32`` and the aggregate sizes the level ended with (``agg_v``,
+        ``agg_p``)."""
         sz = np.zeros(16, dtype=np.int32)
         nul = [None] * 8
         _chk(self._lib.ricadi_precond_structure(self._h, int(level), _i(sz), *nul))
-        nv, np_, nbv, nbp, bs, kc, kcv, kcp, sa, nnzp, child, folded, rect, p32 = (int(x) for x in sz[:14])
+        nv, np_, nbv, nbp, bs, kc, kcv, kcp, sa, nnzp, child, folded, rect, p32, agg_v, agg_p = (int(x) for x in sz)
         n = nv + np_
         out = dict(bv_ptr=np.zeros(nbv + 1, np.int32), bv_rows=np.zeros(nv, np.int32),
                    bp_ptr=np.zeros(nbp + 1, np.int32), bp_rows=np.zeros(np_, np.int32),
@@ -793,7 +797,8 @@ class Context:
         if nbp == 0:
             out["bp_ptr"] = np.zeros(1, np.int32)
         out.update(nv=nv, np=np_, nbv=nbv, nbp=nbp, bs=bs, kc=kc, kcv=kcv, kcp=kcp, smoothed=bool(sa), P=P,
-                   child=bool(child), folded=bool(folded), rect=bool(rect), precond32=bool(p32))
+                   child=bool(child), folded=bool(folded), rect=bool(rect), precond32=bool(p32), agg_v=agg_v,
+                   agg_p=agg_p)
         return out
 
     def precond_vanka(self, level=1):
@@ -955,6 +960,26 @@ def host_plan_levels(calA, calE, J, **opts):
     _chk(load().ricadi_host_plan_levels(a[3][0], j[3][0], _i(a[0]), _i(a[1]), _d(a[2]), _i(e[0]), _i(e[1]), _d(e[2]),
                                         _i(j[0]), _i(j[1]), _d(j[2]), C.byref(o), _i(out)))
     return dict(levels=int(out[0]), kc=int(out[1]), kcv=int(out[2]), kcp=int(out[3]), smoothed=bool(out[4]))
+
+
+PLAN_KEYS = ("nv", "np", "kv", "kp", "agg_v", "agg_p", "has_child", "dense_dim")
+MAX_HIERARCHY_LEVELS = 6
+
+
+def host_plan_hierarchy(calA, calE, J, **opts):
+    """The whole hierarchy ``set_operator`` would build, level by level (``ricadi_host_plan_hierarchy``; host only):
+    a list with one dict per level -- ``nv``, ``np``, the aggregates ``kv`` / ``kp``, their sizes ``agg_v`` /
+    ``agg_p``, ``has_child``, ``dense_dim`` (``kv + kp`` on the last level, 0 above it) and ``smoothed``.  A level is
+    a grid with a sweep of its own: ``host_plan_levels`` counts the dense coarse problem as one level more."""
+    a, e, j = as_csr(calA), as_csr(calE), as_csr(J)
+    o = default_opts(**opts)
+    nlev = np.zeros(1, dtype=np.int32)
+    rows = np.zeros((MAX_HIERARCHY_LEVELS, 8), dtype=np.int32)
+    sa = np.zeros(MAX_HIERARCHY_LEVELS, dtype=np.int32)
+    _chk(load().ricadi_host_plan_hierarchy(a[3][0], j[3][0], _i(a[0]), _i(a[1]), _d(a[2]), _i(e[0]), _i(e[1]),
+                                           _d(e[2]), _i(j[0]), _i(j[1]), _d(j[2]), C.byref(o), _i(nlev), _i(rows),
+                                           _i(sa)))
+    return [dict(zip(PLAN_KEYS, (int(x) for x in rows[l])), smoothed=bool(sa[l])) for l in range(int(nlev[0]))]
 
 
 def host_saddle_tiles(calA, calE, J, **opts):

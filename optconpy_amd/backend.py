@@ -20,7 +20,8 @@ _opts = {}
 
 
 def configure(**opts):
-    """Set inner-solver options (see ``ricadi_opts`` in include/ricadi.h).
+    """Set inner-solver options (see ``ricadi_opts`` in include/ricadi.h), e.g. ``coarse_max=600``,
+    ``child_smoother=1``, ``hierarchy=1`` (the fine multilevel hierarchy).
 
     Takes effect for the next operator; drops the cached context.
     """

@@ -283,6 +283,7 @@ struct ricadi_ctx {
   bool has_op = false;
   int nv = 0, np = 0, n = 0;
   int bs = 32, nbv = 0, nbp = 0, kc = 0;
+  int agg_v = 0, agg_p = 0;   // aggregate sizes the hierarchy rule ended with on this level (HostSetup)
   size_t snnz = 0;
   // operator
   DArr<int> s_rp, s_ci;

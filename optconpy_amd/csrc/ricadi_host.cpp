@@ -7,6 +7,7 @@
 // matrices.  The per-shift parts are linear combinations formed on the device.
 // Nothing here follows reference code: the reference solves these systems with
 // SuperLU.
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -186,6 +187,22 @@ bool sa_criterion(const HostCsr& A, double& rs_out, double& gamma_out) {
   gamma_out = sy > 0.0 ? sk / sy : 1e30;
   return gamma_out <= 0.7;
 }
+
+int root_levels(const ricadi_opts& o) {
+  // (a context that may use L levels has at most L - 1 grids: the dense coarse problem counts)
+  return o.hierarchy == 1 ? RICADI_MAX_HIERARCHY_LEVELS + 1 : std::max(2, o.max_levels);
+}
+ricadi_opts child_opts(const ricadi_opts& o, bool parent_is_child) {
+  ricadi_opts c = o;
+  // aggregates of the child level (in units of ITS dofs = this level's aggregates): pairs of velocity aggregates,
+  // single pressure aggregates; its own dense inverse may be an eighth larger than the cap (pairs do not always
+  // pair up) -- once for the whole chain of a fine hierarchy
+  c.agg_v = 2;
+  c.agg_p = 1;
+  if (!(o.hierarchy == 1 && parent_is_child)) c.coarse_max = o.coarse_max + o.coarse_max / 8;
+  return c;
+}
+int child_levels(const ricadi_opts& o, int levels) { return o.hierarchy == 1 ? levels - 1 : 2; }
 
 void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ricadi_opts& o,
                  HostSetup& hs, int max_levels, double sa_omega) {
@@ -420,6 +437,7 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
   const int* g_rp = e_graph ? E.rp.data() : vv_rp.data();
   const int* g_ci = e_graph ? E.ci.data() : vv_ci.data();
   int av = std::max(1, o.agg_v), ap = std::max(1, o.agg_p);
+  const bool fine = o.hierarchy == 1;
   std::vector<int> va(nv), pa(std::max(np, 1));
   int kv = 0, kp = 0;
   // Is this an operator the smoothed prolongation is made for (stiffness-like, symmetric part dominant)?
@@ -448,8 +466,30 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
     // iterations per shift-solve, 9.99 -> 8.86 s per pass over 128 shifts with the per-shift inversions inside.  A
     // convection-dominated or mass-like operator (criterion false) is served as well by the child as by the inverse
     // (n = 1e5, nu = 0.0025: 182 vs 153 iterations at shift 1, equal from shift 50 on, 219 vs 381 ms per 16 shifts).
-    const int direct_max = std::max(16, stiff ? o.coarse_max + o.coarse_max / 2 : o.coarse_max);
+    // A chain of pairwise velocity coarsening over single pressure aggregates runs out of velocity unknowns: from the
+    // fourth child on k_v falls below k_p and the coarse saddle matrix [[K, B^T], [B, 0]] is singular (B: k_p x k_v
+    // cannot have full row rank; met at n = 5e5, "coarse matrix singular").  A level of the fine hierarchy therefore
+    // coarsens its pressure further until its velocity aggregates outnumber the pressure aggregates by a quarter.
+    if (fine && np > 0 && 4L * kv < 5L * kp && ap < np) {
+      ap += std::max(1, ap / 2);
+      continue;
+    }
+    const int direct_max = std::max(16, stiff && !fine ? o.coarse_max + o.coarse_max / 2 : o.coarse_max);
     if (kv + kp <= direct_max) break;
+    if (fine) {
+      // The fine hierarchy (ricadi_opts::hierarchy = 1): the aggregates stay as they are and the coarse problem goes
+      // to a child, level after level, whatever the operator (the mirror's count hardly moves with the mesh at fine
+      // aggregates).  Only a level that can have no child -- the last one the chain allows, or
+      // an operator without pressure or without a mass-like cal E -- grows its aggregates until its inverse fits (by
+      // 1.5 and at least one: a child starts from (2, 1)).
+      if (max_levels > 2 && np > 0) {
+        hs.multilevel = true;
+        break;
+      }
+      av += std::max(1, av / 2);
+      ap += std::max(1, ap / 2);
+      continue;
+    }
     const bool grow_first = stiff && av + av / 2 <= 128;
     // A third level, only where it can be GENTLE: the coarse problem of these aggregates goes to a
     // child level whose own aggregates are pairs of velocity aggregates and single pressure aggregates
@@ -473,6 +513,8 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
   hs.kcv = kv;
   hs.kcp = kp;
   hs.kc = kv + kp;
+  hs.agg_v = av;
+  hs.agg_p = ap;
   const int kc = hs.kc;
   for (int i = 0; i < nv; ++i) hs.aggof[i] = va[i];
   for (int k = 0; k < np; ++k) hs.aggof[nv + k] = kv + pa[k];
@@ -1223,6 +1265,49 @@ int ricadi_host_plan_levels(int nv, int np, const int32_t* a_rp, const int32_t* 
     out[4] = hs.sa ? 1 : 0;
   } catch (...) {
     ricadi::set_error("ricadi_host_plan_levels: exception");
+    return RICADI_EINVAL;
+  }
+  return RICADI_OK;
+}
+
+// One level of ricadi_host_plan_hierarchy and, through its Galerkin matrices, the levels below it: what
+// ricadi_set_operator does, without the device
+static void plan_level(const ricadi::HostCsr& A, const ricadi::HostCsr& E, const ricadi::HostCsr& J,
+                       const ricadi_opts& o, int levels, bool is_child, std::vector<std::array<int32_t, 9>>& rows) {
+  ricadi::HostSetup hs;
+  const double sa_omega = (is_child || J.nrows == 0 || o.bj_block != 32) ? 0.0 : 0.5;
+  ricadi::build_setup_checked(A, E, J, o, hs, levels, sa_omega);
+  rows.push_back({hs.nv, hs.np, hs.kcv, hs.kcp, hs.agg_v, hs.agg_p, hs.multilevel ? 1 : 0,
+                  hs.multilevel ? 0 : hs.kc, hs.sa ? 1 : 0});
+  if (hs.multilevel)
+    plan_level(hs.l1A, hs.l1E, hs.l1J, ricadi::child_opts(o, is_child), ricadi::child_levels(o, levels), true, rows);
+}
+
+int ricadi_host_plan_hierarchy(int nv, int np, const int32_t* a_rp, const int32_t* a_ci, const double* a_v,
+                               const int32_t* e_rp, const int32_t* e_ci, const double* e_v, const int32_t* j_rp,
+                               const int32_t* j_ci, const double* j_v, const ricadi_opts* opts, int32_t* nlevels_out,
+                               int32_t* levels_out, int32_t* smoothed_out) {
+  if (nv < 1 || np < 0 || !a_rp || !a_ci || !a_v || !e_rp || !e_ci || !e_v || (np > 0 && (!j_rp || !j_ci || !j_v)) ||
+      !opts || !nlevels_out || !levels_out || (opts->hierarchy != 0 && opts->hierarchy != 1)) {
+    ricadi::set_error("ricadi_host_plan_hierarchy: bad argument");
+    return RICADI_EINVAL;
+  }
+  try {
+    const ricadi::HostCsr A = ricadi::make_csr(nv, nv, a_rp, a_ci, a_v), E = ricadi::make_csr(nv, nv, e_rp, e_ci, e_v);
+    const int32_t zero = 0;
+    const ricadi::HostCsr J = np > 0 ? ricadi::make_csr(np, nv, j_rp, j_ci, j_v) : ricadi::make_csr(0, nv, &zero, &zero, a_v);
+    std::vector<std::array<int32_t, 9>> rows;
+    plan_level(A, E, J, *opts, ricadi::root_levels(*opts), false, rows);
+    if ((int)rows.size() > RICADI_MAX_HIERARCHY_LEVELS) throw std::runtime_error("more levels than the rule allows");
+    *nlevels_out = (int32_t)rows.size();
+    std::fill(levels_out, levels_out + 8 * RICADI_MAX_HIERARCHY_LEVELS, 0);
+    if (smoothed_out) std::fill(smoothed_out, smoothed_out + RICADI_MAX_HIERARCHY_LEVELS, 0);
+    for (size_t l = 0; l < rows.size(); ++l) {
+      std::copy(rows[l].begin(), rows[l].begin() + 8, levels_out + 8 * l);
+      if (smoothed_out) smoothed_out[l] = rows[l][8];
+    }
+  } catch (...) {
+    ricadi::set_error("ricadi_host_plan_hierarchy: exception");
     return RICADI_EINVAL;
   }
   return RICADI_OK;

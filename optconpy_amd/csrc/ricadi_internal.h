@@ -68,6 +68,7 @@ struct HostSetup {
   std::vector<uint16_t> sb_lidx;
   // coarse level
   int kc = 0, kcv = 0, kcp = 0;
+  int agg_v = 0, agg_p = 0;            // aggregate sizes the hierarchy rule ended with
   std::vector<int> agg_ptr, agg_rows;  // aggregates over all n dofs
   std::vector<int> aggof;              // n -> coarse index
   std::vector<double> E0, EM, EJ;      // kc x kc dense
@@ -98,6 +99,13 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
 // sweep (a velocity block touching more than 64 coarse columns)
 void build_setup_checked(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ricadi_opts& o,
                          HostSetup& hs, int max_levels, double sa_omega);
+
+// The hierarchy below a level, shared by ricadi_set_operator and ricadi_host_plan_hierarchy: the levels the top
+// context may use (build_setup's max_levels: 2 = no child), and the options and levels of the child of a level with
+// options o that may use `levels` (parent_is_child: that level is a child itself).
+int root_levels(const ricadi_opts& o);
+ricadi_opts child_opts(const ricadi_opts& o, bool parent_is_child);
+int child_levels(const ricadi_opts& o, int levels);
 
 // ---- device records of the preconditioner ------------------------------------------
 // Fixed-stride record of a 32-row velocity block (ricadi_ctx::sw_meta, SweepRecs::meta): a header of

@@ -70,11 +70,11 @@ static ricadi_ctx* walk_levels(ricadi_ctx* c, Batch& lb, Pred&& is) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 402; }
+int ricadi_version(void) { return 403; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
-const char* ricadi_struct_signature(void) { return "ricadi_opts:diiiiiiiiiiid;ricadi_adi_params:ididdiiii"; }
+const char* ricadi_struct_signature(void) { return "ricadi_opts:diiiiiiiiiiiid;ricadi_adi_params:ididdiiii"; }
 
 void ricadi_default_opts(ricadi_opts* o) {
   if (!o) return;
@@ -89,6 +89,7 @@ void ricadi_default_opts(ricadi_opts* o) {
   o->max_levels = 3;
   o->verbose = 0;
   o->compress_qr = 1;
+  o->hierarchy = 0;
   o->child_smoother = 0;
   o->child_damping = 0.7;
 }
@@ -175,12 +176,14 @@ int ricadi_set_opts(ricadi_ctx* c, const ricadi_opts* o) {
   REQUIRE(c && o, RICADI_EINVAL, "ricadi_set_opts: NULL argument");
   REQUIRE(o->gmres_restart >= 2 && o->gmres_restart <= 400, RICADI_EINVAL, "gmres_restart out of range");
   REQUIRE(o->gmres_tol > 0 && o->gmres_maxit > 0, RICADI_EINVAL, "bad gmres_tol / gmres_maxit");
+  REQUIRE(o->hierarchy == 0 || o->hierarchy == 1, RICADI_EINVAL, "hierarchy must be 0 or 1");
   REQUIRE(o->child_smoother == 0 || o->child_smoother == 1, RICADI_EINVAL, "child_smoother must be 0 or 1");
   REQUIRE(o->child_damping > 0 && o->child_damping <= 2, RICADI_EINVAL, "child_damping out of range");
   const bool structural = c->has_op && (o->bj_block != c->opts.bj_block || o->agg_v != c->opts.agg_v ||
                                         o->agg_p != c->opts.agg_p || o->coarse_max != c->opts.coarse_max ||
                                         o->max_levels != c->opts.max_levels ||
                                         o->use_coarse != c->opts.use_coarse ||
+                                        o->hierarchy != c->opts.hierarchy ||
                                         o->child_smoother != c->opts.child_smoother ||
                                         o->child_damping != c->opts.child_damping);
   REQUIRE(!structural, RICADI_ESTATE, "preconditioner options must be set before ricadi_set_operator");
@@ -227,8 +230,7 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   for (size_t k = 0; k < J.nnz(); ++k)
     if (J.ci[k] < 0 || J.ci[k] >= nv) throw ricadi::HipError{"J: column index out of range"};
   // everything shift independent, on the host
-  if (!c->borrowed)
-    c->levels = std::max(2, c->opts.max_levels);
+  if (!c->borrowed) c->levels = root_levels(c->opts);
   // smoothed aggregation of the velocity prolongation: two-level setups, folded preconditioner cycle only
   const double sa_omega = (c->borrowed || np == 0 || c->opts.bj_block != 32) ? 0.0 : c->sw.sa_omega;
   HostSetup hs;
@@ -244,13 +246,11 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
     ch->st = c->st;
     ch->rb = c->rb;
     ch->borrowed = true;
-    ch->opts = c->opts;
-    // aggregates of the child level (in units of ITS dofs = this level's aggregates); they double
-    // until the last level's dense inverse fits coarse_max
-    ch->opts.agg_v = 2;
-    ch->opts.agg_p = 1;
-    ch->opts.coarse_max = c->opts.coarse_max + c->opts.coarse_max / 8;   // pairs do not always pair up
-    ch->levels = 2;
+    // options and depth of the child level (ricadi_host.cpp; ricadi_host_plan_hierarchy walks the same chain): its
+    // aggregates are pairs and double until its dense inverse fits, or -- the fine hierarchy -- stay pairs with a
+    // child of its own below
+    ch->opts = child_opts(c->opts, c->borrowed);
+    ch->levels = child_levels(c->opts, c->levels);
     ch->sw = c->sw;
     ch->sw.timing = false;              // the parent times the child's setup as one phase
     ch->precond32 = c->precond32;
@@ -270,6 +270,8 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   c->nbv = hs.nbv;
   c->nbp = hs.nbp;
   c->kc = hs.kc;
+  c->agg_v = hs.agg_v;
+  c->agg_p = hs.agg_p;
   c->sa = hs.sa;
   c->snnz = hs.s_ci.size();
   c->s_rp.upload(hs.s_rp, st);
@@ -727,7 +729,7 @@ int ricadi_precond_structure(ricadi_ctx* c, int level, int32_t* sizes_out, int32
   const int nnzp = kc <= 0 ? 0 : l->sa ? (int)ptci.size() : n;
   const bool folds = cycle_form(l, 16, false, 0, false, false).folded;   // (whatever the panel width)
   const int32_t sz[16] = {l->nv, l->np, l->nbv, l->nbp, l->bs, kc, kcv, kc - kcv, l->sa ? 1 : 0, nnzp,
-                          l->child ? 1 : 0, folds ? 1 : 0, l->gt_ok ? 1 : 0, l->precond32 ? 1 : 0, 0, 0};
+                          l->child ? 1 : 0, folds ? 1 : 0, l->gt_ok ? 1 : 0, l->precond32 ? 1 : 0, l->agg_v, l->agg_p};
   std::copy(sz, sz + 16, sizes_out);
   down(bv_ptr, l->bv_ptr, (size_t)l->nbv + 1);
   down(bv_rows, l->bv_rows, (size_t)l->nv);
@@ -1253,6 +1255,11 @@ int ricadi_setup_info(ricadi_ctx* c, int* out, int nout) {
     for (int i = 0; i < 6; ++i)
       if (nout > 21 + i) out[21 + i] = v[i];
   }
+  // [27] .. [29]: the hierarchy rule in force, its levels as ricadi_host_plan_hierarchy counts them (grids with a
+  // sweep of their own), the dense inverse of the last one
+  if (nout > 27) out[27] = c->opts.hierarchy;
+  if (nout > 28) out[28] = lv - (c->kc > 0 ? 1 : 0);
+  if (nout > 29) out[29] = lc->kc;
   return RICADI_OK;
 }
 

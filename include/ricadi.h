@@ -393,7 +393,9 @@ int ricadi_sweep_recombine_dev(ricadi_ctx* ctx, int G, const double* dU, int m,
  * them; only the small coefficient table is permuted.  block_n2_out (G doubles, may be
  * NULL): squared Frobenius norm of every column block of dZ -- with coefz the rows of the
  * upper triangular R^-1 these are the blocks of the step-by-step iteration, which is what
- * the reference's stopping rule looks at.                                               */
+ * the reference's stopping rule looks at.  Up to 16 slots and 16 blocks the blocks and
+ * their norms come from the ADI driver's fused kernel (sums in a fixed order: the same
+ * inputs give bitwise the same norms); wider calls are served block by block.          */
 int ricadi_sweep_recombine_slots_dev(ricadi_ctx* ctx, int nslot, int G, const double* dU, int m,
                                      const double* coefz, const double* coefw,
                                      double* dZ, double* dW, double* n2_out, double* block_n2_out);

@@ -40,8 +40,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     B += (size_t)grp * gsB;
     C += (size_t)grp * gsC;
   }
-  // symmetric (A == B, Gram matrix): only tile blocks on / above the diagonal
-  // are computed, the strictly upper ones are mirrored when written
+  // symmetric (A == B, Gram matrix): only tile blocks on / above the diagonal are computed; the strictly upper
+  // ones are mirrored when written (wide form) or by gemm_mirror_kernel behind this launch (thin form)
   if (symmetric && blockIdx.z < by) return;
   const int lane = threadIdx.x & 63;
   const int wave_in_blk = threadIdx.x >> 6;
@@ -152,11 +152,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
           const double v = (red[0][idx][lane] + red[1][idx][lane]) + (red[2][idx][lane] + red[3][idx][lane]);
           const int row = i0 + 16 * a + lk + 4 * e;
           const int col = j0 + 16 * b + lc;
-          if (row < p && col < q) {
-            atomicAdd(&C[(size_t)row * ldc + col], v);
-            if (symmetric && blockIdx.z > by) atomicAdd(&C[(size_t)col * ldc + row], v);
-          }
+          // symmetric: the strict lower triangle is copied from the upper one afterwards (gemm_mirror_kernel)
+          if (row < p && col < q) atomicAdd(&C[(size_t)row * ldc + col], v);
         }
+  }
+}
+// C[i][j] = C[j][i] for j < i (p x p): the thin symmetric product is made EXACTLY symmetric.  Two atomics with the
+// same value per tile and row slice do not do that: with three and more slices the partial sums reach (i, j) and
+// (j, i) in different orders, and the two sums differ in the last bit.
+__global__ __launch_bounds__(256) void gemm_mirror_kernel(int p, double* __restrict__ C, int ldc) {
+  const size_t n = (size_t)p * p;
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    const int i = (int)(e / p), j = (int)(e % p);
+    if (j < i) C[(size_t)i * ldc + j] = C[(size_t)j * ldc + i];
   }
 }
 void launch_gemm_tn(hipStream_t st, int n, int p, int q, const double* A, int lda, const double* B,
@@ -190,9 +198,12 @@ void launch_gemm_tn_b(hipStream_t st, const GroupTab& gt, int n, int p, int q, c
   if (wide)
     hipLaunchKernelGGL((gemm_tn_kernel<4, 4>), grid, block, 0, st, gt, tp_, n, p, q, A, lda, B, ldb,
                        gsB, C, ldc, gsC, rows_per_wave, symmetric, combine);
-  else
+  else {
     hipLaunchKernelGGL((gemm_tn_kernel<2, 2>), grid, block, 0, st, gt, tp_, n, p, q, A, lda, B, ldb,
                        gsB, C, ldc, gsC, rows_per_wave, symmetric, 0);
+    if (symmetric && p > 1)
+      hipLaunchKernelGGL(gemm_mirror_kernel, dim3((p * p + 255) / 256), dim3(256), 0, st, p, C, ldc);
+  }
 }
 
 // gemm_nn:  Y (n x q) = alpha * A (n x p) * C (p x q) + beta * Y.

@@ -140,6 +140,32 @@ static void reduce_over_ranks(ricadi_ctx* c, double* v, int nsum, int nmax) {
   }
 }
 
+// The Z blocks of one sweep and their squared column norms: block j = sum_s coef[j][s] U_s (U_s = ubase + s * ustride,
+// the first NV rows of each; coef the replicated device table coef[(j nslot + s) m + c]) into columns
+// zc0 + j m .. of Z (leading dimension zld), norms2[j m + c] its squared column norms.  All blocks in the two
+// launches of the fused kernel (sums in a fixed order) where it takes the sizes -- nslot <= 16 and G <= 16 --,
+// else block by block through c->sweep_t.  Returns whether the fused kernel ran.  The caller has sized
+// c->sweep_t (NV x m), the GMRES workspace for width m (the per-block norms use its partials) and norms2 (G m).
+static bool sweep_blocks(ricadi_ctx* c, const double* ubase, size_t ustride, int nslot, int G, int m,
+                         const double* coef, double* Z, int zld, int zc0, double* norms2) {
+  hipStream_t st = c->st;
+  const int nv = c->nv;
+  const bool combined = sweep_combine_ok(m, nslot, G);
+  if (combined) {
+    // all blocks and their norms in two launches (K4s)
+    c->sweep_part.ensure(sweep_combine_partial_len(nv, m, G));
+    launch_sweep_combine(st, nv, m, nslot, G, ubase, ustride, coef, Z, zld, zc0, c->sweep_part.p, norms2);
+  } else {
+    for (int j = 0; j < G; ++j) {
+      launch_cols_update(st, nv, m, nslot, ubase, ustride, coef + (size_t)j * nslot * m, 1.0, nullptr, nullptr,
+                         c->sweep_t.p);
+      launch_copy_cols(st, nv, m, c->sweep_t.p, m, 0, Z, zld, zc0 + j * m, 1.0);
+      col_norms2(c, c->sweep_t.p, nv, m, norms2 + (size_t)j * m);
+    }
+  }
+  return combined;
+}
+
 static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, double* dW, int m,
                                 const ricadi_adi_params& prm, AdiStats& stt) {
   int G = std::min(std::min(prm.sweep_width, ns), RICADI_MAX_GROUPS);
@@ -361,20 +387,7 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
     HIPCHK(hipMemcpyAsync(c->sweep_coef.p, coef.data(), sizeof(double) * (size_t)Gs * nslot * m,
                           hipMemcpyHostToDevice, st));
     // Z <- [Z, U R^-1]: block j = sum_i rinv[i][j] U_i, with its squared norm
-    const bool combined = sweep_combine_ok(m, nslot, Gs);
-    if (combined) {
-      // all blocks and their norms in two launches (K4s)
-      c->sweep_part.ensure(sweep_combine_partial_len(nv, m, Gs));
-      launch_sweep_combine(st, nv, m, nslot, Gs, ubase, nm, c->sweep_coef.p, c->Z.p, c->zld, c->zc,
-                           c->sweep_part.p, c->nrm2.p);
-    } else {
-      for (int j = 0; j < Gs; ++j) {
-        launch_cols_update(st, nv, m, nslot, ubase, nm, c->sweep_coef.p + (size_t)j * nslot * m, 1.0,
-                           nullptr, nullptr, c->sweep_t.p);
-        launch_copy_cols(st, nv, m, c->sweep_t.p, m, 0, c->Z.p, c->zld, c->zc + j * m, 1.0);
-        col_norms2(c, c->sweep_t.p, nv, m, c->nrm2.p + (size_t)j * m);
-      }
-    }
+    const bool combined = sweep_blocks(c, ubase, nm, nslot, Gs, m, c->sweep_coef.p, c->Z.p, c->zld, c->zc, c->nrm2.p);
     hn.resize((size_t)Gs * m);
     HIPCHK(hipMemcpyAsync(hn.data(), c->nrm2.p, sizeof(double) * Gs * m, hipMemcpyDeviceToHost, st));
     std::vector<double> rwords;

@@ -894,7 +894,7 @@ int ricadi_sweep_recombine_slots_dev(ricadi_ctx* c, int nslot, int G, const doub
   ensure_work(c, m, std::min(G, RICADI_MAX_GROUPS));
   c->sweep_t.ensure(nvm);
   c->sweep_coef.ensure((size_t)(G + 1) * nslot * m);
-  c->scratch.ensure((size_t)G * m + 64);
+  c->nrm2.ensure((size_t)G * m);
   // coefficient rows replicated over the m columns: G columns of coefz, then coefw
   std::vector<double> coef((size_t)(G + 1) * nslot * m);
   for (int j = 0; j <= G; ++j)
@@ -904,20 +904,16 @@ int ricadi_sweep_recombine_slots_dev(ricadi_ctx* c, int nslot, int G, const doub
     }
   HIPCHK(hipMemcpyAsync(c->sweep_coef.p, coef.data(), sizeof(double) * coef.size(),
                         hipMemcpyHostToDevice, st));
-  // Z-block j = sum_i coefz[i][j] U_i  (columns j*m .. of dZ, leading dimension G*m)
-  for (int j = 0; j < G; ++j) {
-    launch_cols_update(st, nv, m, nslot, dU, nvm, c->sweep_coef.p + (size_t)j * nslot * m, 1.0, nullptr,
-                       nullptr, c->sweep_t.p);
-    launch_copy_cols(st, nv, m, c->sweep_t.p, m, 0, dZ, G * m, j * m, 1.0);
-    col_norms2(c, c->sweep_t.p, nv, m, c->scratch.p + (size_t)j * m);
-  }
+  // Z-block j = sum_i coefz[i][j] U_i  (columns j*m .. of dZ, leading dimension G*m): the ADI driver's own
+  // recombination (fused kernel up to 16 slots and 16 blocks, per block beyond)
+  sweep_blocks(c, dU, nvm, nslot, G, m, c->sweep_coef.p, dZ, G * m, 0, c->nrm2.p);
   // W += E (sum_i coefw[i] U_i)
   launch_cols_update(st, nv, m, nslot, dU, nvm, c->sweep_coef.p + (size_t)G * nslot * m, 1.0, nullptr,
                      nullptr, c->sweep_t.p);
   launch_spmm(st, nv, c->E.rp.p, c->E.ci.p, c->E.v.p, c->sweep_t.p, m, nullptr, dW, m, dW, m, 1.0, 1.0,
               nullptr, m);
   std::vector<double> nr((size_t)G * m);
-  HIPCHK(hipMemcpyAsync(nr.data(), c->scratch.p, sizeof(double) * G * m, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(nr.data(), c->nrm2.p, sizeof(double) * G * m, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));   // also keeps `coef` alive until its upload has run
   double n2 = 0.0;
   for (double v : nr) n2 += v;

@@ -315,10 +315,10 @@ static void panel_cholqr2_wide(ricadi_ctx* c, const double* P, int ldp, int n, i
 // D = Q R for a tall n x kk matrix (ldd): block classical Gram-Schmidt with
 // re-orthogonalisation between panels (both passes on the FP64 MFMA GEMMs).  Inside a panel:
 // CholQR2 on the matrix cores -- panels of 128 columns (panel_cholqr2_wide; round 2: 32 columns,
-// ~20 dependent launches per panel, RICADI_QR_PANEL=32 restores it) when the panel allows it --
+// ~20 dependent launches per panel) when the panel allows it --
 // checked once, after the last panel -- else the whole factorisation is redone with 32-column panels
 // through the Householder TSQR tree (numerically rank-deficient panels, e.g. raw
-// ADI blocks; RICADI_TSQR_HOUSEHOLDER=1 forces it).  Q: n x kk (ld kk), R: kk x kk
+// ADI blocks).  Q: n x kk (ld kk), R: kk x kk
 // row-major upper triangular.  No panel straddles column `split` (the update norm factorises [Z_new, Z_old]).
 static void block_qr_dev(ricadi_ctx* c, const double* D, int ldd, int n, int kk, double* Q,
                          double* R, int split = 0) {

@@ -452,6 +452,49 @@ int ricadi_time_kernel_dev(ricadi_ctx* ctx, int which, int ng, const double* alp
                            const double* betas, int m, int nvec, int reps,
                            double* ms_per_launch);
 
+/* Step probe of the lockstep GMRES (tests): the units the solver's restart cycle is made of, one call each, on the
+ * solver's own workspace and with the batch, iteration form and kernel choice of a solve of ng groups of width m --
+ * without the preconditioner and the operator: the caller supplies w = S P^-1 v_j.  All pointers are device
+ * pointers unless noted; every call is synchronous.  Group-major panels [ng][n][m], n = NV + NP.
+ *   begin: the cycle start (norms of the residual panels dR, g, scale, first Krylov vector into slot 0) for all ng
+ *          groups; dBnorm [ng][m]: ||b|| per column, as the frozen-column rule reads it.  What no later call writes
+ *          reads back as NaN.
+ *   step:  the Arnoldi phase of iteration j (0 <= j < gmres_restart) on the panels dW, for the nact groups listed in
+ *          `groups` (host; ids in 0 .. ng-1); the panels of the other groups are not touched.
+ *   close: the cycle end for all groups, group g with its first ks[g] vectors (host; 0 <= ks[g] <= steps run for g):
+ *          one-reduction form: completion of column ks[g] - 1; R y = g; dX += Z y with the nz FP32 slots
+ *          dZ [nz][ng][n][m] (copied into the solver's Z storage).
+ *   read:  a workspace array as FP64 into dOut (capacity cap doubles; *count: doubles written).  `slot`: Krylov
+ *          vector for RICADI_PROBE_BASIS, ignored otherwise.
+ * RICADI_EINVAL before anything is launched for j, ng, m, a group id or a slot out of range, and for step / close /
+ * read without a begin on the current workspace.                                                                 */
+#define RICADI_PROBE_BASIS 0    /* Krylov vector `slot`, [ng][n][m], converted from its stored type                */
+#define RICADI_PROBE_W 1        /* the FP64 panel w, [ng][n][m]                                                    */
+#define RICADI_PROBE_W32 2      /* the FP32 panel w                                                                */
+#define RICADI_PROBE_VCUR 3     /* FP64 copy of the newest Krylov vector (FP16 / FP32 basis)                       */
+#define RICADI_PROBE_H1 4       /* first-pass coefficients, [ng][gmres_restart + 2][m]                             */
+#define RICADI_PROBE_H2 5       /* second pass; row j + 1: ||w'||^2                                                */
+#define RICADI_PROBE_HSUM 6     /* h1 + h2 as the separate Hessenberg kernel leaves it for an update from w        */
+#define RICADI_PROBE_H 7        /* [ng][m][gmres_restart][gmres_restart + 1]: column j of R, entries 0 .. j + 1    */
+#define RICADI_PROBE_CS 8       /* [ng][m][gmres_restart]                                                          */
+#define RICADI_PROBE_SN 9
+#define RICADI_PROBE_G 10       /* [ng][m][gmres_restart + 1]                                                      */
+#define RICADI_PROBE_SCALE 11   /* [ng][m]                                                                         */
+#define RICADI_PROBE_RESID0 12  /* residual estimates, buffer 0 and 1, [ng][m] each                                */
+#define RICADI_PROBE_RESID1 13
+#define RICADI_PROBE_Y 14       /* [ng][gmres_restart][m]                                                          */
+#define RICADI_PROBE_NRM2 15    /* squared norms of the cycle start, [ng][m]                                       */
+#define RICADI_PROBE_LS_COEF 16 /* one-reduction form, per group: sums [gmres_restart + 2][s|t][16], then two pending
+                                 * columns of gmres_restart + 3 rows of 16 (p, rho, g before the rotation)          */
+#define RICADI_PROBE_FORM 17    /* 8 values 0 / 1: FP16 basis, FP32 basis, preconditioner reads FP16, w kept, fused
+                                 * Hessenberg, FP32 operator input, FP32 panel w, one-reduction form               */
+int ricadi_arnoldi_probe_begin_dev(ricadi_ctx* ctx, int ng, const double* alphas, const double* betas, int m,
+                                   const double* dR, const double* dBnorm);
+int ricadi_arnoldi_probe_step_dev(ricadi_ctx* ctx, int j, const double* dW, int nact, const int* groups);
+int ricadi_arnoldi_probe_close_dev(ricadi_ctx* ctx, const int* ks, int nz, const float* dZ, double* dX);
+int ricadi_arnoldi_probe_read_dev(ricadi_ctx* ctx, int what, int slot, double* dOut, int64_t cap,
+                                  int64_t* count);
+
 /* K5: thin QR factorisation Z = Q R of an NV x c host matrix (c <= NV) by block
  * Gram-Schmidt with re-orthogonalisation over 32-column panels, each panel
  * factorised by a Householder TSQR tree.  R_out: c x c row-major upper triangular;

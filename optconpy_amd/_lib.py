@@ -20,7 +20,7 @@ RICADI_ENOCONV = -3
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 403
+ABI_VERSION = 404
 
 
 class RicadiOpts(C.Structure):
@@ -101,6 +101,10 @@ SIGNATURES = {
                                        _dp]),
     "ricadi_time_kernel_dev": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(C.c_double)]),
+    "ricadi_arnoldi_probe_begin_dev": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _vp, _vp]),
+    "ricadi_arnoldi_probe_step_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int)]),
+    "ricadi_arnoldi_probe_close_dev": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int, _vp, _vp]),
+    "ricadi_arnoldi_probe_read_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     "ricadi_qr": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "ricadi_project_pencil": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "ricadi_project_pencil_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
@@ -704,6 +708,37 @@ class Context:
         _chk(self._lib.ricadi_time_kernel_dev(self._h, int(self.TK.get(which, which)), al.size, _d(al),
                                               _d(be), int(m), int(nvec), int(reps), C.byref(ms)))
         return ms.value
+
+    # RICADI_PROBE_* of include/ricadi.h
+    PROBE = dict(basis=0, w=1, w32=2, vcur=3, h1=4, h2=5, hsum=6, H=7, cs=8, sn=9, g=10, scale=11, resid0=12,
+                 resid1=13, y=14, nrm2=15, ls_coef=16, form=17)
+    PROBE_FORM = ("b16", "b32", "h16", "keepw", "fuseh", "x32", "w32", "lowsync")
+
+    def arnoldi_probe_begin_dev(self, alphas, betas, m, r_ptr, bnorm_ptr):
+        """Cycle start of the step probe for ``len(alphas)`` groups of width ``m``: residual panels
+        ``[ng][n][m]`` at ``r_ptr``, ``||b||`` per column ``[ng][m]`` at ``bnorm_ptr`` (device)."""
+        al = np.ascontiguousarray(alphas, dtype=np.float64)
+        be = np.ascontiguousarray(betas, dtype=np.float64)
+        _chk(self._lib.ricadi_arnoldi_probe_begin_dev(self._h, al.size, _d(al), _d(be), int(m), r_ptr, bnorm_ptr))
+
+    def arnoldi_probe_step_dev(self, j, w_ptr, groups):
+        """The Arnoldi phase of iteration ``j`` on the FP64 panels ``[ng][n][m]`` at ``w_ptr`` for ``groups``."""
+        g = (C.c_int * len(groups))(*[int(x) for x in groups])
+        _chk(self._lib.ricadi_arnoldi_probe_step_dev(self._h, int(j), w_ptr, len(groups), g))
+
+    def arnoldi_probe_close_dev(self, ks, nz, z_ptr, x_ptr):
+        """Cycle end: group ``g`` with ``ks[g]`` vectors, the FP32 slots ``[nz][ng][n][m]`` at ``z_ptr``,
+        ``x += Z y`` on the FP64 panels at ``x_ptr``."""
+        k = (C.c_int * len(ks))(*[int(x) for x in ks])
+        _chk(self._lib.ricadi_arnoldi_probe_close_dev(self._h, k, int(nz), z_ptr, x_ptr))
+
+    def arnoldi_probe_read_dev(self, what, out_ptr, cap, slot=0):
+        """Workspace array ``what`` (``Context.PROBE``) as FP64 into ``out_ptr`` (room for ``cap`` doubles);
+        returns the number of doubles written."""
+        cnt = C.c_int64(0)
+        _chk(self._lib.ricadi_arnoldi_probe_read_dev(self._h, int(self.PROBE.get(what, what)), int(slot), out_ptr,
+                                                     int(cap), C.byref(cnt)))
+        return int(cnt.value)
 
     def setup_info(self):
         a = (C.c_int * 30)()

@@ -258,6 +258,9 @@ struct Switches {
                               // sweep with its loads in one round (the forms before the pipelined kernels)
   bool lowsync = true;        // RICADI_ARNOLDI=cgs2: the three-pass CGS2 Arnoldi on the hot path instead of the
                               // one-reduction form
+  bool fuseh = true;          // RICADI_FUSEH=0: the Hessenberg / Givens update of the hot width in its own launch
+                              // (gmres_hess_kernel; w stays kept, the last pass takes h1 + h2 from that kernel, the
+                              // panel w stays FP64) instead of inside the last Arnoldi pass
   bool split = true;          // RICADI_SPLIT=0: the lockstep GMRES batch on one stream instead of two half-batches
   bool setup_overlap = true;  // RICADI_SETUP_OVERLAP=0: the ADI shifts and the projection operator set up in one batch
                               // before the projection solve, instead of the shifts' setup beside it (setup_overlap_begin)
@@ -422,6 +425,14 @@ struct ricadi_ctx {
   long xcount = 0;            // collectives issued so far (ricadi_exchange_count)
   int coarse_route = -1;      // route the last batch of coarse inverses took (invert_dense_batch); -1: none yet
   int k1_variant = -1;        // saddle SpMM kernel of the last batched launch (saddle_spmm): 0 CSR, 1 tiled, 2 tiled multi-shift; +4: FP32 x
+  // step probe of the Arnoldi phase (ricadi_arnoldi_probe_*_dev, tests): the batch of its last begin, the steps run
+  // per group since, and the workspace that begin filled (another call may have replaced it)
+  struct ArnoldiProbe {
+    int ng = 0, m = 0;
+    std::vector<double> alpha, beta;
+    std::vector<int> kdone;
+    const double* work = nullptr;
+  } probe;
   // stats
   long total_iters = 0, total_solves = 0;
   long escalations = 0;       // solves repeated with wider storage of basis / preconditioner (safety net)

@@ -70,7 +70,7 @@ static ricadi_ctx* walk_levels(ricadi_ctx* c, Batch& lb, Pred&& is) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 403; }
+int ricadi_version(void) { return 404; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
@@ -135,6 +135,7 @@ static Switches read_switches() {
   s.mid32 = !off("RICADI_MID32");
   s.coarse_pipe = !off("RICADI_COARSE_PIPE");
   if (const char* e = getenv("RICADI_ARNOLDI")) s.lowsync = strcmp(e, "cgs2") != 0;
+  s.fuseh = !off("RICADI_FUSEH");
   s.split = !off("RICADI_SPLIT");
   s.setup_overlap = !off("RICADI_SETUP_OVERLAP");
   return s;
@@ -1139,6 +1140,209 @@ int ricadi_time_kernel_dev(ricadi_ctx* c, int which, int ng, const double* alpha
   } else {
     launch();   // warm-up (code object load, caches)
     *ms_per_launch = timed_ms(st, reps, launch);
+  }
+  API_END
+}
+
+// ---- step probe of the Arnoldi phase (tests) -------------------------------------------------------------------
+// The units the lockstep GMRES is made of -- cycle_start_launches, arnoldi_launches, cycle_end_launches of
+// solver_gmres.inl -- one call each on the solver's own workspace, with the batch, the iteration form and the cycle
+// form decided as for a solve, and the workspace read back in FP64.  The preconditioner and the operator are not run:
+// the caller supplies w.  Synchronous.
+namespace {
+struct ProbeSetup {
+  std::vector<ShiftData*> sds;
+  Batch bt;
+  IterationForm f;
+  CycleForm pf;
+  ProbeSetup(ricadi_ctx* c, int ng, const double* alphas, const double* betas, int m) : sds(ng) {
+    get_shifts(c, alphas, betas, ng, sds.data());
+    ensure_work(c, m, ng, 0);
+    bt = make_batch(c, sds.data(), ng, m);
+    f = iteration_form(c, m, ng, false);
+    pf = cycle_form(c, m, bt.blocks16, bt.gs, f.x32, f.h16);
+    c->w32_last = f.w32 ? 1 : 0;
+  }
+  // the batch of the last begin (step, close, read)
+  explicit ProbeSetup(ricadi_ctx* c)
+      : ProbeSetup(c, c->probe.ng, c->probe.alpha.data(), c->probe.beta.data(), c->probe.m) {}
+};
+// begin has run and the workspace it filled is still the context's
+bool probe_live(const ricadi_ctx* c) {
+  return c->probe.ng > 0 && c->probe.work == c->wv.p && c->wrestart == c->opts.gmres_restart;
+}
+double half_bits_to_double(uint16_t h) {
+  const int e = (h >> 10) & 31, f = h & 1023;
+  double v = e == 0 ? std::ldexp((double)f, -24) : e == 31 ? (f ? NAN : INFINITY) : std::ldexp(1024.0 + f, e - 25);
+  return (h & 0x8000) ? -v : v;
+}
+// count stored values of `bytes` bytes each (2: FP16, 4: FP32, 8: FP64) at src, as FP64 at dst (both device)
+void probe_widen(ricadi_ctx* c, const void* src, int bytes, size_t count, double* dst) {
+  if (bytes == 8) {
+    HIPCHK(hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyDeviceToDevice, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return;
+  }
+  std::vector<unsigned char> raw(count * bytes);
+  std::vector<double> wide(count);
+  HIPCHK(hipMemcpyAsync(raw.data(), src, raw.size(), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  for (size_t i = 0; i < count; ++i) {
+    if (bytes == 2) {
+      uint16_t h;
+      std::memcpy(&h, raw.data() + 2 * i, 2);
+      wide[i] = half_bits_to_double(h);
+    } else {
+      float x;
+      std::memcpy(&x, raw.data() + 4 * i, 4);
+      wide[i] = (double)x;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(dst, wide.data(), sizeof(double) * count, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+}
+}  // namespace
+
+int ricadi_arnoldi_probe_begin_dev(ricadi_ctx* c, int ng, const double* alphas, const double* betas, int m,
+                                   const double* dR, const double* dBnorm) {
+  if (int rc = check_panel(c, m)) return rc;
+  REQUIRE(alphas && betas && dR && dBnorm, RICADI_EINVAL, "bad argument");
+  REQUIRE(ng >= 1 && ng <= RICADI_MAX_GROUPS && (size_t)ng * m <= 2048, RICADI_EINVAL,
+          "1 <= ng <= 16 and ng*m <= 2048 required");
+  API_BEGIN
+  hipStream_t st = c->st;
+  c->probe = ricadi_ctx::ArnoldiProbe();
+  ProbeSetup p(c, ng, alphas, betas, m);
+  const int restart = c->opts.gmres_restart;
+  const size_t vs = p.bt.gs * ng, gm = (size_t)ng * m, gsh = (size_t)(restart + 2) * c->wcols;
+  // whatever a step does not write reads back as NaN (all bits set, in every storage type)
+  if (c->basis32) HIPCHK(hipMemsetAsync(c->basisf.p, 0xFF, (size_t)(restart + 1) * vs * (p.f.b16 ? 2 : 4), st));
+  else HIPCHK(hipMemsetAsync(c->basis.p, 0xFF, sizeof(double) * (restart + 1) * vs, st));
+  HIPCHK(hipMemsetAsync(c->h1.p, 0xFF, sizeof(double) * gsh, st));
+  HIPCHK(hipMemsetAsync(c->h2.p, 0xFF, sizeof(double) * 2 * gsh, st));
+  HIPCHK(hipMemsetAsync(c->H.p, 0xFF, sizeof(double) * gm * (restart + 1) * restart, st));
+  HIPCHK(hipMemsetAsync(c->cs.p, 0xFF, sizeof(double) * gm * restart, st));
+  HIPCHK(hipMemsetAsync(c->sn.p, 0xFF, sizeof(double) * gm * restart, st));
+  HIPCHK(hipMemsetAsync(c->yv.p, 0xFF, sizeof(double) * gm * restart, st));
+  HIPCHK(hipMemsetAsync(c->resid.p, 0xFF, sizeof(double) * 2 * c->wcols, st));
+  HIPCHK(hipMemsetAsync(c->ls_coef.p, 0xFF, sizeof(double) * c->ls_coef.n, st));
+  HIPCHK(hipMemcpyAsync(c->wv.p, dR, sizeof(double) * vs, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->bnorm2.p, dBnorm, sizeof(double) * gm, hipMemcpyDeviceToDevice, st));
+  p.bt.all();
+  cycle_start_launches(c, p.f, p.bt, [] { return true; });
+  HIPCHK(hipStreamSynchronize(st));
+  c->probe.ng = ng;
+  c->probe.m = m;
+  c->probe.alpha.assign(alphas, alphas + ng);
+  c->probe.beta.assign(betas, betas + ng);
+  c->probe.kdone.assign(ng, 0);
+  c->probe.work = c->wv.p;
+  API_END
+}
+
+int ricadi_arnoldi_probe_step_dev(ricadi_ctx* c, int j, const double* dW, int nact, const int* groups) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(probe_live(c), RICADI_EINVAL, "no probe cycle: call ricadi_arnoldi_probe_begin_dev first");
+  REQUIRE(j >= 0 && j < c->opts.gmres_restart, RICADI_EINVAL, "0 <= j < gmres_restart required");
+  REQUIRE(dW && groups && nact >= 1 && nact <= c->probe.ng, RICADI_EINVAL, "bad argument");
+  for (int i = 0; i < nact; ++i)
+    REQUIRE(groups[i] >= 0 && groups[i] < c->probe.ng, RICADI_EINVAL, "group id outside 0 .. ng-1");
+  (void)hipSetDevice(c->dev);
+  API_BEGIN
+  hipStream_t st = c->st;
+  ProbeSetup p(c);
+  const int m = c->probe.m;
+  const size_t nm = p.bt.gs;
+  p.bt.set(std::vector<int>(groups, groups + nact));
+  // w as the iteration reads it
+  for (int i = 0; i < nact; ++i) {
+    const size_t off = (size_t)groups[i] * nm;
+    if (p.f.w32) launch_to_f32(st, c->n, m, dW + off, m, c->wv32.p + off, m);
+    else HIPCHK(hipMemcpyAsync(c->wv.p + off, dW + off, sizeof(double) * nm, hipMemcpyDeviceToDevice, st));
+  }
+  const size_t slot = (size_t)RICADI_MAX_M * RICADI_MAX_GROUPS;
+  arnoldi_launches(c, p.f, p.bt, j, c->h_resid + 2 * slot + (size_t)(j & 1) * slot);
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < nact; ++i) c->probe.kdone[groups[i]] = j + 1;
+  API_END
+}
+
+int ricadi_arnoldi_probe_close_dev(ricadi_ctx* c, const int* ks, int nz, const float* dZ, double* dX) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(probe_live(c), RICADI_EINVAL, "no probe cycle: call ricadi_arnoldi_probe_begin_dev first");
+  REQUIRE(ks && dZ && dX && nz >= 1 && nz <= c->opts.gmres_restart, RICADI_EINVAL, "bad argument");
+  for (int g = 0; g < c->probe.ng; ++g)
+    REQUIRE(ks[g] >= 0 && ks[g] <= nz && ks[g] <= c->probe.kdone[g], RICADI_EINVAL,
+            "0 <= k_g <= min(nz, steps run for the group) required");
+  (void)hipSetDevice(c->dev);
+  API_BEGIN
+  hipStream_t st = c->st;
+  ProbeSetup p(c);
+  GroupInts kk = same_int(0);
+  for (int g = 0; g < c->probe.ng; ++g) kk.v[g] = ks[g];
+  HIPCHK(hipMemcpyAsync(c->zbasisf.p, dZ, sizeof(float) * (size_t)nz * p.bt.gs * c->probe.ng, hipMemcpyDeviceToDevice,
+                        st));
+  p.bt.all();
+  cycle_end_launches(c, p.f, p.bt, kk, dX);
+  HIPCHK(hipStreamSynchronize(st));
+  API_END
+}
+
+int ricadi_arnoldi_probe_read_dev(ricadi_ctx* c, int what, int slot, double* dOut, int64_t cap, int64_t* count) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(probe_live(c), RICADI_EINVAL, "no probe cycle: call ricadi_arnoldi_probe_begin_dev first");
+  REQUIRE(dOut && count && cap >= 0, RICADI_EINVAL, "bad argument");
+  const int restart = c->opts.gmres_restart, ng = c->probe.ng, m = c->probe.m;
+  REQUIRE(what != RICADI_PROBE_BASIS || (slot >= 0 && slot <= restart), RICADI_EINVAL,
+          "0 <= slot <= gmres_restart required");
+  (void)hipSetDevice(c->dev);
+  API_BEGIN
+  ProbeSetup p(c);
+  const IterationForm& f = p.f;
+  const size_t gm = (size_t)ng * m, vs = p.bt.gs * ng, h2buf = (size_t)(restart + 2) * c->wcols;
+  const void* src = nullptr;
+  int bytes = 8;
+  size_t cnt = 0;
+  switch (what) {
+    case RICADI_PROBE_BASIS:
+      bytes = f.b16 ? 2 : f.b32 ? 4 : 8;
+      src = c->basis32 ? (const char*)c->basisf.p + (size_t)slot * vs * bytes : (const char*)(c->basis.p + (size_t)slot * vs);
+      cnt = vs;
+      break;
+    case RICADI_PROBE_W: src = c->wv.p, cnt = vs; break;
+    case RICADI_PROBE_W32: src = c->wv32.p, bytes = 4, cnt = vs; break;
+    case RICADI_PROBE_VCUR:
+      if (!c->basis32) throw HipError{"no FP64 copy of the current vector with the FP64-stored basis"};
+      src = c->vcur.p, cnt = vs;
+      break;
+    case RICADI_PROBE_H1: src = c->h1.p, cnt = (size_t)(restart + 2) * gm; break;
+    case RICADI_PROBE_H2: src = c->h2.p, cnt = (size_t)(restart + 2) * gm; break;
+    case RICADI_PROBE_HSUM: src = c->h2.p + h2buf, cnt = (size_t)(restart + 2) * gm; break;
+    case RICADI_PROBE_H: src = c->H.p, cnt = gm * (restart + 1) * restart; break;
+    case RICADI_PROBE_CS: src = c->cs.p, cnt = gm * restart; break;
+    case RICADI_PROBE_SN: src = c->sn.p, cnt = gm * restart; break;
+    case RICADI_PROBE_G: src = c->g.p, cnt = gm * (restart + 1); break;
+    case RICADI_PROBE_SCALE: src = c->scale.p, cnt = gm; break;
+    case RICADI_PROBE_RESID0: src = c->resid.p, cnt = gm; break;
+    case RICADI_PROBE_RESID1: src = c->resid.p + c->wcols, cnt = gm; break;
+    case RICADI_PROBE_Y: src = c->yv.p, cnt = gm * restart; break;
+    case RICADI_PROBE_NRM2: src = c->nrm2.p, cnt = gm; break;
+    case RICADI_PROBE_LS_COEF:
+      if (!f.lowsync) throw HipError{"not the one-reduction form"};
+      src = c->ls_coef.p, cnt = (size_t)ng * lowsync_coef_stride(restart);
+      break;
+    case RICADI_PROBE_FORM: cnt = 8; break;
+    default: throw HipError{"unknown probe quantity"};
+  }
+  *count = (int64_t)cnt;
+  if ((int64_t)cnt > cap) throw HipError{"output buffer too small"};
+  if (what == RICADI_PROBE_FORM) {
+    const double bits[8] = {(double)f.b16,   (double)f.b32, (double)f.h16, (double)f.keepw,
+                            (double)f.fuseh, (double)f.x32, (double)f.w32, (double)f.lowsync};
+    HIPCHK(hipMemcpyAsync(dOut, bits, sizeof(bits), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+  } else {
+    probe_widen(c, src, bytes, cnt, dOut);
   }
   API_END
 }

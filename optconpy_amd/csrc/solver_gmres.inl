@@ -39,7 +39,7 @@ static IterationForm iteration_form(const ricadi_ctx* c, int m, int G, bool lowr
   f.b32 = c->basis32 && !f.b16;
   f.h16 = precond_reads_h16(c, m);
   f.keepw = update_dots_keeps_w(m, f.b16, restart);
-  f.fuseh = update_hess_fused_ok(m, f.b16);
+  f.fuseh = c->sw.fuseh && update_hess_fused_ok(m, f.b16);   // (RICADI_FUSEH=0: the separate Hessenberg kernel)
   // FP32 operator input for a batch of G groups: always with the multi-shift kernel; with one workgroup per (row
   // block, group) the FP32 input by itself measured 1.4 % slower at cfg2 in round 3, but it is what lets the cycle
   // keep its velocity part in FP32 and its blocks in BF16 (round 4), which more than pays for it (RICADI_X32=0: only
@@ -153,20 +153,10 @@ static void arnoldi_lowsync_update(ricadi_ctx* c, const Batch& bt, int j, double
                                   c->resid.p + (size_t)(j & 1) * c->wcols, host_resid);
 }
 
-// The launches of lockstep iteration j for the groups of bt.tab, on bt.st (gmres_core and the kernel timers):
-// preconditioner, operator, Arnoldi.  Residual estimates of the iteration also go to host_resid (may be null).
-static void iteration_launches(ricadi_ctx* c, const IterationForm& f, const CycleForm& pf, const Batch& bt, int j,
-                               bool lowrank, double* host_resid) {
-  const size_t nm = bt.gs, vs = nm * bt.G;
-  const double* vj = (f.b32 || f.b16) ? c->vcur.p : c->basis.p + (size_t)j * vs;
-  _Float16* Vh = reinterpret_cast<_Float16*>(c->basisf.p);   // FP16 storage shares the FP32 buffer
-  // flexible form: Z_j = P^-1 v_j is kept (FP32), the cycle's correction is x += Z y -- no
-  // preconditioner application at the cycle end, and P may differ from step to step
-  // ... and the operator reads that stored FP32 copy (half the bytes of the x gathers; S Z_j = V H then
-  // holds for exactly the vectors the correction uses), so the sweeps need not store the FP64 z at all
-  float* zj = c->zbasisf.p + (size_t)j * vs;
-  precond_apply(c, bt, pf, CycleIO{vj, nm, f.h16 ? Vh + (size_t)j * vs : nullptr, c->zv.p, zj, nm});
-  op_apply(c, bt, c->zv.p, nm, c->wv.p, lowrank, f.x32 ? zj : nullptr, f.w32 ? c->wv32.p : nullptr);
+// The Arnoldi phase of lockstep iteration j on w = S z_j (in wv / wv32, as f says) for the groups of bt.tab
+// (iteration_launches and the step probe of solver_capi.inl): column j of the Hessenberg matrix, its rotation, the
+// residual estimates (also to host_resid, may be null) and the next Krylov vector.
+static void arnoldi_launches(ricadi_ctx* c, const IterationForm& f, const Batch& bt, int j, double* host_resid) {
   if (f.lowsync) {
     // slot j holds the candidate u_j the preconditioner read; v_j replaces it, u_{j+1} goes to slot j + 1
     arnoldi_lowsync_dots(c, bt, same_int(j), false);
@@ -181,6 +171,54 @@ static void iteration_launches(ricadi_ctx* c, const IterationForm& f, const Cycl
                           f.keepw ? c->h2.p + (size_t)(restart + 2) * c->wcols : nullptr);
     arnoldi_update(c, f, bt, j + 1, host_resid);
   }
+}
+
+// Start of a restart cycle for the groups of bt.tab, from their residual panels in wv: norms, g = [||r||, 0 ..],
+// scale = 1 / ||r||, then -- after decide(), which may narrow bt.tab from the norms (false: no group goes on, nothing
+// more is launched) -- the first Krylov vector, the scaled residual, into slot 0 (LockstepSolve::begin_cycle and
+// the probe).
+template <class Decide>
+static bool cycle_start_launches(ricadi_ctx* c, const IterationForm& f, Batch& bt, Decide&& decide) {
+  const size_t nm = bt.gs;
+  panel_norms2(c, bt, c->wv.p, nm, c->nrm2.p);
+  launch_gmres_start_b(bt.st, bt.tab, bt.m, c->opts.gmres_restart, c->nrm2.p, c->g.p, c->scale.p, c->resid.p);
+  if (!decide()) return false;
+  with_basis(c, f, [&](auto* V) {
+    if constexpr (std::is_same<std::remove_pointer_t<decltype(V)>, double>::value)
+      launch_colscale_b(bt.st, bt.tab, c->n, bt.m, c->scale.p, c->wv.p, nm, 0.0, V, nm);
+    else
+      launch_colscale_b(bt.st, bt.tab, c->n, bt.m, c->scale.p, c->wv.p, nm, 0.0, c->vcur.p, nm, V, nm);
+  });
+  return true;
+}
+
+// End of a restart cycle for the groups of bt.tab: x_g += Z_g y_g with the kk.v[g] preconditioned vectors group g
+// built, R y = g per column (one launch each for all groups, k_g by value; end_cycle and the probe).
+static void cycle_end_launches(ricadi_ctx* c, const IterationForm& f, const Batch& bt, const GroupInts& kk, double* x) {
+  const int restart = c->opts.gmres_restart;
+  const size_t nm = bt.gs, vs = nm * bt.G;
+  // one-reduction form: the last column of every group still waits for the correction of its candidate u_{k_g}
+  if (f.lowsync) arnoldi_lowsync_dots(c, bt, kk, true);
+  launch_gmres_backsolve_b(bt.st, bt.tab, bt.m, kk, restart, c->H.p, c->g.p, c->yv.p);
+  launch_cols_update_bk(bt.st, bt.tab, c->n, bt.m, kk, c->zbasisf.p, vs, nm, c->yv.p, (size_t)restart * bt.m, x, nm, x,
+                        nm);
+}
+
+// The launches of lockstep iteration j for the groups of bt.tab, on bt.st (gmres_core and the kernel timers):
+// preconditioner, operator, Arnoldi.  Residual estimates of the iteration also go to host_resid (may be null).
+static void iteration_launches(ricadi_ctx* c, const IterationForm& f, const CycleForm& pf, const Batch& bt, int j,
+                               bool lowrank, double* host_resid) {
+  const size_t nm = bt.gs, vs = nm * bt.G;
+  const double* vj = (f.b32 || f.b16) ? c->vcur.p : c->basis.p + (size_t)j * vs;
+  _Float16* Vh = reinterpret_cast<_Float16*>(c->basisf.p);   // FP16 storage shares the FP32 buffer
+  // flexible form: Z_j = P^-1 v_j is kept (FP32), the cycle's correction is x += Z y -- no
+  // preconditioner application at the cycle end, and P may differ from step to step
+  // ... and the operator reads that stored FP32 copy (half the bytes of the x gathers; S Z_j = V H then
+  // holds for exactly the vectors the correction uses), so the sweeps need not store the FP64 z at all
+  float* zj = c->zbasisf.p + (size_t)j * vs;
+  precond_apply(c, bt, pf, CycleIO{vj, nm, f.h16 ? Vh + (size_t)j * vs : nullptr, c->zv.p, zj, nm});
+  op_apply(c, bt, c->zv.p, nm, c->wv.p, lowrank, f.x32 ? zj : nullptr, f.w32 ? c->wv32.p : nullptr);
+  arnoldi_launches(c, f, bt, j, host_resid);
 }
 
 // ---- two half-batches on two streams ----------------------------------------------------
@@ -420,20 +458,15 @@ struct LockstepSolve {
     lap(c->t_iter);
     bt.set(act);
     residual();
-    panel_norms2(c, bt, c->wv.p, nm, c->nrm2.p);
-    launch_gmres_start_b(st, bt.tab, m, restart, c->nrm2.p, c->g.p, c->scale.p, c->resid.p);
-    HIPCHK(hipMemcpyAsync(hb, c->resid.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    act = next_active(hb);
-    if (act.empty()) return false;
-    // first Krylov vector: the scaled residual
-    bt.set(act);
-    with_basis(c, f, [&](auto* V) {
-      if constexpr (std::is_same<std::remove_pointer_t<decltype(V)>, double>::value)
-        launch_colscale_b(st, bt.tab, c->n, m, c->scale.p, c->wv.p, nm, 0.0, V, nm);
-      else
-        launch_colscale_b(st, bt.tab, c->n, m, c->scale.p, c->wv.p, nm, 0.0, c->vcur.p, nm, V, nm);
+    // who goes on is decided on the host from the residual norms; their first Krylov vector: the scaled residual
+    const bool go = cycle_start_launches(c, f, bt, [&] {
+      HIPCHK(hipMemcpyAsync(hb, c->resid.p, sizeof(double) * GM, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      act = next_active(hb);
+      bt.set(act);
+      return !act.empty();
     });
+    if (!go) return false;
     live = act;
     kk = same_int(0);
     return true;
@@ -490,10 +523,7 @@ struct LockstepSolve {
   // (one launch each for all groups of the cycle, k_g per group by value)
   void end_cycle() {
     bt.set(act);
-    // one-reduction form: the last column of every group still waits for the correction of its candidate u_{k_g}
-    if (f.lowsync) arnoldi_lowsync_dots(c, bt, kk, true);
-    launch_gmres_backsolve_b(st, bt.tab, m, kk, restart, c->H.p, c->g.p, c->yv.p);
-    launch_cols_update_bk(st, bt.tab, c->n, m, kk, c->zbasisf.p, vs, nm, c->yv.p, (size_t)restart * m, x, nm, x, nm);
+    cycle_end_launches(c, f, bt, kk, x);
     lap(c->t_cyc);
   }
 

@@ -568,6 +568,37 @@ int ricadi_time_gram_dev(ricadi_ctx* ctx, const double* dZ, int c, double* dG, i
  * ricadi_clear_cache() drops the stored panels.  No reference counterpart (SuperLU is direct). */
 int ricadi_set_recycle(ricadi_ctx* ctx, int depth);
 
+/* Test hook: the recycled initial guess a batched solve of these ng shifts with the shared right-hand side dR
+ * (NV x m, device) would start from, and nothing else -- no solve, nothing stored.  dX: ng panels of n x m (device);
+ * they receive the guesses, or stay untouched with *rank_out = 0 where there is no guess (depth 0, no stored panel
+ * common to all shifts, Gram matrix of rank 0).  *rank_out: numerical rank of the stored columns' Gram matrix.
+ * Of the counters of ricadi_solve_trace it moves the guess_* ones only.                                          */
+int ricadi_recycle_guess_dev(ricadi_ctx* ctx, int ng, const double* alphas, const double* betas, const double* dR,
+                             int m, double* dX, int* rank_out);
+
+/* ---- trace of the branches the batched shift solve took (tests) ----------
+ * Host counters of the context, bumped where the decision is taken; no kernel, launch or synchronisation depends
+ * on them.  Copies min(nout, RICADI_TRACE_SLOTS) values into out and returns RICADI_OK.  All are cumulative over
+ * the context's life (take differences), except the *_last / guess_{cols,rank,pan} slots -- values of the most recent
+ * event -- and cycle_len_max, the largest so far.  Slots:
+ *    0 solves           calls of the batched solve (every ricadi_shift_solve* call, every sweep of the drivers)
+ *    1 guess_tried      a recycled guess was asked for          2 guess_used   ... and used
+ *    3 guess_cols       stored columns the last guess combined  4 guess_rank   rank of their Gram matrix
+ *    5 guess_pan        1: normal equations from the side-by-side panel, 0: pair by pair
+ *    6 stored           right-hand side / solution pairs stored
+ *    7 smw_solves       solves by Sherman-Morrison-Woodbury     8 smw_setups   ... that built W for some shift
+ *    9 smw_dup          ... with S^-1 U taken from the right-hand side's own columns (Newton driver)
+ *   10 smw_bad          capacitance matrix not inverted or plain solve unconverged
+ *   11 smw_refined      closed-loop residual above the tolerance: one more GMRES on the closed-loop operator
+ *   12 inop_lowrank     solves with the low-rank term inside the Krylov operator (RICADI_SMW=0, m + q > 128)
+ *   13 esc1_groups, 14 esc2_groups    groups continued at storage level 1 / 2
+ *   15 wide_passes, 16 wide_chunks, 17 wide_groups_last   wide panels as sixteen-column groups: passes, lockstep
+ *                       batches, column groups of the last batch
+ *   18 cycles           restart cycles started                 19 cycle_len_last, 20 cycle_len_max   their length
+ *   21 stalled_groups   groups given up for stagnation         22 maxit_groups   groups stopped at gmres_maxit     */
+#define RICADI_TRACE_SLOTS 23
+int ricadi_solve_trace(ricadi_ctx* ctx, int64_t* out, int nout);
+
 /* ---- shift-parallel sweeps across processes (one process per GPU) -------
  * The ADI sweeps of ricadi_lyap_adi / ricadi_ric_newtonadi (sweep_width > 1) shard by shift:
  * every rank owns a fixed subset of the shift list (ricadi_host_deal), sets up and solves only

@@ -20,7 +20,7 @@ RICADI_ENOCONV = -3
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 404
+ABI_VERSION = 405
 
 
 class RicadiOpts(C.Structure):
@@ -112,6 +112,8 @@ SIGNATURES = {
     "ricadi_time_qr_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "ricadi_time_gram_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _dp]),
     "ricadi_set_recycle": (C.c_int, [_vp, C.c_int]),
+    "ricadi_recycle_guess_dev": (C.c_int, [_vp, C.c_int, _dp, _dp, _vp, C.c_int, _vp, C.POINTER(C.c_int)]),
+    "ricadi_solve_trace": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_int]),
     "ricadi_set_exchange": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int64]),
     "ricadi_rccl_unique_id": (C.c_int, [_vp, C.c_int]),
     "ricadi_set_exchange_rccl": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int64]),
@@ -685,6 +687,31 @@ class Context:
                                                     int(r_stride), m, x_ptr, its, _d(rr))
         _chk(rc, allow_noconv=not strict)
         return list(its), rr
+
+    # slots of ricadi_solve_trace (include/ricadi.h)
+    TRACE = ("solves", "guess_tried", "guess_used", "guess_cols", "guess_rank", "guess_pan", "stored", "smw_solves",
+             "smw_setups", "smw_dup", "smw_bad", "smw_refined", "inop_lowrank", "esc1_groups", "esc2_groups",
+             "wide_passes", "wide_chunks", "wide_groups_last", "cycles", "cycle_len_last", "cycle_len_max",
+             "stalled_groups", "maxit_groups")
+
+    def solve_trace(self):
+        """Counters of the branches the batched shift solves of this context took so far (dict; cumulative --
+        take differences -- except ``guess_cols / guess_rank / guess_pan`` and the ``*_last`` ones, which describe
+        the most recent event, and ``cycle_len_max``, the largest so far)."""
+        a = (C.c_int64 * len(self.TRACE))()
+        _chk(self._lib.ricadi_solve_trace(self._h, a, len(self.TRACE)))
+        return dict(zip(self.TRACE, (int(v) for v in a)))
+
+    def recycle_guess_dev(self, alphas, betas, r_ptr, m, x_ptr):
+        """The recycled initial guess a batched solve of these shifts with the shared ``NV x m`` right-hand side
+        at ``r_ptr`` would start from, into the ``n x m`` panels at ``x_ptr``; no solve, nothing stored.  Returns
+        the rank of the stored columns' Gram matrix; 0: no guess, the panels are untouched."""
+        al = np.ascontiguousarray(alphas, dtype=np.float64)
+        be = np.ascontiguousarray(betas, dtype=np.float64)
+        rank = C.c_int(0)
+        _chk(self._lib.ricadi_recycle_guess_dev(self._h, al.size, _d(al), _d(be), r_ptr, int(m), x_ptr,
+                                                C.byref(rank)))
+        return rank.value
 
     def time_spmm_batch_dev(self, alphas, betas, x_ptr, m, y_ptr, reps):
         """Milliseconds per batched saddle-SpMM launch (ng panels, one shift each)."""

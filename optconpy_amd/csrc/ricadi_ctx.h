@@ -433,6 +433,21 @@ struct ricadi_ctx {
     std::vector<int> kdone;
     const double* work = nullptr;
   } probe;
+  // the branches the batched shift solve took (ricadi_solve_trace, tests): host counters, bumped where the decision is
+  // taken; cumulative over the context's life unless named *_last (the values of the most recent event) -- cycle_len_max
+  // is the largest so far.  Order = slots of ricadi_solve_trace.
+  struct SolveTrace {
+    int64_t solves = 0;                                    // calls of solve_batch
+    int64_t guess_tried = 0, guess_used = 0;               // recycle_guess called / returned a guess
+    int64_t guess_cols = 0, guess_rank = 0, guess_pan = 0; // the last guess: stored columns, rank, side-by-side panel used
+    int64_t stored = 0;                                    // calls of recycle_store
+    int64_t smw_solves = 0, smw_setups = 0, smw_dup = 0, smw_bad = 0, smw_refined = 0;
+    int64_t inop_lowrank = 0;                              // solves with the low-rank term inside the Krylov operator
+    int64_t esc1_groups = 0, esc2_groups = 0;              // groups continued at storage level 1 / 2
+    int64_t wide_passes = 0, wide_chunks = 0, wide_groups_last = 0;
+    int64_t cycles = 0, cycle_len_last = 0, cycle_len_max = 0;
+    int64_t stalled_groups = 0, maxit_groups = 0;
+  } trace;
   // stats
   long total_iters = 0, total_solves = 0;
   long escalations = 0;       // solves repeated with wider storage of basis / preconditioner (safety net)

@@ -70,7 +70,7 @@ static ricadi_ctx* walk_levels(ricadi_ctx* c, Batch& lb, Pred&& is) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 404; }
+int ricadi_version(void) { return 405; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
@@ -829,6 +829,35 @@ int ricadi_shift_solve_batch_dev(ricadi_ctx* c, int ng, const double* alphas, co
     if (!res[g].converged) status = solve_status(false);
   }
   API_END_STATUS(status)
+}
+
+int ricadi_recycle_guess_dev(ricadi_ctx* c, int ng, const double* alphas, const double* betas, const double* dR, int m,
+                             double* dX, int* rank_out) {
+  if (int rc = check_panel(c, m)) return rc;
+  REQUIRE(dR && dX && alphas && betas && rank_out, RICADI_EINVAL, "NULL argument");
+  REQUIRE(ng >= 1 && ng <= RICADI_MAX_GROUPS && (size_t)ng * m <= 2048, RICADI_EINVAL,
+          "1 <= ng <= 16 and ng*m <= 2048 required");
+  *rank_out = 0;
+  API_BEGIN
+  std::vector<ShiftData*> sds(ng);
+  get_shifts(c, alphas, betas, ng, sds.data());
+  ensure_work(c, m, ng);
+  load_rhs(c, dR, m, c->bvec.p);
+  if (c->rec_depth > 0 && recycle_guess(c, sds.data(), ng, c->bvec.p, m, dX)) *rank_out = (int)c->trace.guess_rank;
+  HIPCHK(hipStreamSynchronize(c->st));
+  API_END
+}
+
+int ricadi_solve_trace(ricadi_ctx* c, int64_t* out, int nout) {
+  REQUIRE(c && out && nout >= 0, RICADI_EINVAL, "bad argument");
+  const ricadi_ctx::SolveTrace& t = c->trace;
+  const int64_t v[RICADI_TRACE_SLOTS] = {
+      t.solves,      t.guess_tried, t.guess_used,       t.guess_cols,     t.guess_rank,     t.guess_pan,
+      t.stored,      t.smw_solves,  t.smw_setups,       t.smw_dup,        t.smw_bad,        t.smw_refined,
+      t.inop_lowrank, t.esc1_groups, t.esc2_groups,     t.wide_passes,    t.wide_chunks,    t.wide_groups_last,
+      t.cycles,      t.cycle_len_last, t.cycle_len_max, t.stalled_groups, t.maxit_groups};
+  std::copy(v, v + std::min(nout, (int)RICADI_TRACE_SLOTS), out);
+  return RICADI_OK;
 }
 
 int ricadi_shift_solve(ricadi_ctx* c, double alpha, double beta, const double* R, const double* Rp,

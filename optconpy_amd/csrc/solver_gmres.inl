@@ -424,8 +424,14 @@ struct LockstepSolve {
           rstart[j] = r[j];
         }
         nstall[g] = (flat && cyc >= restart) ? nstall[g] + 1 : 0;
-        if (allow_stall && nstall[g] >= 3) res[g].stalled = true;
-        else next.push_back(g);
+        if (allow_stall && nstall[g] >= 3) {
+          res[g].stalled = true;
+          ++c->trace.stalled_groups;
+        } else {
+          next.push_back(g);
+        }
+      } else {
+        ++c->trace.maxit_groups;
       }
     }
     if (slow) cyc = std::min(restart, cyc + (cyc + 1) / 2);
@@ -469,6 +475,9 @@ struct LockstepSolve {
     if (!go) return false;
     live = act;
     kk = same_int(0);
+    ++c->trace.cycles;
+    c->trace.cycle_len_last = cyc;
+    c->trace.cycle_len_max = std::max<int64_t>(c->trace.cycle_len_max, cyc);
     return true;
   }
 
@@ -590,11 +599,14 @@ static void gmres_core_any(ricadi_ctx* c, ShiftData* const* sds, int G, const do
     // chunks of equal size (16 shifts, 3 per chunk: 3 3 3 3 2 2 rather than 3 3 3 3 3 1); the caller's order is
     // kept: neighbouring shifts of a sorted list need similar iteration counts, which is what a lockstep batch wants
     const int nchunk = ((int)todo.size() + per - 1) / per;
+    ++c->trace.wide_passes;
+    c->trace.wide_chunks += nchunk;
     size_t at = 0;
     for (int ch = 0; ch < nchunk; ++ch) {
       const int cnt = ((int)todo.size() - (int)at + (nchunk - ch) - 1) / (nchunk - ch);
       const int Gv = cnt * ncg;
       std::vector<ShiftData*> vsds(Gv);
+      c->trace.wide_groups_last = Gv;
       if (ncg * W != ncols) {
         HIPCHK(hipMemsetAsync(c->split_b.p, 0, sizeof(double) * nmw * Gv, st));
         if (have_x0) HIPCHK(hipMemsetAsync(c->split_x.p, 0, sizeof(double) * nmw * Gv, st));
@@ -640,9 +652,21 @@ static void gmres_core_any(ricadi_ctx* c, ShiftData* const* sds, int G, const do
 // host).  b: the right-hand side shared by the groups (n x m, pressure rows zero).  Returns false when no
 // stored panel is common to all groups (x is not touched then).
 static bool recycle_guess(ricadi_ctx* c, ShiftData* const* sds, int G, const double* b, int m, double* x) {
+  ++c->trace.guess_tried;
+  c->trace.guess_cols = c->trace.guess_rank = c->trace.guess_pan = 0;
   std::vector<const ricadi_ctx::RecB*> ent;
+  // the ring keeps its size when the depth in force drops (an ADI at depth 5, then direct calls at depth 3): only the
+  // newest rec_depth right-hand sides take part, as ricadi_set_recycle documents
+  long oldest = 0;
+  {
+    std::vector<long> ser;
+    for (auto& e : c->rec_ring)
+      if (e && e->serial >= 0) ser.push_back(e->serial);
+    std::sort(ser.begin(), ser.end());
+    if ((int)ser.size() > c->rec_depth && c->rec_depth > 0) oldest = ser[ser.size() - (size_t)c->rec_depth];
+  }
   for (auto& e : c->rec_ring) {
-    if (!e || e->serial < 0) continue;
+    if (!e || e->serial < oldest) continue;
     bool all = true;
     for (int g = 0; g < G && all; ++g) {
       bool has = false;
@@ -710,6 +734,9 @@ static bool recycle_guess(ricadi_ctx* c, ShiftData* const* sds, int G, const dou
   // the diagonal blocks come from a symmetric kernel, the off-diagonal ones were computed above the
   // diagonal only: the mirror image is exact
   const int rank = gram_lstsq_scaled(h, m, Ghh, Ghb, 1e-11, Y);
+  c->trace.guess_cols = h;
+  c->trace.guess_rank = rank;
+  c->trace.guess_pan = pan ? 1 : 0;
   if (rank == 0) return false;
   HIPCHK(hipMemcpyAsync(Yd.p, Y.data(), sizeof(double) * h * m, hipMemcpyHostToDevice, st));
   const GroupTab all = all_groups(G);
@@ -725,12 +752,14 @@ static bool recycle_guess(ricadi_ctx* c, ShiftData* const* sds, int G, const dou
   }
   HIPCHK(hipStreamSynchronize(st));   // Y is a stack object
   if (c->opts.verbose > 1) fprintf(stderr, "[ricadi] recycled guess from %d stored columns (rank %d)\n", h, rank);
+  ++c->trace.guess_used;
   return true;
 }
 
 static void recycle_store(ricadi_ctx* c, ShiftData* const* sds, int G, const double* b, int m, const double* x) {
   hipStream_t st = c->st;
   const int depth = c->rec_depth;
+  ++c->trace.stored;
   ricadi_ctx::RecB* slot = nullptr;
   if ((int)c->rec_ring.size() < depth) {
     c->rec_ring.emplace_back(new ricadi_ctx::RecB);
@@ -860,6 +889,7 @@ static void gmres_solve_batch(ricadi_ctx* c, ShiftData* const* sds, int G, const
     std::vector<GmresResult> r2(G);
     gmres_core_any(c, sds, G, b, gsb, x, m, lowrank, r2.data(), true, &bad, level < 2);
     c->escalations += (long)bad.size();
+    (level == 1 ? c->trace.esc1_groups : c->trace.esc2_groups) += (int64_t)bad.size();
     std::vector<int> still;
     for (int g : bad) {
       if (c->opts.verbose)
@@ -927,7 +957,9 @@ static bool host_invert(std::vector<double>& a, int q) {
 static void solve_batch(ricadi_ctx* c, ShiftData* const* sds, int G, const double* b, size_t gsb,
                         double* x, int m, bool lowrank, double* relres_host, GmresResult* res) {
   const int q = c->q;
+  ++c->trace.solves;
   if (!lowrank || q <= 0 || !c->sw.smw || m + q > RICADI_MAX_M) {
+    if (lowrank && q > 0) ++c->trace.inop_lowrank;
     gmres_solve_batch(c, sds, G, b, gsb, x, m, lowrank && q > 0, relres_host, res);
     return;
   }
@@ -944,7 +976,10 @@ static void solve_batch(ricadi_ctx* c, ShiftData* const* sds, int G, const doubl
   const int ucol = c->lr_ucol;
   c->lr_ucol = -1;             // the hint holds for one solve
   const bool dup = need && (gsb == 0 || G == 1) && ucol >= 0 && ucol + q <= m;
+  ++c->trace.smw_solves;
   if (need) {
+    ++c->trace.smw_setups;
+    if (dup) ++c->trace.smw_dup;
     const int ma = dup ? m : m + q;
     const size_t nma = (size_t)n * ma;
     double* xa;
@@ -985,6 +1020,7 @@ static void solve_batch(ricadi_ctx* c, ShiftData* const* sds, int G, const doubl
       if (!host_invert(cap, q) || !res[g].converged) bad = true;
       std::copy(cap.begin(), cap.end(), caps.begin() + (size_t)g * q * q);
     }
+    if (bad) ++c->trace.smw_bad;
     if (!dup)
       for (int g = 0; g < G; ++g)
         launch_copy_cols(st, n, m, xa + g * nma, ma, 0, x + g * nm, m, 0, 1.0);
@@ -1017,6 +1053,7 @@ static void solve_batch(ricadi_ctx* c, ShiftData* const* sds, int G, const doubl
   bool ok = true;
   for (double v : rr) ok = ok && v <= tol;
   if (!ok) {
+    ++c->trace.smw_refined;
     c->smw_rhs.ensure(nm * G);
     c->smw_x.ensure(nm * G);
     HIPCHK(hipMemcpyAsync(c->smw_rhs.p, c->wv.p, sizeof(double) * nm * G, hipMemcpyDeviceToDevice, st));

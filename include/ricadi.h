@@ -109,6 +109,17 @@ typedef struct ricadi_opts {
 typedef struct ricadi_adi_params {
   int adi_max_steps;
   double adi_newZ_reltol;
+  double adi_res_reltol; /* 0 (default): off.  > 0: second stopping rule of the ADI, on the relative projected
+                            Lyapunov residual -- the iteration ends after the first step j with
+                            ||W_j^T W_j||_F <= adi_res_reltol * ||W_0^T W_0||_F, W_j the residual factor
+                            after step j and W_0 the right-hand side after the optional projection.  The
+                            sweep form applies the rule block by block and ends after the same step as
+                            the step form as long as the residual has not fallen by more than about
+                            eight orders of magnitude within the sweep; below that its value inside the
+                            sweep is rounding noise and the tolerance is met in the next sweep (up to
+                            sweep_width - 1 steps later).  adi_newZ_reltol keeps working: the
+                            rule that fires first ends the iteration (adi_newZ_reltol = 0 switches the
+                            reference's rule off).  The residual history is recorded: ricadi_adi_res_history */
   int nwtn_max_steps;
   double nwtn_upd_reltol;
   double nwtn_upd_abstol;
@@ -270,10 +281,31 @@ int ricadi_shift_solve(ricadi_ctx* ctx, double alpha, double beta,
  * factor then stays on the device (see ricadi_factor_*).
  * stats_out (may be NULL, else >= 8 doubles) receives [steps, rel_newZ,
  * total_gmres_iters, shift_solves, ||W_end^T W_end||_F, shift-solves that
- * missed the GMRES tolerance, their worst relative residual].               */
+ * missed the GMRES tolerance, their worst relative residual, solves repeated
+ * with wider storage].                                                      */
 int ricadi_lyap_adi(ricadi_ctx* ctx, const double* shifts, int nshifts,
                     const double* W, int m, const ricadi_adi_params* prm,
                     double* Z_out, int* c_out, double* stats_out);
+
+/* Relative projected Lyapunov residual ||W_j^T W_j||_F / ||W_0^T W_0||_F after every ADI step of the most recent
+ * Lyapunov solve of the context (ricadi_lyap_adi; for ricadi_ric_newtonadi(_dev) the solve of the last Newton
+ * step): entry j-1 belongs to step j.  *n_out = number of steps recorded; at most `cap` entries are copied to
+ * `out` (may be NULL with cap = 0).  The history is recorded when adi_res_reltol > 0 or after
+ * ricadi_set_adi_res_history(ctx, 1); otherwise nothing is computed for it and *n_out = 0.  RICADI_ESTATE before
+ * any ADI call.  No reference counterpart.                                                                     */
+int ricadi_adi_res_history(ricadi_ctx* ctx, double* out, int cap, int* n_out);
+/* on != 0: record the residual history also while adi_res_reltol = 0 (no rule is added by it).                 */
+int ricadi_set_adi_res_history(ricadi_ctx* ctx, int on);
+/* The rule that ended the most recent Lyapunov solve of the context (as above).  Every slot of the two stats
+ * arrays is taken -- slot 7 of ricadi_lyap_adi's is the count of solves repeated with wider storage --, so the
+ * value has a call of its own instead of a slot.  RICADI_ESTATE before any ADI call.                           */
+#define RICADI_STOP_MAX_STEPS 0          /* adi_max_steps reached                                               */
+#define RICADI_STOP_NEWZ 1               /* relative norm of the new block below adi_newZ_reltol                */
+#define RICADI_STOP_RES 2                /* relative residual at or below adi_res_reltol                        */
+int ricadi_adi_stop_rule(ricadi_ctx* ctx, int* rule_out);
+/* Kernel launches the residual rule has added since the context was created (three per sweep, two per step and two
+ * for the right-hand side of the step form; 0 while neither the rule nor the history is on), for tests.          */
+int ricadi_adi_res_launches(ricadi_ctx* ctx, int64_t* n_out);
 
 /* ---- a1: Newton-Kleinman ADI for the projected Riccati equation -------
  * pru.proj_alg_ric_newtonadi (/root/reference/optcont_main.py:488-492,

@@ -20,7 +20,7 @@ RICADI_ENOCONV = -3
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 405
+ABI_VERSION = 406
 
 
 class RicadiOpts(C.Structure):
@@ -33,7 +33,7 @@ class RicadiOpts(C.Structure):
 
 class RicadiAdiParams(C.Structure):
     _fields_ = [("adi_max_steps", C.c_int), ("adi_newZ_reltol", C.c_double),
-                ("nwtn_max_steps", C.c_int), ("nwtn_upd_reltol", C.c_double),
+                ("adi_res_reltol", C.c_double), ("nwtn_max_steps", C.c_int), ("nwtn_upd_reltol", C.c_double),
                 ("nwtn_upd_abstol", C.c_double), ("project_w", C.c_int),
                 ("verbose", C.c_int), ("compress_cols", C.c_int), ("sweep_width", C.c_int)]
 
@@ -52,6 +52,10 @@ SIGNATURES = {
     "ricadi_struct_signature": (C.c_char_p, []),
     "ricadi_default_opts": (None, [C.POINTER(RicadiOpts)]),
     "ricadi_default_adi_params": (None, [C.POINTER(RicadiAdiParams)]),
+    "ricadi_adi_res_history": (C.c_int, [_vp, _dp, C.c_int, C.POINTER(C.c_int)]),
+    "ricadi_set_adi_res_history": (C.c_int, [_vp, C.c_int]),
+    "ricadi_adi_stop_rule": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "ricadi_adi_res_launches": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "ricadi_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "ricadi_destroy": (C.c_int, [_vp]),
     "ricadi_set_opts": (C.c_int, [_vp, C.POINTER(RicadiOpts)]),
@@ -268,7 +272,7 @@ def adi_params(d=None, project_w=True):
     for k in ("adi_max_steps", "nwtn_max_steps"):
         if k in d:
             setattr(p, k, int(d[k]))
-    for k in ("adi_newZ_reltol", "nwtn_upd_reltol", "nwtn_upd_abstol"):
+    for k in ("adi_newZ_reltol", "nwtn_upd_reltol", "nwtn_upd_abstol", "adi_res_reltol"):
         if k in d:
             setattr(p, k, float(d[k]))
     p.verbose = 1 if d.get("verbose", False) else 0
@@ -510,6 +514,33 @@ class Context:
         return X, iters, relres
 
     # -- solvers ----------------------------------------------------------
+    STOP_RULES = ("max_steps", "newZ", "res")
+
+    def set_adi_res_history(self, on):
+        """Record the relative Lyapunov residual after every ADI step also while ``adi_res_reltol`` is 0."""
+        _chk(self._lib.ricadi_set_adi_res_history(self._h, 1 if on else 0))
+
+    def adi_res_history(self):
+        """``ricadi_adi_res_history``: the relative residual after every step of the last Lyapunov solve
+        (empty unless ``adi_res_reltol > 0`` or :meth:`set_adi_res_history` asked for it)."""
+        n = C.c_int(0)
+        _chk(self._lib.ricadi_adi_res_history(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1))
+        _chk(self._lib.ricadi_adi_res_history(self._h, _d(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
+
+    def adi_res_launches(self):
+        """Kernel launches the residual rule has added on this context so far (0 while it is off)."""
+        n = C.c_int64(0)
+        _chk(self._lib.ricadi_adi_res_launches(self._h, C.byref(n)))
+        return int(n.value)
+
+    def adi_stopped_by(self):
+        """``ricadi_adi_stop_rule`` of the last Lyapunov solve: ``'newZ'``, ``'res'`` or ``'max_steps'``."""
+        r = C.c_int(0)
+        _chk(self._lib.ricadi_adi_stop_rule(self._h, C.byref(r)))
+        return self.STOP_RULES[r.value]
+
     def lyap_adi(self, shifts, W, prm, fetch=True):
         W = as_panel(W, self.nv)
         m = W.shape[1]
@@ -527,7 +558,7 @@ class Context:
         info = dict(adi_steps=int(stats[0]), adi_rel_newZ=stats[1], gmres_iters=int(stats[2]),
                     shift_solves=int(stats[3]), res_fro=stats[4], cols=c,
                     gmres_nonconverged=int(stats[5]), gmres_worst_relres=stats[6],
-                    storage_escalations=int(stats[7]))
+                    storage_escalations=int(stats[7]), adi_stopped_by=self.adi_stopped_by())
         _warn_nonconverged(info)
         return Z, info
 
@@ -561,7 +592,7 @@ class Context:
                     shift_solves=int(stats[5]), cols=c,
                     gmres_nonconverged=int(stats[6]), gmres_worst_relres=stats[7],
                     lyap_res_fro=stats[8], lyap_rhs_fro=stats[9], storage_escalations=int(stats[10]),
-                    adi_sweeps=int(stats[11]))
+                    adi_sweeps=int(stats[11]), adi_stopped_by=self.adi_stopped_by())
         _warn_nonconverged(info)
         return Z, info
 
@@ -595,7 +626,7 @@ class Context:
                     shift_solves=int(stats[5]), cols=c,
                     gmres_nonconverged=int(stats[6]), gmres_worst_relres=stats[7],
                     lyap_res_fro=stats[8], lyap_rhs_fro=stats[9], storage_escalations=int(stats[10]),
-                    adi_sweeps=int(stats[11]))
+                    adi_sweeps=int(stats[11]), adi_stopped_by=self.adi_stopped_by())
         _warn_nonconverged(info)
         return Zt, info
 

@@ -353,6 +353,16 @@ struct ricadi_ctx {
   DArr<double> smw_rhs, smw_x, smw_cap;
   DArr<double> split_b, split_x;   // wide panels as sixteen-column groups (gmres_core_any)
   DArr<double> sweep_u, sweep_t, sweep_coef, sweep_part;   // ADI sweeps: the G solutions, a panel, coefficients, norm partials
+  // residual rule of the ADI (adi_res_reltol / ricadi_set_adi_res_history): the panel [W, E U_s], the partials and
+  // the Gram matrix of the fixed-order Gram kernel; the relative residual after every step of the last solve, the
+  // rule that ended it (RICADI_STOP_*), and whether a solve has run at all
+  DArr<double> res_pan, res_part, res_gram;
+  std::vector<double> adi_res_hist;
+  int adi_stop_rule = 0;
+  bool adi_ran = false, adi_res_record = false;
+  double* h_res = nullptr;    // pinned host copy of res_gram (h_res_cap doubles)
+  size_t h_res_cap = 0;
+  long res_launches = 0;      // kernel launches issued for the residual rule (ricadi_adi_res_launches)
   // per-shift data
   std::map<std::pair<double, double>, std::unique_ptr<ShiftData>> cache;
   // workspaces
@@ -458,6 +468,7 @@ struct ricadi_ctx {
 
   ~ricadi_ctx() {
     if (h_resid) (void)hipHostFree(h_resid);
+    if (h_res) (void)hipHostFree(h_res);
     if (gj_hptrs) (void)hipHostFree(gj_hptrs);
     if (xcomm && xcomm_owned) (void)ncclCommDestroy(xcomm);
     for (int i = 0; i < 2; ++i) {

@@ -1158,6 +1158,143 @@ void launch_sweep_combine(hipStream_t st, int nrows, int m, int nslot, int G, co
   hipLaunchKernelGGL(sweep_norms_kernel, dim3((G * m + 31) / 32), dim3(256), 0, st, nwg, G * m, partial, norms2);
 }
 
+// ---------------------------------------------------------------------------
+// K4r: residual norms of every prefix of an ADI sweep.  All solutions U_s of a sweep were taken against the same
+// residual factor W, so after the first j blocks the residual factor is W + sum_{i <= j} c_i E U_i with the
+// closed-form coefficients c = C_j^-1 1: the norms of ALL prefixes follow on the host from ONE Gram matrix of the
+// (nslot + 1) m columns  P = [W, E U_1, ..., E U_nslot].
+//   sweep_resid_panel_kernel: P (nrows x nc row-major, nc = (nslot + 1) m) in one launch: one thread per entry, the
+//     E product of all slots from the velocity rows of the gathered buffer (U_s = U + s ustride, ld m);
+//   gram_fixed_kernel: P^T P tile by tile (32 x 32 per wave on v_mfma_f64_16x16x4_f64, tile blocks on / above the
+//     diagonal), the four waves of a workgroup (four consecutive row ranges) summed in wave order in LDS, one
+//     partial matrix per row slice;  gram_fixed_reduce_kernel sums the slices in slice order and mirrors.
+// No atomics anywhere: the same panels give bitwise the same Gram matrix, which is what lets rank-sharded sweeps
+// decide on it rank by rank.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sweep_resid_panel_kernel(int nrows, int m, int nslot,
+                                                                const int* __restrict__ rp, const int* __restrict__ ci,
+                                                                const double* __restrict__ ev,
+                                                                const double* __restrict__ W,
+                                                                const double* __restrict__ U, size_t ustride,
+                                                                double* __restrict__ P) {
+  const int nc = (nslot + 1) * m;
+  const size_t idx = blockIdx.x * (size_t)256 + threadIdx.x;
+  if (idx >= (size_t)nrows * nc) return;
+  const int row = (int)(idx / nc), col = (int)(idx % nc);
+  const int s = col / m, cidx = col % m;
+  double v;
+  if (s == 0) {
+    v = W[(size_t)row * m + cidx];
+  } else {
+    const double* __restrict__ u = U + (size_t)(s - 1) * ustride + cidx;
+    v = 0.0;
+    for (int p = rp[row]; p < rp[row + 1]; ++p) v = fma(ev[p], u[(size_t)ci[p] * m], v);
+  }
+  P[idx] = v;
+}
+
+// part: [slices][ncp][ncp], ncp = 32 * gridDim.y; only tile blocks with blockIdx.z >= blockIdx.y are written (fully)
+__global__ __launch_bounds__(256) void gram_fixed_kernel(int n, int nc, const double* __restrict__ P, int ldp,
+                                                         int rows_per_wave, double* __restrict__ part) {
+  if (blockIdx.z < blockIdx.y) return;
+  __shared__ double red[4][16][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lc = lane & 15, lk = lane >> 4;
+  const int i0 = 32 * blockIdx.y, j0 = 32 * blockIdx.z;
+  const int rbeg = (blockIdx.x * 4 + wave) * rows_per_wave;
+  const int rend = min(n, rbeg + rows_per_wave);
+  d4 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = (d4){0.0, 0.0, 0.0, 0.0};
+  for (int r = rbeg; r < rend; r += 4) {
+    const int rr = r + lk;
+    const bool rok = rr < rend;
+    double af[2], bf[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const int ca = i0 + 16 * a + lc, cb = j0 + 16 * a + lc;
+      af[a] = (rok && ca < nc) ? P[(size_t)rr * ldp + ca] : 0.0;
+      bf[a] = (rok && cb < nc) ? P[(size_t)rr * ldp + cb] : 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+        acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
+  }
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) red[wave][(a * 2 + b) * 4 + e][lane] = acc[a][b][e];
+  __syncthreads();
+  if (wave != 0) return;
+  const int ncp = 32 * gridDim.y;
+  double* out = part + (size_t)blockIdx.x * ncp * ncp;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int t = (a * 2 + b) * 4 + e;
+        const double v = (red[0][t][lane] + red[1][t][lane]) + (red[2][t][lane] + red[3][t][lane]);
+        out[(size_t)(i0 + 16 * a + lk + 4 * e) * ncp + j0 + 16 * b + lc] = v;
+      }
+}
+// G (nc x nc, ld nc) = sum of the slices' partials in slice order; entries below the diagonal tile blocks are the
+// mirror of those above
+__global__ __launch_bounds__(256) void gram_fixed_reduce_kernel(int slices, int nc, int ncp,
+                                                                const double* __restrict__ part,
+                                                                double* __restrict__ G) {
+  const size_t idx = blockIdx.x * (size_t)256 + threadIdx.x;
+  if (idx >= (size_t)nc * nc) return;
+  int i = (int)(idx / nc), j = (int)(idx % nc);
+  if ((i >> 5) > (j >> 5)) {
+    const int t = i;
+    i = j;
+    j = t;
+  }
+  const double* p = part + (size_t)i * ncp + j;
+  double s = 0.0;
+  for (int w = 0; w < slices; ++w) s += p[(size_t)w * ncp * ncp];
+  G[idx] = s;
+}
+// row slices of the fixed-order Gram matrix: enough workgroups to fill the chip, partials kept below 64 MB
+static int gram_fixed_slices(int n, int nc, int& rows_per_wave) {
+  const int nt = (nc + 31) / 32;
+  const size_t per_slice = (size_t)(32 * nt) * (32 * nt) * sizeof(double);
+  const int pairs = nt * (nt + 1) / 2;
+  int slices = std::min((n + 255) / 256, std::max(1, 2048 / pairs));
+  slices = std::max(1, std::min(slices, (int)(((size_t)64 << 20) / per_slice)));
+  rows_per_wave = (((n + slices * 4 - 1) / (slices * 4)) + 3) & ~3;
+  return (n + 4 * rows_per_wave - 1) / (4 * rows_per_wave);
+}
+size_t gram_fixed_partial_len(int n, int nc) {
+  int rpw = 0;
+  const int nt = (nc + 31) / 32;
+  return (size_t)gram_fixed_slices(n, nc, rpw) * (32 * nt) * (32 * nt);
+}
+void launch_gram_fixed(hipStream_t st, int n, int nc, const double* P, int ldp, double* partial, double* G) {
+  if (n <= 0 || nc <= 0) return;
+  int rpw = 0;
+  const int slices = gram_fixed_slices(n, nc, rpw);
+  const int nt = (nc + 31) / 32;
+  hipLaunchKernelGGL(gram_fixed_kernel, dim3(slices, nt, nt), dim3(256), 0, st, n, nc, P, ldp, rpw, partial);
+  hipLaunchKernelGGL(gram_fixed_reduce_kernel, dim3((unsigned)(((size_t)nc * nc + 255) / 256)), dim3(256), 0, st,
+                     slices, nc, 32 * nt, partial, G);
+}
+void launch_sweep_resid_panel(hipStream_t st, int nrows, int m, int nslot, const int* rp, const int* ci,
+                              const double* ev, const double* W, const double* U, size_t ustride, double* P) {
+  const size_t tot = (size_t)nrows * (nslot + 1) * m;
+  if (tot == 0) return;
+  hipLaunchKernelGGL(sweep_resid_panel_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, nrows, m,
+                     nslot, rp, ci, ev, W, U, ustride, P);
+}
+
 // coarse matrix combine: out = beta*E0 + alpha*EM + EJ  (dense k x k)
 __global__ void combine3_kernel(size_t n, const double* a0, const double* a1, const double* a2,
                                 double alpha, double beta, double* out) {

@@ -552,6 +552,14 @@ size_t sweep_combine_partial_len(int nrows, int m, int G);
 void launch_sweep_combine(hipStream_t st, int nrows, int m, int nslot, int G, const double* U, size_t ustride,
                           const double* coef, double* Z, int zld, int zc0, double* partial, double* norms2);
 
+// K4r: the panel P = [W, E U_1, ..., E U_nslot] of an ADI sweep (nrows x (nslot + 1) m) in one launch, and the Gram
+// matrix G = P^T P (nc x nc, ld nc) of a row-major panel with every sum in a fixed order (two launches; `partial`:
+// gram_fixed_partial_len doubles): the same panel gives bitwise the same G
+void launch_sweep_resid_panel(hipStream_t st, int nrows, int m, int nslot, const int* rp, const int* ci,
+                              const double* ev, const double* W, const double* U, size_t ustride, double* P);
+size_t gram_fixed_partial_len(int n, int nc);
+void launch_gram_fixed(hipStream_t st, int n, int nc, const double* P, int ldp, double* partial, double* G);
+
 void set_error(const std::string& msg);
 
 }  // namespace ricadi

@@ -166,6 +166,39 @@ static bool sweep_blocks(ricadi_ctx* c, const double* ubase, size_t ustride, int
   return combined;
 }
 
+// Residual rule (adi_res_reltol; ricadi.h): whether the residual of every step is evaluated at all
+static bool adi_res_wanted(const ricadi_ctx* c, const ricadi_adi_params& prm) {
+  return prm.adi_res_reltol > 0.0 || c->adi_res_record;
+}
+// pinned host buffer the Gram matrix of the residual rule is fetched into (a copy to pageable memory would make the
+// host wait by itself, ahead of the synchronisation that fetches the block norms)
+static double* res_host(ricadi_ctx* c, size_t count) {
+  if (count > c->h_res_cap) {
+    if (c->h_res) (void)hipHostFree(c->h_res);
+    c->h_res = nullptr;
+    c->h_res_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&c->h_res, sizeof(double) * count, hipHostMallocDefault));
+    c->h_res_cap = count;
+  }
+  return c->h_res;
+}
+// ||V^T V||_F of V = sum_x d[x] P_blk[x] from the Gram matrix Gm (nc x nc) of the panel P, whose column block b is
+// columns b m .. b m + m: V^T V = sum_xy d[x] d[y] Gm[blk[x], blk[y]].  Plain loops in a fixed order.
+static double gram_combination_fro(const double* Gm, int nc, int m, const int* blk, const double* d, int cnt) {
+  double f = 0.0;
+  for (int a = 0; a < m; ++a)
+    for (int b = 0; b < m; ++b) {
+      double s = 0.0;
+      for (int x = 0; x < cnt; ++x) {
+        double t = 0.0;
+        for (int y = 0; y < cnt; ++y) t += d[y] * Gm[((size_t)blk[x] * m + a) * nc + (size_t)blk[y] * m + b];
+        s += d[x] * t;
+      }
+      f += s * s;
+    }
+  return std::sqrt(f);
+}
+
 static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, double* dW, int m,
                                 const ricadi_adi_params& prm, AdiStats& stt) {
   int G = std::min(std::min(prm.sweep_width, ns), RICADI_MAX_GROUPS);
@@ -263,6 +296,15 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
   // relative block norm of the last two visits of every position of the shift cycle
   std::vector<double> rel_h1(ns, 0.0), rel_h2(ns, 0.0);
   std::vector<double> ps_var, rinv_var, cinv_var, cinv_kept, rdummy, hn;
+  // Residual rule: the relative residual after EVERY block of a sweep comes from one Gram matrix of the columns
+  // [W, E U_1, ..., E U_nslot] (launch_sweep_resid_panel, launch_gram_fixed: fixed summation order, so every rank
+  // gets the same bits from the same gathered panels and decides alone) and the closed-form coefficients C_j^-1 1
+  // of the leading Cauchy blocks.  ||W_0^T W_0|| is the leading block of the first sweep's matrix.
+  const bool res_on = adi_res_wanted(c, prm);
+  std::vector<double> res_h1(res_on ? ns : 0, 0.0), res_h2(res_on ? ns : 0, 0.0), cpre, dpre;
+  const double* hg = nullptr;
+  std::vector<int> bpre;
+  double res_rhs = -1.0;
   for (int sw = 0;; ++sw) {
     // Width of this sweep.  With C = R^T R (R upper triangular) column block j of U R^-1 lies in
     // span{U_1..U_j}: it IS the block the step-by-step iteration appends at step j (up to its
@@ -283,6 +325,17 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
             g_now = g + 1;
             break;
           }
+        }
+      }
+    }
+    if (prm.adi_res_reltol > 0.0) {
+      // the same extrapolation on the residual history (residual after this position of the last two cycles)
+      for (int g = 0; g < g_now; ++g) {
+        const int pos = (steps + g) % ns;
+        if (res_h1[pos] > 0.0 && res_h2[pos] > res_h1[pos] &&
+            res_h1[pos] * (res_h1[pos] / res_h2[pos]) <= prm.adi_res_reltol) {
+          g_now = g + 1;
+          break;
         }
       }
     }
@@ -390,6 +443,18 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
     const bool combined = sweep_blocks(c, ubase, nm, nslot, Gs, m, c->sweep_coef.p, c->Z.p, c->zld, c->zc, c->nrm2.p);
     hn.resize((size_t)Gs * m);
     HIPCHK(hipMemcpyAsync(hn.data(), c->nrm2.p, sizeof(double) * Gs * m, hipMemcpyDeviceToHost, st));
+    const int nc = (nslot + 1) * m;
+    if (res_on) {
+      c->res_pan.ensure((size_t)nv * nc);
+      c->res_part.ensure(gram_fixed_partial_len(nv, nc));
+      c->res_gram.ensure((size_t)nc * nc);
+      launch_sweep_resid_panel(st, nv, m, nslot, c->E.rp.p, c->E.ci.p, c->E.v.p, dW, ubase, nm, c->res_pan.p);
+      launch_gram_fixed(st, nv, nc, c->res_pan.p, nc, c->res_part.p, c->res_gram.p);
+      c->res_launches += 3;
+      double* hgw = res_host(c, (size_t)nc * nc);
+      hg = hgw;
+      HIPCHK(hipMemcpyAsync(hgw, c->res_gram.p, sizeof(double) * nc * nc, hipMemcpyDeviceToHost, st));
+    }
     std::vector<double> rwords;
     if (shard && words_fit) {
       // the ranks' status words, one strided copy out of the gathered buffer
@@ -408,6 +473,11 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
     if (!combined)
       for (int o = 0; o < Gs * m; o += RICADI_XCTL / 8)
         values_of_rank0(c, hn.data() + o, std::min(RICADI_XCTL / 8, Gs * m - o));
+    if (res_on && res_rhs < 0.0) {
+      const int b0 = 0;
+      const double one = 1.0;
+      res_rhs = gram_combination_fro(hg, nc, m, &b0, &one, 1);
+    }
     // the reference's rule, block by block; blocks behind the stopping step are dropped
     int kept = Gs;
     bool stop = false;
@@ -420,9 +490,35 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
       rel_h2[pos] = rel_h1[pos];
       rel_h1[pos] = relj;
       stt.rel = relj;
-      if (relj < prm.adi_newZ_reltol) {
+      int rule = relj < prm.adi_newZ_reltol ? RICADI_STOP_NEWZ : RICADI_STOP_MAX_STEPS;
+      if (res_on) {
+        // residual factor after the first j + 1 blocks: W + sum_{i <= j} (C_{j+1}^-1 1)_i E U_i
+        const double* cj = cinv1.data();
+        if (j + 1 < Gs) {
+          cpre.assign(j + 1, 0.0);
+          rdummy.assign((size_t)(j + 1) * (j + 1), 0.0);
+          if (cauchy_data(ps.data(), j + 1, rdummy.data(), cpre.data()) != RICADI_OK)
+            throw HipError{"Cauchy matrix of a truncated ADI sweep is numerically singular"};
+          cj = cpre.data();
+        }
+        bpre.assign(j + 2, 0);
+        dpre.assign(j + 2, 1.0);
+        for (int i = 0; i <= j; ++i) {
+          bpre[i + 1] = 1 + slot_of[i];
+          dpre[i + 1] = cj[i];
+        }
+        const double wf = gram_combination_fro(hg, nc, m, bpre.data(), dpre.data(), j + 2);
+        const double resj = res_rhs > 0.0 ? wf / res_rhs : 0.0;
+        c->adi_res_hist.push_back(resj);
+        res_h2[pos] = res_h1[pos];
+        res_h1[pos] = resj;
+        if (rule == RICADI_STOP_MAX_STEPS && prm.adi_res_reltol > 0.0 && resj <= prm.adi_res_reltol)
+          rule = RICADI_STOP_RES;
+      }
+      if (rule != RICADI_STOP_MAX_STEPS) {
         kept = j + 1;
         stop = true;
+        c->adi_stop_rule = rule;
         break;
       }
     }
@@ -506,6 +602,9 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
   AdiStats stt;
   Restore<int> keep_rec(c->rec_depth);
   c->rec_depth = std::max(c->rec_user_depth, adi_recycle_depth(c));
+  c->adi_res_hist.clear();
+  c->adi_stop_rule = RICADI_STOP_MAX_STEPS;
+  c->adi_ran = true;
   if (prm.sweep_width > 1 && lyap_adi_sweeps_dev(c, shifts, ns, dW, m, prm, stt)) return stt;
   stt = AdiStats();
   hipStream_t st = c->st;
@@ -520,6 +619,20 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
   const long it0 = c->total_iters;
   double znorm2 = 0.0;
   int zc_last = c->zc;
+  // Residual rule: W^T W after every step (fixed-order Gram kernel), fetched with the block norms.  ||W_0^T W_0||
+  // is launched here and fetched in the first step's synchronisation.
+  const bool res_on = adi_res_wanted(c, prm);
+  const int mm = m * m, blk0 = 0;
+  const double one = 1.0;
+  double* hg = nullptr;
+  double res_rhs = -1.0;
+  if (res_on) {
+    c->res_part.ensure(gram_fixed_partial_len(c->nv, m));
+    c->res_gram.ensure((size_t)2 * mm);
+    hg = res_host(c, (size_t)2 * mm);
+    launch_gram_fixed(st, c->nv, m, dW, m, c->res_part.p, c->res_gram.p);
+    c->res_launches += 2;
+  }
   for (int step = 1; step <= prm.adi_max_steps; ++step) {
     const double p = shifts[(step - 1) % ns];
     ShiftData* sd = get_shift(c, p, 1.0);
@@ -541,6 +654,11 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
     double n2 = 0.0;
     col_norms2(c, c->xs.p, c->nv, m, c->nrm2.p);
     HIPCHK(hipMemcpyAsync(c->h_resid, c->nrm2.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+    if (res_on) {
+      launch_gram_fixed(st, c->nv, m, dW, m, c->res_part.p, c->res_gram.p + mm);
+      c->res_launches += 2;
+      HIPCHK(hipMemcpyAsync(hg, c->res_gram.p, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipStreamSynchronize(st));
     for (int j = 0; j < m; ++j) n2 += c->h_resid[j];
     n2 *= -2.0 * p;
@@ -551,7 +669,21 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
     if (prm.verbose)
       fprintf(stderr, "[ricadi] ADI step %3d: shift %10.3e rel new Z %9.3e gmres its %d\n", step,
               p, stt.rel, r.iters);
-    if (stt.rel < prm.adi_newZ_reltol) break;
+    int rule = stt.rel < prm.adi_newZ_reltol ? RICADI_STOP_NEWZ : RICADI_STOP_MAX_STEPS;
+    if (res_on) {
+      if (res_rhs < 0.0) res_rhs = gram_combination_fro(hg, m, m, &blk0, &one, 1);
+      const double wf = gram_combination_fro(hg + mm, m, m, &blk0, &one, 1);
+      double dec[2] = {res_rhs > 0.0 ? wf / res_rhs : 0.0, (double)rule};
+      values_of_rank0(c, dec, 2);       // (sharded: every rank runs this form on its own solves; rank 0 decides)
+      rule = (int)dec[1];
+      c->adi_res_hist.push_back(dec[0]);
+      if (rule == RICADI_STOP_MAX_STEPS && prm.adi_res_reltol > 0.0 && dec[0] <= prm.adi_res_reltol)
+        rule = RICADI_STOP_RES;
+    }
+    if (rule != RICADI_STOP_MAX_STEPS) {
+      c->adi_stop_rule = rule;
+      break;
+    }
     if (prm.compress_cols > 0 && c->zc - zc_last >= prm.compress_cols) {
       factor_recompress(c);
       zc_last = c->zc;

@@ -70,11 +70,11 @@ static ricadi_ctx* walk_levels(ricadi_ctx* c, Batch& lb, Pred&& is) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 405; }
+int ricadi_version(void) { return 406; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
-const char* ricadi_struct_signature(void) { return "ricadi_opts:diiiiiiiiiiiid;ricadi_adi_params:ididdiiii"; }
+const char* ricadi_struct_signature(void) { return "ricadi_opts:diiiiiiiiiiiid;ricadi_adi_params:iddiddiiii"; }
 
 void ricadi_default_opts(ricadi_opts* o) {
   if (!o) return;
@@ -106,6 +106,7 @@ void ricadi_default_adi_params(ricadi_adi_params* p) {
   p->verbose = 0;
   p->compress_cols = 0;
   p->sweep_width = 1;
+  p->adi_res_reltol = 0.0;
 }
 
 // The only reading of the library's switches (ricadi_ctx::sw); RICADI_RECYCLE and RICADI_INJECT_SWEEP_FAILURE are
@@ -1579,6 +1580,31 @@ int ricadi_lyap_adi(ricadi_ctx* c, const double* shifts, int ns, const double* W
     stats_out[7] = (double)(c->escalations - esc0);
   }
   API_END
+}
+
+int ricadi_adi_res_history(ricadi_ctx* c, double* out, int cap, int* n_out) {
+  REQUIRE(c && n_out && cap >= 0 && (out || cap == 0), RICADI_EINVAL, "bad argument");
+  REQUIRE(c->adi_ran, RICADI_ESTATE, "no ADI iteration has run on this context");
+  const int n = (int)c->adi_res_hist.size();
+  *n_out = n;
+  for (int i = 0; i < std::min(n, cap); ++i) out[i] = c->adi_res_hist[i];
+  return RICADI_OK;
+}
+int ricadi_set_adi_res_history(ricadi_ctx* c, int on) {
+  REQUIRE(c, RICADI_EINVAL, "NULL context");
+  c->adi_res_record = on != 0;
+  return RICADI_OK;
+}
+int ricadi_adi_res_launches(ricadi_ctx* c, int64_t* n_out) {
+  REQUIRE(c && n_out, RICADI_EINVAL, "NULL argument");
+  *n_out = (int64_t)c->res_launches;
+  return RICADI_OK;
+}
+int ricadi_adi_stop_rule(ricadi_ctx* c, int* rule_out) {
+  REQUIRE(c && rule_out, RICADI_EINVAL, "NULL argument");
+  REQUIRE(c->adi_ran, RICADI_ESTATE, "no ADI iteration has run on this context");
+  *rule_out = c->adi_stop_rule;
+  return RICADI_OK;
 }
 
 }  // extern "C"

@@ -202,6 +202,8 @@ def solve_proj_lyap_stein(amat=None, mmat=None, jmat=None, wmat=None,
     prm = _lib.adi_params(d)
     W = _dense(wmat)
     out = {}
+    want_hist = _wants_res_hist(d, prm)
+    ctx.set_adi_res_history(bool(d.get("adi_res_hist", False)))
     try:
         if W.shape[1] > _lib.MAX_M:
             raise ValueError("right-hand side factor wider than {0} columns".format(_lib.MAX_M))
@@ -227,11 +229,20 @@ def solve_proj_lyap_stein(amat=None, mmat=None, jmat=None, wmat=None,
             if d.get("verbose", False):
                 print("projected Lyapunov residual (factored): {0:.3e}; ADI recurrence: {1:.3e}"
                       .format(out["lyap_res"], info["res_fro"]))
+        if want_hist:
+            out["adi_res_hist"] = ctx.adi_res_history()
     finally:
         ctx.set_lowrank(None, None)
+        ctx.set_adi_res_history(False)
     out["zfac"] = Z
     out.update(info)
     return out
+
+
+def _wants_res_hist(d, prm):
+    """``out['adi_res_hist']`` is returned when the residual rule is on (``adi_res_reltol`` > 0) or
+    ``adi_dict['adi_res_hist']`` asks for it."""
+    return prm.adi_res_reltol > 0.0 or bool(d.get("adi_res_hist", False))
 
 
 def proj_alg_ric_newtonadi(mmat=None, amat=None, jmat=None, bmat=None,
@@ -261,6 +272,30 @@ def proj_alg_ric_newtonadi(mmat=None, amat=None, jmat=None, bmat=None,
     if _is_auto(ms):
         ms = _newton_auto_shifts(ctx, d, calE, bmat, wmat, z0, mtxoldb)
         sinfo = dict(ms.info)
+    want_hist = _wants_res_hist(d, prm)
+    ctx.set_adi_res_history(bool(d.get("adi_res_hist", False)))
+    try:
+        out, info = _newtonadi_call(ctx, d, ms, prm, bmat, wmat, z0, mtxoldb)
+        if want_hist:
+            # of the last Newton step's Lyapunov solve
+            out["adi_res_hist"] = ctx.adi_res_history()
+    finally:
+        ctx.set_adi_res_history(False)
+    out.update(info)
+    if sinfo is not None:
+        out["ms"], out["shift_info"] = list(ms), sinfo
+    if d.get("check_lyap_res", False):
+        # optcont_main.py:130: residual of the last Newton step's Lyapunov equation --
+        # in residual-form ADI it is W_end W_end^T, whose norm the driver returns
+        out["lyap_res"] = info["lyap_res_fro"]
+        if d.get("verbose", False):
+            print("last Newton step: projected Lyapunov residual {0:.3e} (rhs {1:.3e})"
+                  .format(info["lyap_res_fro"], info["lyap_rhs_fro"]))
+    return out
+
+
+def _newtonadi_call(ctx, d, ms, prm, bmat, wmat, z0, mtxoldb):
+    """The library call of :func:`proj_alg_ric_newtonadi`; returns ``(out, info)``."""
     if d.get("device_resident", False) or any(_on_device(x) for x in (bmat, wmat, z0, mtxoldb)):
         # every panel in HBM (uploaded here once if it came as an ndarray), the new factor returned as a
         # DeviceFactor: no PCIe traffic in the call when the caller keeps its panels on the device
@@ -277,17 +312,7 @@ def proj_alg_ric_newtonadi(mmat=None, amat=None, jmat=None, bmat=None,
                                     Z0=None if z0 is None else _dense(z0),
                                     oldB=None if mtxoldb is None else _dense(mtxoldb))
         out = dict(zfac=Z)
-    out.update(info)
-    if sinfo is not None:
-        out["ms"], out["shift_info"] = list(ms), sinfo
-    if d.get("check_lyap_res", False):
-        # optcont_main.py:130: residual of the last Newton step's Lyapunov equation --
-        # in residual-form ADI it is W_end W_end^T, whose norm the driver returns
-        out["lyap_res"] = info["lyap_res_fro"]
-        if d.get("verbose", False):
-            print("last Newton step: projected Lyapunov residual {0:.3e} (rhs {1:.3e})"
-                  .format(info["lyap_res_fro"], info["lyap_rhs_fro"]))
-    return out
+    return out, info
 
 
 def _newton_auto_shifts(ctx, d, calE, bmat, wmat, z0, mtxoldb):

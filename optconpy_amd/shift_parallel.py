@@ -279,9 +279,23 @@ def lyap_adi_shift_parallel(ops, ms, W, **kw):
             cx.set_recycle(d)
 
 
+def prefix_residuals(gram, m, ps):
+    """``||W_j^T W_j||_F`` for every prefix ``j = 1 .. g`` of a sweep from the Gram matrix of the ``(g + 1) m``
+    columns ``[W, E U_1, .., E U_g]`` (the solutions in the order of the shifts ``ps``): all ``U_i`` were solved
+    against the same ``W``, so ``W_j = W + E sum_{i <= j} c_i U_i`` with ``c = C_j^-1 1`` of the leading Cauchy
+    block (``ricadi_host_cauchy``) -- the host arithmetic of the library's sweep form (solver_adi.inl)."""
+    g = len(ps)
+    out = np.zeros(g)
+    for j in range(1, g + 1):
+        d = np.r_[1.0, np.asarray(_lib.host_cauchy(ps[:j])[1], dtype=float)]
+        blk = gram[:(j + 1) * m, :(j + 1) * m].reshape(j + 1, m, j + 1, m)
+        out[j - 1] = np.linalg.norm(np.einsum("x,xayb,y->ab", d, blk, d))
+    return out
+
+
 def _lyap_adi_sweeps(ops, ms, W, adi_max_steps=200, adi_newZ_reltol=1e-8,
                      group=None, width=None, max_width=8, verbose=False, col_parts=0,
-                     stop_rule="step"):
+                     stop_rule="step", adi_res_reltol=0.0, adi_res_hist=False):
     """Shift-parallel LR-ADI; returns ``(Z_blocks, info)``.
 
     ``W`` is the (already projected) NV x m residual factor as a tensor on the
@@ -301,6 +315,12 @@ def _lyap_adi_sweeps(ops, ms, W, adi_max_steps=200, adi_newZ_reltol=1e-8,
     of the last two passes over the shift cycle predict the stopping step, and the sweep
     that would contain it is cut there.  ``stop_rule="sweep"``: mean block norm per sweep.
     Rank 0 takes the decisions for everybody.
+
+    ``adi_res_reltol > 0`` adds the library's second rule (``ricadi_adi_params.adi_res_reltol``): the iteration
+    ends after the first step whose relative residual ``||W_j^T W_j||_F / ||W_0^T W_0||_F`` is at or below it,
+    block by block from one Gram matrix per sweep (:func:`prefix_residuals`); whichever rule fires first ends the
+    iteration.  ``info['adi_res_hist']`` is the residual after every step (recorded with the rule on or with
+    ``adi_res_hist=True``, else empty), ``info['adi_stopped_by']`` ``'newZ'``, ``'res'`` or ``'max_steps'``.
     """
     if dist.is_available() and dist.is_initialized():
         world = dist.get_world_size(group)
@@ -345,6 +365,9 @@ def _lyap_adi_sweeps(ops, ms, W, adi_max_steps=200, adi_newZ_reltol=1e-8,
         return buffers[key]
 
     step_rule = stop_rule == "step" and adi_newZ_reltol > 0.0
+    res_on = adi_res_reltol > 0.0 or bool(adi_res_hist)
+    res_h1, res_h2 = np.zeros(ns), np.zeros(ns)
+    res_rhs, res_hist, stopped_by = None, [], "max_steps"
     rel_h1, rel_h2 = np.zeros(ns), np.zeros(ns)
     blocks = []
     znorm2 = 0.0
@@ -360,6 +383,13 @@ def _lyap_adi_sweeps(ops, ms, W, adi_max_steps=200, adi_newZ_reltol=1e-8,
                 pos = (steps + g) % ns
                 if rel_h1[pos] > 0.0 and rel_h2[pos] > rel_h1[pos] and \
                         rel_h1[pos] * (rel_h1[pos] / rel_h2[pos]) < adi_newZ_reltol:
+                    g_now = g + 1
+                    break
+        if adi_res_reltol > 0.0:
+            for g in range(g_now):
+                pos = (steps + g) % ns
+                if res_h1[pos] > 0.0 and res_h2[pos] > res_h1[pos] and \
+                        res_h1[pos] * (res_h1[pos] / res_h2[pos]) <= adi_res_reltol:
                     g_now = g + 1
                     break
         if world > 1:
@@ -383,6 +413,23 @@ def _lyap_adi_sweeps(ops, ms, W, adi_max_steps=200, adi_newZ_reltol=1e-8,
         if world > 1:
             dist.all_gather_into_tensor(U_all.view(-1), U_loc.view(-1), group=group)
         rinv, cinv1 = _lib.host_cauchy(ps)
+        res_blk = np.zeros(0)
+        if res_on:
+            # Gram matrix of [W, E U_1 .. E U_g] (full width, shift order) BEFORE W is advanced
+            cols = [Wq[0] if parts == 1 else torch.cat(Wq, dim=1)]
+            for g in range(g_now):
+                Tg = []
+                for q in range(parts):
+                    pos = [it["pos"] for it in items if it["g"] == g and it["q"] == q][0]
+                    Tq = torch.zeros_like(Wq[q])
+                    ops.apply_E(1.0, U_all[pos], Tq)
+                    Tg.append(Tq)
+                cols.append(Tg[0] if parts == 1 else torch.cat(Tg, dim=1))
+            Pn = torch.cat(cols, dim=1)
+            gram = (Pn.T @ Pn).cpu().numpy()
+            if res_rhs is None:
+                res_rhs = float(np.linalg.norm(gram[:m, :m]))
+            res_blk = prefix_residuals(gram, m, ps) / res_rhs if res_rhs > 0.0 else np.zeros(g_now)
         bn2 = np.zeros(g_now)             # squared norm of every (sequential) block of the sweep
         zparts = []
         for q in range(parts):
@@ -408,25 +455,36 @@ def _lyap_adi_sweeps(ops, ms, W, adi_max_steps=200, adi_newZ_reltol=1e-8,
                 ops.apply_E(1.0, T, Wq[q])
         # stopping decision (rank 0's numbers: the norms come from kernels with atomic
         # accumulation, ranks may differ in the last bits and must not disagree)
-        kept, stop = g_now, False
-        if step_rule:
+        kept, stop, rule = g_now, False, 0
+        if step_rule or res_on:
             z2 = znorm2
             for j in range(g_now):
-                z2 += bn2[j]
-                rel = float(np.sqrt(bn2[j] / z2)) if z2 > 0 else 0.0
                 pos = (steps + j) % ns
-                rel_h2[pos], rel_h1[pos] = rel_h1[pos], rel
-                if rel < adi_newZ_reltol:
-                    kept, stop = j + 1, True
+                if step_rule:
+                    z2 += bn2[j]
+                    rel = float(np.sqrt(bn2[j] / z2)) if z2 > 0 else 0.0
+                    rel_h2[pos], rel_h1[pos] = rel_h1[pos], rel
+                    if rel < adi_newZ_reltol:
+                        kept, stop, rule = j + 1, True, 1
+                if res_on:
+                    res_h2[pos], res_h1[pos] = res_h1[pos], res_blk[j]
+                    if not stop and adi_res_reltol > 0.0 and res_blk[j] <= adi_res_reltol:
+                        kept, stop, rule = j + 1, True, 2
+                if stop:
                     break
-        else:
+        if not step_rule and not stop:
             n2 = float(bn2.sum())
             rel = float(np.sqrt(n2 / g_now / (znorm2 + n2))) if znorm2 + n2 > 0 else 0.0
             stop = rel < adi_newZ_reltol
+            rule = 1 if stop else 0
         if world > 1:
-            dec = W.new_tensor([float(kept), 1.0 if stop else 0.0, rel])
+            dec = W.new_tensor([float(kept), 1.0 if stop else 0.0, rel, float(rule)] + [float(x) for x in res_blk])
             dist.broadcast(dec, src=0, group=group)
             kept, stop, rel = int(round(dec[0].item())), bool(dec[1].item() > 0.5), float(dec[2].item())
+            rule, res_blk = int(round(dec[3].item())), dec[4:].cpu().numpy()
+        res_hist.extend(float(x) for x in res_blk[:kept])
+        if stop:
+            stopped_by = ("max_steps", "newZ", "res")[rule]
         if kept < g_now:
             # W was advanced with C^-1 1 of all g_now shifts; the factor keeps only the first `kept` blocks.
             # Every U_g was solved against the same W, so the kept solutions ARE the sweep of the first
@@ -452,6 +510,7 @@ def _lyap_adi_sweeps(ops, ms, W, adi_max_steps=200, adi_newZ_reltol=1e-8,
     Wend = Wq[0] if parts == 1 else torch.cat(Wq, dim=1).contiguous()
     info = dict(adi_steps=steps, sweeps=nsweeps, width=G, col_parts=parts, adi_rel_newZ=rel, owners=fixed,
                 res_fro=ops.gram_fro(Wend), resfac=Wend,
+                adi_res_hist=np.array(res_hist), adi_stopped_by=stopped_by,
                 gmres_nonconverged=int(getattr(ops, "nonconverged", 0)),
                 gmres_worst_relres=float(getattr(ops, "worst_relres", 0.0)),
                 shift_solves=items_solved / float(parts))

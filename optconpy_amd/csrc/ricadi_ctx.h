@@ -10,9 +10,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <tuple>
 
+#include "adi_stop.h"
 #include "ricadi_internal.h"
 
 namespace ricadi {

@@ -13,23 +13,18 @@ struct AdiStats {
   int sweeps = 0;             // sweep form: batched sweeps run (= all-gathers when sharded)
 };
 
-// dW: NV x m device panel (overwritten by the final residual factor).
-// Appends sqrt(-2p) V_i to c->Z (ld = c->zld) starting at column c->zc.
-// Sweep form of the same ADI: G consecutive steps
-// with distinct shifts are G independent solves against the SAME residual factor,
-//   S(p_g) [U_g; *] = [W; 0],
-// recombined with the G x G Cauchy matrix C_ij = -1/(p_i+p_j) = R^T R:
-//   Z-block = U (R^-1 (x) I),   W <- W + E U ((C^-1 1) (x) I)
-// -- identical to the G sequential steps up to a rotation of the block's columns (Z Z^T
-// and the gain are the same).  The G solves go through ONE batched lockstep GMRES, which
-// is what fills the GPU at n ~ 3e4.  The stopping rule is applied per sweep (mean block
-// norm).  Returns false (nothing done) if the shift list does not allow sweeps.
-// All-gather of `count` doubles per rank through the host's collective (ricadi_set_exchange): the ranks'
-// first `count` doubles of c->xsend arrive rank-major in c->xrecv.  The context stream is drained first.
-// The last RICADI_XCTL bytes of the send buffer (and the last world * RICADI_XCTL of the receive buffer) are
-// kept for the small control messages (decisions, statistics), so that they never touch panels in flight.
+// The last RICADI_XCTL bytes of the send buffer (and the last world * RICADI_XCTL of the receive buffer) are kept
+// for the small control messages (decisions, statistics), so that they never touch panels in flight.
 #define RICADI_XCTL 4096
 static size_t exchange_panel_capacity(const ricadi_ctx* c) { return c->xcap > RICADI_XCTL ? c->xcap - RICADI_XCTL : 0; }
+static void require_exchange_capacity(const ricadi_ctx* c, size_t bytes) {
+  if (bytes > exchange_panel_capacity(c))
+    throw HipError{"exchange buffer too small: " + std::to_string(bytes + RICADI_XCTL) + " bytes per rank needed, " +
+                   std::to_string(c->xcap) + " given to ricadi_set_exchange"};
+}
+// All-gather of `count` doubles per rank through the host's collective (ricadi_set_exchange): the ranks' first
+// `count` doubles of `send` arrive rank-major in `recv`.  The context stream is drained first (callback) or the
+// collective is ordered on it (RCCL).
 static void exchange_at(ricadi_ctx* c, double* send, double* recv, size_t count) {
   ++c->xcount;
   if (c->xcomm) {
@@ -42,10 +37,9 @@ static void exchange_at(ricadi_ctx* c, double* send, double* recv, size_t count)
   const int rc = c->xfn(c->xuser, send, recv, (int64_t)(count * sizeof(double)));
   if (rc != 0) throw HipError{"the all-gather callback of ricadi_set_exchange failed (" + std::to_string(rc) + ")"};
 }
+// ... of the panels: c->xsend to c->xrecv
 static void exchange(ricadi_ctx* c, size_t count) {
-  if (count * sizeof(double) > exchange_panel_capacity(c))
-    throw HipError{"exchange buffer too small: " + std::to_string(count * sizeof(double) + RICADI_XCTL) +
-                   " bytes per rank needed, " + std::to_string(c->xcap) + " given to ricadi_set_exchange"};
+  require_exchange_capacity(c, count * sizeof(double));
   exchange_at(c, c->xsend, c->xrecv, count);
 }
 static double* ctl_send(ricadi_ctx* c) { return c->xsend + exchange_panel_capacity(c) / sizeof(double); }
@@ -110,13 +104,47 @@ static bool setup_overlap_begin(ricadi_ctx* c, const double* shifts, int nuse, b
   setup_issue(c, aux_exec(c), shifts, be.data(), nuse, sds.data(), job);
   return true;
 }
+// body(); with `fail` given, what it throws is recorded there instead
+template <class F>
+static void run_guarded(std::string* fail, F&& body) {
+  if (!fail) {
+    body();
+    return;
+  }
+  try {
+    body();
+  } catch (const HipError& e) {
+    *fail = e.msg;
+  } catch (const std::exception& e) {
+    *fail = e.what();
+  }
+}
+// What every driver does before its first shift solve: the per-shift setup of `shifts` and, with `project`, dW (NV x m)
+// <- P^T dW -- in the overlapped order where setup_overlap_begin takes it, else prefetch_setup; project_panel;
+// setup_finish.  `after_setup` runs between the setup and the projection (the drivers' timers).  With `fail` given
+// (rank-sharded sweeps) a failure of the serial setup or of the projection is recorded there instead of thrown, and
+// the projection is skipped once it is set.
+static void setup_and_project(ricadi_ctx* c, const double* shifts, int nuse, bool project, double* dW, int m,
+                              std::string* fail = nullptr, const std::function<void()>& after_setup = nullptr) {
+  SetupJob sjob;
+  if (!setup_overlap_begin(c, shifts, nuse, project, sjob))
+    run_guarded(fail, [&] { prefetch_setup(c, shifts, nuse, project); });
+  if (after_setup) after_setup();
+  if (project && (!fail || fail->empty())) run_guarded(fail, [&] { project_panel(c, dW, m); });
+  setup_finish(c, sjob);          // (overlapped order only: the projection's time then includes the wait for the setup)
+}
+
+// Control message: v[0..n) of every rank arrive rank-major in ctl_recv (queued; the caller fetches and waits)
+static void ctl_allgather(ricadi_ctx* c, const double* v, int n) {
+  if ((size_t)n * sizeof(double) > RICADI_XCTL) throw HipError{"control message too long"};
+  HIPCHK(hipMemcpyAsync(ctl_send(c), v, sizeof(double) * n, hipMemcpyHostToDevice, c->st));
+  exchange_at(c, ctl_send(c), ctl_recv(c), (size_t)n);
+}
 // v[0..n) <- rank 0's values (decisions must not differ between the ranks: the norms they rest on come
 // from kernels with atomic accumulation).  One tiny all-gather.
 static void values_of_rank0(ricadi_ctx* c, double* v, int n) {
   if (!sharded(c)) return;
-  if ((size_t)n * sizeof(double) > RICADI_XCTL) throw HipError{"control message too long"};
-  HIPCHK(hipMemcpyAsync(ctl_send(c), v, sizeof(double) * n, hipMemcpyHostToDevice, c->st));
-  exchange_at(c, ctl_send(c), ctl_recv(c), (size_t)n);
+  ctl_allgather(c, v, n);
   HIPCHK(hipMemcpyAsync(v, ctl_recv(c), sizeof(double) * n, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
 }
@@ -124,9 +152,7 @@ static void values_of_rank0(ricadi_ctx* c, double* v, int n) {
 static void reduce_over_ranks(ricadi_ctx* c, double* v, int nsum, int nmax) {
   if (!sharded(c)) return;
   const int n = nsum + nmax;
-  if ((size_t)n * sizeof(double) > RICADI_XCTL) throw HipError{"control message too long"};
-  HIPCHK(hipMemcpyAsync(ctl_send(c), v, sizeof(double) * n, hipMemcpyHostToDevice, c->st));
-  exchange_at(c, ctl_send(c), ctl_recv(c), (size_t)n);
+  ctl_allgather(c, v, n);
   std::vector<double> all((size_t)n * c->xworld);
   HIPCHK(hipMemcpyAsync(all.data(), ctl_recv(c), sizeof(double) * all.size(), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
@@ -199,198 +225,186 @@ static double gram_combination_fro(const double* Gm, int nc, int m, const int* b
   return std::sqrt(f);
 }
 
-static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, double* dW, int m,
-                                const ricadi_adi_params& prm, AdiStats& stt) {
+// ... of the single block `blk`
+static double gram_block_fro(const double* Gm, int nc, int m, int blk) {
+  const double one = 1.0;
+  return gram_combination_fro(Gm, nc, m, &blk, &one, 1);
+}
+
+static_assert(AdiStop::kMaxSteps == RICADI_STOP_MAX_STEPS && AdiStop::kNewZ == RICADI_STOP_NEWZ &&
+                  AdiStop::kRes == RICADI_STOP_RES, "AdiStop::Rule restates RICADI_STOP_*");
+
+// The shifts of one sweep with their Cauchy data: R^-1 (g x g, C_ij = -1/(p_i+p_j) = R^T R) and C^-1 1
+struct CauchySet {
+  std::vector<double> ps, rinv, cinv1;
+  // <- the g shifts behind step `first` of the cycle; false: their Cauchy matrix is numerically singular
+  bool fill(const double* shifts, int ns, int first, int g) {
+    ps.resize(g);
+    for (int i = 0; i < g; ++i) ps[i] = shifts[(first + i) % ns];
+    rinv.assign((size_t)g * g, 0.0);
+    cinv1.assign(g, 0.0);
+    return cauchy_data(ps.data(), g, rinv.data(), cinv1.data()) == RICADI_OK;
+  }
+};
+// out <- C_k^-1 1 of the leading k shifts of a sweep (R^-1 of the leading block is the leading block of R^-1)
+static void cauchy_cinv_prefix(const double* ps, int k, std::vector<double>& out) {
+  std::vector<double> rdummy((size_t)k * k, 0.0);
+  out.assign(k, 0.0);
+  if (cauchy_data(ps, k, rdummy.data(), out.data()) != RICADI_OK)
+    throw HipError{"Cauchy matrix of a truncated ADI sweep is numerically singular"};
+}
+
+// The sweep width G this shift list allows (0: none, the caller keeps the step form) and, in `cycle`, the Cauchy data
+// of every sweep until the shift pattern repeats.  A numerically singular Cauchy matrix (the shifts of a sweep too
+// many / too close: 16 consecutive entries of a 128-shift list over 3.5 decades) halves the width until every sweep
+// of the cycle is admissible -- as shift_parallel.py does.  Host arithmetic only: nothing is launched or allocated.
+static int admissible_width(const double* shifts, int ns, int m, const ricadi_adi_params& prm,
+                            std::vector<CauchySet>& cycle) {
   int G = std::min(std::min(prm.sweep_width, ns), RICADI_MAX_GROUPS);
   while (G >= 2 && (prm.adi_max_steps < G || G * m > 2048)) G /= 2;
-  if (G < 2) return false;
+  if (G < 2) return 0;
   for (int i = 0; i < ns; ++i)
     for (int j = i + 1; j < ns; ++j)
-      if (shifts[i] == shifts[j]) return false;     // sweeps need distinct shifts
-  // Cauchy data of every sweep of the cycle up front.  A numerically singular Cauchy matrix (the shifts of a
-  // sweep too many / too close: 16 consecutive entries of a 128-shift list over 3.5 decades) halves the sweep
-  // width until every sweep of the cycle is admissible -- as shift_parallel.py does --; only when no width
-  // >= 2 is left does the caller go back to the sequential form
-  int ncyc = 0;
-  std::vector<std::vector<double>> rinvs, cinvs, pss;
+      if (shifts[i] == shifts[j]) return 0;     // sweeps need distinct shifts
   for (; G >= 2; G /= 2) {
-    ncyc = ns / std::gcd(ns, G);                  // sweeps until the shift pattern repeats
-    rinvs.assign(ncyc, {});
-    cinvs.assign(ncyc, {});
-    pss.assign(ncyc, {});
+    cycle.assign(ns / std::gcd(ns, G), CauchySet());
     bool ok = true;
-    for (int sw = 0; sw < ncyc && ok; ++sw) {
-      pss[sw].resize(G);
-      for (int g = 0; g < G; ++g) pss[sw][g] = shifts[(sw * G + g) % ns];
-      rinvs[sw].resize((size_t)G * G);
-      cinvs[sw].resize(G);
-      ok = cauchy_data(pss[sw].data(), G, rinvs[sw].data(), cinvs[sw].data()) == RICADI_OK;
-    }
-    if (ok) break;
+    for (size_t sw = 0; sw < cycle.size() && ok; ++sw) ok = cycle[sw].fill(shifts, ns, (int)sw * G, G);
+    if (ok) return G;
   }
-  if (G < 2) return false;
-  hipStream_t st = c->st;
-  const int n = c->n, nv = c->nv;
-  const size_t nm = (size_t)n * m;
-  // Shift-parallel form (ricadi_set_exchange): every rank owns a fixed subset of the shift list --
-  // fixed, because the per-shift setup, the Sherman-Morrison-Woodbury panels and the recycled
-  // solutions live with the owner -- and solves only its shifts of a sweep; one all-gather per sweep.
-  const bool shard = sharded(c);
-  const int world = shard ? c->xworld : 1, rank = shard ? c->xrank : 0;
-  std::vector<int32_t> owner(ns, 0);
-  if (shard && deal_shifts(shifts, ns, world, owner.data()) != RICADI_OK) throw HipError{"bad shift list"};
-  ensure_work(c, m, G);
+  return 0;
+}
+
+// Sweep form of the ADI: G consecutive steps with distinct shifts are G
+// independent solves against the SAME residual factor,
+//   S(p_g) [U_g; *] = [W; 0],
+// recombined with the G x G Cauchy matrix C_ij = -1/(p_i+p_j) = R^T R:
+//   Z-block = U (R^-1 (x) I),   W <- W + E U ((C^-1 1) (x) I)
+// -- identical to the G sequential steps up to a rotation of the block's columns (Z Z^T and the gain are the same).
+// The G solves go through ONE batched lockstep GMRES, which is what fills the GPU at n ~ 3e4.  Column block j of
+// U R^-1 lies in span{U_1..U_j}: it IS the block the step-by-step iteration appends at step j (up to its sign), so
+// the stopping rules (AdiStop) are applied block by block, the blocks behind the stopping step are dropped, and the
+// iteration ends after the same step as the sequential one.  Any run of consecutive, distinct shifts is a valid
+// sweep; where AdiStop::cut shortens one, its Cauchy data are computed on the spot.
+//
+// Shift-parallel form (ricadi_set_exchange): every rank owns a fixed subset of the shift list -- fixed, because the
+// per-shift setup, the Sherman-Morrison-Woodbury panels and the recycled solutions live with the owner -- and solves
+// only its shifts of a sweep; one all-gather per sweep.  A failure in the OWNER-LOCAL work of a rank (per-shift
+// setup: a singular block; its solves) must not leave the other ranks waiting in that all-gather: it is recorded in
+// `fail` (guarded), the rank still takes part in the exchange -- with zero panels and its status word set --, and
+// all ranks throw together once the words have gone round.  The words ride in the pressure rows of each rank's first
+// solution panel (the recombination reads velocity rows only), so a sweep costs ONE collective.
+//
+// One sweep is the phases of run(), in that order; the members below them are what one phase leaves for the next.
+struct SweepAdi {
+  ricadi_ctx* const c;
+  const double* const shifts;
+  double* const dW;
+  const ricadi_adi_params& prm;
+  AdiStats& stt;
+  const std::vector<CauchySet>& cycle;
+  const hipStream_t st;
+  const bool shard, words_fit;      // words_fit: the status words ride in the pressure rows
+  const int ns, m, G, nv, world, rank;
+  const size_t nm;
+  std::vector<int32_t> owner;
+  std::string fail;
   Tick tk;
-  auto lap = [&](double& acc) {
+  AdiStop stop;
+  AsyncRecompress job;
+  long it0 = 0;
+  int zc_last = 0, steps = 0, sw = 0;
+  std::vector<double> be, coef, hn, cpre, dpre;
+  std::vector<int> bpre;
+  std::vector<ShiftData*> sds;
+  std::vector<GmresResult> res;
+  CauchySet var;                    // Cauchy data of a sweep that is not one of the cycle's
+  // the sweep in hand: its width and the blocks of it that stay; its Cauchy data; where solution g sits in the
+  // buffer the recombination reads and this rank's g; this rank's solutions and all of them, slot-major
+  int Gs = 0, kept = 0, per_rank = 0, nslot = 0, nmine = 0, nc = 0;
+  bool stopped = false;
+  const CauchySet* cs = nullptr;
+  std::vector<int> slot_of, mine;
+  double* usolve = nullptr;
+  const double* ubase = nullptr;
+  const double* hg = nullptr;       // residual rule: Gram matrix (nc x nc) of [W, E U_1, .., E U_nslot], pinned host
+  double words[2] = {0.0, 0.0};     // this rank's status word (a member: the upload may outlive gather())
+
+  // (after admissible_width: from here on device state is touched)
+  SweepAdi(ricadi_ctx* ctx, const double* shifts_, int ns_, double* dW_, int m_, const ricadi_adi_params& prm_,
+           AdiStats& stt_, int G_, const std::vector<CauchySet>& cycle_)
+      : c(ctx), shifts(shifts_), dW(dW_), prm(prm_), stt(stt_), cycle(cycle_), st(ctx->st), shard(sharded(ctx)),
+        words_fit((size_t)ctx->np * m_ >= 2), ns(ns_), m(m_), G(G_), nv(ctx->nv), world(shard ? ctx->xworld : 1),
+        rank(shard ? ctx->xrank : 0), nm((size_t)ctx->n * m_), owner(ns_, 0),
+        stop(ns_, prm_.adi_newZ_reltol, prm_.adi_res_reltol, prm_.adi_max_steps, adi_res_wanted(ctx, prm_)), job(ctx),
+        be(G_, 1.0), sds(G_), res(G_) {
+    if (shard && deal_shifts(shifts, ns, world, owner.data()) != RICADI_OK) throw HipError{"bad shift list"};
+    ensure_work(c, m, G);
+    tk = Tick();
+  }
+
+  void lap(double& acc) {
     if (c->sw.timing) {
       (void)hipStreamSynchronize(st);
       acc += tk.lap();
     }
-  };
-  // A failure in the OWNER-LOCAL work of a rank (per-shift setup: a singular block; its solves) must not leave the
-  // other ranks waiting in the sweep's all-gather: it is recorded here, the rank still takes part in the exchange
-  // -- with zero panels and its status word set --, and all ranks throw together once the words have gone round.
-  // The words ride in the pressure rows of each rank's first solution panel (the recombination reads velocity
-  // rows only), so a sweep costs ONE collective.
-  std::string fail;
-  auto guarded = [&](auto&& body) {
-    if (!shard) {
-      body();
-      return;
-    }
-    try {
-      body();
-    } catch (const HipError& e) {
-      fail = e.msg;
-    } catch (const std::exception& e) {
-      fail = e.what();
-    }
-  };
-  const bool words_fit = (size_t)c->np * m >= 2;
-  SetupJob sjob;
-  if (!setup_overlap_begin(c, shifts, std::min(ns, prm.adi_max_steps), prm.project_w != 0, sjob))
-    guarded([&] {
-      std::vector<double> mine;
-      const int nuse = std::min(ns, prm.adi_max_steps);
-      for (int i = 0; i < nuse; ++i)
-        if (owner[i] == rank) mine.push_back(shifts[i]);
-      prefetch_setup(c, mine.data(), (int)mine.size(), prm.project_w != 0);
-    });
-  lap(c->t_setup);
-  if (prm.project_w) {
-    // (replicated: the projection operator is set up by every rank; a rank whose own setup failed skips it)
-    if (fail.empty()) guarded([&] { project_panel(c, dW, m); });
   }
-  setup_finish(c, sjob);          // (overlapped order only: `projection` then includes the wait for the setup)
-  lap(c->t_proj);
-  const long it0 = c->total_iters;
-  if (!shard) c->sweep_u.ensure(nm * G);
-  c->sweep_t.ensure((size_t)nv * m);
-  double znorm2 = 0.0;
-  int zc_last = c->zc;
-  std::vector<double> be(G, 1.0), coef;
-  std::vector<ShiftData*> sds(G);
-  std::vector<GmresResult> res(G);
-  AsyncRecompress job(c);
-  int steps = 0;
-  // relative block norm of the last two visits of every position of the shift cycle
-  std::vector<double> rel_h1(ns, 0.0), rel_h2(ns, 0.0);
-  std::vector<double> ps_var, rinv_var, cinv_var, cinv_kept, rdummy, hn;
-  // Residual rule: the relative residual after EVERY block of a sweep comes from one Gram matrix of the columns
-  // [W, E U_1, ..., E U_nslot] (launch_sweep_resid_panel, launch_gram_fixed: fixed summation order, so every rank
-  // gets the same bits from the same gathered panels and decides alone) and the closed-form coefficients C_j^-1 1
-  // of the leading Cauchy blocks.  ||W_0^T W_0|| is the leading block of the first sweep's matrix.
-  const bool res_on = adi_res_wanted(c, prm);
-  std::vector<double> res_h1(res_on ? ns : 0, 0.0), res_h2(res_on ? ns : 0, 0.0), cpre, dpre;
-  const double* hg = nullptr;
-  std::vector<int> bpre;
-  double res_rhs = -1.0;
-  for (int sw = 0;; ++sw) {
-    // Width of this sweep.  With C = R^T R (R upper triangular) column block j of U R^-1 lies in
-    // span{U_1..U_j}: it IS the block the step-by-step iteration appends at step j (up to its
-    // sign), so the reference's stopping rule -- relative norm of the new block below
-    // adi_newZ_reltol (optcont_main.py:123-124) -- is applied block by block below, and the
-    // iteration ends after the same step as the sequential one.  So that the solves behind
-    // the stopping step are not spent in vain, the block norms of the last two passes over
-    // the shift cycle predict that step (per cycle position: same shift, geometric decay)
-    // and the sweep is cut there (any run of consecutive, distinct shifts is a valid sweep;
-    // its Cauchy data are computed on the spot).
-    int g_now = G;
-    if (prm.adi_newZ_reltol > 0.0) {
-      for (int g = 0; g < G; ++g) {
-        const int pos = (steps + g) % ns;
-        if (rel_h1[pos] > 0.0 && rel_h2[pos] > rel_h1[pos]) {
-          const double pred = rel_h1[pos] * (rel_h1[pos] / rel_h2[pos]);
-          if (pred < prm.adi_newZ_reltol) {
-            g_now = g + 1;
-            break;
-          }
-        }
-      }
+  // owner-local work: when sharded its failure is recorded in `fail` instead of thrown
+  template <class F>
+  void guarded(F&& body) { run_guarded(shard ? &fail : nullptr, body); }
+  // row j of the coefficient table <- col[i * stride], i < cnt, replicated over the m columns, in buffer order
+  void fill_row(int j, const double* col, int stride, int cnt) {
+    for (int i = 0; i < cnt; ++i)
+      for (int cidx = 0; cidx < m; ++cidx) coef[((size_t)j * nslot + slot_of[i]) * m + cidx] = col[(size_t)i * stride];
+  }
+
+  // this rank's shifts of the first pass set up, W projected (replicated: every rank sets the projection operator up)
+  void prepare() {
+    std::vector<double> own;
+    for (int i = 0; i < std::min(ns, prm.adi_max_steps); ++i)
+      if (owner[i] == rank) own.push_back(shifts[i]);
+    setup_and_project(c, own.data(), (int)own.size(), prm.project_w != 0, dW, m, shard ? &fail : nullptr,
+                      [&] { lap(c->t_setup); });
+    lap(c->t_proj);
+    it0 = c->total_iters;
+    if (!shard) c->sweep_u.ensure(nm * G);
+    c->sweep_t.ensure((size_t)nv * m);
+    zc_last = c->zc;
+  }
+
+  const CauchySet& cauchy_of(int first, int g) {
+    if (g == G && first % G == 0) return cycle[(first / G) % cycle.size()];
+    if (!var.fill(shifts, ns, first, g)) throw HipError{"Cauchy matrix of a partial ADI sweep is numerically singular"};
+    return var;
+  }
+
+  // who solves what, and where solution g sits in the buffer the recombination reads
+  void deal() {
+    slot_of.assign(Gs, 0);
+    mine.clear();
+    // (not sharded: one rank that owns every shift)
+    std::vector<int> cnt(world, 0);
+    for (int g = 0; g < Gs; ++g) {
+      const int r = owner[(steps + g) % ns];
+      slot_of[g] = cnt[r]++;                       // index among its owner's items, completed below
+      if (r == rank) mine.push_back(g);
     }
-    if (prm.adi_res_reltol > 0.0) {
-      // the same extrapolation on the residual history (residual after this position of the last two cycles)
-      for (int g = 0; g < g_now; ++g) {
-        const int pos = (steps + g) % ns;
-        if (res_h1[pos] > 0.0 && res_h2[pos] > res_h1[pos] &&
-            res_h1[pos] * (res_h1[pos] / res_h2[pos]) <= prm.adi_res_reltol) {
-          g_now = g + 1;
-          break;
-        }
-      }
-    }
-    g_now = std::min(g_now, prm.adi_max_steps - steps);
-    if (g_now < 1) break;
-    const std::vector<double>* psp;
-    const std::vector<double>* rinvp;
-    const std::vector<double>* cinvp;
-    if (g_now == G && steps % G == 0) {
-      psp = &pss[(steps / G) % ncyc];
-      rinvp = &rinvs[(steps / G) % ncyc];
-      cinvp = &cinvs[(steps / G) % ncyc];
-    } else {
-      ps_var.resize(g_now);
-      for (int g = 0; g < g_now; ++g) ps_var[g] = shifts[(steps + g) % ns];
-      rinv_var.assign((size_t)g_now * g_now, 0.0);
-      cinv_var.assign(g_now, 0.0);
-      if (cauchy_data(ps_var.data(), g_now, rinv_var.data(), cinv_var.data()) != RICADI_OK)
-        throw HipError{"Cauchy matrix of a partial ADI sweep is numerically singular"};
-      psp = &ps_var;
-      rinvp = &rinv_var;
-      cinvp = &cinv_var;
-    }
-    const std::vector<double>& ps = *psp;
-    const std::vector<double>& rinv = *rinvp;
-    const std::vector<double>& cinv1 = *cinvp;
-    const int Gs = g_now;
-    // who solves what, and where solution g sits in the buffer the recombination reads
-    std::vector<int> slot_of(Gs), mine;
-    int per_rank = Gs;
-    if (shard) {
-      std::vector<int> cnt(world, 0);
-      for (int g = 0; g < Gs; ++g) {
-        const int r = owner[(steps + g) % ns];
-        slot_of[g] = cnt[r]++;                       // index among its owner's items, completed below
-        if (r == rank) mine.push_back(g);
-      }
-      per_rank = *std::max_element(cnt.begin(), cnt.end());
-      for (int g = 0; g < Gs; ++g) slot_of[g] += owner[(steps + g) % ns] * per_rank;
-    } else {
-      for (int g = 0; g < Gs; ++g) {
-        slot_of[g] = g;
-        mine.push_back(g);
-      }
-    }
-    const int nslot = world * per_rank, nmine = (int)mine.size();
+    per_rank = *std::max_element(cnt.begin(), cnt.end());
+    for (int g = 0; g < Gs; ++g) slot_of[g] += owner[(steps + g) % ns] * per_rank;
+    nslot = world * per_rank;
+    nmine = (int)mine.size();
+    nc = (nslot + 1) * m;
+  }
+
+  // this rank's solves of the sweep, all against the same W, in one lockstep batch
+  void solve_share() {
     std::vector<double> psm(nmine);
-    for (int k = 0; k < nmine; ++k) psm[k] = ps[mine[k]];
+    for (int k = 0; k < nmine; ++k) psm[k] = cs->ps[mine[k]];
     if (nmine && fail.empty()) guarded([&] { get_shifts(c, psm.data(), be.data(), nmine, sds.data()); });
     lap(c->t_setup);
-    double* usolve = shard ? c->xsend : c->sweep_u.p;
+    usolve = shard ? c->xsend : c->sweep_u.p;
     if (shard) {
-      if ((size_t)per_rank * nm * sizeof(double) > exchange_panel_capacity(c))
-        throw HipError{"exchange buffer too small: " + std::to_string((size_t)per_rank * nm * sizeof(double) + RICADI_XCTL) +
-                       " bytes per rank needed, " + std::to_string(c->xcap) + " given to ricadi_set_exchange"};
+      require_exchange_capacity(c, (size_t)per_rank * nm * sizeof(double));
       // padding slots travel as zeros (their coefficients are zero, but 0 * NaN is not)
       if (nmine < per_rank)
         HIPCHK(hipMemsetAsync(c->xsend + (size_t)nmine * nm, 0, sizeof(double) * nm * (per_rank - nmine), st));
@@ -413,38 +427,40 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
         }
       stt.shift_solves += nmine;
     }
-    const double* ubase = usolve;
-    double words[2] = {fail.empty() ? 0.0 : 1.0, 0.0};
-    if (shard) {
-      if (!fail.empty()) HIPCHK(hipMemsetAsync(c->xsend, 0, sizeof(double) * nm * per_rank, st));
-      if (words_fit) {
-        HIPCHK(hipMemcpyAsync(c->xsend + (size_t)nv * m, words, sizeof(words), hipMemcpyHostToDevice, st));
-      } else {
-        // no pressure rows to carry the words: a control message of their own
-        double any = words[0];
-        reduce_over_ranks(c, &any, 0, 1);
-        if (any != 0.0)
-          throw HipError{fail.empty() ? "another rank failed in its share of an ADI sweep" : fail};
-      }
-      exchange(c, (size_t)per_rank * nm);
-      ubase = c->xrecv;
+  }
+
+  // sharded: the sweep's one all-gather, this rank's status word with its panels
+  void gather() {
+    ubase = usolve;
+    if (!shard) return;
+    words[0] = fail.empty() ? 0.0 : 1.0;
+    if (!fail.empty()) HIPCHK(hipMemsetAsync(c->xsend, 0, sizeof(double) * nm * per_rank, st));
+    if (words_fit) {
+      HIPCHK(hipMemcpyAsync(c->xsend + (size_t)nv * m, words, sizeof(words), hipMemcpyHostToDevice, st));
+    } else {
+      // no pressure rows to carry the words: a control message of their own
+      double any = words[0];
+      reduce_over_ranks(c, &any, 0, 1);
+      if (any != 0.0) throw HipError{fail.empty() ? "another rank failed in its share of an ADI sweep" : fail};
     }
-    // coefficient rows (replicated over the m columns), in buffer order: Gs columns of R^-1, then C^-1 1
+    exchange(c, (size_t)per_rank * nm);
+    ubase = c->xrecv;
+  }
+
+  // Z <- [Z, U R^-1]: block j = sum_i rinv[i][j] U_i, with its squared norm; with the residual rule the Gram matrix
+  // of [W, E U_1, .., E U_nslot] (launch_sweep_resid_panel, launch_gram_fixed: fixed summation order, so every rank
+  // gets the same bits from the same gathered panels and decides alone).  One wait for all that the decisions need.
+  void recombine() {
+    // coefficient rows in buffer order: Gs columns of R^-1, then (advance_w) C^-1 1
     coef.assign((size_t)(Gs + 1) * nslot * m, 0.0);
-    auto fill_row = [&](int j, const double* col, int stride, int cnt) {   // row j <- col[i * stride], i < cnt
-      for (int i = 0; i < cnt; ++i)
-        for (int cidx = 0; cidx < m; ++cidx) coef[((size_t)j * nslot + slot_of[i]) * m + cidx] = col[(size_t)i * stride];
-    };
-    for (int j = 0; j < Gs; ++j) fill_row(j, rinv.data() + j, Gs, Gs);
+    for (int j = 0; j < Gs; ++j) fill_row(j, cs->rinv.data() + j, Gs, Gs);
     c->sweep_coef.ensure(coef.size());
     HIPCHK(hipMemcpyAsync(c->sweep_coef.p, coef.data(), sizeof(double) * (size_t)Gs * nslot * m,
                           hipMemcpyHostToDevice, st));
-    // Z <- [Z, U R^-1]: block j = sum_i rinv[i][j] U_i, with its squared norm
     const bool combined = sweep_blocks(c, ubase, nm, nslot, Gs, m, c->sweep_coef.p, c->Z.p, c->zld, c->zc, c->nrm2.p);
     hn.resize((size_t)Gs * m);
     HIPCHK(hipMemcpyAsync(hn.data(), c->nrm2.p, sizeof(double) * Gs * m, hipMemcpyDeviceToHost, st));
-    const int nc = (nslot + 1) * m;
-    if (res_on) {
+    if (stop.res_on) {
       c->res_pan.ensure((size_t)nv * nc);
       c->res_part.ensure(gram_fixed_partial_len(nv, nc));
       c->res_gram.ensure((size_t)nc * nc);
@@ -473,72 +489,59 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
     if (!combined)
       for (int o = 0; o < Gs * m; o += RICADI_XCTL / 8)
         values_of_rank0(c, hn.data() + o, std::min(RICADI_XCTL / 8, Gs * m - o));
-    if (res_on && res_rhs < 0.0) {
-      const int b0 = 0;
-      const double one = 1.0;
-      res_rhs = gram_combination_fro(hg, nc, m, &b0, &one, 1);
+    // ||W_0^T W_0|| is the leading block of the first sweep's matrix
+    if (stop.res_on && stop.res_rhs < 0.0) stop.res_rhs = gram_block_fro(hg, nc, m, 0);
+  }
+
+  // ||W_j^T W_j||_F of the residual factor after the first j + 1 blocks, W + sum_{i <= j} (C_{j+1}^-1 1)_i E U_i
+  double prefix_residual(int j) {
+    const double* cj = cs->cinv1.data();
+    if (j + 1 < Gs) {
+      cauchy_cinv_prefix(cs->ps.data(), j + 1, cpre);
+      cj = cpre.data();
     }
-    // the reference's rule, block by block; blocks behind the stopping step are dropped
-    int kept = Gs;
-    bool stop = false;
-    for (int j = 0; j < Gs; ++j) {
+    bpre.assign(j + 2, 0);
+    dpre.assign(j + 2, 1.0);
+    for (int i = 0; i <= j; ++i) {
+      bpre[i + 1] = 1 + slot_of[i];
+      dpre[i + 1] = cj[i];
+    }
+    return gram_combination_fro(hg, nc, m, bpre.data(), dpre.data(), j + 2);
+  }
+
+  // the rules, block by block; the blocks behind the stopping step are dropped
+  void decide() {
+    kept = Gs;
+    stopped = false;
+    for (int j = 0; j < Gs && !stopped; ++j) {
       double b2 = 0.0;
       for (int cc = 0; cc < m; ++cc) b2 += hn[(size_t)j * m + cc];
-      znorm2 += b2;
-      const double relj = znorm2 > 0.0 ? std::sqrt(b2 / znorm2) : 0.0;
-      const int pos = (steps + j) % ns;
-      rel_h2[pos] = rel_h1[pos];
-      rel_h1[pos] = relj;
-      stt.rel = relj;
-      int rule = relj < prm.adi_newZ_reltol ? RICADI_STOP_NEWZ : RICADI_STOP_MAX_STEPS;
-      if (res_on) {
-        // residual factor after the first j + 1 blocks: W + sum_{i <= j} (C_{j+1}^-1 1)_i E U_i
-        const double* cj = cinv1.data();
-        if (j + 1 < Gs) {
-          cpre.assign(j + 1, 0.0);
-          rdummy.assign((size_t)(j + 1) * (j + 1), 0.0);
-          if (cauchy_data(ps.data(), j + 1, rdummy.data(), cpre.data()) != RICADI_OK)
-            throw HipError{"Cauchy matrix of a truncated ADI sweep is numerically singular"};
-          cj = cpre.data();
-        }
-        bpre.assign(j + 2, 0);
-        dpre.assign(j + 2, 1.0);
-        for (int i = 0; i <= j; ++i) {
-          bpre[i + 1] = 1 + slot_of[i];
-          dpre[i + 1] = cj[i];
-        }
-        const double wf = gram_combination_fro(hg, nc, m, bpre.data(), dpre.data(), j + 2);
-        const double resj = res_rhs > 0.0 ? wf / res_rhs : 0.0;
-        c->adi_res_hist.push_back(resj);
-        res_h2[pos] = res_h1[pos];
-        res_h1[pos] = resj;
-        if (rule == RICADI_STOP_MAX_STEPS && prm.adi_res_reltol > 0.0 && resj <= prm.adi_res_reltol)
-          rule = RICADI_STOP_RES;
-      }
-      if (rule != RICADI_STOP_MAX_STEPS) {
+      const double wf = stop.res_on ? prefix_residual(j) : 0.0;
+      const AdiStop::Verdict v = stop.record(steps + j, b2, stop.res_on ? &wf : nullptr);
+      stt.rel = v.rel;
+      if (stop.res_on) c->adi_res_hist.push_back(v.res);
+      if (v.rule != RICADI_STOP_MAX_STEPS) {
         kept = j + 1;
-        stop = true;
-        c->adi_stop_rule = rule;
-        break;
+        stopped = true;
+        c->adi_stop_rule = v.rule;
       }
     }
-    // W <- W + E (U C^-1 1) over the blocks that are KEPT: every U_g was solved against the same W, so
-    // the first `kept` solutions are the sweep of the first `kept` shifts, whose Cauchy data differ only
-    // in C^-1 1 (R^-1 of the leading block is the leading block of R^-1) -- W stays the residual factor
-    // of the truncated Z, and ||W^T W|| the residual norm that is reported
-    const double* cw = cinv1.data();
+  }
+
+  // W <- W + E (U C^-1 1) over the blocks that are KEPT: every U_g was solved against the same W, so the first
+  // `kept` solutions are the sweep of the first `kept` shifts, whose Cauchy data differ only in C^-1 1 -- W stays
+  // the residual factor of the truncated Z, and ||W^T W|| the residual norm that is reported
+  void advance_w() {
+    const double* cw = cs->cinv1.data();
     if (kept < Gs) {
-      cinv_kept.assign(kept, 0.0);
-      rdummy.assign((size_t)kept * kept, 0.0);
-      if (cauchy_data(ps.data(), kept, rdummy.data(), cinv_kept.data()) != RICADI_OK)
-        throw HipError{"Cauchy matrix of a truncated ADI sweep is numerically singular"};
-      cw = cinv_kept.data();
+      cauchy_cinv_prefix(cs->ps.data(), kept, cpre);
+      cw = cpre.data();
     }
     fill_row(Gs, cw, 1, kept);
-    HIPCHK(hipMemcpyAsync(c->sweep_coef.p + (size_t)Gs * nslot * m, coef.data() + (size_t)Gs * nslot * m,
-                          sizeof(double) * (size_t)nslot * m, hipMemcpyHostToDevice, st));
-    launch_cols_update(st, nv, m, nslot, ubase, nm, c->sweep_coef.p + (size_t)Gs * nslot * m, 1.0,
-                       nullptr, nullptr, c->sweep_t.p);
+    double* crow = c->sweep_coef.p + (size_t)Gs * nslot * m;
+    HIPCHK(hipMemcpyAsync(crow, coef.data() + (size_t)Gs * nslot * m, sizeof(double) * (size_t)nslot * m,
+                          hipMemcpyHostToDevice, st));
+    launch_cols_update(st, nv, m, nslot, ubase, nm, crow, 1.0, nullptr, nullptr, c->sweep_t.p);
     launch_spmm(st, nv, c->E.rp.p, c->E.ci.p, c->E.v.p, c->sweep_t.p, m, nullptr, dW, m, dW, m, 1.0,
                 1.0, nullptr, m);
     HIPCHK(hipStreamSynchronize(st));     // `coef` is reused by the next sweep
@@ -548,43 +551,69 @@ static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, dou
     stt.sweeps = sw + 1;
     lap(c->t_recomb);
     const bool dbg = c->sw.debug_sweeps;
-    if (prm.verbose || dbg) {
-      int its = 0;
-      for (int k = 0; k < nmine; ++k) its = std::max(its, res[k].iters);
-      if (dbg) {
-        double wf = 0.0;
-        gram_norms(c, dW, c->nv, m, &wf, nullptr);
-        fprintf(stderr, "[ricadi rank %d] sweep %d: Gs %d kept %d per_rank %d nmine %d  ||W^T W|| %.6e  znorm2 %.6e  its", rank, sw + 1,
-                Gs, kept, per_rank, nmine, wf, znorm2);
-        for (int k = 0; k < nmine; ++k) fprintf(stderr, " %d", res[k].iters);
-        fprintf(stderr, "\n");
+    if (!prm.verbose && !dbg) return;
+    int its = 0;
+    for (int k = 0; k < nmine; ++k) its = std::max(its, res[k].iters);
+    if (dbg) {
+      double wf = 0.0;
+      gram_norms(c, dW, c->nv, m, &wf, nullptr);
+      fprintf(stderr, "[ricadi rank %d] sweep %d: Gs %d kept %d per_rank %d nmine %d  ||W^T W|| %.6e  znorm2 %.6e  its", rank, sw + 1,
+              Gs, kept, per_rank, nmine, wf, stop.znorm2);
+      for (int k = 0; k < nmine; ++k) fprintf(stderr, " %d", res[k].iters);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "[ricadi] ADI sweep %3d (steps %d..%d): rel new Z %9.3e, gmres its <= %d%s\n",
+            sw + 1, steps - kept + 1, steps, stt.rel, its, shard ? " (this rank)" : "");
+  }
+
+  void finish() {
+    job.finish();
+    lap(c->t_compress);
+    stt.gmres_iters = c->total_iters - it0;
+    if (shard) {
+      // a rank has only seen its own solves
+      double v[4] = {(double)stt.gmres_iters, (double)stt.shift_solves, (double)stt.nonconverged, stt.worst_relres};
+      reduce_over_ranks(c, v, 3, 1);
+      stt.gmres_iters = (long)(v[0] + 0.5);
+      stt.shift_solves = (long)(v[1] + 0.5);
+      stt.nonconverged = (long)(v[2] + 0.5);
+      stt.worst_relres = v[3];
+    }
+    gram_norms(c, dW, c->nv, m, &stt.res_fro, nullptr);
+  }
+
+  void run() {
+    prepare();
+    for (;; ++sw) {
+      Gs = stop.cut(steps, G);
+      if (Gs < 1) break;
+      cs = &cauchy_of(steps, Gs);
+      deal();
+      solve_share();
+      gather();
+      recombine();
+      decide();
+      advance_w();
+      if (stopped || steps >= prm.adi_max_steps) break;
+      if (prm.compress_cols > 0 && c->zc - zc_last >= prm.compress_cols) {
+        // splice in what the helper finished during the last sweeps, hand it the next prefix
+        job.finish();
+        job.start();
+        zc_last = c->zc;
+        lap(c->t_compress);
       }
-      fprintf(stderr, "[ricadi] ADI sweep %3d (steps %d..%d): rel new Z %9.3e, gmres its <= %d%s\n",
-              sw + 1, steps - kept + 1, steps, stt.rel, its, shard ? " (this rank)" : "");
     }
-    if (stop) break;
-    if (steps >= prm.adi_max_steps) break;
-    if (prm.compress_cols > 0 && c->zc - zc_last >= prm.compress_cols) {
-      // splice in what the helper finished during the last sweeps, hand it the next prefix
-      job.finish();
-      job.start();
-      zc_last = c->zc;
-      lap(c->t_compress);
-    }
+    finish();
   }
-  job.finish();
-  lap(c->t_compress);
-  stt.gmres_iters = c->total_iters - it0;
-  if (shard) {
-    // a rank has only seen its own solves
-    double v[4] = {(double)stt.gmres_iters, (double)stt.shift_solves, (double)stt.nonconverged, stt.worst_relres};
-    reduce_over_ranks(c, v, 3, 1);
-    stt.gmres_iters = (long)(v[0] + 0.5);
-    stt.shift_solves = (long)(v[1] + 0.5);
-    stt.nonconverged = (long)(v[2] + 0.5);
-    stt.worst_relres = v[3];
-  }
-  gram_norms(c, dW, c->nv, m, &stt.res_fro, nullptr);
+};
+
+// Returns false (nothing done) if the shift list does not allow sweeps.
+static bool lyap_adi_sweeps_dev(ricadi_ctx* c, const double* shifts, int ns, double* dW, int m,
+                                const ricadi_adi_params& prm, AdiStats& stt) {
+  std::vector<CauchySet> cycle;
+  const int G = admissible_width(shifts, ns, m, prm, cycle);
+  if (G < 2) return false;
+  SweepAdi(c, shifts, ns, dW, m, prm, stt, G, cycle).run();
   return true;
 }
 
@@ -597,6 +626,11 @@ static int adi_recycle_depth(const ricadi_ctx* c) {
   return e ? std::max(0, std::min(8, atoi(e))) : (c->n <= 200000 ? 5 : 3);
 }
 
+// Step form: one shift solve per step, S(p) [V; *] = [W; 0], then W <- W - 2 p E V and Z <- [Z, sqrt(-2p) V].
+// dW: NV x m device panel (overwritten by the final residual factor); the blocks are appended to c->Z (ld = c->zld)
+// starting at column c->zc.  Tries the sweep form first where sweep_width asks for it.  Both rules of AdiStop end the
+// iteration; what it reports goes to c->adi_res_hist / c->adi_stop_rule.  On a sharded context every rank runs this
+// form on its own solves and, with the residual evaluated, rank 0's verdict is handed round every step.
 static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double* dW, int m,
                              const ricadi_adi_params& prm) {
   AdiStats stt;
@@ -611,22 +645,15 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
   ensure_work(c, m);
   // per-shift data of the whole shift cycle (and of the projection) up front: the coarse
   // inverses then come out of one batched factorisation instead of one at a time
-  SetupJob sjob;
-  if (!setup_overlap_begin(c, shifts, std::min(ns, prm.adi_max_steps), prm.project_w != 0, sjob))
-    prefetch_setup(c, shifts, std::min(ns, prm.adi_max_steps), prm.project_w != 0);
-  if (prm.project_w) project_panel(c, dW, m);
-  setup_finish(c, sjob);
+  setup_and_project(c, shifts, std::min(ns, prm.adi_max_steps), prm.project_w != 0, dW, m);
   const long it0 = c->total_iters;
-  double znorm2 = 0.0;
   int zc_last = c->zc;
   // Residual rule: W^T W after every step (fixed-order Gram kernel), fetched with the block norms.  ||W_0^T W_0||
   // is launched here and fetched in the first step's synchronisation.
-  const bool res_on = adi_res_wanted(c, prm);
-  const int mm = m * m, blk0 = 0;
-  const double one = 1.0;
+  AdiStop stop(ns, prm.adi_newZ_reltol, prm.adi_res_reltol, prm.adi_max_steps, adi_res_wanted(c, prm));
+  const int mm = m * m;
   double* hg = nullptr;
-  double res_rhs = -1.0;
-  if (res_on) {
+  if (stop.res_on) {
     c->res_part.ensure(gram_fixed_partial_len(c->nv, m));
     c->res_gram.ensure((size_t)2 * mm);
     hg = res_host(c, (size_t)2 * mm);
@@ -651,10 +678,10 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
                 -2.0 * p, 1.0, nullptr, m);
     // Z <- [Z, sqrt(-2p) V]
     launch_copy_cols(st, c->nv, m, c->xs.p, m, 0, c->Z.p, c->zld, c->zc, std::sqrt(-2.0 * p));
-    double n2 = 0.0;
+    double n2 = 0.0, wf = 0.0;
     col_norms2(c, c->xs.p, c->nv, m, c->nrm2.p);
     HIPCHK(hipMemcpyAsync(c->h_resid, c->nrm2.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
-    if (res_on) {
+    if (stop.res_on) {
       launch_gram_fixed(st, c->nv, m, dW, m, c->res_part.p, c->res_gram.p + mm);
       c->res_launches += 2;
       HIPCHK(hipMemcpyAsync(hg, c->res_gram.p, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, st));
@@ -662,26 +689,27 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
     HIPCHK(hipStreamSynchronize(st));
     for (int j = 0; j < m; ++j) n2 += c->h_resid[j];
     n2 *= -2.0 * p;
-    znorm2 += n2;
+    if (stop.res_on) {
+      if (stop.res_rhs < 0.0) stop.res_rhs = gram_block_fro(hg, m, m, 0);
+      wf = gram_block_fro(hg + mm, m, m, 0);
+    }
+    AdiStop::Verdict v = stop.record(step - 1, n2, stop.res_on ? &wf : nullptr);
     c->zc += m;
     stt.steps = step;
-    stt.rel = znorm2 > 0.0 ? std::sqrt(n2 / znorm2) : 0.0;
+    stt.rel = v.rel;
     if (prm.verbose)
       fprintf(stderr, "[ricadi] ADI step %3d: shift %10.3e rel new Z %9.3e gmres its %d\n", step,
               p, stt.rel, r.iters);
-    int rule = stt.rel < prm.adi_newZ_reltol ? RICADI_STOP_NEWZ : RICADI_STOP_MAX_STEPS;
-    if (res_on) {
-      if (res_rhs < 0.0) res_rhs = gram_combination_fro(hg, m, m, &blk0, &one, 1);
-      const double wf = gram_combination_fro(hg + mm, m, m, &blk0, &one, 1);
-      double dec[2] = {res_rhs > 0.0 ? wf / res_rhs : 0.0, (double)rule};
-      values_of_rank0(c, dec, 2);       // (sharded: every rank runs this form on its own solves; rank 0 decides)
-      rule = (int)dec[1];
+    if (stop.res_on) {
+      // (sharded: every rank runs this form on its own solves, whose last bits differ; rank 0's residual and the
+      // rule it found go round, so that the ranks report the same history and end together)
+      double dec[2] = {v.res, (double)v.rule};
+      values_of_rank0(c, dec, 2);
+      v.rule = (int)dec[1];
       c->adi_res_hist.push_back(dec[0]);
-      if (rule == RICADI_STOP_MAX_STEPS && prm.adi_res_reltol > 0.0 && dec[0] <= prm.adi_res_reltol)
-        rule = RICADI_STOP_RES;
     }
-    if (rule != RICADI_STOP_MAX_STEPS) {
-      c->adi_stop_rule = rule;
+    if (v.rule != RICADI_STOP_MAX_STEPS) {
+      c->adi_stop_rule = v.rule;
       break;
     }
     if (prm.compress_cols > 0 && c->zc - zc_last >= prm.compress_cols) {

@@ -32,16 +32,16 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
   // the rhs factor W is projected once here; the K_k part is in range(P^T) already
   ricadi_adi_params p2 = *prm;
   Tick tk0;
-  SetupJob sjob;       // overlapped order (setup_overlap_begin): the solve time below includes the setup's finish
-  if (!setup_overlap_begin(c, shifts, std::min(ns, prm->adi_max_steps), prm->project_w != 0, sjob))
-    prefetch_setup(c, shifts, std::min(ns, prm->adi_max_steps), prm->project_w != 0);
-  const double t_pre = c->sw.timing ? ((void)hipStreamSynchronize(st), tk0.lap()) : 0.0;
-  if (prm->project_w) project_panel(c, dWm.p, mw);
-  setup_finish(c, sjob);
+  double t_pre = 0.0;
+  const int nuse = std::min(ns, prm->adi_max_steps);
+  // (overlapped order, setup_overlap_begin: the solve time below includes the setup's finish)
+  setup_and_project(c, shifts, nuse, prm->project_w != 0, dWm.p, mw, nullptr, [&] {
+    if (c->sw.timing) t_pre = ((void)hipStreamSynchronize(st), tk0.lap());
+  });
   if (c->sw.timing) {
     (void)hipStreamSynchronize(st);
     fprintf(stderr, "[ricadi timing] per-shift setup of %d shifts + projection operator %.1f ms, projection solve %.1f ms\n",
-            std::min(ns, prm->adi_max_steps), 1e3 * t_pre, 1e3 * tk0.lap());
+            nuse, 1e3 * t_pre, 1e3 * tk0.lap());
   }
   p2.project_w = 0;
   if (p2.compress_cols <= 0) {

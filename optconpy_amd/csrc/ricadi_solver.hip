@@ -20,4 +20,6 @@ namespace ricadi {
 #include "solver_adi.inl"
 }  // namespace ricadi
 #include "solver_newton.inl"
-#include "solver_capi.inl"
+#include "solver_capi.inl"         // guards, shared set-up, the product's entry points
+#include "solver_capi_probe.inl"   // the tests' probes
+#include "solver_capi_timing.inl"  // the benchmark's timers

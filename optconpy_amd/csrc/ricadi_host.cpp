@@ -1,10 +1,12 @@
 // ricadi_host.cpp -- host-side setup logic of libricadi_hip.so (no device code).
 //
-// Builds, once per operator, everything of the two-level preconditioner that
-// does not depend on the ADI shift: the unified saddle-point sparsity pattern,
-// the block-Jacobi partitions (greedy graph aggregation), the dense diagonal
-// blocks of cal A and cal E, the aggregation coarse space and its Galerkin
-// matrices.  The per-shift parts are linear combinations formed on the device.
+// Builds, once per operator and per level of the hierarchy, everything of the
+// preconditioner that does not depend on the ADI shift (build_setup, a list of
+// phases): the unified saddle-point sparsity pattern, the block-Jacobi
+// partitions (greedy graph aggregation), the dense diagonal blocks of cal A and
+// cal E, the aggregation coarse space chosen by the hierarchy rule and its
+// Galerkin matrices -- dense, or sparse for a child level.  The per-shift parts
+// are linear combinations formed on the device.
 // Nothing here follows reference code: the reference solves these systems with
 // SuperLU.
 #include <array>
@@ -52,22 +54,36 @@ void sort_rows(HostCsr& a) {
   }
 }
 
+// Counts the cnt keys key[k] in [0, nb) into ptr (ptr[b] .. ptr[b + 1] becomes the range of key b) and returns the
+// start of every range: scattering entry k to pos[key[k]]++ in entry order is the counting sort, stable in the entry
+// index, that the transposes and the row lists of a partition are.
+static std::vector<int> bucket_starts(int nb, const int* key, size_t cnt, std::vector<int>& ptr) {
+  ptr.assign(nb + 1, 0);
+  for (size_t k = 0; k < cnt; ++k) ptr[key[k] + 1]++;
+  for (int b = 0; b < nb; ++b) ptr[b + 1] += ptr[b];
+  return std::vector<int>(ptr.begin(), ptr.end() - 1);
+}
+
+// t = a^T for CSR arrays of nrows rows and ncols columns (entries of a row of t in the order of a's rows)
+static void transpose_arrays(int nrows, int ncols, const std::vector<int>& rp, const std::vector<int>& ci,
+                             const std::vector<double>& v, std::vector<int>& t_rp, std::vector<int>& t_ci,
+                             std::vector<double>& t_v) {
+  std::vector<int> pos = bucket_starts(ncols, ci.data(), ci.size(), t_rp);
+  t_ci.resize(ci.size());
+  t_v.resize(ci.size());
+  for (int i = 0; i < nrows; ++i)
+    for (int k = rp[i]; k < rp[i + 1]; ++k) {
+      const int d = pos[ci[k]]++;
+      t_ci[d] = i;
+      t_v[d] = v[k];
+    }
+}
+
 HostCsr transpose(const HostCsr& a) {
   HostCsr t;
   t.nrows = a.ncols;
   t.ncols = a.nrows;
-  t.rp.assign(t.nrows + 1, 0);
-  for (size_t k = 0; k < a.nnz(); ++k) t.rp[a.ci[k] + 1]++;
-  for (int i = 0; i < t.nrows; ++i) t.rp[i + 1] += t.rp[i];
-  t.ci.resize(a.nnz());
-  t.v.resize(a.nnz());
-  std::vector<int> pos(t.rp.begin(), t.rp.end() - 1);
-  for (int i = 0; i < a.nrows; ++i)
-    for (int k = a.rp[i]; k < a.rp[i + 1]; ++k) {
-      const int d = pos[a.ci[k]]++;
-      t.ci[d] = i;
-      t.v[d] = a.v[k];
-    }
+  transpose_arrays(a.nrows, a.ncols, a.rp, a.ci, a.v, t.rp, t.ci, t.v);
   return t;
 }
 
@@ -100,15 +116,35 @@ int aggregate(int n, const int* rp, const int* ci, int bsize, int* blk) {
   return nb;
 }
 
-static void lists_from_blocks(int n, const int* blk, int nb, std::vector<int>& ptr,
-                              std::vector<int>& rows) {
-  ptr.assign(nb + 1, 0);
-  for (int i = 0; i < n; ++i) ptr[blk[i] + 1]++;
-  for (int b = 0; b < nb; ++b) ptr[b + 1] += ptr[b];
+static void lists_from_blocks(int n, const int* blk, int nb, std::vector<int>& ptr, std::vector<int>& rows) {
+  std::vector<int> pos = bucket_starts(nb, blk, (size_t)n, ptr);
   rows.resize(n);
-  std::vector<int> pos(ptr.begin(), ptr.end() - 1);
   for (int i = 0; i < n; ++i) rows[pos[blk[i]]++] = i;
 }
+
+// Rows of a sparse matrix accumulated through a marker array: the first touch of a column in the current row appends
+// an entry (0.0 in each of the nval value arrays that share the pattern), so a row lists its columns in first-touch
+// order; slot() returns the entry to add to.
+struct RowAccumulator {
+  std::vector<int> where;
+  std::vector<int>& ci;
+  std::vector<double>* val[3];
+  int nval, r0 = 0;
+  RowAccumulator(int ncols, std::vector<int>& ci_, std::vector<double>* v0, std::vector<double>* v1 = nullptr,
+                 std::vector<double>* v2 = nullptr)
+      : where(ncols, -1), ci(ci_), val{v0, v1, v2}, nval(v2 ? 3 : v1 ? 2 : 1) {}
+  void begin_row() { r0 = (int)ci.size(); }
+  int slot(int col) {
+    int at = where[col];
+    if (at < r0) {              // not seen in this row yet
+      at = (int)ci.size();
+      where[col] = at;
+      ci.push_back(col);
+      for (int q = 0; q < nval; ++q) val[q]->push_back(0.0);
+    }
+    return at;
+  }
+};
 
 // Galerkin product R^T M C for aggregation maps: entry (i, j) of M goes to (rowmap[i], colmap[j]).
 // rows_ptr / rows_list: the fine rows of every coarse row.
@@ -118,20 +154,13 @@ static HostCsr galerkin(const HostCsr& M, int nrow_c, const int* rows_ptr, const
   out.nrows = nrow_c;
   out.ncols = ncol_c;
   out.rp.assign(1, 0);
-  std::vector<int> where(ncol_c, -1);
+  RowAccumulator acc(ncol_c, out.ci, &out.v);
   for (int a = 0; a < nrow_c; ++a) {
-    const int r0 = (int)out.ci.size();
+    acc.begin_row();
     for (int q = rows_ptr[a]; q < rows_ptr[a + 1]; ++q) {
       const int i = rows_list[q] - row_off;
       for (int k = M.rp[i]; k < M.rp[i + 1]; ++k) {
-        const int cj = colmap[M.ci[k]];
-        int at = where[cj];
-        if (at < r0) {
-          at = (int)out.ci.size();
-          where[cj] = at;
-          out.ci.push_back(cj);
-          out.v.push_back(0.0);
-        }
+        const int at = acc.slot(colmap[M.ci[k]]);
         out.v[at] += M.v[k];
       }
     }
@@ -204,24 +233,31 @@ ricadi_opts child_opts(const ricadi_opts& o, bool parent_is_child) {
 }
 int child_levels(const ricadi_opts& o, int levels) { return o.hierarchy == 1 ? levels - 1 : 2; }
 
-void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ricadi_opts& o,
-                 HostSetup& hs, int max_levels, double sa_omega) {
-  const int nv = A.nrows, np = J.nrows, n = nv + np;
-  hs.nv = nv;
-  hs.np = np;
-  hs.n = n;
-  HostCsr JT = transpose(J);
+// ---- build_setup: one phase per job -------------------------------------------------------------------------------
+// What the hierarchy rule decides for a level
+struct Aggregates {
+  std::vector<int> va, pa;   // aggregate of every velocity / pressure row
+  int kv = 0, kp = 0;        // how many there are
+  int av = 0, ap = 0;        // the aggregate sizes the rule ended with
+  bool multilevel = false;   // the coarse problem goes to a child level
+};
+// What more than one phase reads and no caller sees (the pressure blocks' map is read by its own phase only)
+struct SetupWork {
+  std::vector<int> vv_rp, vv_ci;   // velocity-velocity pattern (union of A and E), for the graph work
+  std::vector<int> pp_rp, pp_ci;   // pressure graph: pattern of J J^T
+  std::vector<int> blk, local;     // block-Jacobi block of a velocity row and the row's position in it
+};
 
-  // ---- unified saddle pattern -------------------------------------------
-  hs.s_rp.assign(n + 1, 0);
-  hs.s_ci.clear();
-  hs.s_srcA.clear();
-  hs.s_srcE.clear();
-  hs.s_srcJ.clear();
+// Owns s_rp, s_ci, s_srcA, s_srcE, s_srcJ, dA, dE (and w.vv_*): the unified saddle pattern with its three value sources.
+// dA / dE take the LAST stored entry (i, i) of a row; the smoothed prolongation SUMS the entries (i, i) of A (its dg).
+// The two differ only for a CSR with duplicate columns, which make_csr sorts but does not merge.
+static void saddle_pattern(const HostCsr& A, const HostCsr& E, const HostCsr& J, const HostCsr& JT, HostSetup& hs,
+                           SetupWork& w) {
+  const int nv = hs.nv, np = hs.np;
+  hs.s_rp.assign(hs.n + 1, 0);
   hs.dA.assign(nv, 0.0);
   hs.dE.assign(nv, 0.0);
-  // velocity-velocity pattern kept aside for the graph work
-  std::vector<int> vv_rp(nv + 1, 0), vv_ci;
+  w.vv_rp.assign(nv + 1, 0);
   for (int i = 0; i < nv; ++i) {
     int a = A.rp[i], ae = A.rp[i + 1], e = E.rp[i], ee = E.rp[i + 1];
     while (a < ae || e < ee) {
@@ -235,13 +271,13 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
       hs.s_srcA.push_back(va);
       hs.s_srcE.push_back(ve);
       hs.s_srcJ.push_back(0.0);
-      vv_ci.push_back(c);
+      w.vv_ci.push_back(c);
       if (c == i) {
         hs.dA[i] = va;
         hs.dE[i] = ve;
       }
     }
-    vv_rp[i + 1] = (int)vv_ci.size();
+    w.vv_rp[i + 1] = (int)w.vv_ci.size();
     for (int k = JT.rp[i]; k < JT.rp[i + 1]; ++k) {
       hs.s_ci.push_back(nv + JT.ci[k]);
       hs.s_srcA.push_back(0.0);
@@ -259,174 +295,166 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
     }
     hs.s_rp[nv + k + 1] = (int)hs.s_ci.size();
   }
+}
 
-  // ---- block-Jacobi partition of the velocity block -----------------------
+// Owns bs, nbv, bv_ptr, bv_rows, bv_A, bv_E (and w.blk, w.local): the block-Jacobi partition of the velocity block
+static void velocity_blocks(const HostCsr& A, const HostCsr& E, const ricadi_opts& o, HostSetup& hs, SetupWork& w) {
+  const int nv = hs.nv;
   const int bs = (o.bj_block <= 16) ? 16 : (o.bj_block <= 32 ? 32 : 64);
   hs.bs = bs;
-  std::vector<int> blk(nv);
-  hs.nbv = aggregate(nv, vv_rp.data(), vv_ci.data(), bs, blk.data());
-  lists_from_blocks(nv, blk.data(), hs.nbv, hs.bv_ptr, hs.bv_rows);
-  std::vector<int> local(nv);
+  w.blk.resize(nv);
+  hs.nbv = aggregate(nv, w.vv_rp.data(), w.vv_ci.data(), bs, w.blk.data());
+  lists_from_blocks(nv, w.blk.data(), hs.nbv, hs.bv_ptr, hs.bv_rows);
+  w.local.resize(nv);
   for (int b = 0; b < hs.nbv; ++b)
-    for (int k = hs.bv_ptr[b]; k < hs.bv_ptr[b + 1]; ++k) local[hs.bv_rows[k]] = k - hs.bv_ptr[b];
+    for (int k = hs.bv_ptr[b]; k < hs.bv_ptr[b + 1]; ++k) w.local[hs.bv_rows[k]] = k - hs.bv_ptr[b];
   hs.bv_A.assign((size_t)hs.nbv * bs * bs, 0.0);
   hs.bv_E.assign((size_t)hs.nbv * bs * bs, 0.0);
   for (int i = 0; i < nv; ++i) {
-    const int b = blk[i];
-    double* Ba = hs.bv_A.data() + (size_t)b * bs * bs + (size_t)local[i] * bs;
-    double* Be = hs.bv_E.data() + (size_t)b * bs * bs + (size_t)local[i] * bs;
+    const int b = w.blk[i];
+    double* Ba = hs.bv_A.data() + (size_t)b * bs * bs + (size_t)w.local[i] * bs;
+    double* Be = hs.bv_E.data() + (size_t)b * bs * bs + (size_t)w.local[i] * bs;
     for (int k = A.rp[i]; k < A.rp[i + 1]; ++k)
-      if (blk[A.ci[k]] == b) Ba[local[A.ci[k]]] += A.v[k];
+      if (w.blk[A.ci[k]] == b) Ba[w.local[A.ci[k]]] += A.v[k];
     for (int k = E.rp[i]; k < E.rp[i + 1]; ++k)
-      if (blk[E.ci[k]] == b) Be[local[E.ci[k]]] += E.v[k];
+      if (w.blk[E.ci[k]] == b) Be[w.local[E.ci[k]]] += E.v[k];
   }
+}
 
-  // ---- pressure graph (pattern of J J^T) and its block partition ----------
-  std::vector<int> pp_rp(np + 1, 0), pp_ci;
-  {
-    std::vector<int> mark(np, -1);
-    for (int k = 0; k < np; ++k) {
-      for (int q = J.rp[k]; q < J.rp[k + 1]; ++q) {
-        const int j = J.ci[q];
-        for (int t = JT.rp[j]; t < JT.rp[j + 1]; ++t) {
-          const int k2 = JT.ci[t];
-          if (mark[k2] != k) {
-            mark[k2] = k;
-            pp_ci.push_back(k2);
-          }
+// Owns nbp, bp_ptr, bp_rows (and w.pp_*): the pressure graph (pattern of J J^T) and its block partition
+static void pressure_blocks(const HostCsr& J, const HostCsr& JT, HostSetup& hs, SetupWork& w) {
+  const int np = hs.np;
+  w.pp_rp.assign(np + 1, 0);
+  std::vector<int> mark(np, -1);
+  for (int k = 0; k < np; ++k) {
+    for (int q = J.rp[k]; q < J.rp[k + 1]; ++q) {
+      const int j = J.ci[q];
+      for (int t = JT.rp[j]; t < JT.rp[j + 1]; ++t) {
+        const int k2 = JT.ci[t];
+        if (mark[k2] != k) {
+          mark[k2] = k;
+          w.pp_ci.push_back(k2);
         }
       }
-      std::sort(pp_ci.begin() + pp_rp[k], pp_ci.end());
-      pp_rp[k + 1] = (int)pp_ci.size();
     }
+    std::sort(w.pp_ci.begin() + w.pp_rp[k], w.pp_ci.end());
+    w.pp_rp[k + 1] = (int)w.pp_ci.size();
   }
   std::vector<int> pblk(std::max(np, 1));
-  hs.nbp = np > 0 ? aggregate(np, pp_rp.data(), pp_ci.data(), bs, pblk.data()) : 0;
+  hs.nbp = np > 0 ? aggregate(np, w.pp_rp.data(), w.pp_ci.data(), hs.bs, pblk.data()) : 0;
   lists_from_blocks(np, pblk.data(), hs.nbp, hs.bp_ptr, hs.bp_rows);
+}
 
-  // ---- dense J sub-blocks for the consistent SIMPLE Schur complement ---------
-  // S_bb = sum_beta J_{b,beta} Ahat_beta^-1 J_{b,beta}^T needs, per pressure block b,
-  // the bs x bs slices of J against every velocity block beta it touches.  J does
-  // not depend on the shift, so the slices are extracted once.
-  {
-    hs.jd_ptr.assign(1, 0);
-    hs.jd_vblk.clear();
-    hs.jd_val.clear();
-    std::vector<int> slot(std::max(hs.nbv, 1), -1), touched;
-    for (int b = 0; b < hs.nbp; ++b) {
-      touched.clear();
-      const size_t base = hs.jd_vblk.size();
-      for (int q = hs.bp_ptr[b]; q < hs.bp_ptr[b + 1]; ++q) {
-        const int k = hs.bp_rows[q], il = q - hs.bp_ptr[b];
-        for (int e = J.rp[k]; e < J.rp[k + 1]; ++e) {
-          const int j = J.ci[e], vb = blk[j];
-          if (slot[vb] < 0) {
-            slot[vb] = (int)touched.size();
-            touched.push_back(vb);
-            hs.jd_vblk.push_back(vb);
-            hs.jd_val.resize(hs.jd_val.size() + (size_t)bs * bs, 0.0);
-          }
-          hs.jd_val[(base + slot[vb]) * (size_t)bs * bs + (size_t)il * bs + local[j]] += J.v[e];
+// Owns jd_ptr, jd_vblk, jd_val: the dense J sub-blocks of the consistent SIMPLE Schur complement.
+// S_bb = sum_beta J_{b,beta} Ahat_beta^-1 J_{b,beta}^T needs, per pressure block b,
+// the bs x bs slices of J against every velocity block beta it touches.  J does
+// not depend on the shift, so the slices are extracted once.
+static void schur_j_blocks(const HostCsr& J, HostSetup& hs, const SetupWork& w) {
+  const int bs = hs.bs;
+  hs.jd_ptr.assign(1, 0);
+  std::vector<int> slot(std::max(hs.nbv, 1), -1), touched;
+  for (int b = 0; b < hs.nbp; ++b) {
+    touched.clear();
+    const size_t base = hs.jd_vblk.size();
+    for (int q = hs.bp_ptr[b]; q < hs.bp_ptr[b + 1]; ++q) {
+      const int k = hs.bp_rows[q], il = q - hs.bp_ptr[b];
+      for (int e = J.rp[k]; e < J.rp[k + 1]; ++e) {
+        const int j = J.ci[e], vb = w.blk[j];
+        if (slot[vb] < 0) {
+          slot[vb] = (int)touched.size();
+          touched.push_back(vb);
+          hs.jd_vblk.push_back(vb);
+          hs.jd_val.resize(hs.jd_val.size() + (size_t)bs * bs, 0.0);
+        }
+        hs.jd_val[(base + slot[vb]) * (size_t)bs * bs + (size_t)il * bs + w.local[j]] += J.v[e];
+      }
+    }
+    for (int vb : touched) slot[vb] = -1;
+    hs.jd_ptr.push_back((int)hs.jd_vblk.size());
+  }
+}
+
+// Owns sb_*: the row blocks and the tile format of the LDS-tiled SpMM.
+// Rows are visited aggregate by aggregate (compact mesh patches) and packed
+// greedily into blocks of <= kSbMaxRows rows whose set of distinct columns stays
+// within kSbMaxCols, so that the x tile of a block fits the LDS budget.
+constexpr int kSbMaxRows = 32, kSbMaxCols = 152;   // 152 x 16 x 8 B tiles: 8 workgroups per CU fit the 160 KB LDS
+static void saddle_tiles(HostSetup& hs) {
+  const int nv = hs.nv, np = hs.np, n = hs.n;
+  std::vector<int> order;
+  order.reserve(n);
+  for (int q = 0; q < nv; ++q) order.push_back(hs.bv_rows[q]);
+  for (int q = 0; q < np; ++q) order.push_back(nv + hs.bp_rows[q]);
+  hs.sb_rowptr.assign(1, 0);
+  hs.sb_rp.assign(1, 0);
+  hs.sb_cptr.assign(1, 0);
+  std::vector<int> stamp(n, -1), pos(n, -1), cols, brows;
+  int bid = 0;
+  size_t at = 0;
+  while (at < order.size()) {
+    cols.clear();
+    brows.clear();
+    // a velocity block never continues into the pressure rows
+    const bool vel = order[at] < nv;
+    while (at < order.size() && (int)brows.size() < kSbMaxRows && (order[at] < nv) == vel) {
+      const int row = order[at];
+      int fresh = 0;
+      for (int k = hs.s_rp[row]; k < hs.s_rp[row + 1]; ++k)
+        if (stamp[hs.s_ci[k]] != bid) ++fresh;
+      if (!brows.empty() && (int)cols.size() + fresh > kSbMaxCols) break;
+      for (int k = hs.s_rp[row]; k < hs.s_rp[row + 1]; ++k) {
+        const int c = hs.s_ci[k];
+        if (stamp[c] != bid) {
+          stamp[c] = bid;
+          cols.push_back(c);
         }
       }
-      for (int vb : touched) slot[vb] = -1;
-      hs.jd_ptr.push_back((int)hs.jd_vblk.size());
+      brows.push_back(row);
+      ++at;
     }
-  }
-
-  // ---- row blocks of the LDS-tiled SpMM ------------------------------------
-  // Rows are visited aggregate by aggregate (compact mesh patches) and packed
-  // greedily into blocks of <= 32 rows whose set of distinct columns stays
-  // within kSbMaxCols, so that the x tile of a block fits the LDS budget.
-  {
-    int kSbMaxRows = 32, kSbMaxCols = 152;   // 152 x 16 x 8 B tiles: 8 workgroups per CU fit the 160 KB LDS
-    std::vector<int> order;
-    order.reserve(n);
-    for (int q = 0; q < nv; ++q) order.push_back(hs.bv_rows[q]);
-    for (int q = 0; q < np; ++q) order.push_back(nv + hs.bp_rows[q]);
-    hs.sb_rowptr.assign(1, 0);
-    hs.sb_rows.clear();
-    hs.sb_rp.assign(1, 0);
-    hs.sb_cptr.assign(1, 0);
-    hs.sb_cols.clear();
-    hs.sb_perm.clear();
-    hs.sb_lidx.clear();
-    hs.sb_max_cols = hs.sb_max_nnz = 0;
-    std::vector<int> stamp(n, -1), pos(n, -1), cols, brows;
-    int bid = 0;
-    size_t at = 0;
-    while (at < order.size()) {
-      cols.clear();
-      brows.clear();
-      // a velocity block never continues into the pressure rows
-      const bool vel = order[at] < nv;
-      while (at < order.size() && (int)brows.size() < kSbMaxRows && (order[at] < nv) == vel) {
-        const int row = order[at];
-        int fresh = 0;
-        for (int k = hs.s_rp[row]; k < hs.s_rp[row + 1]; ++k)
-          if (stamp[hs.s_ci[k]] != bid) ++fresh;
-        if (!brows.empty() && (int)cols.size() + fresh > kSbMaxCols) break;
+    std::sort(cols.begin(), cols.end());
+    for (size_t j = 0; j < cols.size(); ++j) pos[cols[j]] = (int)j;
+    // Rows of similar length next to each other: a wave of the kernel steps through the 16-entry chunks of FOUR
+    // consecutive local rows together (DPP broadcasts need all lanes), i.e. through the LONGEST of the four;
+    // sorted by (half-)chunk count the four rows of a wave-pass need the same number of steps almost everywhere
+    // (P2 vertex / edge-midpoint rows differ by a factor two in their entry counts).
+    std::stable_sort(brows.begin(), brows.end(), [&](int a, int b) {
+      return (hs.s_rp[a + 1] - hs.s_rp[a] + 7) / 8 > (hs.s_rp[b + 1] - hs.s_rp[b] + 7) / 8;   // half chunks
+    });
+    const size_t nnz0 = hs.sb_perm.size();
+    // Entry order within a row: the kernel's 32-lane halves pair the local rows (2j, 2j+1), and
+    // their two ds_read_b64 of a step (16 columns = 128 B each) are conflict free iff the two tile
+    // rows have opposite parity (LDS bank = (byte / 4) mod 64).  Even local rows therefore list
+    // their even tile rows first, odd local rows their odd ones: the parities differ wherever both
+    // rows are in their first or both in their second part.
+    int ql = 0;
+    for (int row : brows) {
+      for (int pass = 0; pass < 2; ++pass)
         for (int k = hs.s_rp[row]; k < hs.s_rp[row + 1]; ++k) {
-          const int c = hs.s_ci[k];
-          if (stamp[c] != bid) {
-            stamp[c] = bid;
-            cols.push_back(c);
-          }
+          const int l = pos[hs.s_ci[k]];
+          const bool first = (l & 1) == (ql & 1);
+          if (first != (pass == 0)) continue;
+          hs.sb_perm.push_back(k);
+          hs.sb_lidx.push_back((uint16_t)l);
         }
-        brows.push_back(row);
-        ++at;
-      }
-      std::sort(cols.begin(), cols.end());
-      for (size_t j = 0; j < cols.size(); ++j) pos[cols[j]] = (int)j;
-      // Rows of similar length next to each other: a wave of the kernel steps through the 16-entry chunks of FOUR
-      // consecutive local rows together (DPP broadcasts need all lanes), i.e. through the LONGEST of the four;
-      // sorted by (half-)chunk count the four rows of a wave-pass need the same number of steps almost everywhere
-      // (P2 vertex / edge-midpoint rows differ by a factor two in their entry counts).  RICADI_SB_SORT=0: visit order.
-      const bool sort_rows_by_len = true;
-      if (sort_rows_by_len)
-        std::stable_sort(brows.begin(), brows.end(), [&](int a, int b) {
-          return (hs.s_rp[a + 1] - hs.s_rp[a] + 7) / 8 > (hs.s_rp[b + 1] - hs.s_rp[b] + 7) / 8;   // half chunks
-        });
-      const size_t nnz0 = hs.sb_perm.size();
-      // Entry order within a row: the kernel's 32-lane halves pair the local rows (2j, 2j+1), and
-      // their two ds_read_b64 of a step (16 columns = 128 B each) are conflict free iff the two tile
-      // rows have opposite parity (LDS bank = (byte / 4) mod 64).  Even local rows therefore list
-      // their even tile rows first, odd local rows their odd ones: the parities differ wherever both
-      // rows are in their first or both in their second part.
-      const bool parity_order = true;
-      int ql = 0;
-      for (int row : brows) {
-        for (int pass = 0; pass < 2; ++pass)
-          for (int k = hs.s_rp[row]; k < hs.s_rp[row + 1]; ++k) {
-            const int l = pos[hs.s_ci[k]];
-            const bool first = !parity_order || ((l & 1) == (ql & 1));
-            if (first != (pass == 0)) continue;
-            hs.sb_perm.push_back(k);
-            hs.sb_lidx.push_back((uint16_t)l);
-          }
-        hs.sb_rows.push_back(row);
-        hs.sb_rp.push_back((int)hs.sb_perm.size());
-        ++ql;
-      }
-      for (int c : cols) hs.sb_cols.push_back(c);
-      hs.sb_cptr.push_back((int)hs.sb_cols.size());
-      hs.sb_rowptr.push_back((int)hs.sb_rows.size());
-      hs.sb_max_cols = std::max(hs.sb_max_cols, (int)cols.size());
-      hs.sb_max_nnz = std::max(hs.sb_max_nnz, (int)(hs.sb_perm.size() - nnz0));
-      ++bid;
+      hs.sb_rows.push_back(row);
+      hs.sb_rp.push_back((int)hs.sb_perm.size());
+      ++ql;
     }
-    hs.sb_nblk = bid;
+    for (int c : cols) hs.sb_cols.push_back(c);
+    hs.sb_cptr.push_back((int)hs.sb_cols.size());
+    hs.sb_rowptr.push_back((int)hs.sb_rows.size());
+    hs.sb_max_cols = std::max(hs.sb_max_cols, (int)cols.size());
+    hs.sb_max_nnz = std::max(hs.sb_max_nnz, (int)(hs.sb_perm.size() - nnz0));
+    ++bid;
   }
+  hs.sb_nblk = bid;
+}
 
-  // ---- aggregation coarse space -------------------------------------------
-  hs.kc = hs.kcv = hs.kcp = 0;
-  hs.agg_ptr.assign(1, 0);
-  hs.agg_rows.clear();
-  hs.aggof.assign(n, 0);
-  hs.E0.clear();
-  hs.EM.clear();
-  hs.EJ.clear();
-  if (!o.use_coarse) return;
+// The hierarchy rule: the aggregates of this level and whether its coarse problem goes to a child level.  stiff: the
+// operator is one the smoothed prolongation is made for (sa_criterion).  Writes no HostSetup field.
+static Aggregates hierarchy_rule(const HostCsr& E, const ricadi_opts& o, int bs, int nv, int np, const SetupWork& w,
+                                 int max_levels, bool stiff) {
   // graph for velocity aggregates: pattern of cal E if it is a genuine
   // (mass-like) matrix -- keeps the components apart -- else the union pattern
   const bool e_graph = E.nnz() > (size_t)(2 * nv);
@@ -434,15 +462,14 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
   // pattern and mix the velocity components; a child level built on those stagnates (measured at n = 1e5:
   // relres 0.9 after 3000 iterations, two levels: 169) -- stay with two levels then.
   if (!e_graph) max_levels = 2;
-  const int* g_rp = e_graph ? E.rp.data() : vv_rp.data();
-  const int* g_ci = e_graph ? E.ci.data() : vv_ci.data();
+  const int* g_rp = e_graph ? E.rp.data() : w.vv_rp.data();
+  const int* g_ci = e_graph ? E.ci.data() : w.vv_ci.data();
   int av = std::max(1, o.agg_v), ap = std::max(1, o.agg_p);
   const bool fine = o.hierarchy == 1;
-  std::vector<int> va(nv), pa(std::max(np, 1));
+  Aggregates g;
+  g.va.resize(nv);
+  g.pa.resize(std::max(np, 1));
   int kv = 0, kp = 0;
-  // Is this an operator the smoothed prolongation is made for (stiffness-like, symmetric part dominant)?
-  double sa_rs = -1.0, sa_gamma = -1.0;
-  const bool stiff = sa_omega > 0.0 && np > 0 && sa_criterion(A, sa_rs, sa_gamma);
   for (int attempt = 0; attempt < 16; ++attempt) {
     // The coarse pressure aggregates must not coincide with the Schur
     // block-Jacobi blocks (same graph, same greedy rule, same size): with
@@ -450,8 +477,8 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
     // (measured: N=40, ap == bs == 32 stalls at 1e-2, ap in {16,24,48,64}
     // converges in 137-182 iterations).
     if (ap == bs) ap = ap + ap / 2;
-    kv = aggregate(nv, g_rp, g_ci, av, va.data());
-    kp = np > 0 ? aggregate(np, pp_rp.data(), pp_ci.data(), ap, pa.data()) : 0;
+    kv = aggregate(nv, g_rp, g_ci, av, g.va.data());
+    kp = np > 0 ? aggregate(np, w.pp_rp.data(), w.pp_ci.data(), ap, g.pa.data()) : 0;
     // Dense inverse of this level's coarse matrix whenever it fits coarse_max.  (Rounds 2-3 handed the coarse problem
     // to a child level from HALF of coarse_max on -- the per-shift inversion grows with k^3 and the child's matrix is
     // half as large -- tuned on the one-solve-per-shift cycle: cfg3, k 3 046 -> 1 658, 72 -> 79 iterations, 188 -> 160 ms
@@ -483,7 +510,7 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
       // an operator without pressure or without a mass-like cal E -- grows its aggregates until its inverse fits (by
       // 1.5 and at least one: a child starts from (2, 1)).
       if (max_levels > 2 && np > 0) {
-        hs.multilevel = true;
+        g.multilevel = true;
         break;
       }
       av += std::max(1, av / 2);
@@ -499,7 +526,7 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
     // pair of level-2 aggregate sizes).  Larger problems therefore still grow the
     // aggregates of THIS level, but only until the gentle child fits (in steps of 1.5, not 2).
     if (max_levels > 2 && np > 0 && !grow_first && 0.55 * kv + kp <= std::max(16, o.coarse_max)) {
-      hs.multilevel = true;
+      g.multilevel = true;
       break;
     }
     if (max_levels > 2 && np > 0) {
@@ -510,16 +537,59 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
     av *= 2;
     ap *= 2;
   }
-  hs.kcv = kv;
-  hs.kcp = kp;
-  hs.kc = kv + kp;
-  hs.agg_v = av;
-  hs.agg_p = ap;
-  const int kc = hs.kc;
-  for (int i = 0; i < nv; ++i) hs.aggof[i] = va[i];
-  for (int k = 0; k < np; ++k) hs.aggof[nv + k] = kv + pa[k];
-  lists_from_blocks(n, hs.aggof.data(), kc, hs.agg_ptr, hs.agg_rows);
-  // ---- prolongation P (rows): plain aggregation, or smoothed on the velocity rows ----------------
+  g.kv = kv;
+  g.kp = kp;
+  g.av = av;
+  g.ap = ap;
+  return g;
+}
+
+// Owns kc, kcv, kcp, agg_v, agg_p, multilevel, aggof, agg_ptr, agg_rows: the coarse space the rule chose
+static void coarse_space(const Aggregates& g, HostSetup& hs) {
+  hs.kcv = g.kv;
+  hs.kcp = g.kp;
+  hs.kc = g.kv + g.kp;
+  hs.agg_v = g.av;
+  hs.agg_p = g.ap;
+  hs.multilevel = g.multilevel;
+  hs.aggof.resize(hs.n);
+  for (int i = 0; i < hs.nv; ++i) hs.aggof[i] = g.va[i];
+  for (int k = 0; k < hs.np; ++k) hs.aggof[hs.nv + k] = g.kv + g.pa[k];
+  lists_from_blocks(hs.n, hs.aggof.data(), hs.kc, hs.agg_ptr, hs.agg_rows);
+}
+
+// rho(D^-1 K0), K0 = (A + A^T) / 2, D = dg: 20 steps of the power iteration from a fixed pseudo-random start
+static double jacobi_radius(const HostCsr& A, const HostCsr& At, const std::vector<double>& dg) {
+  const int nv = A.nrows;
+  std::vector<double> x(nv), y(nv);
+  unsigned sd = 12345u;
+  for (int i = 0; i < nv; ++i) {
+    sd = sd * 1664525u + 1013904223u;
+    x[i] = (double)(sd >> 8) / 16777216.0 - 0.5;
+  }
+  double rho = 0.0;
+  for (int it = 0; it < 20; ++it) {
+    double nx = 0.0, ny = 0.0;
+    for (int i = 0; i < nv; ++i) {
+      double t = 0.0;
+      for (int k = A.rp[i]; k < A.rp[i + 1]; ++k) t += A.v[k] * x[A.ci[k]];
+      for (int k = At.rp[i]; k < At.rp[i + 1]; ++k) t += At.v[k] * x[At.ci[k]];
+      y[i] = dg[i] != 0.0 ? 0.5 * t / dg[i] : 0.0;
+      nx += x[i] * x[i];
+      ny += y[i] * y[i];
+    }
+    rho = nx > 0.0 ? std::sqrt(ny / nx) : 0.0;
+    const double sc = ny > 0.0 ? 1.0 / std::sqrt(ny) : 0.0;
+    for (int i = 0; i < nv; ++i) x[i] = y[i] * sc;
+  }
+  return rho;
+}
+
+// Owns sa, p_*, pd_*, pt_*: the prolongation P by rows -- plain aggregation (sa = false, arrays empty), or smoothed on
+// the velocity rows -- with P - Y and P^T.  sa_rs / sa_gamma: the ratios of sa_criterion, for the verbose line.
+static void smoothed_prolongation(const HostCsr& A, const ricadi_opts& o, double sa_omega, bool stiff, double sa_rs,
+                                  double sa_gamma, HostSetup& hs, const Aggregates& g) {
+  const int nv = hs.nv, np = hs.np, kv = g.kv;
   hs.sa = sa_omega > 0.0 && !hs.multilevel && np > 0 && kv > 0;
   if (hs.sa) {
     hs.sa = stiff;
@@ -527,215 +597,191 @@ void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ric
       fprintf(stderr, "[ricadi] smoothed aggregation %s: row sums / diagonal of sym(cal A) = %.3f, skew / symmetric "
               "off-diagonal mass %.3f\n", hs.sa ? "on" : "off", sa_rs, sa_gamma);
   }
-  hs.p_rp.clear(); hs.p_ci.clear(); hs.p_v.clear();
-  hs.pt_rp.clear(); hs.pt_ci.clear(); hs.pt_v.clear();
-  hs.pd_rp.clear(); hs.pd_ci.clear(); hs.pd_v.clear();
-  if (hs.sa) {
-    const HostCsr At = transpose(A);
-    // damping relative to the spectral radius of D^-1 K0 (power iteration): the prolongation smoother
-    // I - omega D^-1 K0 must not amplify -- a mass-like cal A (lau.app_prj_via_sadpnt hands the mass matrix over
-    // as the operator) has rho ~ 4 for P2 elements, and omega = 0.67 made GMRES fail there
-    {
-      std::vector<double> dg(nv, 0.0), x(nv), y(nv);
-      for (int i = 0; i < nv; ++i)
-        for (int k = A.rp[i]; k < A.rp[i + 1]; ++k)
-          if (A.ci[k] == i) dg[i] += A.v[k];
-      unsigned sd = 12345u;
-      for (int i = 0; i < nv; ++i) {
-        sd = sd * 1664525u + 1013904223u;
-        x[i] = (double)(sd >> 8) / 16777216.0 - 0.5;
-      }
-      double rho = 0.0;
-      for (int it = 0; it < 20; ++it) {
-        double nx = 0.0, ny = 0.0;
-        for (int i = 0; i < nv; ++i) {
-          double t = 0.0;
-          for (int k = A.rp[i]; k < A.rp[i + 1]; ++k) t += A.v[k] * x[A.ci[k]];
-          for (int k = At.rp[i]; k < At.rp[i + 1]; ++k) t += At.v[k] * x[At.ci[k]];
-          y[i] = dg[i] != 0.0 ? 0.5 * t / dg[i] : 0.0;
-          nx += x[i] * x[i];
-          ny += y[i] * y[i];
-        }
-        rho = nx > 0.0 ? std::sqrt(ny / nx) : 0.0;
-        const double sc = ny > 0.0 ? 1.0 / std::sqrt(ny) : 0.0;
-        for (int i = 0; i < nv; ++i) x[i] = y[i] * sc;
-      }
-      if (rho > 2.0) sa_omega *= 2.0 / rho;
-      if (o.verbose) fprintf(stderr, "[ricadi] smoothed aggregation: rho(D^-1 K0) ~ %.2f, omega %.3f\n", rho, sa_omega);
+  if (!hs.sa) return;
+  const HostCsr At = transpose(A);
+  std::vector<double> dg(nv, 0.0);   // the SUM of the stored entries (i, i) of a row: D of the smoother and of rho
+  for (int i = 0; i < nv; ++i)
+    for (int k = A.rp[i]; k < A.rp[i + 1]; ++k)
+      if (A.ci[k] == i) dg[i] += A.v[k];
+  // damping relative to the spectral radius of D^-1 K0 (power iteration): the prolongation smoother
+  // I - omega D^-1 K0 must not amplify -- a mass-like cal A (lau.app_prj_via_sadpnt hands the mass matrix over
+  // as the operator) has rho ~ 4 for P2 elements, and omega = 0.67 made GMRES fail there
+  const double rho = jacobi_radius(A, At, dg);
+  if (rho > 2.0) sa_omega *= 2.0 / rho;
+  if (o.verbose) fprintf(stderr, "[ricadi] smoothed aggregation: rho(D^-1 K0) ~ %.2f, omega %.3f\n", rho, sa_omega);
+  hs.p_rp.assign(1, 0);
+  hs.pd_rp.assign(1, 0);
+  RowAccumulator acc(hs.kc, hs.p_ci, &hs.p_v);
+  for (int i = 0; i < nv; ++i) {
+    acc.begin_row();
+    auto add = [&](int a, double w) {
+      const int at = acc.slot(a);
+      hs.p_v[at] += w;
+    };
+    add(g.va[i], 1.0);
+    const double d = dg[i];
+    if (d != 0.0) {
+      const double sc = -0.5 * sa_omega / d;         // K0 = (A + A^T) / 2
+      for (int k = A.rp[i]; k < A.rp[i + 1]; ++k) add(g.va[A.ci[k]], sc * A.v[k]);
+      for (int k = At.rp[i]; k < At.rp[i + 1]; ++k) add(g.va[At.ci[k]], sc * At.v[k]);
     }
-    hs.p_rp.assign(1, 0);
-    hs.pd_rp.assign(1, 0);
-    std::vector<int> where(kc, -1);
-    for (int i = 0; i < nv; ++i) {
-      const int r0 = (int)hs.p_ci.size();
-      auto add = [&](int a, double w) {
-        int at = where[a];
-        if (at < r0) {
-          at = (int)hs.p_ci.size();
-          where[a] = at;
-          hs.p_ci.push_back(a);
-          hs.p_v.push_back(0.0);
-        }
-        hs.p_v[at] += w;
-      };
-      add(va[i], 1.0);
-      double d = 0.0;
-      for (int k = A.rp[i]; k < A.rp[i + 1]; ++k)
-        if (A.ci[k] == i) d += A.v[k];
-      if (d != 0.0) {
-        const double sc = -0.5 * sa_omega / d;         // K0 = (A + A^T) / 2
-        for (int k = A.rp[i]; k < A.rp[i + 1]; ++k) add(va[A.ci[k]], sc * A.v[k]);
-        for (int k = At.rp[i]; k < At.rp[i + 1]; ++k) add(va[At.ci[k]], sc * At.v[k]);
-      }
-      hs.p_rp.push_back((int)hs.p_ci.size());
-      for (int k = r0; k < (int)hs.p_ci.size(); ++k) {
-        hs.pd_ci.push_back(hs.p_ci[k]);
-        hs.pd_v.push_back(hs.p_v[k] - (hs.p_ci[k] == va[i] ? 1.0 : 0.0));
-      }
-      hs.pd_rp.push_back((int)hs.pd_ci.size());
+    hs.p_rp.push_back((int)hs.p_ci.size());
+    for (int k = acc.r0; k < (int)hs.p_ci.size(); ++k) {
+      hs.pd_ci.push_back(hs.p_ci[k]);
+      hs.pd_v.push_back(hs.p_v[k] - (hs.p_ci[k] == g.va[i] ? 1.0 : 0.0));
     }
-    for (int k = 0; k < np; ++k) {
-      hs.p_ci.push_back(kv + pa[k]);
-      hs.p_v.push_back(1.0);
-      hs.p_rp.push_back((int)hs.p_ci.size());
-    }
-    // P^T by rows
-    hs.pt_rp.assign(kc + 1, 0);
-    for (int c : hs.p_ci) hs.pt_rp[c + 1]++;
-    for (int a = 0; a < kc; ++a) hs.pt_rp[a + 1] += hs.pt_rp[a];
-    hs.pt_ci.resize(hs.p_ci.size());
-    hs.pt_v.resize(hs.p_ci.size());
-    std::vector<int> pos(hs.pt_rp.begin(), hs.pt_rp.end() - 1);
-    for (int i = 0; i < n; ++i)
-      for (int k = hs.p_rp[i]; k < hs.p_rp[i + 1]; ++k) {
-        const int at = pos[hs.p_ci[k]]++;
-        hs.pt_ci[at] = i;
-        hs.pt_v[at] = hs.p_v[k];
-      }
+    hs.pd_rp.push_back((int)hs.pd_ci.size());
   }
-  // the entries of row j of P (plain aggregation: the single (aggof[j], 1))
-  auto prow = [&](int j, const int*& ci, const double*& v) -> int {
-    static const double one = 1.0;
-    if (hs.sa) {
-      ci = hs.p_ci.data() + hs.p_rp[j];
-      v = hs.p_v.data() + hs.p_rp[j];
-      return hs.p_rp[j + 1] - hs.p_rp[j];
-    }
-    ci = hs.aggof.data() + j;
-    v = &one;
-    return 1;
-  };
+  for (int k = 0; k < np; ++k) {
+    hs.p_ci.push_back(kv + g.pa[k]);
+    hs.p_v.push_back(1.0);
+    hs.p_rp.push_back((int)hs.p_ci.size());
+  }
+  transpose_arrays(hs.n, hs.kc, hs.p_rp, hs.p_ci, hs.p_v, hs.pt_rp, hs.pt_ci, hs.pt_v);
+}
+
+// the entries of row j of P (plain aggregation: the single (aggof[j], 1))
+static int prolongation_row(const HostSetup& hs, int j, const int*& ci, const double*& v) {
+  static const double one = 1.0;
+  if (hs.sa) {
+    ci = hs.p_ci.data() + hs.p_rp[j];
+    v = hs.p_v.data() + hs.p_rp[j];
+    return hs.p_rp[j + 1] - hs.p_rp[j];
+  }
+  ci = hs.aggof.data() + j;
+  v = &one;
+  return 1;
+}
+
+// Owns l1A, l1E, l1J (a level with a child: its Galerkin matrices) or E0, EM, EJ (dense P^T A P, P^T E P and the
+// coarse J with its transpose)
+static void coarse_matrices(const HostCsr& A, const HostCsr& E, const HostCsr& J, HostSetup& hs, const Aggregates& g) {
+  const int nv = hs.nv, np = hs.np, kv = g.kv, kp = g.kp, kc = hs.kc;
   if (hs.multilevel) {
-    hs.l1A = galerkin(A, kv, hs.agg_ptr.data(), hs.agg_rows.data(), 0, va.data(), kv);
-    hs.l1E = galerkin(E, kv, hs.agg_ptr.data(), hs.agg_rows.data(), 0, va.data(), kv);
-    hs.l1J = galerkin(J, kp, hs.agg_ptr.data() + kv, hs.agg_rows.data(), nv, va.data(), kv);
-  } else {
+    hs.l1A = galerkin(A, kv, hs.agg_ptr.data(), hs.agg_rows.data(), 0, g.va.data(), kv);
+    hs.l1E = galerkin(E, kv, hs.agg_ptr.data(), hs.agg_rows.data(), 0, g.va.data(), kv);
+    hs.l1J = galerkin(J, kp, hs.agg_ptr.data() + kv, hs.agg_rows.data(), nv, g.va.data(), kv);
+    return;
+  }
   hs.E0.assign((size_t)kc * kc, 0.0);
   hs.EM.assign((size_t)kc * kc, 0.0);
   hs.EJ.assign((size_t)kc * kc, 0.0);
   for (int i = 0; i < nv; ++i) {
     const int *ri, *cj;
     const double *rw, *cw;
-    const int nri = prow(i, ri, rw);
+    const int nri = prolongation_row(hs, i, ri, rw);
     for (int k = A.rp[i]; k < A.rp[i + 1]; ++k) {
-      const int ncj = prow(A.ci[k], cj, cw);
+      const int ncj = prolongation_row(hs, A.ci[k], cj, cw);
       for (int a = 0; a < nri; ++a)
         for (int b = 0; b < ncj; ++b) hs.E0[(size_t)ri[a] * kc + cj[b]] += rw[a] * A.v[k] * cw[b];
     }
     for (int k = E.rp[i]; k < E.rp[i + 1]; ++k) {
-      const int ncj = prow(E.ci[k], cj, cw);
+      const int ncj = prolongation_row(hs, E.ci[k], cj, cw);
       for (int a = 0; a < nri; ++a)
         for (int b = 0; b < ncj; ++b) hs.EM[(size_t)ri[a] * kc + cj[b]] += rw[a] * E.v[k] * cw[b];
     }
   }
   for (int k = 0; k < np; ++k)
     for (int q = J.rp[k]; q < J.rp[k + 1]; ++q) {
-      const int cp = kv + pa[k];
+      const int cp = kv + g.pa[k];
       const int* cj;
       const double* cw;
-      const int ncj = prow(J.ci[q], cj, cw);
+      const int ncj = prolongation_row(hs, J.ci[q], cj, cw);
       for (int b = 0; b < ncj; ++b) {
         hs.EJ[(size_t)cp * kc + cj[b]] += J.v[q] * cw[b];
         hs.EJ[(size_t)cj[b] * kc + cp] += J.v[q] * cw[b];
       }
     }
-  }
-  // ---- prolongated operator S*Y (n x kc, sparse) -----------------------------
-  // Row i of the unified saddle pattern with its columns mapped to their aggregates and
-  // duplicates merged (a row touches ~6 aggregates instead of ~28 columns).  The
-  // residual after the coarse correction, r - S (Y e), is then one short-row CSR SpMM
-  // over the L2-resident coarse vector instead of a full saddle SpMM.
+}
+
+// Owns sy_rp, sy_ci, sy_A, sy_E, sy_J: the prolongated operator S*Y (n x kc, sparse).
+// Row i of the unified saddle pattern with its columns mapped to their aggregates and
+// duplicates merged (a row touches ~6 aggregates instead of ~28 columns).  The
+// residual after the coarse correction, r - S (Y e), is then one short-row CSR SpMM
+// over the L2-resident coarse vector instead of a full saddle SpMM.
+static void prolongated_operator(HostSetup& hs) {
   hs.sy_rp.assign(1, 0);
-  hs.sy_ci.clear();
-  hs.sy_A.clear();
-  hs.sy_E.clear();
-  hs.sy_J.clear();
-  {
-    std::vector<int> where(kc, -1);
-    for (int i = 0; i < n; ++i) {
-      const int r0 = (int)hs.sy_ci.size();
-      for (int k = hs.s_rp[i]; k < hs.s_rp[i + 1]; ++k) {
-        const int* cj;
-        const double* cw;
-        const int ncj = prow(hs.s_ci[k], cj, cw);
-        for (int b = 0; b < ncj; ++b) {
-          const int a = cj[b];
-          int at = where[a];
-          if (at < r0) {              // not seen in this row yet
-            at = (int)hs.sy_ci.size();
-            where[a] = at;
-            hs.sy_ci.push_back(a);
-            hs.sy_A.push_back(0.0);
-            hs.sy_E.push_back(0.0);
-            hs.sy_J.push_back(0.0);
-          }
-          hs.sy_A[at] += hs.s_srcA[k] * cw[b];
-          hs.sy_E[at] += hs.s_srcE[k] * cw[b];
-          hs.sy_J[at] += hs.s_srcJ[k] * cw[b];
-        }
+  RowAccumulator acc(hs.kc, hs.sy_ci, &hs.sy_A, &hs.sy_E, &hs.sy_J);
+  for (int i = 0; i < hs.n; ++i) {
+    acc.begin_row();
+    for (int k = hs.s_rp[i]; k < hs.s_rp[i + 1]; ++k) {
+      const int* cj;
+      const double* cw;
+      const int ncj = prolongation_row(hs, hs.s_ci[k], cj, cw);
+      for (int b = 0; b < ncj; ++b) {
+        const int at = acc.slot(cj[b]);
+        hs.sy_A[at] += hs.s_srcA[k] * cw[b];
+        hs.sy_E[at] += hs.s_srcE[k] * cw[b];
+        hs.sy_J[at] += hs.s_srcJ[k] * cw[b];
       }
-      hs.sy_rp.push_back((int)hs.sy_ci.size());
     }
+    hs.sy_rp.push_back((int)hs.sy_ci.size());
   }
-  // S*Y in the tile format of the LDS-tiled SpMM, on the SAME row blocks as S: per block
-  // the distinct aggregates its rows touch (the LDS tile of coarse-vector rows) and per
-  // entry the 16-bit tile row; values are gathered through sy_perm.
+}
+
+// Owns syb_*: S*Y in the tile format of the LDS-tiled SpMM, on the SAME row blocks as S: per block
+// the distinct aggregates its rows touch (the LDS tile of coarse-vector rows) and per
+// entry the 16-bit tile row; values are gathered through sy_perm.
+static void prolongated_tiles(HostSetup& hs) {
   hs.syb_rp.assign(1, 0);
   hs.syb_cptr.assign(1, 0);
-  hs.syb_cols.clear();
-  hs.syb_perm.clear();
-  hs.syb_lidx.clear();
-  hs.syb_max_cols = 0;
-  {
-    std::vector<int> pos(kc, -1), cols;
-    for (int b = 0; b < hs.sb_nblk; ++b) {
-      cols.clear();
-      for (int q = hs.sb_rowptr[b]; q < hs.sb_rowptr[b + 1]; ++q) {
-        const int row = hs.sb_rows[q];
-        for (int k = hs.sy_rp[row]; k < hs.sy_rp[row + 1]; ++k)
-          if (pos[hs.sy_ci[k]] < 0) {
-            pos[hs.sy_ci[k]] = 0;
-            cols.push_back(hs.sy_ci[k]);
-          }
-      }
-      std::sort(cols.begin(), cols.end());
-      for (size_t j = 0; j < cols.size(); ++j) pos[cols[j]] = (int)j;
-      for (int q = hs.sb_rowptr[b]; q < hs.sb_rowptr[b + 1]; ++q) {
-        const int row = hs.sb_rows[q];
-        for (int k = hs.sy_rp[row]; k < hs.sy_rp[row + 1]; ++k) {
-          hs.syb_perm.push_back(k);
-          hs.syb_lidx.push_back((uint16_t)pos[hs.sy_ci[k]]);
+  std::vector<int> pos(hs.kc, -1), cols;
+  for (int b = 0; b < hs.sb_nblk; ++b) {
+    cols.clear();
+    for (int q = hs.sb_rowptr[b]; q < hs.sb_rowptr[b + 1]; ++q) {
+      const int row = hs.sb_rows[q];
+      for (int k = hs.sy_rp[row]; k < hs.sy_rp[row + 1]; ++k)
+        if (pos[hs.sy_ci[k]] < 0) {
+          pos[hs.sy_ci[k]] = 0;
+          cols.push_back(hs.sy_ci[k]);
         }
-        hs.syb_rp.push_back((int)hs.syb_perm.size());
-      }
-      for (int c : cols) {
-        hs.syb_cols.push_back(c);
-        pos[c] = -1;
-      }
-      hs.syb_cptr.push_back((int)hs.syb_cols.size());
-      hs.syb_max_cols = std::max(hs.syb_max_cols, (int)cols.size());
     }
+    std::sort(cols.begin(), cols.end());
+    for (size_t j = 0; j < cols.size(); ++j) pos[cols[j]] = (int)j;
+    for (int q = hs.sb_rowptr[b]; q < hs.sb_rowptr[b + 1]; ++q) {
+      const int row = hs.sb_rows[q];
+      for (int k = hs.sy_rp[row]; k < hs.sy_rp[row + 1]; ++k) {
+        hs.syb_perm.push_back(k);
+        hs.syb_lidx.push_back((uint16_t)pos[hs.sy_ci[k]]);
+      }
+      hs.syb_rp.push_back((int)hs.syb_perm.size());
+    }
+    for (int c : cols) {
+      hs.syb_cols.push_back(c);
+      pos[c] = -1;
+    }
+    hs.syb_cptr.push_back((int)hs.syb_cols.size());
+    hs.syb_max_cols = std::max(hs.syb_max_cols, (int)cols.size());
   }
+}
+
+HostSetup build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const HostCsr& JT, const ricadi_opts& o,
+                      int max_levels, double sa_omega) {
+  HostSetup hs;
+  SetupWork w;
+  hs.nv = A.nrows;
+  hs.np = J.nrows;
+  hs.n = hs.nv + hs.np;
+  saddle_pattern(A, E, J, JT, hs, w);
+  velocity_blocks(A, E, o, hs, w);
+  pressure_blocks(J, JT, hs, w);
+  schur_j_blocks(J, hs, w);
+  saddle_tiles(hs);
+  if (!o.use_coarse) {   // no coarse space: kc = 0, one empty aggregate list
+    hs.agg_ptr.assign(1, 0);
+    hs.aggof.assign(hs.n, 0);
+    return hs;
+  }
+  // Is this an operator the smoothed prolongation is made for (stiffness-like, symmetric part dominant)?
+  double sa_rs = -1.0, sa_gamma = -1.0;
+  const bool stiff = sa_omega > 0.0 && hs.np > 0 && sa_criterion(A, sa_rs, sa_gamma);
+  const Aggregates g = hierarchy_rule(E, o, hs.bs, hs.nv, hs.np, w, max_levels, stiff);
+  coarse_space(g, hs);
+  smoothed_prolongation(A, o, sa_omega, stiff, sa_rs, sa_gamma, hs, g);
+  coarse_matrices(A, E, J, hs, g);
+  prolongated_operator(hs);
+  prolongated_tiles(hs);
+  return hs;
 }
 
 // Cauchy data of one shift-parallel ADI sweep:
@@ -949,19 +995,19 @@ static std::vector<double> block_slices(const HostSetup& hs, const std::vector<i
   return out;
 }
 
-void build_setup_checked(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ricadi_opts& o,
-                         HostSetup& hs, int max_levels, double sa_omega) {
-  build_setup(A, E, J, o, hs, max_levels, sa_omega);
-  if (!hs.sa) return;
+HostSetup build_setup_checked(const HostCsr& A, const HostCsr& E, const HostCsr& J, const HostCsr& JT,
+                              const ricadi_opts& o, int max_levels, double sa_omega) {
+  HostSetup hs = build_setup(A, E, J, JT, o, max_levels, sa_omega);
+  if (!hs.sa) return hs;
   // the folded first sweep takes per-block dense slices of S*P of at most 64 columns
   std::vector<int> ptr, cols;
   const int kmax = block_columns(hs, hs.sy_rp, hs.sy_ci, ptr, cols);
   if (kmax > 64 || !block_apply2_ok(hs.bs, 64)) {
     if (o.verbose)
       fprintf(stderr, "[ricadi] smoothed aggregation off: a velocity block touches %d coarse columns\n", kmax);
-    hs = HostSetup();
-    build_setup(A, E, J, o, hs, max_levels, 0.0);
+    return build_setup(A, E, J, JT, o, max_levels, 0.0);
   }
+  return hs;
 }
 
 // Multi-shift operands of a CSR matrix with three value sources (a, e, j) in the tile order perm; ncol_v: columns
@@ -1243,21 +1289,40 @@ int ricadi_host_sa_criterion(int nv, const int32_t* a_rp, const int32_t* a_ci, c
   return RICADI_OK;
 }
 
+// The operator of the three planning / tile entries below, and their common default for the smoothing weight
+struct HostOperator {
+  ricadi::HostCsr A, E, J, JT;
+};
+static double default_sa_omega(int np, const ricadi_opts& o) { return (np == 0 || o.bj_block != 32) ? 0.0 : 0.5; }
+
+// Their argument check (rest_ok: what an entry requires beyond the operator) and the operator itself -- J empty
+// without pressure; column ranges are not checked.  false: the error is set and names the entry.
+static bool host_operator(const char* entry, int nv, int np, const int32_t* a_rp, const int32_t* a_ci,
+                          const double* a_v, const int32_t* e_rp, const int32_t* e_ci, const double* e_v,
+                          const int32_t* j_rp, const int32_t* j_ci, const double* j_v, bool rest_ok, HostOperator& op) {
+  if (nv < 1 || np < 0 || !a_rp || !a_ci || !a_v || !e_rp || !e_ci || !e_v || (np > 0 && (!j_rp || !j_ci || !j_v)) ||
+      !rest_ok) {
+    ricadi::set_error(std::string(entry) + ": bad argument");
+    return false;
+  }
+  const int32_t zero = 0;
+  op.A = ricadi::make_csr(nv, nv, a_rp, a_ci, a_v);
+  op.E = ricadi::make_csr(nv, nv, e_rp, e_ci, e_v);
+  op.J = np > 0 ? ricadi::make_csr(np, nv, j_rp, j_ci, j_v) : ricadi::make_csr(0, nv, &zero, &zero, a_v);
+  op.JT = ricadi::transpose(op.J);
+  return true;
+}
+
 int ricadi_host_plan_levels(int nv, int np, const int32_t* a_rp, const int32_t* a_ci, const double* a_v,
                             const int32_t* e_rp, const int32_t* e_ci, const double* e_v, const int32_t* j_rp,
                             const int32_t* j_ci, const double* j_v, const ricadi_opts* opts, int32_t* out) {
-  if (nv < 1 || np < 0 || !a_rp || !a_ci || !a_v || !e_rp || !e_ci || !e_v || (np > 0 && (!j_rp || !j_ci || !j_v)) ||
-      !opts || !out) {
-    ricadi::set_error("ricadi_host_plan_levels: bad argument");
-    return RICADI_EINVAL;
-  }
   try {
-    const ricadi::HostCsr A = ricadi::make_csr(nv, nv, a_rp, a_ci, a_v), E = ricadi::make_csr(nv, nv, e_rp, e_ci, e_v);
-    const int32_t zero = 0;
-    const ricadi::HostCsr J = np > 0 ? ricadi::make_csr(np, nv, j_rp, j_ci, j_v) : ricadi::make_csr(0, nv, &zero, &zero, a_v);
-    ricadi::HostSetup hs;
-    const double sa_omega = (np == 0 || opts->bj_block != 32) ? 0.0 : 0.5;
-    ricadi::build_setup(A, E, J, *opts, hs, std::max(2, opts->max_levels), sa_omega);
+    HostOperator op;
+    if (!host_operator("ricadi_host_plan_levels", nv, np, a_rp, a_ci, a_v, e_rp, e_ci, e_v, j_rp, j_ci, j_v,
+                       opts && out, op))
+      return RICADI_EINVAL;
+    const ricadi::HostSetup hs = ricadi::build_setup(op.A, op.E, op.J, op.JT, *opts, std::max(2, opts->max_levels),
+                                                     default_sa_omega(np, *opts));
     out[0] = hs.kc == 0 ? 1 : hs.multilevel ? 3 : 2;
     out[1] = hs.kc;
     out[2] = hs.kcv;
@@ -1273,31 +1338,28 @@ int ricadi_host_plan_levels(int nv, int np, const int32_t* a_rp, const int32_t* 
 // One level of ricadi_host_plan_hierarchy and, through its Galerkin matrices, the levels below it: what
 // ricadi_set_operator does, without the device
 static void plan_level(const ricadi::HostCsr& A, const ricadi::HostCsr& E, const ricadi::HostCsr& J,
-                       const ricadi_opts& o, int levels, bool is_child, std::vector<std::array<int32_t, 9>>& rows) {
-  ricadi::HostSetup hs;
-  const double sa_omega = (is_child || J.nrows == 0 || o.bj_block != 32) ? 0.0 : 0.5;
-  ricadi::build_setup_checked(A, E, J, o, hs, levels, sa_omega);
+                       const ricadi::HostCsr& JT, const ricadi_opts& o, int levels, bool is_child,
+                       std::vector<std::array<int32_t, 9>>& rows) {
+  const ricadi::HostSetup hs =
+      ricadi::build_setup_checked(A, E, J, JT, o, levels, is_child ? 0.0 : default_sa_omega(J.nrows, o));
   rows.push_back({hs.nv, hs.np, hs.kcv, hs.kcp, hs.agg_v, hs.agg_p, hs.multilevel ? 1 : 0,
                   hs.multilevel ? 0 : hs.kc, hs.sa ? 1 : 0});
   if (hs.multilevel)
-    plan_level(hs.l1A, hs.l1E, hs.l1J, ricadi::child_opts(o, is_child), ricadi::child_levels(o, levels), true, rows);
+    plan_level(hs.l1A, hs.l1E, hs.l1J, ricadi::transpose(hs.l1J), ricadi::child_opts(o, is_child),
+               ricadi::child_levels(o, levels), true, rows);
 }
 
 int ricadi_host_plan_hierarchy(int nv, int np, const int32_t* a_rp, const int32_t* a_ci, const double* a_v,
                                const int32_t* e_rp, const int32_t* e_ci, const double* e_v, const int32_t* j_rp,
                                const int32_t* j_ci, const double* j_v, const ricadi_opts* opts, int32_t* nlevels_out,
                                int32_t* levels_out, int32_t* smoothed_out) {
-  if (nv < 1 || np < 0 || !a_rp || !a_ci || !a_v || !e_rp || !e_ci || !e_v || (np > 0 && (!j_rp || !j_ci || !j_v)) ||
-      !opts || !nlevels_out || !levels_out || (opts->hierarchy != 0 && opts->hierarchy != 1)) {
-    ricadi::set_error("ricadi_host_plan_hierarchy: bad argument");
-    return RICADI_EINVAL;
-  }
   try {
-    const ricadi::HostCsr A = ricadi::make_csr(nv, nv, a_rp, a_ci, a_v), E = ricadi::make_csr(nv, nv, e_rp, e_ci, e_v);
-    const int32_t zero = 0;
-    const ricadi::HostCsr J = np > 0 ? ricadi::make_csr(np, nv, j_rp, j_ci, j_v) : ricadi::make_csr(0, nv, &zero, &zero, a_v);
+    HostOperator op;
+    if (!host_operator("ricadi_host_plan_hierarchy", nv, np, a_rp, a_ci, a_v, e_rp, e_ci, e_v, j_rp, j_ci, j_v,
+                       opts && nlevels_out && levels_out && (opts->hierarchy == 0 || opts->hierarchy == 1), op))
+      return RICADI_EINVAL;
     std::vector<std::array<int32_t, 9>> rows;
-    plan_level(A, E, J, *opts, ricadi::root_levels(*opts), false, rows);
+    plan_level(op.A, op.E, op.J, op.JT, *opts, ricadi::root_levels(*opts), false, rows);
     if ((int)rows.size() > RICADI_MAX_HIERARCHY_LEVELS) throw std::runtime_error("more levels than the rule allows");
     *nlevels_out = (int32_t)rows.size();
     std::fill(levels_out, levels_out + 8 * RICADI_MAX_HIERARCHY_LEVELS, 0);
@@ -1318,19 +1380,14 @@ int ricadi_host_saddle_tiles(int nv, int np, const int32_t* a_rp, const int32_t*
                              const int32_t* j_ci, const double* j_v, const ricadi_opts* opts, int32_t* sizes_out,
                              int32_t* rows2, int32_t* rp2, int32_t* cols2, uint16_t* lidx, uint16_t* lidx_ms,
                              double* vAJ, double* vE, int32_t* perm, int32_t* s_rp, int32_t* s_ci, double* s_src) {
-  if (nv < 1 || np < 0 || !a_rp || !a_ci || !a_v || !e_rp || !e_ci || !e_v || (np > 0 && (!j_rp || !j_ci || !j_v)) ||
-      !opts || !sizes_out) {
-    ricadi::set_error("ricadi_host_saddle_tiles: bad argument");
-    return RICADI_EINVAL;
-  }
   try {
-    const ricadi::HostCsr A = ricadi::make_csr(nv, nv, a_rp, a_ci, a_v), E = ricadi::make_csr(nv, nv, e_rp, e_ci, e_v);
-    const int32_t zero = 0;
-    const ricadi::HostCsr J = np > 0 ? ricadi::make_csr(np, nv, j_rp, j_ci, j_v) : ricadi::make_csr(0, nv, &zero, &zero, a_v);
-    ricadi::HostSetup hs;
-    const double sa_omega = (np == 0 || opts->bj_block != 32) ? 0.0 : 0.5;
-    ricadi::build_setup_checked(A, E, J, *opts, hs, std::max(2, opts->max_levels), sa_omega);
-    const ricadi::PrecondRecords r = ricadi::build_records(hs, J, ricadi::transpose(J), false, true);
+    HostOperator op;
+    if (!host_operator("ricadi_host_saddle_tiles", nv, np, a_rp, a_ci, a_v, e_rp, e_ci, e_v, j_rp, j_ci, j_v,
+                       opts && sizes_out, op))
+      return RICADI_EINVAL;
+    const ricadi::HostSetup hs = ricadi::build_setup_checked(
+        op.A, op.E, op.J, op.JT, *opts, std::max(2, opts->max_levels), default_sa_omega(np, *opts));
+    const ricadi::PrecondRecords r = ricadi::build_records(hs, op.J, op.JT, false, true);
     const int nb = hs.sb_nblk, mc = std::max(hs.sb_max_cols, 1);
     const size_t nnz = hs.s_ci.size();
     const int32_t sz[8] = {hs.n, nb, hs.sb_max_cols, hs.sb_max_nnz, (int32_t)nnz, r.sb_ok ? 1 : 0, r.ms_ok ? 1 : 0,

@@ -39,8 +39,8 @@ struct VankaPatches {
 };
 VankaPatches vanka_patches(int nv, const HostCsr& J);
 
-// Host-built description of the saddle operator and the two-level
-// preconditioner's fixed (shift independent) parts.
+// Host-built description of the saddle operator and of the fixed (shift independent) parts of one level of the
+// preconditioner.
 struct HostSetup {
   int nv = 0, np = 0, n = 0;
   // unified saddle pattern, three value sources
@@ -60,8 +60,8 @@ struct HostSetup {
   // row = pressure dof local to its block, column = velocity dof local to its block
   std::vector<int> jd_ptr, jd_vblk;
   std::vector<double> jd_val;
-  // LDS-tiled SpMM: rows grouped in blocks of <= 64 (pairs of block-Jacobi
-  // aggregates = compact mesh patches); per block the distinct columns and
+  // LDS-tiled SpMM: rows grouped in blocks of <= 32 (visited block-Jacobi aggregate by
+  // aggregate = compact mesh patches); per block the distinct columns and
   // 16-bit local column indices; arrays in block order
   int sb_nblk = 0, sb_max_cols = 0, sb_max_nnz = 0;
   std::vector<int> sb_rowptr, sb_rows, sb_rp, sb_cptr, sb_cols, sb_perm;
@@ -93,12 +93,13 @@ struct HostSetup {
   std::vector<int> syb_rp, syb_cptr, syb_cols, syb_perm;
   std::vector<uint16_t> syb_lidx;
 };
-void build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ricadi_opts& o,
-                 HostSetup& hs, int max_levels = 2, double sa_omega = 0.0);
+// JT = transpose(J): the caller computes it once per level (build_records and the upload need it too)
+HostSetup build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, const HostCsr& JT, const ricadi_opts& o,
+                      int max_levels, double sa_omega);
 // build_setup, rebuilt without smoothed aggregation when the smoothed prolongation does not fit the folded first
 // sweep (a velocity block touching more than 64 coarse columns)
-void build_setup_checked(const HostCsr& A, const HostCsr& E, const HostCsr& J, const ricadi_opts& o,
-                         HostSetup& hs, int max_levels, double sa_omega);
+HostSetup build_setup_checked(const HostCsr& A, const HostCsr& E, const HostCsr& J, const HostCsr& JT,
+                              const ricadi_opts& o, int max_levels, double sa_omega);
 
 // The hierarchy below a level, shared by ricadi_set_operator and ricadi_host_plan_hierarchy: the levels the top
 // context may use (build_setup's max_levels: 2 = no child), and the options and levels of the child of a level with

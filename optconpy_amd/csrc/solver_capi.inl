@@ -276,9 +276,8 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   if (!c->borrowed) c->levels = root_levels(c->opts);
   // smoothed aggregation of the velocity prolongation: two-level setups, folded preconditioner cycle only
   const double sa_omega = (c->borrowed || np == 0 || c->opts.bj_block != 32) ? 0.0 : c->sw.sa_omega;
-  HostSetup hs;
-  build_setup_checked(A, E, J, c->opts, hs, c->levels, sa_omega);
   const HostCsr JT = transpose(J);
+  const HostSetup hs = build_setup_checked(A, E, J, JT, c->opts, c->levels, sa_omega);
   const PrecondRecords pr = build_records(hs, J, JT, c->sw.sweep_meta, c->sw.ms_spmm);
   // the child level (same stream and rocBLAS handle) takes the coarse problem
   c->cache.clear();

@@ -86,7 +86,7 @@ def make_precond(Ap, J, gv, variant, bs=32, av=16, ap=24, cc=None, pbs=None, sa=
     Yv = sps.csr_matrix((np.ones(nv), (np.arange(nv), va)), shape=(nv, kv))
     Yp = sps.csr_matrix((np.ones(npp), (np.arange(npp), pa)), shape=(npp, kp))
     if sa is not None:
-        # smoothed aggregation of the velocity prolongation as the product builds it (ricadi_host.cpp:build_setup):
+        # smoothed aggregation of the velocity prolongation as the product builds it (ricadi_host.cpp:smoothed_prolongation):
         # P_v = (I - omega D^-1 sym(cal A)) Y_v, omega = 0.5 (scaled down where rho(D^-1 K0) > 2), shift independent
         K0 = (0.5 * (sa + sa.T)).tocsr()
         dinv = 1.0 / sa.diagonal()

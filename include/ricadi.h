@@ -292,13 +292,16 @@ int ricadi_lyap_adi(ricadi_ctx* ctx, const double* shifts, int nshifts,
  * step): entry j-1 belongs to step j.  *n_out = number of steps recorded; at most `cap` entries are copied to
  * `out` (may be NULL with cap = 0).  The history is recorded when adi_res_reltol > 0 or after
  * ricadi_set_adi_res_history(ctx, 1); otherwise nothing is computed for it and *n_out = 0.  RICADI_ESTATE before
- * any ADI call.  No reference counterpart.                                                                     */
+ * any ADI call.  No reference counterpart.
+ * After ricadi_ric_radi(_dev) it is that call's history instead: the relative projected RICCATI residual
+ * ||R_j^T R_j||_F / ||R_0^T R_0||_F after every RADI step -- always recorded there, the quantity is free.        */
 int ricadi_adi_res_history(ricadi_ctx* ctx, double* out, int cap, int* n_out);
 /* on != 0: record the residual history also while adi_res_reltol = 0 (no rule is added by it).                 */
 int ricadi_set_adi_res_history(ricadi_ctx* ctx, int on);
 /* The rule that ended the most recent Lyapunov solve of the context (as above).  Every slot of the two stats
  * arrays is taken -- slot 7 of ricadi_lyap_adi's is the count of solves repeated with wider storage --, so the
- * value has a call of its own instead of a slot.  RICADI_ESTATE before any ADI call.                           */
+ * value has a call of its own instead of a slot.  RICADI_ESTATE before any ADI call.  After ricadi_ric_radi(_dev):
+ * the rule that ended that call, RICADI_STOP_RES (res_reltol) or RICADI_STOP_MAX_STEPS (max_steps).             */
 #define RICADI_STOP_MAX_STEPS 0          /* adi_max_steps reached                                               */
 #define RICADI_STOP_NEWZ 1               /* relative norm of the new block below adi_newZ_reltol                */
 #define RICADI_STOP_RES 2                /* relative residual at or below adi_res_reltol                        */
@@ -375,6 +378,44 @@ int ricadi_ric_newtonadi_dev(ricadi_ctx* ctx, const double* shifts, int nshifts,
                              const double* dB, int nb, const double* dW, int mw,
                              const double* dZ0, int c0, const double* dOldB,
                              const ricadi_adi_params* prm, int* c_out, double* stats_out);
+
+/* ---- a1r: low-rank RADI for the projected Riccati equation (Benner, Bujanovic, Kuerschner, Saak, Numer. Math.
+ * 2018; pru.proj_alg_ric_radi; no reference counterpart) -------------------------------------------------------
+ * The same equation as a1, cal A X cal E^T + cal E X cal A^T - cal E X B B^T X cal E^T + W W^T = 0 on ker J
+ * (with oldB: cal A + oldB B^T in place of cal A), solved directly for X = Z Z^T: one saddle-point shift solve with
+ * the current closed loop per step, no outer iteration, no initial iterate.  With R_0 = P^T W (project_w != 0;
+ * else W is taken as projected), U_0 = -oldB (or 0), step j with the real shift p < 0 of the cycle is
+ *   [[cal A - U B^T + p cal E, J^T], [J, 0]] [V; *] = [R; 0],   G = V^T B,   Y = I + G G^T = L L^T,
+ *   Z <- [Z, sqrt(-2p) V L^-T],   T = (-2p) V Y^-1,   R <- R + cal E T,   U <- U + (cal E T) G.
+ * The Riccati residual of Z Z^T is exactly R R^T: the call stops with RICADI_STOP_RES once
+ * ||R_j^T R_j||_F / ||R_0^T R_0||_F <= res_reltol, else with RICADI_STOP_MAX_STEPS after max_steps
+ * (ricadi_adi_stop_rule; the history: ricadi_adi_res_history).  The factor grows by mw columns per step and is
+ * recompressed whenever it has grown by compress_cols columns (<= 0: 512); it stays in the context
+ * (ricadi_factor_cols / _get / _get_dev).  Shift solves that miss the GMRES tolerance are counted, not fatal.
+ * B NV x nb, W NV x mw, oldB NV x nb or NULL; 1 <= nb <= 64, mw >= 1, mw + nb <= 128.  Z_out (may be NULL): NV x zcap
+ * doubles, zcap >= max_steps * mw.  K_out (may be NULL): the gain cal E X B = U + oldB, NV x nb.
+ * stats_out (>= 8 doubles): [steps, last relative residual, ||R_0^T R_0||_F, total GMRES iterations, shift solves,
+ * solves that missed the tolerance, their worst relative residual, solves repeated with wider storage].
+ * RICADI_EINVAL, before anything is launched, for bad widths, max_steps < 1, nshifts < 1, a shift >= 0 and
+ * zcap < max_steps * mw with Z_out given; RICADI_ESTATE on a context with an exchange set (nothing is sharded here);
+ * RICADI_EBREAKDOWN when Y has a pivot that is not positive and finite (NaN / Inf in a solve).
+ * Recycling of solved right-hand sides (ricadi_set_recycle) is off inside the call and as before after it.       */
+int ricadi_ric_radi(ricadi_ctx* ctx, const double* shifts, int nshifts, const double* B, int nb, const double* W,
+                    int mw, const double* oldB, int max_steps, double res_reltol, int compress_cols, int project_w,
+                    int verbose, double* Z_out, int zcap, int* c_out, double* K_out, double* stats_out);
+/* a1r with every panel ALREADY IN HBM (row-major, leading dimension = width; dOldB and dK_out may be NULL); the
+ * factor stays in the context.                                                                                  */
+int ricadi_ric_radi_dev(ricadi_ctx* ctx, const double* shifts, int nshifts, const double* dB, int nb,
+                        const double* dW, int mw, const double* dOldB, int max_steps, double res_reltol,
+                        int compress_cols, int project_w, int verbose, int* c_out, double* dK_out,
+                        double* stats_out);
+/* The dense part of ONE RADI step on device operands, for tests: dV (its first NV rows, leading dimension ldv >= m),
+ * dB NV x nb, dRU = [R | U] NV x (m + nb) updated in place, the new block of Z written to columns [zoff, zoff + m)
+ * of dZblk (leading dimension ldz >= zoff + m); dG_out m x nb; dC_out m x (2m + nb) (may be NULL):
+ * [sqrt(-2p) L^-T | (-2p) Y^-1 | (-2p) Y^-1 G].  1 <= m <= 127, 1 <= nb <= 64, p < 0.  All sums run in a fixed
+ * order: the same call gives bitwise the same outputs.  RICADI_EBREAKDOWN as above.                              */
+int ricadi_radi_update_dev(ricadi_ctx* ctx, double p, const double* dV, int ldv, int m, const double* dB, int nb,
+                           double* dRU, double* dZblk, int ldz, int zoff, double* dG_out, double* dC_out);
 
 /* ---- device-pointer level (multi-GPU orchestration, benchmarks) --------
  * Same operations on buffers that already live in HBM (e.g. torch tensors'

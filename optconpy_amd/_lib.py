@@ -17,10 +17,11 @@ LIB_PATH = os.environ.get("RICADI_LIB", os.path.join(_HERE, "libricadi_hip.so"))
 
 RICADI_OK = 0
 RICADI_ENOCONV = -3
+RICADI_STOP_MAX_STEPS, RICADI_STOP_NEWZ, RICADI_STOP_RES = 0, 1, 2      # ricadi_adi_stop_rule (include/ricadi.h)
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 406
+ABI_VERSION = 407
 
 
 class RicadiOpts(C.Structure):
@@ -86,6 +87,12 @@ SIGNATURES = {
     "ricadi_factor_get_dev": (C.c_int, [_vp, _vp, C.c_int]),
     "ricadi_ric_newtonadi_dev": (C.c_int, [_vp, _dp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp,
                                            C.POINTER(RicadiAdiParams), C.POINTER(C.c_int), _dp]),
+    "ricadi_ric_radi": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_int,
+                                  C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
+    "ricadi_ric_radi_dev": (C.c_int, [_vp, _dp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_double,
+                                      C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _vp, _dp]),
+    "ricadi_radi_update_dev": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int,
+                                         C.c_int, _vp, _vp]),
     "ricadi_spmm_dev": (C.c_int, [_vp, C.c_double, C.c_double, _vp, C.c_int, _vp]),
     "ricadi_shift_solve_dev": (C.c_int, [_vp, C.c_double, C.c_double, _vp, C.c_int, _vp,
                                          C.POINTER(C.c_int), _dp]),
@@ -629,6 +636,73 @@ class Context:
                     adi_sweeps=int(stats[11]), adi_stopped_by=self.adi_stopped_by())
         _warn_nonconverged(info)
         return Zt, info
+
+    @staticmethod
+    def _radi_info(stats, c, rule):
+        return dict(radi_steps=int(stats[0]), res_rel=stats[1], rhs_fro=stats[2], gmres_iters=int(stats[3]),
+                    shift_solves=int(stats[4]), cols=c, gmres_nonconverged=int(stats[5]),
+                    gmres_worst_relres=stats[6], storage_escalations=int(stats[7]), stop_rule=rule)
+
+    def ric_radi(self, shifts, B, W, oldB=None, max_steps=200, res_reltol=1e-10, compress_cols=0, project_w=True,
+                 verbose=False, fetch=True):
+        """``ricadi_ric_radi``: low-rank RADI for the projected Riccati equation on host panels.  Returns
+        ``(Z, K, info)``: the factor (``None`` with ``fetch=False``: it stays in the context), the gain
+        ``cal E X B`` and the statistics (``info['stop_rule']`` is ``'res'`` or ``'max_steps'``)."""
+        B = as_panel(B, self.nv)
+        W = as_panel(W, self.nv)
+        sh = np.ascontiguousarray(shifts, dtype=np.float64)
+        nb, mw = B.shape[1], W.shape[1]
+        oldB = None if oldB is None else as_panel(oldB, self.nv)
+        cap = max(int(max_steps), 0) * mw
+        Z = np.empty((self.nv, max(cap, 1))) if fetch else None
+        K = np.zeros((self.nv, nb))
+        cc = C.c_int(0)
+        stats = np.zeros(8)
+        self._zdev = None
+        _chk(self._lib.ricadi_ric_radi(
+            self._h, _d(sh), sh.size, _d(B), nb, _d(W), mw, None if oldB is None else _d(oldB), int(max_steps),
+            float(res_reltol), int(compress_cols), 1 if project_w else 0, 1 if verbose else 0,
+            None if Z is None else _d(Z), cap, C.byref(cc), _d(K), _d(stats)))
+        c = cc.value
+        if fetch:
+            Z = Z.ravel()[:self.nv * c].reshape(self.nv, c)
+            Z.flags.writeable = False        # as ric_newtonadi: gain(B, Z=<this array>) may use the device copy
+            self._zdev = Z
+        info = self._radi_info(stats, c, self.adi_stopped_by())
+        _warn_nonconverged(info)
+        return Z, K, info
+
+    def ric_radi_dev(self, shifts, B_t, W_t, old_t=None, max_steps=200, res_reltol=1e-10, compress_cols=0,
+                     project_w=True, verbose=False):
+        """``ricadi_ric_radi_dev``: every panel is a torch CUDA tensor (float64, contiguous, NV rows); the factor and
+        the gain come back as fresh CUDA tensors.  Returns ``(Zt, Kt, info)``."""
+        import torch
+        sh = np.ascontiguousarray(shifts, dtype=np.float64)
+        for t in (B_t, W_t, old_t):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                                      and t.dim() == 2 and t.shape[0] == self.nv):
+                raise ValueError("device panels must be contiguous float64 CUDA tensors with NV rows")
+        cc = C.c_int(0)
+        stats = np.zeros(8)
+        self._zdev = None
+        Kt = torch.zeros_like(B_t)
+        torch.cuda.current_stream().synchronize()          # the library runs on its own stream
+        _chk(self._lib.ricadi_ric_radi_dev(
+            self._h, _d(sh), sh.size, B_t.data_ptr(), B_t.shape[1], W_t.data_ptr(), W_t.shape[1],
+            None if old_t is None else old_t.data_ptr(), int(max_steps), float(res_reltol), int(compress_cols),
+            1 if project_w else 0, 1 if verbose else 0, C.byref(cc), Kt.data_ptr(), _d(stats)))
+        c = cc.value
+        Zt = torch.empty((self.nv, c), dtype=torch.float64, device=B_t.device)
+        if c > 0:
+            _chk(self._lib.ricadi_factor_get_dev(self._h, Zt.data_ptr(), c))
+        info = self._radi_info(stats, c, self.adi_stopped_by())
+        _warn_nonconverged(info)
+        return Zt, Kt, info
+
+    def radi_update_dev(self, p, v_ptr, ldv, m, b_ptr, nb, ru_ptr, z_ptr, ldz, zoff, g_ptr, c_ptr=None):
+        """``ricadi_radi_update_dev``: the dense part of one RADI step on device pointers (tests)."""
+        _chk(self._lib.ricadi_radi_update_dev(self._h, float(p), v_ptr, int(ldv), int(m), b_ptr, int(nb), ru_ptr,
+                                              z_ptr, int(ldz), int(zoff), g_ptr, c_ptr))
 
     def compress(self, Z=None, thresh=None, k=None):
         """``Z=None`` compresses the factor left on the device."""

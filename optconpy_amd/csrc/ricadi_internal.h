@@ -280,7 +280,7 @@ __host__ __device__ inline size_t rckb_index(int j, int c, int k) {
   return j < (k & ~3) ? ((size_t)(j >> 2) * 16 + c) * 4 + (j & 3) : (size_t)j * 16 + c;
 }
 
-// ---- kernel launchers (ricadi_spmm.hip, ricadi_arnoldi.hip, ricadi_precond.hip, ricadi_dense.hip) -----
+// ---- kernel launchers (ricadi_spmm.hip, ricadi_arnoldi.hip, ricadi_precond.hip, ricadi_dense.hip, ricadi_radi.hip) -----
 // The *_b launchers are the batched forms (GroupTab + group strides `gs*`, in
 // doubles); the plain ones run a single panel.
 void launch_spmm_h(hipStream_t st, const GroupTab& gt, int nrows, const int* rp, const int* ci,
@@ -560,6 +560,18 @@ void launch_sweep_resid_panel(hipStream_t st, int nrows, int m, int nslot, const
                               const double* ev, const double* W, const double* U, size_t ustride, double* P);
 size_t gram_fixed_partial_len(int n, int nc);
 void launch_gram_fixed(hipStream_t st, int n, int nc, const double* P, int ldp, double* partial, double* G);
+
+// K6: the dense part of a RADI step (ricadi_radi.hip).  vtb: G (m x nb) = V^T B of V (n rows, leading dimension ldv)
+// and B (n x nb), sums in a fixed order (`partial`: radi_vtb_partial_len doubles).  factor: one workgroup, m <= 127,
+// nb <= 64: Y = I + G G^T = L L^T and C = [sqrt(-2p) L^-T | (-2p) Y^-1 | (-2p) Y^-1 G] (m x (2m + nb)); *flag raised on
+// a pivot that is not positive and finite.  update: [R | U] (nv x (m + nb), in place) += (cal E V) C[:, m:], columns
+// [zc, zc + m) of Z (leading dimension zld) = V C[:, :m]; V is read on its first nv rows.
+size_t radi_vtb_partial_len(int n, int m, int nb);
+void launch_radi_vtb(hipStream_t st, int n, int m, int nb, const double* V, int ldv, const double* B, double* partial,
+                     double* G);
+void launch_radi_factor(hipStream_t st, int m, int nb, double p, const double* G, double* C, int* flag);
+void launch_radi_update(hipStream_t st, int nv, int m, int nb, const int* rp, const int* ci, const double* ev,
+                        const double* V, int ldv, const double* C, double* RU, double* Z, int zld, int zc);
 
 void set_error(const std::string& msg);
 

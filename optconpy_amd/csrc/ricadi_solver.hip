@@ -19,6 +19,7 @@ namespace ricadi {
 #include "solver_dense.inl"
 #include "solver_adi.inl"
 }  // namespace ricadi
+#include "solver_radi.inl"
 #include "solver_newton.inl"
 #include "solver_capi.inl"         // guards, shared set-up, the product's entry points
 #include "solver_capi_probe.inl"   // the tests' probes

@@ -112,7 +112,7 @@ static void factor_download(ricadi_ctx* c, double* Z_out) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 406; }
+int ricadi_version(void) { return 407; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
@@ -943,6 +943,75 @@ int ricadi_ric_newtonadi_dev(ricadi_ctx* c, const double* shifts, int ns, const 
   if (c_out) *c_out = c->zc;
   HIPCHK(hipStreamSynchronize(c->st));
   API_END
+}
+
+// ---- RADI (solver_radi.inl) ----
+// the checks both entries make before anything is launched
+static int check_radi(const ricadi_ctx* c, const double* shifts, int ns, const void* B, int nb, const void* W, int mw,
+                      int max_steps) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(ns >= 1 && shifts && B && W, RICADI_EINVAL, "bad argument");
+  REQUIRE(nb >= 1 && nb <= 64 && mw >= 1 && mw + nb <= RICADI_MAX_M, RICADI_EINVAL, "bad widths");
+  REQUIRE(max_steps >= 1, RICADI_EINVAL, "max_steps must be positive");
+  for (int i = 0; i < ns; ++i) REQUIRE(shifts[i] < 0.0, RICADI_EINVAL, "RADI shifts must be negative");
+  REQUIRE(!sharded(c), RICADI_ESTATE, "ricadi_ric_radi does not shard: clear the exchange of this context first");
+  return RICADI_OK;
+}
+static void radi_stats_out(const RadiStats& s, double* stats_out) {
+  if (!stats_out) return;
+  stats_out[0] = s.steps;
+  stats_out[1] = s.res;
+  stats_out[2] = s.rhs;
+  stats_out[3] = (double)s.gmres_iters;
+  stats_out[4] = (double)s.shift_solves;
+  stats_out[5] = (double)s.nonconverged;
+  stats_out[6] = s.worst_relres;
+  stats_out[7] = (double)s.escalations;
+}
+#define RADI_BREAKDOWN_MSG "RADI: I + G G^T has a pivot that is not positive and finite (NaN / Inf in a shift solve)"
+
+int ricadi_ric_radi(ricadi_ctx* c, const double* shifts, int ns, const double* B, int nb, const double* W, int mw,
+                    const double* oldB, int max_steps, double res_reltol, int compress_cols, int project_w,
+                    int verbose, double* Z_out, int zcap, int* c_out, double* K_out, double* stats_out) {
+  if (int rc = check_radi(c, shifts, ns, B, nb, W, mw, max_steps)) return rc;
+  REQUIRE(!Z_out || (long)zcap >= (long)max_steps * mw, RICADI_EINVAL, "Z_out capacity below max_steps * mw");
+  bool breakdown = false;
+  API_BEGIN_ON(c)
+  hipStream_t st = c->st;
+  const int nv = c->nv;
+  TArr<double> dB(c->pool, (size_t)nv * nb), dWm(c->pool, (size_t)nv * mw), dOld(c->pool), dK(c->pool);
+  HIPCHK(hipMemcpyAsync(dB.p, B, sizeof(double) * nv * nb, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dWm.p, W, sizeof(double) * nv * mw, hipMemcpyHostToDevice, st));
+  if (oldB) {
+    dOld.alloc((size_t)nv * nb);
+    HIPCHK(hipMemcpyAsync(dOld.p, oldB, sizeof(double) * nv * nb, hipMemcpyHostToDevice, st));
+  }
+  if (K_out) dK.alloc((size_t)nv * nb);
+  const RadiStats s = ric_radi_run(c, shifts, ns, dB.p, nb, dWm.p, mw, oldB ? dOld.p : nullptr, max_steps, res_reltol,
+                                   compress_cols, project_w != 0, verbose != 0, dK.p);
+  radi_stats_out(s, stats_out);
+  breakdown = s.breakdown;
+  if (c_out) *c_out = c->zc;
+  if (!breakdown) {
+    if (K_out) HIPCHK(hipMemcpyAsync(K_out, dK.p, sizeof(double) * nv * nb, hipMemcpyDeviceToHost, st));
+    if (Z_out && c->zc > 0) factor_download(c, Z_out);
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  API_END_STATUS(breakdown ? (ricadi::set_error(RADI_BREAKDOWN_MSG), RICADI_EBREAKDOWN) : RICADI_OK)
+}
+
+int ricadi_ric_radi_dev(ricadi_ctx* c, const double* shifts, int ns, const double* dB, int nb, const double* dW, int mw,
+                        const double* dOldB, int max_steps, double res_reltol, int compress_cols, int project_w,
+                        int verbose, int* c_out, double* dK_out, double* stats_out) {
+  if (int rc = check_radi(c, shifts, ns, dB, nb, dW, mw, max_steps)) return rc;
+  bool breakdown = false;
+  API_BEGIN_ON(c)
+  const RadiStats s = ric_radi_run(c, shifts, ns, dB, nb, dW, mw, dOldB, max_steps, res_reltol, compress_cols,
+                                   project_w != 0, verbose != 0, dK_out);
+  radi_stats_out(s, stats_out);
+  breakdown = s.breakdown;
+  if (c_out) *c_out = c->zc;
+  API_END_STATUS(breakdown ? (ricadi::set_error(RADI_BREAKDOWN_MSG), RICADI_EBREAKDOWN) : RICADI_OK)
 }
 
 // Copy of the device-resident factor into a DEVICE buffer (nv x cz row-major, ld cz; cz = ricadi_factor_cols)

@@ -480,4 +480,22 @@ int ricadi_dense_inverse_batch(ricadi_ctx* c, int k, int nb, double* A, int* rou
   API_END
 }
 
+// the dense part of one RADI step (radi_dense_step), synchronous
+int ricadi_radi_update_dev(ricadi_ctx* c, double p, const double* dV, int ldv, int m, const double* dB, int nb,
+                           double* dRU, double* dZblk, int ldz, int zoff, double* dG_out, double* dC_out) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(dV && dB && dRU && dZblk && dG_out, RICADI_EINVAL, "NULL argument");
+  REQUIRE(m >= 1 && m <= 127 && nb >= 1 && nb <= 64 && p < 0.0, RICADI_EINVAL, "1 <= m <= 127, 1 <= nb <= 64, p < 0 required");
+  REQUIRE(ldv >= m && zoff >= 0 && ldz >= zoff + m, RICADI_EINVAL, "bad leading dimension");
+  int flag = 0;
+  API_BEGIN_ON(c)
+  TArr<double> dC(c->pool), dPart(c->pool, radi_vtb_partial_len(c->nv, m, nb));
+  if (!dC_out) dC.alloc((size_t)m * (2 * m + nb));
+  int* dflag = c->flag.p + 3;
+  radi_dense_step(c, p, dV, ldv, m, dB, nb, dRU, dZblk, ldz, zoff, dG_out, dC_out ? dC_out : dC.p, dPart.p, dflag);
+  HIPCHK(hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  API_END_STATUS(flag ? (ricadi::set_error(RADI_BREAKDOWN_MSG), RICADI_EBREAKDOWN) : RICADI_OK)
+}
+
 }  // extern "C"

@@ -12,16 +12,8 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
   hipStream_t st = c->st;
   const int nv = c->nv;
   const int mfull = mw + nb;
-  // The Newton loop installs its own low-rank term (K_k - old) B^T in the context; whatever
-  // way this function is left -- also by an exception -- no stale term may stay behind for
-  // later ricadi_lyap_adi / ricadi_shift_solve calls.
-  struct LowRankReset {
-    ricadi_ctx* c;
-    ~LowRankReset() {
-      c->q = 0;
-      ++c->lr_epoch;
-    }
-  } lowrank_reset{c};
+  // The Newton loop installs its own low-rank term (K_k - old) B^T in the context (LowRankReset: solver_radi.inl)
+  LowRankReset lowrank_reset{c};
   ensure_work(c, mfull);
   TArr<double> dWm(c->pool, (size_t)nv * mw), dK(c->pool, (size_t)nv * nb), dKall(c->pool, (size_t)nv * nb),
       dRhs(c->pool, (size_t)nv * mfull), Zown(c->pool), Znew(c->pool);

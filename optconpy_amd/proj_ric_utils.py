@@ -17,7 +17,7 @@ import scipy.sparse as sps
 from . import _lib, adi_shifts, backend
 
 __all__ = [
-    "solve_proj_lyap_stein", "proj_alg_ric_newtonadi", "compress_Zsvd",
+    "solve_proj_lyap_stein", "proj_alg_ric_newtonadi", "proj_alg_ric_radi", "compress_Zsvd",
     "get_mTzzTtb", "comp_proj_lyap_res_norm", "DEFAULT_MS", "DeviceFactor", "to_device",
 ]
 
@@ -313,6 +313,51 @@ def _newtonadi_call(ctx, d, ms, prm, bmat, wmat, z0, mtxoldb):
                                     oldB=None if mtxoldb is None else _dense(mtxoldb))
         out = dict(zfac=Z)
     return out, info
+
+
+def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=None, mtxoldb=None,
+                      transposed=False, radi_dict=None):
+    """Low-rank RADI (Benner, Bujanovic, Kuerschner, Saak 2018) for the projected algebraic Riccati equation of
+    :func:`proj_alg_ric_newtonadi` -- same operands, same orientation rules --, solved directly: one saddle-point
+    shift solve with the current closed loop per step, no Newton loop, no initial iterate.  The projected Riccati
+    residual of the iterate is ``R_j R_j^T`` with the residual factor the iteration carries, so the call stops on
+    ``||R_j^T R_j||_F / ||R_0^T R_0||_F <= radi_res_reltol``.
+
+    ``z0`` is accepted for call compatibility with :func:`proj_alg_ric_newtonadi` and IGNORED: the iteration
+    starts from zero.
+
+    ``radi_dict`` keys: ``ms`` (negative real shifts, cycled; ``'auto'`` generates them as the Newton call does for
+    its first step), ``radi_max_steps`` (200), ``radi_res_reltol`` (1e-10), ``compress_cols`` (the factor is
+    recompressed whenever it has grown by that many columns; default 512), ``verbose``, ``device_resident``.
+
+    Returns a dict: ``zfac`` (ndarray; a :class:`DeviceFactor` when given device panels or with
+    ``device_resident``), ``gain`` = ``cal E X B`` (ndarray), ``radi_steps``, ``res_hist`` (the relative residual
+    after every step), ``stop_rule`` (``_lib.RICADI_STOP_RES`` or ``_lib.RICADI_STOP_MAX_STEPS``),
+    ``gmres_nonconverged``, ``shift_solves``, ``gmres_iters`` (and ``ms`` / ``shift_info`` with ``ms='auto'``)."""
+    d = {} if radi_dict is None else radi_dict
+    calA, calE = _orient(amat, mmat, transposed)
+    ctx = backend.context_for(calA, calE, jmat)
+    ctx.set_lowrank(None, None)
+    ms = _shifts(d)
+    sinfo = None
+    if _is_auto(ms):
+        ms = _newton_auto_shifts(ctx, d, calE, bmat, wmat, None, mtxoldb)
+        sinfo = dict(ms.info)
+    kw = dict(max_steps=int(d.get("radi_max_steps", 200)), res_reltol=float(d.get("radi_res_reltol", 1e-10)),
+              compress_cols=int(d.get("compress_cols", 0)), verbose=bool(d.get("verbose", False)))
+    if d.get("device_resident", False) or any(_on_device(x) for x in (bmat, wmat, mtxoldb)):
+        Zt, Kt, info = ctx.ric_radi_dev(ms, to_device(bmat).t, to_device(wmat).t,
+                                        old_t=None if mtxoldb is None else to_device(mtxoldb).t, **kw)
+        Z, K = DeviceFactor(Zt), Kt.cpu().numpy()
+    else:
+        Z, K, info = ctx.ric_radi(ms, _dense(bmat), _dense(wmat),
+                                  oldB=None if mtxoldb is None else _dense(mtxoldb), **kw)
+    out = dict(zfac=Z, gain=K, radi_steps=info["radi_steps"], res_hist=ctx.adi_res_history(),
+               stop_rule=ctx.STOP_RULES.index(info["stop_rule"]), gmres_nonconverged=info["gmres_nonconverged"],
+               shift_solves=info["shift_solves"], gmres_iters=info["gmres_iters"])
+    if sinfo is not None:
+        out["ms"], out["shift_info"] = list(ms), sinfo
+    return out
 
 
 def _newton_auto_shifts(ctx, d, calE, bmat, wmat, z0, mtxoldb):

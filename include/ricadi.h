@@ -409,6 +409,43 @@ int ricadi_ric_radi_dev(ricadi_ctx* ctx, const double* shifts, int nshifts, cons
                         const double* dW, int mw, const double* dOldB, int max_steps, double res_reltol,
                         int compress_cols, int project_w, int verbose, int* c_out, double* dK_out,
                         double* stats_out);
+/* Where ricadi_ric_radi(_dev) takes its shifts from; a context setting like ricadi_set_recycle, default CYCLE.
+ *   RICADI_RADI_SHIFTS_CYCLE        the caller's list, cycled.
+ *   RICADI_RADI_SHIFTS_HAMILTONIAN  shifts[0] for the first step; every later shift is generated from the state of the
+ *     iteration ("residual Hamiltonian shifts", section 4.5 of the RADI paper): with Q an orthonormal
+ *     basis of the new block of Z (k <= mw columns, all in ker J: the columns of the block's QR whose diagonal entry
+ *     of R is at least 1e-12 of the largest one),
+ *       H_A = Q^T cal A Q, H_E = Q^T cal E Q, H_R = Q^T R, H_U = Q^T U, H_B = Q^T B,
+ *       A_c = H_A - H_U H_B^T,  At = H_E^-1 A_c,  Rt = H_E^-1 H_R,
+ *       Ham = [[At^T, -H_B H_B^T], [-Rt Rt^T, -At]]   (2k x 2k),
+ *     the candidates are the eigenvalues of Ham with negative real part, one of each conjugate pair; the next shift is
+ *     p = -|lambda| of the candidate whose eigenvector x = [r; q] has the largest ||q|| / ||x||.  The list is the
+ *     fallback (a counter of its own, cycling, starting at shifts[1]): no candidate, a shift that is not finite and
+ *     negative, or a breakdown of the selection (ricadi_host_radi_shift).
+ *     Requires mw <= 32 (else ricadi_ric_radi(_dev) return RICADI_EINVAL before anything is launched).  Only shifts[0]
+ *     is set up in advance; a generated shift's per-shift data are rebuilt in ONE entry the context owns and never
+ *     enter the per-shift cache: after the call the cache holds what it held before plus the entries of the list that
+ *     were used.
+ * RICADI_EINVAL for another mode.                                                                                   */
+#define RICADI_RADI_SHIFTS_CYCLE 0
+#define RICADI_RADI_SHIFTS_HAMILTONIAN 1
+int ricadi_set_radi_shifts(ricadi_ctx* ctx, int mode);
+/* The shift of every step of the most recent ricadi_ric_radi(_dev) call of the context, in either mode: *n_out = steps
+ * started (one more than the steps completed when the call ended by a breakdown); at most `cap` entries are copied to
+ * `out` (may be NULL with cap = 0).  RICADI_ESTATE before any RADI call.                                             */
+int ricadi_radi_shift_history(ricadi_ctx* ctx, double* out, int cap, int* n_out);
+/* How many of those shifts were fallbacks to the caller's list (HAMILTONIAN mode; 0 in CYCLE mode).  RICADI_ESTATE
+ * before any RADI call.  (Every slot of stats_out is taken, so these values have calls of their own.)               */
+int ricadi_radi_shift_fallbacks(ricadi_ctx* ctx, int* n_out);
+/* The reduced matrices of the shift selection on device operands, for tests:
+ *   dH_out (k x (2k + m + 2nb), row-major) = Q^T [cal A Q | cal E Q | R | U | B]
+ * with dQ NV x k (leading dimension k, any columns), dRU = [R | U] NV x (m + nb), dB NV x nb.  One pass over the rows of
+ * cal A and cal E; every sum runs in a fixed order: the same call gives bitwise the same dH_out.
+ * 1 <= k <= 32, 1 <= m <= 32, 1 <= nb <= 64 (the driver calls it with k = m).                                         */
+int ricadi_radi_reduce_dev(ricadi_ctx* ctx, const double* dQ, int k, const double* dRU, int m, const double* dB,
+                           int nb, double* dH_out);
+/* Entries of the per-shift cache, summed over the levels of the preconditioner hierarchy, for tests.               */
+int ricadi_probe_cache_entries(ricadi_ctx* ctx, int* n_out);
 /* The dense part of ONE RADI step on device operands, for tests: dV (its first NV rows, leading dimension ldv >= m),
  * dB NV x nb, dRU = [R | U] NV x (m + nb) updated in place, the new block of Z written to columns [zoff, zoff + m)
  * of dZblk (leading dimension ldz >= zoff + m); dG_out m x nb; dC_out m x (2m + nb) (may be NULL):
@@ -797,6 +834,19 @@ int ricadi_host_aggregate(int n, const int32_t* rowptr, const int32_t* col,
  * amplify the solves' errors by more than ~1e5 (smallest relative pivot of C below 1e-6: shifts too
  * many / too close); the drivers then halve the sweep width.                                    */
 int ricadi_host_cauchy(const double* shifts, int g, double* rinv_out, double* cinv1_out);
+/* The next RADI shift under RICADI_RADI_SHIFTS_HAMILTONIAN from the reduced matrices
+ * H = Q^T [cal A Q | cal E Q | R | U | B] (k x (2k + m + 2nb), row-major; ricadi_radi_reduce_dev), by the rule stated
+ * at ricadi_set_radi_shifts.  Host only, no GPU needed.  The library links no LAPACK: the eigenvalues of the real
+ * 2k x 2k matrix Ham come from a balancing by powers of two, a Householder reduction to Hessenberg form and the
+ * double-shift QR iteration; the eigenvector of a candidate is the null vector of Ham - lambda I by complex Gaussian
+ * elimination with complete pivoting.  *p_out: the shift (negative), or 0 when Ham has no eigenvalue with negative real
+ * part.  *margin_out (may be NULL): the largest criterion value over the second largest, +inf with one candidate.
+ * RICADI_EINVAL unless 1 <= k <= 32, 1 <= m <= 32, 1 <= nb <= 64; RICADI_EBREAKDOWN when H_E is singular (LU pivot
+ * below 1e-14 of its largest entry), H holds a value that is not finite, or the QR iteration does not converge.       */
+int ricadi_host_radi_shift(int k, int m, int nb, const double* H, double* p_out, double* margin_out);
+/* The same, and all 2k eigenvalues of Ham (real and imaginary parts, in no particular order), for tests.             */
+int ricadi_host_radi_shift_eigs(int k, int m, int nb, const double* H, double* p_out, double* margin_out,
+                                double* wr_out, double* wi_out);
 
 #ifdef __cplusplus
 }

@@ -18,10 +18,11 @@ LIB_PATH = os.environ.get("RICADI_LIB", os.path.join(_HERE, "libricadi_hip.so"))
 RICADI_OK = 0
 RICADI_ENOCONV = -3
 RICADI_STOP_MAX_STEPS, RICADI_STOP_NEWZ, RICADI_STOP_RES = 0, 1, 2      # ricadi_adi_stop_rule (include/ricadi.h)
+RICADI_RADI_SHIFTS_CYCLE, RICADI_RADI_SHIFTS_HAMILTONIAN = 0, 1          # ricadi_set_radi_shifts
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 407
+ABI_VERSION = 408
 
 
 class RicadiOpts(C.Structure):
@@ -93,6 +94,11 @@ SIGNATURES = {
                                       C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _vp, _dp]),
     "ricadi_radi_update_dev": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int,
                                          C.c_int, _vp, _vp]),
+    "ricadi_set_radi_shifts": (C.c_int, [_vp, C.c_int]),
+    "ricadi_radi_shift_history": (C.c_int, [_vp, _dp, C.c_int, C.POINTER(C.c_int)]),
+    "ricadi_radi_shift_fallbacks": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "ricadi_radi_reduce_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
+    "ricadi_probe_cache_entries": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "ricadi_spmm_dev": (C.c_int, [_vp, C.c_double, C.c_double, _vp, C.c_int, _vp]),
     "ricadi_shift_solve_dev": (C.c_int, [_vp, C.c_double, C.c_double, _vp, C.c_int, _vp,
                                          C.POINTER(C.c_int), _dp]),
@@ -150,6 +156,10 @@ SIGNATURES = {
     "ricadi_host_vanka_patches": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _ip]),
     "ricadi_precond_vanka": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip]),
     "ricadi_host_cauchy": (C.c_int, [_dp, C.c_int, _dp, _dp]),
+    "ricadi_host_radi_shift": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double)]),
+    "ricadi_host_radi_shift_eigs": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double), _dp, _dp]),
 }
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _vp, C.c_int64)
@@ -699,6 +709,42 @@ class Context:
         _warn_nonconverged(info)
         return Zt, Kt, info
 
+    RADI_SHIFT_MODES = {"cycle": RICADI_RADI_SHIFTS_CYCLE, "hamiltonian": RICADI_RADI_SHIFTS_HAMILTONIAN}
+
+    def set_radi_shifts(self, mode):
+        """``ricadi_set_radi_shifts``: ``'cycle'`` (default; the list is cycled) or ``'hamiltonian'`` (the list's first
+        entry starts, every later shift is generated from the iteration, the list is the fallback).  A context
+        setting, like :meth:`set_recycle`.  Returns the mode that was in force."""
+        new = self.RADI_SHIFT_MODES[mode] if isinstance(mode, str) else int(mode)
+        old = getattr(self, "_radi_shift_mode", RICADI_RADI_SHIFTS_CYCLE)
+        _chk(self._lib.ricadi_set_radi_shifts(self._h, new))
+        self._radi_shift_mode = new
+        return old
+
+    def radi_shift_history(self):
+        """``ricadi_radi_shift_history``: the shift of every step of the last RADI call (either mode)."""
+        n = C.c_int(0)
+        _chk(self._lib.ricadi_radi_shift_history(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1))
+        _chk(self._lib.ricadi_radi_shift_history(self._h, _d(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
+
+    def radi_shift_fallbacks(self):
+        """``ricadi_radi_shift_fallbacks``: how many shifts of the last RADI call came from the fallback list."""
+        n = C.c_int(0)
+        _chk(self._lib.ricadi_radi_shift_fallbacks(self._h, C.byref(n)))
+        return int(n.value)
+
+    def cache_entries(self):
+        """``ricadi_probe_cache_entries``: entries of the per-shift cache over all levels (tests)."""
+        n = C.c_int(0)
+        _chk(self._lib.ricadi_probe_cache_entries(self._h, C.byref(n)))
+        return int(n.value)
+
+    def radi_reduce_dev(self, q_ptr, k, ru_ptr, m, b_ptr, nb, h_ptr):
+        """``ricadi_radi_reduce_dev``: H = Q^T [cal A Q | cal E Q | R | U | B] on device pointers (tests)."""
+        _chk(self._lib.ricadi_radi_reduce_dev(self._h, q_ptr, int(k), ru_ptr, int(m), b_ptr, int(nb), h_ptr))
+
     def radi_update_dev(self, p, v_ptr, ldv, m, b_ptr, nb, ru_ptr, z_ptr, ldz, zoff, g_ptr, c_ptr=None):
         """``ricadi_radi_update_dev``: the dense part of one RADI step on device pointers (tests)."""
         _chk(self._lib.ricadi_radi_update_dev(self._h, float(p), v_ptr, int(ldv), int(m), b_ptr, int(nb), ru_ptr,
@@ -1116,6 +1162,23 @@ def host_cauchy(shifts):
     c1 = np.empty(g)
     _chk(load().ricadi_host_cauchy(_d(sh), g, _d(rinv), _d(c1)))
     return rinv, c1
+
+
+def host_radi_shift(k, m, nb, H, eigs=False):
+    """``ricadi_host_radi_shift``: the next RADI shift from H = Q^T [cal A Q | cal E Q | R | U | B]
+    (k x (2k + m + 2nb)); host only.  Returns ``(p, margin)`` -- p = 0.0 without a candidate --, with ``eigs`` also
+    the 2k eigenvalues of the projected Hamiltonian.  ValueError for bad sizes, RuntimeError on a breakdown."""
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    k, m, nb = int(k), int(m), int(nb)
+    if min(k, m, nb) >= 1 and H.size != k * (2 * k + m + 2 * nb):       # (sizes out of range: the library says so)
+        raise ValueError("H must be k x (2k + m + 2nb)")
+    p, mg = C.c_double(0.0), C.c_double(0.0)
+    if not eigs:
+        _chk(load().ricadi_host_radi_shift(int(k), int(m), int(nb), _d(H), C.byref(p), C.byref(mg)))
+        return p.value, mg.value
+    wr, wi = np.zeros(2 * max(int(k), 1)), np.zeros(2 * max(int(k), 1))
+    _chk(load().ricadi_host_radi_shift_eigs(int(k), int(m), int(nb), _d(H), C.byref(p), C.byref(mg), _d(wr), _d(wi)))
+    return p.value, mg.value, wr + 1j * wi
 
 
 def host_plan_levels(calA, calE, J, **opts):

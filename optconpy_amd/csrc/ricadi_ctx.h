@@ -365,8 +365,18 @@ struct ricadi_ctx {
   double* h_res = nullptr;    // pinned host copy of res_gram (h_res_cap doubles)
   size_t h_res_cap = 0;
   long res_launches = 0;      // kernel launches issued for the residual rule (ricadi_adi_res_launches)
+  // RADI (solver_radi.inl): where the shifts come from (ricadi_set_radi_shifts), the shift of every step of the last
+  // call, how many of them fell back to the caller's list, and whether a call has run at all
+  int radi_shift_mode = 0;
+  std::vector<double> radi_shift_hist;
+  int radi_fallbacks = 0;
+  bool radi_ran = false;
   // per-shift data
   std::map<std::pair<double, double>, std::unique_ptr<ShiftData>> cache;
+  // The ONE entry the RADI driver rebuilds for every generated shift (a level owns its own): it is lent to `cache`
+  // under the shift's key for the duration of a step and taken back, so that generated shifts leave nothing in the
+  // map and the buffers are reused from step to step and from call to call (OwnedShift, solver_radi.inl)
+  std::unique_ptr<ShiftData> radi_sd;
   // workspaces
   int wcols = 0, wrestart = 0;   // total columns (width x groups) and restart length the workspace holds
   DArr<double> basis, vcur, wv, zv, r2, tp, rc, ec, xs, bvec, pw1, pw2;

@@ -11,9 +11,11 @@
 // SuperLU.
 #include <array>
 #include <cmath>
+#include <complex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <numeric>
 #include <stdexcept>
 
@@ -1230,9 +1232,392 @@ VankaPatches vanka_patches(int nv, const HostCsr& J) {
   return vp;
 }
 
+// ---- RADI: the next shift from the projected residual Hamiltonian ---------------------------
+// The library links no LAPACK and rocSOLVER has no non-symmetric eigensolver: a small dense solver for real matrices of
+// order <= 64 -- balancing (scaling by powers of two), Householder reduction to Hessenberg form, Francis' double-shift
+// QR iteration for the eigenvalues (the classical hqr scheme), and per wanted eigenvalue the null vector of
+// Ham - lambda I by complex Gaussian elimination with complete pivoting.
+
+// scaling part of the Parlett-Reinsch balancing: a similarity by a diagonal of powers of two (exact)
+static void balance_scale(int n, std::vector<double>& a) {
+  bool done = false;
+  while (!done) {
+    done = true;
+    for (int i = 0; i < n; ++i) {
+      double r = 0.0, c = 0.0;
+      for (int j = 0; j < n; ++j)
+        if (j != i) {
+          c += std::fabs(a[(size_t)j * n + i]);
+          r += std::fabs(a[(size_t)i * n + j]);
+        }
+      if (c == 0.0 || r == 0.0 || !std::isfinite(c) || !std::isfinite(r)) continue;
+      double g = r / 2.0, f = 1.0;
+      const double s = c + r;
+      while (c < g) {
+        f *= 2.0;
+        c *= 4.0;
+      }
+      g = r * 2.0;
+      while (c > g) {
+        f /= 2.0;
+        c /= 4.0;
+      }
+      if ((c + r) / f < 0.95 * s) {
+        done = false;
+        g = 1.0 / f;
+        for (int j = 0; j < n; ++j) a[(size_t)i * n + j] *= g;
+        for (int j = 0; j < n; ++j) a[(size_t)j * n + i] *= f;
+      }
+    }
+  }
+}
+
+// Householder reduction to upper Hessenberg form in place (the transformations are not kept)
+static void hessenberg(int n, std::vector<double>& a) {
+  std::vector<double> v(n);
+  for (int j = 0; j + 2 < n; ++j) {
+    double nrm2 = 0.0;
+    for (int i = j + 1; i < n; ++i) nrm2 += a[(size_t)i * n + j] * a[(size_t)i * n + j];
+    if (nrm2 == 0.0) continue;
+    const double x0 = a[(size_t)(j + 1) * n + j];
+    const double alpha = -std::copysign(std::sqrt(nrm2), x0);
+    for (int i = j + 1; i < n; ++i) v[i] = a[(size_t)i * n + j];
+    v[j + 1] -= alpha;
+    double vv = 0.0;
+    for (int i = j + 1; i < n; ++i) vv += v[i] * v[i];
+    if (vv == 0.0) continue;
+    const double beta = 2.0 / vv;
+    for (int c = j; c < n; ++c) {          // from the left: rows j + 1 ..
+      double s = 0.0;
+      for (int i = j + 1; i < n; ++i) s += v[i] * a[(size_t)i * n + c];
+      s *= beta;
+      for (int i = j + 1; i < n; ++i) a[(size_t)i * n + c] -= s * v[i];
+    }
+    for (int r = 0; r < n; ++r) {          // from the right: columns j + 1 ..
+      double s = 0.0;
+      for (int i = j + 1; i < n; ++i) s += a[(size_t)r * n + i] * v[i];
+      s *= beta;
+      for (int i = j + 1; i < n; ++i) a[(size_t)r * n + i] -= s * v[i];
+    }
+    a[(size_t)(j + 1) * n + j] = alpha;
+    for (int i = j + 2; i < n; ++i) a[(size_t)i * n + j] = 0.0;
+  }
+}
+
+// Eigenvalues of an upper Hessenberg matrix (destroyed) by the double-shift QR iteration; conjugate pairs come out as
+// exact conjugates, real eigenvalues with wi = 0.  false: 60 iterations on one eigenvalue did not converge.
+static bool hqr_eigenvalues(int n, std::vector<double>& h, double* wr, double* wi) {
+  const double eps = 2.220446049250313e-16;
+  auto A = [&](int i, int j) -> double& { return h[(size_t)i * n + j]; };
+  double anorm = 0.0;
+  for (int i = 0; i < n; ++i)
+    for (int j = std::max(i - 1, 0); j < n; ++j) anorm += std::fabs(A(i, j));
+  if (!std::isfinite(anorm)) return false;
+  int nn = n - 1;
+  double t = 0.0, p = 0.0, q = 0.0, r = 0.0, s, x, y, z, w;
+  while (nn >= 0) {
+    int its = 0, l;
+    do {
+      for (l = nn; l >= 1; --l) {
+        s = std::fabs(A(l - 1, l - 1)) + std::fabs(A(l, l));
+        if (s == 0.0) s = anorm;
+        if (std::fabs(A(l, l - 1)) <= eps * s) {
+          A(l, l - 1) = 0.0;
+          break;
+        }
+      }
+      x = A(nn, nn);
+      if (l == nn) {                       // one root
+        wr[nn] = x + t;
+        wi[nn--] = 0.0;
+      } else {
+        y = A(nn - 1, nn - 1);
+        w = A(nn, nn - 1) * A(nn - 1, nn);
+        if (l == nn - 1) {                 // two roots
+          p = 0.5 * (y - x);
+          q = p * p + w;
+          z = std::sqrt(std::fabs(q));
+          x += t;
+          if (q >= 0.0) {
+            z = p + std::copysign(z, p);
+            wr[nn - 1] = wr[nn] = x + z;
+            if (z != 0.0) wr[nn] = x - w / z;
+            wi[nn - 1] = wi[nn] = 0.0;
+          } else {
+            wr[nn - 1] = wr[nn] = x + p;
+            wi[nn - 1] = z;
+            wi[nn] = -z;
+          }
+          nn -= 2;
+        } else {
+          if (its == 60) return false;
+          if (its == 10 || its == 20) {    // exceptional shift
+            t += x;
+            for (int i = 0; i <= nn; ++i) A(i, i) -= x;
+            s = std::fabs(A(nn, nn - 1)) + std::fabs(A(nn - 1, nn - 2));
+            y = x = 0.75 * s;
+            w = -0.4375 * s * s;
+          }
+          ++its;
+          int m;
+          for (m = nn - 2; m >= l; --m) {  // two consecutive small subdiagonal entries
+            z = A(m, m);
+            r = x - z;
+            s = y - z;
+            p = (r * s - w) / A(m + 1, m) + A(m, m + 1);
+            q = A(m + 1, m + 1) - z - r - s;
+            r = A(m + 2, m + 1);
+            s = std::fabs(p) + std::fabs(q) + std::fabs(r);
+            if (s != 0.0) {
+              p /= s;
+              q /= s;
+              r /= s;
+            }
+            if (m == l) break;
+            const double u = std::fabs(A(m, m - 1)) * (std::fabs(q) + std::fabs(r));
+            const double v = std::fabs(p) * (std::fabs(A(m - 1, m - 1)) + std::fabs(z) + std::fabs(A(m + 1, m + 1)));
+            if (u <= eps * v) break;
+          }
+          for (int i = m + 2; i <= nn; ++i) {
+            A(i, i - 2) = 0.0;
+            if (i != m + 2) A(i, i - 3) = 0.0;
+          }
+          for (int k = m; k <= nn - 1; ++k) {   // the double QR step on rows l .. nn, columns m .. nn
+            if (k != m) {
+              p = A(k, k - 1);
+              q = A(k + 1, k - 1);
+              r = k != nn - 1 ? A(k + 2, k - 1) : 0.0;
+              if ((x = std::fabs(p) + std::fabs(q) + std::fabs(r)) != 0.0) {
+                p /= x;
+                q /= x;
+                r /= x;
+              }
+            }
+            s = std::copysign(std::sqrt(p * p + q * q + r * r), p);
+            if (s == 0.0) continue;
+            if (k == m) {
+              if (l != m) A(k, k - 1) = -A(k, k - 1);
+            } else {
+              A(k, k - 1) = -s * x;
+            }
+            p += s;
+            x = p / s;
+            y = q / s;
+            z = r / s;
+            q /= p;
+            r /= p;
+            for (int j = k; j <= nn; ++j) {
+              p = A(k, j) + q * A(k + 1, j);
+              if (k != nn - 1) {
+                p += r * A(k + 2, j);
+                A(k + 2, j) -= p * z;
+              }
+              A(k + 1, j) -= p * y;
+              A(k, j) -= p * x;
+            }
+            const int mmin = nn < k + 3 ? nn : k + 3;
+            for (int i = l; i <= mmin; ++i) {
+              p = x * A(i, k) + y * A(i, k + 1);
+              if (k != nn - 1) {
+                p += z * A(i, k + 2);
+                A(i, k + 2) -= p * r;
+              }
+              A(i, k + 1) -= p * q;
+              A(i, k) -= p;
+            }
+          }
+        }
+      }
+    } while (l < nn - 1);
+  }
+  return true;
+}
+
+// Null vector of M = Ham - lambda I (n x n, complex): Gaussian elimination with complete pivoting; the last pivot is
+// the one that vanishes, its unknown is set to 1 and the rest follows by back substitution.
+static void null_vector(int n, const std::vector<double>& ham, std::complex<double> lambda,
+                        std::vector<std::complex<double>>& x) {
+  typedef std::complex<double> cd;
+  std::vector<cd> M((size_t)n * n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) M[(size_t)i * n + j] = cd(ham[(size_t)i * n + j], 0.0) - (i == j ? lambda : cd(0.0, 0.0));
+  std::vector<int> cp(n);
+  std::iota(cp.begin(), cp.end(), 0);
+  int rank = n - 1;
+  for (int k = 0; k < n - 1; ++k) {
+    int pi = k, pj = k;
+    double best = -1.0;
+    for (int i = k; i < n; ++i)
+      for (int j = k; j < n; ++j) {
+        const double v = std::norm(M[(size_t)i * n + j]);
+        if (v > best) {
+          best = v;
+          pi = i;
+          pj = j;
+        }
+      }
+    if (!(best > 0.0)) {                   // the rest is exactly zero: more than one free unknown, take the first
+      rank = k;
+      break;
+    }
+    if (pi != k)
+      for (int j = 0; j < n; ++j) std::swap(M[(size_t)k * n + j], M[(size_t)pi * n + j]);
+    if (pj != k) {
+      for (int i = 0; i < n; ++i) std::swap(M[(size_t)i * n + k], M[(size_t)i * n + pj]);
+      std::swap(cp[k], cp[pj]);
+    }
+    const cd piv = M[(size_t)k * n + k];
+    for (int i = k + 1; i < n; ++i) {
+      const cd f = M[(size_t)i * n + k] / piv;
+      if (f == cd(0.0, 0.0)) continue;
+      for (int j = k + 1; j < n; ++j) M[(size_t)i * n + j] -= f * M[(size_t)k * n + j];
+    }
+  }
+  std::vector<cd> y(n, cd(0.0, 0.0));
+  y[rank] = cd(1.0, 0.0);
+  for (int i = rank - 1; i >= 0; --i) {
+    cd s(0.0, 0.0);
+    for (int j = i + 1; j <= rank; ++j) s += M[(size_t)i * n + j] * y[j];
+    y[i] = -s / M[(size_t)i * n + i];
+  }
+  x.assign(n, cd(0.0, 0.0));
+  for (int i = 0; i < n; ++i) x[cp[i]] = y[i];
+}
+
+// Ham (2k x 2k, row-major) from H = Q^T [cal A Q | cal E Q | R | U | B] (k x (2k + m + 2nb)):
+//   A_c = H_A - H_U H_B^T,  At = H_E^-1 A_c,  Rt = H_E^-1 H_R,  Ham = [[At^T, -H_B H_B^T], [-Rt Rt^T, -At]].
+// false: H_E is singular to working precision (LU with partial pivoting) or an entry is not finite.
+static bool radi_hamiltonian(int k, int m, int nb, const double* H, std::vector<double>& ham) {
+  const int ldh = 2 * k + m + 2 * nb, w = k + m;
+  const double *HA = H, *HE = H + k, *HR = H + 2 * k, *HU = H + 2 * k + m, *HB = H + 2 * k + m + nb;
+  for (int i = 0; i < k * ldh; ++i)
+    if (!std::isfinite(H[i])) return false;
+  std::vector<double> E((size_t)k * k), X((size_t)k * w);       // X = [A_c | H_R], then H_E^-1 of it
+  double emax = 0.0;
+  for (int i = 0; i < k; ++i) {
+    for (int j = 0; j < k; ++j) {
+      E[(size_t)i * k + j] = HE[(size_t)i * ldh + j];
+      emax = std::max(emax, std::fabs(E[(size_t)i * k + j]));
+      double s = HA[(size_t)i * ldh + j];
+      for (int c = 0; c < nb; ++c) s -= HU[(size_t)i * ldh + c] * HB[(size_t)j * ldh + c];
+      X[(size_t)i * w + j] = s;
+    }
+    for (int j = 0; j < m; ++j) X[(size_t)i * w + k + j] = HR[(size_t)i * ldh + j];
+  }
+  for (int c = 0; c < k; ++c) {
+    int pr = c;
+    for (int i = c + 1; i < k; ++i)
+      if (std::fabs(E[(size_t)i * k + c]) > std::fabs(E[(size_t)pr * k + c])) pr = i;
+    if (!(std::fabs(E[(size_t)pr * k + c]) > 1e-14 * emax)) return false;
+    if (pr != c) {
+      for (int j = 0; j < k; ++j) std::swap(E[(size_t)c * k + j], E[(size_t)pr * k + j]);
+      for (int j = 0; j < w; ++j) std::swap(X[(size_t)c * w + j], X[(size_t)pr * w + j]);
+    }
+    const double piv = E[(size_t)c * k + c];
+    for (int i = c + 1; i < k; ++i) {
+      const double f = E[(size_t)i * k + c] / piv;
+      if (f == 0.0) continue;
+      for (int j = c + 1; j < k; ++j) E[(size_t)i * k + j] -= f * E[(size_t)c * k + j];
+      for (int j = 0; j < w; ++j) X[(size_t)i * w + j] -= f * X[(size_t)c * w + j];
+    }
+  }
+  for (int i = k - 1; i >= 0; --i)
+    for (int j = 0; j < w; ++j) {
+      double s = X[(size_t)i * w + j];
+      for (int c = i + 1; c < k; ++c) s -= E[(size_t)i * k + c] * X[(size_t)c * w + j];
+      X[(size_t)i * w + j] = s / E[(size_t)i * k + i];
+    }
+  const int n = 2 * k;
+  ham.assign((size_t)n * n, 0.0);
+  for (int i = 0; i < k; ++i)
+    for (int j = 0; j < k; ++j) {
+      ham[(size_t)i * n + j] = X[(size_t)j * w + i];
+      ham[(size_t)(k + i) * n + k + j] = -X[(size_t)i * w + j];
+      double sb = 0.0, sr = 0.0;
+      for (int c = 0; c < nb; ++c) sb += HB[(size_t)i * ldh + c] * HB[(size_t)j * ldh + c];
+      for (int c = 0; c < m; ++c) sr += X[(size_t)i * w + k + c] * X[(size_t)j * w + k + c];
+      ham[(size_t)i * n + k + j] = -sb;
+      ham[(size_t)(k + i) * n + j] = -sr;
+    }
+  for (double v : ham)
+    if (!std::isfinite(v)) return false;
+  return true;
+}
+
+// The rule: candidates are the eigenvalues of Ham in the open left half plane, one of each conjugate pair (Im >= 0);
+// criterion ||q|| / ||x|| of the eigenvector x = [r; q]; p = -|lambda| of the largest, margin = largest / second
+// largest (+inf with one candidate), p = 0 without a candidate.  wr / wi (2k each, may be NULL): all eigenvalues.
+int radi_shift_select(int k, int m, int nb, const double* H, double* p_out, double* margin_out, double* wr_out,
+                      double* wi_out) {
+  std::vector<double> ham;
+  if (!radi_hamiltonian(k, m, nb, H, ham)) {
+    set_error("ricadi_host_radi_shift: H_E is singular or H holds a value that is not finite");
+    return RICADI_EBREAKDOWN;
+  }
+  const int n = 2 * k;
+  std::vector<double> h = ham, wr(n), wi(n);
+  balance_scale(n, h);
+  hessenberg(n, h);
+  if (!hqr_eigenvalues(n, h, wr.data(), wi.data())) {
+    set_error("ricadi_host_radi_shift: the QR iteration did not converge");
+    return RICADI_EBREAKDOWN;
+  }
+  if (wr_out) std::copy(wr.begin(), wr.end(), wr_out);
+  if (wi_out) std::copy(wi.begin(), wi.end(), wi_out);
+  double best = -1.0, second = -1.0, pbest = 0.0;
+  int ncand = 0;
+  std::vector<std::complex<double>> x;
+  for (int i = 0; i < n; ++i) {
+    if (!(wr[i] < 0.0) || wi[i] < 0.0) continue;
+    ++ncand;
+    null_vector(n, ham, std::complex<double>(wr[i], wi[i]), x);
+    double nq = 0.0, nx = 0.0;
+    for (int j = 0; j < n; ++j) {
+      const double v = std::norm(x[j]);
+      nx += v;
+      if (j >= k) nq += v;
+    }
+    const double crit = nx > 0.0 ? std::sqrt(nq / nx) : 0.0;
+    if (crit > best) {
+      second = best;
+      best = crit;
+      pbest = -std::hypot(wr[i], wi[i]);
+    } else if (crit > second) {
+      second = crit;
+    }
+  }
+  *p_out = ncand ? pbest : 0.0;
+  if (margin_out)
+    *margin_out = ncand >= 2 && second > 0.0 ? best / second : std::numeric_limits<double>::infinity();
+  return RICADI_OK;
+}
+
 }  // namespace ricadi
 
 extern "C" {
+
+static int radi_shift_entry(int k, int m, int nb, const double* H, double* p_out, double* margin_out, double* wr,
+                            double* wi) {
+  if (k < 1 || k > 32 || m < 1 || m > 32 || nb < 1 || nb > 64 || !H || !p_out) {
+    ricadi::set_error("ricadi_host_radi_shift: bad argument (1 <= k, m <= 32, 1 <= nb <= 64)");
+    return RICADI_EINVAL;
+  }
+  try {
+    return ricadi::radi_shift_select(k, m, nb, H, p_out, margin_out, wr, wi);
+  } catch (const std::exception&) {
+    ricadi::set_error("ricadi_host_radi_shift: exception");
+    return RICADI_EHIP;
+  }
+}
+
+int ricadi_host_radi_shift(int k, int m, int nb, const double* H, double* p_out, double* margin_out) {
+  return radi_shift_entry(k, m, nb, H, p_out, margin_out, nullptr, nullptr);
+}
+
+int ricadi_host_radi_shift_eigs(int k, int m, int nb, const double* H, double* p_out, double* margin_out,
+                                double* wr_out, double* wi_out) {
+  return radi_shift_entry(k, m, nb, H, p_out, margin_out, wr_out, wi_out);
+}
 
 int ricadi_host_vanka_patches(int nv, int np, const int32_t* j_rp, const int32_t* j_ci, const double* j_v,
                               int32_t* sizes_out, int32_t* colour_ptr, int32_t* patch_idx) {

@@ -572,6 +572,17 @@ void launch_radi_vtb(hipStream_t st, int n, int m, int nb, const double* V, int 
 void launch_radi_factor(hipStream_t st, int m, int nb, double p, const double* G, double* C, int* flag);
 void launch_radi_update(hipStream_t st, int nv, int m, int nb, const int* rp, const int* ci, const double* ev,
                         const double* V, int ldv, const double* C, double* RU, double* Z, int zld, int zc);
+// reduce: H (k x (2k + m + 2nb), row-major) = Q^T [cal A Q | cal E Q | R | U | B] for the shift selection: Q nv x k
+// (ld k), RU = [R | U] nv x (m + nb), B nv x nb; rp / ci / vA / vE the saddle pattern with its two value sources (rows
+// and columns below nv); 1 <= k, m <= 32, 1 <= nb <= 64; sums in a fixed order (`partial`: radi_reduce_partial_len).
+size_t radi_reduce_partial_len(int nv, int k, int m, int nb);
+void launch_radi_reduce(hipStream_t st, int nv, int k, int m, int nb, const int* rp, const int* ci, const double* vA,
+                        const double* vE, const double* Q, const double* RU, const double* B, double* partial,
+                        double* H);
+// The shift selection on the host (ricadi_host.cpp; ricadi_host_radi_shift): RICADI_OK / RICADI_EBREAKDOWN.  wr_out /
+// wi_out (2k each, may be NULL): all eigenvalues of the Hamiltonian.
+int radi_shift_select(int k, int m, int nb, const double* H, double* p_out, double* margin_out, double* wr_out,
+                      double* wi_out);
 
 void set_error(const std::string& msg);
 

@@ -10,6 +10,10 @@
 //                                              C = [sqrt(-2p) L^-T | (-2p) Y^-1 | (-2p) Y^-1 G]  (m x (2m + nb));
 //   radi_update_kernel                         one pass over the rows of cal E: (cal E V)_row and V_row times C, added
 //                                              into the panel [R | U] and written as the new block of Z.
+// With shifts generated from the iteration (ricadi_set_radi_shifts) a step also needs
+//   radi_reduce_kernel                         H = Q^T [cal A Q | cal E Q | R | U | B] for an orthonormal basis Q of the
+//                                              new block of Z: one pass over the rows of cal A and cal E, one partial
+//                                              per row slice, the slices summed by radi_vtb_reduce_kernel.
 // FP64 throughout, no atomics, every sum in a fixed order: the same inputs give bitwise the same outputs.
 #include "ricadi_internal.h"
 
@@ -202,6 +206,123 @@ void launch_radi_update(hipStream_t st, int nv, int m, int nb, const int* rp, co
   const size_t lds = sizeof(double) * (size_t)(2 * RADI_RB + RADI_CT) * m;
   hipLaunchKernelGGL(radi_update_kernel, dim3((nv + RADI_RB - 1) / RADI_RB), dim3(256), lds, st, nv, m, nb, rp, ci, ev,
                      V, ldv, C, RU, Z, zld, zc);
+}
+
+// ---- the reduced matrices of the shift selection ------------------------------------------------------------------
+// H = Q^T [cal A Q | cal E Q | R | U | B]  (k x W, W = 2k + m + 2nb, row-major; k = m <= 32, nb <= 64) in one pass over
+// the velocity rows of the saddle pattern (rp / ci, columns below nv only) with its two value sources vA / vE.
+// A workgroup owns a slice of rows (a multiple of RADI_HB) and walks it in chunks of RADI_HB rows.  Per chunk it
+//   1. gathers the Q rows the chunk's sparse rows name and forms (cal A Q)_row and (cal E Q)_row, copies the rows of
+//      [R | U] and B beside them -- the row Y_r of W entries -- and its own rows of Q, all into LDS;
+//   2. adds Q_r^T Y_r into registers: thread = (sub, column j) holds H[0 .. k)[j] of the rows r = sub (mod nsub) of
+//      every chunk, nsub = min(256 / W, RADI_HB), in row order.
+// At the end the nsub partial sums of a column are added in sub order through LDS, and radi_vtb_reduce_kernel adds the
+// slices in slice order: no atomics, every sum in a fixed order.
+// LDS (doubles): RADI_HB (ldy + ldq) + (nsub > 1 ? k W : 0), ldy = W | 1, ldq = k | 1 (odd: the gather phase writes
+// and the sum phase reads along rows, a later column walk would touch every bank); nsub > 1 means W <= 128, so at most
+// 16 * (129 + 33) + 32 * 128 doubles = 53 KB, and 16 * (225 + 33) = 33 KB for the widest W = 224.
+constexpr int RADI_HB = 16, RADI_HK = 32;
+__global__ __launch_bounds__(256) void radi_reduce_kernel(int nv, int k, int m, int nb, int rows_per_slice, int nsub,
+                                                          const int* __restrict__ rp, const int* __restrict__ ci,
+                                                          const double* __restrict__ vA,
+                                                          const double* __restrict__ vE,
+                                                          const double* __restrict__ Q,
+                                                          const double* __restrict__ RU,
+                                                          const double* __restrict__ B, double* __restrict__ part) {
+  extern __shared__ double sh[];
+  const int W = 2 * k + m + 2 * nb, ldy = W | 1, ldq = k | 1, ldp = m + nb;
+  double* ys = sh;                          // RADI_HB x ldy
+  double* qs = ys + RADI_HB * ldy;          // RADI_HB x ldq
+  double* red = qs + RADI_HB * ldq;         // k x W (nsub > 1 only)
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.x * rows_per_slice, r1 = min(nv, r0 + rows_per_slice);
+  const bool summing = tid < nsub * W;
+  const int sub = summing ? tid / W : 0, j = summing ? tid - sub * W : 0;
+  double acc[RADI_HK];
+#pragma unroll
+  for (int i = 0; i < RADI_HK; ++i) acc[i] = 0.0;
+  for (int row0 = r0; row0 < r1; row0 += RADI_HB) {
+    const int nr = min(RADI_HB, r1 - row0);
+    for (int e = tid; e < RADI_HB * k; e += 256) {
+      const int r = e / k, c = e - r * k;
+      double a = 0.0, s = 0.0, q = 0.0;
+      if (r < nr) {
+        const int row = row0 + r;
+        q = Q[(size_t)row * k + c];
+        const int p1 = rp[row + 1];
+#pragma unroll 4
+        for (int p = rp[row]; p < p1; ++p) {
+          const int col = ci[p];
+          const double qv = col < nv ? Q[(size_t)col * k + c] : 0.0;      // (beyond nv: the J^T part of the saddle row)
+          a = fma(vA[p], qv, a);
+          s = fma(vE[p], qv, s);
+        }
+      }
+      ys[r * ldy + c] = a;
+      ys[r * ldy + k + c] = s;
+      qs[r * ldq + c] = q;
+    }
+    for (int e = tid; e < RADI_HB * ldp; e += 256) {
+      const int r = e / ldp, c = e - r * ldp;
+      ys[r * ldy + 2 * k + c] = r < nr ? RU[(size_t)(row0 + r) * ldp + c] : 0.0;
+    }
+    for (int e = tid; e < RADI_HB * nb; e += 256) {
+      const int r = e / nb, c = e - r * nb;
+      ys[r * ldy + 2 * k + ldp + c] = r < nr ? B[(size_t)(row0 + r) * nb + c] : 0.0;
+    }
+    __syncthreads();
+    if (summing) {
+      for (int r = sub; r < nr; r += nsub) {
+        const double y = ys[r * ldy + j];
+        const double* qr = qs + r * ldq;
+#pragma unroll
+        for (int i = 0; i < RADI_HK; ++i)
+          if (i < k) acc[i] = fma(qr[i], y, acc[i]);
+      }
+    }
+    __syncthreads();
+  }
+  double* out = part + (size_t)blockIdx.x * k * W;
+  if (nsub == 1) {
+    if (summing) {
+#pragma unroll
+      for (int i = 0; i < RADI_HK; ++i)
+        if (i < k) out[i * W + j] = acc[i];
+    }
+    return;
+  }
+  for (int s = 0; s < nsub; ++s) {          // the sub-sums of a column, in sub order
+    if (summing && sub == s) {
+#pragma unroll
+      for (int i = 0; i < RADI_HK; ++i)
+        if (i < k) red[i * W + j] = s == 0 ? acc[i] : red[i * W + j] + acc[i];
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < k * W; e += 256) out[e] = red[e];
+}
+// row slices: 64 rows or more each (a multiple of RADI_HB), at most 1024 of them
+static int radi_reduce_slices(int n, int& rows_per_slice) {
+  const int want = std::max(1, std::min((n + 63) / 64, 1024));
+  rows_per_slice = RADI_HB * (((n + want - 1) / want + RADI_HB - 1) / RADI_HB);
+  return (n + rows_per_slice - 1) / rows_per_slice;
+}
+size_t radi_reduce_partial_len(int nv, int k, int m, int nb) {
+  int rps = 0;
+  return (size_t)radi_reduce_slices(std::max(nv, 1), rps) * k * (2 * k + m + 2 * nb);
+}
+void launch_radi_reduce(hipStream_t st, int nv, int k, int m, int nb, const int* rp, const int* ci, const double* vA,
+                        const double* vE, const double* Q, const double* RU, const double* B, double* partial,
+                        double* H) {
+  if (nv <= 0) return;
+  const int W = 2 * k + m + 2 * nb;
+  const int nsub = std::max(1, std::min(256 / W, RADI_HB));
+  int rps = 0;
+  const int slices = radi_reduce_slices(nv, rps);
+  const size_t lds = sizeof(double) * ((size_t)RADI_HB * ((W | 1) + (k | 1)) + (nsub > 1 ? (size_t)k * W : 0));
+  hipLaunchKernelGGL(radi_reduce_kernel, dim3(slices), dim3(256), lds, st, nv, k, m, nb, rps, nsub, rp, ci, vA, vE, Q,
+                     RU, B, partial);
+  hipLaunchKernelGGL(radi_vtb_reduce_kernel, dim3((k * W + 255) / 256), dim3(256), 0, st, slices, k * W, partial, H);
 }
 
 }  // namespace ricadi

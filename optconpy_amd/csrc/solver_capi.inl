@@ -112,7 +112,7 @@ static void factor_download(ricadi_ctx* c, double* Z_out) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 407; }
+int ricadi_version(void) { return 408; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
@@ -281,6 +281,7 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   const PrecondRecords pr = build_records(hs, J, JT, c->sw.sweep_meta, c->sw.ms_spmm);
   // the child level (same stream and rocBLAS handle) takes the coarse problem
   c->cache.clear();
+  c->radi_sd.reset();
   c->child.reset();
   if (hs.multilevel) {
     std::unique_ptr<ricadi_ctx> ch(new ricadi_ctx);
@@ -529,6 +530,7 @@ int ricadi_exchange_count(ricadi_ctx* c, int64_t* count_out) {
 int ricadi_set_dims(ricadi_ctx* c, int nv) {
   REQUIRE(c && nv > 0, RICADI_EINVAL, "bad argument");
   c->cache.clear();
+  c->radi_sd.reset();
   for (auto& e : c->rec_ring) e->serial = -1;
   c->has_op = false;
   c->nv = nv;
@@ -955,6 +957,8 @@ static int check_radi(const ricadi_ctx* c, const double* shifts, int ns, const v
   REQUIRE(max_steps >= 1, RICADI_EINVAL, "max_steps must be positive");
   for (int i = 0; i < ns; ++i) REQUIRE(shifts[i] < 0.0, RICADI_EINVAL, "RADI shifts must be negative");
   REQUIRE(!sharded(c), RICADI_ESTATE, "ricadi_ric_radi does not shard: clear the exchange of this context first");
+  REQUIRE(c->radi_shift_mode != RICADI_RADI_SHIFTS_HAMILTONIAN || mw <= 32, RICADI_EINVAL,
+          "RICADI_RADI_SHIFTS_HAMILTONIAN needs mw <= 32");
   return RICADI_OK;
 }
 static void radi_stats_out(const RadiStats& s, double* stats_out) {
@@ -1012,6 +1016,27 @@ int ricadi_ric_radi_dev(ricadi_ctx* c, const double* shifts, int ns, const doubl
   breakdown = s.breakdown;
   if (c_out) *c_out = c->zc;
   API_END_STATUS(breakdown ? (ricadi::set_error(RADI_BREAKDOWN_MSG), RICADI_EBREAKDOWN) : RICADI_OK)
+}
+
+int ricadi_set_radi_shifts(ricadi_ctx* c, int mode) {
+  REQUIRE(c && (mode == RICADI_RADI_SHIFTS_CYCLE || mode == RICADI_RADI_SHIFTS_HAMILTONIAN), RICADI_EINVAL,
+          "mode must be RICADI_RADI_SHIFTS_CYCLE or RICADI_RADI_SHIFTS_HAMILTONIAN");
+  c->radi_shift_mode = mode;
+  return RICADI_OK;
+}
+int ricadi_radi_shift_history(ricadi_ctx* c, double* out, int cap, int* n_out) {
+  REQUIRE(c && n_out && cap >= 0 && (out || cap == 0), RICADI_EINVAL, "bad argument");
+  REQUIRE(c->radi_ran, RICADI_ESTATE, "no RADI iteration has run on this context");
+  const int n = (int)c->radi_shift_hist.size();
+  *n_out = n;
+  for (int i = 0; i < std::min(n, cap); ++i) out[i] = c->radi_shift_hist[i];
+  return RICADI_OK;
+}
+int ricadi_radi_shift_fallbacks(ricadi_ctx* c, int* n_out) {
+  REQUIRE(c && n_out, RICADI_EINVAL, "NULL argument");
+  REQUIRE(c->radi_ran, RICADI_ESTATE, "no RADI iteration has run on this context");
+  *n_out = c->radi_fallbacks;
+  return RICADI_OK;
 }
 
 // Copy of the device-resident factor into a DEVICE buffer (nv x cz row-major, ld cz; cz = ricadi_factor_cols)

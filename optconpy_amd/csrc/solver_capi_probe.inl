@@ -498,4 +498,26 @@ int ricadi_radi_update_dev(ricadi_ctx* c, double p, const double* dV, int ldv, i
   API_END_STATUS(flag ? (ricadi::set_error(RADI_BREAKDOWN_MSG), RICADI_EBREAKDOWN) : RICADI_OK)
 }
 
+// the reduced matrices of the shift selection (launch_radi_reduce), synchronous
+int ricadi_radi_reduce_dev(ricadi_ctx* c, const double* dQ, int k, const double* dRU, int m, const double* dB, int nb,
+                           double* dH_out) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(dQ && dRU && dB && dH_out, RICADI_EINVAL, "NULL argument");
+  REQUIRE(k >= 1 && k <= 32 && m >= 1 && m <= 32 && nb >= 1 && nb <= 64, RICADI_EINVAL,
+          "1 <= k <= 32, 1 <= m <= 32, 1 <= nb <= 64 required");
+  API_BEGIN_ON(c)
+  TArr<double> part(c->pool, radi_reduce_partial_len(c->nv, k, m, nb));
+  launch_radi_reduce(c->st, c->nv, k, m, nb, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, dQ, dRU, dB, part.p, dH_out);
+  HIPCHK(hipStreamSynchronize(c->st));
+  API_END
+}
+
+int ricadi_probe_cache_entries(ricadi_ctx* c, int* n_out) {
+  REQUIRE(c && n_out, RICADI_EINVAL, "NULL argument");
+  size_t n = 0;
+  for (const ricadi_ctx* l = c; l; l = l->child.get()) n += l->cache.size();
+  *n_out = (int)n;
+  return RICADI_OK;
+}
+
 }  // extern "C"

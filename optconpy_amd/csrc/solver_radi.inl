@@ -20,6 +20,122 @@ struct RadiStats {
   bool breakdown = false;           // the factorisation kernel met a pivot that is not positive and finite
 };
 
+// The per-shift entry of a GENERATED shift (RICADI_RADI_SHIFTS_HAMILTONIAN): c->cache is an unbounded map keyed by the
+// shift, and thirty distinct shifts per call would each leave their per-shift data behind (the dense coarse inverse
+// alone is about 40 MB at cfg2).  Instead every level lends its one ricadi_ctx::radi_sd to its map under the shift's
+// key, marked stale -- so that setup_issue rebuilds it in the buffers it already has and resets smw_epoch and the
+// `rec` serials, as for any stale entry -- and takes it back before the next shift, at the end of the call and when
+// the call is left by an exception.  A level whose map already holds the key (a shift of the caller's list) is left
+// alone.
+struct OwnedShift {
+  ricadi_ctx* c;
+  std::pair<double, double> key{0.0, 0.0};
+  std::vector<ricadi_ctx*> lent;
+  explicit OwnedShift(ricadi_ctx* ctx) : c(ctx) {}
+  OwnedShift(const OwnedShift&) = delete;
+  OwnedShift& operator=(const OwnedShift&) = delete;
+  void lend(double p) {
+    take_back();
+    key = std::make_pair(p, 1.0);
+    for (ricadi_ctx* l = c; l; l = l->child.get()) {
+      if (l->cache.count(key)) continue;
+      if (!l->radi_sd) l->radi_sd.reset(new ShiftData);
+      l->radi_sd->valid = false;
+      l->radi_sd->last_iters = -1;
+      l->radi_sd->sub = nullptr;
+      lent.push_back(l);              // (before the emplace: if that throws, take_back finds nothing to take)
+      l->cache.emplace(key, std::move(l->radi_sd));
+    }
+  }
+  void take_back() {
+    for (ricadi_ctx* l : lent) {
+      auto it = l->cache.find(key);
+      if (it == l->cache.end()) continue;
+      l->radi_sd = std::move(it->second);
+      l->cache.erase(it);
+    }
+    lent.clear();
+  }
+  ~OwnedShift() { take_back(); }
+};
+
+// Scratch of the shift selection (HAMILTONIAN mode), sized once per call
+struct RadiShiftWork {
+  TArr<double> Q, Q1, G, T, Rq, H, part, gpart;
+  explicit RadiShiftWork(ricadi_ctx* c)
+      : Q(c->pool), Q1(c->pool), G(c->pool), T(c->pool), Rq(c->pool), H(c->pool), part(c->pool), gpart(c->pool) {}
+  void alloc(ricadi_ctx* c, int m, int nb) {
+    const int nv = c->nv;
+    Q.alloc((size_t)nv * m);
+    Q1.alloc((size_t)nv * m);
+    G.alloc((size_t)m * m);
+    T.alloc((size_t)4 * 128 * 128);
+    Rq.alloc((size_t)m * m);
+    H.alloc((size_t)m * (3 * m + 2 * nb));
+    part.alloc(radi_reduce_partial_len(nv, m, m, nb));
+    gpart.alloc(gram_fixed_partial_len(nv, m));
+  }
+};
+
+// Q R = the new block of Z (nv x m at dZblk, leading dimension ldz, read where it lies) and the reduced matrices
+// H = Q^T [cal A Q | cal E Q | R | U | B] (ricadi_radi.hip), all on the stream, no host synchronisation.  The QR is the
+// CholQR2 panel step of block_qr_dev on its kernels (cholqr_wide, the MFMA GEMM for Q), with the two Gram matrices from
+// the fixed-order Gram kernel instead of the atomically accumulated GEMM: the same inputs give bitwise the same Q, R
+// and H.  *qrflag (device) is raised when a Gram matrix is not positive definite to working precision; the caller then
+// repeats the QR with block_qr_dev (Householder TSQR).
+static void radi_shift_issue(ricadi_ctx* c, RadiShiftWork& w, const double* dZblk, int ldz, int m, const double* dRU,
+                             const double* dB, int nb, int* qrflag) {
+  hipStream_t st = c->st;
+  const int nv = c->nv;
+  double *T1 = w.T.p, *R1 = T1 + 16384, *T2 = R1 + 16384, *R2 = T2 + 16384;
+  HIPCHK(hipMemsetAsync(qrflag, 0, sizeof(int), st));
+  launch_gram_fixed(st, nv, m, dZblk, ldz, w.gpart.p, w.G.p);
+  launch_cholqr_wide(st, m, w.G.p, m, T1, R1, qrflag);
+  launch_gemm_nn(st, nv, m, m, dZblk, ldz, T1, 128, w.Q1.p, m, 1.0, 0.0);
+  launch_gram_fixed(st, nv, m, w.Q1.p, m, w.gpart.p, w.G.p);
+  launch_cholqr_wide(st, m, w.G.p, m, T2, R2, qrflag);
+  launch_gemm_nn(st, nv, m, m, w.Q1.p, m, T2, 128, w.Q.p, m, 1.0, 0.0);
+  launch_gemm_nn(st, m, m, m, R2, 128, R1, 128, w.Rq.p, m, 1.0, 0.0);        // R = R_2 R_1
+  launch_radi_reduce(st, nv, m, m, nb, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, w.Q.p, dRU, dB, w.part.p, w.H.p);
+}
+
+// The next shift from what a step has fetched: hH = Q^T [cal A Q | cal E Q | R | U | B] for all m columns
+// of the block's Q, hR = R of its QR.  The basis of the selection is the columns of Q whose diagonal entry of R is at
+// least 1e-12 of the largest one (a W of deficient rank -- the DRE forms of the test problems: 8 columns, rank 4 --
+// makes every block of Z as deficient, and the other columns of Q are then arbitrary directions): the rows of H of
+// those columns, and their columns in the two projected operators.  false: fall back to the caller's list -- an entry
+// that is not finite, a breakdown of the selection, no candidate, or a shift that is not finite and negative.
+static bool radi_next_shift(int m, int nb, const double* hH, const double* hR, double* p_out, double* margin_out) {
+  const int hw = 3 * m + 2 * nb;
+  double dmax = 0.0;
+  for (int i = 0; i < m; ++i) {
+    const double d = std::fabs(hR[(size_t)i * m + i]);
+    if (!(d <= std::numeric_limits<double>::max())) return false;
+    dmax = std::max(dmax, d);
+  }
+  if (dmax == 0.0) return false;
+  std::vector<int> keep;
+  for (int i = 0; i < m; ++i)
+    if (std::fabs(hR[(size_t)i * m + i]) >= 1e-12 * dmax) keep.push_back(i);
+  const int k = (int)keep.size(), kw = 2 * k + m + 2 * nb;
+  std::vector<double> Hk((size_t)k * kw);
+  for (int a = 0; a < k; ++a) {
+    const double* row = hH + (size_t)keep[a] * hw;
+    double* out = Hk.data() + (size_t)a * kw;
+    for (int b = 0; b < k; ++b) {
+      out[b] = row[keep[b]];
+      out[k + b] = row[m + keep[b]];
+    }
+    std::copy(row + 2 * m, row + hw, out + 2 * k);
+  }
+  double p = 0.0, margin = 0.0;
+  if (ricadi::radi_shift_select(k, m, nb, Hk.data(), &p, &margin, nullptr, nullptr) != RICADI_OK) return false;
+  if (!(p < 0.0) || !(p >= -std::numeric_limits<double>::max())) return false;
+  *p_out = p;
+  *margin_out = margin;
+  return true;
+}
+
 // The dense part of one step on device operands: G = V^T B, the coefficient matrix C, the fused update of [R | U]
 // and the block of Z (ricadi_radi.hip).  dG (m x nb), dC (m x (2m + nb)), dPart (radi_vtb_partial_len) and the flag
 // word are the caller's; the word is cleared here and raised by the factorisation kernel.
@@ -45,6 +161,11 @@ static void radi_dense_step(ricadi_ctx* c, double p, const double* dV, int ldv, 
 // The factor is left in the context (c->Z, c->zc); the gain cal E X B = U + old goes to dK_out (nv x nb, may be NULL).
 // Recycling of solved right-hand sides is off inside (the panel width changes after the first step; the ring's
 // assumptions have not been checked for that).
+// Shifts: RICADI_RADI_SHIFTS_CYCLE cycles through `shifts`.  RICADI_RADI_SHIFTS_HAMILTONIAN (mw <= 32) starts with
+// shifts[0] and generates every later shift from the iteration: right after the residual Gram launch the QR of the new
+// block of Z and the reduction kernel are issued -- speculatively, once too often at the end --, H and R are fetched
+// with the Gram matrix and the flag words in the step's ONE synchronisation, and the host selects the shift after the
+// stop test (radi_next_shift); `shifts` is the fallback cycle, with a counter of its own.
 static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const double* dB, int nb, const double* dW,
                               int mw, const double* dOld, int max_steps, double res_reltol, int compress_cols,
                               bool project_w, bool verbose, double* dK_out) {
@@ -65,8 +186,14 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
       dC(c->pool, (size_t)m * (2 * m + nb)), dPart(c->pool, radi_vtb_partial_len(nv, m, nb));
   // W is projected in place: private copy
   HIPCHK(hipMemcpyAsync(dWm.p, dW, sizeof(double) * nv * m, hipMemcpyDeviceToDevice, st));
-  // per-shift data of the whole cycle (and of the projection) up front, as lyap_adi_dev
-  setup_and_project(c, shifts, std::min(ns, max_steps), project_w, dWm.p, m);
+  const bool ham = c->radi_shift_mode == RICADI_RADI_SHIFTS_HAMILTONIAN;
+  const int hw = 3 * m + 2 * nb;                      // columns of H
+  c->radi_shift_hist.clear();
+  c->radi_fallbacks = 0;
+  c->radi_ran = true;
+  // per-shift data of the whole cycle (and of the projection) up front, as lyap_adi_dev; with generated shifts the
+  // first shift only
+  setup_and_project(c, shifts, ham ? 1 : std::min(ns, max_steps), project_w, dWm.p, m);
   // the panel [R | U]: R = P^T W, U = -old
   launch_copy_cols(st, nv, m, dWm.p, m, 0, dRU.p, mp, 0, 1.0);
   if (dOld) launch_copy_cols(st, nv, nb, dOld, nb, 0, dRU.p, mp, m, -1.0);
@@ -82,14 +209,38 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
   // fetched with the first step's
   c->res_part.ensure(gram_fixed_partial_len(nv, m));
   c->res_gram.ensure((size_t)2 * mm);
-  double* hg = res_host(c, (size_t)2 * mm + 1);
-  int* hflag = reinterpret_cast<int*>(hg + 2 * mm);
+  double* hg = res_host(c, (size_t)2 * mm + 1 + (ham ? (size_t)m * hw + mm : 0));
+  int* hflag = reinterpret_cast<int*>(hg + 2 * mm);          // [0] the factorisation's flag, [1] the QR's
+  double *hH = hg + 2 * mm + 1, *hR = hH + (size_t)m * hw;
   int* dflag = c->flag.p + 3;
+  int* qrflag = c->flag.p + 1;                               // (block_qr_dev's word: the fallback QR reuses it)
+  hflag[1] = 0;
+  RadiShiftWork sw(c);
+  if (ham) sw.alloc(c, m, nb);
+  OwnedShift owned(c);
+  double p_next = shifts[0], margin = 0.0;
+  bool fell_back = false;
+  int nfb = 1;                                               // the fallback cycle's own counter
+  double tph[4] = {0, 0, 0, 0};                              // RICADI_TIMING: setup, solve + dense step, QR + reduction, selection
+  Tick tk;
+  auto lap = [&](int i) {
+    if (c->sw.timing) {
+      (void)hipStreamSynchronize(st);
+      tph[i] += tk.lap();
+    }
+  };
   launch_gram_fixed(st, nv, m, dRU.p, mp, c->res_part.p, c->res_gram.p);
   c->res_launches += 2;
   for (int step = 1; step <= max_steps; ++step) {
-    const double p = shifts[(step - 1) % ns];
+    const double p = ham ? p_next : shifts[(step - 1) % ns];
+    c->radi_shift_hist.push_back(p);
+    if (c->sw.timing) tk.lap();
+    if (ham && step > 1) {
+      if (fell_back) owned.take_back();
+      else owned.lend(p);
+    }
     ShiftData* sd = get_shift(c, p, 1.0);
+    lap(0);
     GmresResult r;
     int ldv = m;
     if (uzero) {
@@ -119,9 +270,18 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
     uzero = false;
     launch_gram_fixed(st, nv, m, dRU.p, mp, c->res_part.p, c->res_gram.p + mm);
     c->res_launches += 2;
+    lap(1);
+    const double* dZblk = c->Z.p + c->zc;
+    if (ham) {
+      radi_shift_issue(c, sw, dZblk, c->zld, m, dRU.p, dB, nb, qrflag);
+      HIPCHK(hipMemcpyAsync(hH, sw.H.p, sizeof(double) * m * hw, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(hR, sw.Rq.p, sizeof(double) * mm, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(hflag + 1, qrflag, sizeof(int), hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipMemcpyAsync(hg, c->res_gram.p, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(hflag, dflag, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    if (c->sw.timing) tph[2] += tk.lap();
     if (*hflag != 0) {
       stt.breakdown = true;
       break;
@@ -132,11 +292,35 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
     c->zc += m;
     stt.steps = step;
     c->adi_res_hist.push_back(stt.res);
-    if (verbose)
-      fprintf(stderr, "[ricadi] RADI step %3d: shift %10.3e rel residual %9.3e gmres its %d\n", step, p, stt.res, r.iters);
+    if (verbose) {
+      if (ham)
+        fprintf(stderr, "[ricadi] RADI step %3d: shift %10.3e (%s, margin %.3f) rel residual %9.3e gmres its %d\n", step,
+                p, step == 1 ? "first" : fell_back ? "fallback" : "generated", step == 1 || fell_back ? 0.0 : margin,
+                stt.res, r.iters);
+      else
+        fprintf(stderr, "[ricadi] RADI step %3d: shift %10.3e rel residual %9.3e gmres its %d\n", step, p, stt.res,
+                r.iters);
+    }
     if (stt.res <= res_reltol) {
       c->adi_stop_rule = RICADI_STOP_RES;
       break;
+    }
+    if (ham && step < max_steps) {
+      if (hflag[1] != 0) {
+        // the block's Gram matrix is not positive definite to working precision: Householder TSQR, and H once more
+        block_qr_dev(c, dZblk, c->zld, nv, m, sw.Q.p, sw.Rq.p);
+        launch_radi_reduce(st, nv, m, m, nb, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, sw.Q.p, dRU.p, dB, sw.part.p,
+                           sw.H.p);
+        HIPCHK(hipMemcpyAsync(hH, sw.H.p, sizeof(double) * m * hw, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hR, sw.Rq.p, sizeof(double) * mm, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+      }
+      fell_back = !radi_next_shift(m, nb, hH, hR, &p_next, &margin);
+      if (fell_back) {
+        p_next = shifts[nfb++ % ns];
+        ++c->radi_fallbacks;
+      }
+      if (c->sw.timing) tph[3] += tk.lap();
     }
     if (step < max_steps && c->zc - zc_last >= compress_cols) {
       factor_recompress(c);
@@ -145,6 +329,9 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
   }
   stt.gmres_iters = c->total_iters - it0;
   stt.escalations = c->escalations - esc0;
+  if (c->sw.timing)
+    fprintf(stderr, "[ricadi timing] RADI %d steps (%s shifts): per-shift setup %.1f ms, solve + dense step %.1f, QR + reduction %.1f, host selection %.1f\n",
+            stt.steps, ham ? "generated" : "cycled", 1e3 * tph[0], 1e3 * tph[1], 1e3 * tph[2], 1e3 * tph[3]);
   if (dK_out && !stt.breakdown) {
     launch_copy_cols(st, nv, nb, dRU.p, mp, m, dK_out, nb, 0, 1.0);
     if (dOld) launch_axpby(st, (size_t)nv * nb, 1.0, dOld, 1.0, dK_out);

@@ -327,36 +327,54 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
     starts from zero.
 
     ``radi_dict`` keys: ``ms`` (negative real shifts, cycled; ``'auto'`` generates them as the Newton call does for
-    its first step), ``radi_max_steps`` (200), ``radi_res_reltol`` (1e-10), ``compress_cols`` (the factor is
-    recompressed whenever it has grown by that many columns; default 512), ``verbose``, ``device_resident``.
+    its first step; ``'hamiltonian'`` starts with ``adi_shifts.initial_shift`` of the operator and generates every
+    later shift from the iteration itself -- ``ricadi_set_radi_shifts``; needs at most 32 columns in
+    ``wmat``), ``ms_fallback`` (with ``ms='hamiltonian'`` only: a list of negative reals that replaces that one-element
+    list -- its first entry starts, the list is cycled where a shift cannot be generated), ``radi_max_steps`` (200),
+    ``radi_res_reltol`` (1e-10), ``compress_cols`` (the factor is recompressed whenever it has grown by that many
+    columns; default 512), ``verbose``, ``device_resident``.
 
     Returns a dict: ``zfac`` (ndarray; a :class:`DeviceFactor` when given device panels or with
     ``device_resident``), ``gain`` = ``cal E X B`` (ndarray), ``radi_steps``, ``res_hist`` (the relative residual
     after every step), ``stop_rule`` (``_lib.RICADI_STOP_RES`` or ``_lib.RICADI_STOP_MAX_STEPS``),
-    ``gmres_nonconverged``, ``shift_solves``, ``gmres_iters`` (and ``ms`` / ``shift_info`` with ``ms='auto'``)."""
+    ``gmres_nonconverged``, ``shift_solves``, ``gmres_iters`` (and ``ms`` / ``shift_info`` with ``ms='auto'``; with
+    ``ms='hamiltonian'`` ``ms`` -- the shift of every step -- and ``shift_fallbacks``)."""
     d = {} if radi_dict is None else radi_dict
     calA, calE = _orient(amat, mmat, transposed)
     ctx = backend.context_for(calA, calE, jmat)
     ctx.set_lowrank(None, None)
-    ms = _shifts(d)
+    generated = isinstance(d.get("ms"), str) and d["ms"] == "hamiltonian"
     sinfo = None
-    if _is_auto(ms):
-        ms = _newton_auto_shifts(ctx, d, calE, bmat, wmat, None, mtxoldb)
-        sinfo = dict(ms.info)
+    if generated:
+        fb = d.get("ms_fallback")
+        ms = [adi_shifts.initial_shift(ctx.diag_ratio)] if fb is None else _shifts(dict(ms=list(fb)))
+    else:
+        ms = _shifts(d)
+        if _is_auto(ms):
+            ms = _newton_auto_shifts(ctx, d, calE, bmat, wmat, None, mtxoldb)
+            sinfo = dict(ms.info)
     kw = dict(max_steps=int(d.get("radi_max_steps", 200)), res_reltol=float(d.get("radi_res_reltol", 1e-10)),
               compress_cols=int(d.get("compress_cols", 0)), verbose=bool(d.get("verbose", False)))
-    if d.get("device_resident", False) or any(_on_device(x) for x in (bmat, wmat, mtxoldb)):
-        Zt, Kt, info = ctx.ric_radi_dev(ms, to_device(bmat).t, to_device(wmat).t,
-                                        old_t=None if mtxoldb is None else to_device(mtxoldb).t, **kw)
-        Z, K = DeviceFactor(Zt), Kt.cpu().numpy()
-    else:
-        Z, K, info = ctx.ric_radi(ms, _dense(bmat), _dense(wmat),
-                                  oldB=None if mtxoldb is None else _dense(mtxoldb), **kw)
+    # the shift mode is a context setting: set for this call, and as before after it, also when the call fails
+    mode_before = ctx.set_radi_shifts("hamiltonian") if generated else None
+    try:
+        if d.get("device_resident", False) or any(_on_device(x) for x in (bmat, wmat, mtxoldb)):
+            Zt, Kt, info = ctx.ric_radi_dev(ms, to_device(bmat).t, to_device(wmat).t,
+                                            old_t=None if mtxoldb is None else to_device(mtxoldb).t, **kw)
+            Z, K = DeviceFactor(Zt), Kt.cpu().numpy()
+        else:
+            Z, K, info = ctx.ric_radi(ms, _dense(bmat), _dense(wmat),
+                                      oldB=None if mtxoldb is None else _dense(mtxoldb), **kw)
+    finally:
+        if generated:
+            ctx.set_radi_shifts(mode_before)
     out = dict(zfac=Z, gain=K, radi_steps=info["radi_steps"], res_hist=ctx.adi_res_history(),
                stop_rule=ctx.STOP_RULES.index(info["stop_rule"]), gmres_nonconverged=info["gmres_nonconverged"],
                shift_solves=info["shift_solves"], gmres_iters=info["gmres_iters"])
     if sinfo is not None:
         out["ms"], out["shift_info"] = list(ms), sinfo
+    if generated:
+        out["ms"], out["shift_fallbacks"] = list(ctx.radi_shift_history()), ctx.radi_shift_fallbacks()
     return out
 
 

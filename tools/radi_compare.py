@@ -3,6 +3,9 @@ panels: steps, shift solves, GMRES iterations, wall-clock to the gain K and fina
 their distance to the oracle's K (tests/golden/cfg2_golden.npz).  Not a pass/fail gate: the lines it prints (JSON,
 one per path and tolerance, then a summary) are the record behind DESIGN.md section 3d.
 
+RADI runs twice per tolerance: with the benchmark's shift list cycled ("radi") and with the shifts generated from the
+iteration ("radi-ham": ms='hamiltonian'; its lines also carry the fallback count and the shifts).
+
 Both paths start from zero, with the per-shift cache cleared before every call (the setup is part of the call), and
 end with K on the host.  RADI runs at several residual tolerances; the one compared is the loosest whose K is as
 close to the fixture as Newton's (within 10 %), else the tightest.  Timings: one warm-up call of every variant, then
@@ -59,18 +62,23 @@ def main():
                        shift_solves=out["shift_solves"], gmres_iters=out["gmres_iters"], cols=out["zfac"].shape[1],
                        nonconverged=out["gmres_nonconverged"])
 
-    def radi(tol):
+    def radi(tol, generated=False):
         def run():
             ctx.clear_cache()
             out = pru.proj_alg_ric_radi(mmat=pr.M, amat=F, jmat=pr.J, bmat=tb_d, wmat=trct_d,
-                                        radi_dict=dict(ms=ms, radi_res_reltol=tol, radi_max_steps=400))
-            return -out["gain"], dict(path="radi", radi_res_reltol=tol, steps=out["radi_steps"],
-                                      shift_solves=out["shift_solves"], gmres_iters=out["gmres_iters"],
-                                      cols=out["zfac"].shape[1], nonconverged=out["gmres_nonconverged"],
-                                      stop_rule=out["stop_rule"], last_res=float(out["res_hist"][-1]))
+                                        radi_dict=dict(ms="hamiltonian" if generated else ms, radi_res_reltol=tol,
+                                                       radi_max_steps=400))
+            info = dict(path="radi-ham" if generated else "radi", radi_res_reltol=tol, steps=out["radi_steps"],
+                        shift_solves=out["shift_solves"], gmres_iters=out["gmres_iters"],
+                        cols=out["zfac"].shape[1], nonconverged=out["gmres_nonconverged"],
+                        stop_rule=out["stop_rule"], last_res=float(out["res_hist"][-1]))
+            if generated:
+                info.update(shift_fallbacks=out["shift_fallbacks"], shifts=[float(p) for p in out["ms"]])
+            return -out["gain"], info
         return run
 
-    variants = [("newton-adi", newton)] + [("radi %g" % t, radi(t)) for t in args.tols]
+    variants = ([("newton-adi", newton)] + [("radi %g" % t, radi(t)) for t in args.tols]
+                + [("radi-ham %g" % t, radi(t, generated=True)) for t in args.tols])
     rec, times = {}, {name: [] for name, _ in variants}
     for name, fn in variants:                         # warm-up: every shape the timed calls use
         K, info = fn()
@@ -98,6 +106,12 @@ def main():
     lines.append(dict(path="summary", compared_radi_res_reltol=pick["radi_res_reltol"], newton_ms=nt, radi_ms=rt,
                       newton_K_vs_fixture=nd, radi_K_vs_fixture=pick["K_vs_fixture"],
                       faster="radi" if rt < nt else "newton-adi", ratio=max(rt, nt) / min(rt, nt)))
+    for t in args.tols:                               # generated shifts against the cycled list, tolerance by tolerance
+        c, h = rec["radi %g" % t], rec["radi-ham %g" % t]
+        lines.append(dict(path="summary-shifts", radi_res_reltol=t, cycled_steps=c["steps"], generated_steps=h["steps"],
+                          cycled_ms=c["ms_median"], generated_ms=h["ms_median"], newton_ms=nt,
+                          generated_K_vs_fixture=h["K_vs_fixture"],
+                          faster="generated" if h["ms_median"] < c["ms_median"] else "cycled"))
     text = "\n".join(json.dumps(l) for l in lines)
     print(text)
     if args.out:

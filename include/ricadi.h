@@ -414,7 +414,7 @@ int ricadi_ric_radi_dev(ricadi_ctx* ctx, const double* shifts, int nshifts, cons
  *   RICADI_RADI_SHIFTS_HAMILTONIAN  shifts[0] for the first step; every later shift is generated from the state of the
  *     iteration ("residual Hamiltonian shifts", section 4.5 of the RADI paper): with Q an orthonormal
  *     basis of the new block of Z (k <= mw columns, all in ker J: the columns of the block's QR whose diagonal entry
- *     of R is at least 1e-12 of the largest one),
+ *     of R is at least RICADI_RADI_RANK_TOL = 3e-8 of the largest one),
  *       H_A = Q^T cal A Q, H_E = Q^T cal E Q, H_R = Q^T R, H_U = Q^T U, H_B = Q^T B,
  *       A_c = H_A - H_U H_B^T,  At = H_E^-1 A_c,  Rt = H_E^-1 H_R,
  *       Ham = [[At^T, -H_B H_B^T], [-Rt Rt^T, -At]]   (2k x 2k),
@@ -446,6 +446,20 @@ int ricadi_radi_reduce_dev(ricadi_ctx* ctx, const double* dQ, int k, const doubl
                            int nb, double* dH_out);
 /* Entries of the per-shift cache, summed over the levels of the preconditioner hierarchy, for tests.               */
 int ricadi_probe_cache_entries(ricadi_ctx* ctx, int* n_out);
+/* Branches of the RADI driver, for tests.
+ * ricadi_probe_radi_refuse: under RICADI_RADI_SHIFTS_HAMILTONIAN the selection made after each of the n listed steps
+ *   (1-based) counts as refused: it still runs and is recorded, and the step that follows takes the next entry of the
+ *   caller's list.  The list stays in the context until it is replaced or cleared (n = 0; steps may then be NULL);
+ *   empty by default.  RICADI_EINVAL for n < 0, n > 0 without steps, or a step below 1.
+ * ricadi_probe_radi_counters, of the most recent ricadi_ric_radi(_dev) call: out[0] how often the block's CholQR2 raised
+ *   its flag (normalised pivot below 1e-12) and the QR and the reduction were repeated with the Householder QR, out[1]
+ *   how often the factor was recompressed inside the call.
+ * ricadi_probe_radi_kept, of the most recent call: the size of the basis (columns of the block's Q kept) of every
+ *   selection made, in order; *n_out their number, at most `cap` copied to `out` (may be NULL with cap = 0).
+ * The last two return RICADI_ESTATE before any RADI call.                                                            */
+int ricadi_probe_radi_refuse(ricadi_ctx* ctx, const int* steps, int n);
+int ricadi_probe_radi_counters(ricadi_ctx* ctx, int* out);
+int ricadi_probe_radi_kept(ricadi_ctx* ctx, int* out, int cap, int* n_out);
 /* The dense part of ONE RADI step on device operands, for tests: dV (its first NV rows, leading dimension ldv >= m),
  * dB NV x nb, dRU = [R | U] NV x (m + nb) updated in place, the new block of Z written to columns [zoff, zoff + m)
  * of dZblk (leading dimension ldz >= zoff + m); dG_out m x nb; dC_out m x (2m + nb) (may be NULL):
@@ -847,6 +861,27 @@ int ricadi_host_radi_shift(int k, int m, int nb, const double* H, double* p_out,
 /* The same, and all 2k eigenvalues of Ham (real and imaginary parts, in no particular order), for tests.             */
 int ricadi_host_radi_shift_eigs(int k, int m, int nb, const double* H, double* p_out, double* margin_out,
                                 double* wr_out, double* wi_out);
+/* What the RADI driver does with what a step has fetched: H = Q^T [cal A Q | cal E Q | R | U | B] for ALL m columns of
+ * the block's Q (m x (3m + 2nb), row-major) and R of the block's QR (m x m, row-major).  The basis of the selection is
+ * the columns i of Q with |R_ii| >= RICADI_RADI_RANK_TOL max_j |R_jj|; H is restricted to their rows, and to their columns in its
+ * first two blocks, and handed to ricadi_host_radi_shift.  (The QR is unpivoted: the kept columns of Q span the block's
+ * range when the dependent columns come last, as in a W = [independent | combinations])  Host only,
+ * no GPU needed.  *kept_out (may be NULL): the
+ * size of the basis (0 where R itself is refused).  Returns 0 with *p_out (negative) and *margin_out (may be NULL)
+ * set, or -- not an error, the driver then takes the next entry of the caller's list and the outputs but *kept_out
+ * are left alone -- one of the values below.  RICADI_EINVAL unless 1 <= m <= 32, 1 <= nb <= 64.                       */
+/* The rank tolerance: the columns of a block are solutions of shift solves of relative accuracy gmres_tol (default
+ * 1e-10), so columns that depend on their predecessors exactly -- a W of deficient rank -- have |R_ii| at that
+ * accuracy times the solves' conditioning, not at rounding level (measured 1e-13 ... 4e-10 of the largest entry on the
+ * dre test forms; the independent columns of every test problem are above 7e-4).  3e-8 is the level of the internal
+ * recompressions: a direction below it changes Z Z^T by less than the rounding unit.                              */
+#define RICADI_RADI_RANK_TOL 3e-8
+#define RICADI_RADI_REFUSED_R_NOT_FINITE 1   /* a diagonal entry of R is not finite                                */
+#define RICADI_RADI_REFUSED_R_ZERO 2         /* the diagonal of R is zero                                          */
+#define RICADI_RADI_REFUSED_BREAKDOWN 3      /* ricadi_host_radi_shift returned RICADI_EBREAKDOWN                  */
+#define RICADI_RADI_REFUSED_NO_SHIFT 4       /* no candidate, or a shift that is not finite and negative          */
+int ricadi_host_radi_next_shift(int m, int nb, const double* H, const double* R, double* p_out, double* margin_out,
+                                int* kept_out);
 
 #ifdef __cplusplus
 }

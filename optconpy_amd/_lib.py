@@ -22,7 +22,7 @@ RICADI_RADI_SHIFTS_CYCLE, RICADI_RADI_SHIFTS_HAMILTONIAN = 0, 1          # ricad
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 408
+ABI_VERSION = 409
 
 
 class RicadiOpts(C.Structure):
@@ -99,6 +99,9 @@ SIGNATURES = {
     "ricadi_radi_shift_fallbacks": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "ricadi_radi_reduce_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
     "ricadi_probe_cache_entries": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "ricadi_probe_radi_refuse": (C.c_int, [_vp, _ip, C.c_int]),
+    "ricadi_probe_radi_counters": (C.c_int, [_vp, _ip]),
+    "ricadi_probe_radi_kept": (C.c_int, [_vp, _ip, C.c_int, C.POINTER(C.c_int)]),
     "ricadi_spmm_dev": (C.c_int, [_vp, C.c_double, C.c_double, _vp, C.c_int, _vp]),
     "ricadi_shift_solve_dev": (C.c_int, [_vp, C.c_double, C.c_double, _vp, C.c_int, _vp,
                                          C.POINTER(C.c_int), _dp]),
@@ -160,6 +163,8 @@ SIGNATURES = {
                                          C.POINTER(C.c_double)]),
     "ricadi_host_radi_shift_eigs": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), _dp, _dp]),
+    "ricadi_host_radi_next_shift": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _vp, C.c_int64)
@@ -741,6 +746,26 @@ class Context:
         _chk(self._lib.ricadi_probe_cache_entries(self._h, C.byref(n)))
         return int(n.value)
 
+    def probe_radi_refuse(self, steps=()):
+        """``ricadi_probe_radi_refuse``: the selection after each of the listed steps (1-based) of later HAMILTONIAN
+        RADI calls counts as refused; stays until replaced or cleared (an empty list).  Tests."""
+        st = np.ascontiguousarray(sorted(int(v) for v in steps), dtype=np.int32)
+        _chk(self._lib.ricadi_probe_radi_refuse(self._h, _i(st) if st.size else None, int(st.size)))
+
+    def probe_radi_counters(self):
+        """``ricadi_probe_radi_counters``: dict(qr_repeats, recompressions) of the last RADI call (tests)."""
+        out = np.zeros(2, dtype=np.int32)
+        _chk(self._lib.ricadi_probe_radi_counters(self._h, _i(out)))
+        return dict(qr_repeats=int(out[0]), recompressions=int(out[1]))
+
+    def probe_radi_kept(self):
+        """``ricadi_probe_radi_kept``: the basis size of every shift selection of the last RADI call (tests)."""
+        n = C.c_int(0)
+        _chk(self._lib.ricadi_probe_radi_kept(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.int32)
+        _chk(self._lib.ricadi_probe_radi_kept(self._h, _i(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
+
     def radi_reduce_dev(self, q_ptr, k, ru_ptr, m, b_ptr, nb, h_ptr):
         """``ricadi_radi_reduce_dev``: H = Q^T [cal A Q | cal E Q | R | U | B] on device pointers (tests)."""
         _chk(self._lib.ricadi_radi_reduce_dev(self._h, q_ptr, int(k), ru_ptr, int(m), b_ptr, int(nb), h_ptr))
@@ -1179,6 +1204,29 @@ def host_radi_shift(k, m, nb, H, eigs=False):
     wr, wi = np.zeros(2 * max(int(k), 1)), np.zeros(2 * max(int(k), 1))
     _chk(load().ricadi_host_radi_shift_eigs(int(k), int(m), int(nb), _d(H), C.byref(p), C.byref(mg), _d(wr), _d(wi)))
     return p.value, mg.value, wr + 1j * wi
+
+
+RADI_REFUSALS = {1: "r_not_finite", 2: "r_zero", 3: "breakdown", 4: "no_shift"}      # RICADI_RADI_REFUSED_*
+
+
+def host_radi_next_shift(m, nb, H, R):
+    """``ricadi_host_radi_next_shift``: what the RADI driver does with what a step has fetched -- H = Q^T [cal A Q |
+    cal E Q | R | U | B] for all m columns of the block's Q (m x (3m + 2nb)) and R of its QR (m x m); host only.
+    Returns ``(p, margin, kept, refusal)``: ``refusal`` is None and p, margin are set, or it is one of
+    ``RADI_REFUSALS``' names and p, margin are None (the driver then falls back to its list).  ``kept``: the size of the
+    basis of the selection.  ValueError for bad sizes."""
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    m, nb = int(m), int(nb)
+    if min(m, nb) >= 1 and (H.size != m * (3 * m + 2 * nb) or R.size != m * m):
+        raise ValueError("H must be m x (3m + 2nb) and R m x m")
+    p, mg, kept = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+    rc = load().ricadi_host_radi_next_shift(m, nb, _d(H), _d(R), C.byref(p), C.byref(mg), C.byref(kept))
+    if rc < 0:
+        _chk(rc)
+    if rc > 0:
+        return None, None, kept.value, RADI_REFUSALS[rc]
+    return p.value, mg.value, kept.value, None
 
 
 def host_plan_levels(calA, calE, J, **opts):

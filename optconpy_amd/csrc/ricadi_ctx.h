@@ -371,6 +371,12 @@ struct ricadi_ctx {
   std::vector<double> radi_shift_hist;
   int radi_fallbacks = 0;
   bool radi_ran = false;
+  // of the last call, for the tests (solver_capi_probe.inl): the basis size of every selection made, how often the
+  // block's QR and the reduction were repeated with the Householder QR, how often the factor was recompressed; and
+  // the probe's list of steps after which the selection counts as refused (stays until the probe clears it)
+  std::vector<int> radi_kept_hist;
+  int radi_qr_repeats = 0, radi_recompressions = 0;
+  std::vector<int> radi_refuse;
   // per-shift data
   std::map<std::pair<double, double>, std::unique_ptr<ShiftData>> cache;
   // The ONE entry the RADI driver rebuilds for every generated shift (a level owns its own): it is lent to `cache`

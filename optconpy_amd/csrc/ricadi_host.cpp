@@ -1592,6 +1592,51 @@ int radi_shift_select(int k, int m, int nb, const double* H, double* p_out, doub
   return RICADI_OK;
 }
 
+// The next shift from what a step of the RADI driver has fetched: H = Q^T [cal A Q | cal E Q | R | U | B]
+// for all m columns of the block's Q (m x (3m + 2nb)), R of its QR (m x m).  The basis of the selection is the columns
+// of Q whose diagonal entry of R is at least RICADI_RADI_RANK_TOL of the largest one (a W of deficient rank -- the DRE
+// forms of the test problems: 8 columns, rank 4 -- makes every block of Z as deficient, and the other columns of Q are
+// then arbitrary directions): the rows of H of those columns, and their columns in the two projected operators.  The
+// tolerance is not rounding level: the block's columns come from iterative solves, and columns that depend on their
+// predecessors do so only to the solves' accuracy (ricadi.h).
+// 0: *p_out / *margin_out hold the shift and its margin.  A RICADI_RADI_REFUSED_* value: the driver falls back to the
+// caller's list -- an entry of R that is not finite, R = 0, a breakdown of the selection, no candidate or a shift that
+// is not finite and negative.  *kept_out (may be NULL): the size of the basis, 0 where R itself is refused.
+int radi_next_shift(int m, int nb, const double* hH, const double* hR, double* p_out, double* margin_out,
+                    int* kept_out) {
+  const int hw = 3 * m + 2 * nb;
+  if (kept_out) *kept_out = 0;
+  double dmax = 0.0;
+  for (int i = 0; i < m; ++i) {
+    const double d = std::fabs(hR[(size_t)i * m + i]);
+    if (!(d <= std::numeric_limits<double>::max())) return RICADI_RADI_REFUSED_R_NOT_FINITE;
+    dmax = std::max(dmax, d);
+  }
+  if (dmax == 0.0) return RICADI_RADI_REFUSED_R_ZERO;
+  std::vector<int> keep;
+  for (int i = 0; i < m; ++i)
+    if (std::fabs(hR[(size_t)i * m + i]) >= RICADI_RADI_RANK_TOL * dmax) keep.push_back(i);
+  const int k = (int)keep.size(), kw = 2 * k + m + 2 * nb;
+  if (kept_out) *kept_out = k;
+  std::vector<double> Hk((size_t)k * kw);
+  for (int a = 0; a < k; ++a) {
+    const double* row = hH + (size_t)keep[a] * hw;
+    double* out = Hk.data() + (size_t)a * kw;
+    for (int b = 0; b < k; ++b) {
+      out[b] = row[keep[b]];
+      out[k + b] = row[m + keep[b]];
+    }
+    std::copy(row + 2 * m, row + hw, out + 2 * k);
+  }
+  double p = 0.0, margin = 0.0;
+  if (radi_shift_select(k, m, nb, Hk.data(), &p, &margin, nullptr, nullptr) != RICADI_OK)
+    return RICADI_RADI_REFUSED_BREAKDOWN;
+  if (!(p < 0.0) || !(p >= -std::numeric_limits<double>::max())) return RICADI_RADI_REFUSED_NO_SHIFT;
+  *p_out = p;
+  if (margin_out) *margin_out = margin;
+  return 0;
+}
+
 }  // namespace ricadi
 
 extern "C" {
@@ -1617,6 +1662,20 @@ int ricadi_host_radi_shift(int k, int m, int nb, const double* H, double* p_out,
 int ricadi_host_radi_shift_eigs(int k, int m, int nb, const double* H, double* p_out, double* margin_out,
                                 double* wr_out, double* wi_out) {
   return radi_shift_entry(k, m, nb, H, p_out, margin_out, wr_out, wi_out);
+}
+
+int ricadi_host_radi_next_shift(int m, int nb, const double* H, const double* R, double* p_out, double* margin_out,
+                                int* kept_out) {
+  if (m < 1 || m > 32 || nb < 1 || nb > 64 || !H || !R || !p_out) {
+    ricadi::set_error("ricadi_host_radi_next_shift: bad argument (1 <= m <= 32, 1 <= nb <= 64)");
+    return RICADI_EINVAL;
+  }
+  try {
+    return ricadi::radi_next_shift(m, nb, H, R, p_out, margin_out, kept_out);
+  } catch (const std::exception&) {
+    ricadi::set_error("ricadi_host_radi_next_shift: exception");
+    return RICADI_EHIP;
+  }
 }
 
 int ricadi_host_vanka_patches(int nv, int np, const int32_t* j_rp, const int32_t* j_ci, const double* j_v,

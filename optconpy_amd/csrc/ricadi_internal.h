@@ -583,6 +583,10 @@ void launch_radi_reduce(hipStream_t st, int nv, int k, int m, int nb, const int*
 // wi_out (2k each, may be NULL): all eigenvalues of the Hamiltonian.
 int radi_shift_select(int k, int m, int nb, const double* H, double* p_out, double* margin_out, double* wr_out,
                       double* wi_out);
+// The driver's use of it (ricadi_host.cpp; ricadi_host_radi_next_shift): the basis of the selection from the diagonal
+// of the block's R (m x m), H (m x (3m + 2nb)) restricted to it, radi_shift_select.  0 or a RICADI_RADI_REFUSED_*
+// value; *kept_out (may be NULL): the size of the basis.
+int radi_next_shift(int m, int nb, const double* H, const double* R, double* p_out, double* margin_out, int* kept_out);
 
 void set_error(const std::string& msg);
 

@@ -520,4 +520,28 @@ int ricadi_probe_cache_entries(ricadi_ctx* c, int* n_out) {
   return RICADI_OK;
 }
 
+// branches of the RADI driver (ric_radi_run): the steps after which the selection counts as refused, and what the
+// last call counted
+int ricadi_probe_radi_refuse(ricadi_ctx* c, const int* steps, int n) {
+  REQUIRE(c && n >= 0 && (steps || n == 0), RICADI_EINVAL, "bad argument");
+  for (int i = 0; i < n; ++i) REQUIRE(steps[i] >= 1, RICADI_EINVAL, "steps are counted from 1");
+  c->radi_refuse.assign(steps, steps + n);
+  return RICADI_OK;
+}
+int ricadi_probe_radi_counters(ricadi_ctx* c, int* out) {
+  REQUIRE(c && out, RICADI_EINVAL, "NULL argument");
+  REQUIRE(c->radi_ran, RICADI_ESTATE, "no RADI iteration has run on this context");
+  out[0] = c->radi_qr_repeats;
+  out[1] = c->radi_recompressions;
+  return RICADI_OK;
+}
+int ricadi_probe_radi_kept(ricadi_ctx* c, int* out, int cap, int* n_out) {
+  REQUIRE(c && n_out && cap >= 0 && (out || cap == 0), RICADI_EINVAL, "bad argument");
+  REQUIRE(c->radi_ran, RICADI_ESTATE, "no RADI iteration has run on this context");
+  const int n = (int)c->radi_kept_hist.size();
+  *n_out = n;
+  for (int i = 0; i < std::min(n, cap); ++i) out[i] = c->radi_kept_hist[i];
+  return RICADI_OK;
+}
+
 }  // extern "C"

@@ -99,43 +99,6 @@ static void radi_shift_issue(ricadi_ctx* c, RadiShiftWork& w, const double* dZbl
   launch_radi_reduce(st, nv, m, m, nb, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, w.Q.p, dRU, dB, w.part.p, w.H.p);
 }
 
-// The next shift from what a step has fetched: hH = Q^T [cal A Q | cal E Q | R | U | B] for all m columns
-// of the block's Q, hR = R of its QR.  The basis of the selection is the columns of Q whose diagonal entry of R is at
-// least 1e-12 of the largest one (a W of deficient rank -- the DRE forms of the test problems: 8 columns, rank 4 --
-// makes every block of Z as deficient, and the other columns of Q are then arbitrary directions): the rows of H of
-// those columns, and their columns in the two projected operators.  false: fall back to the caller's list -- an entry
-// that is not finite, a breakdown of the selection, no candidate, or a shift that is not finite and negative.
-static bool radi_next_shift(int m, int nb, const double* hH, const double* hR, double* p_out, double* margin_out) {
-  const int hw = 3 * m + 2 * nb;
-  double dmax = 0.0;
-  for (int i = 0; i < m; ++i) {
-    const double d = std::fabs(hR[(size_t)i * m + i]);
-    if (!(d <= std::numeric_limits<double>::max())) return false;
-    dmax = std::max(dmax, d);
-  }
-  if (dmax == 0.0) return false;
-  std::vector<int> keep;
-  for (int i = 0; i < m; ++i)
-    if (std::fabs(hR[(size_t)i * m + i]) >= 1e-12 * dmax) keep.push_back(i);
-  const int k = (int)keep.size(), kw = 2 * k + m + 2 * nb;
-  std::vector<double> Hk((size_t)k * kw);
-  for (int a = 0; a < k; ++a) {
-    const double* row = hH + (size_t)keep[a] * hw;
-    double* out = Hk.data() + (size_t)a * kw;
-    for (int b = 0; b < k; ++b) {
-      out[b] = row[keep[b]];
-      out[k + b] = row[m + keep[b]];
-    }
-    std::copy(row + 2 * m, row + hw, out + 2 * k);
-  }
-  double p = 0.0, margin = 0.0;
-  if (ricadi::radi_shift_select(k, m, nb, Hk.data(), &p, &margin, nullptr, nullptr) != RICADI_OK) return false;
-  if (!(p < 0.0) || !(p >= -std::numeric_limits<double>::max())) return false;
-  *p_out = p;
-  *margin_out = margin;
-  return true;
-}
-
 // The dense part of one step on device operands: G = V^T B, the coefficient matrix C, the fused update of [R | U]
 // and the block of Z (ricadi_radi.hip).  dG (m x nb), dC (m x (2m + nb)), dPart (radi_vtb_partial_len) and the flag
 // word are the caller's; the word is cleared here and raised by the factorisation kernel.
@@ -165,7 +128,7 @@ static void radi_dense_step(ricadi_ctx* c, double p, const double* dV, int ldv, 
 // shifts[0] and generates every later shift from the iteration: right after the residual Gram launch the QR of the new
 // block of Z and the reduction kernel are issued -- speculatively, once too often at the end --, H and R are fetched
 // with the Gram matrix and the flag words in the step's ONE synchronisation, and the host selects the shift after the
-// stop test (radi_next_shift); `shifts` is the fallback cycle, with a counter of its own.
+// stop test (ricadi::radi_next_shift, ricadi_host.cpp); `shifts` is the fallback cycle, with a counter of its own.
 static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const double* dB, int nb, const double* dW,
                               int mw, const double* dOld, int max_steps, double res_reltol, int compress_cols,
                               bool project_w, bool verbose, double* dK_out) {
@@ -190,6 +153,9 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
   const int hw = 3 * m + 2 * nb;                      // columns of H
   c->radi_shift_hist.clear();
   c->radi_fallbacks = 0;
+  c->radi_kept_hist.clear();
+  c->radi_qr_repeats = 0;
+  c->radi_recompressions = 0;
   c->radi_ran = true;
   // per-shift data of the whole cycle (and of the projection) up front, as lyap_adi_dev; with generated shifts the
   // first shift only
@@ -314,8 +280,12 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
         HIPCHK(hipMemcpyAsync(hH, sw.H.p, sizeof(double) * m * hw, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(hR, sw.Rq.p, sizeof(double) * mm, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+        ++c->radi_qr_repeats;
       }
-      fell_back = !radi_next_shift(m, nb, hH, hR, &p_next, &margin);
+      int kept = 0;
+      fell_back = ricadi::radi_next_shift(m, nb, hH, hR, &p_next, &margin, &kept) != 0 ||
+                  std::find(c->radi_refuse.begin(), c->radi_refuse.end(), step) != c->radi_refuse.end();
+      c->radi_kept_hist.push_back(kept);
       if (fell_back) {
         p_next = shifts[nfb++ % ns];
         ++c->radi_fallbacks;
@@ -324,6 +294,7 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
     }
     if (step < max_steps && c->zc - zc_last >= compress_cols) {
       factor_recompress(c);
+      ++c->radi_recompressions;
       zc_last = c->zc;
     }
   }

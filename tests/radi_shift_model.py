@@ -1,10 +1,10 @@
 """Model of RADI with shifts generated from the iteration itself ("residual Hamiltonian shifts": Benner, Bujanovic,
 Kuerschner, Saak, Numer. Math. 2018, section 4.5): tests/radi_model.radi plus the selection rule, with
-NumPy's ``eig`` and ``qr``.
+NumPy's eigenvalues and ``qr`` (the eigenvectors of the candidates are extended-precision null vectors: ``select``).
 
 After a step the iteration holds the residual factor R, U (gain so far minus ``old``), B and the new block of Z.  With
 Q an orthonormal basis of that block (k <= m columns, all in ker J, so the pressure drops out of every projection; from
-the block's QR, leaving out the columns whose diagonal entry of R is below 1e-12 of the largest one: the ``dre`` call
+the block's QR, leaving out the columns whose diagonal entry of R is below 3e-8 of the largest one: the ``dre`` call
 forms have a W of 8 columns and rank 4, and so has every block of their Z)
 
     H_A = Q^T cal A Q,  H_E = Q^T cal E Q,  H_R = Q^T R,  H_U = Q^T U,  H_B = Q^T B
@@ -21,7 +21,7 @@ import numpy as np
 import dense_model as dm
 import radi_model as rm
 
-RANK_TOL = 1e-12
+RANK_TOL = 3e-8       # RICADI_RADI_RANK_TOL: above the accuracy of the device's iterative solves, far below any independent column
 
 
 def pack(Q, calA, calE, R, U, B):
@@ -76,14 +76,49 @@ def hamiltonian(k, m, nb, H):
     return np.block([[At.T, -HB @ HB.T], [-Rt @ Rt.T, -At]])
 
 
+def null_vector(M):
+    """The null vector of a numerically singular square matrix: Gaussian elimination with complete pivoting in extended
+    precision (complex longdouble), the last pivot taken as zero, back substitution."""
+    A = np.array(M, dtype=np.clongdouble)
+    n = A.shape[0]
+    cols = np.arange(n)
+    for c in range(n - 1):
+        sub = np.abs(A[c:, c:])
+        i, j = np.unravel_index(np.argmax(sub), sub.shape)
+        i, j = i + c, j + c
+        A[[c, i]] = A[[i, c]]
+        A[:, [c, j]] = A[:, [j, c]]
+        cols[[c, j]] = cols[[j, c]]
+        if A[c, c] == 0:
+            break
+        A[c + 1:, c:] -= np.outer(A[c + 1:, c] / A[c, c], A[c, c:])
+    y = np.zeros(n, dtype=np.clongdouble)
+    y[n - 1] = 1
+    for r in range(n - 2, -1, -1):
+        y[r] = -(A[r, r + 1:] @ y[r + 1:]) / A[r, r] if A[r, r] != 0 else 0
+    x = np.zeros(n, dtype=np.clongdouble)
+    x[cols] = y
+    return x
+
+
 def select(k, m, nb, H):
     """(p, margin, eigenvalues of Ham, criterion values sorted descending): the rule on a packed H.  p = 0.0 without
-    a candidate."""
-    lam, X = np.linalg.eig(hamiltonian(k, m, nb, H))
+    a candidate.  The eigenvalues are LAPACK's; the eigenvector of a candidate is the null vector of Ham - lambda I
+    in extended precision, not LAPACK's: late in an iteration R~ R~^T is tiny against the other blocks of Ham, the lower
+    half q of an eigenvector with it, and ``eig`` returns it to an ABSOLUTE accuracy of the rounding unit -- criterion
+    values wrong by up to 2.8e-7 (relative) on the N = 8 test runs, against an eigendecomposition in 50 digits that
+    the null vectors reproduce within 1e-14."""
+    Ham = hamiltonian(k, m, nb, H)
+    lam = np.linalg.eigvals(Ham)
     cands = [i for i in range(lam.size) if lam[i].real < 0 and lam[i].imag >= 0]      # (LAPACK pairs are exact conjugates)
     if not cands:
         return 0.0, np.inf, lam, np.zeros(0)
-    crit = np.array([np.linalg.norm(X[k:, i]) / np.linalg.norm(X[:, i]) for i in cands])
+    HamL = np.asarray(Ham, dtype=np.longdouble)
+    crit = []
+    for i in cands:
+        x = null_vector(HamL - np.clongdouble(lam[i]) * np.eye(2 * k, dtype=np.longdouble))
+        crit.append(float(np.sqrt(np.sum(np.abs(x[k:]) ** 2) / np.sum(np.abs(x) ** 2))))
+    crit = np.array(crit)
     order = np.argsort(-crit)
     best = cands[order[0]]
     margin = np.inf if len(cands) == 1 else crit[order[0]] / max(crit[order[1]], 1e-300)
@@ -98,10 +133,16 @@ def initial_shift(calA, calE):
     return adi_shifts.initial_shift(np.abs(da[ok] / de[ok]))
 
 
-def radi(calA, calE, J, B, W, fallback, old=None, max_steps=200, res_reltol=1e-10, record=None):
+def radi(calA, calE, J, B, W, fallback, old=None, max_steps=200, res_reltol=1e-10, record=None, refuse=(),
+         record_full=None):
     """radi_model.radi with generated shifts: fallback[0] is the first shift, the list the fallback cycle.  Returns
-    the dict of radi_model.radi plus ms (the shift of every step), margins (of every selection made), fallbacks.
-    record (a list): every packed (k, m, nb, H) the run produces is appended."""
+    the dict of radi_model.radi plus ms (the shift of every step), margins (of every selection whose shift was used),
+    fallbacks, kept (the basis size of every selection the driver makes: none after step max_steps).
+    record (a list): every packed (k, m, nb, H) the run produces is appended.
+    record_full (a list): (m, nb, H, Rq) with the packed H of ALL m columns of the block's Q (m x (3m + 2nb)) and the
+    R of its QR -- what the device fetches; keep_columns, restrict and select turn it into the shift.
+    refuse: the selection after each of these steps (1-based) counts as refused -- it is still made and recorded, and
+    the next step takes the next entry of the list (ricadi_probe_radi_refuse)."""
     calA, calE, J = rm._dn(calA), rm._dn(calE), rm._dn(J)
     B, W = rm._dn(B), rm._dn(W)
     nv, m = W.shape
@@ -109,7 +150,8 @@ def radi(calA, calE, J, B, W, fallback, old=None, max_steps=200, res_reltol=1e-1
     R = rm.project(calE, J, W)
     U = np.zeros_like(B) if old is None else -rm._dn(old)
     rhs = np.linalg.norm(R.T @ R)
-    blocks, hist, ms, margins, stopped = [], [], [], [], "max_steps"
+    blocks, hist, ms, margins, kept, stopped = [], [], [], [], [], "max_steps"
+    refuse = set(int(v) for v in refuse)
     p, nfb, fallbacks = float(fallback[0]), 1, 0
     for j in range(max_steps):
         ms.append(p)
@@ -131,8 +173,12 @@ def radi(calA, calE, J, B, W, fallback, old=None, max_steps=200, res_reltol=1e-1
         H = pack(Q[:, keep], calA, calE, R, U, B)
         if record is not None:
             record.append((k, m, nb, H.copy()))
+        if record_full is not None:
+            record_full.append((m, nb, pack(Q, calA, calE, R, U, B), Rq.copy()))
+        if j + 1 < max_steps:
+            kept.append(k)
         pn, margin, _, _ = select(k, m, nb, H)
-        if not (np.isfinite(pn) and pn < 0.0):
+        if not (np.isfinite(pn) and pn < 0.0) or (j + 1) in refuse:
             pn = float(fallback[nfb % len(fallback)])
             nfb += 1
             fallbacks += 1
@@ -141,7 +187,8 @@ def radi(calA, calE, J, B, W, fallback, old=None, max_steps=200, res_reltol=1e-1
         p = float(pn)
     Z = np.hstack(blocks)
     return dict(Z=Z, gain=U if old is None else U + rm._dn(old), res_hist=np.array(hist), steps=len(hist),
-                stopped=stopped, rhs=rhs, ms=np.array(ms), margins=np.array(margins), fallbacks=fallbacks)
+                stopped=stopped, rhs=rhs, ms=np.array(ms), margins=np.array(margins), fallbacks=fallbacks,
+                kept=np.array(kept, dtype=int))
 
 
 def random_instance(k, m, nb, seed):

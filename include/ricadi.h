@@ -426,10 +426,19 @@ int ricadi_ric_radi_dev(ricadi_ctx* ctx, const double* shifts, int nshifts, cons
  *     is set up in advance; a generated shift's per-shift data are rebuilt in ONE entry the context owns and never
  *     enter the per-shift cache: after the call the cache holds what it held before plus the entries of the list that
  *     were used.
- * RICADI_EINVAL for another mode.                                                                                   */
+ *   RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT  the same rule on another basis: with Q R the QR of the
+ *     new block, the basis is Q S, S (mw x k) the left singular vectors of R of its k = min(32, #{sigma_i >=
+ *     RICADI_RADI_RANK_TOL sigma_1}) largest singular values -- the dominant part of the block's range, whatever the
+ *     order of its columns.  The selection stays of order 2k <= 64 for any width: accepted for 1 <= mw <= 127,
+ *     nb <= 64 (and mw + nb <= 128), RADI's own limits.  Everything else -- first shift, fallback list, cache -- as HAMILTONIAN.
+ * ricadi_set_radi_shifts takes CYCLE and HAMILTONIAN and returns RICADI_EINVAL for every other value, as it did before
+ * the third mode existed (callers and tests rely on that refusal); ricadi_set_radi_shift_mode (ABI 410) is the same
+ * setting and takes all three, RICADI_EINVAL for another value.                                                      */
 #define RICADI_RADI_SHIFTS_CYCLE 0
 #define RICADI_RADI_SHIFTS_HAMILTONIAN 1
+#define RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT 2
 int ricadi_set_radi_shifts(ricadi_ctx* ctx, int mode);
+int ricadi_set_radi_shift_mode(ricadi_ctx* ctx, int mode);
 /* The shift of every step of the most recent ricadi_ric_radi(_dev) call of the context, in either mode: *n_out = steps
  * started (one more than the steps completed when the call ended by a breakdown); at most `cap` entries are copied to
  * `out` (may be NULL with cap = 0).  RICADI_ESTATE before any RADI call.                                             */
@@ -444,6 +453,10 @@ int ricadi_radi_shift_fallbacks(ricadi_ctx* ctx, int* n_out);
  * 1 <= k <= 32, 1 <= m <= 32, 1 <= nb <= 64 (the driver calls it with k = m).                                         */
 int ricadi_radi_reduce_dev(ricadi_ctx* ctx, const double* dQ, int k, const double* dRU, int m, const double* dB,
                            int nb, double* dH_out);
+/* The same for a wide block, on the kernel RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT uses above 32 columns: k = m,
+ * 33 <= m <= 127, 1 <= nb <= 64; dH_out m x (3m + 2nb).  Bitwise the same on a second call.                          */
+int ricadi_radi_reduce_wide_dev(ricadi_ctx* ctx, const double* dQ, int k, const double* dRU, int m, const double* dB,
+                                int nb, double* dH_out);
 /* Entries of the per-shift cache, summed over the levels of the preconditioner hierarchy, for tests.               */
 int ricadi_probe_cache_entries(ricadi_ctx* ctx, int* n_out);
 /* Branches of the RADI driver, for tests.
@@ -882,6 +895,14 @@ int ricadi_host_radi_shift_eigs(int k, int m, int nb, const double* H, double* p
 #define RICADI_RADI_REFUSED_NO_SHIFT 4       /* no candidate, or a shift that is not finite and negative          */
 int ricadi_host_radi_next_shift(int m, int nb, const double* H, const double* R, double* p_out, double* margin_out,
                                 int* kept_out);
+/* The same under RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT: the basis is Q S, S (m x k) the left singular vectors of R
+ * of its k = min(32, #{sigma_i >= RICADI_RADI_RANK_TOL sigma_1}) largest singular values, from a one-sided Jacobi
+ * iteration on R itself (singular values resolved far below the tolerance; nothing squares the condition).  H is
+ * turned into [S^T H_A S | S^T H_E S | S^T (H_R, H_U, H_B)] (k x (2k + m + 2nb)) and handed to the same selection.
+ * *kept_out = k.  The refusals are the four values above, with EVERY entry of R looked at in place of its diagonal
+ * (R = 0: no singular value is positive).  RICADI_EINVAL unless 1 <= m <= 127, 1 <= nb <= 64.                         */
+int ricadi_host_radi_next_shift_dominant(int m, int nb, const double* H, const double* R, double* p_out,
+                                         double* margin_out, int* kept_out);
 
 #ifdef __cplusplus
 }

@@ -19,10 +19,11 @@ RICADI_OK = 0
 RICADI_ENOCONV = -3
 RICADI_STOP_MAX_STEPS, RICADI_STOP_NEWZ, RICADI_STOP_RES = 0, 1, 2      # ricadi_adi_stop_rule (include/ricadi.h)
 RICADI_RADI_SHIFTS_CYCLE, RICADI_RADI_SHIFTS_HAMILTONIAN = 0, 1          # ricadi_set_radi_shifts
+RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT = 2
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 409
+ABI_VERSION = 410
 
 
 class RicadiOpts(C.Structure):
@@ -95,9 +96,11 @@ SIGNATURES = {
     "ricadi_radi_update_dev": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int,
                                          C.c_int, _vp, _vp]),
     "ricadi_set_radi_shifts": (C.c_int, [_vp, C.c_int]),
+    "ricadi_set_radi_shift_mode": (C.c_int, [_vp, C.c_int]),
     "ricadi_radi_shift_history": (C.c_int, [_vp, _dp, C.c_int, C.POINTER(C.c_int)]),
     "ricadi_radi_shift_fallbacks": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "ricadi_radi_reduce_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
+    "ricadi_radi_reduce_wide_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
     "ricadi_probe_cache_entries": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "ricadi_probe_radi_refuse": (C.c_int, [_vp, _ip, C.c_int]),
     "ricadi_probe_radi_counters": (C.c_int, [_vp, _ip]),
@@ -165,6 +168,8 @@ SIGNATURES = {
                                               C.POINTER(C.c_double), _dp, _dp]),
     "ricadi_host_radi_next_shift": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "ricadi_host_radi_next_shift_dominant": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_double),
+                                                       C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _vp, C.c_int64)
@@ -714,15 +719,17 @@ class Context:
         _warn_nonconverged(info)
         return Zt, Kt, info
 
-    RADI_SHIFT_MODES = {"cycle": RICADI_RADI_SHIFTS_CYCLE, "hamiltonian": RICADI_RADI_SHIFTS_HAMILTONIAN}
+    RADI_SHIFT_MODES = {"cycle": RICADI_RADI_SHIFTS_CYCLE, "hamiltonian": RICADI_RADI_SHIFTS_HAMILTONIAN,
+                        "hamiltonian-dominant": RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT}
 
     def set_radi_shifts(self, mode):
-        """``ricadi_set_radi_shifts``: ``'cycle'`` (default; the list is cycled) or ``'hamiltonian'`` (the list's first
-        entry starts, every later shift is generated from the iteration, the list is the fallback).  A context
-        setting, like :meth:`set_recycle`.  Returns the mode that was in force."""
+        """``ricadi_set_radi_shift_mode``: ``'cycle'`` (default; the list is cycled), ``'hamiltonian'`` (the list's
+        first entry starts, every later shift is generated from the iteration, the list is the fallback) or
+        ``'hamiltonian-dominant'`` (the same on the at most 32 dominant directions of the new block: any width).  A
+        context setting, like :meth:`set_recycle`.  Returns the mode that was in force."""
         new = self.RADI_SHIFT_MODES[mode] if isinstance(mode, str) else int(mode)
         old = getattr(self, "_radi_shift_mode", RICADI_RADI_SHIFTS_CYCLE)
-        _chk(self._lib.ricadi_set_radi_shifts(self._h, new))
+        _chk(self._lib.ricadi_set_radi_shift_mode(self._h, new))
         self._radi_shift_mode = new
         return old
 
@@ -769,6 +776,10 @@ class Context:
     def radi_reduce_dev(self, q_ptr, k, ru_ptr, m, b_ptr, nb, h_ptr):
         """``ricadi_radi_reduce_dev``: H = Q^T [cal A Q | cal E Q | R | U | B] on device pointers (tests)."""
         _chk(self._lib.ricadi_radi_reduce_dev(self._h, q_ptr, int(k), ru_ptr, int(m), b_ptr, int(nb), h_ptr))
+
+    def radi_reduce_wide_dev(self, q_ptr, k, ru_ptr, m, b_ptr, nb, h_ptr):
+        """``ricadi_radi_reduce_wide_dev``: the same on the wide kernel, k = m in 33 .. 127 (tests)."""
+        _chk(self._lib.ricadi_radi_reduce_wide_dev(self._h, q_ptr, int(k), ru_ptr, int(m), b_ptr, int(nb), h_ptr))
 
     def radi_update_dev(self, p, v_ptr, ldv, m, b_ptr, nb, ru_ptr, z_ptr, ldz, zoff, g_ptr, c_ptr=None):
         """``ricadi_radi_update_dev``: the dense part of one RADI step on device pointers (tests)."""
@@ -1209,19 +1220,21 @@ def host_radi_shift(k, m, nb, H, eigs=False):
 RADI_REFUSALS = {1: "r_not_finite", 2: "r_zero", 3: "breakdown", 4: "no_shift"}      # RICADI_RADI_REFUSED_*
 
 
-def host_radi_next_shift(m, nb, H, R):
+def host_radi_next_shift(m, nb, H, R, dominant=False):
     """``ricadi_host_radi_next_shift``: what the RADI driver does with what a step has fetched -- H = Q^T [cal A Q |
     cal E Q | R | U | B] for all m columns of the block's Q (m x (3m + 2nb)) and R of its QR (m x m); host only.
     Returns ``(p, margin, kept, refusal)``: ``refusal`` is None and p, margin are set, or it is one of
     ``RADI_REFUSALS``' names and p, margin are None (the driver then falls back to its list).  ``kept``: the size of the
-    basis of the selection.  ValueError for bad sizes."""
+    basis of the selection.  ValueError for bad sizes.  ``dominant``: ``ricadi_host_radi_next_shift_dominant`` -- the
+    basis is the at most 32 dominant left singular directions of R (m <= 127)."""
     H = np.ascontiguousarray(H, dtype=np.float64)
     R = np.ascontiguousarray(R, dtype=np.float64)
     m, nb = int(m), int(nb)
     if min(m, nb) >= 1 and (H.size != m * (3 * m + 2 * nb) or R.size != m * m):
         raise ValueError("H must be m x (3m + 2nb) and R m x m")
     p, mg, kept = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
-    rc = load().ricadi_host_radi_next_shift(m, nb, _d(H), _d(R), C.byref(p), C.byref(mg), C.byref(kept))
+    fn = load().ricadi_host_radi_next_shift_dominant if dominant else load().ricadi_host_radi_next_shift
+    rc = fn(m, nb, _d(H), _d(R), C.byref(p), C.byref(mg), C.byref(kept))
     if rc < 0:
         _chk(rc)
     if rc > 0:

@@ -1306,7 +1306,10 @@ static void hessenberg(int n, std::vector<double>& a) {
 
 // Eigenvalues of an upper Hessenberg matrix (destroyed) by the double-shift QR iteration; conjugate pairs come out as
 // exact conjugates, real eigenvalues with wi = 0.  false: 60 iterations on one eigenvalue did not converge.
-static bool hqr_eigenvalues(int n, std::vector<double>& h, double* wr, double* wi) {
+// patient: the second attempt radi_shift_select makes on a fresh copy where the first has failed (Hamiltonians of order
+// 64 from wide blocks: met on the N = 8 model runs of tests/radi_dominant_model.py) -- an exceptional shift every ten
+// iterations and up to 300 of them; the first attempt and its results are as they always were.
+static bool hqr_eigenvalues(int n, std::vector<double>& h, double* wr, double* wi, bool patient = false) {
   const double eps = 2.220446049250313e-16;
   auto A = [&](int i, int j) -> double& { return h[(size_t)i * n + j]; };
   double anorm = 0.0;
@@ -1350,8 +1353,8 @@ static bool hqr_eigenvalues(int n, std::vector<double>& h, double* wr, double* w
           }
           nn -= 2;
         } else {
-          if (its == 60) return false;
-          if (its == 10 || its == 20) {    // exceptional shift
+          if (its == (patient ? 300 : 60)) return false;
+          if (its == 10 || its == 20 || (patient && its > 20 && its % 10 == 0)) {    // exceptional shift
             t += x;
             for (int i = 0; i <= nn; ++i) A(i, i) -= x;
             s = std::fabs(A(nn, nn - 1)) + std::fabs(A(nn - 1, nn - 2));
@@ -1558,7 +1561,14 @@ int radi_shift_select(int k, int m, int nb, const double* H, double* p_out, doub
   std::vector<double> h = ham, wr(n), wi(n);
   balance_scale(n, h);
   hessenberg(n, h);
-  if (!hqr_eigenvalues(n, h, wr.data(), wi.data())) {
+  bool converged = hqr_eigenvalues(n, h, wr.data(), wi.data());
+  if (!converged) {
+    h = ham;
+    balance_scale(n, h);
+    hessenberg(n, h);
+    converged = hqr_eigenvalues(n, h, wr.data(), wi.data(), true);
+  }
+  if (!converged) {
     set_error("ricadi_host_radi_shift: the QR iteration did not converge");
     return RICADI_EBREAKDOWN;
   }
@@ -1637,6 +1647,111 @@ int radi_next_shift(int m, int nb, const double* hH, const double* hR, double* p
   return 0;
 }
 
+// Singular values and left singular vectors of R (m x m, row-major) by one-sided (Hestenes) Jacobi: plane rotations
+// from the right make the columns of A = R mutually orthogonal, A V = U Sigma; their norms are the singular values,
+// the normalised columns the left singular vectors.  The method works on R itself -- an eigensolver on R R^T would
+// square the condition and lose every singular value below 1e-8 of the largest, where RICADI_RADI_RANK_TOL cuts.
+// Sweeps over all pairs in a fixed order until no pair's cosine exceeds 1e-15 sqrt(m), the rounding error of the
+// cosine itself (at most 60 sweeps).  A: the rotated
+// matrix, COLUMN by column (A[j m + i] = entry (i, j)); sig: the column norms.
+static void jacobi_left_svd(int m, const double* R, std::vector<double>& A, std::vector<double>& sig) {
+  A.resize((size_t)m * m);
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < m; ++j) A[(size_t)j * m + i] = R[(size_t)i * m + j];
+  const double tol = 1e-15 * std::sqrt((double)m);
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    bool rotated = false;
+    for (int p = 0; p < m - 1; ++p)
+      for (int q = p + 1; q < m; ++q) {
+        double* ap = A.data() + (size_t)p * m;
+        double* aq = A.data() + (size_t)q * m;
+        double a = 0.0, b = 0.0, g = 0.0;
+        for (int i = 0; i < m; ++i) {
+          a += ap[i] * ap[i];
+          b += aq[i] * aq[i];
+          g += ap[i] * aq[i];
+        }
+        if (g == 0.0 || !(std::fabs(g) > tol * std::sqrt(a) * std::sqrt(b))) continue;
+        rotated = true;
+        const double zeta = (b - a) / (2.0 * g);
+        const double t = std::copysign(1.0, zeta) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+        const double cs = 1.0 / std::sqrt(1.0 + t * t), sn = cs * t;
+        for (int i = 0; i < m; ++i) {
+          const double x = ap[i], y = aq[i];
+          ap[i] = cs * x - sn * y;
+          aq[i] = sn * x + cs * y;
+        }
+      }
+    if (!rotated) break;
+  }
+  sig.resize(m);
+  for (int j = 0; j < m; ++j) {
+    double s = 0.0;
+    for (int i = 0; i < m; ++i) s += A[(size_t)j * m + i] * A[(size_t)j * m + i];
+    sig[j] = std::sqrt(s);
+  }
+}
+
+// radi_next_shift with the basis Q S in place of a choice of columns of Q (RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT;
+// DESIGN.md 3d-2): S (m x k) holds the left singular vectors of R of its k = min(32, #{sigma_i >= RICADI_RADI_RANK_TOL
+// sigma_1}) largest singular values, so Q S spans the dominant part of the block's range whatever the order of its
+// columns, and a block of up to 127 columns leaves a selection of order 2k <= 64.  The packed matrix handed to
+// radi_shift_select is  [S^T H_A S | S^T H_E S | S^T (H_R, H_U, H_B)]  (k x (2k + m + 2nb)).
+// Return values and *kept_out as radi_next_shift; here EVERY entry of R is looked at, not only its diagonal.
+int radi_next_shift_dominant(int m, int nb, const double* hH, const double* hR, double* p_out, double* margin_out,
+                             int* kept_out) {
+  const int hw = 3 * m + 2 * nb;
+  if (kept_out) *kept_out = 0;
+  for (int i = 0; i < m * m; ++i)
+    if (!(std::fabs(hR[i]) <= std::numeric_limits<double>::max())) return RICADI_RADI_REFUSED_R_NOT_FINITE;
+  std::vector<double> A, sig;
+  jacobi_left_svd(m, hR, A, sig);
+  std::vector<int> order(m);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sig[a] > sig[b]; });
+  const double smax = sig[order[0]];
+  if (!(smax <= std::numeric_limits<double>::max())) return RICADI_RADI_REFUSED_R_NOT_FINITE;
+  if (smax == 0.0) return RICADI_RADI_REFUSED_R_ZERO;
+  int k = 0;
+  while (k < m && k < 32 && sig[order[k]] >= RICADI_RADI_RANK_TOL * smax) ++k;
+  if (kept_out) *kept_out = k;
+  // S by columns: S[a] = column order[a] of A over its norm
+  std::vector<double> S((size_t)k * m);
+  for (int a = 0; a < k; ++a)
+    for (int i = 0; i < m; ++i) S[(size_t)a * m + i] = A[(size_t)order[a] * m + i] / sig[order[a]];
+  // T = S^T H (k x hw), then the two projected operators once more from the right
+  const int kw = 2 * k + m + 2 * nb;
+  std::vector<double> T((size_t)k * hw, 0.0), Hk((size_t)k * kw);
+  for (int a = 0; a < k; ++a)
+    for (int i = 0; i < m; ++i) {
+      const double s = S[(size_t)a * m + i];
+      const double* row = hH + (size_t)i * hw;
+      double* out = T.data() + (size_t)a * hw;
+      for (int j = 0; j < hw; ++j) out[j] += s * row[j];
+    }
+  for (int a = 0; a < k; ++a) {
+    const double* t = T.data() + (size_t)a * hw;
+    double* out = Hk.data() + (size_t)a * kw;
+    for (int b = 0; b < k; ++b) {
+      double sa = 0.0, se = 0.0;
+      for (int j = 0; j < m; ++j) {
+        sa += t[j] * S[(size_t)b * m + j];
+        se += t[m + j] * S[(size_t)b * m + j];
+      }
+      out[b] = sa;
+      out[k + b] = se;
+    }
+    std::copy(t + 2 * m, t + hw, out + 2 * k);
+  }
+  double p = 0.0, margin = 0.0;
+  if (radi_shift_select(k, m, nb, Hk.data(), &p, &margin, nullptr, nullptr) != RICADI_OK)
+    return RICADI_RADI_REFUSED_BREAKDOWN;
+  if (!(p < 0.0) || !(p >= -std::numeric_limits<double>::max())) return RICADI_RADI_REFUSED_NO_SHIFT;
+  *p_out = p;
+  if (margin_out) *margin_out = margin;
+  return 0;
+}
+
 }  // namespace ricadi
 
 extern "C" {
@@ -1674,6 +1789,20 @@ int ricadi_host_radi_next_shift(int m, int nb, const double* H, const double* R,
     return ricadi::radi_next_shift(m, nb, H, R, p_out, margin_out, kept_out);
   } catch (const std::exception&) {
     ricadi::set_error("ricadi_host_radi_next_shift: exception");
+    return RICADI_EHIP;
+  }
+}
+
+int ricadi_host_radi_next_shift_dominant(int m, int nb, const double* H, const double* R, double* p_out,
+                                         double* margin_out, int* kept_out) {
+  if (m < 1 || m > 127 || nb < 1 || nb > 64 || !H || !R || !p_out) {
+    ricadi::set_error("ricadi_host_radi_next_shift_dominant: bad argument (1 <= m <= 127, 1 <= nb <= 64)");
+    return RICADI_EINVAL;
+  }
+  try {
+    return ricadi::radi_next_shift_dominant(m, nb, H, R, p_out, margin_out, kept_out);
+  } catch (const std::exception&) {
+    ricadi::set_error("ricadi_host_radi_next_shift_dominant: exception");
     return RICADI_EHIP;
   }
 }

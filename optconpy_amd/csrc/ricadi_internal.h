@@ -574,7 +574,8 @@ void launch_radi_update(hipStream_t st, int nv, int m, int nb, const int* rp, co
                         const double* V, int ldv, const double* C, double* RU, double* Z, int zld, int zc);
 // reduce: H (k x (2k + m + 2nb), row-major) = Q^T [cal A Q | cal E Q | R | U | B] for the shift selection: Q nv x k
 // (ld k), RU = [R | U] nv x (m + nb), B nv x nb; rp / ci / vA / vE the saddle pattern with its two value sources (rows
-// and columns below nv); 1 <= k, m <= 32, 1 <= nb <= 64; sums in a fixed order (`partial`: radi_reduce_partial_len).
+// and columns below nv); 1 <= nb <= 64; sums in a fixed order (`partial`: radi_reduce_partial_len).  1 <= k, m <= 32:
+// radi_reduce_kernel; 33 <= k = m <= 127: radi_reduce_wide_kernel (output tiles on the FP64 matrix cores).
 size_t radi_reduce_partial_len(int nv, int k, int m, int nb);
 void launch_radi_reduce(hipStream_t st, int nv, int k, int m, int nb, const int* rp, const int* ci, const double* vA,
                         const double* vE, const double* Q, const double* RU, const double* B, double* partial,
@@ -587,6 +588,10 @@ int radi_shift_select(int k, int m, int nb, const double* H, double* p_out, doub
 // of the block's R (m x m), H (m x (3m + 2nb)) restricted to it, radi_shift_select.  0 or a RICADI_RADI_REFUSED_*
 // value; *kept_out (may be NULL): the size of the basis.
 int radi_next_shift(int m, int nb, const double* H, const double* R, double* p_out, double* margin_out, int* kept_out);
+// The same with the dominant left singular directions of R as the basis (m <= 127, at most 32 kept;
+// ricadi_host_radi_next_shift_dominant).
+int radi_next_shift_dominant(int m, int nb, const double* H, const double* R, double* p_out, double* margin_out,
+                             int* kept_out);
 
 void set_error(const std::string& msg);
 

@@ -13,9 +13,12 @@
 // With shifts generated from the iteration (ricadi_set_radi_shifts) a step also needs
 //   radi_reduce_kernel                         H = Q^T [cal A Q | cal E Q | R | U | B] for an orthonormal basis Q of the
 //                                              new block of Z: one pass over the rows of cal A and cal E, one partial
-//                                              per row slice, the slices summed by radi_vtb_reduce_kernel.
+//                                              per row slice, the slices summed by radi_vtb_reduce_kernel;
+//   radi_reduce_wide_kernel                    the same for blocks of 33 .. 127 columns: the
+//                                              output tiled over workgroups, on the FP64 matrix cores.
 // FP64 throughout, no atomics, every sum in a fixed order: the same inputs give bitwise the same outputs.
 #include "ricadi_internal.h"
+#include "ricadi_device.h"
 
 namespace ricadi {
 
@@ -307,14 +310,141 @@ static int radi_reduce_slices(int n, int& rows_per_slice) {
   rows_per_slice = RADI_HB * (((n + want - 1) / want + RADI_HB - 1) / RADI_HB);
   return (n + rows_per_slice - 1) / rows_per_slice;
 }
+// ---- the same for a wide block: 33 <= k = m <= 127, W = 3m + 2nb <= 509 ---------------------------------------------
+// k W <= 64 643 outputs are too many for per-thread accumulators, so the output is tiled over workgroups:
+// grid = (row slices, column tiles).  A column tile holds RADI_WCT = 64 columns of Y = [cal A Q | cal E Q | R | U | B]
+// and all k rows of H:
+//   tile t < ngt = ceil(k / 32) ("gather tile"):  columns [32t, 32t + 32) of cal A Q AND of cal E Q, so that one walk
+//       over a sparse row and ONE gather of Q serve both, as in the narrow kernel; every entry of the two products is
+//       formed once -- no gather is repeated across tiles, only the row's index / value stream is read by each of
+//       the ngt gather tiles (2 at m = 58, 4 at m = 127);
+//   tile t >= ngt ("dense tile"):  columns [64 (t - ngt), ..) of [R | U | B]: plain copies, no gather.
+// Per chunk of RADI_WB = 16 rows a workgroup puts its own rows of Q (16 x k, zero-padded to a multiple of 16 columns)
+// and the tile's rows of Y (16 x 64) into LDS; wave w owns the tile's columns [16w, 16w + 16) and all ceil(k / 16) <= 8
+// row tiles of H: Q_chunk^T Y_chunk on v_mfma_f64_16x16x4_f64, four instructions of depth 4 per row tile and chunk,
+// the chunks of the slice in row order.  One partial per row slice, the slices summed in slice order by
+// radi_vtb_reduce_kernel: no atomics, every sum in a fixed order.
+// LDS (static): 16 x 144 + 16 x 80 doubles = 28 KB (leading dimensions = 16 mod 32 doubles: the four rows a wave
+// reads at once fall into different banks).
+constexpr int RADI_WB = 16, RADI_WCT = 64, RADI_WLQ = 144, RADI_WLY = 80;
+__global__ __launch_bounds__(256) void radi_reduce_wide_kernel(int nv, int k, int nb, int rows_per_slice,
+                                                               const int* __restrict__ rp, const int* __restrict__ ci,
+                                                               const double* __restrict__ vA,
+                                                               const double* __restrict__ vE,
+                                                               const double* __restrict__ Q,
+                                                               const double* __restrict__ RU,
+                                                               const double* __restrict__ B,
+                                                               double* __restrict__ part) {
+  __shared__ double qs[RADI_WB * RADI_WLQ];
+  __shared__ double ys[RADI_WB * RADI_WLY];
+  const int W = 3 * k + 2 * nb, ldp = k + nb, ndense = ldp + nb;
+  const int ngt = (k + 31) / 32, nrt = (k + 15) / 16, kp = 16 * nrt;
+  const int t = blockIdx.y;
+  const bool gather = t < ngt;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lc = lane & 15, lk = lane >> 4;
+  const int r0 = blockIdx.x * rows_per_slice, r1 = min(nv, r0 + rows_per_slice);
+  d4 acc[8];
+#pragma unroll
+  for (int a = 0; a < 8; ++a) acc[a] = (d4){0.0, 0.0, 0.0, 0.0};
+  for (int row0 = r0; row0 < r1; row0 += RADI_WB) {
+    const int nr = min(RADI_WB, r1 - row0);
+    for (int e = tid; e < RADI_WB * kp; e += 256) {
+      const int r = e / kp, c = e - r * kp;
+      qs[r * RADI_WLQ + c] = (r < nr && c < k) ? Q[(size_t)(row0 + r) * k + c] : 0.0;
+    }
+    if (gather) {
+      for (int e = tid; e < RADI_WB * 32; e += 256) {
+        const int r = e >> 5, j = e & 31, c = 32 * t + j;
+        double a = 0.0, s = 0.0;
+        if (r < nr && c < k) {
+          const int row = row0 + r;
+          const int p1 = rp[row + 1];
+#pragma unroll 4
+          for (int p = rp[row]; p < p1; ++p) {
+            const int col = ci[p];
+            const double qv = col < nv ? Q[(size_t)col * k + c] : 0.0;      // (beyond nv: the J^T part of the saddle row)
+            a = fma(vA[p], qv, a);
+            s = fma(vE[p], qv, s);
+          }
+        }
+        ys[r * RADI_WLY + j] = a;
+        ys[r * RADI_WLY + 32 + j] = s;
+      }
+    } else {
+      for (int e = tid; e < RADI_WB * RADI_WCT; e += 256) {
+        const int r = e >> 6, j = e & 63, c = RADI_WCT * (t - ngt) + j;
+        double v = 0.0;
+        if (r < nr) {
+          if (c < ldp) v = RU[(size_t)(row0 + r) * ldp + c];
+          else if (c < ndense) v = B[(size_t)(row0 + r) * nb + c - ldp];
+        }
+        ys[r * RADI_WLY + j] = v;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int r = 4 * ks + lk;
+      const double bf = ys[r * RADI_WLY + 16 * wave + lc];
+#pragma unroll
+      for (int a = 0; a < 8; ++a)
+        if (a < nrt) acc[a] = __builtin_amdgcn_mfma_f64_16x16x4f64(qs[r * RADI_WLQ + 16 * a + lc], bf, acc[a], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  // the wave's column jl of the tile -> column of H (-1: padding)
+  const int jl = 16 * wave + lc;
+  int col = -1;
+  if (gather) {
+    const int c = 32 * t + (jl & 31);
+    if (c < k) col = jl < 32 ? c : k + c;
+  } else {
+    const int c = RADI_WCT * (t - ngt) + jl;
+    if (c < ndense) col = 2 * k + c;
+  }
+  if (col < 0) return;
+  double* out = part + (size_t)blockIdx.x * k * W;
+#pragma unroll
+  for (int a = 0; a < 8; ++a)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = 16 * a + lk + 4 * e;
+      if (a < nrt && i < k) out[(size_t)i * W + col] = acc[a][e];
+    }
+}
+// row slices of the wide kernel: 64 rows or more each (a multiple of RADI_WB), at most 1024 of them, the partials
+// kept below 64 MB
+static int radi_reduce_wide_slices(int n, int k, int W, int& rows_per_slice) {
+  const int cap = std::max(1, (int)(((size_t)64 << 20) / (sizeof(double) * (size_t)k * W)));
+  const int want = std::max(1, std::min(std::min((n + 63) / 64, 1024), cap));
+  rows_per_slice = RADI_WB * (((n + want - 1) / want + RADI_WB - 1) / RADI_WB);
+  return (n + rows_per_slice - 1) / rows_per_slice;
+}
 size_t radi_reduce_partial_len(int nv, int k, int m, int nb) {
   int rps = 0;
-  return (size_t)radi_reduce_slices(std::max(nv, 1), rps) * k * (2 * k + m + 2 * nb);
+  const int W = 2 * k + m + 2 * nb;
+  if (k > RADI_HK) return (size_t)radi_reduce_wide_slices(std::max(nv, 1), k, W, rps) * k * W;
+  return (size_t)radi_reduce_slices(std::max(nv, 1), rps) * k * W;
+}
+static void launch_radi_reduce_wide(hipStream_t st, int nv, int k, int nb, const int* rp, const int* ci,
+                                    const double* vA, const double* vE, const double* Q, const double* RU,
+                                    const double* B, double* partial, double* H) {
+  const int W = 3 * k + 2 * nb;
+  int rps = 0;
+  const int slices = radi_reduce_wide_slices(nv, k, W, rps);
+  const int tiles = (k + 31) / 32 + (k + 2 * nb + RADI_WCT - 1) / RADI_WCT;
+  hipLaunchKernelGGL(radi_reduce_wide_kernel, dim3(slices, tiles), dim3(256), 0, st, nv, k, nb, rps, rp, ci, vA, vE, Q,
+                     RU, B, partial);
+  hipLaunchKernelGGL(radi_vtb_reduce_kernel, dim3((k * W + 255) / 256), dim3(256), 0, st, slices, k * W, partial, H);
 }
 void launch_radi_reduce(hipStream_t st, int nv, int k, int m, int nb, const int* rp, const int* ci, const double* vA,
                         const double* vE, const double* Q, const double* RU, const double* B, double* partial,
                         double* H) {
   if (nv <= 0) return;
+  if (k > RADI_HK) {          // (k = m there: the callers check)
+    launch_radi_reduce_wide(st, nv, k, nb, rp, ci, vA, vE, Q, RU, B, partial, H);
+    return;
+  }
   const int W = 2 * k + m + 2 * nb;
   const int nsub = std::max(1, std::min(256 / W, RADI_HB));
   int rps = 0;

@@ -112,7 +112,7 @@ static void factor_download(ricadi_ctx* c, double* Z_out) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 409; }
+int ricadi_version(void) { return 410; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
@@ -959,6 +959,7 @@ static int check_radi(const ricadi_ctx* c, const double* shifts, int ns, const v
   REQUIRE(!sharded(c), RICADI_ESTATE, "ricadi_ric_radi does not shard: clear the exchange of this context first");
   REQUIRE(c->radi_shift_mode != RICADI_RADI_SHIFTS_HAMILTONIAN || mw <= 32, RICADI_EINVAL,
           "RICADI_RADI_SHIFTS_HAMILTONIAN needs mw <= 32");
+  // (RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT: mw <= 127 and nb <= 64, which every mode needs and the lines above check)
   return RICADI_OK;
 }
 static void radi_stats_out(const RadiStats& s, double* stats_out) {
@@ -1021,6 +1022,17 @@ int ricadi_ric_radi_dev(ricadi_ctx* c, const double* shifts, int ns, const doubl
 int ricadi_set_radi_shifts(ricadi_ctx* c, int mode) {
   REQUIRE(c && (mode == RICADI_RADI_SHIFTS_CYCLE || mode == RICADI_RADI_SHIFTS_HAMILTONIAN), RICADI_EINVAL,
           "mode must be RICADI_RADI_SHIFTS_CYCLE or RICADI_RADI_SHIFTS_HAMILTONIAN");
+  c->radi_shift_mode = mode;
+  return RICADI_OK;
+}
+// the same setting with the modes added since ABI 410; ricadi_set_radi_shifts keeps the two modes and the refusals
+// it had
+int ricadi_set_radi_shift_mode(ricadi_ctx* c, int mode) {
+  REQUIRE(c && (mode == RICADI_RADI_SHIFTS_CYCLE || mode == RICADI_RADI_SHIFTS_HAMILTONIAN ||
+                mode == RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT),
+          RICADI_EINVAL,
+          "mode must be RICADI_RADI_SHIFTS_CYCLE, RICADI_RADI_SHIFTS_HAMILTONIAN or "
+          "RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT");
   c->radi_shift_mode = mode;
   return RICADI_OK;
 }

@@ -512,6 +512,20 @@ int ricadi_radi_reduce_dev(ricadi_ctx* c, const double* dQ, int k, const double*
   API_END
 }
 
+// the same on the wide kernel (launch_radi_reduce above 32 columns), synchronous
+int ricadi_radi_reduce_wide_dev(ricadi_ctx* c, const double* dQ, int k, const double* dRU, int m, const double* dB,
+                                int nb, double* dH_out) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(dQ && dRU && dB && dH_out, RICADI_EINVAL, "NULL argument");
+  REQUIRE(k == m && m >= 33 && m <= 127 && nb >= 1 && nb <= 64, RICADI_EINVAL,
+          "k = m, 33 <= m <= 127, 1 <= nb <= 64 required");
+  API_BEGIN_ON(c)
+  TArr<double> part(c->pool, radi_reduce_partial_len(c->nv, k, m, nb));
+  launch_radi_reduce(c->st, c->nv, k, m, nb, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, dQ, dRU, dB, part.p, dH_out);
+  HIPCHK(hipStreamSynchronize(c->st));
+  API_END
+}
+
 int ricadi_probe_cache_entries(ricadi_ctx* c, int* n_out) {
   REQUIRE(c && n_out, RICADI_EINVAL, "NULL argument");
   size_t n = 0;

@@ -124,7 +124,8 @@ static void radi_dense_step(ricadi_ctx* c, double p, const double* dV, int ldv, 
 // The factor is left in the context (c->Z, c->zc); the gain cal E X B = U + old goes to dK_out (nv x nb, may be NULL).
 // Recycling of solved right-hand sides is off inside (the panel width changes after the first step; the ring's
 // assumptions have not been checked for that).
-// Shifts: RICADI_RADI_SHIFTS_CYCLE cycles through `shifts`.  RICADI_RADI_SHIFTS_HAMILTONIAN (mw <= 32) starts with
+// Shifts: RICADI_RADI_SHIFTS_CYCLE cycles through `shifts`.  RICADI_RADI_SHIFTS_HAMILTONIAN (mw <= 32; with
+// ..._DOMINANT any mw, the host's ricadi::radi_next_shift_dominant in place of radi_next_shift) starts with
 // shifts[0] and generates every later shift from the iteration: right after the residual Gram launch the QR of the new
 // block of Z and the reduction kernel are issued -- speculatively, once too often at the end --, H and R are fetched
 // with the Gram matrix and the flag words in the step's ONE synchronisation, and the host selects the shift after the
@@ -149,7 +150,8 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
       dC(c->pool, (size_t)m * (2 * m + nb)), dPart(c->pool, radi_vtb_partial_len(nv, m, nb));
   // W is projected in place: private copy
   HIPCHK(hipMemcpyAsync(dWm.p, dW, sizeof(double) * nv * m, hipMemcpyDeviceToDevice, st));
-  const bool ham = c->radi_shift_mode == RICADI_RADI_SHIFTS_HAMILTONIAN;
+  const bool dominant = c->radi_shift_mode == RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT;      // (mw <= 127)
+  const bool ham = dominant || c->radi_shift_mode == RICADI_RADI_SHIFTS_HAMILTONIAN;
   const int hw = 3 * m + 2 * nb;                      // columns of H
   c->radi_shift_hist.clear();
   c->radi_fallbacks = 0;
@@ -283,7 +285,8 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
         ++c->radi_qr_repeats;
       }
       int kept = 0;
-      fell_back = ricadi::radi_next_shift(m, nb, hH, hR, &p_next, &margin, &kept) != 0 ||
+      fell_back = (dominant ? ricadi::radi_next_shift_dominant(m, nb, hH, hR, &p_next, &margin, &kept)
+                            : ricadi::radi_next_shift(m, nb, hH, hR, &p_next, &margin, &kept)) != 0 ||
                   std::find(c->radi_refuse.begin(), c->radi_refuse.end(), step) != c->radi_refuse.end();
       c->radi_kept_hist.push_back(kept);
       if (fell_back) {

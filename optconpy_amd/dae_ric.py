@@ -2,7 +2,8 @@
 
 Python 3 counterpart of ``solve_flow_daeric`` (``/root/reference/solve_dae_ric.py:7-213``,
 called from ``/root/reference/optcont_main.py:584-600``) on top of the MI355X
-solver modules: per time step one Newton-ADI solve, one column compression,
+solver modules: per time step one Newton-ADI solve (or, with
+``ric_solver='radi'``, one RADI solve), one column compression,
 the feedback gain and one feed-forward saddle-point solve -- all on the GPU
 through :mod:`optconpy_amd.proj_ric_utils` / :mod:`optconpy_amd.lin_alg_utils`.
 Same keyword arguments and the same returned ``feedbackthroughdict`` (time ->
@@ -80,11 +81,26 @@ def solve_flow_daeric(mmat=None, amat=None, jmat=None, bmat=None,
                       get_tdpart=None, gttdprtargs=None,
                       get_datastr=None, gtdtstrargs=None,
                       check_c_consist=True,
-                      store=None, pru=None, lau=None, verbose=False):
+                      store=None, pru=None, lau=None, verbose=False,
+                      ric_solver=None, radi_dict=None):
     """See the module docstring.  ``store`` defaults to :class:`NpyStore`;
     ``pru`` / ``lau`` default to the MI355X modules (the test-suite passes the
-    CPU oracle's modules here to obtain reference values)."""
+    CPU oracle's modules here to obtain reference values).
+
+    ``ric_solver``: ``None`` -- every step's Riccati equation by Newton-ADI
+    (``pru.proj_alg_ric_newtonadi``, started from ``Z_{k+1}``) -- or ``'radi'``
+    -- by low-rank RADI (``pru.proj_alg_ric_radi`` with ``radi_dict``, default
+    ``dict(ms='hamiltonian-dominant')``: W has up to ``comprz_maxc + NY``
+    columns, more than the column rule of ``ms='hamiltonian'`` takes; DESIGN.md
+    3d-2), started from zero.  The rest of a step is the same.  ``ValueError``
+    for another value or a ``pru`` without ``proj_alg_ric_radi``."""
     pru = _pru if pru is None else pru
+    if ric_solver not in (None, "radi"):
+        raise ValueError("ric_solver must be None (Newton-ADI) or 'radi'")
+    if ric_solver == "radi":
+        if not hasattr(pru, "proj_alg_ric_radi"):
+            raise ValueError("ric_solver='radi' needs a pru with proj_alg_ric_radi")
+        radi_dict = dict(ms="hamiltonian-dominant") if radi_dict is None else radi_dict
     lau = _lau if lau is None else lau
     store = NpyStore() if store is None else store
     gttdprtargs = {} if gttdprtargs is None else gttdprtargs
@@ -151,11 +167,18 @@ def solve_flow_daeric(mmat=None, amat=None, jmat=None, bmat=None,
         except IOError:
             ft = -(0.5 * MT + tau * (AT + NT))
             wfac = np.hstack([MT @ Zc, np.sqrt(tau) * tct])
-            Zp = pru.proj_alg_ric_newtonadi(
-                mmat=MT, amat=ft, transposed=True,
-                mtxoldb=None if old_gain is None else np.sqrt(tau) * old_gain,
-                jmat=jmat, bmat=np.sqrt(tau) * tb, wmat=wfac, z0=Zc,
-                nwtn_adi_dict=nwtn_adi_dict)["zfac"]
+            if ric_solver == "radi":
+                Zp = pru.proj_alg_ric_radi(
+                    mmat=MT, amat=ft, transposed=True,
+                    mtxoldb=None if old_gain is None else np.sqrt(tau) * old_gain,
+                    jmat=jmat, bmat=np.sqrt(tau) * tb, wmat=wfac,
+                    radi_dict=radi_dict)["zfac"]
+            else:
+                Zp = pru.proj_alg_ric_newtonadi(
+                    mmat=MT, amat=ft, transposed=True,
+                    mtxoldb=None if old_gain is None else np.sqrt(tau) * old_gain,
+                    jmat=jmat, bmat=np.sqrt(tau) * tb, wmat=wfac, z0=Zc,
+                    nwtn_adi_dict=nwtn_adi_dict)["zfac"]
             if comprz_maxc is not None or comprz_thresh is not None:
                 Zc = pru.compress_Zsvd(Zp, thresh=comprz_thresh, k=comprz_maxc)
             else:

@@ -329,7 +329,8 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
     ``radi_dict`` keys: ``ms`` (negative real shifts, cycled; ``'auto'`` generates them as the Newton call does for
     its first step; ``'hamiltonian'`` starts with ``adi_shifts.initial_shift`` of the operator and generates every
     later shift from the iteration itself -- ``ricadi_set_radi_shifts``; needs at most 32 columns in
-    ``wmat``), ``ms_fallback`` (with ``ms='hamiltonian'`` only: a list of negative reals that replaces that one-element
+    ``wmat``; ``'hamiltonian-dominant'`` is the same rule on the at most 32 dominant directions of the new block,
+    for a ``wmat`` of any width RADI takes -- DESIGN.md 3d-2), ``ms_fallback`` (with a generated ``ms`` only: a list of negative reals that replaces that one-element
     list -- its first entry starts, the list is cycled where a shift cannot be generated), ``radi_max_steps`` (200),
     ``radi_res_reltol`` (1e-10), ``compress_cols`` (the factor is recompressed whenever it has grown by that many
     columns; default 512), ``verbose``, ``device_resident``.
@@ -338,12 +339,12 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
     ``device_resident``), ``gain`` = ``cal E X B`` (ndarray), ``radi_steps``, ``res_hist`` (the relative residual
     after every step), ``stop_rule`` (``_lib.RICADI_STOP_RES`` or ``_lib.RICADI_STOP_MAX_STEPS``),
     ``gmres_nonconverged``, ``shift_solves``, ``gmres_iters`` (and ``ms`` / ``shift_info`` with ``ms='auto'``; with
-    ``ms='hamiltonian'`` ``ms`` -- the shift of every step -- and ``shift_fallbacks``)."""
+    a generated ``ms``: ``ms`` -- the shift of every step -- and ``shift_fallbacks``)."""
     d = {} if radi_dict is None else radi_dict
     calA, calE = _orient(amat, mmat, transposed)
     ctx = backend.context_for(calA, calE, jmat)
     ctx.set_lowrank(None, None)
-    generated = isinstance(d.get("ms"), str) and d["ms"] == "hamiltonian"
+    generated = isinstance(d.get("ms"), str) and d["ms"] in ("hamiltonian", "hamiltonian-dominant")
     sinfo = None
     if generated:
         fb = d.get("ms_fallback")
@@ -356,7 +357,7 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
     kw = dict(max_steps=int(d.get("radi_max_steps", 200)), res_reltol=float(d.get("radi_res_reltol", 1e-10)),
               compress_cols=int(d.get("compress_cols", 0)), verbose=bool(d.get("verbose", False)))
     # the shift mode is a context setting: set for this call, and as before after it, also when the call fails
-    mode_before = ctx.set_radi_shifts("hamiltonian") if generated else None
+    mode_before = ctx.set_radi_shifts(d["ms"]) if generated else None
     try:
         if d.get("device_resident", False) or any(_on_device(x) for x in (bmat, wmat, mtxoldb)):
             Zt, Kt, info = ctx.ric_radi_dev(ms, to_device(bmat).t, to_device(wmat).t,

@@ -76,7 +76,11 @@ typedef struct ricadi_opts {
                             smoothed prolongation applies to keep TWO levels instead, up to k <= 1.5
                             coarse_max, and grow their aggregates up to (121, 182) for it: at their small
                             shifts the child is a poor stand-in for the inverse (n = 2e5: 229 vs 118
-                            iterations), and the smoothed coarse operator does not go with a child      */
+                            iterations), and the smoothed coarse operator does not go with a child.
+                            Under either rule a level keeps k_p <= k_v (else its coarse saddle matrix is
+                            singular): it coarsens its pressure aggregates further for that, and where they
+                            cannot join -- they never cross components of the graph of J J^T -- the level
+                            goes without a coarse space, as with use_coarse = 0                          */
   int verbose;
   int compress_qr;       /* ricadi_compress: 1 (default) = thin block QR + SVD of R, the reference's
                             "QR ... SVD" (singular values resolved to eps*s_1), for factors of up to

@@ -169,7 +169,12 @@ def auto_shifts(ctx, W, num=8, warm_steps=2, default=None):
         solves += info["shift_solves"]
         blocks.append(Zw)
     B = np.hstack(blocks)
-    Qraw, R = ctx.qr(B)
+    if B.shape[1] > ctx.nv:
+        # an operator with fewer velocity unknowns than [W0, Z_warm] has columns: ricadi_qr takes c <= NV only, and
+        # such a block (NV < c rows, a handful of columns) is factorised on the host
+        Qraw, R = np.linalg.qr(B)
+    else:
+        Qraw, R = ctx.qr(B)
     Q = np.ascontiguousarray(basis(Qraw, R))
     cands = np.zeros(0)
     if Q.shape[1] > 0:

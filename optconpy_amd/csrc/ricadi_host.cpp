@@ -503,6 +503,13 @@ static Aggregates hierarchy_rule(const HostCsr& E, const ricadi_opts& o, int bs,
       ap += std::max(1, ap / 2);
       continue;
     }
+    // The default hierarchy needs k_p <= k_v for the same reason (a tiny operator, or pressure rows with disjoint
+    // supports: few velocity aggregates under many pressure components).  No operator whose coarse matrix could be
+    // inverted so far has k_p > k_v, so this changes no structure that worked.
+    if (!fine && np > 0 && kp > kv && ap < np) {
+      ap += std::max(1, ap / 2);
+      continue;
+    }
     const int direct_max = std::max(16, stiff && !fine ? o.coarse_max + o.coarse_max / 2 : o.coarse_max);
     if (kv + kp <= direct_max) break;
     if (fine) {
@@ -538,6 +545,12 @@ static Aggregates hierarchy_rule(const HostCsr& E, const ricadi_opts& o, int bs,
     }
     av *= 2;
     ap *= 2;
+  }
+  // Pressure aggregates never join components of the graph of J J^T: where more components than velocity aggregates
+  // are left, no aggregate size gives a regular coarse matrix, and the level goes without a coarse space (kv = kp = 0).
+  if (np > 0 && kp > kv) {
+    kv = kp = 0;
+    g.multilevel = false;
   }
   g.kv = kv;
   g.kp = kp;
@@ -778,6 +791,11 @@ HostSetup build_setup(const HostCsr& A, const HostCsr& E, const HostCsr& J, cons
   double sa_rs = -1.0, sa_gamma = -1.0;
   const bool stiff = sa_omega > 0.0 && hs.np > 0 && sa_criterion(A, sa_rs, sa_gamma);
   const Aggregates g = hierarchy_rule(E, o, hs.bs, hs.nv, hs.np, w, max_levels, stiff);
+  if (g.kv + g.kp == 0) {   // the rule found no regular coarse space: as without use_coarse
+    hs.agg_ptr.assign(1, 0);
+    hs.aggof.assign(hs.n, 0);
+    return hs;
+  }
   coarse_space(g, hs);
   smoothed_prolongation(A, o, sa_omega, stiff, sa_rs, sa_gamma, hs, g);
   coarse_matrices(A, E, J, hs, g);

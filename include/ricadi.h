@@ -403,7 +403,10 @@ int ricadi_ric_newtonadi_dev(ricadi_ctx* ctx, const double* shifts, int nshifts,
  * RICADI_EINVAL, before anything is launched, for bad widths, max_steps < 1, nshifts < 1, a shift >= 0 and
  * zcap < max_steps * mw with Z_out given; RICADI_ESTATE on a context with an exchange set (nothing is sharded here);
  * RICADI_EBREAKDOWN when Y has a pivot that is not positive and finite (NaN / Inf in a solve).
- * Recycling of solved right-hand sides (ricadi_set_recycle) is off inside the call and as before after it.       */
+ * Recycling of solved right-hand sides (ricadi_set_recycle) is off inside the call and as before after it.
+ * With a sweep width above 1 (ricadi_set_radi_sweep_width below; ABI 411; default 1) and RICADI_RADI_SHIFTS_CYCLE, up to
+ * that many consecutive steps are solved in ONE lockstep batch against the same panel and recombined: the same steps,
+ * history, stopping rule and gain; stats_out[4] then counts every solve issued.                                     */
 int ricadi_ric_radi(ricadi_ctx* ctx, const double* shifts, int nshifts, const double* B, int nb, const double* W,
                     int mw, const double* oldB, int max_steps, double res_reltol, int compress_cols, int project_w,
                     int verbose, double* Z_out, int zcap, int* c_out, double* K_out, double* stats_out);
@@ -484,6 +487,36 @@ int ricadi_probe_radi_kept(ricadi_ctx* ctx, int* out, int cap, int* n_out);
  * order: the same call gives bitwise the same outputs.  RICADI_EBREAKDOWN as above.                              */
 int ricadi_radi_update_dev(ricadi_ctx* ctx, double p, const double* dV, int ldv, int m, const double* dB, int nb,
                            double* dRU, double* dZblk, int ldz, int zoff, double* dG_out, double* dC_out);
+/* The SWEEP form of a1r (ABI 411): with RICADI_RADI_SHIFTS_CYCLE and a width G > 1, G consecutive
+ * steps with pairwise distinct shifts p_1 .. p_G run as G solves against the SAME panel [R_0 | U_0] in ONE lockstep
+ * batch (cal A_0 = cal A - U_0 B^T the closed loop at the start of the sweep),
+ *   [[cal A_0 + p_g cal E, J^T], [J, 0]] [Vh_g; *] = [R_0; 0],   Vh = [Vh_1 .. Vh_G],   S = cal E Vh,   Gh = Vh^T B,
+ *   M_gh = -(I + Gh_g Gh_h^T) / (p_g + p_h) = L L^T,   y = L^-1 (1_G (x) I),   h = L^-1 Gh,   T_j = L^-T[:, :j mw],
+ *   Z <- [Z, Vh T_k],   R <- R_0 + S T_k y[:k mw],   U <- U_0 + S T_k h[:k mw],
+ * which equals the G sequential steps block by block up to a rotation inside each block (Z Z^T, the gain and the
+ * residual after every step are the same in exact arithmetic; G = 1 is the step above).  The residual after every
+ * step of the sweep comes from ONE fetch of Gh and of the Gram matrix of [R_0 | S]; the sweep keeps k blocks, k the
+ * first step whose residual is <= res_reltol, else as many as max_steps leaves, and drops the blocks behind it: steps,
+ * history, stopping rule and ricadi_radi_shift_history mean what they mean at width 1, while the count of shift solves
+ * (stats_out[4]) counts every solve issued and may exceed the steps by up to G - 1.
+ * ricadi_set_radi_sweep_width: a context setting like ricadi_set_radi_shift_mode, default 1 (the sequential form,
+ * bitwise as before); RICADI_EINVAL for width < 1 or > 16.  The width that runs is ricadi_host_radi_sweep_width's.
+ * With width > 1 and a generated-shift mode ricadi_ric_radi(_dev) return RICADI_EINVAL before anything is launched.
+ * ricadi_radi_sweep_info, of the most recent ricadi_ric_radi(_dev) call: out[0] the effective width, out[1] sweeps
+ * run (0 at width 1), out[2] solves issued.  RICADI_ESTATE before any RADI call.                                  */
+#define RICADI_RADI_SWEEP_PIVOT 1e-5       /* smallest relative Cauchy pivot of an admitted sweep   */
+#define RICADI_RADI_SWEEP_MAX_K 128        /* G mw of a sweep                                                        */
+int ricadi_set_radi_sweep_width(ricadi_ctx* ctx, int width);
+int ricadi_radi_sweep_info(ricadi_ctx* ctx, int* out);
+/* The recombination of a sweep on device operands, for tests: the G solution panels lie at dV + g vstride (their
+ * first NV rows, leading dimension ldv >= m, the first m columns are used), dS = cal E Vh NV x G m, dCf the
+ * coefficient matrix G m x (k m + m + nb) of ricadi_host_radi_sweep.  Writes columns [zoff, zoff + k m) of dZblk
+ * (leading dimension ldz) = Vh Cf[:, :k m] and adds S Cf[:, k m:] into dRU = [R | U] NV x (m + nb).
+ * 1 <= G <= 16, G m <= 128, 1 <= k <= G, 1 <= nb <= 64.  FP64 matrix cores, no atomics, every sum in ascending
+ * order: the same call gives bitwise the same outputs.                                                            */
+int ricadi_radi_sweep_combine_dev(ricadi_ctx* ctx, int G, const double* dV, int64_t vstride, int ldv, int m,
+                                  const double* dS, const double* dCf, int k, int nb, double* dRU, double* dZblk,
+                                  int ldz, int zoff);
 
 /* ---- device-pointer level (multi-GPU orchestration, benchmarks) --------
  * Same operations on buffers that already live in HBM (e.g. torch tensors'
@@ -907,6 +940,26 @@ int ricadi_host_radi_next_shift(int m, int nb, const double* H, const double* R,
  * (R = 0: no singular value is positive).  RICADI_EINVAL unless 1 <= m <= 127, 1 <= nb <= 64.                         */
 int ricadi_host_radi_next_shift_dominant(int m, int nb, const double* H, const double* R, double* p_out,
                                          double* margin_out, int* kept_out);
+/* What the host does between the one fetch of a RADI sweep and its recombination (the formulas at
+ * ricadi_set_radi_sweep_width).  Host only, no GPU needed; long double inside.
+ * ricadi_host_radi_sweep: g shifts (negative, pairwise distinct), Ghat g m x nb, Gamma (g + 1) m x (g + 1) m the Gram
+ *   matrix of [R_0 | S], rhs = ||R^T R||_F of the iteration's first residual factor (<= 0: every residual reads 0),
+ *   steps_left >= 1.  *k_out = the steps kept: the first j whose relative residual is <= res_reltol, else
+ *   min(g, steps_left); res_out (>= g doubles) the relative residuals after steps 1 .. k; Cf_out (>= g m (g m + m + nb)
+ *   doubles) = [T_k | T_k y[:k m] | T_k h[:k m]], row-major g m x (k m + m + nb), leading dimension k m + m + nb.
+ *   1 <= g <= 16, g m <= RICADI_RADI_SWEEP_MAX_K, 1 <= nb <= 64.  RICADI_EBREAKDOWN if a pivot of M is not positive
+ *   and finite.
+ * ricadi_host_radi_sweep_width: the effective width for a cycled list of ns shifts: the largest G <= want with G <= ns,
+ *   G mw <= RICADI_RADI_SWEEP_MAX_K, G times the column groups of an (mw + nb)-wide panel in the batched solve (one up
+ *   to 32 columns, ceil((mw + nb) / 16) above) <= 16 and G <= max_steps; then halved until every sweep of the cycle
+ *   -- sweep s takes entries s G .. s G + G - 1 of the cycled list -- has pairwise distinct shifts and a smallest pivot
+ *   prod_{k<j} ((p_j - p_k) / (p_j + p_k))^2 >= RICADI_RADI_SWEEP_PIVOT.  1: the sequential form.  A prefix of an
+ *   admissible sweep is admissible.  1 <= want <= 16.                                                               */
+int ricadi_host_radi_sweep(int g, int m, int nb, const double* shifts, const double* Ghat, const double* Gamma,
+                           double rhs, double res_reltol, int steps_left, int* k_out, double* res_out,
+                           double* Cf_out);
+int ricadi_host_radi_sweep_width(const double* shifts, int ns, int mw, int nb, int want, int max_steps,
+                                 int* width_out);
 
 #ifdef __cplusplus
 }

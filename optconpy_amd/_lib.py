@@ -23,7 +23,7 @@ RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT = 2
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 410
+ABI_VERSION = 411
 
 
 class RicadiOpts(C.Structure):
@@ -95,6 +95,10 @@ SIGNATURES = {
                                       C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _vp, _dp]),
     "ricadi_radi_update_dev": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int,
                                          C.c_int, _vp, _vp]),
+    "ricadi_set_radi_sweep_width": (C.c_int, [_vp, C.c_int]),
+    "ricadi_radi_sweep_info": (C.c_int, [_vp, _ip]),
+    "ricadi_radi_sweep_combine_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, C.c_int,
+                                                C.c_int, _vp, _vp, C.c_int, C.c_int]),
     "ricadi_set_radi_shifts": (C.c_int, [_vp, C.c_int]),
     "ricadi_set_radi_shift_mode": (C.c_int, [_vp, C.c_int]),
     "ricadi_radi_shift_history": (C.c_int, [_vp, _dp, C.c_int, C.POINTER(C.c_int)]),
@@ -170,6 +174,10 @@ SIGNATURES = {
                                               C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "ricadi_host_radi_next_shift_dominant": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_double),
                                                        C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "ricadi_host_radi_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int,
+                                         C.POINTER(C.c_int), _dp, _dp]),
+    "ricadi_host_radi_sweep_width": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(C.c_int)]),
 }
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _vp, C.c_int64)
@@ -733,6 +741,28 @@ class Context:
         self._radi_shift_mode = new
         return old
 
+    def set_radi_sweep_width(self, width):
+        """``ricadi_set_radi_sweep_width``: how many consecutive steps of a cycled RADI run go through one lockstep
+        batch of solves (1, the default: one solve per step; at most 16).  The width that runs is what the shift list
+        allows (:func:`host_radi_sweep_width`).  A context setting.  Returns the width that was in force."""
+        new = int(width)
+        old = getattr(self, "_radi_sweep_width", 1)
+        _chk(self._lib.ricadi_set_radi_sweep_width(self._h, new))
+        self._radi_sweep_width = new
+        return old
+
+    def radi_sweep_info(self):
+        """``ricadi_radi_sweep_info``: dict(width, sweeps, solves) of the last RADI call: the effective sweep width,
+        the sweeps run (0 at width 1) and the shift solves issued."""
+        out = np.zeros(3, dtype=np.int32)
+        _chk(self._lib.ricadi_radi_sweep_info(self._h, _i(out)))
+        return dict(width=int(out[0]), sweeps=int(out[1]), solves=int(out[2]))
+
+    def radi_sweep_combine_dev(self, G, v_ptr, vstride, ldv, m, s_ptr, cf_ptr, k, nb, ru_ptr, z_ptr, ldz, zoff):
+        """``ricadi_radi_sweep_combine_dev``: the recombination of a RADI sweep on device pointers (tests)."""
+        _chk(self._lib.ricadi_radi_sweep_combine_dev(self._h, int(G), v_ptr, int(vstride), int(ldv), int(m), s_ptr,
+                                                     cf_ptr, int(k), int(nb), ru_ptr, z_ptr, int(ldz), int(zoff)))
+
     def radi_shift_history(self):
         """``ricadi_radi_shift_history``: the shift of every step of the last RADI call (either mode)."""
         n = C.c_int(0)
@@ -1240,6 +1270,37 @@ def host_radi_next_shift(m, nb, H, R, dominant=False):
     if rc > 0:
         return None, None, kept.value, RADI_REFUSALS[rc]
     return p.value, mg.value, kept.value, None
+
+
+def host_radi_sweep(shifts, m, nb, Ghat, Gamma, rhs, res_reltol, steps_left):
+    """``ricadi_host_radi_sweep``: what the RADI driver does with what a sweep has fetched -- the g shifts, Ghat = Vh^T B
+    (g m x nb) and Gamma, the Gram matrix of [R_0 | cal E Vh] ((g + 1) m square); host only.  Returns ``(k, res, Cf)``:
+    the steps kept, the relative residual after each, and Cf = [T_k | T_k y | T_k h] (g m x (k m + m + nb)).
+    ValueError for bad sizes, RuntimeError on a breakdown."""
+    sh = np.ascontiguousarray(shifts, dtype=np.float64)
+    Ghat = np.ascontiguousarray(Ghat, dtype=np.float64)
+    Gamma = np.ascontiguousarray(Gamma, dtype=np.float64)
+    g, m, nb = int(sh.size), int(m), int(nb)
+    if min(g, m, nb) >= 1 and (Ghat.size != g * m * nb or Gamma.size != ((g + 1) * m) ** 2):
+        raise ValueError("Ghat must be g m x nb and Gamma (g + 1) m square")
+    k = C.c_int(0)
+    res = np.zeros(max(g, 1))
+    Cf = np.zeros(max(g * m, 1) * (max(g * m, 1) + max(m, 1) + max(nb, 1)))
+    _chk(load().ricadi_host_radi_sweep(g, m, nb, _d(sh), _d(Ghat), _d(Gamma), float(rhs), float(res_reltol),
+                                       int(steps_left), C.byref(k), _d(res), _d(Cf)))
+    kk = k.value
+    ldc = kk * m + m + nb
+    return kk, res[:kk].copy(), Cf[:g * m * ldc].reshape(g * m, ldc).copy()
+
+
+def host_radi_sweep_width(shifts, mw, nb, want, max_steps):
+    """``ricadi_host_radi_sweep_width``: the sweep width a cycled RADI run takes for this list (1: one solve per
+    step); host only."""
+    sh = np.ascontiguousarray(shifts, dtype=np.float64)
+    w = C.c_int(0)
+    _chk(load().ricadi_host_radi_sweep_width(_d(sh), int(sh.size), int(mw), int(nb), int(want), int(max_steps),
+                                             C.byref(w)))
+    return int(w.value)
 
 
 def host_plan_levels(calA, calE, J, **opts):

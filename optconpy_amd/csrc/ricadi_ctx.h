@@ -377,6 +377,10 @@ struct ricadi_ctx {
   std::vector<int> radi_kept_hist;
   int radi_qr_repeats = 0, radi_recompressions = 0;
   std::vector<int> radi_refuse;
+  // the sweep form (ricadi_set_radi_sweep_width): the width asked for, and of the last call the
+  // effective width, the sweeps run and the solves issued (ricadi_radi_sweep_info)
+  int radi_sweep_width = 1;
+  int radi_sweep_info[3] = {1, 0, 0};
   // per-shift data
   std::map<std::pair<double, double>, std::unique_ptr<ShiftData>> cache;
   // The ONE entry the RADI driver rebuilds for every generated shift (a level owns its own): it is lent to `cache`

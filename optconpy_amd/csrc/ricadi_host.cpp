@@ -1770,9 +1770,197 @@ int radi_next_shift_dominant(int m, int nb, const double* hH, const double* hR, 
   return 0;
 }
 
+// ---- the sweep form of RADI (solver_radi.inl) ------------------------------------------------
+// What the host does between the one fetch of a sweep and the recombination kernel.  With the g shifts p, Gh = Vh^T B
+// (g m x nb) and Gamma = P^T P, P = [R_0 | cal E Vh]:
+//   M_gh = -(I_m + Gh_g Gh_h^T) / (p_g + p_h) = L L^T,  y = L^-1 (1_g (x) I_m),  h = L^-1 Gh,  T_j = L^-T[:, :j m],
+//   res_j = ||c_j^T Gamma c_j||_F / rhs,  c_j = [I_m; T_j y[:j m]],   Cf = [T_k | T_k y[:k m] | T_k h[:k m]].
+// T_j y[:j m] and T_j h[:j m] grow by the rows of block j from one step to the next, so the whole history costs one
+// pass over L^-1.  Arithmetic: long double for M, its factor, L^-1 and the coefficients.  M inherits the conditioning of the sweep's Cauchy matrix (cond(M) up to
+// ~1 / RICADI_RADI_SWEEP_PIVOT^2 and more when Gh is large), and FP64 would lose that many digits of Cf before the
+// kernel ever uses it; with 11 more bits the factorisation's error stays below the rounding of Cf to FP64 for every
+// admitted sweep.  The quadratic forms of the history run in FP64: their input Gamma is an FP64 Gram matrix.  At
+// g m = 128 that leaves ~1e6 long double multiply-adds per sweep of 8 solves (DESIGN.md 3d-3 has the measured time).
+int radi_sweep(int g, int m, int nb, const double* shifts, const double* Ghat, const double* Gamma, double rhs,
+               double res_reltol, int steps_left, int* k_out, double* res_out, double* Cf_out) {
+  typedef long double ld;
+  const int K = g * m, nc = K + m;
+  std::vector<ld> L((size_t)K * K, 0.0L), Li((size_t)K * K, 0.0L);
+  for (int a = 0; a < g; ++a)
+    for (int b = 0; b <= a; ++b) {
+      const ld den = -((ld)shifts[a] + (ld)shifts[b]);
+      for (int i = 0; i < m; ++i)
+        for (int j = 0; j < m; ++j) {
+          ld s = i == j ? 1.0L : 0.0L;
+          const double *gi = Ghat + (size_t)(a * m + i) * nb, *gj = Ghat + (size_t)(b * m + j) * nb;
+          for (int t = 0; t < nb; ++t) s += (ld)gi[t] * (ld)gj[t];
+          L[(size_t)(a * m + i) * K + b * m + j] = s / den;
+        }
+    }
+  // Cholesky factor in the lower triangle, row by row
+  for (int i = 0; i < K; ++i) {
+    for (int j = 0; j <= i; ++j) {
+      ld s = L[(size_t)i * K + j];
+      for (int t = 0; t < j; ++t) s -= L[(size_t)i * K + t] * L[(size_t)j * K + t];
+      if (j < i) {
+        L[(size_t)i * K + j] = s / L[(size_t)j * K + j];
+      } else {
+        if (!(s > 0.0L) || !(s <= (ld)std::numeric_limits<double>::max())) return RICADI_EBREAKDOWN;
+        L[(size_t)i * K + i] = sqrtl(s);
+      }
+    }
+    for (int j = i + 1; j < K; ++j) L[(size_t)i * K + j] = 0.0L;
+  }
+  // L^-1 by forward substitution, row by row (row i of L X = I: unit-stride updates with the rows above, t ascending)
+  for (int i = 0; i < K; ++i) {
+    ld* xi = &Li[(size_t)i * K];
+    for (int t = 0; t < i; ++t) {
+      const ld l = L[(size_t)i * K + t];
+      const ld* xt = &Li[(size_t)t * K];
+      for (int j = 0; j <= t; ++j) xi[j] -= l * xt[j];
+    }
+    const ld d = L[(size_t)i * K + i];
+    for (int j = 0; j < i; ++j) xi[j] /= d;
+    xi[i] = 1.0L / d;
+  }
+  std::vector<ld> y((size_t)K * m, 0.0L), h((size_t)K * nb, 0.0L), ty((size_t)K * m, 0.0L), th((size_t)K * nb, 0.0L);
+  for (int i = 0; i < K; ++i) {
+    for (int t = 0; t <= i; ++t) y[(size_t)i * m + t % m] += Li[(size_t)i * K + t];
+    for (int t = 0; t <= i; ++t)
+      for (int b = 0; b < nb; ++b) h[(size_t)i * nb + b] += Li[(size_t)i * K + t] * (ld)Ghat[(size_t)t * nb + b];
+  }
+  const int jmax = std::min(g, steps_left);
+  // the quadratic form in FP64: Gamma is an FP64 Gram matrix, off by 2^-53 |P|^T |P| already, and c is rounded once
+  std::vector<double> gc((size_t)nc * m), tyd((size_t)K * m, 0.0);
+  int k = 0;
+  for (int j = 1; j <= jmax; ++j) {
+    // rows of block j of L^-1 enter T_j y and T_j h (L^-T[i, r] = L^-1[r, i], zero for i > r)
+    for (int r = (j - 1) * m; r < j * m; ++r)
+      for (int i = 0; i <= r; ++i) {
+        const ld l = Li[(size_t)r * K + i];
+        for (int a = 0; a < m; ++a) ty[(size_t)i * m + a] += l * y[(size_t)r * m + a];
+        for (int b = 0; b < nb; ++b) th[(size_t)i * nb + b] += l * h[(size_t)r * nb + b];
+      }
+    // c = [I_m; ty] has rows below (j + 1) m only
+    const int nr = (j + 1) * m;
+    for (int i = 0; i < j * m; ++i)
+      for (int a = 0; a < m; ++a) tyd[(size_t)i * m + a] = (double)ty[(size_t)i * m + a];
+    for (int i = 0; i < nr; ++i) {
+      double* gi = &gc[(size_t)i * m];
+      for (int a = 0; a < m; ++a) gi[a] = Gamma[(size_t)i * nc + a];
+      for (int t = m; t < nr; ++t) {
+        const double gam = Gamma[(size_t)i * nc + t];
+        for (int a = 0; a < m; ++a) gi[a] += gam * tyd[(size_t)(t - m) * m + a];
+      }
+    }
+    double f = 0.0;
+    for (int a = 0; a < m; ++a)
+      for (int b = 0; b < m; ++b) {
+        double s = gc[(size_t)a * m + b];
+        for (int t = m; t < nr; ++t) s += tyd[(size_t)(t - m) * m + a] * gc[(size_t)t * m + b];
+        f += s * s;
+      }
+    const double res = rhs > 0.0 ? std::sqrt(f) / rhs : 0.0;
+    res_out[j - 1] = res;
+    k = j;
+    if (res <= res_reltol) break;
+  }
+  *k_out = k;                       // (ty / th hold the sums of the first k blocks)
+  const int km = k * m, ldc = km + m + nb;
+  for (int i = 0; i < K; ++i) {
+    double* row = Cf_out + (size_t)i * ldc;
+    for (int c = 0; c < km; ++c) row[c] = c >= i ? (double)Li[(size_t)c * K + i] : 0.0;
+    for (int a = 0; a < m; ++a) row[km + a] = (double)ty[(size_t)i * m + a];
+    for (int b = 0; b < nb; ++b) row[km + m + b] = (double)th[(size_t)i * nb + b];
+  }
+  return RICADI_OK;
+}
+
+// min_j prod_{k<j} ((p_j - p_k) / (p_j + p_k))^2 of a sweep's shifts: cauchy_data's pivots (0 where two are equal)
+static long double radi_sweep_pivot(const double* ps, int g) {
+  long double out = 1.0L;
+  for (int j = 0; j < g; ++j) {
+    long double piv = 1.0L;
+    for (int k = 0; k < j; ++k) {
+      const long double q = ((long double)ps[j] - (long double)ps[k]) / ((long double)ps[j] + (long double)ps[k]);
+      piv *= q * q;
+    }
+    out = std::min(out, piv);
+  }
+  return out;
+}
+
+int radi_sweep_groups(int mw, int nb) { return mw + nb > 32 ? (mw + nb + 15) / 16 : 1; }
+
+// The effective sweep width of a cycled list (1: the sequential form).  Host arithmetic only.
+int radi_sweep_width(const double* shifts, int ns, int mw, int nb, int want, int max_steps) {
+  int G = std::min(std::min(want, ns), std::min(RICADI_RADI_SWEEP_MAX_K / mw, RICADI_MAX_GROUPS / radi_sweep_groups(mw, nb)));
+  G = std::max(1, std::min(G, max_steps));
+  std::vector<double> ps;
+  for (; G >= 2; G /= 2) {
+    const int nsweep = ns / std::gcd(ns, G);
+    bool ok = true;
+    for (int s = 0; s < nsweep && ok; ++s) {
+      ps.resize(G);
+      for (int i = 0; i < G; ++i) ps[i] = shifts[((size_t)s * G + i) % ns];
+      ok = radi_sweep_pivot(ps.data(), G) >= (long double)RICADI_RADI_SWEEP_PIVOT;
+    }
+    if (ok) return G;
+  }
+  return 1;
+}
+
 }  // namespace ricadi
 
 extern "C" {
+
+int ricadi_host_radi_sweep(int g, int m, int nb, const double* shifts, const double* Ghat, const double* Gamma,
+                           double rhs, double res_reltol, int steps_left, int* k_out, double* res_out,
+                           double* Cf_out) {
+  if (g < 1 || g > RICADI_MAX_GROUPS || m < 1 || g * m > RICADI_RADI_SWEEP_MAX_K || nb < 1 || nb > 64 || steps_left < 1 ||
+      !shifts || !Ghat || !Gamma || !k_out || !res_out || !Cf_out) {
+    ricadi::set_error("ricadi_host_radi_sweep: bad argument (1 <= g <= 16, g m <= 128, 1 <= nb <= 64, steps_left >= 1)");
+    return RICADI_EINVAL;
+  }
+  for (int i = 0; i < g; ++i) {
+    bool ok = shifts[i] < 0.0;
+    for (int j = 0; j < i; ++j) ok = ok && shifts[i] != shifts[j];
+    if (!ok) {
+      ricadi::set_error("ricadi_host_radi_sweep: the shifts of a sweep must be negative and pairwise distinct");
+      return RICADI_EINVAL;
+    }
+  }
+  try {
+    const int rc = ricadi::radi_sweep(g, m, nb, shifts, Ghat, Gamma, rhs, res_reltol, steps_left, k_out, res_out, Cf_out);
+    if (rc == RICADI_EBREAKDOWN)
+      ricadi::set_error("RADI sweep: M has a pivot that is not positive and finite (NaN / Inf in a shift solve)");
+    return rc;
+  } catch (const std::exception&) {
+    ricadi::set_error("ricadi_host_radi_sweep: exception");
+    return RICADI_EHIP;
+  }
+}
+
+int ricadi_host_radi_sweep_width(const double* shifts, int ns, int mw, int nb, int want, int max_steps,
+                                 int* width_out) {
+  if (!shifts || !width_out || ns < 1 || mw < 1 || nb < 1 || nb > 64 || mw + nb > RICADI_MAX_M || want < 1 ||
+      want > RICADI_MAX_GROUPS || max_steps < 1) {
+    ricadi::set_error("ricadi_host_radi_sweep_width: bad argument");
+    return RICADI_EINVAL;
+  }
+  for (int i = 0; i < ns; ++i)
+    if (!(shifts[i] < 0.0)) {
+      ricadi::set_error("ricadi_host_radi_sweep_width: RADI shifts must be negative");
+      return RICADI_EINVAL;
+    }
+  try {
+    *width_out = ricadi::radi_sweep_width(shifts, ns, mw, nb, want, max_steps);
+  } catch (const std::exception&) {
+    ricadi::set_error("ricadi_host_radi_sweep_width: exception");
+    return RICADI_EHIP;
+  }
+  return RICADI_OK;
+}
 
 static int radi_shift_entry(int k, int m, int nb, const double* H, double* p_out, double* margin_out, double* wr,
                             double* wi) {

@@ -16,6 +16,10 @@
 //                                              per row slice, the slices summed by radi_vtb_reduce_kernel;
 //   radi_reduce_wide_kernel                    the same for blocks of 33 .. 127 columns: the
 //                                              output tiled over workgroups, on the FP64 matrix cores.
+// The sweep form (G steps as one lockstep batch of solves) replaces the last two by
+//   radi_sweep_combine_kernel                  Z block = Vh Cf[:, :k m], [R | U] += (cal E Vh) Cf[:, k m:] for the dense
+//                                              coefficient matrix the host makes of the sweep's small matrices, on the
+//                                              FP64 matrix cores.
 // FP64 throughout, no atomics, every sum in a fixed order: the same inputs give bitwise the same outputs.
 #include "ricadi_internal.h"
 #include "ricadi_device.h"
@@ -209,6 +213,80 @@ void launch_radi_update(hipStream_t st, int nv, int m, int nb, const int* rp, co
   const size_t lds = sizeof(double) * (size_t)(2 * RADI_RB + RADI_CT) * m;
   hipLaunchKernelGGL(radi_update_kernel, dim3((nv + RADI_RB - 1) / RADI_RB), dim3(256), lds, st, nv, m, nb, rp, ci, ev,
                      V, ldv, C, RU, Z, zld, zc);
+}
+
+// ---- the recombination of a sweep ---------------------------------------------------------
+// Z[:, zc : zc + k m] = Vh Cf[:, :k m]  and  [R | U] += S Cf[:, k m:]  in one pass over the velocity rows: Vh = the G
+// solution panels side by side (panel g at V + g vstride, leading dimension ldv, its first m columns), S = cal E Vh
+// (nv x K, K = G m <= 128, leading dimension lds), Cf K x (k m + m + nb) row-major -- the dense generalisation of
+// launch_sweep_combine, whose coefficient is (G x G) (x) I_m.
+// grid = (chunks of 64 rows, column tiles of RADI_SCT = 64 output columns): the first ceil(k m / 64) tiles are columns
+// of the Z block (A operand: rows of Vh), the others columns of [R | U] (A operand: rows of S).  A wave owns 16 rows
+// and the tile's four 16-column fragments: v_mfma_f64_16x16x4_f64 with gemm_nn's fragment maps (lane l holds
+// A[row l & 15][k l >> 4], B[k l >> 4][col l & 15], D[row (l >> 4) + 4 reg][col l & 15]), K / 4 instructions per
+// fragment, k ascending.  Cf's columns are tiled over workgroups and its B fragments are read where they lie: the
+// whole matrix is at most 128 x 208 doubles, every wave of a tile reads the same 64 KB of it and it stays in L2 / the
+// vector L1; an LDS stage would save a fourth of that traffic and cost a barrier per tile.  The rows of Vh / S are read
+// once per column tile (at most four tiles).  No atomics, no reduction across waves: bitwise reproducible.
+// The A fragments are strided loads: the sixteen lanes of a k-step read sixteen different rows at stride ldv / lds,
+// 32 contiguous bytes (four k) of each, and every column tile reads the row block again.  At K <= 128 and 0.06 ms per
+// sweep (n = 3e4) that is not what a sweep waits for; if K or nv grow, staging the 64 x K row block in LDS once per
+// workgroup (coalesced row reads, shared by the column tiles) is the lever.
+constexpr int RADI_SCT = 64;
+__global__ __launch_bounds__(256) void radi_sweep_combine_kernel(int nv, int G, int m, int nb, int k,
+                                                                 const double* __restrict__ V, size_t vstride, int ldv,
+                                                                 const double* __restrict__ S, int lds,
+                                                                 const double* __restrict__ Cf,
+                                                                 double* __restrict__ RU, double* __restrict__ Z,
+                                                                 int zld, int zc) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lc = lane & 15, lk = lane >> 4;
+  const int K = G * m, km = k * m, ldp = m + nb, ldc = km + ldp;
+  const int nzt = (km + RADI_SCT - 1) / RADI_SCT;
+  const bool zt = (int)blockIdx.y < nzt;
+  const int j0 = RADI_SCT * (zt ? (int)blockIdx.y : (int)blockIdx.y - nzt);    // first column inside Z block / [R | U]
+  const int ncol = zt ? km : ldp, coff = zt ? 0 : km;                          // columns there; their offset in Cf
+  const int row0 = (blockIdx.x * 4 + wave) * 16;
+  if (row0 >= nv) return;
+  const int arow = row0 + lc;
+  const bool aok = arow < nv;
+  d4 acc[4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) acc[b] = (d4){0.0, 0.0, 0.0, 0.0};
+  int g = lk / m, c = lk - g * m;                                              // kk = g m + c
+  for (int kk0 = 0; kk0 < K; kk0 += 4) {
+    const int kk = kk0 + lk;
+    const bool kok = kk < K;
+    double af = 0.0;
+    if (aok && kok) af = zt ? V[(size_t)g * vstride + (size_t)arow * ldv + c] : S[(size_t)arow * lds + kk];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int col = j0 + 16 * b + lc;
+      const double bf = (kok && col < ncol) ? Cf[(size_t)kk * ldc + coff + col] : 0.0;
+      acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[b], 0, 0, 0);
+    }
+    c += 4;
+    while (c >= m) {
+      c -= m;
+      ++g;
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int row = row0 + lk + 4 * e, col = j0 + 16 * b + lc;
+      if (row >= nv || col >= ncol) continue;
+      if (zt) Z[(size_t)row * zld + zc + col] = acc[b][e];
+      else RU[(size_t)row * ldp + col] += acc[b][e];
+    }
+}
+void launch_radi_sweep_combine(hipStream_t st, int nv, int G, int m, int nb, int k, const double* V, size_t vstride,
+                               int ldv, const double* S, int lds, const double* Cf, double* RU, double* Z, int zld,
+                               int zc) {
+  if (nv <= 0) return;
+  const int tiles = (k * m + RADI_SCT - 1) / RADI_SCT + (m + nb + RADI_SCT - 1) / RADI_SCT;
+  hipLaunchKernelGGL(radi_sweep_combine_kernel, dim3((nv + 63) / 64, tiles), dim3(256), 0, st, nv, G, m, nb, k, V,
+                     vstride, ldv, S, lds, Cf, RU, Z, zld, zc);
 }
 
 // ---- the reduced matrices of the shift selection ------------------------------------------------------------------

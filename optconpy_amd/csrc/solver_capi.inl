@@ -112,7 +112,7 @@ static void factor_download(ricadi_ctx* c, double* Z_out) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 410; }
+int ricadi_version(void) { return 411; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
@@ -960,6 +960,8 @@ static int check_radi(const ricadi_ctx* c, const double* shifts, int ns, const v
   REQUIRE(c->radi_shift_mode != RICADI_RADI_SHIFTS_HAMILTONIAN || mw <= 32, RICADI_EINVAL,
           "RICADI_RADI_SHIFTS_HAMILTONIAN needs mw <= 32");
   // (RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT: mw <= 127 and nb <= 64, which every mode needs and the lines above check)
+  REQUIRE(c->radi_sweep_width == 1 || c->radi_shift_mode == RICADI_RADI_SHIFTS_CYCLE, RICADI_EINVAL,
+          "a RADI sweep width above 1 needs RICADI_RADI_SHIFTS_CYCLE: generated shifts are one at a time");
   return RICADI_OK;
 }
 static void radi_stats_out(const RadiStats& s, double* stats_out) {
@@ -1034,6 +1036,17 @@ int ricadi_set_radi_shift_mode(ricadi_ctx* c, int mode) {
           "mode must be RICADI_RADI_SHIFTS_CYCLE, RICADI_RADI_SHIFTS_HAMILTONIAN or "
           "RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT");
   c->radi_shift_mode = mode;
+  return RICADI_OK;
+}
+int ricadi_set_radi_sweep_width(ricadi_ctx* c, int width) {
+  REQUIRE(c && width >= 1 && width <= RICADI_MAX_GROUPS, RICADI_EINVAL, "1 <= width <= 16 required");
+  c->radi_sweep_width = width;
+  return RICADI_OK;
+}
+int ricadi_radi_sweep_info(ricadi_ctx* c, int* out) {
+  REQUIRE(c && out, RICADI_EINVAL, "NULL argument");
+  REQUIRE(c->radi_ran, RICADI_ESTATE, "no RADI iteration has run on this context");
+  for (int i = 0; i < 3; ++i) out[i] = c->radi_sweep_info[i];
   return RICADI_OK;
 }
 int ricadi_radi_shift_history(ricadi_ctx* c, double* out, int cap, int* n_out) {

@@ -498,6 +498,23 @@ int ricadi_radi_update_dev(ricadi_ctx* c, double p, const double* dV, int ldv, i
   API_END_STATUS(flag ? (ricadi::set_error(RADI_BREAKDOWN_MSG), RICADI_EBREAKDOWN) : RICADI_OK)
 }
 
+// the recombination of a RADI sweep (launch_radi_sweep_combine), synchronous
+int ricadi_radi_sweep_combine_dev(ricadi_ctx* c, int G, const double* dV, int64_t vstride, int ldv, int m,
+                                  const double* dS, const double* dCf, int k, int nb, double* dRU, double* dZblk,
+                                  int ldz, int zoff) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(dV && dS && dCf && dRU && dZblk, RICADI_EINVAL, "NULL argument");
+  REQUIRE(G >= 1 && G <= RICADI_MAX_GROUPS && m >= 1 && G * m <= RICADI_RADI_SWEEP_MAX_K && k >= 1 && k <= G && nb >= 1 &&
+              nb <= 64,
+          RICADI_EINVAL, "1 <= G <= 16, G m <= 128, 1 <= k <= G, 1 <= nb <= 64 required");
+  REQUIRE(ldv >= m && zoff >= 0 && ldz >= zoff + k * m && (G == 1 || vstride >= (int64_t)c->nv * ldv), RICADI_EINVAL,
+          "bad leading dimension or stride");
+  API_BEGIN_ON(c)
+  launch_radi_sweep_combine(c->st, c->nv, G, m, nb, k, dV, (size_t)vstride, ldv, dS, G * m, dCf, dRU, dZblk, ldz, zoff);
+  HIPCHK(hipStreamSynchronize(c->st));
+  API_END
+}
+
 // the reduced matrices of the shift selection (launch_radi_reduce), synchronous
 int ricadi_radi_reduce_dev(ricadi_ctx* c, const double* dQ, int k, const double* dRU, int m, const double* dB, int nb,
                            double* dH_out) {

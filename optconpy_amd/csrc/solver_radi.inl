@@ -112,6 +112,135 @@ static void radi_dense_step(ricadi_ctx* c, double p, const double* dV, int ldv, 
   launch_radi_update(st, c->nv, m, nb, c->E.rp.p, c->E.ci.p, c->E.v.p, dV, ldv, dC, dRU, dZ, zld, zc);
 }
 
+// The SWEEP form of the iteration (CYCLE mode, effective width Gw > 1; the formulas at
+// ricadi_set_radi_sweep_width): the loop of ric_radi_run below with G = min(Gw, steps left) steps per pass.
+//   1. ONE solve_batch with the G shifts against the panel [R_0 | U_0] (gsb = 0, c->q = nb, lr_ucol = m: the `dup`
+//      path, S^-1 U out of the same solve for every shift; while U is identically zero the m columns of R, plain);
+//   2. P = [R_0 | cal E Vh] (launch_sweep_resid_panel on the compacted solution panels), Gamma = P^T P
+//      (launch_gram_fixed), Gh_g = Vh_g^T B (launch_radi_vtb per shift): fixed summation orders;
+//   3. the sweep's ONE host synchronisation: Gamma and Gh;
+//   4. ricadi::radi_sweep: the steps kept, the residual after each, the coefficient matrix Cf;
+//   5. Cf uploaded;  6. launch_radi_sweep_combine: the kept blocks of Z, [R | U] advanced to R_k, U_k.
+// hbuf: pinned, nc^2 + K nb + K (K + m + nb) doubles (nc = K + m, K = Gw m).
+static void radi_run_sweeps(ricadi_ctx* c, RadiStats& stt, const double* shifts, int ns, int Gw, const double* dB,
+                            int nb, int m, double* dRU, bool uzero, int max_steps, double res_reltol,
+                            int compress_cols, bool verbose, double* hbuf) {
+  hipStream_t st = c->st;
+  const int nv = c->nv, n = c->n, mp = m + nb, Kw = Gw * m, ncw = Kw + m;
+  TArr<double> dR0(c->pool, (size_t)nv * m), dVc(c->pool, (size_t)nv * Kw), dP(c->pool, (size_t)nv * ncw),
+      dGh(c->pool, (size_t)Kw * nb), dGam(c->pool, (size_t)ncw * ncw), dCf(c->pool, (size_t)Kw * (Kw + mp)),
+      dPart(c->pool, radi_vtb_partial_len(nv, m, nb));
+  c->res_part.ensure(gram_fixed_partial_len(nv, ncw));
+  c->sweep_u.ensure((size_t)n * mp * Gw);
+  double *hGam = hbuf, *hGh = hGam + (size_t)ncw * ncw, *hCf = hGh + (size_t)Kw * nb;
+  std::vector<double> ps(Gw), be(Gw, 1.0), resv(Gw);
+  std::vector<ShiftData*> sds(Gw);
+  std::vector<GmresResult> res(Gw);
+  int zc_last = 0, sweeps = 0;
+  double tph[5] = {0, 0, 0, 0, 0};          // RICADI_TIMING: setup, solve, reductions + fetch, host, combine
+  Tick tk;
+  auto lap = [&](int i) {
+    if (c->sw.timing) {
+      (void)hipStreamSynchronize(st);
+      tph[i] += tk.lap();
+    }
+  };
+  while (stt.steps < max_steps) {
+    const int left = max_steps - stt.steps, G = std::min(Gw, left), K = G * m, nc = K + m;
+    for (int g = 0; g < G; ++g) ps[g] = shifts[(stt.steps + g) % ns];
+    if (c->sw.timing) tk.lap();
+    get_shifts(c, ps.data(), be.data(), G, sds.data());
+    lap(0);
+    double* x = c->sweep_u.p;
+    int ldv = m;
+    if (uzero) {
+      c->q = 0;
+      launch_copy_cols(st, nv, m, dRU, mp, 0, c->bvec.p, m, 0, 1.0);
+      if (c->np > 0) HIPCHK(hipMemsetAsync(c->bvec.p + (size_t)nv * m, 0, sizeof(double) * (size_t)c->np * m, st));
+      solve_batch(c, sds.data(), G, c->bvec.p, 0, x, m, false, nullptr, res.data());
+    } else {
+      c->q = nb;
+      ++c->lr_epoch;
+      launch_copy_cols(st, nv, nb, dRU, mp, m, c->U.p, nb, 0, 1.0);
+      c->lr_ucol = m;
+      load_rhs(c, dRU, mp, c->bvec.p);
+      solve_batch(c, sds.data(), G, c->bvec.p, 0, x, mp, true, nullptr, res.data());
+      c->lr_ucol = -1;
+      ldv = mp;
+    }
+    const size_t vstride = (size_t)n * ldv;
+    int its = 0;
+    for (int g = 0; g < G; ++g) {
+      its = std::max(its, res[g].iters);
+      if (res[g].converged) continue;
+      stt.nonconverged++;
+      stt.worst_relres = std::max(stt.worst_relres, res[g].max_relres);
+      if (verbose)
+        fprintf(stderr, "[ricadi] RADI sweep %d shift %g: GMRES stopped at relres %.2e after %d its\n", sweeps + 1,
+                ps[g], res[g].max_relres, res[g].iters);
+    }
+    stt.shift_solves += G;
+    lap(1);
+    // the reductions: P = [R_0 | cal E Vh], its Gram matrix, Gh
+    launch_copy_cols(st, nv, m, dRU, mp, 0, dR0.p, m, 0, 1.0);
+    const double* vb = x;
+    size_t vs = vstride;
+    if (ldv != m) {
+      for (int g = 0; g < G; ++g) launch_copy_cols(st, nv, m, x + g * vstride, ldv, 0, dVc.p + (size_t)g * nv * m, m, 0, 1.0);
+      vb = dVc.p;
+      vs = (size_t)nv * m;
+    }
+    launch_sweep_resid_panel(st, nv, m, G, c->E.rp.p, c->E.ci.p, c->E.v.p, dR0.p, vb, vs, dP.p);
+    c->res_part.ensure(gram_fixed_partial_len(nv, nc));       // (a shorter last sweep slices the rows differently)
+    launch_gram_fixed(st, nv, nc, dP.p, nc, c->res_part.p, dGam.p);
+    for (int g = 0; g < G; ++g)
+      launch_radi_vtb(st, nv, m, nb, x + g * vstride, ldv, dB, dPart.p, dGh.p + (size_t)g * m * nb);
+    c->res_launches += 3 + 2 * G;
+    HIPCHK(hipMemcpyAsync(hGam, dGam.p, sizeof(double) * nc * nc, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hGh, dGh.p, sizeof(double) * K * nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (c->sw.timing) tph[2] += tk.lap();
+    if (sweeps == 0) stt.rhs = gram_block_fro(hGam, nc, m, 0);
+    int k = 0;
+    const int rc = ricadi::radi_sweep(G, m, nb, ps.data(), hGh, hGam, stt.rhs, res_reltol, left, &k, resv.data(), hCf);
+    if (c->sw.timing) tph[3] += tk.lap();
+    if (rc != RICADI_OK) {
+      c->radi_shift_hist.push_back(ps[0]);
+      stt.breakdown = true;
+      break;
+    }
+    const int km = k * m;
+    HIPCHK(hipMemcpyAsync(dCf.p, hCf, sizeof(double) * K * (km + mp), hipMemcpyHostToDevice, st));
+    launch_radi_sweep_combine(st, nv, G, m, nb, k, x, vstride, ldv, dP.p + m, nc, dCf.p, dRU, c->Z.p, c->zld, c->zc);
+    uzero = false;
+    ++sweeps;
+    c->zc += km;
+    for (int j = 0; j < k; ++j) {
+      c->radi_shift_hist.push_back(ps[j]);
+      c->adi_res_hist.push_back(resv[j]);
+      if (verbose)
+        fprintf(stderr, "[ricadi] RADI step %3d: shift %10.3e rel residual %9.3e (sweep %d of %d solves, gmres its %d)\n",
+                stt.steps + j + 1, ps[j], resv[j], sweeps, G, its);
+    }
+    stt.steps += k;
+    stt.res = resv[k - 1];
+    lap(4);
+    if (stt.res <= res_reltol) {
+      c->adi_stop_rule = RICADI_STOP_RES;
+      break;
+    }
+    if (stt.steps < max_steps && c->zc - zc_last >= compress_cols) {
+      factor_recompress(c);
+      ++c->radi_recompressions;
+      zc_last = c->zc;
+    }
+  }
+  c->radi_sweep_info[1] = sweeps;
+  if (c->sw.timing)
+    fprintf(stderr, "[ricadi timing] RADI %d steps in %d sweeps of width %d: per-shift setup %.1f ms, solve %.1f, reductions + fetch %.1f, host %.1f, combine %.1f\n",
+            stt.steps, sweeps, Gw, 1e3 * tph[0], 1e3 * tph[1], 1e3 * tph[2], 1e3 * tph[3], 1e3 * tph[4]);
+}
+
 // RADI on DEVICE operands (row-major, their own width as leading dimension): dB nv x nb, dW nv x mw, dOld nv x nb or
 // NULL.  Step j with the shift p of the cycle:
 //   [[cal A - U B^T + p cal E, J^T], [J, 0]] [V; *] = [R; 0]   -- solve_batch with c->U = U, c->V = B; [R | U] is ONE
@@ -145,7 +274,13 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
   c->adi_stop_rule = RICADI_STOP_MAX_STEPS;
   c->adi_ran = true;
   if (compress_cols <= 0) compress_cols = 512;       // as the Newton driver
-  ensure_work(c, mp, 1, nb);
+  // the sweep form: CYCLE mode only (the entries refuse the other modes at width > 1), the width the list allows
+  const int Gw = c->radi_shift_mode == RICADI_RADI_SHIFTS_CYCLE && c->radi_sweep_width > 1
+                     ? ricadi::radi_sweep_width(shifts, ns, mw, nb, c->radi_sweep_width, max_steps)
+                     : 1;
+  c->radi_sweep_info[0] = Gw;
+  c->radi_sweep_info[1] = c->radi_sweep_info[2] = 0;
+  ensure_work(c, mp, Gw, nb);
   TArr<double> dWm(c->pool, (size_t)nv * m), dRU(c->pool, (size_t)nv * mp), dG(c->pool, (size_t)m * nb),
       dC(c->pool, (size_t)m * (2 * m + nb)), dPart(c->pool, radi_vtb_partial_len(nv, m, nb));
   // W is projected in place: private copy
@@ -177,7 +312,8 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
   // fetched with the first step's
   c->res_part.ensure(gram_fixed_partial_len(nv, m));
   c->res_gram.ensure((size_t)2 * mm);
-  double* hg = res_host(c, (size_t)2 * mm + 1 + (ham ? (size_t)m * hw + mm : 0));
+  const size_t hsweep = Gw > 1 ? (size_t)(Gw + 1) * m * (Gw + 1) * m + (size_t)Gw * m * nb + (size_t)Gw * m * (Gw * m + mp) : 0;
+  double* hg = res_host(c, std::max((size_t)2 * mm + 1 + (ham ? (size_t)m * hw + mm : 0), hsweep));
   int* hflag = reinterpret_cast<int*>(hg + 2 * mm);          // [0] the factorisation's flag, [1] the QR's
   double *hH = hg + 2 * mm + 1, *hR = hH + (size_t)m * hw;
   int* dflag = c->flag.p + 3;
@@ -197,8 +333,13 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
       tph[i] += tk.lap();
     }
   };
-  launch_gram_fixed(st, nv, m, dRU.p, mp, c->res_part.p, c->res_gram.p);
-  c->res_launches += 2;
+  if (Gw > 1) {
+    radi_run_sweeps(c, stt, shifts, ns, Gw, dB, nb, m, dRU.p, uzero, max_steps, res_reltol, compress_cols, verbose, hg);
+    max_steps = 0;                                           // (the loop below is the sequential form)
+  } else {
+    launch_gram_fixed(st, nv, m, dRU.p, mp, c->res_part.p, c->res_gram.p);
+    c->res_launches += 2;
+  }
   for (int step = 1; step <= max_steps; ++step) {
     const double p = ham ? p_next : shifts[(step - 1) % ns];
     c->radi_shift_hist.push_back(p);
@@ -303,7 +444,8 @@ static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const
   }
   stt.gmres_iters = c->total_iters - it0;
   stt.escalations = c->escalations - esc0;
-  if (c->sw.timing)
+  c->radi_sweep_info[2] = (int)stt.shift_solves;
+  if (c->sw.timing && Gw == 1)
     fprintf(stderr, "[ricadi timing] RADI %d steps (%s shifts): per-shift setup %.1f ms, solve + dense step %.1f, QR + reduction %.1f, host selection %.1f\n",
             stt.steps, ham ? "generated" : "cycled", 1e3 * tph[0], 1e3 * tph[1], 1e3 * tph[2], 1e3 * tph[3]);
   if (dK_out && !stt.breakdown) {

@@ -333,12 +333,15 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
     for a ``wmat`` of any width RADI takes -- DESIGN.md 3d-2), ``ms_fallback`` (with a generated ``ms`` only: a list of negative reals that replaces that one-element
     list -- its first entry starts, the list is cycled where a shift cannot be generated), ``radi_max_steps`` (200),
     ``radi_res_reltol`` (1e-10), ``compress_cols`` (the factor is recompressed whenever it has grown by that many
-    columns; default 512), ``verbose``, ``device_resident``.
+    columns; default 512), ``sweep_width`` (1; with a list of shifts, up to that many consecutive steps are solved
+    in ONE lockstep batch against the same panel and recombined -- the sweep form; at most 16, what
+    runs is what the list allows; a ``ValueError`` with a generated ``ms``), ``verbose``, ``device_resident``.
 
     Returns a dict: ``zfac`` (ndarray; a :class:`DeviceFactor` when given device panels or with
     ``device_resident``), ``gain`` = ``cal E X B`` (ndarray), ``radi_steps``, ``res_hist`` (the relative residual
     after every step), ``stop_rule`` (``_lib.RICADI_STOP_RES`` or ``_lib.RICADI_STOP_MAX_STEPS``),
-    ``gmres_nonconverged``, ``shift_solves``, ``gmres_iters`` (and ``ms`` / ``shift_info`` with ``ms='auto'``; with
+    ``gmres_nonconverged``, ``shift_solves`` (every solve issued: with sweeps up to ``sweep_width - 1`` more than
+    ``radi_steps``), ``gmres_iters``, ``sweep_width`` (the width that ran), ``sweeps`` (and ``ms`` / ``shift_info`` with ``ms='auto'``; with
     a generated ``ms``: ``ms`` -- the shift of every step -- and ``shift_fallbacks``)."""
     d = {} if radi_dict is None else radi_dict
     calA, calE = _orient(amat, mmat, transposed)
@@ -357,8 +360,12 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
     kw = dict(max_steps=int(d.get("radi_max_steps", 200)), res_reltol=float(d.get("radi_res_reltol", 1e-10)),
               compress_cols=int(d.get("compress_cols", 0)), verbose=bool(d.get("verbose", False)))
     # the shift mode is a context setting: set for this call, and as before after it, also when the call fails
-    mode_before = ctx.set_radi_shifts(d["ms"]) if generated else None
+    # ... and so is the sweep width
+    width_before = ctx.set_radi_sweep_width(int(d.get("sweep_width", 1)))       # (the default MEANS width 1)
+    mode_before = None
     try:
+        if generated:
+            mode_before = ctx.set_radi_shifts(d["ms"])
         if d.get("device_resident", False) or any(_on_device(x) for x in (bmat, wmat, mtxoldb)):
             Zt, Kt, info = ctx.ric_radi_dev(ms, to_device(bmat).t, to_device(wmat).t,
                                             old_t=None if mtxoldb is None else to_device(mtxoldb).t, **kw)
@@ -367,11 +374,14 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
             Z, K, info = ctx.ric_radi(ms, _dense(bmat), _dense(wmat),
                                       oldB=None if mtxoldb is None else _dense(mtxoldb), **kw)
     finally:
-        if generated:
+        if mode_before is not None:
             ctx.set_radi_shifts(mode_before)
+        ctx.set_radi_sweep_width(width_before)
+    swi = ctx.radi_sweep_info()
     out = dict(zfac=Z, gain=K, radi_steps=info["radi_steps"], res_hist=ctx.adi_res_history(),
                stop_rule=ctx.STOP_RULES.index(info["stop_rule"]), gmres_nonconverged=info["gmres_nonconverged"],
-               shift_solves=info["shift_solves"], gmres_iters=info["gmres_iters"])
+               shift_solves=info["shift_solves"], gmres_iters=info["gmres_iters"], sweep_width=swi["width"],
+               sweeps=swi["sweeps"])
     if sinfo is not None:
         out["ms"], out["shift_info"] = list(ms), sinfo
     if generated:

@@ -11,7 +11,11 @@ end with K on the host.  RADI runs at several residual tolerances; the one compa
 close to the fixture as Newton's (within 10 %), else the tightest.  Timings: one warm-up call of every variant, then
 the variants alternate for --trials rounds; median and best of the host clock around calls that end synchronised.
 
-python tools/radi_compare.py [--N 58] [--trials 5] [--out profiles/radi_cfg2.json]"""
+With --sweep-width W [W ...] the cycled list also runs in sweeps of those widths ("radi-sweepW": radi_dict['sweep_width'],
+DESIGN.md 3d-3), in the same process and alternating with the others; their lines carry the effective width, the
+sweeps and the solves issued, and a "summary-sweeps" line per tolerance compares them with width 1.
+
+python tools/radi_compare.py [--N 58] [--trials 5] [--sweep-width 2 4 8] [--out profiles/radi_cfg2.json]"""
 import argparse
 import json
 import os
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--shifts", type=int, default=16)
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--tols", type=float, nargs="+", default=[1e-6, 1e-7, 1e-8, 1e-10, 1e-12])
+    ap.add_argument("--sweep-width", type=int, nargs="*", default=[])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import sadptprj_riclyap_adi.lin_alg_utils as lau
@@ -62,13 +67,15 @@ def main():
                        shift_solves=out["shift_solves"], gmres_iters=out["gmres_iters"], cols=out["zfac"].shape[1],
                        nonconverged=out["gmres_nonconverged"])
 
-    def radi(tol, generated=False):
+    def radi(tol, generated=False, width=1):
         def run():
             ctx.clear_cache()
             out = pru.proj_alg_ric_radi(mmat=pr.M, amat=F, jmat=pr.J, bmat=tb_d, wmat=trct_d,
                                         radi_dict=dict(ms="hamiltonian" if generated else ms, radi_res_reltol=tol,
-                                                       radi_max_steps=400))
-            info = dict(path="radi-ham" if generated else "radi", radi_res_reltol=tol, steps=out["radi_steps"],
+                                                       radi_max_steps=400, sweep_width=width))
+            info = dict(path="radi-ham" if generated else "radi" if width == 1 else "radi-sweep%d" % width,
+                        radi_res_reltol=tol, steps=out["radi_steps"], sweep_width=out["sweep_width"],
+                        sweeps=out["sweeps"],
                         shift_solves=out["shift_solves"], gmres_iters=out["gmres_iters"],
                         cols=out["zfac"].shape[1], nonconverged=out["gmres_nonconverged"],
                         stop_rule=out["stop_rule"], last_res=float(out["res_hist"][-1]))
@@ -78,7 +85,8 @@ def main():
         return run
 
     variants = ([("newton-adi", newton)] + [("radi %g" % t, radi(t)) for t in args.tols]
-                + [("radi-ham %g" % t, radi(t, generated=True)) for t in args.tols])
+                + [("radi-ham %g" % t, radi(t, generated=True)) for t in args.tols]
+                + [("radi-sweep%d %g" % (w, t), radi(t, width=w)) for w in args.sweep_width if w > 1 for t in args.tols])
     rec, times = {}, {name: [] for name, _ in variants}
     for name, fn in variants:                         # warm-up: every shape the timed calls use
         K, info = fn()
@@ -112,6 +120,16 @@ def main():
                           cycled_ms=c["ms_median"], generated_ms=h["ms_median"], newton_ms=nt,
                           generated_K_vs_fixture=h["K_vs_fixture"],
                           faster="generated" if h["ms_median"] < c["ms_median"] else "cycled"))
+    for t in args.tols:                               # sweeps against width 1, tolerance by tolerance
+        c = rec["radi %g" % t]
+        for w in args.sweep_width:
+            if w > 1:
+                r = rec["radi-sweep%d %g" % (w, t)]
+                lines.append(dict(path="summary-sweeps", radi_res_reltol=t, asked=w, sweep_width=r["sweep_width"],
+                                  steps=r["steps"], shift_solves=r["shift_solves"], gmres_iters=r["gmres_iters"],
+                                  ms=r["ms_median"], width1_ms=c["ms_median"], width1_steps=c["steps"],
+                                  width1_gmres_iters=c["gmres_iters"], K_vs_fixture=r["K_vs_fixture"],
+                                  speedup=c["ms_median"] / r["ms_median"]))
     text = "\n".join(json.dumps(l) for l in lines)
     print(text)
     if args.out:

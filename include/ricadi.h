@@ -501,13 +501,46 @@ int ricadi_radi_update_dev(ricadi_ctx* ctx, double p, const double* dV, int ldv,
  * (stats_out[4]) counts every solve issued and may exceed the steps by up to G - 1.
  * ricadi_set_radi_sweep_width: a context setting like ricadi_set_radi_shift_mode, default 1 (the sequential form,
  * bitwise as before); RICADI_EINVAL for width < 1 or > 16.  The width that runs is ricadi_host_radi_sweep_width's.
- * With width > 1 and a generated-shift mode ricadi_ric_radi(_dev) return RICADI_EINVAL before anything is launched.
+ * With width > 1 and a generated-shift mode ricadi_ric_radi(_dev) return RICADI_EINVAL before anything is launched
+ * (unless ricadi_set_radi_sweep_shifts below is on).
  * ricadi_radi_sweep_info, of the most recent ricadi_ric_radi(_dev) call: out[0] the effective width, out[1] sweeps
  * run (0 at width 1), out[2] solves issued.  RICADI_ESTATE before any RADI call.                                  */
 #define RICADI_RADI_SWEEP_PIVOT 1e-5       /* smallest relative Cauchy pivot of an admitted sweep   */
 #define RICADI_RADI_SWEEP_MAX_K 128        /* G mw of a sweep                                                        */
 int ricadi_set_radi_sweep_width(ricadi_ctx* ctx, int width);
 int ricadi_radi_sweep_info(ricadi_ctx* ctx, int* out);
+/* Sweeps whose shifts are GENERATED from the iteration (ABI 412): a context setting, default 0.
+ * ricadi_set_radi_sweep_shifts(ctx, on) returns the previous value (0 / 1), RICADI_EINVAL (-1) for another `on`.
+ * With it on, ricadi_ric_radi(_dev) require RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT (else RICADI_EINVAL before anything
+ * is launched) and accept a sweep width above 1 with it.  At width 1 the call is the DOMINANT mode itself, bit for bit.
+ * Above 1:
+ *   cap      G = min(width, 128 / mw, 16 / column groups of the panel, max_steps); no halving.
+ *   first    sweep: ONE step with shifts[0].
+ *   basis    after a sweep that kept k blocks and did not end the iteration: Zg = the last min(k, 127 / mw) kept blocks
+ *            (c <= 127 columns), Q Rq = Zg, S the dominant <= 32 left singular vectors of Rq (RICADI_RADI_RANK_TOL), the
+ *            basis Q S; H = Q^T [cal A Q | cal E Q | R | U | B] is c x (2c + mw + 2nb).
+ *   select   the candidates of the HAMILTONIAN rule on that basis, ALL of them, ordered by descending criterion (on an
+ *            exact tie the larger |lambda| first); walking them in that order a candidate is admitted if it is finite
+ *            and negative and the smallest Cauchy pivot prod_{k<j} ((p_j - p_k) / (p_j + p_k))^2 of the admitted list
+ *            with it appended stays >= RICADI_RADI_SWEEP_PIVOT; up to min(G, steps left).  The next sweep solves the
+ *            admitted shifts in acceptance order (it may be narrower than G).
+ *   fallback a refused selection (RICADI_RADI_REFUSED_*, none admitted): the next sweep is ONE step with the next entry
+ *            of the list (a counter of its own from shifts[1], cycling), counted in ricadi_radi_shift_fallbacks.
+ * Two host synchronisations per sweep (the second is skipped when the sweep ended the iteration).  The cache holds
+ * after the call what it held before plus the entries of the list that were used.  ricadi_probe_radi_refuse: a sweep
+ * whose last kept step is listed counts as refused.  ricadi_probe_radi_kept: one entry per selection.
+ * ricadi_radi_sweep_info: out[0] the cap G, out[1] sweeps, out[2] solves issued.
+ * ricadi_radi_sweep_widths, of the most recent ricadi_ric_radi(_dev) call in a sweep form: the solves of every sweep in
+ * order; *n_out their number (0 after a sequential call), at most `cap` copied to `out` (may be NULL with cap = 0).
+ * RICADI_ESTATE before any RADI call.                                                                              */
+int ricadi_set_radi_sweep_shifts(ricadi_ctx* ctx, int on);
+int ricadi_radi_sweep_widths(ricadi_ctx* ctx, int* out, int cap, int* n_out);
+/* The reduction for such a group on device operands, for tests: dH_out (c x (2c + m + 2nb)) with dQ NV x c; any
+ * 1 <= c <= 127 with 1 <= m <= 127 (m <= 32 where c <= 32), 2c + m + 2nb <= 509.  c <= 32 and c = m run the kernels
+ * of ricadi_radi_reduce_dev / _wide_dev (the same bits); 33 <= c, m != c the group form of the wide kernel: FP64
+ * matrix cores, no atomics, a fixed summation order -- bitwise the same on a second call.                          */
+int ricadi_radi_reduce_group_dev(ricadi_ctx* ctx, const double* dQ, int c, const double* dRU, int m, const double* dB,
+                                 int nb, double* dH_out);
 /* The recombination of a sweep on device operands, for tests: the G solution panels lie at dV + g vstride (their
  * first NV rows, leading dimension ldv >= m, the first m columns are used), dS = cal E Vh NV x G m, dCf the
  * coefficient matrix G m x (k m + m + nb) of ricadi_host_radi_sweep.  Writes columns [zoff, zoff + k m) of dZblk
@@ -958,6 +991,14 @@ int ricadi_host_radi_next_shift_dominant(int m, int nb, const double* H, const d
 int ricadi_host_radi_sweep(int g, int m, int nb, const double* shifts, const double* Ghat, const double* Gamma,
                            double rhs, double res_reltol, int steps_left, int* k_out, double* res_out,
                            double* Cf_out);
+/* The shifts of the next sweep under ricadi_set_radi_sweep_shifts (the rule there) from what a sweep
+ * has fetched: H (c x (2c + m + 2nb)) and R (c x c) of the group's QR.  ps_out / crit_out (>= want each; crit_out may
+ * be NULL): the admitted shifts in acceptance order and their criteria; *n_out their number; *kept_out (may be NULL)
+ * the size of the basis.  Returns 0, or one of the RICADI_RADI_REFUSED_* values with *n_out = 0 (NO_SHIFT: no candidate
+ * was admitted).  want = 1 gives ricadi_host_radi_next_shift_dominant's shift (c = m).  RICADI_EINVAL unless
+ * 1 <= c, m <= 127, 1 <= nb <= 64, 1 <= want <= 16.  Host only.                                                     */
+int ricadi_host_radi_sweep_shifts(int c, int m, int nb, const double* H, const double* R, int want, double* ps_out,
+                                  double* crit_out, int* n_out, int* kept_out);
 int ricadi_host_radi_sweep_width(const double* shifts, int ns, int mw, int nb, int want, int max_steps,
                                  int* width_out);
 

@@ -23,7 +23,7 @@ RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT = 2
 MAX_M = 128
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 411
+ABI_VERSION = 412
 
 
 class RicadiOpts(C.Structure):
@@ -97,6 +97,9 @@ SIGNATURES = {
                                          C.c_int, _vp, _vp]),
     "ricadi_set_radi_sweep_width": (C.c_int, [_vp, C.c_int]),
     "ricadi_radi_sweep_info": (C.c_int, [_vp, _ip]),
+    "ricadi_set_radi_sweep_shifts": (C.c_int, [_vp, C.c_int]),
+    "ricadi_radi_sweep_widths": (C.c_int, [_vp, _ip, C.c_int, C.POINTER(C.c_int)]),
+    "ricadi_radi_reduce_group_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
     "ricadi_radi_sweep_combine_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, C.c_int,
                                                 C.c_int, _vp, _vp, C.c_int, C.c_int]),
     "ricadi_set_radi_shifts": (C.c_int, [_vp, C.c_int]),
@@ -178,6 +181,8 @@ SIGNATURES = {
                                          C.POINTER(C.c_int), _dp, _dp]),
     "ricadi_host_radi_sweep_width": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.POINTER(C.c_int)]),
+    "ricadi_host_radi_sweep_shifts": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp,
+                                                C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _vp, C.c_int64)
@@ -751,9 +756,27 @@ class Context:
         self._radi_sweep_width = new
         return old
 
+    def set_radi_sweep_shifts(self, on):
+        """``ricadi_set_radi_sweep_shifts``: with ``'hamiltonian-dominant'`` shifts, let a sweep width above 1 run as
+        sweeps whose shifts the iteration generates.  A context setting, off by default.  Returns the
+        value that was in force."""
+        rc = self._lib.ricadi_set_radi_sweep_shifts(self._h, int(on))
+        if rc < 0:
+            _chk(rc)
+        return bool(rc)
+
+    def radi_sweep_widths(self):
+        """``ricadi_radi_sweep_widths``: the solves of every sweep of the last RADI call (empty after a sequential
+        call)."""
+        n = C.c_int(0)
+        _chk(self._lib.ricadi_radi_sweep_widths(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.int32)
+        _chk(self._lib.ricadi_radi_sweep_widths(self._h, _i(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
+
     def radi_sweep_info(self):
-        """``ricadi_radi_sweep_info``: dict(width, sweeps, solves) of the last RADI call: the effective sweep width,
-        the sweeps run (0 at width 1) and the shift solves issued."""
+        """``ricadi_radi_sweep_info``: dict(width, sweeps, solves) of the last RADI call: the effective sweep width
+        (with generated sweep shifts: the cap), the sweeps run (0 at width 1) and the shift solves issued."""
         out = np.zeros(3, dtype=np.int32)
         _chk(self._lib.ricadi_radi_sweep_info(self._h, _i(out)))
         return dict(width=int(out[0]), sweeps=int(out[1]), solves=int(out[2]))
@@ -810,6 +833,10 @@ class Context:
     def radi_reduce_wide_dev(self, q_ptr, k, ru_ptr, m, b_ptr, nb, h_ptr):
         """``ricadi_radi_reduce_wide_dev``: the same on the wide kernel, k = m in 33 .. 127 (tests)."""
         _chk(self._lib.ricadi_radi_reduce_wide_dev(self._h, q_ptr, int(k), ru_ptr, int(m), b_ptr, int(nb), h_ptr))
+
+    def radi_reduce_group_dev(self, q_ptr, c, ru_ptr, m, b_ptr, nb, h_ptr):
+        """``ricadi_radi_reduce_group_dev``: the same for a group of c columns against an m-column residual (tests)."""
+        _chk(self._lib.ricadi_radi_reduce_group_dev(self._h, q_ptr, int(c), ru_ptr, int(m), b_ptr, int(nb), h_ptr))
 
     def radi_update_dev(self, p, v_ptr, ldv, m, b_ptr, nb, ru_ptr, z_ptr, ldz, zoff, g_ptr, c_ptr=None):
         """``ricadi_radi_update_dev``: the dense part of one RADI step on device pointers (tests)."""
@@ -1270,6 +1297,28 @@ def host_radi_next_shift(m, nb, H, R, dominant=False):
     if rc > 0:
         return None, None, kept.value, RADI_REFUSALS[rc]
     return p.value, mg.value, kept.value, None
+
+
+def host_radi_sweep_shifts(c, m, nb, H, R, want):
+    """``ricadi_host_radi_sweep_shifts``: the shifts of the next sweep of a RADI run with generated sweep shifts, from
+    what a sweep has fetched -- H = Q^T [cal A Q | cal E Q | R | U | B] for the c columns of the group's Q
+    (c x (2c + m + 2nb)) and R of its QR (c x c); host only.  Returns ``(ps, crit, kept, refusal)``: the admitted shifts
+    in acceptance order (at most ``want``) and their criteria, the size of the basis, and None or one of
+    ``RADI_REFUSALS``' names (ps and crit are then empty).  ValueError for bad sizes."""
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    c, m, nb, want = int(c), int(m), int(nb), int(want)
+    if min(c, m, nb) >= 1 and (H.size != c * (2 * c + m + 2 * nb) or R.size != c * c):
+        raise ValueError("H must be c x (2c + m + 2nb) and R c x c")
+    ps, crit = np.zeros(max(want, 1)), np.zeros(max(want, 1))
+    n, kept = C.c_int(0), C.c_int(0)
+    rc = load().ricadi_host_radi_sweep_shifts(c, m, nb, _d(H), _d(R), want, _d(ps), _d(crit), C.byref(n),
+                                              C.byref(kept))
+    if rc < 0:
+        _chk(rc)
+    if rc > 0:
+        return np.zeros(0), np.zeros(0), kept.value, RADI_REFUSALS[rc]
+    return ps[:n.value].copy(), crit[:n.value].copy(), kept.value, None
 
 
 def host_radi_sweep(shifts, m, nb, Ghat, Gamma, rhs, res_reltol, steps_left):

@@ -381,12 +381,18 @@ struct ricadi_ctx {
   // effective width, the sweeps run and the solves issued (ricadi_radi_sweep_info)
   int radi_sweep_width = 1;
   int radi_sweep_info[3] = {1, 0, 0};
+  // sweeps with generated shifts (ricadi_set_radi_sweep_shifts): the setting, and the solves of every
+  // sweep of the last call (ricadi_radi_sweep_widths)
+  int radi_sweep_shifts = 0;
+  std::vector<int> radi_sweep_widths;
   // per-shift data
   std::map<std::pair<double, double>, std::unique_ptr<ShiftData>> cache;
   // The ONE entry the RADI driver rebuilds for every generated shift (a level owns its own): it is lent to `cache`
   // under the shift's key for the duration of a step and taken back, so that generated shifts leave nothing in the
   // map and the buffers are reused from step to step and from call to call (OwnedShift, solver_radi.inl)
   std::unique_ptr<ShiftData> radi_sd;
+  // ... and the entries a sweep of generated shifts borrows the same way, one per solve of the sweep (OwnedShifts)
+  std::vector<std::unique_ptr<ShiftData>> radi_sdv;
   // workspaces
   int wcols = 0, wrestart = 0;   // total columns (width x groups) and restart length the workspace holds
   DArr<double> basis, vcur, wv, zv, r2, tp, rc, ec, xs, bvec, pw1, pw2;

@@ -1566,10 +1566,10 @@ static bool radi_hamiltonian(int k, int m, int nb, const double* H, std::vector<
 }
 
 // The rule: candidates are the eigenvalues of Ham in the open left half plane, one of each conjugate pair (Im >= 0);
-// criterion ||q|| / ||x|| of the eigenvector x = [r; q]; p = -|lambda| of the largest, margin = largest / second
-// largest (+inf with one candidate), p = 0 without a candidate.  wr / wi (2k each, may be NULL): all eigenvalues.
-int radi_shift_select(int k, int m, int nb, const double* H, double* p_out, double* margin_out, double* wr_out,
-                      double* wi_out) {
+// criterion ||q|| / ||x|| of the eigenvector x = [r; q]; the shift of a candidate is -|lambda|.  cands: (shift,
+// criterion) of every candidate in the order of the eigenvalues.  wr / wi (2k each, may be NULL): all eigenvalues.
+static int radi_shift_candidates(int k, int m, int nb, const double* H, double* wr_out, double* wi_out,
+                                 std::vector<std::pair<double, double>>& cands) {
   std::vector<double> ham;
   if (!radi_hamiltonian(k, m, nb, H, ham)) {
     set_error("ricadi_host_radi_shift: H_E is singular or H holds a value that is not finite");
@@ -1592,12 +1592,10 @@ int radi_shift_select(int k, int m, int nb, const double* H, double* p_out, doub
   }
   if (wr_out) std::copy(wr.begin(), wr.end(), wr_out);
   if (wi_out) std::copy(wi.begin(), wi.end(), wi_out);
-  double best = -1.0, second = -1.0, pbest = 0.0;
-  int ncand = 0;
+  cands.clear();
   std::vector<std::complex<double>> x;
   for (int i = 0; i < n; ++i) {
     if (!(wr[i] < 0.0) || wi[i] < 0.0) continue;
-    ++ncand;
     null_vector(n, ham, std::complex<double>(wr[i], wi[i]), x);
     double nq = 0.0, nx = 0.0;
     for (int j = 0; j < n; ++j) {
@@ -1605,15 +1603,30 @@ int radi_shift_select(int k, int m, int nb, const double* H, double* p_out, doub
       nx += v;
       if (j >= k) nq += v;
     }
-    const double crit = nx > 0.0 ? std::sqrt(nq / nx) : 0.0;
+    cands.emplace_back(-std::hypot(wr[i], wi[i]), nx > 0.0 ? std::sqrt(nq / nx) : 0.0);
+  }
+  return RICADI_OK;
+}
+
+// p = the shift of the candidate with the largest criterion (the first of equal ones), margin = largest / second
+// largest (+inf with one candidate), p = 0 without a candidate.
+int radi_shift_select(int k, int m, int nb, const double* H, double* p_out, double* margin_out, double* wr_out,
+                      double* wi_out) {
+  std::vector<std::pair<double, double>> cands;
+  const int rc = radi_shift_candidates(k, m, nb, H, wr_out, wi_out, cands);
+  if (rc != RICADI_OK) return rc;
+  double best = -1.0, second = -1.0, pbest = 0.0;
+  for (const auto& cd : cands) {
+    const double crit = cd.second;
     if (crit > best) {
       second = best;
       best = crit;
-      pbest = -std::hypot(wr[i], wi[i]);
+      pbest = cd.first;
     } else if (crit > second) {
       second = crit;
     }
   }
+  const int ncand = (int)cands.size();
   *p_out = ncand ? pbest : 0.0;
   if (margin_out)
     *margin_out = ncand >= 2 && second > 0.0 ? best / second : std::numeric_limits<double>::infinity();
@@ -1716,33 +1729,36 @@ static void jacobi_left_svd(int m, const double* R, std::vector<double>& A, std:
 // columns, and a block of up to 127 columns leaves a selection of order 2k <= 64.  The packed matrix handed to
 // radi_shift_select is  [S^T H_A S | S^T H_E S | S^T (H_R, H_U, H_B)]  (k x (2k + m + 2nb)).
 // Return values and *kept_out as radi_next_shift; here EVERY entry of R is looked at, not only its diagonal.
-int radi_next_shift_dominant(int m, int nb, const double* hH, const double* hR, double* p_out, double* margin_out,
-                             int* kept_out) {
-  const int hw = 3 * m + 2 * nb;
-  if (kept_out) *kept_out = 0;
-  for (int i = 0; i < m * m; ++i)
+// The basis Q S of a group of c columns against an m-column residual (c = m: the block of one step; c != m: the kept
+// blocks of a sweep): hH is c x (2c + m + 2nb), hR c x c; Hk the rotated k x (2k + m + 2nb).
+static int radi_dominant_rotate(int c, int m, int nb, const double* hH, const double* hR, std::vector<double>& Hk,
+                                int* k_out) {
+  const int hw = 2 * c + m + 2 * nb;
+  *k_out = 0;
+  for (int i = 0; i < c * c; ++i)
     if (!(std::fabs(hR[i]) <= std::numeric_limits<double>::max())) return RICADI_RADI_REFUSED_R_NOT_FINITE;
   std::vector<double> A, sig;
-  jacobi_left_svd(m, hR, A, sig);
-  std::vector<int> order(m);
+  jacobi_left_svd(c, hR, A, sig);
+  std::vector<int> order(c);
   std::iota(order.begin(), order.end(), 0);
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sig[a] > sig[b]; });
   const double smax = sig[order[0]];
   if (!(smax <= std::numeric_limits<double>::max())) return RICADI_RADI_REFUSED_R_NOT_FINITE;
   if (smax == 0.0) return RICADI_RADI_REFUSED_R_ZERO;
   int k = 0;
-  while (k < m && k < 32 && sig[order[k]] >= RICADI_RADI_RANK_TOL * smax) ++k;
-  if (kept_out) *kept_out = k;
+  while (k < c && k < 32 && sig[order[k]] >= RICADI_RADI_RANK_TOL * smax) ++k;
+  *k_out = k;
   // S by columns: S[a] = column order[a] of A over its norm
-  std::vector<double> S((size_t)k * m);
+  std::vector<double> S((size_t)k * c);
   for (int a = 0; a < k; ++a)
-    for (int i = 0; i < m; ++i) S[(size_t)a * m + i] = A[(size_t)order[a] * m + i] / sig[order[a]];
+    for (int i = 0; i < c; ++i) S[(size_t)a * c + i] = A[(size_t)order[a] * c + i] / sig[order[a]];
   // T = S^T H (k x hw), then the two projected operators once more from the right
   const int kw = 2 * k + m + 2 * nb;
-  std::vector<double> T((size_t)k * hw, 0.0), Hk((size_t)k * kw);
+  std::vector<double> T((size_t)k * hw, 0.0);
+  Hk.assign((size_t)k * kw, 0.0);
   for (int a = 0; a < k; ++a)
-    for (int i = 0; i < m; ++i) {
-      const double s = S[(size_t)a * m + i];
+    for (int i = 0; i < c; ++i) {
+      const double s = S[(size_t)a * c + i];
       const double* row = hH + (size_t)i * hw;
       double* out = T.data() + (size_t)a * hw;
       for (int j = 0; j < hw; ++j) out[j] += s * row[j];
@@ -1752,15 +1768,25 @@ int radi_next_shift_dominant(int m, int nb, const double* hH, const double* hR, 
     double* out = Hk.data() + (size_t)a * kw;
     for (int b = 0; b < k; ++b) {
       double sa = 0.0, se = 0.0;
-      for (int j = 0; j < m; ++j) {
-        sa += t[j] * S[(size_t)b * m + j];
-        se += t[m + j] * S[(size_t)b * m + j];
+      for (int j = 0; j < c; ++j) {
+        sa += t[j] * S[(size_t)b * c + j];
+        se += t[c + j] * S[(size_t)b * c + j];
       }
       out[b] = sa;
       out[k + b] = se;
     }
-    std::copy(t + 2 * m, t + hw, out + 2 * k);
+    std::copy(t + 2 * c, t + hw, out + 2 * k);
   }
+  return 0;
+}
+
+int radi_next_shift_dominant(int m, int nb, const double* hH, const double* hR, double* p_out, double* margin_out,
+                             int* kept_out) {
+  std::vector<double> Hk;
+  int k = 0;
+  const int refused = radi_dominant_rotate(m, m, nb, hH, hR, Hk, &k);
+  if (kept_out) *kept_out = k;
+  if (refused) return refused;
   double p = 0.0, margin = 0.0;
   if (radi_shift_select(k, m, nb, Hk.data(), &p, &margin, nullptr, nullptr) != RICADI_OK)
     return RICADI_RADI_REFUSED_BREAKDOWN;
@@ -1768,6 +1794,46 @@ int radi_next_shift_dominant(int m, int nb, const double* hH, const double* hR, 
   *p_out = p;
   if (margin_out) *margin_out = margin;
   return 0;
+}
+
+static long double radi_sweep_pivot(const double* ps, int g);
+
+// The shifts of the NEXT SWEEP from what a sweep has fetched (ricadi_set_radi_sweep_shifts): the
+// dominant rule on the group of c columns of Z the sweep kept (hH c x (2c + m + 2nb), hR c x c), all candidates ordered
+// by descending criterion (on an exact tie the larger |lambda| first), and of those up to `want`, greedily: a candidate
+// is admitted if it is finite and negative and the smallest Cauchy pivot of the admitted list with it appended
+// (cauchy_data's pivots, in acceptance order) stays >= RICADI_RADI_SWEEP_PIVOT.  ps_out / crit_out (want each): the
+// admitted shifts in acceptance order and their criteria, *n_out their number.  Returns 0, or a RICADI_RADI_REFUSED_*
+// value (NO_SHIFT where no candidate is admitted; *n_out = 0 then).  want = 1 is radi_next_shift_dominant's shift.
+int radi_next_shifts_dominant(int c, int m, int nb, const double* hH, const double* hR, int want, double* ps_out,
+                              double* crit_out, int* n_out, int* kept_out) {
+  *n_out = 0;
+  std::vector<double> Hk;
+  int k = 0;
+  const int refused = radi_dominant_rotate(c, m, nb, hH, hR, Hk, &k);
+  if (kept_out) *kept_out = k;
+  if (refused) return refused;
+  std::vector<std::pair<double, double>> cands;
+  if (radi_shift_candidates(k, m, nb, Hk.data(), nullptr, nullptr, cands) != RICADI_OK)
+    return RICADI_RADI_REFUSED_BREAKDOWN;
+  std::stable_sort(cands.begin(), cands.end(), [](const std::pair<double, double>& a, const std::pair<double, double>& b) {
+    return a.second > b.second || (a.second == b.second && a.first < b.first);
+  });
+  std::vector<double> acc;
+  for (const auto& cd : cands) {
+    if ((int)acc.size() >= want) break;
+    const double p = cd.first;
+    if (!(p < 0.0) || !(p >= -std::numeric_limits<double>::max())) continue;
+    acc.push_back(p);
+    if (radi_sweep_pivot(acc.data(), (int)acc.size()) >= (long double)RICADI_RADI_SWEEP_PIVOT) {
+      ps_out[acc.size() - 1] = p;
+      if (crit_out) crit_out[acc.size() - 1] = cd.second;
+    } else {
+      acc.pop_back();
+    }
+  }
+  *n_out = (int)acc.size();
+  return acc.empty() ? RICADI_RADI_REFUSED_NO_SHIFT : 0;
 }
 
 // ---- the sweep form of RADI (solver_radi.inl) ------------------------------------------------
@@ -2009,6 +2075,21 @@ int ricadi_host_radi_next_shift_dominant(int m, int nb, const double* H, const d
     return ricadi::radi_next_shift_dominant(m, nb, H, R, p_out, margin_out, kept_out);
   } catch (const std::exception&) {
     ricadi::set_error("ricadi_host_radi_next_shift_dominant: exception");
+    return RICADI_EHIP;
+  }
+}
+
+int ricadi_host_radi_sweep_shifts(int c, int m, int nb, const double* H, const double* R, int want, double* ps_out,
+                                  double* crit_out, int* n_out, int* kept_out) {
+  if (c < 1 || c > 127 || m < 1 || m > 127 || nb < 1 || nb > 64 || want < 1 || want > RICADI_MAX_GROUPS || !H || !R ||
+      !ps_out || !n_out) {
+    ricadi::set_error("ricadi_host_radi_sweep_shifts: bad argument (1 <= c, m <= 127, 1 <= nb <= 64, 1 <= want <= 16)");
+    return RICADI_EINVAL;
+  }
+  try {
+    return ricadi::radi_next_shifts_dominant(c, m, nb, H, R, want, ps_out, crit_out, n_out, kept_out);
+  } catch (const std::exception&) {
+    ricadi::set_error("ricadi_host_radi_sweep_shifts: exception");
     return RICADI_EHIP;
   }
 }

@@ -575,7 +575,8 @@ void launch_radi_update(hipStream_t st, int nv, int m, int nb, const int* rp, co
 // reduce: H (k x (2k + m + 2nb), row-major) = Q^T [cal A Q | cal E Q | R | U | B] for the shift selection: Q nv x k
 // (ld k), RU = [R | U] nv x (m + nb), B nv x nb; rp / ci / vA / vE the saddle pattern with its two value sources (rows
 // and columns below nv); 1 <= nb <= 64; sums in a fixed order (`partial`: radi_reduce_partial_len).  1 <= k, m <= 32:
-// radi_reduce_kernel; 33 <= k = m <= 127: radi_reduce_wide_kernel (output tiles on the FP64 matrix cores).
+// radi_reduce_kernel; 33 <= k <= 127: radi_reduce_wide_kernel (output tiles on the FP64 matrix cores), k = m a wide
+// block, k != m (1 <= m <= 127, 2k + m + 2nb <= 509) the group of blocks a sweep kept.
 size_t radi_reduce_partial_len(int nv, int k, int m, int nb);
 void launch_radi_reduce(hipStream_t st, int nv, int k, int m, int nb, const int* rp, const int* ci, const double* vA,
                         const double* vE, const double* Q, const double* RU, const double* B, double* partial,
@@ -592,6 +593,11 @@ int radi_next_shift(int m, int nb, const double* H, const double* R, double* p_o
 // ricadi_host_radi_next_shift_dominant).
 int radi_next_shift_dominant(int m, int nb, const double* H, const double* R, double* p_out, double* margin_out,
                              int* kept_out);
+// The shifts of the next sweep (ricadi_host_radi_sweep_shifts): the dominant rule on a group of c
+// columns (H c x (2c + m + 2nb), R c x c), the candidates ordered by criterion, up to `want` admitted greedily under the
+// sweep's pivot bound.  0 or a RICADI_RADI_REFUSED_* value.
+int radi_next_shifts_dominant(int c, int m, int nb, const double* H, const double* R, int want, double* ps_out,
+                              double* crit_out, int* n_out, int* kept_out);
 // The sweep form of RADI.  Host (ricadi_host.cpp; ricadi_host_radi_sweep / _sweep_width): the kept
 // steps, the residual after each and the coefficient matrix Cf (g m x (k m + m + nb)) from what a sweep has fetched;
 // the effective width of a cycled list; the column groups the batched solve makes of an (mw + nb)-wide panel.

@@ -14,7 +14,7 @@
 //   radi_reduce_kernel                         H = Q^T [cal A Q | cal E Q | R | U | B] for an orthonormal basis Q of the
 //                                              new block of Z: one pass over the rows of cal A and cal E, one partial
 //                                              per row slice, the slices summed by radi_vtb_reduce_kernel;
-//   radi_reduce_wide_kernel                    the same for blocks of 33 .. 127 columns: the
+//   radi_reduce_wide_kernel<GROUP>             the same for blocks of 33 .. 127 columns: the
 //                                              output tiled over workgroups, on the FP64 matrix cores.
 // The sweep form (G steps as one lockstep batch of solves) replaces the last two by
 //   radi_sweep_combine_kernel                  Z block = Vh Cf[:, :k m], [R | U] += (cal E Vh) Cf[:, k m:] for the dense
@@ -404,8 +404,12 @@ static int radi_reduce_slices(int n, int& rows_per_slice) {
 // radi_vtb_reduce_kernel: no atomics, every sum in a fixed order.
 // LDS (static): 16 x 144 + 16 x 80 doubles = 28 KB (leading dimensions = 16 mod 32 doubles: the four rows a wave
 // reads at once fall into different banks).
+// GROUP: the basis is a GROUP of c = k columns of Z against a residual of m != k columns
+// (W = 2k + m + 2nb <= 509): the same tiles, chunks and summation order, the dense tiles cover m + 2nb columns.  The
+// instantiation without it is the kernel of a single wide block (m_arg unused), its code and bits as before.
 constexpr int RADI_WB = 16, RADI_WCT = 64, RADI_WLQ = 144, RADI_WLY = 80;
-__global__ __launch_bounds__(256) void radi_reduce_wide_kernel(int nv, int k, int nb, int rows_per_slice,
+template <bool GROUP>
+__global__ __launch_bounds__(256) void radi_reduce_wide_kernel(int nv, int k, int m_arg, int nb, int rows_per_slice,
                                                                const int* __restrict__ rp, const int* __restrict__ ci,
                                                                const double* __restrict__ vA,
                                                                const double* __restrict__ vE,
@@ -415,7 +419,8 @@ __global__ __launch_bounds__(256) void radi_reduce_wide_kernel(int nv, int k, in
                                                                double* __restrict__ part) {
   __shared__ double qs[RADI_WB * RADI_WLQ];
   __shared__ double ys[RADI_WB * RADI_WLY];
-  const int W = 3 * k + 2 * nb, ldp = k + nb, ndense = ldp + nb;
+  const int m = GROUP ? m_arg : k;
+  const int W = 2 * k + m + 2 * nb, ldp = m + nb, ndense = ldp + nb;
   const int ngt = (k + 31) / 32, nrt = (k + 15) / 16, kp = 16 * nrt;
   const int t = blockIdx.y;
   const bool gather = t < ngt;
@@ -504,23 +509,27 @@ size_t radi_reduce_partial_len(int nv, int k, int m, int nb) {
   if (k > RADI_HK) return (size_t)radi_reduce_wide_slices(std::max(nv, 1), k, W, rps) * k * W;
   return (size_t)radi_reduce_slices(std::max(nv, 1), rps) * k * W;
 }
-static void launch_radi_reduce_wide(hipStream_t st, int nv, int k, int nb, const int* rp, const int* ci,
+static void launch_radi_reduce_wide(hipStream_t st, int nv, int k, int m, int nb, const int* rp, const int* ci,
                                     const double* vA, const double* vE, const double* Q, const double* RU,
                                     const double* B, double* partial, double* H) {
-  const int W = 3 * k + 2 * nb;
+  const int W = 2 * k + m + 2 * nb;
   int rps = 0;
   const int slices = radi_reduce_wide_slices(nv, k, W, rps);
-  const int tiles = (k + 31) / 32 + (k + 2 * nb + RADI_WCT - 1) / RADI_WCT;
-  hipLaunchKernelGGL(radi_reduce_wide_kernel, dim3(slices, tiles), dim3(256), 0, st, nv, k, nb, rps, rp, ci, vA, vE, Q,
-                     RU, B, partial);
+  const int tiles = (k + 31) / 32 + (m + 2 * nb + RADI_WCT - 1) / RADI_WCT;
+  if (m == k)
+    hipLaunchKernelGGL(radi_reduce_wide_kernel<false>, dim3(slices, tiles), dim3(256), 0, st, nv, k, m, nb, rps, rp, ci,
+                       vA, vE, Q, RU, B, partial);
+  else
+    hipLaunchKernelGGL(radi_reduce_wide_kernel<true>, dim3(slices, tiles), dim3(256), 0, st, nv, k, m, nb, rps, rp, ci,
+                       vA, vE, Q, RU, B, partial);
   hipLaunchKernelGGL(radi_vtb_reduce_kernel, dim3((k * W + 255) / 256), dim3(256), 0, st, slices, k * W, partial, H);
 }
 void launch_radi_reduce(hipStream_t st, int nv, int k, int m, int nb, const int* rp, const int* ci, const double* vA,
                         const double* vE, const double* Q, const double* RU, const double* B, double* partial,
                         double* H) {
   if (nv <= 0) return;
-  if (k > RADI_HK) {          // (k = m there: the callers check)
-    launch_radi_reduce_wide(st, nv, k, nb, rp, ci, vA, vE, Q, RU, B, partial, H);
+  if (k > RADI_HK) {          // (k = m: a wide block; k != m: the group of a sweep, W <= 509: the callers check)
+    launch_radi_reduce_wide(st, nv, k, m, nb, rp, ci, vA, vE, Q, RU, B, partial, H);
     return;
   }
   const int W = 2 * k + m + 2 * nb;

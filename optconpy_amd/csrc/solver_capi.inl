@@ -112,7 +112,7 @@ static void factor_download(ricadi_ctx* c, double* Z_out) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 411; }
+int ricadi_version(void) { return 412; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
@@ -282,6 +282,7 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   // the child level (same stream and rocBLAS handle) takes the coarse problem
   c->cache.clear();
   c->radi_sd.reset();
+  c->radi_sdv.clear();
   c->child.reset();
   if (hs.multilevel) {
     std::unique_ptr<ricadi_ctx> ch(new ricadi_ctx);
@@ -531,6 +532,7 @@ int ricadi_set_dims(ricadi_ctx* c, int nv) {
   REQUIRE(c && nv > 0, RICADI_EINVAL, "bad argument");
   c->cache.clear();
   c->radi_sd.reset();
+  c->radi_sdv.clear();
   for (auto& e : c->rec_ring) e->serial = -1;
   c->has_op = false;
   c->nv = nv;
@@ -960,8 +962,10 @@ static int check_radi(const ricadi_ctx* c, const double* shifts, int ns, const v
   REQUIRE(c->radi_shift_mode != RICADI_RADI_SHIFTS_HAMILTONIAN || mw <= 32, RICADI_EINVAL,
           "RICADI_RADI_SHIFTS_HAMILTONIAN needs mw <= 32");
   // (RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT: mw <= 127 and nb <= 64, which every mode needs and the lines above check)
-  REQUIRE(c->radi_sweep_width == 1 || c->radi_shift_mode == RICADI_RADI_SHIFTS_CYCLE, RICADI_EINVAL,
+  REQUIRE(c->radi_sweep_shifts || c->radi_sweep_width == 1 || c->radi_shift_mode == RICADI_RADI_SHIFTS_CYCLE, RICADI_EINVAL,
           "a RADI sweep width above 1 needs RICADI_RADI_SHIFTS_CYCLE: generated shifts are one at a time");
+  REQUIRE(!c->radi_sweep_shifts || c->radi_shift_mode == RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT, RICADI_EINVAL,
+          "ricadi_set_radi_sweep_shifts needs RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT");
   return RICADI_OK;
 }
 static void radi_stats_out(const RadiStats& s, double* stats_out) {
@@ -1041,6 +1045,21 @@ int ricadi_set_radi_shift_mode(ricadi_ctx* c, int mode) {
 int ricadi_set_radi_sweep_width(ricadi_ctx* c, int width) {
   REQUIRE(c && width >= 1 && width <= RICADI_MAX_GROUPS, RICADI_EINVAL, "1 <= width <= 16 required");
   c->radi_sweep_width = width;
+  return RICADI_OK;
+}
+// sweeps whose shifts the iteration generates (solver_radi.inl): returns the previous value
+int ricadi_set_radi_sweep_shifts(ricadi_ctx* c, int on) {
+  REQUIRE(c && (on == 0 || on == 1), RICADI_EINVAL, "on must be 0 or 1");
+  const int before = c->radi_sweep_shifts;
+  c->radi_sweep_shifts = on;
+  return before;
+}
+int ricadi_radi_sweep_widths(ricadi_ctx* c, int* out, int cap, int* n_out) {
+  REQUIRE(c && n_out && cap >= 0 && (out || cap == 0), RICADI_EINVAL, "bad argument");
+  REQUIRE(c->radi_ran, RICADI_ESTATE, "no RADI iteration has run on this context");
+  const int n = (int)c->radi_sweep_widths.size();
+  *n_out = n;
+  for (int i = 0; i < std::min(n, cap); ++i) out[i] = c->radi_sweep_widths[i];
   return RICADI_OK;
 }
 int ricadi_radi_sweep_info(ricadi_ctx* c, int* out) {

@@ -543,6 +543,21 @@ int ricadi_radi_reduce_wide_dev(ricadi_ctx* c, const double* dQ, int k, const do
   API_END
 }
 
+// the same for the group of blocks a sweep kept: c columns of Q against an m-column residual
+int ricadi_radi_reduce_group_dev(ricadi_ctx* c, const double* dQ, int cq, const double* dRU, int m, const double* dB,
+                                 int nb, double* dH_out) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(dQ && dRU && dB && dH_out, RICADI_EINVAL, "NULL argument");
+  REQUIRE(cq >= 1 && cq <= 127 && m >= 1 && m <= 127 && nb >= 1 && nb <= 64 && (cq > 32 || m <= 32) &&
+              2 * cq + m + 2 * nb <= 509,
+          RICADI_EINVAL, "1 <= c, m <= 127 (m <= 32 where c <= 32), 1 <= nb <= 64, 2c + m + 2nb <= 509 required");
+  API_BEGIN_ON(c)
+  TArr<double> part(c->pool, radi_reduce_partial_len(c->nv, cq, m, nb));
+  launch_radi_reduce(c->st, c->nv, cq, m, nb, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, dQ, dRU, dB, part.p, dH_out);
+  HIPCHK(hipStreamSynchronize(c->st));
+  API_END
+}
+
 int ricadi_probe_cache_entries(ricadi_ctx* c, int* n_out) {
   REQUIRE(c && n_out, RICADI_EINVAL, "NULL argument");
   size_t n = 0;

@@ -330,24 +330,30 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
     its first step; ``'hamiltonian'`` starts with ``adi_shifts.initial_shift`` of the operator and generates every
     later shift from the iteration itself -- ``ricadi_set_radi_shifts``; needs at most 32 columns in
     ``wmat``; ``'hamiltonian-dominant'`` is the same rule on the at most 32 dominant directions of the new block,
-    for a ``wmat`` of any width RADI takes -- DESIGN.md 3d-2), ``ms_fallback`` (with a generated ``ms`` only: a list of negative reals that replaces that one-element
+    for a ``wmat`` of any width RADI takes -- DESIGN.md 3d-2; ``'hamiltonian-sweep'`` is that rule in SWEEPS: the
+    iteration generates up to ``sweep_width`` shifts at a time from all blocks the last sweep kept and solves them in
+    ONE lockstep batch, ``ricadi_set_radi_sweep_shifts``, DESIGN.md 3d-4 -- ``sweep_width`` defaults to 8 for this
+    ``ms`` only, 1 .. 16 are accepted, and at 1 it is ``'hamiltonian-dominant'``), ``ms_fallback`` (with a generated ``ms`` only: a list of negative reals that replaces that one-element
     list -- its first entry starts, the list is cycled where a shift cannot be generated), ``radi_max_steps`` (200),
     ``radi_res_reltol`` (1e-10), ``compress_cols`` (the factor is recompressed whenever it has grown by that many
     columns; default 512), ``sweep_width`` (1; with a list of shifts, up to that many consecutive steps are solved
     in ONE lockstep batch against the same panel and recombined -- the sweep form; at most 16, what
-    runs is what the list allows; a ``ValueError`` with a generated ``ms``), ``verbose``, ``device_resident``.
+    runs is what the list allows; a ``ValueError`` with a generated ``ms`` other than ``'hamiltonian-sweep'``),
+    ``verbose``, ``device_resident``.
 
     Returns a dict: ``zfac`` (ndarray; a :class:`DeviceFactor` when given device panels or with
     ``device_resident``), ``gain`` = ``cal E X B`` (ndarray), ``radi_steps``, ``res_hist`` (the relative residual
     after every step), ``stop_rule`` (``_lib.RICADI_STOP_RES`` or ``_lib.RICADI_STOP_MAX_STEPS``),
     ``gmres_nonconverged``, ``shift_solves`` (every solve issued: with sweeps up to ``sweep_width - 1`` more than
     ``radi_steps``), ``gmres_iters``, ``sweep_width`` (the width that ran), ``sweeps`` (and ``ms`` / ``shift_info`` with ``ms='auto'``; with
-    a generated ``ms``: ``ms`` -- the shift of every step -- and ``shift_fallbacks``)."""
+    a generated ``ms``: ``ms`` -- the shift of every step -- and ``shift_fallbacks``; with ``'hamiltonian-sweep'`` also
+    ``sweep_widths``, the solves of every sweep, and ``sweep_width`` is the cap of the call)."""
     d = {} if radi_dict is None else radi_dict
     calA, calE = _orient(amat, mmat, transposed)
     ctx = backend.context_for(calA, calE, jmat)
     ctx.set_lowrank(None, None)
-    generated = isinstance(d.get("ms"), str) and d["ms"] in ("hamiltonian", "hamiltonian-dominant")
+    gensweep = isinstance(d.get("ms"), str) and d["ms"] == "hamiltonian-sweep"
+    generated = gensweep or (isinstance(d.get("ms"), str) and d["ms"] in ("hamiltonian", "hamiltonian-dominant"))
     sinfo = None
     if generated:
         fb = d.get("ms_fallback")
@@ -361,11 +367,14 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
               compress_cols=int(d.get("compress_cols", 0)), verbose=bool(d.get("verbose", False)))
     # the shift mode is a context setting: set for this call, and as before after it, also when the call fails
     # ... and so is the sweep width
-    width_before = ctx.set_radi_sweep_width(int(d.get("sweep_width", 1)))       # (the default MEANS width 1)
-    mode_before = None
+    # ... and the generated sweep shifts ('hamiltonian-sweep': the dominant mode, the setting, a default width of 8)
+    width_before = ctx.set_radi_sweep_width(int(d.get("sweep_width", 8 if gensweep else 1)))   # (else the default MEANS 1)
+    mode_before = sweep_shifts_before = None
     try:
         if generated:
-            mode_before = ctx.set_radi_shifts(d["ms"])
+            mode_before = ctx.set_radi_shifts("hamiltonian-dominant" if gensweep else d["ms"])
+        if gensweep:
+            sweep_shifts_before = ctx.set_radi_sweep_shifts(True)
         if d.get("device_resident", False) or any(_on_device(x) for x in (bmat, wmat, mtxoldb)):
             Zt, Kt, info = ctx.ric_radi_dev(ms, to_device(bmat).t, to_device(wmat).t,
                                             old_t=None if mtxoldb is None else to_device(mtxoldb).t, **kw)
@@ -374,6 +383,8 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
             Z, K, info = ctx.ric_radi(ms, _dense(bmat), _dense(wmat),
                                       oldB=None if mtxoldb is None else _dense(mtxoldb), **kw)
     finally:
+        if sweep_shifts_before is not None:
+            ctx.set_radi_sweep_shifts(sweep_shifts_before)
         if mode_before is not None:
             ctx.set_radi_shifts(mode_before)
         ctx.set_radi_sweep_width(width_before)
@@ -386,6 +397,8 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
         out["ms"], out["shift_info"] = list(ms), sinfo
     if generated:
         out["ms"], out["shift_fallbacks"] = list(ctx.radi_shift_history()), ctx.radi_shift_fallbacks()
+    if gensweep:
+        out["sweep_widths"] = [int(v) for v in ctx.radi_sweep_widths()]
     return out
 
 

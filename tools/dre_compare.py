@@ -8,6 +8,13 @@ time's gain and w from the other variant's.
 
     python tools/dre_compare.py --nts 2 [--N 106] [--nu 0.0025] [--radi-max-steps 200] [--out profiles/dre_radi_cfg4.jsonl]
 
+With ``--radi-sweep-width W`` a third variant runs beside the two: ``ms='hamiltonian-sweep'`` at that width (DESIGN.md
+3d-4; the cap of a step is min(W, 128 // columns of W, ...): 2 at 58 columns); its line carries the sweeps and the solves
+of every sweep per time step, and every variant's distances are to Newton-ADI (Newton-ADI's to RADI).  ``--append``
+adds the lines to ``--out`` instead of replacing it:
+
+    python tools/dre_compare.py --nts 2 --radi-sweep-width 8 --append --out profiles/dre_radi_sweep_cfg4.jsonl
+
 ``radi_max_steps`` bounds the factor the RADI call reserves (radi_max_steps x columns of W x NV doubles: 8.3 GB at 58
 columns, NV = 89 042 and 200 steps; the cfg4-dre steps need up to 143); the line reports the steps the runs needed.
 """
@@ -30,6 +37,8 @@ def main():
     ap.add_argument("--shifts", type=int, default=64)
     ap.add_argument("--radi-max-steps", type=int, default=200)
     ap.add_argument("--radi-res-reltol", type=float, default=1e-10)
+    ap.add_argument("--radi-sweep-width", type=int, default=0)
+    ap.add_argument("--append", action="store_true")
     ap.add_argument("--out", default=os.path.join("profiles", "dre_radi_cfg4.jsonl"))
     args = ap.parse_args()
 
@@ -46,6 +55,9 @@ def main():
     nad = dict(pb.default_nwtn_adi_dict(), ms=pb.logshifts(0.5, 2e3, args.shifts, interleave=True))
     radi_dict = dict(ms="hamiltonian-dominant", radi_max_steps=args.radi_max_steps,
                      radi_res_reltol=args.radi_res_reltol)
+    radi_dicts = {"radi": radi_dict}
+    if args.radi_sweep_width > 0:
+        radi_dicts["radi-sweep"] = dict(radi_dict, ms="hamiltonian-sweep", sweep_width=args.radi_sweep_width)
     NY2 = mct.shape[1]
 
     def ystar(t):
@@ -71,6 +83,9 @@ def main():
                 if name == "proj_alg_ric_radi":
                     r.update(steps=int(o["radi_steps"]), fallbacks=int(o["shift_fallbacks"]),
                              res_rel=float(o["res_hist"][-1]), stop_rule=int(o["stop_rule"]))
+                    if "sweep_widths" in o:
+                        r.update(sweep_cap=int(o["sweep_width"]), sweeps=int(o["sweeps"]),
+                                 sweep_widths=[int(v) for v in o["sweep_widths"]])
                 else:
                     r.update(steps=int(o["adi_steps"]), newton_steps=int(o["nwtn_steps"]))
                 rec.append(r)
@@ -87,8 +102,8 @@ def main():
                   vmat=pr.y_masmat, rhsv=np.zeros((pr.NV, 1)), gamma=1e-1, tmesh=tmesh, ystarvec=ystar,
                   nwtn_adi_dict=nad, comprz_thresh=5e-5, comprz_maxc=50, get_tdpart=tdpart,
                   get_datastr=lambda time=None, **k: "dre%d_t%.6f" % (tag, time), gtdtstrargs={})
-        if solver == "radi":
-            kw.update(ric_solver="radi", radi_dict=radi_dict)
+        if solver in radi_dicts:
+            kw.update(ric_solver="radi", radi_dict=radi_dicts[solver])
         del rec[:]
         store = MemoryStore()
         t0 = time.perf_counter()
@@ -98,7 +113,7 @@ def main():
         return el, list(rec), outs
 
     results = {}
-    for solver in ("newton-adi", "radi"):
+    for solver in ["newton-adi"] + list(radi_dicts):
         sweep(solver)                                            # warm-up
         results[solver] = sweep(solver)
 
@@ -107,7 +122,7 @@ def main():
 
     info = backend.context().setup_info()
     lines = []
-    for solver, other in (("newton-adi", "radi"), ("radi", "newton-adi")):
+    for solver, other in [("newton-adi", "radi")] + [(v, "newton-adi") for v in radi_dicts]:
         el, steps, outs = results[solver]
         line = dict(variant=solver, workload="cfg4-dre", N=args.N, n=int(pr.NV + pr.NP), nts=Nts,
                     seconds_per_sweep=round(el, 3), seconds_in_riccati=round(sum(r["seconds"] for r in steps), 3),
@@ -116,12 +131,12 @@ def main():
                     gain_rel_to_other=[rel(outs[t][0], results[other][2][t][0]) for t in tmesh],
                     w_rel_to_other=[rel(outs[t][1], results[other][2][t][1]) for t in tmesh],
                     preconditioner_levels=info["levels"])
-        if solver == "radi":
-            line.update(fallbacks=sum(r["fallbacks"] for r in steps), radi_dict=radi_dict,
+        if solver in radi_dicts:
+            line.update(fallbacks=sum(r["fallbacks"] for r in steps), radi_dict=radi_dicts[solver],
                         radi_steps_needed=max(r["steps"] for r in steps))
         lines.append(line)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
+    with open(args.out, "a" if args.append else "w") as fh:
         for line in lines:
             s = json.dumps(line)
             fh.write(s + "\n")

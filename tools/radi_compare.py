@@ -15,7 +15,14 @@ With --sweep-width W [W ...] the cycled list also runs in sweeps of those widths
 DESIGN.md 3d-3), in the same process and alternating with the others; their lines carry the effective width, the
 sweeps and the solves issued, and a "summary-sweeps" line per tolerance compares them with width 1.
 
-python tools/radi_compare.py [--N 58] [--trials 5] [--sweep-width 2 4 8] [--out profiles/radi_cfg2.json]"""
+With --gen-sweep-width W [W ...] the generated shifts also run in sweeps of up to W solves ("radi-hamsweepW":
+ms='hamiltonian-sweep'), alternating with the others; their lines carry the cap, the sweeps, the solves
+of every sweep and the shifts, and a "summary-gen-sweeps" line per tolerance compares them with 'hamiltonian', with the
+cycled list at the widest --sweep-width and with Newton-ADI.  --only PREFIX [PREFIX ...] runs just the variants whose
+names start so and prints no summaries (for a RICADI_TIMING=1 run of a few variants).
+
+python tools/radi_compare.py [--N 58] [--trials 5] [--sweep-width 2 4 8] [--gen-sweep-width 2 4 8]
+                             [--out profiles/radi_cfg2.json]"""
 import argparse
 import json
 import os
@@ -37,6 +44,8 @@ def main():
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--tols", type=float, nargs="+", default=[1e-6, 1e-7, 1e-8, 1e-10, 1e-12])
     ap.add_argument("--sweep-width", type=int, nargs="*", default=[])
+    ap.add_argument("--gen-sweep-width", type=int, nargs="*", default=[])
+    ap.add_argument("--only", nargs="*", default=[])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import sadptprj_riclyap_adi.lin_alg_utils as lau
@@ -68,12 +77,15 @@ def main():
                        nonconverged=out["gmres_nonconverged"])
 
     def radi(tol, generated=False, width=1):
+        gensweep = generated and width > 1
         def run():
             ctx.clear_cache()
             out = pru.proj_alg_ric_radi(mmat=pr.M, amat=F, jmat=pr.J, bmat=tb_d, wmat=trct_d,
-                                        radi_dict=dict(ms="hamiltonian" if generated else ms, radi_res_reltol=tol,
-                                                       radi_max_steps=400, sweep_width=width))
-            info = dict(path="radi-ham" if generated else "radi" if width == 1 else "radi-sweep%d" % width,
+                                        radi_dict=dict(ms="hamiltonian-sweep" if gensweep else "hamiltonian" if generated
+                                                       else ms, radi_res_reltol=tol, radi_max_steps=400,
+                                                       sweep_width=width))
+            info = dict(path="radi-hamsweep%d" % width if gensweep else "radi-ham" if generated else "radi" if width == 1
+                        else "radi-sweep%d" % width,
                         radi_res_reltol=tol, steps=out["radi_steps"], sweep_width=out["sweep_width"],
                         sweeps=out["sweeps"],
                         shift_solves=out["shift_solves"], gmres_iters=out["gmres_iters"],
@@ -81,12 +93,18 @@ def main():
                         stop_rule=out["stop_rule"], last_res=float(out["res_hist"][-1]))
             if generated:
                 info.update(shift_fallbacks=out["shift_fallbacks"], shifts=[float(p) for p in out["ms"]])
+            if gensweep:
+                info.update(sweep_widths=out["sweep_widths"])
             return -out["gain"], info
         return run
 
     variants = ([("newton-adi", newton)] + [("radi %g" % t, radi(t)) for t in args.tols]
                 + [("radi-ham %g" % t, radi(t, generated=True)) for t in args.tols]
-                + [("radi-sweep%d %g" % (w, t), radi(t, width=w)) for w in args.sweep_width if w > 1 for t in args.tols])
+                + [("radi-sweep%d %g" % (w, t), radi(t, width=w)) for w in args.sweep_width if w > 1 for t in args.tols]
+                + [("radi-hamsweep%d %g" % (w, t), radi(t, generated=True, width=w)) for w in args.gen_sweep_width if w > 1
+                   for t in args.tols])
+    if args.only:
+        variants = [v for v in variants if any(v[0].startswith(p) for p in args.only)]
     rec, times = {}, {name: [] for name, _ in variants}
     for name, fn in variants:                         # warm-up: every shape the timed calls use
         K, info = fn()
@@ -102,6 +120,9 @@ def main():
         rec[name].update(N=args.N, n=pr.NV + pr.NP, ms_median=statistics.median(times[name]), ms_best=min(times[name]),
                          ms_all=[round(t, 2) for t in times[name]], trials=args.trials)
         lines.append(rec[name])
+    if args.only:
+        print("\n".join(json.dumps(l) for l in lines))
+        return
     nd = rec["newton-adi"]["K_vs_fixture"]
     pick = None
     for t in sorted(args.tols, reverse=True):
@@ -130,6 +151,23 @@ def main():
                                   ms=r["ms_median"], width1_ms=c["ms_median"], width1_steps=c["steps"],
                                   width1_gmres_iters=c["gmres_iters"], K_vs_fixture=r["K_vs_fixture"],
                                   speedup=c["ms_median"] / r["ms_median"]))
+    wmax = max([w for w in args.sweep_width if w > 1], default=None)
+    for t in args.tols:                               # generated shifts in sweeps against one per step, tolerance by tolerance
+        h = rec["radi-ham %g" % t]
+        for w in args.gen_sweep_width:
+            if w > 1:
+                r = rec["radi-hamsweep%d %g" % (w, t)]
+                cyc = None if wmax is None else rec["radi-sweep%d %g" % (wmax, t)]
+                lines.append(dict(path="summary-gen-sweeps", radi_res_reltol=t, asked=w, cap=r["sweep_width"],
+                                  steps=r["steps"], sweeps=r["sweeps"], shift_solves=r["shift_solves"],
+                                  sweep_widths=r["sweep_widths"], gmres_iters=r["gmres_iters"], ms=r["ms_median"],
+                                  ms_spread=[min(r["ms_all"]), max(r["ms_all"])], fallbacks=r["shift_fallbacks"],
+                                  one_per_step_ms=h["ms_median"], one_per_step_steps=h["steps"],
+                                  one_per_step_gmres_iters=h["gmres_iters"],
+                                  cycled_sweep_ms=None if cyc is None else cyc["ms_median"],
+                                  cycled_sweep_width=wmax, cycled_sweep_steps=None if cyc is None else cyc["steps"],
+                                  newton_ms=nt, K_vs_fixture=r["K_vs_fixture"],
+                                  speedup_vs_one_per_step=h["ms_median"] / r["ms_median"]))
     text = "\n".join(json.dumps(l) for l in lines)
     print(text)
     if args.out:

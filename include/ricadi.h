@@ -717,6 +717,44 @@ int ricadi_qr(ricadi_ctx* ctx, const double* Z, int c, double* Q_out, double* R_
 int ricadi_project_pencil(ricadi_ctx* ctx, const double* Q, int k, double* HA, double* HE);
 int ricadi_project_pencil_dev(ricadi_ctx* ctx, const double* dQ, int k, double* dHA, double* dHE);
 
+/* ---- balanced truncation from two low-rank factors (exports added under ABI 412) ----
+ * ricadi_cross_gram_dev: G = X^T Y (p x q row-major, leading dimension q) of two row-major DEVICE panels, X n x p with
+ *   leading dimension ldx >= p, Y n x q with ldy >= q, 1 <= p, q <= 1024; dG a device buffer of p q doubles.  A 32 x 32
+ *   tile per wave on the FP64 matrix cores, row slices summed in a fixed order and no atomics: the same inputs give
+ *   bitwise the same G.  Needs a context, not an operator.
+ * ricadi_project_pencil_twosided_dev: the Petrov-Galerkin form of K7,
+ *   HA = L^T (cal A - U V^T) Rb,  HE = L^T cal E Rb  (r x r row-major),
+ *   for a left basis L and a right basis Rb (NV x r row-major device panels, 1 <= r <= 128): one pass over the velocity
+ *   rows of the operator, rows gathered from Rb and multiplied by the workgroup's own rows of L; partials summed in
+ *   workgroup order, bitwise reproducible.  With L = Rb = Q it is ricadi_project_pencil_dev's pencil.
+ * ricadi_lqg_balance_dev: square-root balancing of two factors on the RESIDENT operator, which must be set in the
+ *   orientation cal A = A, cal E = M of the system M v' = A v + J^T p + B u, y = C v -- the one the filter equation's
+ *   solve (transposed=True) leaves resident.  dZc (NV x kc, X = Zc Zc^T the regulator / observability factor) and dZf
+ *   (NV x kf, Y = Zf Zf^T the filter / reachability factor), dB (NV x nb) and dCt = C^T (NV x nc) are device panels with
+ *   leading dimension = width, 1 <= kc, kf, nb, nc <= 1024.  S = Zc^T cal E Zf = U Sigma V^T (host Jacobi SVD),
+ *   r = #{sigma_i > tol sigma_1} capped by order (order <= 0: no cap), by 128, kc, kf and NV; 0 <= tol < 1.
+ *   T_l = Zc U_r Sigma_r^-1/2 -> dTl, T_r = Zf V_r Sigma_r^-1/2 -> dTr (device, NV x r, leading dimension r; buffers of
+ *   NV rcap doubles, rcap the cap above), so that T_l^T cal E T_r = I_r;  *r_out = r;  sigma_out (host, min(kc, kf)
+ *   doubles): all singular values, descending -- the LQG characteristic values when the factors solve the two Riccati
+ *   equations, the Hankel singular values when they solve the two Lyapunov equations.  Host outputs, row-major with the
+ *   leading dimension of their width:  Ar_out = T_l^T cal A T_r and Er_out = T_l^T cal E T_r (r x r; buffers rcap^2),
+ *   Br_out = T_l^T B (r x nb; rcap nb), Cr_out = C T_r (nc x r; nc rcap).  A low-rank term of the context is part of
+ *   cal A (at most 1024 columns).  RICADI_EHIP with a message when S is zero or not finite or its SVD did not converge.
+ * ricadi_host_lqg_balance: the host step alone (no GPU, no context): S kc x kf row-major; outputs r, sigma_out
+ *   (min(kc, kf)), coefl_out = U_r Sigma_r^-1/2 (kc x r) and coefr_out = V_r Sigma_r^-1/2 (kf x r), leading dimension r,
+ *   in buffers of kc (kf) times min(kc, kf, order) doubles: coefl^T S coefr = I_r.  RICADI_EINVAL for a bad argument or
+ *   an entry of S that is not finite, RICADI_EBREAKDOWN for S = 0, RICADI_ENOCONV if the Jacobi iteration has not
+ *   converged in its 60 sweeps (nothing is written then).                                                   */
+int ricadi_cross_gram_dev(ricadi_ctx* ctx, int n, int p, int q, const double* dX, int ldx, const double* dY, int ldy,
+                          double* dG);
+int ricadi_project_pencil_twosided_dev(ricadi_ctx* ctx, const double* dL, const double* dRb, int r, double* dHA,
+                                       double* dHE);
+int ricadi_lqg_balance_dev(ricadi_ctx* ctx, const double* dZc, int kc, const double* dZf, int kf, const double* dB,
+                           int nb, const double* dCt, int nc, double tol, int order, int* r_out, double* sigma_out,
+                           double* dTl, double* dTr, double* Ar_out, double* Er_out, double* Br_out, double* Cr_out);
+int ricadi_host_lqg_balance(int kc, int kf, const double* S, double tol, int order, int* r_out, double* sigma_out,
+                            double* coefl_out, double* coefr_out);
+
 /* Structure of the preconditioner the context built for its operator:
  * out = [NV, NP, velocity blocks, Schur blocks, block size, coarse dimension,
  *        SpMM row blocks, max distinct columns per row block,

@@ -138,6 +138,12 @@ SIGNATURES = {
     "ricadi_qr": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "ricadi_project_pencil": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "ricadi_project_pencil_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    "ricadi_cross_gram_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
+    "ricadi_project_pencil_twosided_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),
+    "ricadi_lqg_balance_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_double,
+                                         C.c_int, C.POINTER(C.c_int), _dp, _vp, _vp, _dp, _dp, _dp, _dp]),
+    "ricadi_host_lqg_balance": (C.c_int, [C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.POINTER(C.c_int), _dp, _dp,
+                                          _dp]),
     "ricadi_setup_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
     "ricadi_time_qr_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "ricadi_time_gram_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _dp]),
@@ -1199,6 +1205,71 @@ def _project_pencil_dev(self, q_ptr, k, ha_ptr, he_ptr):
 
 Context.project_pencil = _project_pencil
 Context.project_pencil_dev = _project_pencil_dev
+
+
+def _cross_gram_dev(self, n, p, q, x_ptr, ldx, y_ptr, ldy, g_ptr):
+    """``G = X^T Y`` (p x q, row-major) of two row-major device panels (``X`` n x p with leading dimension ``ldx``,
+    ``Y`` n x q with ``ldy``; p, q <= 1024) on the FP64 matrix cores, sums in a fixed order: bitwise reproducible."""
+    _chk(self._lib.ricadi_cross_gram_dev(self._h, int(n), int(p), int(q), x_ptr, int(ldx), y_ptr, int(ldy), g_ptr))
+
+
+def _project_pencil_twosided_dev(self, l_ptr, rb_ptr, r, ha_ptr, he_ptr):
+    """``(H_A, H_E) = (L^T (cal A - U V^T) Rb, L^T cal E Rb)`` for two NV x r device panels (r <= 128): the two-sided
+    form of :meth:`project_pencil_dev`.  Bitwise reproducible."""
+    self._need_op()
+    _chk(self._lib.ricadi_project_pencil_twosided_dev(self._h, l_ptr, rb_ptr, int(r), ha_ptr, he_ptr))
+
+
+def _lqg_balance_dev(self, zc_t, zf_t, b_t, ct_t, tol, order):
+    """``ricadi_lqg_balance_dev`` on contiguous float64 CUDA tensors ``Zc`` (NV x kc), ``Zf`` (NV x kf), ``B``
+    (NV x nb), ``C^T`` (NV x nc); the resident operator must be ``(cal A, cal E) = (A, M)``.  Returns
+    ``(r, sigma, T_l, T_r, A_r, E_r, B_r, C_r)``: ``T_l`` / ``T_r`` CUDA tensors (NV x r), the rest ndarrays."""
+    import torch
+    self._need_op()
+    nv = self.nv
+    kc, kf, nb, nc = zc_t.shape[1], zf_t.shape[1], b_t.shape[1], ct_t.shape[1]
+    for t, w in ((zc_t, kc), (zf_t, kf), (b_t, nb), (ct_t, nc)):
+        if t.shape[0] != nv or not t.is_contiguous() or t.dtype != torch.float64 or not 1 <= w <= 1024:
+            raise ValueError("panels must be contiguous float64 NV x w tensors, 1 <= w <= 1024")
+    order = int(order) if order else 0
+    rcap = min(kc, kf, nv, MAX_M, order if order > 0 else MAX_M)
+    tl = torch.empty(nv * rcap, dtype=torch.float64, device=zc_t.device)
+    tr = torch.empty(nv * rcap, dtype=torch.float64, device=zc_t.device)
+    sig = np.zeros(min(kc, kf))
+    ar, er = np.zeros(rcap * rcap), np.zeros(rcap * rcap)
+    br, cr = np.zeros(rcap * nb), np.zeros(nc * rcap)
+    r = C.c_int(0)
+    torch.cuda.current_stream().synchronize()
+    _chk(self._lib.ricadi_lqg_balance_dev(self._h, zc_t.data_ptr(), kc, zf_t.data_ptr(), kf, b_t.data_ptr(), nb,
+                                          ct_t.data_ptr(), nc, float(tol), order, C.byref(r), _d(sig), tl.data_ptr(),
+                                          tr.data_ptr(), _d(ar), _d(er), _d(br), _d(cr)))
+    r = r.value
+    return (r, sig, tl[:nv * r].view(nv, r), tr[:nv * r].view(nv, r), ar[:r * r].reshape(r, r).copy(),
+            er[:r * r].reshape(r, r).copy(), br[:r * nb].reshape(r, nb).copy(), cr[:nc * r].reshape(nc, r).copy())
+
+
+Context.cross_gram_dev = _cross_gram_dev
+Context.project_pencil_twosided_dev = _project_pencil_twosided_dev
+Context.lqg_balance_dev = _lqg_balance_dev
+
+
+def host_lqg_balance(S, tol=1e-12, order=0):
+    """``ricadi_host_lqg_balance``: the host step of the square-root balancing, ``S = Zc^T M Zf`` (kc x kf) -> ``(r,
+    sigma, coefL, coefR)`` with ``sigma`` all singular values (descending), ``r = #{sigma_i > tol sigma_1}`` capped by
+    ``order`` (0: no cap), ``coefL = U_r Sigma_r^-1/2`` (kc x r), ``coefR = V_r Sigma_r^-1/2`` (kf x r); host only.
+    ValueError for a bad argument or an ``S`` that is not finite, RuntimeError for ``S = 0``."""
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    if S.ndim != 2 or S.size == 0:
+        raise ValueError("S must be a non-empty matrix")
+    kc, kf = S.shape
+    order = int(order) if order else 0
+    rcap = min(kc, kf, order) if order > 0 else min(kc, kf)
+    sig, cl, cr = np.zeros(min(kc, kf)), np.zeros(kc * rcap), np.zeros(kf * rcap)
+    r = C.c_int(0)
+    rc = load().ricadi_host_lqg_balance(kc, kf, _d(S), float(tol), order, C.byref(r), _d(sig), _d(cl), _d(cr))
+    _chk(rc)
+    r = r.value
+    return r, sig, cl[:kc * r].reshape(kc, r).copy(), cr[:kf * r].reshape(kf, r).copy()
 
 
 def _vanka_records(call):

@@ -1287,6 +1287,101 @@ void launch_gram_fixed(hipStream_t st, int n, int nc, const double* P, int ldp, 
   hipLaunchKernelGGL(gram_fixed_reduce_kernel, dim3((unsigned)(((size_t)nc * nc + 255) / 256)), dim3(256), 0, st,
                      slices, nc, 32 * nt, partial, G);
 }
+// ---------------------------------------------------------------------------
+// K4x: the cross-Gram matrix G = X^T Y of two row-major panels (X: n x p, ld ldx; Y: n x q, ld ldy; p, q <= 1024),
+// gram_fixed_kernel's scheme without the symmetry: a 32 x 32 tile per wave on v_mfma_f64_16x16x4_f64, row slices
+// across workgroups, the four waves of a workgroup summed in wave order in LDS, one partial per slice;
+// cross_gram_reduce_kernel sums the slices in slice order.  Every tile block is written.  No atomics: the same
+// panels give bitwise the same G (the balancing step's S = Zc^T (M Zf), L^T B, Rb^T C^T).
+// ---------------------------------------------------------------------------
+// part: [slices][pp][qp], pp = 32 * gridDim.y, qp = 32 * gridDim.z; every entry is written
+__global__ __launch_bounds__(256) void cross_gram_kernel(int n, int p, int q, const double* __restrict__ X, int ldx,
+                                                         const double* __restrict__ Y, int ldy, int rows_per_wave,
+                                                         double* __restrict__ part) {
+  __shared__ double red[4][16][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lc = lane & 15, lk = lane >> 4;
+  const int i0 = 32 * blockIdx.y, j0 = 32 * blockIdx.z;
+  const int rbeg = (blockIdx.x * 4 + wave) * rows_per_wave;
+  const int rend = min(n, rbeg + rows_per_wave);
+  d4 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = (d4){0.0, 0.0, 0.0, 0.0};
+  for (int r = rbeg; r < rend; r += 4) {
+    const int rr = r + lk;
+    const bool rok = rr < rend;
+    double af[2], bf[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const int ca = i0 + 16 * a + lc, cb = j0 + 16 * a + lc;
+      af[a] = (rok && ca < p) ? X[(size_t)rr * ldx + ca] : 0.0;
+      bf[a] = (rok && cb < q) ? Y[(size_t)rr * ldy + cb] : 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+        acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
+  }
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) red[wave][(a * 2 + b) * 4 + e][lane] = acc[a][b][e];
+  __syncthreads();
+  if (wave != 0) return;
+  const int pp = 32 * gridDim.y, qp = 32 * gridDim.z;
+  double* out = part + (size_t)blockIdx.x * pp * qp;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int t = (a * 2 + b) * 4 + e;
+        const double v = (red[0][t][lane] + red[1][t][lane]) + (red[2][t][lane] + red[3][t][lane]);
+        out[(size_t)(i0 + 16 * a + lk + 4 * e) * qp + j0 + 16 * b + lc] = v;
+      }
+}
+// G (p x q, ld q) = sum of the slices' partials in slice order
+__global__ __launch_bounds__(256) void cross_gram_reduce_kernel(int slices, int p, int q, int pp, int qp,
+                                                                const double* __restrict__ part,
+                                                                double* __restrict__ G) {
+  const size_t idx = blockIdx.x * (size_t)256 + threadIdx.x;
+  if (idx >= (size_t)p * q) return;
+  const int i = (int)(idx / q), j = (int)(idx % q);
+  const double* s0 = part + (size_t)i * qp + j;
+  double s = 0.0;
+  for (int w = 0; w < slices; ++w) s += s0[(size_t)w * pp * qp];
+  G[idx] = s;
+}
+// row slices of the cross-Gram matrix: enough workgroups to fill the chip, partials kept below 64 MB
+static int cross_gram_slices(int n, int p, int q, int& rows_per_wave) {
+  const int pt = (p + 31) / 32, qt = (q + 31) / 32;
+  const size_t per_slice = (size_t)(32 * pt) * (32 * qt) * sizeof(double);
+  int slices = std::min((n + 255) / 256, std::max(1, 2048 / (pt * qt)));
+  slices = std::max(1, std::min(slices, (int)(((size_t)64 << 20) / per_slice)));
+  rows_per_wave = (((n + slices * 4 - 1) / (slices * 4)) + 3) & ~3;
+  return (n + 4 * rows_per_wave - 1) / (4 * rows_per_wave);
+}
+size_t cross_gram_partial_len(int n, int p, int q) {
+  int rpw = 0;
+  const int pt = (p + 31) / 32, qt = (q + 31) / 32;
+  return (size_t)cross_gram_slices(n, p, q, rpw) * (32 * pt) * (32 * qt);
+}
+void launch_cross_gram(hipStream_t st, int n, int p, int q, const double* X, int ldx, const double* Y, int ldy,
+                       double* partial, double* G) {
+  if (n <= 0 || p <= 0 || q <= 0) return;
+  int rpw = 0;
+  const int slices = cross_gram_slices(n, p, q, rpw);
+  const int pt = (p + 31) / 32, qt = (q + 31) / 32;
+  hipLaunchKernelGGL(cross_gram_kernel, dim3(slices, pt, qt), dim3(256), 0, st, n, p, q, X, ldx, Y, ldy, rpw, partial);
+  hipLaunchKernelGGL(cross_gram_reduce_kernel, dim3((unsigned)(((size_t)p * q + 255) / 256)), dim3(256), 0, st,
+                     slices, p, q, 32 * pt, 32 * qt, partial, G);
+}
 void launch_sweep_resid_panel(hipStream_t st, int nrows, int m, int nslot, const int* rp, const int* ci,
                               const double* ev, const double* W, const double* U, size_t ustride, double* P) {
   const size_t tot = (size_t)nrows * (nslot + 1) * m;

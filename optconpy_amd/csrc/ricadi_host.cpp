@@ -1685,15 +1685,16 @@ int radi_next_shift(int m, int nb, const double* hH, const double* hR, double* p
 // Sweeps over all pairs in a fixed order until no pair's cosine exceeds 1e-15 sqrt(m), the rounding error of the
 // cosine itself (at most 60 sweeps).  A: the rotated
 // matrix, COLUMN by column (A[j m + i] = entry (i, j)); sig: the column norms.
-static void jacobi_left_svd(int m, const double* R, std::vector<double>& A, std::vector<double>& sig) {
-  A.resize((size_t)m * m);
-  for (int i = 0; i < m; ++i)
-    for (int j = 0; j < m; ++j) A[(size_t)j * m + i] = R[(size_t)i * m + j];
+// jacobi_rotate_columns is the iteration for `cols` columns of length `rows`; V (optional, cols x cols, column by column,
+// the identity on entry) takes the same rotations, so that A_in V = A_out.  Returns whether a sweep without a rotation
+// was reached (false: the 60 sweeps ran out and the columns may not be orthogonal to the tolerance).
+static bool jacobi_rotate_columns(int rows, int cols, std::vector<double>& A, double* V) {
+  const int m = rows;
   const double tol = 1e-15 * std::sqrt((double)m);
   for (int sweep = 0; sweep < 60; ++sweep) {
     bool rotated = false;
-    for (int p = 0; p < m - 1; ++p)
-      for (int q = p + 1; q < m; ++q) {
+    for (int p = 0; p < cols - 1; ++p)
+      for (int q = p + 1; q < cols; ++q) {
         double* ap = A.data() + (size_t)p * m;
         double* aq = A.data() + (size_t)q * m;
         double a = 0.0, b = 0.0, g = 0.0;
@@ -1712,15 +1713,80 @@ static void jacobi_left_svd(int m, const double* R, std::vector<double>& A, std:
           ap[i] = cs * x - sn * y;
           aq[i] = sn * x + cs * y;
         }
+        if (V) {
+          double* vp = V + (size_t)p * cols;
+          double* vq = V + (size_t)q * cols;
+          for (int i = 0; i < cols; ++i) {
+            const double x = vp[i], y = vq[i];
+            vp[i] = cs * x - sn * y;
+            vq[i] = sn * x + cs * y;
+          }
+        }
       }
-    if (!rotated) break;
+    if (!rotated) return true;
   }
-  sig.resize(m);
-  for (int j = 0; j < m; ++j) {
+  return false;
+}
+static void column_norms(int rows, int cols, const std::vector<double>& A, std::vector<double>& sig) {
+  sig.resize(cols);
+  for (int j = 0; j < cols; ++j) {
     double s = 0.0;
-    for (int i = 0; i < m; ++i) s += A[(size_t)j * m + i] * A[(size_t)j * m + i];
+    for (int i = 0; i < rows; ++i) s += A[(size_t)j * rows + i] * A[(size_t)j * rows + i];
     sig[j] = std::sqrt(s);
   }
+}
+static void jacobi_left_svd(int m, const double* R, std::vector<double>& A, std::vector<double>& sig) {
+  A.resize((size_t)m * m);
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < m; ++j) A[(size_t)j * m + i] = R[(size_t)i * m + j];
+  (void)jacobi_rotate_columns(m, m, A, nullptr);       // (the shift selection takes what 60 sweeps give, as before)
+  column_norms(m, m, A, sig);
+}
+
+// ---- square-root balancing of two low-rank factors (ricadi_host_lqg_balance) -----------------
+// S = Zc^T M Zf (kc x kf, row-major) = U Sigma V^T by the Jacobi iteration above on the SHORTER side's columns (S when
+// kc >= kf, else S^T), the rotations accumulated for the other side's vectors.  r = #{sigma_i > tol sigma_1}, at most
+// `order` (order <= 0: no cap).  sig_out: all min(kc, kf) values, descending.  coefL (kc x r) = U_r Sigma_r^-1/2 and
+// coefR (kf x r) = V_r Sigma_r^-1/2, row-major with leading dimension r, so that coefL^T S coefR = I_r; the caller's
+// buffers hold kc (kf) times min(kc, kf, order) doubles.  RICADI_ENOCONV (nothing written but *r_out = 0) if the
+// iteration has not converged in its 60 sweeps.
+int lqg_balance(int kc, int kf, const double* S, double tol, int order, int* r_out, double* sig_out, double* coefL,
+                double* coefR) {
+  *r_out = 0;
+  bool nonzero = false;
+  for (size_t i = 0; i < (size_t)kc * kf; ++i) {
+    if (!(std::fabs(S[i]) <= std::numeric_limits<double>::max())) return RICADI_EINVAL;
+    nonzero = nonzero || S[i] != 0.0;
+  }
+  if (!nonzero) return RICADI_EBREAKDOWN;
+  const bool tall = kc >= kf;                    // rotate the columns of S itself
+  const int rows = tall ? kc : kf, cols = tall ? kf : kc;
+  std::vector<double> A((size_t)rows * cols), W((size_t)cols * cols, 0.0), sig;
+  for (int j = 0; j < cols; ++j) {
+    W[(size_t)j * cols + j] = 1.0;
+    for (int i = 0; i < rows; ++i) A[(size_t)j * rows + i] = tall ? S[(size_t)i * kf + j] : S[(size_t)j * kf + i];
+  }
+  if (!jacobi_rotate_columns(rows, cols, A, W.data())) return RICADI_ENOCONV;
+  column_norms(rows, cols, A, sig);
+  std::vector<int> idx(cols);
+  std::iota(idx.begin(), idx.end(), 0);
+  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return sig[a] > sig[b]; });
+  const double smax = sig[idx[0]];
+  if (!(smax > 0.0) || !(smax <= std::numeric_limits<double>::max())) return RICADI_EBREAKDOWN;
+  for (int a = 0; a < cols; ++a) sig_out[a] = sig[idx[a]];
+  int r = 0;
+  while (r < cols && (order <= 0 || r < order) && sig[idx[r]] > tol * smax) ++r;
+  *r_out = r;
+  // the long vectors (columns of A over their norms) belong to the side that was rotated, the accumulated ones to the other
+  double* longc = tall ? coefL : coefR;
+  double* shortc = tall ? coefR : coefL;
+  for (int a = 0; a < r; ++a) {
+    const int j = idx[a];
+    const double sg = sig[j], sq = 1.0 / std::sqrt(sg);
+    for (int i = 0; i < rows; ++i) longc[(size_t)i * r + a] = A[(size_t)j * rows + i] / sg * sq;
+    for (int i = 0; i < cols; ++i) shortc[(size_t)i * r + a] = W[(size_t)j * cols + i] * sq;
+  }
+  return RICADI_OK;
 }
 
 // radi_next_shift with the basis Q S in place of a choice of columns of Q (RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT;
@@ -2090,6 +2156,24 @@ int ricadi_host_radi_sweep_shifts(int c, int m, int nb, const double* H, const d
     return ricadi::radi_next_shifts_dominant(c, m, nb, H, R, want, ps_out, crit_out, n_out, kept_out);
   } catch (const std::exception&) {
     ricadi::set_error("ricadi_host_radi_sweep_shifts: exception");
+    return RICADI_EHIP;
+  }
+}
+
+int ricadi_host_lqg_balance(int kc, int kf, const double* S, double tol, int order, int* r_out, double* sigma_out,
+                            double* coefl_out, double* coefr_out) {
+  if (kc < 1 || kf < 1 || !S || !(tol >= 0.0 && tol < 1.0) || !r_out || !sigma_out || !coefl_out || !coefr_out) {
+    ricadi::set_error("ricadi_host_lqg_balance: bad argument (kc, kf >= 1, 0 <= tol < 1)");
+    return RICADI_EINVAL;
+  }
+  try {
+    const int rc = ricadi::lqg_balance(kc, kf, S, tol, order, r_out, sigma_out, coefl_out, coefr_out);
+    if (rc == RICADI_EINVAL) ricadi::set_error("ricadi_host_lqg_balance: S has an entry that is not finite");
+    if (rc == RICADI_EBREAKDOWN) ricadi::set_error("ricadi_host_lqg_balance: S is zero");
+    if (rc == RICADI_ENOCONV) ricadi::set_error("ricadi_host_lqg_balance: the Jacobi SVD did not converge in 60 sweeps");
+    return rc;
+  } catch (const std::exception&) {
+    ricadi::set_error("ricadi_host_lqg_balance: exception");
     return RICADI_EHIP;
   }
 }

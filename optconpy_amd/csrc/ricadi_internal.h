@@ -457,6 +457,11 @@ void launch_project_pencil(hipStream_t st, int nv, int k, const int* rp, const i
                            const double* vE, const double* Q, const double* U, const double* V, int q,
                            double* part, double* HA, double* HE);
 void launch_project_lowrank(hipStream_t st, int k, int q, const double* QU, const double* QV, double* HA);
+// the two-sided form: HA = L^T cal A Rb, HE = L^T cal E Rb (r x r; L, Rb: NV x r row-major, r <= 128);
+// part: project_part_count(nv, r, r) doubles
+void launch_project_pencil_twosided(hipStream_t st, int nv, int r, const int* rp, const int* ci, const double* vA,
+                                    const double* vE, const double* L, const double* Rb, double* part, double* HA,
+                                    double* HE);
 
 // coloured Vanka sweep of a child level (ricadi_precond.hip): the patch matrices S[idx, idx] of up to RICADI_MAX_GROUPS
 // shifts per launch (mats[i]: npatches x 64 x 64 of shift i; patches from first_lone on: diagonal only); one colour
@@ -560,6 +565,11 @@ void launch_sweep_resid_panel(hipStream_t st, int nrows, int m, int nslot, const
                               const double* ev, const double* W, const double* U, size_t ustride, double* P);
 size_t gram_fixed_partial_len(int n, int nc);
 void launch_gram_fixed(hipStream_t st, int n, int nc, const double* P, int ldp, double* partial, double* G);
+// K4x: the cross-Gram matrix G = X^T Y (p x q, ld q) of two row-major panels (n x p, ld ldx; n x q, ld ldy;
+// p, q <= 1024), the same scheme with every tile block written (`partial`: cross_gram_partial_len doubles)
+size_t cross_gram_partial_len(int n, int p, int q);
+void launch_cross_gram(hipStream_t st, int n, int p, int q, const double* X, int ldx, const double* Y, int ldy,
+                       double* partial, double* G);
 
 // K6: the dense part of a RADI step (ricadi_radi.hip).  vtb: G (m x nb) = V^T B of V (n rows, leading dimension ldv)
 // and B (n x nb), sums in a fixed order (`partial`: radi_vtb_partial_len doubles).  factor: one workgroup, m <= 127,
@@ -598,6 +608,12 @@ int radi_next_shift_dominant(int m, int nb, const double* H, const double* R, do
 // sweep's pivot bound.  0 or a RICADI_RADI_REFUSED_* value.
 int radi_next_shifts_dominant(int c, int m, int nb, const double* H, const double* R, int want, double* ps_out,
                               double* crit_out, int* n_out, int* kept_out);
+// Square-root balancing of two factors (ricadi_host_lqg_balance): S (kc x kf) = U Sigma V^T by
+// the host Jacobi iteration, r = #{sigma_i > tol sigma_1} capped by order (<= 0: no cap), sig_out the min(kc, kf) values,
+// coefL = U_r Sigma_r^-1/2 (kc x r), coefR = V_r Sigma_r^-1/2 (kf x r), leading dimension r.  RICADI_OK, RICADI_EINVAL
+// (an entry that is not finite), RICADI_EBREAKDOWN (S = 0) or RICADI_ENOCONV (60 sweeps without convergence).
+int lqg_balance(int kc, int kf, const double* S, double tol, int order, int* r_out, double* sig_out, double* coefL,
+                double* coefR);
 // The sweep form of RADI.  Host (ricadi_host.cpp; ricadi_host_radi_sweep / _sweep_width): the kept
 // steps, the residual after each and the coefficient matrix Cf (g m x (k m + m + nb)) from what a sweep has fetched;
 // the effective width of a cycled list; the column groups the batched solve makes of an (mw + nb)-wide panel.

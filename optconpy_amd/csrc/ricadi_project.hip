@@ -9,6 +9,9 @@
 // contiguous Q rows on v_mfma_f64_16x16x4_f64.  The result is a k x k partial per workgroup; a second kernel
 // sums the partials in workgroup order.  No atomics: the same inputs give bitwise the same H.
 //
+// The two-sided form (TWOSIDED) multiplies the products formed from a right basis by the rows of a second, left basis:
+// L^T cal A Rb and L^T cal E Rb, the reduced pencil of a balanced truncation.
+//
 // The dense form of the same kernel (Y = two dense NV x q panels instead of the two sparse products) gives
 // Q^T U and Q^T V of the low-rank term, so H_A - (Q^T U)(V^T Q) is reproducible as well.
 #include "ricadi_device.h"
@@ -19,12 +22,15 @@ namespace ricadi {
 // D[row = (l>>4) + 4*reg][col = l&15].
 //
 // part: [gridDim.x][2][kp][np2], kp = 16 * ceil(k / 16), np2 = 16 * gridDim.y; every entry is written.
-template <bool DENSE>
+// TWOSIDED (the Petrov-Galerkin form, L^T cal A Q and L^T cal E Q): the workgroup's own rows come from the left basis L
+// (NV x k as Q), the gathered rows from Q as before; without it L is not read and the arithmetic is the one-basis one.
+template <bool DENSE, bool TWOSIDED>
 __global__ __launch_bounds__(256) void project_pencil_kernel(int nv, int k, int n2, int rows_per_wg,
                                                              const int* __restrict__ rp, const int* __restrict__ ci,
                                                              const double* __restrict__ vA,
                                                              const double* __restrict__ vE,
                                                              const double* __restrict__ Q,
+                                                             const double* __restrict__ L,
                                                              const double* __restrict__ U,
                                                              const double* __restrict__ V,
                                                              double* __restrict__ part) {
@@ -46,6 +52,7 @@ __global__ __launch_bounds__(256) void project_pencil_kernel(int nv, int k, int 
     accE[t] = (d4){0.0, 0.0, 0.0, 0.0};
   }
   const int col = j0 + jj;
+  const double* __restrict__ own = TWOSIDED ? L : Q;
   for (int r0 = rbeg; r0 < rend; r0 += 16) {
     const int row = r0 + rr;
     double a = 0.0, e = 0.0;
@@ -74,7 +81,7 @@ __global__ __launch_bounds__(256) void project_pencil_kernel(int nv, int k, int 
       for (int t = 0; t < 2; ++t) {
         const int i = 16 * (wave + 4 * t) + lc;
         if (wave + 4 * t < kt) {
-          const double aq = (rk < rend && i < k) ? Q[(size_t)rk * k + i] : 0.0;
+          const double aq = (rk < rend && i < k) ? own[(size_t)rk * k + i] : 0.0;
           accA[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq, bA, accA[t], 0, 0, 0);
           accE[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq, bE, accE[t], 0, 0, 0);
         }
@@ -144,14 +151,28 @@ void launch_project_pencil(hipStream_t st, int nv, int k, const int* rp, const i
   int rpw = 0;
   const int nwg = project_grid(nv, ct, rpw);
   if (dense)
-    hipLaunchKernelGGL(project_pencil_kernel<true>, dim3(nwg, ct), dim3(256), 0, st, nv, k, n2, rpw, rp, ci, vA,
-                       vE, Q, U, V, part);
+    hipLaunchKernelGGL((project_pencil_kernel<true, false>), dim3(nwg, ct), dim3(256), 0, st, nv, k, n2, rpw, rp, ci,
+                       vA, vE, Q, Q, U, V, part);
   else
-    hipLaunchKernelGGL(project_pencil_kernel<false>, dim3(nwg, ct), dim3(256), 0, st, nv, k, n2, rpw, rp, ci, vA,
-                       vE, Q, U, V, part);
+    hipLaunchKernelGGL((project_pencil_kernel<false, false>), dim3(nwg, ct), dim3(256), 0, st, nv, k, n2, rpw, rp, ci,
+                       vA, vE, Q, Q, U, V, part);
   const int tot = 2 * k * n2;
   hipLaunchKernelGGL(project_reduce_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, nwg, k, n2,
                      16 * ((k + 15) / 16), 16 * ct, part, HA, HE);
+}
+
+// H_A = L^T cal A Rb, H_E = L^T cal E Rb (r x r): the same pass, grid and partial layout with both bases
+void launch_project_pencil_twosided(hipStream_t st, int nv, int r, const int* rp, const int* ci, const double* vA,
+                                    const double* vE, const double* L, const double* Rb, double* part, double* HA,
+                                    double* HE) {
+  const int ct = (r + 15) / 16;
+  int rpw = 0;
+  const int nwg = project_grid(nv, ct, rpw);
+  hipLaunchKernelGGL((project_pencil_kernel<false, true>), dim3(nwg, ct), dim3(256), 0, st, nv, r, r, rpw, rp, ci, vA,
+                     vE, Rb, L, nullptr, nullptr, part);
+  const int tot = 2 * r * r;
+  hipLaunchKernelGGL(project_reduce_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, nwg, r, r, 16 * ct, 16 * ct,
+                     part, HA, HE);
 }
 
 void launch_project_lowrank(hipStream_t st, int k, int q, const double* QU, const double* QV, double* HA) {

@@ -836,6 +836,106 @@ int ricadi_project_pencil(ricadi_ctx* c, const double* Q, int k, double* HA, dou
   API_END
 }
 
+// ---- balanced truncation from two factors ----
+// G = X^T Y on device panels, fixed summation order
+static void cross_gram_dev(ricadi_ctx* c, int n, int p, int q, const double* dX, int ldx, const double* dY, int ldy,
+                           double* dG) {
+  TArr<double> part(c->pool, cross_gram_partial_len(n, p, q));
+  launch_cross_gram(c->st, n, p, q, dX, ldx, dY, ldy, part.p, dG);
+  HIPCHK(hipGetLastError());
+}
+
+int ricadi_cross_gram_dev(ricadi_ctx* c, int n, int p, int q, const double* dX, int ldx, const double* dY, int ldy,
+                          double* dG) {
+  REQUIRE(c && dX && dY && dG, RICADI_EINVAL, "NULL argument");
+  REQUIRE(n >= 1 && p >= 1 && p <= 1024 && q >= 1 && q <= 1024 && ldx >= p && ldy >= q, RICADI_EINVAL,
+          "n >= 1, 1 <= p, q <= 1024, ldx >= p and ldy >= q required");
+  API_BEGIN_ON(c)
+  cross_gram_dev(c, n, p, q, dX, ldx, dY, ldy, dG);
+  HIPCHK(hipStreamSynchronize(c->st));
+  API_END
+}
+
+// H_A = L^T (cal A - U V^T) Rb, H_E = L^T cal E Rb on device panels; the low-rank term through two cross-Gram matrices
+static void project_pencil_twosided_dev(ricadi_ctx* c, const double* dL, const double* dRb, int r, double* dHA,
+                                        double* dHE) {
+  const int nv = c->nv, q = c->q;
+  TArr<double> part(c->pool, project_part_count(nv, r, r));
+  launch_project_pencil_twosided(c->st, nv, r, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, dL, dRb, part.p, dHA, dHE);
+  if (q > 0) {
+    TArr<double> lu(c->pool, (size_t)r * q), rv(c->pool, (size_t)r * q);
+    cross_gram_dev(c, nv, r, q, dL, r, c->U.p, q, lu.p);
+    cross_gram_dev(c, nv, r, q, dRb, r, c->V.p, q, rv.p);
+    launch_project_lowrank(c->st, r, q, lu.p, rv.p, dHA);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->st));
+}
+
+int ricadi_project_pencil_twosided_dev(ricadi_ctx* c, const double* dL, const double* dRb, int r, double* dHA,
+                                       double* dHE) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(dL && dRb && dHA && dHE && r >= 1 && r <= RICADI_MAX_M, RICADI_EINVAL, "bad argument (1 <= r <= 128)");
+  REQUIRE(c->q <= 1024, RICADI_EINVAL, "the low-rank term of the context has more than 1024 columns");
+  API_BEGIN_ON(c)
+  project_pencil_twosided_dev(c, dL, dRb, r, dHA, dHE);
+  API_END
+}
+
+int ricadi_lqg_balance_dev(ricadi_ctx* c, const double* dZc, int kc, const double* dZf, int kf, const double* dB, int nb,
+                           const double* dCt, int nc, double tol, int order, int* r_out, double* sigma_out, double* dTl,
+                           double* dTr, double* Ar_out, double* Er_out, double* Br_out, double* Cr_out) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(dZc && dZf && dB && dCt && r_out && sigma_out && dTl && dTr && Ar_out && Er_out && Br_out && Cr_out,
+          RICADI_EINVAL, "NULL argument");
+  REQUIRE(kc >= 1 && kc <= 1024 && kf >= 1 && kf <= 1024 && nb >= 1 && nb <= 1024 && nc >= 1 && nc <= 1024,
+          RICADI_EINVAL, "1 <= kc, kf, nb, nc <= 1024 required");
+  REQUIRE(tol >= 0.0 && tol < 1.0, RICADI_EINVAL, "0 <= tol < 1 required");
+  REQUIRE(c->q <= 1024, RICADI_EINVAL, "the low-rank term of the context has more than 1024 columns");
+  *r_out = 0;
+  API_BEGIN_ON(c)
+  hipStream_t st = c->st;
+  const int nv = c->nv;
+  const int rcap = std::min(std::min(kc, kf), std::min(order > 0 ? order : RICADI_MAX_M, std::min(RICADI_MAX_M, nv)));
+  // S = Zc^T (cal E Zf): the product in panels of at most RICADI_MAX_M columns, then one cross-Gram matrix
+  TArr<double> EZ(c->pool, (size_t)nv * kf), dS(c->pool, (size_t)kc * kf);
+  for (int c0 = 0; c0 < kf; c0 += RICADI_MAX_M) {
+    const int w = std::min(RICADI_MAX_M, kf - c0);
+    launch_spmm(st, nv, c->E.rp.p, c->E.ci.p, c->E.v.p, dZf + c0, kf, nullptr, EZ.p + c0, kf, nullptr, 0, 1.0, 0.0,
+                nullptr, w);
+  }
+  cross_gram_dev(c, nv, kc, kf, dZc, kc, EZ.p, kf, dS.p);
+  std::vector<double> S((size_t)kc * kf), cl((size_t)kc * rcap), cr((size_t)kf * rcap);
+  HIPCHK(hipMemcpyAsync(S.data(), dS.p, sizeof(double) * S.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  int r = 0;
+  const int rc = lqg_balance(kc, kf, S.data(), tol, rcap, &r, sigma_out, cl.data(), cr.data());
+  if (rc == RICADI_ENOCONV) throw ricadi::HipError{"ricadi_lqg_balance_dev: the Jacobi SVD of Zc^T cal E Zf did not converge"};
+  if (rc != RICADI_OK) throw ricadi::HipError{"ricadi_lqg_balance_dev: Zc^T cal E Zf is zero or not finite"};
+  *r_out = r;
+  // T_l = Zc (U_r Sigma_r^-1/2), T_r = Zf (V_r Sigma_r^-1/2)
+  TArr<double> dcl(c->pool, (size_t)kc * r), dcr(c->pool, (size_t)kf * r);
+  HIPCHK(hipMemcpyAsync(dcl.p, cl.data(), sizeof(double) * kc * r, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dcr.p, cr.data(), sizeof(double) * kf * r, hipMemcpyHostToDevice, st));
+  launch_gemm_nn(st, nv, kc, r, dZc, kc, dcl.p, r, dTl, r, 1.0, 0.0);
+  launch_gemm_nn(st, nv, kf, r, dZf, kf, dcr.p, r, dTr, r, 1.0, 0.0);
+  // the reduced model: [A_r | E_r | B_r | C_r^T]
+  const size_t rr = (size_t)r * r;
+  TArr<double> dH(c->pool, 2 * rr + (size_t)r * (nb + nc));
+  project_pencil_twosided_dev(c, dTl, dTr, r, dH.p, dH.p + rr);
+  cross_gram_dev(c, nv, r, nb, dTl, r, dB, nb, dH.p + 2 * rr);
+  cross_gram_dev(c, nv, r, nc, dTr, r, dCt, nc, dH.p + 2 * rr + (size_t)r * nb);
+  std::vector<double> crt((size_t)r * nc);
+  HIPCHK(hipMemcpyAsync(Ar_out, dH.p, sizeof(double) * rr, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(Er_out, dH.p + rr, sizeof(double) * rr, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(Br_out, dH.p + 2 * rr, sizeof(double) * r * nb, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(crt.data(), dH.p + 2 * rr + (size_t)r * nb, sizeof(double) * r * nc, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < nc; ++i)
+    for (int a = 0; a < r; ++a) Cr_out[(size_t)i * r + a] = crt[(size_t)a * nc + i];
+  API_END
+}
+
 int ricadi_lyap_adi(ricadi_ctx* c, const double* shifts, int ns, const double* W, int m,
                     const ricadi_adi_params* prm, double* Z_out, int* c_out, double* stats_out) {
   if (int rc = check_panel(c, m)) return rc;

@@ -175,18 +175,51 @@ int ricadi_synchronize(ricadi_ctx* ctx);
  *  /root/reference/optcont_main.py:488-492, solve_dae_ric.py:152-159) and of
  * lau.solve_sadpnt_smw (/root/reference/solve_dae_ric.py:192-194).
  * A = cal A, E = cal E already in the orientation they are applied in
- * (the Python shim resolves `transposed`).                                  */
+ * (the Python shim resolves `transposed`).
+ *
+ * Replacing an operator.  A context may be given one operator after another,
+ * of any size, constraint count and hierarchy depth:
+ *  - A replacement forgets everything tied to the resident operator: the
+ *    per-shift cache (child levels included), the child level, the low-rank
+ *    term (q = 0), the resident factor, the workspace sizes, the recycled
+ *    right-hand sides and their solutions, and everything a reporter says "of
+ *    the last call" (ADI residual history and stop rule, RADI shift history,
+ *    fallbacks, sweep info and widths, the probes' last-call counters, the
+ *    kernel forms of ricadi_setup_info): asked right after the call, a
+ *    reporter answers as a fresh context's does.
+ *  - A replacement keeps the settings (options, ricadi_set_recycle, the RADI
+ *    shift mode, sweep width and sweep shifts, ricadi_set_adi_res_history, the
+ *    probe's refuse list, the exchange) and the counters documented as
+ *    cumulative (ricadi_solve_trace, the iteration totals,
+ *    ricadi_exchange_count).  Device buffers keep their capacity.
+ *  - The solves are iterative and start from zero: after a replacement the
+ *    context computes what a fresh context with the same options computes.
+ *  - A replacement refused during validation leaves the old operator intact:
+ *    NULL arrays, bad sizes, a column index out of range, a refusal of the
+ *    host setup.  The old operator, its cache and its factor answer as before.
+ *  - A replacement that fails after it began leaves no operator: every call
+ *    that needs one refuses with "set the operator first" until
+ *    ricadi_set_operator or ricadi_set_dims succeeds.                        */
 int ricadi_set_operator(ricadi_ctx* ctx, int nv, int np,
                         const int32_t* a_rowptr, const int32_t* a_col, const double* a_val,
                         const int32_t* e_rowptr, const int32_t* e_col, const double* e_val,
                         const int32_t* j_rowptr, const int32_t* j_col, const double* j_val);
 
 /* Drop the per-shift data (assembled values, block inverses, coarse inverse)
- * cached for every (alpha, beta) used so far; they are rebuilt on demand.    */
+ * cached for every (alpha, beta) used so far; they are rebuilt on demand.
+ * ricadi_clear_cache forgets the per-shift data and the recycled right-hand
+ * sides, on every level; it keeps the operator, the child level, the low-rank
+ * term, the resident factor, the settings and every reporter's last answer.
+ * It also keeps the slots of the ring of recycled right-hand sides (emptied):
+ * they refill in another order than a new context's growing ring, so recycled
+ * initial guesses after it may differ from a new context's in the last bits.   */
 int ricadi_clear_cache(ricadi_ctx* ctx);
 
 /* Dimension-only context (no operator): enough for ricadi_compress and for
- * ricadi_gain with an explicit `mt_*` matrix, which need NV only.           */
+ * ricadi_gain with an explicit `mt_*` matrix, which need NV only.
+ * ricadi_set_dims forgets exactly what ricadi_set_operator forgets (one helper
+ * serves both) and keeps what it keeps; the context then has no operator until
+ * the next ricadi_set_operator.                                              */
 int ricadi_set_dims(ricadi_ctx* ctx, int nv);
 
 /* Low-rank term  - U * Vt ;  U is NV x q row-major, V is NV x q row-major

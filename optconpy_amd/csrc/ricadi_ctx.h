@@ -430,9 +430,12 @@ struct ricadi_ctx {
   DArr<int> info2;
   hipEvent_t ev_z = nullptr;
   // recycling of solved right-hand sides: ring of the last shared rhs panels (nv x w; pressure rows are zero)
+  // rows: the nv the panel was stored with -- b holds rows * w doubles, so only entries with rows == nv may be read
+  // with the resident operator's row count (the panel rebuild of recycle_store, the Gram paths of recycle_guess)
   struct RecB {
     long serial = -1;
     int w = 0;
+    int rows = 0;
     DArr<double> b;
   };
   std::vector<std::unique_ptr<RecB>> rec_ring;

@@ -244,6 +244,44 @@ int ricadi_synchronize(ricadi_ctx* c) {
   API_END
 }
 
+// Everything a context holds that is tied to the resident operator or left by calls on it ("what a context
+// remembers"): ricadi_set_operator -- the child level's included -- and ricadi_set_dims forget through this one
+// helper, so they cannot differ in what they forget.  Workspaces and scratch keep their capacity; settings (recycle
+// depth, RADI modes, the probe's refuse list, the exchange, the options) and the cumulative counters (solve trace,
+// total_iters, exchange count) stay.  Leaves has_op false: the caller says what the context describes next.
+static void forget_operator(ricadi_ctx* c) {
+  c->has_op = false;
+  c->cache.clear();
+  c->radi_sd.reset();
+  c->radi_sdv.clear();
+  c->child.reset();
+  c->q = 0;
+  c->zc = 0;
+  c->wcols = 0;                // workspaces depend on n
+  // the ring goes, slots and all: recycle_guess lists its entries in slot order, so a ring that kept its (invalid)
+  // slots would fill them in another order than a fresh context's growing ring, and the normal equations of the same
+  // guess would come out permuted -- other rounding, other bits (found by tests/test_gpu_context_reuse.py)
+  c->rec_ring.clear();
+  c->rec_pan_w = 0;
+  c->lr_ucol = -1;
+  // "of the last call": a reporter asked now answers as a fresh context's does
+  c->adi_ran = false;
+  c->adi_res_hist.clear();
+  c->adi_stop_rule = 0;
+  c->radi_ran = false;
+  c->radi_shift_hist.clear();
+  c->radi_fallbacks = 0;
+  c->radi_kept_hist.clear();
+  c->radi_qr_repeats = c->radi_recompressions = 0;
+  c->radi_sweep_info[0] = 1;
+  c->radi_sweep_info[1] = c->radi_sweep_info[2] = 0;
+  c->radi_sweep_widths.clear();
+  c->w32_last = c->mid32_last = -1;
+  c->k1_variant = -1;
+  c->coarse_route = -1;
+  c->probe = ricadi_ctx::ArnoldiProbe();
+}
+
 int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, const int32_t* a_ci,
                         const double* a_v, const int32_t* e_rp, const int32_t* e_ci,
                         const double* e_v, const int32_t* j_rp, const int32_t* j_ci,
@@ -279,11 +317,13 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   const HostCsr JT = transpose(J);
   const HostSetup hs = build_setup_checked(A, E, J, JT, c->opts, c->levels, sa_omega);
   const PrecondRecords pr = build_records(hs, J, JT, c->sw.sweep_meta, c->sw.ms_spmm);
+  // validation ends here: what follows replaces the resident operator.  has_op is false from this first mutation to
+  // the last statement, and the sizes are zero until the upload sets them, so a replacement that fails half way leaves
+  // a context that refuses every call ("set the operator first") instead of one that describes the old operator
+  // without its child level and its cache
+  forget_operator(c);
+  c->nv = c->np = c->n = 0;
   // the child level (same stream and rocBLAS handle) takes the coarse problem
-  c->cache.clear();
-  c->radi_sd.reset();
-  c->radi_sdv.clear();
-  c->child.reset();
   if (hs.multilevel) {
     std::unique_ptr<ricadi_ctx> ch(new ricadi_ctx);
     ch->dev = c->dev;
@@ -401,10 +441,6 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
   c->sybE.upload(pr.sybE, st);
   c->syb_lidx_ms.upload(pr.syb_lidx_ms, st);
   HIPCHK(hipStreamSynchronize(st));
-  c->q = 0;
-  c->wcols = 0;  // workspaces depend on n
-  c->zc = 0;
-  c->has_op = true;
   if (c->opts.verbose) {
     if (pr.gt_ok)
       fprintf(stderr, "[ricadi] last velocity sweep in rectangular form: <= %d pressure dofs per block (slice width %d)\n",
@@ -415,6 +451,7 @@ int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, cons
             nv, np, c->snnz, c->nbv, c->nbp, c->bs, c->kc, hs.kcv, hs.kcp, hs.sb_nblk,
             hs.sb_max_cols, hs.sb_max_nnz, hs.sb_nblk ? (double)hs.sb_cols.size() / hs.sb_nblk : 0.0);
   }
+  c->has_op = true;
   API_END
 }
 
@@ -530,17 +567,10 @@ int ricadi_exchange_count(ricadi_ctx* c, int64_t* count_out) {
 
 int ricadi_set_dims(ricadi_ctx* c, int nv) {
   REQUIRE(c && nv > 0, RICADI_EINVAL, "bad argument");
-  c->cache.clear();
-  c->radi_sd.reset();
-  c->radi_sdv.clear();
-  for (auto& e : c->rec_ring) e->serial = -1;
-  c->has_op = false;
+  forget_operator(c);
   c->nv = nv;
   c->np = 0;
   c->n = nv;
-  c->q = 0;
-  c->zc = 0;
-  c->wcols = 0;
   return RICADI_OK;
 }
 

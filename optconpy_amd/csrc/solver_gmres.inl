@@ -661,12 +661,12 @@ static bool recycle_guess(ricadi_ctx* c, ShiftData* const* sds, int G, const dou
   {
     std::vector<long> ser;
     for (auto& e : c->rec_ring)
-      if (e && e->serial >= 0) ser.push_back(e->serial);
+      if (e && e->serial >= 0 && e->rows == c->nv) ser.push_back(e->serial);
     std::sort(ser.begin(), ser.end());
     if ((int)ser.size() > c->rec_depth && c->rec_depth > 0) oldest = ser[ser.size() - (size_t)c->rec_depth];
   }
   for (auto& e : c->rec_ring) {
-    if (!e || e->serial < oldest) continue;
+    if (!e || e->serial < oldest || e->rows != c->nv) continue;
     bool all = true;
     for (int g = 0; g < G && all; ++g) {
       bool has = false;
@@ -770,6 +770,7 @@ static void recycle_store(ricadi_ctx* c, ShiftData* const* sds, int G, const dou
   }
   slot->serial = ++c->rec_serial;
   slot->w = m;
+  slot->rows = c->nv;
   slot->b.ensure((size_t)c->nv * m);
   HIPCHK(hipMemcpyAsync(slot->b.p, b, sizeof(double) * c->nv * m, hipMemcpyDeviceToDevice, st));
   {
@@ -782,7 +783,7 @@ static void recycle_store(ricadi_ctx* c, ShiftData* const* sds, int G, const dou
       HIPCHK(hipMemsetAsync(c->rec_pan.p, 0, sizeof(double) * (size_t)c->nv * 8 * m, st));
       c->rec_pan_w = m;
       for (auto& e : c->rec_ring)
-        if (e.get() != slot && e->serial >= 0 && e->w == m)
+        if (e.get() != slot && e->serial >= 0 && e->w == m && e->rows == c->nv)
           launch_copy_cols(st, c->nv, m, e->b.p, m, 0, c->rec_pan.p, 8 * m, (int)(&e - &c->rec_ring[0]) * m, 1.0);
     }
     if (si < 8) launch_copy_cols(st, c->nv, m, b, m, 0, c->rec_pan.p, 8 * m, si * m, 1.0);

@@ -1002,6 +1002,13 @@ int ricadi_host_aggregate(int n, const int32_t* rowptr, const int32_t* col,
  * amplify the solves' errors by more than ~1e5 (smallest relative pivot of C below 1e-6: shifts too
  * many / too close); the drivers then halve the sweep width.                                    */
 int ricadi_host_cauchy(const double* shifts, int g, double* rinv_out, double* cinv1_out);
+/* The width the sweep form of ricadi_lyap_adi runs for a window of its shift cycle that is not one of the aligned
+ * full sweeps (a sweep cut by the stopping prediction, and every sweep behind such a cut): the window is the g
+ * entries first .. first + g - 1 of the cycled list of ns shifts, and *width_out is g halved until ricadi_host_cauchy
+ * takes the leading *width_out of them -- one shift is always taken, so the iteration goes on with a narrower sweep
+ * where the window's Cauchy matrix is refused.  Host only, no GPU needed; export added under ABI 412.
+ * RICADI_EINVAL unless first >= 0, 1 <= g <= min(ns, 16) and every shift is negative.                              */
+int ricadi_host_adi_window_width(const double* shifts, int ns, int first, int g, int* width_out);
 /* The next RADI shift under RICADI_RADI_SHIFTS_HAMILTONIAN from the reduced matrices
  * H = Q^T [cal A Q | cal E Q | R | U | B] (k x (2k + m + 2nb), row-major; ricadi_radi_reduce_dev), by the rule stated
  * at ricadi_set_radi_shifts.  Host only, no GPU needed.  The library links no LAPACK: the eigenvalues of the real

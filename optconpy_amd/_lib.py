@@ -175,6 +175,7 @@ SIGNATURES = {
     "ricadi_host_vanka_patches": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _ip]),
     "ricadi_precond_vanka": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip]),
     "ricadi_host_cauchy": (C.c_int, [_dp, C.c_int, _dp, _dp]),
+    "ricadi_host_adi_window_width": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "ricadi_host_radi_shift": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_double),
                                          C.POINTER(C.c_double)]),
     "ricadi_host_radi_shift_eigs": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_double),
@@ -1326,6 +1327,15 @@ def host_cauchy(shifts):
     c1 = np.empty(g)
     _chk(load().ricadi_host_cauchy(_d(sh), g, _d(rinv), _d(c1)))
     return rinv, c1
+
+
+def host_adi_window_width(shifts, first, g):
+    """``ricadi_host_adi_window_width``: the width the sweep form of the ADI runs for the window of ``g`` shifts
+    behind step ``first`` of the cycled list (``g`` halved until ``ricadi_host_cauchy`` takes it); host only."""
+    sh = np.ascontiguousarray(shifts, dtype=np.float64)
+    w = C.c_int(0)
+    _chk(load().ricadi_host_adi_window_width(_d(sh), int(sh.size), int(first), int(g), C.byref(w)))
+    return int(w.value)
 
 
 def host_radi_shift(k, m, nb, H, eigs=False):

@@ -972,6 +972,18 @@ int cauchy_data(const double* shifts, int g, double* rinv, double* cinv1) {
   return RICADI_OK;
 }
 
+// The width that runs for the window of g shifts behind step `first` of the cycled list: g, halved until cauchy_data
+// takes the leading shifts of the window (one shift is always taken).  What the sweep form of the ADI does with a
+// window that is not one of its cycle's (a sweep cut by the stopping prediction, and every sweep behind it).
+int adi_window_width(const double* shifts, int ns, int first, int g) {
+  std::vector<double> ps(g), rinv((size_t)g * g), cinv1(g);
+  for (; g >= 2; g /= 2) {
+    for (int i = 0; i < g; ++i) ps[i] = shifts[(first + i) % ns];
+    if (cauchy_data(ps.data(), g, rinv.data(), cinv1.data()) == RICADI_OK) break;
+  }
+  return std::max(g, 1);
+}
+
 // ---- device records of the preconditioner (uploaded by ricadi_set_operator) ---------------------------------------
 // Sorted distinct columns that the rows of every velocity block touch in the CSR matrix (rp, ci): the lists one after
 // the other in cols, block b's at [ptr[b], ptr[b + 1]); returns the length of the longest list.
@@ -2382,6 +2394,20 @@ int ricadi_host_cauchy(const double* shifts, int g, double* rinv_out, double* ci
     ricadi::set_error("ricadi_host_cauchy: Cauchy matrix not positive definite "
                       "(shifts must be distinct, negative and few)");
   return rc;
+}
+
+int ricadi_host_adi_window_width(const double* shifts, int ns, int first, int g, int* width_out) {
+  if (!shifts || !width_out || ns < 1 || first < 0 || g < 1 || g > RICADI_MAX_GROUPS || g > ns) {
+    ricadi::set_error("ricadi_host_adi_window_width: bad argument (first >= 0, 1 <= g <= min(ns, 16))");
+    return RICADI_EINVAL;
+  }
+  for (int i = 0; i < ns; ++i)
+    if (!(shifts[i] < 0.0)) {
+      ricadi::set_error("ricadi_host_adi_window_width: ADI shifts must be negative");
+      return RICADI_EINVAL;
+    }
+  *width_out = ricadi::adi_window_width(shifts, ns, first, g);
+  return RICADI_OK;
 }
 
 }  // extern "C"

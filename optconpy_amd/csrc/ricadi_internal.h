@@ -158,6 +158,7 @@ PrecondRecords build_records(const HostSetup& hs, const HostCsr& J, const HostCs
                              bool ms_spmm);
 bool sa_criterion(const HostCsr& A, double& rs_out, double& gamma_out);
 int cauchy_data(const double* shifts, int g, double* rinv, double* cinv1);
+int adi_window_width(const double* shifts, int ns, int first, int g);
 int deal_shifts(const double* shifts, int ns, int world, int32_t* owner);
 int gram_lstsq(int h, int m, const double* Ghh, const double* Ghb, double rtol, double* Y);
 // the same on the column-normalised problem (unit diagonal), solution scaled back; Ghh / Ghb are overwritten

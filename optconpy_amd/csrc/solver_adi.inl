@@ -285,7 +285,8 @@ static int admissible_width(const double* shifts, int ns, int m, const ricadi_ad
 // U R^-1 lies in span{U_1..U_j}: it IS the block the step-by-step iteration appends at step j (up to its sign), so
 // the stopping rules (AdiStop) are applied block by block, the blocks behind the stopping step are dropped, and the
 // iteration ends after the same step as the sequential one.  Any run of consecutive, distinct shifts is a valid
-// sweep; where AdiStop::cut shortens one, its Cauchy data are computed on the spot.
+// sweep; where AdiStop::cut shortens one, its Cauchy data -- and those of the misaligned sweeps behind it -- are computed
+// on the spot, for a window narrowed until cauchy_data takes it (cauchy_of).
 //
 // Shift-parallel form (ricadi_set_exchange): every rank owns a fixed subset of the shift list -- fixed, because the
 // per-shift setup, the Sherman-Morrison-Woodbury panels and the recycled solutions live with the owner -- and solves
@@ -372,9 +373,14 @@ struct SweepAdi {
     zc_last = c->zc;
   }
 
-  const CauchySet& cauchy_of(int first, int g) {
+  // Cauchy data of the window of g shifts behind step `first`: an aligned full sweep is one of the cycle's; any other
+  // window (a cut sweep and every sweep behind it) gets its data on the spot, narrowed -- g is updated -- where
+  // cauchy_data refuses it (adi_window_width: halved down to one shift, which is always taken).  Host arithmetic on
+  // the replicated shift list: every rank narrows alike.
+  const CauchySet& cauchy_of(int first, int& g) {
     if (g == G && first % G == 0) return cycle[(first / G) % cycle.size()];
-    if (!var.fill(shifts, ns, first, g)) throw HipError{"Cauchy matrix of a partial ADI sweep is numerically singular"};
+    g = adi_window_width(shifts, ns, first, g);
+    if (!var.fill(shifts, ns, first, g)) throw HipError{"Cauchy matrix of a single-shift ADI sweep refused: bad shift"};
     return var;
   }
 

@@ -609,6 +609,38 @@ int ricadi_shift_solve_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas,
                                  const double* betas, const double* dR,
                                  int64_t r_stride, int m, double* dX,
                                  int* iters_out, double* relres_out);
+/* ---- saddle systems at COMPLEX shifts (exports added under ABI 412) ----------------------
+ * alpha = ar + i ai with ar <= 0 and alpha != 0, beta real: RICADI_EINVAL for ar > 0, alpha = 0 or a value that is not
+ * finite (the preconditioner has never been applied at a non-negative shift).  A complex panel of mc columns is a
+ * row-major array of complex doubles (real part first): the same memory as a real row-major panel of 2 mc columns with
+ * the real parts in the even columns.  1 <= mc <= 8; strides are counted in complex elements; all pointers but the
+ * shifts and the *_out arrays are device pointers.  A low-rank term set on the context (ricadi_set_lowrank, q > 0) is
+ * REFUSED with RICADI_EINVAL in this version: remove it first.  Every sum runs in a fixed order, no atomics: the same
+ * call gives bitwise the same result.
+ * ricadi_shift_solve_cplx_batch_dev:  S(alphas_re[g] + i alphas_im[g], betas[g]) X_g = [R_g; 0] for g < ng <= 16,
+ *   R_g = dR + g r_stride (NV x mc; r_stride 0 = one right-hand side for all groups, else >= NV mc), X_g = dX + g n mc
+ *   (n x mc).  Right-preconditioned flexible GMRES with complex inner products, all groups in lockstep, from zero, with
+ *   the context's gmres_restart / gmres_tol / gmres_maxit; the preconditioner is the real cycle applied to the real and
+ *   the imaginary part at the real proxy shift of ricadi_host_cplx_proxy.  iters_out[ng], relres_out[ng mc] (the true
+ *   relative residuals, recomputed with the complex product) may be NULL.  RICADI_ENOCONV as the real entry.
+ * ricadi_op_apply_cplx_batch_dev:  the product alone, y_g = S(alpha_g, beta_g) x_g, for tests; x_g = dX + g x_stride,
+ *   y_g = dY + g y_stride (strides >= n mc); active / nactive as ricadi_op_apply_batch_dev; variant_out (may be NULL):
+ *   1 the tiled form (operators with the multi-shift tiles), 2 the CSR form (every other operator).
+ * ricadi_cplx_orth_dev:  one CGS2 step of the complex Arnoldi kernels, for tests: w_g = dW + g n mc (n x mc, n = NV +
+ *   NP of the resident operator) against the nvec basis panels v_{j,g} = dV + j v_stride + g g_stride (1 <= nvec <= 400);
+ *   dH + g (nvec + 1) mc receives (nvec + 1) x mc complex: the summed coefficients v_j^H w of the two passes, then the
+ *   norm of what is left; w is overwritten by the unit vector (zero where nothing is left).
+ * ricadi_host_cplx_proxy:  the proxy shift -2^round(log2 |alpha|) (host only, no context).                        */
+int ricadi_shift_solve_cplx_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas_re, const double* alphas_im,
+                                      const double* betas, const double* dR, int64_t r_stride, int mc, double* dX,
+                                      int* iters_out, double* relres_out);
+int ricadi_op_apply_cplx_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas_re, const double* alphas_im,
+                                   const double* betas, const double* dX, int64_t x_stride, int mc,
+                                   const int32_t* active, int nactive, double* dY, int64_t y_stride, int* variant_out);
+int ricadi_cplx_orth_dev(ricadi_ctx* ctx, int ng, int mc, int nvec, const double* dV, int64_t v_stride,
+                         int64_t g_stride, double* dW, double* dH);
+int ricadi_host_cplx_proxy(double ar, double ai, double* alpha_pre_out);
+
 /* dW (NV x m) += coef * E * dV (first NV rows of an n x m or NV x m panel) */
 int ricadi_apply_e_dev(ricadi_ctx* ctx, double coef, const double* dV, int m, double* dW);
 /* dOut (nrows x m) = sum_i coef[i] * panel_i, panel_i = dBasis + i*stride

@@ -161,6 +161,12 @@ SIGNATURES = {
     "ricadi_op_apply_batch_dev": (C.c_int, [_vp, C.c_int, _dp, _dp, _vp, C.c_int64, C.c_int, _ip, C.c_int, C.c_int,
                                             C.c_double, _vp, C.c_int64, C.c_double, _vp, C.c_int64,
                                             C.POINTER(C.c_int)]),
+    "ricadi_shift_solve_cplx_batch_dev": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _vp, C.c_int64, C.c_int, _vp,
+                                                    C.POINTER(C.c_int), _dp]),
+    "ricadi_op_apply_cplx_batch_dev": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _vp, C.c_int64, C.c_int, _ip, C.c_int,
+                                                 _vp, C.c_int64, C.POINTER(C.c_int)]),
+    "ricadi_cplx_orth_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "ricadi_host_cplx_proxy": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "ricadi_host_saddle_tiles": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp,
                                            C.POINTER(RicadiOpts), _ip, _ip, _ip, _ip, _up, _up, _dp, _dp, _ip, _ip,
                                            _ip, _dp]),
@@ -1252,6 +1258,106 @@ def _lqg_balance_dev(self, zc_t, zf_t, b_t, ct_t, tol, order):
 Context.cross_gram_dev = _cross_gram_dev
 Context.project_pencil_twosided_dev = _project_pencil_twosided_dev
 Context.lqg_balance_dev = _lqg_balance_dev
+
+
+# ---- complex shifts (include/ricadi.h, "saddle systems at COMPLEX shifts") --------------------
+MAX_MC = 8               # widest complex panel
+
+
+def _cplx_ptr(t, shape=None):
+    """Device pointer of a contiguous complex128 CUDA tensor (through ``torch.view_as_real``)."""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.complex128 and t.is_contiguous()):
+        raise ValueError("a contiguous complex128 CUDA tensor is required")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("tensor of shape {0} required, got {1}".format(tuple(shape), tuple(t.shape)))
+    return torch.view_as_real(t).data_ptr()
+
+
+def _cplx_shifts(alphas, betas):
+    al = np.atleast_1d(np.asarray(alphas, dtype=np.complex128)).ravel()
+    be = np.ones(al.size) if betas is None else np.atleast_1d(np.asarray(betas, dtype=np.float64)).ravel()
+    if be.size != al.size or al.size < 1:
+        raise ValueError("one beta per alpha required")
+    return np.ascontiguousarray(al.real), np.ascontiguousarray(al.imag), np.ascontiguousarray(be)
+
+
+def _shift_solve_cplx_batch_dev(self, alphas, R_t, betas=None, X_t=None, strict=True):
+    """``S(alphas[g], betas[g]) X_g = [R_g; 0]`` at complex shifts (``Re alpha <= 0``, ``alpha != 0``; ``betas``
+    default 1) in one lockstep batch of ``ng = len(alphas) <= 16`` groups.  ``R_t``: complex128 CUDA tensor
+    ``(NV, mc)`` -- one right-hand side for all groups -- or ``(ng, NV, mc)``, ``mc <= 8``.  Returns ``(X, iters,
+    relres)``: ``X`` ``(ng, n, mc)`` complex128 on the device (``X_t`` if given), iterations per group, true relative
+    residuals ``(ng, mc)``.  ``strict=False`` returns what it has when a group stops at ``gmres_maxit``."""
+    import torch
+    self._need_op()
+    ar, ai, be = _cplx_shifts(alphas, betas)
+    ng = ar.size
+    shared = R_t.dim() == 2
+    mc = int(R_t.shape[-1])
+    _cplx_ptr(R_t, (self.nv, mc) if shared else (ng, self.nv, mc))
+    if X_t is None:
+        X_t = torch.empty((ng, self.n, mc), dtype=torch.complex128, device=R_t.device)
+    its = (C.c_int * ng)()
+    rr = np.zeros((ng, mc))
+    torch.cuda.current_stream().synchronize()
+    rc = self._lib.ricadi_shift_solve_cplx_batch_dev(self._h, ng, _d(ar), _d(ai), _d(be), _cplx_ptr(R_t),
+                                                     0 if shared else self.nv * mc, mc,
+                                                     _cplx_ptr(X_t, (ng, self.n, mc)), its, _d(rr))
+    _chk(rc, allow_noconv=not strict)
+    return X_t, list(its), rr
+
+
+def _op_apply_cplx_batch_dev(self, alphas, X_t, betas=None, Y_t=None, active=None):
+    """``Y_g = S(alphas[g], betas[g]) X_g`` on complex128 CUDA tensors ``(ng, rows, mc)`` with ``rows >= n`` (the
+    group stride is ``rows * mc``; only the first n rows of a group are read / written), ``mc <= 8``; ``active``: the
+    group ids to apply it to.  Returns ``(Y, variant)``, variant 1 the tiled form, 2 the CSR form."""
+    import torch
+    self._need_op()
+    ar, ai, be = _cplx_shifts(alphas, betas)
+    ng = ar.size
+    if X_t.dim() != 3 or X_t.shape[0] != ng:
+        raise ValueError("X must be (ng, rows, mc)")
+    rows, mc = int(X_t.shape[1]), int(X_t.shape[2])
+    if Y_t is None:
+        Y_t = torch.zeros_like(X_t)
+    act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+    var = C.c_int(-1)
+    torch.cuda.current_stream().synchronize()
+    _chk(self._lib.ricadi_op_apply_cplx_batch_dev(self._h, ng, _d(ar), _d(ai), _d(be), _cplx_ptr(X_t), rows * mc, mc,
+                                                  None if act is None else _i(act), 0 if act is None else act.size,
+                                                  _cplx_ptr(Y_t, X_t.shape), int(Y_t.shape[1]) * mc, C.byref(var)))
+    return Y_t, int(var.value)
+
+
+def _cplx_orth_dev(self, V_t, W_t):
+    """One CGS2 step of the complex Arnoldi kernels: ``W_t`` ``(ng, n, mc)`` against the basis ``V_t`` ``(nvec, ng, n,
+    mc)`` (complex128 CUDA tensors, ``n`` the resident operator's).  ``W_t`` is overwritten by the unit vectors;
+    returns ``H`` ``(ng, nvec + 1, mc)`` complex128 on the device: the summed coefficients, then the norm."""
+    import torch
+    self._need_op()
+    if V_t.dim() != 4 or W_t.dim() != 3 or tuple(V_t.shape[1:]) != tuple(W_t.shape) or W_t.shape[1] != self.n:
+        raise ValueError("V must be (nvec, ng, n, mc) and W (ng, n, mc)")
+    nvec, ng, n, mc = (int(s) for s in V_t.shape)
+    H = torch.zeros((ng, nvec + 1, mc), dtype=torch.complex128, device=W_t.device)
+    torch.cuda.current_stream().synchronize()
+    _chk(self._lib.ricadi_cplx_orth_dev(self._h, ng, mc, nvec, _cplx_ptr(V_t), ng * n * mc, n * mc, _cplx_ptr(W_t),
+                                        _cplx_ptr(H)))
+    return H
+
+
+def host_cplx_proxy(alpha):
+    """``ricadi_host_cplx_proxy``: the real shift ``-2^round(log2 |alpha|)`` the complex solver preconditions
+    ``alpha`` with; ValueError for ``Re alpha > 0``, ``alpha = 0`` or a value that is not finite.  Host only."""
+    a = complex(alpha)
+    out = C.c_double(0.0)
+    _chk(load().ricadi_host_cplx_proxy(a.real, a.imag, C.byref(out)))
+    return float(out.value)
+
+
+Context.shift_solve_cplx_batch_dev = _shift_solve_cplx_batch_dev
+Context.op_apply_cplx_batch_dev = _op_apply_cplx_batch_dev
+Context.cplx_orth_dev = _cplx_orth_dev
+Context.host_cplx_proxy = staticmethod(host_cplx_proxy)
 
 
 def host_lqg_balance(S, tol=1e-12, order=0):

@@ -4,7 +4,7 @@
 set -euo pipefail
 cd "$(dirname "$0")"
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function"
-SRCS="ricadi_spmm.hip ricadi_arnoldi.hip ricadi_precond.hip ricadi_dense.hip ricadi_radi.hip ricadi_project.hip ricadi_solver.hip ricadi_host.cpp"
+SRCS="ricadi_spmm.hip ricadi_arnoldi.hip ricadi_precond.hip ricadi_dense.hip ricadi_radi.hip ricadi_project.hip ricadi_cplx.hip ricadi_solver.hip ricadi_host.cpp"
 mkdir -p build
 pids=()
 for s in $SRCS; do

@@ -418,6 +418,16 @@ struct ricadi_ctx {
   hipStream_t st_half = nullptr;
   hipEvent_t ev_res_half[2] = {nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // workspaces of the complex-shift path (solver_cplx.inl), sized on first use and apart from
+  // the real ones: per group and per basis vector the sizes they hold (0: none; forget_operator resets them -- they
+  // depend on n), then the FP64 basis V and Z_j = P^-1 v_j, the panels w, r, b, and the small arrays of the Arnoldi
+  // passes and of the Hessenberg stage
+  struct CplxWork {
+    int groups = 0, nvec = 0, n = 0;
+    bool basis = false;
+    DArr<double> V, Zb, w, r, b;
+    DArr<double> partial, h1, h2, hout, nrm2, scale, Hm, cs, sn, gv, y, bnorm, resid;
+  } cw;
   // factor
   DArr<double> Z;
   int zc = 0, zld = 0;

@@ -2410,4 +2410,13 @@ int ricadi_host_adi_window_width(const double* shifts, int ns, int first, int g,
   return RICADI_OK;
 }
 
+int ricadi_host_cplx_proxy(double ar, double ai, double* alpha_pre_out) {
+  if (!alpha_pre_out || !ricadi::cplx_shift_ok(ar, ai)) {
+    ricadi::set_error("ricadi_host_cplx_proxy: a finite shift alpha != 0 with Re alpha <= 0 required");
+    return RICADI_EINVAL;
+  }
+  *alpha_pre_out = ricadi::cplx_proxy(ar, ai);
+  return RICADI_OK;
+}
+
 }  // extern "C"

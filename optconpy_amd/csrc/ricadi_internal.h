@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <map>
@@ -627,6 +628,56 @@ int radi_sweep_groups(int mw, int nb);
 void launch_radi_sweep_combine(hipStream_t st, int nv, int G, int m, int nb, int k, const double* V, size_t vstride,
                                int ldv, const double* S, int lds, const double* Cf, double* RU, double* Z, int zld,
                                int zc);
+
+// K1c / K3c: the complex-shift path (ricadi_cplx.hip).  A complex panel of mc <= 8 columns is
+// the real row-major panel of m2 = 2 mc columns (real parts in the even columns, leading dimension m2); group strides
+// are in doubles.  Coefficient rows (h, y, the partial sums) hold 16 doubles whatever m2: complex column c at 2c, 2c + 1.
+// A shift the complex path takes: finite, not zero, real part <= 0.  Its real proxy shift, at which the (real)
+// preconditioner is applied: -2^round(log2 |alpha|), halves rounded up -- the frequencies of a sweep share few setups.
+inline bool cplx_shift_ok(double ar, double ai) {
+  return std::isfinite(ar) && std::isfinite(ai) && ar <= 0.0 && (ar != 0.0 || ai != 0.0);
+}
+inline double cplx_proxy(double ar, double ai) {
+  return -std::ldexp(1.0, (int)std::floor(std::log2(std::hypot(ar, ai)) + 0.5));
+}
+struct CplxCoefs {            // alpha_g = ar + i ai and beta_g per group id (by value)
+  double ar[RICADI_MAX_GROUPS], ai[RICADI_MAX_GROUPS], beta[RICADI_MAX_GROUPS];
+};
+// y_g = S(alpha_g, beta_g) x_g: CSR form on the unified saddle pattern with its three value sources; tiled form on the
+// multi-shift tile format (lidx with the velocity-velocity flag in bit 15, vAJ, vE; max_cols <= 160)
+void launch_cplx_spmm_csr(hipStream_t st, const GroupTab& gt, const CplxCoefs& cf, int nrows, const int* rp,
+                          const int* ci, const double* vA, const double* vE, const double* vJ, const double* x,
+                          size_t gsx, double* y, size_t gsy, int m2);
+bool cplx_spmm_tiled_ok(int max_cols, size_t panel_rows);
+void launch_cplx_spmm_tiled(hipStream_t st, const GroupTab& gt, const CplxCoefs& cf, int nblk, const int* rows2,
+                            const int* rp2, const int* cols2, const uint16_t* lidx, const double* vAJ, const double* vE,
+                            const double* x, size_t gsx, double* y, size_t gsy, int m2, int max_cols);
+// out[g][j] = v_j^H w (j < nvec; basis vector j of group g at V + j vstride + g gsv) and, with want_self, ||w||^2 per
+// column at row nvec; partial: groups x cplx_num_blocks(n) x ldp x 16 doubles (ldp >= nvec + want_self), summed in block
+// order by a second launch; out: rows of 16, group stride gso
+int cplx_num_blocks(int nrows);
+void launch_cplx_dots(hipStream_t st, const GroupTab& gt, int n, int m2, int nvec, int want_self, const double* V,
+                      size_t vstride, size_t gsv, const double* w, size_t gsw, double* partial, int ldp, double* out,
+                      size_t gso);
+// w_g += sign sum_{j < nvecs[g]} v_j h_j
+void launch_cplx_update(hipStream_t st, const GroupTab& gt, const GroupInts& nvecs, int n, int m2, const double* V,
+                        size_t vstride, size_t gsv, const double* h, size_t gsh, double sign, double* w, size_t gsw);
+// out = a in + b scale[g][column] other on `count` doubles per group (other == NULL: a in; scale == NULL: 1; a == 0:
+// `in` is not read)
+void launch_cplx_axpby(hipStream_t st, const GroupTab& gt, size_t count, int m2, double a, const double* in, size_t gsi,
+                       double b, const double* scale, const double* other, size_t gso, double* out, size_t gsout);
+// hout = h1 + h2 (nvec rows), row nvec = (||w||, 0) from nrm2 (16 per group), scale (16 per group) = 1 / ||w|| or 0
+void launch_cplx_orth_finish(hipStream_t st, const GroupTab& gt, int nvec, const double* h1, const double* h2,
+                             const double* nrm2, size_t gsh, double* hout, double* scale);
+// the small stages of the complex GMRES, one wave per group; per (group, column) slots of 8 columns per group:
+// Hm restart x (restart + 1) complex, cs restart, sn restart complex, gv (restart + 1) complex, bnorm / resid 8 per group
+void launch_cplx_gmres_start(hipStream_t st, const GroupTab& gt, int mc, int restart, const double* nrm2,
+                             const double* bnorm, double* gv, double* scale, double* resid);
+void launch_cplx_gmres_hess(hipStream_t st, const GroupTab& gt, int mc, int j, int restart, const double* hcol,
+                            size_t gsh, double* Hm, double* cs, double* sn, double* gv, const double* bnorm,
+                            double* resid);
+void launch_cplx_gmres_backsolve(hipStream_t st, const GroupTab& gt, const GroupInts& ks, int mc, int restart,
+                                 const double* Hm, const double* gv, double* y, size_t gsy);
 
 void set_error(const std::string& msg);
 

@@ -24,3 +24,4 @@ namespace ricadi {
 #include "solver_capi.inl"         // guards, shared set-up, the product's entry points
 #include "solver_capi_probe.inl"   // the tests' probes
 #include "solver_capi_timing.inl"  // the benchmark's timers
+#include "solver_cplx.inl"         // complex shifts: product, CGS2 step, lockstep flexible GMRES, their entry points

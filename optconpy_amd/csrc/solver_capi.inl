@@ -258,6 +258,8 @@ static void forget_operator(ricadi_ctx* c) {
   c->q = 0;
   c->zc = 0;
   c->wcols = 0;                // workspaces depend on n
+  c->cw.groups = c->cw.nvec = c->cw.n = 0;   // ... the complex ones too
+  c->cw.basis = false;
   // the ring goes, slots and all: recycle_guess lists its entries in slot order, so a ring that kept its (invalid)
   // slots would fill them in another order than a fresh context's growing ring, and the normal equations of the same
   // guess would come out permuted -- other rounding, other bits (found by tests/test_gpu_context_reuse.py)

@@ -26,7 +26,8 @@ import numpy as np
 from . import _lib, backend
 from . import proj_ric_utils as pru
 
-__all__ = ["balance_factors", "lqgbt_reduce", "MAX_COLS", "MAX_ORDER"]
+__all__ = ["balance_factors", "lqgbt_reduce", "freq_response", "reduced_freq_response", "reduction_error",
+           "MAX_COLS", "MAX_ORDER"]
 
 MAX_COLS = 1024          # widest factor ricadi_lqg_balance_dev takes
 MAX_ORDER = _lib.MAX_M   # largest reduced order
@@ -157,3 +158,76 @@ def lqgbt_reduce(mmat=None, amat=None, jmat=None, bmat=None, cmat=None, radi_dic
         out["bk"] = sg[:, None] * cr.T
         out["ck"] = -(br.T * sg)
     return out
+
+
+# ---- frequency response ----------------------------------------------------------------------
+FREQ_BATCH = 16          # frequencies per lockstep batch (the library's group limit)
+FREQ_COLS = _lib.MAX_MC  # columns of B per solve (the widest complex panel)
+
+
+def _omegas(omegas):
+    om = np.atleast_1d(np.asarray(omegas, dtype=np.float64)).ravel()
+    if om.size == 0 or not np.all(np.isfinite(om)) or not np.all(om > 0.0):
+        raise ValueError("omegas must be positive and finite")
+    return om
+
+
+def freq_response(mmat=None, amat=None, jmat=None, bmat=None, cmat=None, omegas=None, info=False):
+    """The transfer function ``G(i w) = C (i w M - A)^-1 B`` on ker J of ``M v' = A v + J^T p + B u``, ``J v = 0``,
+    ``y = C v`` at the frequencies ``omegas`` (positive, finite; else ``ValueError``), on the device.
+
+    ``G[k] = C V_k`` with ``[[A - i w_k M, J^T], [J, 0]] [V_k; L] = [-B; 0]``: saddle solves at the complex shifts
+    ``-i w_k`` on the operator ``(cal A, cal E) = (A, M)`` -- the orientation :func:`balance_factors` uses --, sixteen
+    frequencies per lockstep batch, the columns of ``B`` in chunks of eight.  ``bmat`` (NV x NU) and ``cmat`` = ``C``
+    (NY x NV) are expected Leray-projected, as for :func:`lqgbt_reduce`.  Only ``B``, ``C^T`` and ``G`` cross PCIe.
+
+    Returns ``G`` (``len(omegas)`` x NY x NU, complex128); with ``info=True`` a pair ``(G, d)``, ``d['iters']`` the
+    GMRES iterations per frequency (summed over the column chunks) and ``d['relres']`` the worst true relative residual
+    per frequency.  A low-rank term set on the context is cleared, as by :func:`balance_factors`."""
+    import torch
+    om = _omegas(omegas)
+    calA, calE = pru._orient(amat, mmat, True)
+    ctx = backend.context_for(calA, calE, jmat)
+    ctx.set_lowrank(None, None)
+    B = pru._dense(bmat)
+    Cm = pru._dense(cmat)
+    if B.shape[0] != ctx.nv or Cm.shape[1] != ctx.nv:
+        raise ValueError("bmat must be NV x NU and cmat NY x NV")
+    nu, ny, nv = B.shape[1], Cm.shape[0], ctx.nv
+    Bd = pru.to_device(-B).t.to(torch.complex128)
+    Cd = pru.to_device(np.ascontiguousarray(Cm.T)).t.to(torch.complex128).T      # C as a view of the uploaded C^T
+    G = torch.empty((om.size, ny, nu), dtype=torch.complex128, device=Bd.device)
+    iters = np.zeros(om.size, dtype=np.int64)
+    relres = np.zeros(om.size)
+    for k0 in range(0, om.size, FREQ_BATCH):
+        w = om[k0:k0 + FREQ_BATCH]
+        for c0 in range(0, nu, FREQ_COLS):
+            R = Bd[:, c0:c0 + FREQ_COLS].contiguous()
+            X, its, rr = ctx.shift_solve_cplx_batch_dev(-1j * w, R)
+            G[k0:k0 + w.size, :, c0:c0 + R.shape[1]] = torch.matmul(Cd, X[:, :nv, :])
+            iters[k0:k0 + w.size] += np.asarray(its)
+            relres[k0:k0 + w.size] = np.maximum(relres[k0:k0 + w.size], rr.max(axis=1))
+    torch.cuda.synchronize()
+    Gh = G.cpu().numpy()
+    return (Gh, dict(iters=iters, relres=relres)) if info else Gh
+
+
+def reduced_freq_response(red, omegas):
+    """``G_r(i w) = C_r (i w E_r - A_r)^-1 B_r`` of a reduced model (the dict of :func:`balance_factors` /
+    :func:`lqgbt_reduce`) at the frequencies ``omegas``; NumPy, ``len(omegas)`` x NY x NU complex128."""
+    om = _omegas(omegas)
+    ar, er, br, cr = (np.asarray(red[k], dtype=np.float64) for k in ("ar", "er", "br", "cr"))
+    return np.stack([cr @ np.linalg.solve(1j * w * er - ar, br.astype(np.complex128)) for w in om])
+
+
+def reduction_error(mmat=None, amat=None, jmat=None, bmat=None, cmat=None, red=None, omegas=None):
+    """How far the reduced model ``red`` is from the full one on the imaginary axis: a dict with ``omegas``, ``err``
+    (``sigma_max(G(i w) - G_r(i w))`` per frequency), ``full`` (``sigma_max(G(i w))``) and ``hinf_lower`` (``max err``:
+    a lower bound of the H-infinity error, to be held against ``2 sum_{i > r} hsv_i`` for balanced truncation).  The full
+    response comes from :func:`freq_response`, the reduced one from :func:`reduced_freq_response`."""
+    om = _omegas(omegas)
+    G = freq_response(mmat=mmat, amat=amat, jmat=jmat, bmat=bmat, cmat=cmat, omegas=om)
+    Gr = reduced_freq_response(red, om)
+    err = np.array([np.linalg.norm(G[k] - Gr[k], 2) for k in range(om.size)])
+    full = np.array([np.linalg.norm(G[k], 2) for k in range(om.size)])
+    return dict(omegas=om, err=err, full=full, hinf_lower=float(err.max()))

@@ -640,6 +640,40 @@ int ricadi_op_apply_cplx_batch_dev(ricadi_ctx* ctx, int ng, const double* alphas
 int ricadi_cplx_orth_dev(ricadi_ctx* ctx, int ng, int mc, int nvec, const double* dV, int64_t v_stride,
                          int64_t g_stride, double* dW, double* dH);
 int ricadi_host_cplx_proxy(double ar, double ai, double* alpha_pre_out);
+/* Step probe of the complex cycle (tests; exports added under ABI 412): the units the restart cycle of
+ * ricadi_shift_solve_cplx_batch_dev is made of, one call each, on the solver's own workspace and with the strides of
+ * a solve of ng groups of mc complex columns -- without the preconditioner and the operator: the caller supplies
+ * w = S P^-1 v_j.  Complex panels [ng][n][mc] (n = NV + NP) are device pointers; every call is synchronous.
+ *   begin: sizes the workspace as a solve does, fills V, Hm, cs, sn, gv, y, scale, resid and hout with 0xFF bytes
+ *          (what no later call writes reads back as NaN), computes the squared norms of the residual panels dR and
+ *          runs the cycle start (gv[0], scale, resid, v_0 into V slot 0) for all ng groups.  bnorm: HOST array
+ *          [ng][mc], ||b|| per column.
+ *   step:  the Arnoldi phase of iteration j (0 <= j < gmres_restart) on the panels dW for the nact groups listed in
+ *          `groups` (host; distinct ids in 0 .. ng-1): CGS2 against V[0 .. j] into V[j + 1], then column j of the
+ *          Hessenberg matrix, its rotation, gv and resid.  The CGS2 step also leaves ||w'||^2 in nrm2 and 1 / ||w'||
+ *          in scale.  The other groups are not touched.
+ *   close: the cycle end for all groups, group g with its first ks[g] vectors (host; 0 <= ks[g] <= min(nz, steps run
+ *          for g)): R y = g, then dX += Z y with the nz FP64 panels dZ [nz][ng][n][mc] (copied into the solver's Z
+ *          storage) on the caller's panels dX [ng][n][mc].
+ *   read:  one workspace array (RICADI_CPROBE_*) into dOut (capacity cap doubles; *count: doubles written), `slot`:
+ *          the Krylov vector for RICADI_CPROBE_V, ignored otherwise.
+ * RICADI_EINVAL before anything is launched for j, ng, mc, a group id, ks, nz, `what` or a slot out of range, and for
+ * step / close / read without a begin on the current workspace (a complex solve, a ricadi_cplx_orth_dev call or a new
+ * operator ends the probe cycle).  A later solve on the context is bitwise what it is on a fresh context.          */
+#define RICADI_CPROBE_V 0      /* Krylov vector `slot`, [ng][n][mc] complex                                        */
+#define RICADI_CPROBE_HOUT 1   /* coefficient column of the last CGS2 step, [ng][gmres_restart + 2][8] complex     */
+#define RICADI_CPROBE_HM 2     /* [ng][8][gmres_restart][gmres_restart + 1] complex: column j of R, entries 0 .. j + 1 */
+#define RICADI_CPROBE_CS 3     /* [ng][8][gmres_restart] real                                                      */
+#define RICADI_CPROBE_SN 4     /* [ng][8][gmres_restart] complex                                                   */
+#define RICADI_CPROBE_GV 5     /* [ng][8][gmres_restart + 1] complex                                               */
+#define RICADI_CPROBE_Y 6      /* [ng][gmres_restart][8] complex                                                   */
+#define RICADI_CPROBE_SCALE 7  /* [ng][16] real: the factor of a complex column in both slots of its pair          */
+#define RICADI_CPROBE_RESID 8  /* [ng][8] real                                                                     */
+#define RICADI_CPROBE_NRM2 9   /* [ng][16] real: squared norm of complex column c at 2 c, 0 at 2 c + 1             */
+int ricadi_cplx_probe_begin_dev(ricadi_ctx* ctx, int ng, int mc, const double* dR, const double* bnorm);
+int ricadi_cplx_probe_step_dev(ricadi_ctx* ctx, int j, const double* dW, int nact, const int* groups);
+int ricadi_cplx_probe_close_dev(ricadi_ctx* ctx, const int* ks, int nz, const double* dZ, double* dX);
+int ricadi_cplx_probe_read_dev(ricadi_ctx* ctx, int what, int slot, double* dOut, int64_t cap, int64_t* count);
 
 /* dW (NV x m) += coef * E * dV (first NV rows of an n x m or NV x m panel) */
 int ricadi_apply_e_dev(ricadi_ctx* ctx, double coef, const double* dV, int m, double* dW);

@@ -167,6 +167,10 @@ SIGNATURES = {
                                                  _vp, C.c_int64, C.POINTER(C.c_int)]),
     "ricadi_cplx_orth_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, _vp, _vp]),
     "ricadi_host_cplx_proxy": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "ricadi_cplx_probe_begin_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _dp]),
+    "ricadi_cplx_probe_step_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int)]),
+    "ricadi_cplx_probe_close_dev": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int, _vp, _vp]),
+    "ricadi_cplx_probe_read_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     "ricadi_host_saddle_tiles": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp,
                                            C.POINTER(RicadiOpts), _ip, _ip, _ip, _ip, _up, _up, _dp, _dp, _ip, _ip,
                                            _ip, _dp]),
@@ -1354,6 +1358,69 @@ def host_cplx_proxy(alpha):
     return float(out.value)
 
 
+# RICADI_CPROBE_* of include/ricadi.h
+CPROBE = dict(V=0, hout=1, Hm=2, cs=3, sn=4, gv=5, y=6, scale=7, resid=8, nrm2=9)
+
+
+def _cplx_probe_begin_dev(self, R_t, bnorm):
+    """Cycle start of the complex step probe: residual panels ``R_t`` ``(ng, n, mc)`` (complex128 CUDA tensor),
+    ``bnorm`` ``(ng, mc)`` host array of ``||b||`` per column."""
+    import torch
+    self._need_op()
+    if R_t.dim() != 3:
+        raise ValueError("R must be (ng, n, mc)")
+    ng, n, mc = (int(s) for s in R_t.shape)
+    bn = np.ascontiguousarray(bnorm, dtype=np.float64)
+    if n != self.n or bn.shape != (ng, mc):
+        raise ValueError("R must be (ng, n, mc) with the resident n and bnorm (ng, mc)")
+    torch.cuda.current_stream().synchronize()
+    _chk(self._lib.ricadi_cplx_probe_begin_dev(self._h, ng, mc, _cplx_ptr(R_t), _d(bn)))
+    self._cprobe = (ng, n, mc)
+
+
+def _cplx_probe_step_dev(self, j, W_t, groups):
+    """The Arnoldi phase of iteration ``j`` on the panels ``W_t`` ``(ng, n, mc)`` for the listed groups."""
+    import torch
+    g = (C.c_int * len(groups))(*[int(x) for x in groups])
+    torch.cuda.current_stream().synchronize()
+    _chk(self._lib.ricadi_cplx_probe_step_dev(self._h, int(j), _cplx_ptr(W_t), len(groups), g))
+
+
+def _cplx_probe_close_dev(self, ks, Z_t, X_t):
+    """Cycle end: group ``g`` with ``ks[g]`` vectors, ``Z_t`` ``(nz, ng, n, mc)``; ``X_t`` ``(ng, n, mc)`` is updated
+    in place (``x += Z y``)."""
+    import torch
+    k = (C.c_int * len(ks))(*[int(x) for x in ks])
+    torch.cuda.current_stream().synchronize()
+    _chk(self._lib.ricadi_cplx_probe_close_dev(self._h, k, int(Z_t.shape[0]), _cplx_ptr(Z_t), _cplx_ptr(X_t)))
+
+
+def _cplx_probe_read_dev(self, what, slot=0):
+    """Workspace array ``what`` (``CPROBE``) of the probe cycle as a NumPy array: ``V`` ``(ng, n, mc)``, ``hout``
+    ``(ng, restart + 2, 8)``, ``Hm`` ``(ng, 8, restart, restart + 1)``, ``sn`` ``(ng, 8, restart)``, ``gv``
+    ``(ng, 8, restart + 1)``, ``y`` ``(ng, restart, 8)`` complex; ``cs`` ``(ng, 8, restart)``, ``scale`` / ``nrm2``
+    ``(ng, 16)``, ``resid`` ``(ng, 8)`` real."""
+    import torch
+    ng, n, mc = getattr(self, "_cprobe", (1, self.n, 1))       # (no begin: the entry refuses the call)
+    rs = int((getattr(self, "_opts", None) or default_opts()).gmres_restart)
+    shapes = dict(V=(ng, n, mc), hout=(ng, rs + 2, 8), Hm=(ng, 8, rs, rs + 1), cs=(ng, 8, rs), sn=(ng, 8, rs),
+                  gv=(ng, 8, rs + 1), y=(ng, rs, 8), scale=(ng, 16), resid=(ng, 8), nrm2=(ng, 16))
+    real = what in ("cs", "scale", "resid", "nrm2")
+    cap = int(np.prod(shapes[what])) * (1 if real else 2)
+    buf = torch.full((cap,), float("nan"), dtype=torch.float64, device="cuda:0")
+    cnt = C.c_int64(0)
+    torch.cuda.current_stream().synchronize()
+    _chk(self._lib.ricadi_cplx_probe_read_dev(self._h, int(CPROBE[what]), int(slot), buf.data_ptr(), cap, C.byref(cnt)))
+    if int(cnt.value) != cap:
+        raise RuntimeError("probe array {0}: {1} doubles, expected {2}".format(what, cnt.value, cap))
+    a = buf.cpu().numpy()
+    return a.reshape(shapes[what]).copy() if real else a.view(np.complex128).reshape(shapes[what]).copy()
+
+
+Context.cplx_probe_begin_dev = _cplx_probe_begin_dev
+Context.cplx_probe_step_dev = _cplx_probe_step_dev
+Context.cplx_probe_close_dev = _cplx_probe_close_dev
+Context.cplx_probe_read_dev = _cplx_probe_read_dev
 Context.shift_solve_cplx_batch_dev = _shift_solve_cplx_batch_dev
 Context.op_apply_cplx_batch_dev = _op_apply_cplx_batch_dev
 Context.cplx_orth_dev = _cplx_orth_dev

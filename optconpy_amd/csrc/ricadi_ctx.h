@@ -484,6 +484,14 @@ struct ricadi_ctx {
     std::vector<int> kdone;
     const double* work = nullptr;
   } probe;
+  // step probe of the complex cycle (ricadi_cplx_probe_*_dev, tests): the batch of its last begin, the steps run per
+  // group since, the restart length and the basis it filled.  A complex solve or CGS2 call ends the cycle (they use
+  // the same workspace), as does a new operator.
+  struct CplxProbe {
+    int ng = 0, mc = 0, restart = 0;
+    std::vector<int> kdone;
+    const double* work = nullptr;
+  } cprobe;
   // the branches the batched shift solve took (ricadi_solve_trace, tests): host counters, bumped where the decision is
   // taken; cumulative over the context's life unless named *_last (the values of the most recent event) -- cycle_len_max
   // is the largest so far.  Order = slots of ricadi_solve_trace.

@@ -282,6 +282,7 @@ static void forget_operator(ricadi_ctx* c) {
   c->k1_variant = -1;
   c->coarse_route = -1;
   c->probe = ricadi_ctx::ArnoldiProbe();
+  c->cprobe = ricadi_ctx::CplxProbe();
 }
 
 int ricadi_set_operator(ricadi_ctx* c, int nv, int np, const int32_t* a_rp, const int32_t* a_ci,

@@ -122,17 +122,62 @@ struct CplxResult {
   bool converged = true;
 };
 
+// The sizes and strides of a restart cycle of ng groups of mc complex columns on the context's workspace (after
+// cplx_ensure_work): what the solve and the step probe hand to the three cycle functions below
+struct CplxCycle {
+  int mc, m2, n, restart, ldp;
+  size_t gs, vstride, gsh, gsy;
+};
+CplxCycle cplx_cycle(const ricadi_ctx* c, int ng, int mc) {
+  CplxCycle cy{};
+  cy.mc = mc;
+  cy.m2 = 2 * mc;
+  cy.n = c->n;
+  cy.restart = c->opts.gmres_restart;
+  cy.ldp = c->cw.nvec + 1;
+  cy.gs = (size_t)c->n * cy.m2;
+  cy.vstride = cy.gs * ng;
+  cy.gsh = (size_t)cy.ldp * 16;
+  cy.gsy = (size_t)cy.restart * 16;
+  return cy;
+}
+
+// cycle start from the squared residual norms in cw.nrm2: gv[0], scale, resid; v_0 = r / ||r|| into V slot 0
+void cplx_cycle_start_launches(ricadi_ctx* c, const CplxCycle& cy, const GroupTab& tab) {
+  ricadi_ctx::CplxWork& k = c->cw;
+  launch_cplx_gmres_start(c->st, tab, cy.mc, cy.restart, k.nrm2.p, k.bnorm.p, k.gv.p, k.scale.p, k.resid.p);
+  launch_cplx_axpby(c->st, tab, cy.gs, cy.m2, 0.0, nullptr, 0, 1.0, k.scale.p, k.r.p, cy.gs, k.V.p, cy.gs);
+}
+
+// Arnoldi step j after the product (w = S P^-1 v_j in cw.w): CGS2 against V[0 .. j] into V[j + 1], column j of the
+// Hessenberg matrix through the rotations, the residual estimate into cw.resid
+void cplx_arnoldi_launches(ricadi_ctx* c, const CplxCycle& cy, const GroupTab& ct, int j) {
+  ricadi_ctx::CplxWork& k = c->cw;
+  cplx_orth(c, ct, cy.m2, j + 1, k.V.p, cy.vstride, cy.gs, k.w.p, cy.gs, cy.ldp, k.V.p + (size_t)(j + 1) * cy.vstride,
+            cy.gs);
+  launch_cplx_gmres_hess(c->st, ct, cy.mc, j, cy.restart, k.hout.p, cy.gsh, k.Hm.p, k.cs.p, k.sn.p, k.gv.p, k.bnorm.p,
+                         k.resid.p);
+}
+
+// cycle end: R y = g with the first ks[g] columns, x += Z y
+void cplx_cycle_end_launches(ricadi_ctx* c, const CplxCycle& cy, const GroupTab& tab, const GroupInts& ks, double* dX) {
+  ricadi_ctx::CplxWork& k = c->cw;
+  launch_cplx_gmres_backsolve(c->st, tab, ks, cy.mc, cy.restart, k.Hm.p, k.gv.p, k.y.p, cy.gsy);
+  launch_cplx_update(c->st, tab, ks, cy.n, cy.m2, k.Zb.p, cy.vstride, cy.gs, k.y.p, cy.gsy, 1.0, dX, cy.gs);
+}
+
 // S(alpha_g, beta_g) X_g = [R_g; 0] for ng groups in lockstep: flexible GMRES(restart) from zero, Z_j kept in FP64.
 CplxResult cplx_solve(ricadi_ctx* c, int ng, const CplxCoefs& cf, const double* dR, size_t gsr, int mc, double* dX) {
   hipStream_t st = c->st;
   const int m2 = 2 * mc, n = c->n, restart = c->opts.gmres_restart, maxit = c->opts.gmres_maxit;
   const double tol = c->opts.gmres_tol;
-  const size_t gs = (size_t)n * m2, vstride = gs * ng;
   CplxPrecond pc(c, ng, cf, m2);
   cplx_ensure_work(c, ng, restart + 1, true);
+  c->cprobe = ricadi_ctx::CplxProbe();   // the workspace of a probe cycle in flight is the solve's now
   ricadi_ctx::CplxWork& k = c->cw;
-  const int ldp = k.nvec + 1;
-  const size_t gsh = (size_t)ldp * 16;
+  const CplxCycle cy = cplx_cycle(c, ng, mc);
+  const int ldp = cy.ldp;
+  const size_t gs = cy.gs, vstride = cy.vstride;
   const GroupTab all = all_groups(ng);
   // b_g = [R_g; 0], x_g = 0, r_g = b_g
   HIPCHK(hipMemsetAsync(k.b.p, 0, sizeof(double) * gs * ng, st));
@@ -183,8 +228,7 @@ CplxResult cplx_solve(ricadi_ctx* c, int ng, const CplxCoefs& cf, const double* 
     if (act.empty()) break;
     tab = cplx_table(act);
     // cycle start: v_0 = r / ||r||
-    launch_cplx_gmres_start(st, tab, mc, restart, k.nrm2.p, k.bnorm.p, k.gv.p, k.scale.p, k.resid.p);
-    launch_cplx_axpby(st, tab, gs, m2, 0.0, nullptr, 0, 1.0, k.scale.p, k.r.p, gs, k.V.p, gs);
+    cplx_cycle_start_launches(c, cy, tab);
     std::vector<int> cyc = act;
     GroupInts ks = same_int(0);
     for (int j = 0; j < restart && !cyc.empty(); ++j) {
@@ -194,8 +238,7 @@ CplxResult cplx_solve(ricadi_ctx* c, int ng, const CplxCoefs& cf, const double* 
       pc.bt.tab = ct;
       precond_apply(c, pc.bt, pc.pf, CycleIO{vj, gs, nullptr, zj, nullptr, 0});
       cplx_product(c, ct, cf, m2, zj, gs, k.w.p, gs);
-      cplx_orth(c, ct, m2, j + 1, k.V.p, vstride, gs, k.w.p, gs, ldp, k.V.p + (size_t)(j + 1) * vstride, gs);
-      launch_cplx_gmres_hess(st, ct, mc, j, restart, k.hout.p, gsh, k.Hm.p, k.cs.p, k.sn.p, k.gv.p, k.bnorm.p, k.resid.p);
+      cplx_arnoldi_launches(c, cy, ct, j);
       HIPCHK(hipMemcpyAsync(h8.data(), k.resid.p, sizeof(double) * ng * 8, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
       std::vector<int> on;
@@ -209,8 +252,7 @@ CplxResult cplx_solve(ricadi_ctx* c, int ng, const CplxCoefs& cf, const double* 
       cyc = on;
     }
     // cycle end: R y = g, x += Z y
-    launch_cplx_gmres_backsolve(st, tab, ks, mc, restart, k.Hm.p, k.gv.p, k.y.p, (size_t)restart * 16);
-    launch_cplx_update(st, tab, ks, n, m2, k.Zb.p, vstride, gs, k.y.p, (size_t)restart * 16, 1.0, dX, gs);
+    cplx_cycle_end_launches(c, cy, tab, ks, dX);
   }
   HIPCHK(hipStreamSynchronize(st));
   c->total_solves += ng;
@@ -281,6 +323,7 @@ int ricadi_cplx_orth_dev(ricadi_ctx* c, int ng, int mc, int nvec, const double* 
   API_BEGIN_ON(c)
   const int m2 = 2 * mc;
   cplx_ensure_work(c, ng, nvec, false);
+  c->cprobe = ricadi_ctx::CplxProbe();   // (the step writes the coefficient arrays of a probe cycle in flight)
   const int ldp = c->cw.nvec + 1;
   const GroupTab all = all_groups(ng);
   cplx_orth(c, all, m2, nvec, dV, (size_t)v_stride * 2, (size_t)g_stride * 2, dW, (size_t)nm * 2, ldp, dW,
@@ -288,6 +331,130 @@ int ricadi_cplx_orth_dev(ricadi_ctx* c, int ng, int mc, int nvec, const double* 
   for (int g = 0; g < ng; ++g)
     HIPCHK(hipMemcpy2DAsync(dH + (size_t)g * (nvec + 1) * m2, sizeof(double) * m2, c->cw.hout.p + (size_t)g * ldp * 16,
                             sizeof(double) * 16, sizeof(double) * m2, nvec + 1, hipMemcpyDeviceToDevice, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  API_END
+}
+
+// ---- step probe of the complex cycle (tests) --------------------------------------------------------------------
+// The units cplx_solve is made of -- cplx_cycle_start_launches, cplx_arnoldi_launches, cplx_cycle_end_launches -- one
+// call each on the solver's own workspace with the strides of a solve (cplx_cycle).  Neither the preconditioner nor
+// the operator runs: the caller supplies w.  Synchronous.
+static bool cplx_probe_live(const ricadi_ctx* c) {
+  const ricadi_ctx::CplxProbe& p = c->cprobe;
+  return p.ng > 0 && c->cw.basis && p.work == c->cw.V.p && p.restart == c->opts.gmres_restart && c->cw.n == c->n;
+}
+
+int ricadi_cplx_probe_begin_dev(ricadi_ctx* c, int ng, int mc, const double* dR, const double* bnorm) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(ng >= 1 && ng <= RICADI_MAX_GROUPS, RICADI_EINVAL, "1 <= ng <= 16 required");
+  REQUIRE(mc >= 1 && mc <= 8, RICADI_EINVAL, "complex panels have 1 <= mc <= 8 columns");
+  REQUIRE(dR && bnorm, RICADI_EINVAL, "NULL argument");
+  API_BEGIN_ON(c)
+  hipStream_t st = c->st;
+  c->cprobe = ricadi_ctx::CplxProbe();
+  const int restart = c->opts.gmres_restart;
+  cplx_ensure_work(c, ng, restart + 1, true);
+  ricadi_ctx::CplxWork& k = c->cw;
+  const CplxCycle cy = cplx_cycle(c, ng, mc);
+  const size_t G = (size_t)ng, rs = (size_t)restart;
+  // whatever a step does not write reads back as NaN (all bits set)
+  auto nan_fill = [&](DArr<double>& a, size_t count) { HIPCHK(hipMemsetAsync(a.p, 0xFF, sizeof(double) * count, st)); };
+  nan_fill(k.V, (rs + 1) * cy.vstride);
+  nan_fill(k.Hm, G * 8 * rs * (rs + 1) * 2);
+  nan_fill(k.cs, G * 8 * rs);
+  nan_fill(k.sn, G * 8 * rs * 2);
+  nan_fill(k.gv, G * 8 * (rs + 1) * 2);
+  nan_fill(k.y, G * cy.gsy);
+  nan_fill(k.scale, G * 16);
+  nan_fill(k.resid, G * 8);
+  nan_fill(k.hout, G * cy.gsh);
+  HIPCHK(hipMemcpyAsync(k.r.p, dR, sizeof(double) * cy.vstride, hipMemcpyDeviceToDevice, st));
+  std::vector<double> bn(G * 8, 0.0);
+  for (int g = 0; g < ng; ++g) std::copy(bnorm + (size_t)g * mc, bnorm + (size_t)(g + 1) * mc, bn.begin() + g * 8);
+  HIPCHK(hipMemcpyAsync(k.bnorm.p, bn.data(), sizeof(double) * bn.size(), hipMemcpyHostToDevice, st));
+  const GroupTab all = all_groups(ng);
+  launch_cplx_dots(st, all, cy.n, cy.m2, 0, 1, nullptr, 0, 0, k.r.p, cy.gs, k.partial.p, cy.ldp, k.nrm2.p, 16);
+  cplx_cycle_start_launches(c, cy, all);
+  HIPCHK(hipStreamSynchronize(st));
+  c->cprobe.ng = ng;
+  c->cprobe.mc = mc;
+  c->cprobe.restart = restart;
+  c->cprobe.kdone.assign(ng, 0);
+  c->cprobe.work = k.V.p;
+  API_END
+}
+
+int ricadi_cplx_probe_step_dev(ricadi_ctx* c, int j, const double* dW, int nact, const int* groups) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(cplx_probe_live(c), RICADI_EINVAL, "no probe cycle: call ricadi_cplx_probe_begin_dev first");
+  REQUIRE(j >= 0 && j < c->opts.gmres_restart, RICADI_EINVAL, "0 <= j < gmres_restart required");
+  REQUIRE(dW && groups && nact >= 1 && nact <= c->cprobe.ng, RICADI_EINVAL, "bad argument");
+  for (int i = 0; i < nact; ++i)
+    REQUIRE(groups[i] >= 0 && groups[i] < c->cprobe.ng && std::find(groups, groups + i, groups[i]) == groups + i,
+            RICADI_EINVAL, "distinct group ids in 0 .. ng-1 required");
+  API_BEGIN_ON(c)
+  hipStream_t st = c->st;
+  const CplxCycle cy = cplx_cycle(c, c->cprobe.ng, c->cprobe.mc);
+  for (int i = 0; i < nact; ++i) {
+    const size_t off = (size_t)groups[i] * cy.gs;
+    HIPCHK(hipMemcpyAsync(c->cw.w.p + off, dW + off, sizeof(double) * cy.gs, hipMemcpyDeviceToDevice, st));
+  }
+  cplx_arnoldi_launches(c, cy, cplx_table(std::vector<int>(groups, groups + nact)), j);
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < nact; ++i) c->cprobe.kdone[groups[i]] = j + 1;
+  API_END
+}
+
+int ricadi_cplx_probe_close_dev(ricadi_ctx* c, const int* ks, int nz, const double* dZ, double* dX) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(cplx_probe_live(c), RICADI_EINVAL, "no probe cycle: call ricadi_cplx_probe_begin_dev first");
+  REQUIRE(ks && dZ && dX && nz >= 1 && nz <= c->opts.gmres_restart, RICADI_EINVAL, "bad argument");
+  for (int g = 0; g < c->cprobe.ng; ++g)
+    REQUIRE(ks[g] >= 0 && ks[g] <= nz && ks[g] <= c->cprobe.kdone[g], RICADI_EINVAL,
+            "0 <= k_g <= min(nz, steps run for the group) required");
+  API_BEGIN_ON(c)
+  hipStream_t st = c->st;
+  const CplxCycle cy = cplx_cycle(c, c->cprobe.ng, c->cprobe.mc);
+  GroupInts kk = same_int(0);
+  for (int g = 0; g < c->cprobe.ng; ++g) kk.v[g] = ks[g];
+  HIPCHK(hipMemcpyAsync(c->cw.Zb.p, dZ, sizeof(double) * (size_t)nz * cy.vstride, hipMemcpyDeviceToDevice, st));
+  cplx_cycle_end_launches(c, cy, all_groups(c->cprobe.ng), kk, dX);
+  HIPCHK(hipStreamSynchronize(st));
+  API_END
+}
+
+int ricadi_cplx_probe_read_dev(ricadi_ctx* c, int what, int slot, double* dOut, int64_t cap, int64_t* count) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(cplx_probe_live(c), RICADI_EINVAL, "no probe cycle: call ricadi_cplx_probe_begin_dev first");
+  REQUIRE(dOut && count && cap >= 0, RICADI_EINVAL, "bad argument");
+  REQUIRE(what >= RICADI_CPROBE_V && what <= RICADI_CPROBE_NRM2, RICADI_EINVAL, "unknown probe quantity");
+  REQUIRE(what != RICADI_CPROBE_V || (slot >= 0 && slot <= c->opts.gmres_restart), RICADI_EINVAL,
+          "0 <= slot <= gmres_restart required");
+  API_BEGIN_ON(c)
+  const ricadi_ctx::CplxWork& k = c->cw;
+  const CplxCycle cy = cplx_cycle(c, c->cprobe.ng, c->cprobe.mc);
+  const size_t G = (size_t)c->cprobe.ng, rs = (size_t)cy.restart;
+  const double* src = nullptr;
+  size_t cnt = 0;
+  switch (what) {
+    case RICADI_CPROBE_V: src = k.V.p + (size_t)slot * cy.vstride, cnt = cy.vstride; break;
+    case RICADI_CPROBE_HOUT: src = k.hout.p, cnt = G * (rs + 2) * 16; break;
+    case RICADI_CPROBE_HM: src = k.Hm.p, cnt = G * 8 * rs * (rs + 1) * 2; break;
+    case RICADI_CPROBE_CS: src = k.cs.p, cnt = G * 8 * rs; break;
+    case RICADI_CPROBE_SN: src = k.sn.p, cnt = G * 8 * rs * 2; break;
+    case RICADI_CPROBE_GV: src = k.gv.p, cnt = G * 8 * (rs + 1) * 2; break;
+    case RICADI_CPROBE_Y: src = k.y.p, cnt = G * cy.gsy; break;
+    case RICADI_CPROBE_SCALE: src = k.scale.p, cnt = G * 16; break;
+    case RICADI_CPROBE_RESID: src = k.resid.p, cnt = G * 8; break;
+    default: src = k.nrm2.p, cnt = G * 16; break;
+  }
+  *count = (int64_t)cnt;
+  if ((int64_t)cnt > cap) throw HipError{"output buffer too small"};
+  if (what == RICADI_CPROBE_HOUT)   // rows 0 .. gmres_restart + 1 of every group (the group stride is the workspace's)
+    HIPCHK(hipMemcpy2DAsync(dOut, sizeof(double) * (rs + 2) * 16, src, sizeof(double) * cy.gsh,
+                            sizeof(double) * (rs + 2) * 16, G, hipMemcpyDeviceToDevice, c->st));
+  else
+    HIPCHK(hipMemcpyAsync(dOut, src, sizeof(double) * cnt, hipMemcpyDeviceToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   API_END
 }

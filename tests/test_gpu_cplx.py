@@ -1,7 +1,11 @@
 """GPU tests of the complex-shift path (ricadi_cplx.hip, solver_cplx.inl, lqgbt.freq_response)
 against the FP64 model of tests/cplx_model.py and dense complex references, on the tiny and irregular operators of
 tests/small_ops.py, the N = 4 finite-element operator and -- for one full-width launch of the tiled product -- cfg2's
-operator (N = 58).  Every check prints ``[cplx] operator | check | measured | bound`` before it asserts.
+operator (N = 58).  The product also runs on the operators that reach what the family does not: rows longer than the 48
+entries a tile row keeps in registers (tiled form), the two sides of ``max_cols <= 160``, a CSR case without constraints
+and several groups per ``grid.y`` slot; the CGS2 entry on more than one chunk of 32 basis vectors, on a column with
+nothing left over and on a narrow call after a wide one.  The GMRES cycle's own kernels have
+tests/test_gpu_cplx_steps.py.  Every check prints ``[cplx] operator | check | measured | bound`` before it asserts.
 
 tests/test_cplx_model_cpu.py holds the model to its references; it has to pass for these to mean anything.
 """
@@ -174,6 +178,84 @@ def test_product_full_width_at_cfg2():
     assert _say("fe58", "tiled product ng 16 mc 8: error / bound", worst, 1.0)
 
 
+class _Op:
+    """(calA, calE, J) with the attributes of a SmallOp that _product_checks uses."""
+
+    def __init__(self, name, ops, **opts):
+        self.name, self.ops, self.opts = name, ops, opts
+        self.nv, self.np = ops[0].shape[0], ops[2].shape[0]
+        self.n = self.nv + self.np
+
+
+def _tile_row_lengths(tiles):
+    return np.diff(tiles["rp2"], axis=1).ravel()
+
+
+def test_product_long_rows_on_the_tiled_form():
+    """The streamed tail of the tiled product (entries from the 49th of a row on), which no operator of the small
+    family reaches (their longest tile row has 45 entries; the arrowhead operator takes the CSR form): the ``long100``
+    operator of test_gpu_saddle_spmm.py with a 48 added -- rows of exactly 48 (registers only), 49 (one streamed
+    entry), 64 and 100 entries and a pressure row of 60, tiled form."""
+    ops, rows = cm.long_row_operator()
+    op = _Op("long100+48", ops)
+    tiles = _lib.host_saddle_tiles(*ops)
+    lens = _tile_row_lengths(tiles)
+    print("[cplx] %s | n %d, widened rows %s, longest tile rows %s, max_cols %d" %
+          (op.name, op.n, rows, sorted(lens)[-5:], tiles["max_cols"]))
+    assert tiles["ms_ok"] and op.n == 1937 and lens.max() == 100 and np.sum(lens == 48) >= 1 and np.sum(lens == 49) >= 1
+    with _lib.Context(0) as ctx:
+        ctx.set_operator(*ops)
+        _product_checks(op, ctx)
+
+
+@pytest.mark.parametrize("nv,seed,tiled", [(160, 860, True), (161, 861, False)])
+def test_product_at_the_max_cols_boundary(nv, seed, tiled):
+    """The two sides of the rule ``max_cols <= 160`` of the tiled form: the arrowhead operator with 160 unknowns has
+    one row of 160 entries and row blocks of 160 columns (tiled, 112 streamed entries in one row); with 161 it takes
+    the CSR form -- the one CSR case without constraints (np = 0)."""
+    op = _Op("arrow%d" % nv, so.synthetic(nv=nv, np_=0, seed=seed, arrow=True, lumped=True))
+    tiles = _lib.host_saddle_tiles(*op.ops)
+    assert tiles["max_cols"] == nv and tiles["ms_ok"] == tiled and _tile_row_lengths(tiles).max() == nv and op.np == 0
+    with _lib.Context(0) as ctx:
+        ctx.set_operator(*op.ops)
+        _product_checks(op, ctx)
+
+
+@pytest.mark.parametrize("active", [list(range(0, 16, 2)), None], ids=["every-second-group", "all-groups"])
+def test_product_several_groups_per_slot(active):
+    """nv65_np24 (tiled, 4 row blocks), ng = 16, mc = 8, every active group compared entry by entry.  The tiled launch
+    splits the active groups over at most 8 ``grid.y`` slots: the eight groups 0, 2, .. 14 get a slot each, gathered
+    through the group table; all sixteen give every slot two groups, which reuse the one LDS tile between the two
+    barriers."""
+    op = so.get("nv65_np24")
+    rng = np.random.default_rng(160)
+    alphas, betas = list(SHIFTS16), list(1.0 + 0.125 * np.arange(16))
+    act = list(range(16)) if active is None else active
+    X = np.full((16, op.n, 8), np.nan + 1j * np.nan)
+    X[act] = _crandn(rng, len(act), op.n, 8)
+    assert _lib.host_saddle_tiles(*op.ops, **op.opts)["ms_ok"]
+    with _lib.Context(0, **op.opts) as ctx:
+        ctx.set_operator(*op.ops)
+        Xd = _cdev(X)
+        outs = []
+        for _ in range(2):
+            Yd = _cdev(np.full(X.shape, np.nan + 1j * np.nan))
+            _, var = ctx.op_apply_cplx_batch_dev(alphas, Xd, betas=betas, Y_t=Yd, active=active)
+            outs.append(_host(Yd))
+            assert var == 1
+    Y = outs[0]
+    assert np.array_equal(outs[0].view(np.float64), outs[1].view(np.float64), equal_nan=True), "not bitwise repeatable"
+    worst = 0.0
+    for g in range(16):
+        if g not in act:
+            assert np.all(np.isnan(Y[g].view(np.float64))), "an inactive group was written"
+            continue
+        ref, bound = cm.product(op.ops, alphas[g], betas[g], X[g])
+        assert np.all(np.isfinite(Y[g].view(np.float64)))
+        worst = max(worst, float(np.max(np.abs(Y[g] - ref) / np.maximum(bound, np.finfo(float).tiny))))
+    assert _say(op.name, "product ng 16 mc 8, %d active groups: error / bound" % len(act), worst, 1.0)
+
+
 # ------------------------------------------------------------------------------------------------ 7. the CGS2 step
 @pytest.fixture(scope="module", params=[3, 61, 450, 1937])
 def orth_ctx(request):
@@ -188,12 +270,14 @@ def orth_ctx(request):
 
 @pytest.mark.parametrize("ng", [1, 3])
 @pytest.mark.parametrize("mc", [1, 8])
-@pytest.mark.parametrize("nvec", [1, 2, 9])
+@pytest.mark.parametrize("nvec", [1, 2, 9, 31, 32, 33, 70])
 def test_cgs2_step(orth_ctx, nvec, mc, ng):
     """One CGS2 step against an orthonormal basis (NumPy QR, per group and column): the new vector is orthogonal to the
     basis to ``8 n eps``, ``w_in = V h + h_last w_out`` to ``8 (nvec + 2) n eps ||w_in||``, the coefficients within the
     model's bound of ``V^H w`` (cplx_model.cgs2_coef_bound), bitwise twice.  Where nvec >= n (n = 3, nvec = 9) an
-    orthonormal basis that leaves something over has at most n - 1 vectors: that many are used."""
+    orthonormal basis that leaves something over has at most n - 1 vectors: that many are used (n = 61 runs 31, 32,
+    33 and 60).  The dot pass walks the basis in chunks of 32: 31 and 32 fill one chunk, 33 and 70 start a second and
+    a third one (a partial one each), which reuse the LDS staging of the first."""
     n, ctx = orth_ctx
     nv_ = min(nvec, n - 1)
     rng = np.random.default_rng(1000 * n + 100 * nvec + 10 * mc + ng)
@@ -227,6 +311,75 @@ def test_cgs2_step(orth_ctx, nvec, mc, ng):
                                                        (8 * (nv_ + 2) * n * EPS * np.linalg.norm(W[g, :, c]))))
     ok = [_say("n %d" % n, "cgs2 nvec %d mc %d ng %d: %s / bound" % (nv_, mc, ng, k), v, 1.0) for k, v in worst.items()]
     assert all(ok), worst
+
+
+def _orth_basis(rng, nvec, ng, n, mc):
+    V = np.zeros((nvec, ng, n, mc), dtype=np.complex128)
+    for g in range(ng):
+        for c in range(mc):
+            V[:, g, :, c] = np.linalg.qr(_crandn(rng, n, nvec))[0].T
+    return V
+
+
+def test_cgs2_nothing_left(orth_ctx):
+    """A column with nothing left over goes through the CGS2 entry: column 0 of group 0 is zero -- its coefficients
+    and ``h_last`` are exactly zero and the returned vector is exactly zero, not NaN --, column 1 of group 1 lies in
+    the span of the basis up to rounding (``W = V c``): its coefficients are within the model's bound of ``c``,
+    ``h_last`` is at rounding level (``8 (nvec + 2) n eps ||w||``; no bar on the direction of what is left), and every
+    returned value of either case is finite.  The other columns are ordinary and meet the bars of test_cgs2_step."""
+    n, ctx = orth_ctx
+    nvec, ng, mc = min(9, n - 1), 2, 3
+    rng = np.random.default_rng(5000 + n)
+    V = _orth_basis(rng, nvec, ng, n, mc)
+    W = _crandn(rng, ng, n, mc)
+    W[0, :, 0] = 0.0
+    coef = _crandn(rng, nvec)
+    W[1, :, 1] = V[:, 1, :, 1].T @ coef
+    Wd = _cdev(W)
+    H = _host(ctx.cplx_orth_dev(_cdev(V), Wd))
+    Wo = _host(Wd)
+    assert np.all(np.isfinite(H.view(np.float64))) and np.all(np.isfinite(Wo.view(np.float64)))
+    assert np.all(H[0, :, 0] == 0.0) and np.all(Wo[0, :, 0] == 0.0), "a zero column did not come back as zeros"
+    assert np.all(H[:, nvec].imag == 0.0) and np.all(H[:, nvec].real >= 0.0)
+    worst = 0.0
+    for g in range(ng):
+        exact, bound = cm.cgs2_coef_bound(V[:, g], W[g])
+        err = np.abs(H[g, :nvec] - exact)
+        worst = max(worst, float(np.max(np.where(err == 0.0, 0.0, err / np.maximum(bound, np.finfo(float).tiny)))))
+    ok = _say("n %d" % n, "cgs2 zero / in-span columns: coef / bound", worst, 1.0)
+    wn = float(np.linalg.norm(W[1, :, 1]))
+    ok &= _say("n %d" % n, "cgs2 in-span column: h_last", float(H[1, nvec, 1].real), 8 * (nvec + 2) * n * EPS * wn)
+    for g, c in ((0, 1), (0, 2), (1, 0), (1, 2)):
+        Vc = V[:, g, :, c].T
+        ok &= _say("n %d" % n, "cgs2 ordinary column (%d, %d): orth / bound" % (g, c),
+                   float(np.linalg.norm(Vc.conj().T @ Wo[g, :, c]) / (8 * n * EPS)), 1.0)
+        assert H[g, nvec, c].real > 0.0
+    assert ok
+
+
+def test_cgs2_narrow_call_after_a_wide_one():
+    """The workspaces only grow: after a call with nvec = 40 the row stride of the coefficient arrays (41 rows) is
+    larger than the 3 rows a call with nvec = 2 fills.  The narrow call's result on that context is bitwise the
+    result on a fresh context."""
+    n, ng, mc = 61, 3, 8
+    rng = np.random.default_rng(4002)
+    V40, V2 = _orth_basis(rng, 40, ng, n, mc), _orth_basis(rng, 2, ng, n, mc)
+    W40, W2 = _crandn(rng, ng, n, mc), _crandn(rng, ng, n, mc)
+    ops = so.synthetic(nv=n, np_=0, seed=700 + n, lumped=True)
+
+    def narrow(wide_first):
+        with _lib.Context(0) as ctx:
+            ctx.set_operator(*ops)
+            if wide_first:
+                assert np.all(np.isfinite(_host(ctx.cplx_orth_dev(_cdev(V40), _cdev(W40))).view(np.float64)))
+            Wd = _cdev(W2)
+            H = _host(ctx.cplx_orth_dev(_cdev(V2), Wd))
+            return H, _host(Wd)
+
+    (H1, W1), (H0, W0) = narrow(True), narrow(False)
+    assert np.all(np.isfinite(H0.view(np.float64))) and np.all(H0[:, 2].real > 0.0)
+    assert np.array_equal(H1.view(np.float64), H0.view(np.float64)), "coefficients differ after a wide call"
+    assert np.array_equal(W1.view(np.float64), W0.view(np.float64)), "unit vectors differ after a wide call"
 
 
 # ------------------------------------------------------------------------------------------------ 8. the solve

@@ -387,11 +387,10 @@ struct ricadi_ctx {
   std::vector<int> radi_sweep_widths;
   // per-shift data
   std::map<std::pair<double, double>, std::unique_ptr<ShiftData>> cache;
-  // The ONE entry the RADI driver rebuilds for every generated shift (a level owns its own): it is lent to `cache`
-  // under the shift's key for the duration of a step and taken back, so that generated shifts leave nothing in the
-  // map and the buffers are reused from step to step and from call to call (OwnedShift, solver_radi.inl)
-  std::unique_ptr<ShiftData> radi_sd;
-  // ... and the entries a sweep of generated shifts borrows the same way, one per solve of the sweep (OwnedShifts)
+  // The entries the RADI driver rebuilds for its generated shifts (a level owns its own): entry g is lent to `cache`
+  // under the key of solve g of a sweep -- entry 0 under the one shift of a sequential step -- and taken back, so that
+  // generated shifts leave nothing in the map and the buffers are reused from step to step and from call to call
+  // (OwnedShifts, solver_radi.inl)
   std::vector<std::unique_ptr<ShiftData>> radi_sdv;
   // workspaces
   int wcols = 0, wrestart = 0;   // total columns (width x groups) and restart length the workspace holds

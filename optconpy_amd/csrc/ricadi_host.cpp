@@ -2035,10 +2035,14 @@ static long double radi_sweep_pivot(const double* ps, int g) {
 }
 
 int radi_sweep_groups(int mw, int nb) { return mw + nb > 32 ? (mw + nb + 15) / 16 : 1; }
+// The widest sweep the kernels and the batched solve take at these panel widths
+int radi_sweep_cap(int mw, int nb) {
+  return std::min(RICADI_RADI_SWEEP_MAX_K / mw, RICADI_MAX_GROUPS / radi_sweep_groups(mw, nb));
+}
 
 // The effective sweep width of a cycled list (1: the sequential form).  Host arithmetic only.
 int radi_sweep_width(const double* shifts, int ns, int mw, int nb, int want, int max_steps) {
-  int G = std::min(std::min(want, ns), std::min(RICADI_RADI_SWEEP_MAX_K / mw, RICADI_MAX_GROUPS / radi_sweep_groups(mw, nb)));
+  int G = std::min(std::min(want, ns), radi_sweep_cap(mw, nb));
   G = std::max(1, std::min(G, max_steps));
   std::vector<double> ps;
   for (; G >= 2; G /= 2) {

@@ -618,11 +618,13 @@ int lqg_balance(int kc, int kf, const double* S, double tol, int order, int* r_o
                 double* coefR);
 // The sweep form of RADI.  Host (ricadi_host.cpp; ricadi_host_radi_sweep / _sweep_width): the kept
 // steps, the residual after each and the coefficient matrix Cf (g m x (k m + m + nb)) from what a sweep has fetched;
-// the effective width of a cycled list; the column groups the batched solve makes of an (mw + nb)-wide panel.
+// the effective width of a cycled list; the column groups the batched solve makes of an (mw + nb)-wide panel; the
+// widest sweep those groups and the kernels' RICADI_RADI_SWEEP_MAX_K columns allow.
 int radi_sweep(int g, int m, int nb, const double* shifts, const double* Ghat, const double* Gamma, double rhs,
                double res_reltol, int steps_left, int* k_out, double* res_out, double* Cf_out);
 int radi_sweep_width(const double* shifts, int ns, int mw, int nb, int want, int max_steps);
 int radi_sweep_groups(int mw, int nb);
+int radi_sweep_cap(int mw, int nb);
 // Device (ricadi_radi.hip): Z[:, zc : zc + k m] = Vh Cf[:, :k m], [R | U] += S Cf[:, k m:]; Vh's panel g at
 // V + g vstride (leading dimension ldv, m columns used), S nv x G m with leading dimension lds.
 void launch_radi_sweep_combine(hipStream_t st, int nv, int G, int m, int nb, int k, const double* V, size_t vstride,

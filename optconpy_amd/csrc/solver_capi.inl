@@ -252,7 +252,6 @@ int ricadi_synchronize(ricadi_ctx* c) {
 static void forget_operator(ricadi_ctx* c) {
   c->has_op = false;
   c->cache.clear();
-  c->radi_sd.reset();
   c->radi_sdv.clear();
   c->child.reset();
   c->q = 0;

@@ -20,49 +20,15 @@ struct RadiStats {
   bool breakdown = false;           // the factorisation kernel met a pivot that is not positive and finite
 };
 
-// The per-shift entry of a GENERATED shift (RICADI_RADI_SHIFTS_HAMILTONIAN): c->cache is an unbounded map keyed by the
-// shift, and thirty distinct shifts per call would each leave their per-shift data behind (the dense coarse inverse
-// alone is about 40 MB at cfg2).  Instead every level lends its one ricadi_ctx::radi_sd to its map under the shift's
-// key, marked stale -- so that setup_issue rebuilds it in the buffers it already has and resets smw_epoch and the
-// `rec` serials, as for any stale entry -- and takes it back before the next shift, at the end of the call and when
-// the call is left by an exception.  A level whose map already holds the key (a shift of the caller's list) is left
-// alone.
-struct OwnedShift {
-  ricadi_ctx* c;
-  std::pair<double, double> key{0.0, 0.0};
-  std::vector<ricadi_ctx*> lent;
-  explicit OwnedShift(ricadi_ctx* ctx) : c(ctx) {}
-  OwnedShift(const OwnedShift&) = delete;
-  OwnedShift& operator=(const OwnedShift&) = delete;
-  void lend(double p) {
-    take_back();
-    key = std::make_pair(p, 1.0);
-    for (ricadi_ctx* l = c; l; l = l->child.get()) {
-      if (l->cache.count(key)) continue;
-      if (!l->radi_sd) l->radi_sd.reset(new ShiftData);
-      l->radi_sd->valid = false;
-      l->radi_sd->last_iters = -1;
-      l->radi_sd->sub = nullptr;
-      lent.push_back(l);              // (before the emplace: if that throws, take_back finds nothing to take)
-      l->cache.emplace(key, std::move(l->radi_sd));
-    }
-  }
-  void take_back() {
-    for (ricadi_ctx* l : lent) {
-      auto it = l->cache.find(key);
-      if (it == l->cache.end()) continue;
-      l->radi_sd = std::move(it->second);
-      l->cache.erase(it);
-    }
-    lent.clear();
-  }
-  ~OwnedShift() { take_back(); }
-};
-
-// The same for the up to RICADI_MAX_GROUPS generated shifts of one SWEEP (ricadi_set_radi_sweep_shifts; DESIGN.md
-// 3d-4): solve g of the sweep borrows entry g of the level's ricadi_ctx::radi_sdv (ricadi_ctx::radi_sd stays with the
-// sequential modes).  take_back() before a sweep that takes an entry of the caller's list: that one enters the cache
-// as any listed shift does.
+// The per-shift entries of GENERATED shifts (RICADI_RADI_SHIFTS_HAMILTONIAN[_DOMINANT]; the up to RICADI_MAX_GROUPS
+// of one sweep with ricadi_set_radi_sweep_shifts): c->cache is an unbounded map keyed by the shift, and
+// thirty distinct shifts per call would each leave their per-shift data behind (the dense coarse inverse alone is about
+// 40 MB at cfg2).  Instead every level lends entry g of its ricadi_ctx::radi_sdv to its map under the key of shift g
+// -- a sequential step lends entry 0: lend(&p, 1) --, marked stale -- so that setup_issue rebuilds it in the buffers it
+// already has and resets smw_epoch and the `rec` serials, as for any stale entry -- and takes it back before the next
+// shifts, at the end of the call and when the call is left by an exception.  A level whose map already holds the key
+// (a shift of the caller's list) is left alone.  take_back() before a solve that takes an entry of the caller's list:
+// that one enters the cache as any listed shift does.
 struct OwnedShifts {
   ricadi_ctx* c;
   std::vector<std::pair<std::pair<double, double>, std::pair<ricadi_ctx*, int>>> lent;      // key, (level, slot)
@@ -80,7 +46,7 @@ struct OwnedShifts {
         l->radi_sdv[g]->valid = false;
         l->radi_sdv[g]->last_iters = -1;
         l->radi_sdv[g]->sub = nullptr;
-        lent.push_back(std::make_pair(key, std::make_pair(l, g)));      // (before the emplace, as OwnedShift)
+        lent.push_back(std::make_pair(key, std::make_pair(l, g)));      // (before the emplace: should that throw)
         l->cache.emplace(key, std::move(l->radi_sdv[g]));
       }
     }
@@ -160,205 +126,36 @@ static void radi_dense_step(ricadi_ctx* c, double p, const double* dV, int ldv, 
   launch_radi_update(st, c->nv, m, nb, c->E.rp.p, c->E.ci.p, c->E.v.p, dV, ldv, dC, dRU, dZ, zld, zc);
 }
 
-// The SWEEP form of the iteration (effective width Gw > 1; the formulas at
-// ricadi_set_radi_sweep_width): the loop of ric_radi_run below with G <= Gw steps per pass.
-//   1. ONE solve_batch with the G shifts against the panel [R_0 | U_0] (gsb = 0, c->q = nb, lr_ucol = m: the `dup`
-//      path, S^-1 U out of the same solve for every shift; while U is identically zero the m columns of R, plain);
-//   2. P = [R_0 | cal E Vh] (launch_sweep_resid_panel on the compacted solution panels), Gamma = P^T P
-//      (launch_gram_fixed), Gh_g = Vh_g^T B (launch_radi_vtb per shift): fixed summation orders;
-//   3. the sweep's host synchronisation: Gamma and Gh;
-//   4. ricadi::radi_sweep: the steps kept, the residual after each, the coefficient matrix Cf;
-//   5. Cf uploaded;  6. launch_radi_sweep_combine: the kept blocks of Z, [R | U] advanced to R_k, U_k.
-// CYCLE mode (gen = false): sweep s takes the next G = min(Gw, steps left) entries of the cycled list.
-// GENERATED shifts (gen = true: ricadi_set_radi_sweep_shifts with RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT; DESIGN.md
-// 3d-4): the first sweep is ONE step with shifts[0]; after the stop test of a sweep that does not end the iteration
-//   7. the CholQR2 of the group of Z the sweep kept (its last min(k, 127 / m) blocks, read where they lie in c->Z,
-//      BEFORE any recompression) and the reduction H = Q^T [cal A Q | cal E Q | R | U | B] (radi_shift_issue at
-//      c = blocks * m columns), H, R and the QR's flag fetched: the sweep's SECOND host synchronisation (block_qr_dev
-//      and the reduction once more where the flag is raised);
-//   8. ricadi::radi_next_shifts_dominant: up to min(Gw, steps left) shifts for the next sweep, in acceptance order.
-// A refused selection (or one after a step ricadi_probe_radi_refuse lists) makes the next sweep ONE step with the next
-// entry of `shifts` (a counter of its own from shifts[1], cycling).  Generated shifts borrow their per-shift entries
-// (OwnedShifts); entries of the list enter the cache.
-// hbuf: pinned, nc^2 + K nb + K (K + m + nb) doubles (nc = K + m, K = Gw m), and with gen cq (2 cq + m + 2 nb) + cq^2
-// + 1 more (cq = min(Gw, 127 / m) m).
-static void radi_run_sweeps(ricadi_ctx* c, RadiStats& stt, const double* shifts, int ns, int Gw, bool gen,
-                            const double* dB, int nb, int m, double* dRU, bool uzero, int max_steps, double res_reltol,
-                            int compress_cols, bool verbose, double* hbuf) {
-  hipStream_t st = c->st;
-  const int nv = c->nv, n = c->n, mp = m + nb, Kw = Gw * m, ncw = Kw + m;
-  TArr<double> dR0(c->pool, (size_t)nv * m), dVc(c->pool, (size_t)nv * Kw), dP(c->pool, (size_t)nv * ncw),
-      dGh(c->pool, (size_t)Kw * nb), dGam(c->pool, (size_t)ncw * ncw), dCf(c->pool, (size_t)Kw * (Kw + mp)),
-      dPart(c->pool, radi_vtb_partial_len(nv, m, nb));
-  c->res_part.ensure(gram_fixed_partial_len(nv, ncw));
-  c->sweep_u.ensure((size_t)n * mp * Gw);
-  double *hGam = hbuf, *hGh = hGam + (size_t)ncw * ncw, *hCf = hGh + (size_t)Kw * nb;
-  // generated shifts: the group's scratch, the fetched H, R and flag behind the sweep's own host buffers
-  const int cqw = std::min(Gw, 127 / m) * m;
-  double *hH = gen ? hCf + (size_t)Kw * (Kw + mp) : nullptr, *hR = gen ? hH + (size_t)cqw * (2 * cqw + m + 2 * nb) : nullptr;
-  int* hqr = gen ? reinterpret_cast<int*>(hR + (size_t)cqw * cqw) : nullptr;
-  int* qrflag = c->flag.p + 1;              // (block_qr_dev's word: the fallback QR reuses it)
-  RadiShiftWork sw(c);
-  OwnedShifts owned(c);
-  if (gen) sw.alloc(c, cqw, m, nb);
-  std::vector<double> ps(Gw), be(Gw, 1.0), resv(Gw), psn(Gw), crit(Gw);
-  std::vector<ShiftData*> sds(Gw);
-  std::vector<GmresResult> res(Gw);
-  int zc_last = 0, sweeps = 0;
-  int Gnext = 1, nfb = 1;                   // gen: the solves of the next sweep (its shifts in ps), the list's counter
-  bool listed = true;                       // gen: the next sweep takes an entry of the caller's list
-  if (gen) ps[0] = shifts[0];
-  // RICADI_TIMING: setup, solve, reductions + fetch, host, combine, QR + reduction, selection
-  double tph[7] = {0, 0, 0, 0, 0, 0, 0};
-  Tick tk;
-  auto lap = [&](int i) {
-    if (c->sw.timing) {
-      (void)hipStreamSynchronize(st);
-      tph[i] += tk.lap();
-    }
-  };
-  while (stt.steps < max_steps) {
-    const int left = max_steps - stt.steps, G = gen ? Gnext : std::min(Gw, left), K = G * m, nc = K + m;
-    if (!gen)
-      for (int g = 0; g < G; ++g) ps[g] = shifts[(stt.steps + g) % ns];
-    if (c->sw.timing) tk.lap();
-    if (gen) {
-      if (listed) owned.take_back();
-      else owned.lend(ps.data(), G);
-    }
-    get_shifts(c, ps.data(), be.data(), G, sds.data());
-    lap(0);
-    double* x = c->sweep_u.p;
-    int ldv = m;
-    if (uzero) {
-      c->q = 0;
-      launch_copy_cols(st, nv, m, dRU, mp, 0, c->bvec.p, m, 0, 1.0);
-      if (c->np > 0) HIPCHK(hipMemsetAsync(c->bvec.p + (size_t)nv * m, 0, sizeof(double) * (size_t)c->np * m, st));
-      solve_batch(c, sds.data(), G, c->bvec.p, 0, x, m, false, nullptr, res.data());
-    } else {
-      c->q = nb;
-      ++c->lr_epoch;
-      launch_copy_cols(st, nv, nb, dRU, mp, m, c->U.p, nb, 0, 1.0);
-      c->lr_ucol = m;
-      load_rhs(c, dRU, mp, c->bvec.p);
-      solve_batch(c, sds.data(), G, c->bvec.p, 0, x, mp, true, nullptr, res.data());
-      c->lr_ucol = -1;
-      ldv = mp;
-    }
-    const size_t vstride = (size_t)n * ldv;
-    int its = 0;
-    for (int g = 0; g < G; ++g) {
-      its = std::max(its, res[g].iters);
-      if (res[g].converged) continue;
-      stt.nonconverged++;
-      stt.worst_relres = std::max(stt.worst_relres, res[g].max_relres);
-      if (verbose)
-        fprintf(stderr, "[ricadi] RADI sweep %d shift %g: GMRES stopped at relres %.2e after %d its\n", sweeps + 1,
-                ps[g], res[g].max_relres, res[g].iters);
-    }
-    stt.shift_solves += G;
-    c->radi_sweep_widths.push_back(G);
-    lap(1);
-    // the reductions: P = [R_0 | cal E Vh], its Gram matrix, Gh
-    launch_copy_cols(st, nv, m, dRU, mp, 0, dR0.p, m, 0, 1.0);
-    const double* vb = x;
-    size_t vs = vstride;
-    if (ldv != m) {
-      for (int g = 0; g < G; ++g) launch_copy_cols(st, nv, m, x + g * vstride, ldv, 0, dVc.p + (size_t)g * nv * m, m, 0, 1.0);
-      vb = dVc.p;
-      vs = (size_t)nv * m;
-    }
-    launch_sweep_resid_panel(st, nv, m, G, c->E.rp.p, c->E.ci.p, c->E.v.p, dR0.p, vb, vs, dP.p);
-    c->res_part.ensure(gram_fixed_partial_len(nv, nc));       // (a narrower sweep slices the rows differently)
-    launch_gram_fixed(st, nv, nc, dP.p, nc, c->res_part.p, dGam.p);
-    for (int g = 0; g < G; ++g)
-      launch_radi_vtb(st, nv, m, nb, x + g * vstride, ldv, dB, dPart.p, dGh.p + (size_t)g * m * nb);
-    c->res_launches += 3 + 2 * G;
-    HIPCHK(hipMemcpyAsync(hGam, dGam.p, sizeof(double) * nc * nc, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hGh, dGh.p, sizeof(double) * K * nb, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (c->sw.timing) tph[2] += tk.lap();
-    if (sweeps == 0) stt.rhs = gram_block_fro(hGam, nc, m, 0);
-    int k = 0;
-    const int rc = ricadi::radi_sweep(G, m, nb, ps.data(), hGh, hGam, stt.rhs, res_reltol, left, &k, resv.data(), hCf);
-    if (c->sw.timing) tph[3] += tk.lap();
-    if (rc != RICADI_OK) {
-      c->radi_shift_hist.push_back(ps[0]);
-      stt.breakdown = true;
-      break;
-    }
-    const int km = k * m;
-    HIPCHK(hipMemcpyAsync(dCf.p, hCf, sizeof(double) * K * (km + mp), hipMemcpyHostToDevice, st));
-    launch_radi_sweep_combine(st, nv, G, m, nb, k, x, vstride, ldv, dP.p + m, nc, dCf.p, dRU, c->Z.p, c->zld, c->zc);
-    uzero = false;
-    ++sweeps;
-    c->zc += km;
-    for (int j = 0; j < k; ++j) {
-      c->radi_shift_hist.push_back(ps[j]);
-      c->adi_res_hist.push_back(resv[j]);
-      if (verbose)
-        fprintf(stderr, "[ricadi] RADI step %3d: shift %10.3e%s rel residual %9.3e (sweep %d of %d solves, gmres its %d)\n",
-                stt.steps + j + 1, ps[j], !gen ? "" : sweeps == 1 ? " (first)" : listed ? " (fallback)" : " (generated)",
-                resv[j], sweeps, G, its);
-    }
-    stt.steps += k;
-    stt.res = resv[k - 1];
-    lap(4);
-    if (stt.res <= res_reltol) {
-      c->adi_stop_rule = RICADI_STOP_RES;
-      break;
-    }
-    if (gen && stt.steps < max_steps) {
-      // the group of Z the sweep kept, where it lies in the factor: its QR, the reduction, the second synchronisation
-      const int cq = std::min(k, 127 / m) * m, hw = 2 * cq + m + 2 * nb;
-      const double* dZg = c->Z.p + (c->zc - cq);
-      auto fetch = [&] {
-        HIPCHK(hipMemcpyAsync(hH, sw.H.p, sizeof(double) * cq * hw, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(hR, sw.Rq.p, sizeof(double) * cq * cq, hipMemcpyDeviceToHost, st));
-      };
-      radi_shift_issue(c, sw, dZg, c->zld, cq, m, dRU, dB, nb, qrflag);
-      fetch();
-      HIPCHK(hipMemcpyAsync(hqr, qrflag, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      if (*hqr != 0) {
-        // the group's Gram matrix is not positive definite to working precision: Householder TSQR, and H once more
-        block_qr_dev(c, dZg, c->zld, nv, cq, sw.Q.p, sw.Rq.p);
-        launch_radi_reduce(st, nv, cq, m, nb, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, sw.Q.p, dRU, dB, sw.part.p,
-                           sw.H.p);
-        fetch();
-        HIPCHK(hipStreamSynchronize(st));
-        ++c->radi_qr_repeats;
-      }
-      if (c->sw.timing) tph[5] += tk.lap();
-      const int want = std::min(Gw, max_steps - stt.steps);
-      int kept = 0, nsel = 0;
-      listed = ricadi::radi_next_shifts_dominant(cq, m, nb, hH, hR, want, psn.data(), crit.data(), &nsel, &kept) != 0 ||
-               std::find(c->radi_refuse.begin(), c->radi_refuse.end(), stt.steps) != c->radi_refuse.end();
-      c->radi_kept_hist.push_back(kept);
-      if (listed) {
-        ps[0] = shifts[nfb++ % ns];
-        Gnext = 1;
-        ++c->radi_fallbacks;
-      } else {
-        std::copy(psn.begin(), psn.begin() + nsel, ps.begin());
-        Gnext = nsel;
-      }
-      if (c->sw.timing) tph[6] += tk.lap();
-    }
-    if (stt.steps < max_steps && c->zc - zc_last >= compress_cols) {
-      factor_recompress(c);
-      ++c->radi_recompressions;
-      zc_last = c->zc;
-    }
+// The pinned host buffer of one call (res_host), laid out in this ONE place: what a pass fetches and what it uploads.
+// At sweep width Gw (K = Gw m, nc = K + m): Gam nc x nc, Gh K x nb, Cf K x (K + m + nb); with a selection (gen) H
+// cq x (2 cq + m + 2 nb) and R cq x cq of its widest group (cq = min(Gw, 127 / m) m); last the flag words ([0] the
+// factorisation's, [1] the selection QR's).  The sequential form is the shape Gw = 1: its two m x m Gram matrices lie
+// in Gam, its selection has cq = m.
+struct RadiHostBuf {
+  size_t count;                     // doubles in all
+  double *Gam, *Gh, *Cf, *H, *R;
+  int* flags;
+  RadiHostBuf(ricadi_ctx* c, int Gw, int m, int nb, bool gen) {
+    const size_t K = (size_t)Gw * m, nc = K + m, cq = gen ? (size_t)std::min(Gw, 127 / m) * m : 0;
+    const size_t sizes[5] = {nc * nc, K * nb, K * (K + m + nb), cq * (2 * cq + m + 2 * nb), cq * cq};
+    count = 1;
+    for (size_t s : sizes) count += s;
+    Gam = res_host(c, count);
+    Gh = Gam + sizes[0];
+    Cf = Gh + sizes[1];
+    H = Cf + sizes[2];
+    R = H + sizes[3];
+    flags = reinterpret_cast<int*>(R + sizes[4]);
+    flags[0] = flags[1] = 0;
   }
-  c->radi_sweep_info[1] = sweeps;
-  if (c->sw.timing) {
-    fprintf(stderr, "[ricadi timing] RADI %d steps in %d sweeps of width %d: per-shift setup %.1f ms, solve %.1f, reductions + fetch %.1f, host %.1f, combine %.1f",
-            stt.steps, sweeps, Gw, 1e3 * tph[0], 1e3 * tph[1], 1e3 * tph[2], 1e3 * tph[3], 1e3 * tph[4]);
-    if (gen) fprintf(stderr, ", QR + reduction %.1f, host selection %.1f", 1e3 * tph[5], 1e3 * tph[6]);
-    fprintf(stderr, "\n");
-  }
-}
+};
+
+// The solve's hint that U is columns [lr_ucol, lr_ucol + q) of its right-hand side holds for ONE solve: no exit
+// between setting it and that solve -- also not an exception -- leaves it behind
+struct UcolHintReset {
+  ricadi_ctx* c;
+  ~UcolHintReset() { c->lr_ucol = -1; }
+};
 
 // RADI on DEVICE operands (row-major, their own width as leading dimension): dB nv x nb, dW nv x mw, dOld nv x nb or
 // NULL.  Step j with the shift p of the cycle:
@@ -372,217 +169,442 @@ static void radi_run_sweeps(ricadi_ctx* c, RadiStats& stt, const double* shifts,
 // The factor is left in the context (c->Z, c->zc); the gain cal E X B = U + old goes to dK_out (nv x nb, may be NULL).
 // Recycling of solved right-hand sides is off inside (the panel width changes after the first step; the ring's
 // assumptions have not been checked for that).
-// Shifts: RICADI_RADI_SHIFTS_CYCLE cycles through `shifts`.  RICADI_RADI_SHIFTS_HAMILTONIAN (mw <= 32; with
-// ..._DOMINANT any mw, the host's ricadi::radi_next_shift_dominant in place of radi_next_shift) starts with
-// shifts[0] and generates every later shift from the iteration: right after the residual Gram launch the QR of the new
-// block of Z and the reduction kernel are issued -- speculatively, once too often at the end --, H and R are fetched
-// with the Gram matrix and the flag words in the step's ONE synchronisation, and the host selects the shift after the
-// stop test (ricadi::radi_next_shift, ricadi_host.cpp); `shifts` is the fallback cycle, with a counter of its own.
-static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const double* dB, int nb, const double* dW,
-                              int mw, const double* dOld, int max_steps, double res_reltol, int compress_cols,
-                              bool project_w, bool verbose, double* dK_out) {
+//
+// One call is prepare(), run_steps() or run_sweeps(), finish() (ric_radi_run below).  The two loops are lists of the
+// phases; a decision both forms make is ONE member function, and the members are what the phases share.  The guards
+// are members, so every exit runs them.
+struct RadiRun {
+  ricadi_ctx* const c;
+  const double *const shifts, *const dB, *const dOld;
+  const int ns, nb, m, mp, nv, max_steps;
+  const double res_reltol;
+  const int compress_cols;
+  const bool verbose;
+  const hipStream_t st;
+  const bool dominant, ham, gen;    // (dominant: mw <= 127)  gen: the sweep form generates its shifts
+  const int Gw;                     // the sweep width in force; 1: the sequential form
   RadiStats stt;
-  hipStream_t st = c->st;
-  const int nv = c->nv, m = mw, mp = mw + nb, mm = mw * mw;
-  LowRankReset lowrank_reset{c};
-  Restore<int> keep_rec(c->rec_depth);
-  c->rec_depth = 0;
-  c->q = 0;
-  ++c->lr_epoch;
-  c->adi_res_hist.clear();
-  c->adi_stop_rule = RICADI_STOP_MAX_STEPS;
-  c->adi_ran = true;
-  if (compress_cols <= 0) compress_cols = 512;       // as the Newton driver
+  LowRankReset lowrank_reset;
+  Restore<int> keep_rec;
+  TArr<double> dWm, dRU, dPart;     // W projected in place: private copy; the panel [R | U]; radi_vtb's partials
+  RadiShiftWork sw;
+  OwnedShifts owned;
+  RadiHostBuf h;
+  int* const dflag;
+  int* const qrflag;                // (block_qr_dev's word: the fallback QR reuses it)
+  bool uzero;                       // U is identically zero
+  bool listed = true;               // generated shifts: the pass in hand takes an entry of the caller's list
+  int nfb = 1, zc_last = 0;         // the fallback list's own counter; the factor's columns at the last recompression
+  long it0 = 0, esc0 = 0;
+  // RICADI_TIMING.  Steps: setup, solve + dense step, QR + reduction, selection.  Sweeps: setup, solve, reductions +
+  // fetch, host, combine, QR + reduction, selection
+  double tph[7] = {0, 0, 0, 0, 0, 0, 0};
+  Tick tk;
+  // the sweep form: its scratch, the shifts of the sweep in hand (ps; gen: of the next one as soon as they are chosen),
+  // what its solves returned, and what one phase leaves for the next
+  TArr<double> dR0, dVc, dP, dGh, dGam, dCf;
+  std::vector<double> ps, be, resv, psn, crit;
+  std::vector<ShiftData*> sds;
+  std::vector<GmresResult> res;
+  int sweeps = 0, G = 0, k = 0, ldv = 0, its = 0;
+
+  RadiRun(ricadi_ctx* ctx, const double* shifts_, int ns_, const double* dB_, int nb_, int mw, const double* dOld_,
+          int max_steps_, double res_reltol_, int compress_cols_, bool verbose_)
+      : c(ctx), shifts(shifts_), dB(dB_), dOld(dOld_), ns(ns_), nb(nb_), m(mw), mp(mw + nb_), nv(ctx->nv),
+        max_steps(max_steps_), res_reltol(res_reltol_), compress_cols(compress_cols_ <= 0 ? 512 : compress_cols_),
+        verbose(verbose_), st(ctx->st), dominant(ctx->radi_shift_mode == RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT),
+        ham(dominant || ctx->radi_shift_mode == RICADI_RADI_SHIFTS_HAMILTONIAN),
+        gen(ctx->radi_sweep_shifts != 0 && dominant), Gw(width_in_force()), lowrank_reset{ctx},
+        keep_rec(ctx->rec_depth), dWm(ctx->pool), dRU(ctx->pool), dPart(ctx->pool), sw(ctx), owned(ctx),
+        h(ctx, Gw, mw, nb_, Gw > 1 ? gen : ham), dflag(ctx->flag.p + 3), qrflag(ctx->flag.p + 1),
+        uzero(dOld_ == nullptr), dR0(ctx->pool), dVc(ctx->pool), dP(ctx->pool), dGh(ctx->pool), dGam(ctx->pool),
+        dCf(ctx->pool) {}
+
   // the sweep form: CYCLE mode at the width the list allows; generated shifts (ricadi_set_radi_sweep_shifts, the
   // entries admit it with the DOMINANT mode only) at the cap -- no halving, the selection admits
-  // shifts sweep by sweep; at 1 the sequential form below, mode 2 as it is without the setting
-  const bool gensweep = c->radi_sweep_shifts != 0 && c->radi_shift_mode == RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT;
-  const int Gw = c->radi_sweep_width <= 1 ? 1
-                 : gensweep ? std::max(1, std::min(std::min(c->radi_sweep_width, max_steps),
-                                                    std::min(RICADI_RADI_SWEEP_MAX_K / mw,
-                                                             RICADI_MAX_GROUPS / ricadi::radi_sweep_groups(mw, nb))))
-                 : c->radi_shift_mode == RICADI_RADI_SHIFTS_CYCLE
-                     ? ricadi::radi_sweep_width(shifts, ns, mw, nb, c->radi_sweep_width, max_steps)
-                     : 1;
-  c->radi_sweep_info[0] = Gw;
-  c->radi_sweep_info[1] = c->radi_sweep_info[2] = 0;
-  c->radi_sweep_widths.clear();
-  ensure_work(c, mp, Gw, nb);
-  TArr<double> dWm(c->pool, (size_t)nv * m), dRU(c->pool, (size_t)nv * mp), dG(c->pool, (size_t)m * nb),
-      dC(c->pool, (size_t)m * (2 * m + nb)), dPart(c->pool, radi_vtb_partial_len(nv, m, nb));
-  // W is projected in place: private copy
-  HIPCHK(hipMemcpyAsync(dWm.p, dW, sizeof(double) * nv * m, hipMemcpyDeviceToDevice, st));
-  const bool dominant = c->radi_shift_mode == RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT;      // (mw <= 127)
-  const bool ham = dominant || c->radi_shift_mode == RICADI_RADI_SHIFTS_HAMILTONIAN;
-  const int hw = 3 * m + 2 * nb;                      // columns of H
-  c->radi_shift_hist.clear();
-  c->radi_fallbacks = 0;
-  c->radi_kept_hist.clear();
-  c->radi_qr_repeats = 0;
-  c->radi_recompressions = 0;
-  c->radi_ran = true;
-  // per-shift data of the whole cycle (and of the projection) up front, as lyap_adi_dev; with generated shifts the
-  // first shift only
-  setup_and_project(c, shifts, ham ? 1 : std::min(ns, max_steps), project_w, dWm.p, m);
-  // the panel [R | U]: R = P^T W, U = -old
-  launch_copy_cols(st, nv, m, dWm.p, m, 0, dRU.p, mp, 0, 1.0);
-  if (dOld) launch_copy_cols(st, nv, nb, dOld, nb, 0, dRU.p, mp, m, -1.0);
-  else HIPCHK(hipMemset2DAsync(dRU.p + m, sizeof(double) * mp, 0, sizeof(double) * nb, nv, st));
-  bool uzero = dOld == nullptr;
-  c->U.ensure((size_t)nv * nb);
-  c->V.ensure((size_t)nv * nb);
-  HIPCHK(hipMemcpyAsync(c->V.p, dB, sizeof(double) * nv * nb, hipMemcpyDeviceToDevice, st));
-  factor_reserve(c, max_steps * m);
-  const long it0 = c->total_iters, esc0 = c->escalations;
-  int zc_last = 0;
-  // ||R_j^T R_j||: the fixed-order Gram kernel on the R columns of the panel; ||R_0^T R_0|| is launched here and
-  // fetched with the first step's
-  c->res_part.ensure(gram_fixed_partial_len(nv, m));
-  c->res_gram.ensure((size_t)2 * mm);
-  const size_t cqw = (size_t)std::min(Gw, 127 / m) * m;       // columns of a generated sweep's selection group
-  const size_t hsweep = Gw > 1 ? (size_t)(Gw + 1) * m * (Gw + 1) * m + (size_t)Gw * m * nb + (size_t)Gw * m * (Gw * m + mp) +
-                                     (gensweep ? cqw * (2 * cqw + m + 2 * nb) + cqw * cqw + 1 : 0)
-                               : 0;
-  double* hg = res_host(c, std::max((size_t)2 * mm + 1 + (ham ? (size_t)m * hw + mm : 0), hsweep));
-  int* hflag = reinterpret_cast<int*>(hg + 2 * mm);          // [0] the factorisation's flag, [1] the QR's
-  double *hH = hg + 2 * mm + 1, *hR = hH + (size_t)m * hw;
-  int* dflag = c->flag.p + 3;
-  int* qrflag = c->flag.p + 1;                               // (block_qr_dev's word: the fallback QR reuses it)
-  hflag[1] = 0;
-  RadiShiftWork sw(c);
-  if (ham && Gw == 1) sw.alloc(c, m, m, nb);
-  OwnedShift owned(c);
-  double p_next = shifts[0], margin = 0.0;
-  bool fell_back = false;
-  int nfb = 1;                                               // the fallback cycle's own counter
-  double tph[4] = {0, 0, 0, 0};                              // RICADI_TIMING: setup, solve + dense step, QR + reduction, selection
-  Tick tk;
-  auto lap = [&](int i) {
+  // shifts sweep by sweep; at 1 the sequential form, mode 2 as it is without the setting
+  int width_in_force() const {
+    const int want = c->radi_sweep_width;
+    if (want <= 1) return 1;
+    if (gen) return std::max(1, std::min(std::min(want, max_steps), ricadi::radi_sweep_cap(m, nb)));
+    if (c->radi_shift_mode != RICADI_RADI_SHIFTS_CYCLE) return 1;
+    return ricadi::radi_sweep_width(shifts, ns, m, nb, want, max_steps);
+  }
+
+  void lap(int i) {
     if (c->sw.timing) {
       (void)hipStreamSynchronize(st);
       tph[i] += tk.lap();
     }
-  };
-  if (Gw > 1) {
-    radi_run_sweeps(c, stt, shifts, ns, Gw, gensweep, dB, nb, m, dRU.p, uzero, max_steps, res_reltol, compress_cols,
-                    verbose, hg);
-    max_steps = 0;                                           // (the loop below is the sequential form)
-  } else {
-    launch_gram_fixed(st, nv, m, dRU.p, mp, c->res_part.p, c->res_gram.p);
-    c->res_launches += 2;
   }
-  for (int step = 1; step <= max_steps; ++step) {
-    const double p = ham ? p_next : shifts[(step - 1) % ns];
-    c->radi_shift_hist.push_back(p);
-    if (c->sw.timing) tk.lap();
-    if (ham && step > 1) {
-      if (fell_back) owned.take_back();
-      else owned.lend(p);
-    }
-    ShiftData* sd = get_shift(c, p, 1.0);
-    lap(0);
-    GmresResult r;
-    int ldv = m;
+
+  // the context's "last call" state cleared, the workspaces sized, the first shifts set up, W projected, the panel
+  // [R | U] = [P^T W | -old] and V = B in place, the factor empty
+  void prepare(const double* dW, bool project_w) {
+    c->rec_depth = 0;
+    c->q = 0;
+    ++c->lr_epoch;
+    c->adi_res_hist.clear();
+    c->adi_stop_rule = RICADI_STOP_MAX_STEPS;
+    c->adi_ran = true;
+    c->radi_sweep_info[0] = Gw;
+    c->radi_sweep_info[1] = c->radi_sweep_info[2] = 0;
+    c->radi_sweep_widths.clear();
+    ensure_work(c, mp, Gw, nb);
+    dWm.alloc((size_t)nv * m);
+    dRU.alloc((size_t)nv * mp);
+    dPart.alloc(radi_vtb_partial_len(nv, m, nb));
+    HIPCHK(hipMemcpyAsync(dWm.p, dW, sizeof(double) * nv * m, hipMemcpyDeviceToDevice, st));
+    c->radi_shift_hist.clear();
+    c->radi_fallbacks = 0;
+    c->radi_kept_hist.clear();
+    c->radi_qr_repeats = 0;
+    c->radi_recompressions = 0;
+    c->radi_ran = true;
+    // per-shift data of the whole cycle (and of the projection) up front, as lyap_adi_dev; with generated shifts the
+    // first shift only
+    setup_and_project(c, shifts, ham ? 1 : std::min(ns, max_steps), project_w, dWm.p, m);
+    launch_copy_cols(st, nv, m, dWm.p, m, 0, dRU.p, mp, 0, 1.0);
+    if (dOld) launch_copy_cols(st, nv, nb, dOld, nb, 0, dRU.p, mp, m, -1.0);
+    else HIPCHK(hipMemset2DAsync(dRU.p + m, sizeof(double) * mp, 0, sizeof(double) * nb, nv, st));
+    c->U.ensure((size_t)nv * nb);
+    c->V.ensure((size_t)nv * nb);
+    HIPCHK(hipMemcpyAsync(c->V.p, dB, sizeof(double) * nv * nb, hipMemcpyDeviceToDevice, st));
+    factor_reserve(c, max_steps * m);
+    it0 = c->total_iters;
+    esc0 = c->escalations;
+  }
+
+  // Per-shift entries for the G shifts at p: generated shifts borrow theirs; before an entry of the caller's list
+  // what was lent goes back, and that entry enters the cache as any listed shift does.
+  void entries_for(const double* p, int g, bool from_list) {
+    if (from_list) owned.take_back();
+    else owned.lend(p, g);
+  }
+
+  // The context and the right-hand side made ready for a solve against the panel, and the solve: solve(width, lowrank)
+  // reads c->bvec.  While U is identically zero the m columns of R, plain; else [R | U] with c->U = U, c->q = nb and
+  // lr_ucol = m -- the `dup` path: S^-1 U out of the same solve.  Returns the leading dimension of the solutions.
+  template <class F>
+  int solve_panel(F&& solve) {
     if (uzero) {
       c->q = 0;
       launch_copy_cols(st, nv, m, dRU.p, mp, 0, c->bvec.p, m, 0, 1.0);
       if (c->np > 0) HIPCHK(hipMemsetAsync(c->bvec.p + (size_t)nv * m, 0, sizeof(double) * (size_t)c->np * m, st));
-      r = gmres_solve(c, sd, c->bvec.p, c->xs.p, m, false, nullptr);
-    } else {
-      c->q = nb;
-      ++c->lr_epoch;
-      launch_copy_cols(st, nv, nb, dRU.p, mp, m, c->U.p, nb, 0, 1.0);
-      c->lr_ucol = m;
-      load_rhs(c, dRU.p, mp, c->bvec.p);
-      r = gmres_solve(c, sd, c->bvec.p, c->xs.p, mp, true, nullptr);
-      c->lr_ucol = -1;
-      ldv = mp;
+      solve(m, false);
+      return m;
     }
-    if (!r.converged) {
-      stt.nonconverged++;
-      stt.worst_relres = std::max(stt.worst_relres, r.max_relres);
-      if (verbose)
-        fprintf(stderr, "[ricadi] RADI step %d shift %g: GMRES stopped at relres %.2e after %d its\n", step, p,
-                r.max_relres, r.iters);
-    }
+    c->q = nb;
+    ++c->lr_epoch;
+    launch_copy_cols(st, nv, nb, dRU.p, mp, m, c->U.p, nb, 0, 1.0);
+    UcolHintReset hint_reset{c};
+    c->lr_ucol = m;
+    load_rhs(c, dRU.p, mp, c->bvec.p);
+    solve(mp, true);
+    return mp;
+  }
+
+  // a solve's outcome into the statistics; unit and idx name the pass in the verbose line ("step" 3, "sweep" 2)
+  void record(const GmresResult& r, const char* unit, int idx, double p) {
     stt.shift_solves++;
-    radi_dense_step(c, p, c->xs.p, ldv, m, dB, nb, dRU.p, c->Z.p, c->zld, c->zc, dG.p, dC.p, dPart.p, dflag);
-    uzero = false;
-    launch_gram_fixed(st, nv, m, dRU.p, mp, c->res_part.p, c->res_gram.p + mm);
-    c->res_launches += 2;
-    lap(1);
-    const double* dZblk = c->Z.p + c->zc;
-    if (ham) {
-      radi_shift_issue(c, sw, dZblk, c->zld, m, m, dRU.p, dB, nb, qrflag);
-      HIPCHK(hipMemcpyAsync(hH, sw.H.p, sizeof(double) * m * hw, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(hR, sw.Rq.p, sizeof(double) * mm, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(hflag + 1, qrflag, sizeof(int), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipMemcpyAsync(hg, c->res_gram.p, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hflag, dflag, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (r.converged) return;
+    stt.nonconverged++;
+    stt.worst_relres = std::max(stt.worst_relres, r.max_relres);
+    if (verbose)
+      fprintf(stderr, "[ricadi] RADI %s %d shift %g: GMRES stopped at relres %.2e after %d its\n", unit, idx, p,
+              r.max_relres, r.iters);
+  }
+
+  // H and R of a selection over cq columns on their way to the host
+  void fetch_selection(int cq) {
+    HIPCHK(hipMemcpyAsync(h.H, sw.H.p, sizeof(double) * cq * (2 * cq + m + 2 * nb), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h.R, sw.Rq.p, sizeof(double) * cq * cq, hipMemcpyDeviceToHost, st));
+  }
+  // the selection's CholQR2 of the cq columns of Z at dZg and its reduction issued; H, R and the QR's flag follow.  The
+  // caller synchronises.
+  void issue_selection(const double* dZg, int cq) {
+    radi_shift_issue(c, sw, dZg, c->zld, cq, m, dRU.p, dB, nb, qrflag);
+    fetch_selection(cq);
+    HIPCHK(hipMemcpyAsync(h.flags + 1, qrflag, sizeof(int), hipMemcpyDeviceToHost, st));
+  }
+  // the Gram matrix of those columns was not positive definite to working precision: Householder TSQR, and H once more
+  void repeat_selection_if_flagged(const double* dZg, int cq) {
+    if (h.flags[1] == 0) return;
+    block_qr_dev(c, dZg, c->zld, nv, cq, sw.Q.p, sw.Rq.p);
+    launch_radi_reduce(st, nv, cq, m, nb, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, sw.Q.p, dRU.p, dB, sw.part.p,
+                       sw.H.p);
+    fetch_selection(cq);
     HIPCHK(hipStreamSynchronize(st));
-    if (c->sw.timing) tph[2] += tk.lap();
-    if (*hflag != 0) {
-      stt.breakdown = true;
-      break;
+    ++c->radi_qr_repeats;
+  }
+
+  // Generated or fallback, after a selection that returned rc with a basis of `kept`: refused by the host or by the
+  // probe's list (ricadi_probe_radi_refuse, after this many steps), the next shift is the next entry of `shifts` -- a
+  // counter of its own from shifts[1], cycling -- into *p.  Returns whether it fell back.
+  bool fall_back(int rc, int kept, double* p) {
+    const bool fb = rc != 0 || std::find(c->radi_refuse.begin(), c->radi_refuse.end(), stt.steps) != c->radi_refuse.end();
+    c->radi_kept_hist.push_back(kept);
+    if (fb) {
+      *p = shifts[nfb++ % ns];
+      ++c->radi_fallbacks;
     }
-    if (step == 1) stt.rhs = gram_block_fro(hg, m, m, 0);
-    const double wf = gram_block_fro(hg + mm, m, m, 0);
-    stt.res = stt.rhs > 0.0 ? wf / stt.rhs : 0.0;
-    c->zc += m;
-    stt.steps = step;
-    c->adi_res_hist.push_back(stt.res);
-    if (verbose) {
-      if (ham)
-        fprintf(stderr, "[ricadi] RADI step %3d: shift %10.3e (%s, margin %.3f) rel residual %9.3e gmres its %d\n", step,
-                p, step == 1 ? "first" : fell_back ? "fallback" : "generated", step == 1 || fell_back ? 0.0 : margin,
-                stt.res, r.iters);
-      else
-        fprintf(stderr, "[ricadi] RADI step %3d: shift %10.3e rel residual %9.3e gmres its %d\n", step, p, stt.res,
-                r.iters);
-    }
-    if (stt.res <= res_reltol) {
-      c->adi_stop_rule = RICADI_STOP_RES;
-      break;
-    }
-    if (ham && step < max_steps) {
-      if (hflag[1] != 0) {
-        // the block's Gram matrix is not positive definite to working precision: Householder TSQR, and H once more
-        block_qr_dev(c, dZblk, c->zld, nv, m, sw.Q.p, sw.Rq.p);
-        launch_radi_reduce(st, nv, m, m, nb, c->s_rp.p, c->s_ci.p, c->srcA.p, c->srcE.p, sw.Q.p, dRU.p, dB, sw.part.p,
-                           sw.H.p);
-        HIPCHK(hipMemcpyAsync(hH, sw.H.p, sizeof(double) * m * hw, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(hR, sw.Rq.p, sizeof(double) * mm, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        ++c->radi_qr_repeats;
+    return fb;
+  }
+
+  bool stopped() {
+    if (stt.res > res_reltol) return false;
+    c->adi_stop_rule = RICADI_STOP_RES;
+    return true;
+  }
+
+  void recompress_if_due() {
+    if (stt.steps >= max_steps || c->zc - zc_last < compress_cols) return;
+    factor_recompress(c);
+    ++c->radi_recompressions;
+    zc_last = c->zc;
+  }
+
+  // The SEQUENTIAL form.  Shifts: RICADI_RADI_SHIFTS_CYCLE cycles through `shifts`.  RICADI_RADI_SHIFTS_HAMILTONIAN
+  // (mw <= 32; with ..._DOMINANT any mw, the host's ricadi::radi_next_shift_dominant in place of radi_next_shift)
+  // starts with shifts[0] and generates every later shift from the iteration: right after the residual Gram launch
+  // the QR of the new block of Z and the reduction kernel are issued -- speculatively, once too often at the end --, H
+  // and R are fetched with the Gram matrix and the flag words in the step's ONE synchronisation, and the host selects
+  // the shift after the stop test (ricadi::radi_next_shift, ricadi_host.cpp); `shifts` is the fallback cycle.
+  void run_steps() {
+    const int mm = m * m;
+    TArr<double> dG(c->pool, (size_t)m * nb), dC(c->pool, (size_t)m * (2 * m + nb));
+    // ||R_j^T R_j||: the fixed-order Gram kernel on the R columns of the panel; ||R_0^T R_0|| is launched here and
+    // fetched with the first step's
+    c->res_part.ensure(gram_fixed_partial_len(nv, m));
+    c->res_gram.ensure((size_t)2 * mm);
+    if (ham) sw.alloc(c, m, m, nb);
+    launch_gram_fixed(st, nv, m, dRU.p, mp, c->res_part.p, c->res_gram.p);
+    c->res_launches += 2;
+    double p = shifts[0], margin = 0.0;
+    for (int step = 1; step <= max_steps; ++step) {
+      if (!ham) p = shifts[(step - 1) % ns];
+      c->radi_shift_hist.push_back(p);
+      if (c->sw.timing) tk.lap();
+      if (ham) entries_for(&p, 1, listed);
+      ShiftData* sd = get_shift(c, p, 1.0);
+      lap(0);
+      GmresResult r;
+      const int ld = solve_panel([&](int w, bool lr) { r = gmres_solve(c, sd, c->bvec.p, c->xs.p, w, lr, nullptr); });
+      record(r, "step", step, p);
+      radi_dense_step(c, p, c->xs.p, ld, m, dB, nb, dRU.p, c->Z.p, c->zld, c->zc, dG.p, dC.p, dPart.p, dflag);
+      uzero = false;
+      launch_gram_fixed(st, nv, m, dRU.p, mp, c->res_part.p, c->res_gram.p + mm);
+      c->res_launches += 2;
+      lap(1);
+      const double* dZblk = c->Z.p + c->zc;
+      if (ham) issue_selection(dZblk, m);
+      HIPCHK(hipMemcpyAsync(h.Gam, c->res_gram.p, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(h.flags, dflag, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (c->sw.timing) tph[2] += tk.lap();
+      if (h.flags[0] != 0) {
+        stt.breakdown = true;
+        break;
       }
-      int kept = 0;
-      fell_back = (dominant ? ricadi::radi_next_shift_dominant(m, nb, hH, hR, &p_next, &margin, &kept)
-                            : ricadi::radi_next_shift(m, nb, hH, hR, &p_next, &margin, &kept)) != 0 ||
-                  std::find(c->radi_refuse.begin(), c->radi_refuse.end(), step) != c->radi_refuse.end();
-      c->radi_kept_hist.push_back(kept);
-      if (fell_back) {
-        p_next = shifts[nfb++ % ns];
-        ++c->radi_fallbacks;
+      if (step == 1) stt.rhs = gram_block_fro(h.Gam, m, m, 0);
+      const double wf = gram_block_fro(h.Gam + mm, m, m, 0);
+      stt.res = stt.rhs > 0.0 ? wf / stt.rhs : 0.0;
+      c->zc += m;
+      stt.steps = step;
+      c->adi_res_hist.push_back(stt.res);
+      if (verbose) {
+        if (ham)
+          fprintf(stderr, "[ricadi] RADI step %3d: shift %10.3e (%s, margin %.3f) rel residual %9.3e gmres its %d\n", step,
+                  p, step == 1 ? "first" : listed ? "fallback" : "generated", listed ? 0.0 : margin, stt.res, r.iters);
+        else
+          fprintf(stderr, "[ricadi] RADI step %3d: shift %10.3e rel residual %9.3e gmres its %d\n", step, p, stt.res,
+                  r.iters);
       }
-      if (c->sw.timing) tph[3] += tk.lap();
+      if (stopped()) break;
+      if (ham && step < max_steps) {
+        repeat_selection_if_flagged(dZblk, m);
+        int kept = 0;
+        listed = fall_back(dominant ? ricadi::radi_next_shift_dominant(m, nb, h.H, h.R, &p, &margin, &kept)
+                                    : ricadi::radi_next_shift(m, nb, h.H, h.R, &p, &margin, &kept),
+                           kept, &p);
+        if (c->sw.timing) tph[3] += tk.lap();
+      }
+      recompress_if_due();
     }
-    if (step < max_steps && c->zc - zc_last >= compress_cols) {
-      factor_recompress(c);
-      ++c->radi_recompressions;
-      zc_last = c->zc;
+    if (c->sw.timing)
+      fprintf(stderr, "[ricadi timing] RADI %d steps (%s shifts): per-shift setup %.1f ms, solve + dense step %.1f, QR + reduction %.1f, host selection %.1f\n",
+              stt.steps, ham ? "generated" : "cycled", 1e3 * tph[0], 1e3 * tph[1], 1e3 * tph[2], 1e3 * tph[3]);
+  }
+
+  // The SWEEP form (effective width Gw > 1; the formulas at ricadi_set_radi_sweep_width): the loop of
+  // run_steps with G <= Gw steps per pass.
+  //   1. ONE solve_batch with the G shifts against the panel [R_0 | U_0] (gsb = 0; solve_panel);
+  //   2. P = [R_0 | cal E Vh] (launch_sweep_resid_panel on the compacted solution panels), Gamma = P^T P
+  //      (launch_gram_fixed), Gh_g = Vh_g^T B (launch_radi_vtb per shift): fixed summation orders;
+  //   3. the sweep's host synchronisation: Gamma and Gh (sweep_reduce);
+  //   4. ricadi::radi_sweep: the steps kept, the residual after each, the coefficient matrix Cf (sweep_host);
+  //   5. Cf uploaded;  6. launch_radi_sweep_combine: the kept blocks of Z, [R | U] advanced to R_k, U_k (sweep_combine).
+  // CYCLE mode (gen false): sweep s takes the next G = min(Gw, steps left) entries of the cycled list.
+  // GENERATED shifts (gen: ricadi_set_radi_sweep_shifts with RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT):
+  // the first sweep is ONE step with shifts[0]; after the stop test of a sweep that does not end the iteration
+  // select_sweep chooses the next sweep's shifts, or ONE step with the list's next entry.
+  void run_sweeps() {
+    const int Kw = Gw * m, ncw = Kw + m;
+    dR0.alloc((size_t)nv * m);
+    dVc.alloc((size_t)nv * Kw);
+    dP.alloc((size_t)nv * ncw);
+    dGh.alloc((size_t)Kw * nb);
+    dGam.alloc((size_t)ncw * ncw);
+    dCf.alloc((size_t)Kw * (Kw + mp));
+    c->res_part.ensure(gram_fixed_partial_len(nv, ncw));
+    c->sweep_u.ensure((size_t)c->n * mp * Gw);
+    // generated shifts: the scratch of the widest group a selection may meet
+    if (gen) sw.alloc(c, std::min(Gw, 127 / m) * m, m, nb);
+    ps.resize(Gw);
+    be.assign(Gw, 1.0);
+    resv.resize(Gw);
+    psn.resize(Gw);
+    crit.resize(Gw);
+    sds.resize(Gw);
+    res.resize(Gw);
+    int Gnext = 1;                  // gen: the solves of the next sweep
+    ps[0] = shifts[0];
+    while (stt.steps < max_steps) {
+      const int left = max_steps - stt.steps;
+      G = gen ? Gnext : std::min(Gw, left);
+      if (!gen)
+        for (int g = 0; g < G; ++g) ps[g] = shifts[(stt.steps + g) % ns];
+      if (c->sw.timing) tk.lap();
+      if (gen) entries_for(ps.data(), G, listed);
+      get_shifts(c, ps.data(), be.data(), G, sds.data());
+      lap(0);
+      ldv = solve_panel([&](int w, bool lr) {
+        solve_batch(c, sds.data(), G, c->bvec.p, 0, c->sweep_u.p, w, lr, nullptr, res.data());
+      });
+      its = 0;
+      for (int g = 0; g < G; ++g) {
+        its = std::max(its, res[g].iters);
+        record(res[g], "sweep", sweeps + 1, ps[g]);
+      }
+      c->radi_sweep_widths.push_back(G);
+      lap(1);
+      sweep_reduce();
+      if (c->sw.timing) tph[2] += tk.lap();
+      if (!sweep_host(left)) break;
+      sweep_combine();
+      lap(4);
+      if (stopped()) break;
+      if (gen && stt.steps < max_steps) Gnext = select_sweep();
+      recompress_if_due();
+    }
+    c->radi_sweep_info[1] = sweeps;
+    if (c->sw.timing) {
+      fprintf(stderr, "[ricadi timing] RADI %d steps in %d sweeps of width %d: per-shift setup %.1f ms, solve %.1f, reductions + fetch %.1f, host %.1f, combine %.1f",
+              stt.steps, sweeps, Gw, 1e3 * tph[0], 1e3 * tph[1], 1e3 * tph[2], 1e3 * tph[3], 1e3 * tph[4]);
+      if (gen) fprintf(stderr, ", QR + reduction %.1f, host selection %.1f", 1e3 * tph[5], 1e3 * tph[6]);
+      fprintf(stderr, "\n");
     }
   }
-  stt.gmres_iters = c->total_iters - it0;
-  stt.escalations = c->escalations - esc0;
-  c->radi_sweep_info[2] = (int)stt.shift_solves;
-  if (c->sw.timing && Gw == 1)
-    fprintf(stderr, "[ricadi timing] RADI %d steps (%s shifts): per-shift setup %.1f ms, solve + dense step %.1f, QR + reduction %.1f, host selection %.1f\n",
-            stt.steps, ham ? "generated" : "cycled", 1e3 * tph[0], 1e3 * tph[1], 1e3 * tph[2], 1e3 * tph[3]);
-  if (dK_out && !stt.breakdown) {
-    launch_copy_cols(st, nv, nb, dRU.p, mp, m, dK_out, nb, 0, 1.0);
-    if (dOld) launch_axpby(st, (size_t)nv * nb, 1.0, dOld, 1.0, dK_out);
+
+  // 2., 3.: the reductions of the sweep's G solutions (c->sweep_u, leading dimension ldv) and their fetch
+  void sweep_reduce() {
+    const int K = G * m, nc = K + m;
+    const double* x = c->sweep_u.p;
+    const size_t vstride = (size_t)c->n * ldv;
+    launch_copy_cols(st, nv, m, dRU.p, mp, 0, dR0.p, m, 0, 1.0);
+    const double* vb = x;
+    size_t vs = vstride;
+    if (ldv != m) {
+      for (int g = 0; g < G; ++g) launch_copy_cols(st, nv, m, x + g * vstride, ldv, 0, dVc.p + (size_t)g * nv * m, m, 0, 1.0);
+      vb = dVc.p;
+      vs = (size_t)nv * m;
+    }
+    launch_sweep_resid_panel(st, nv, m, G, c->E.rp.p, c->E.ci.p, c->E.v.p, dR0.p, vb, vs, dP.p);
+    c->res_part.ensure(gram_fixed_partial_len(nv, nc));       // (a narrower sweep slices the rows differently)
+    launch_gram_fixed(st, nv, nc, dP.p, nc, c->res_part.p, dGam.p);
+    for (int g = 0; g < G; ++g)
+      launch_radi_vtb(st, nv, m, nb, x + g * vstride, ldv, dB, dPart.p, dGh.p + (size_t)g * m * nb);
+    c->res_launches += 3 + 2 * G;
+    HIPCHK(hipMemcpyAsync(h.Gam, dGam.p, sizeof(double) * nc * nc, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h.Gh, dGh.p, sizeof(double) * K * nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
   }
-  HIPCHK(hipStreamSynchronize(st));
-  return stt;
+
+  // 4.: k, resv and Cf from what was fetched; false: breakdown, the iteration ends
+  bool sweep_host(int left) {
+    if (sweeps == 0) stt.rhs = gram_block_fro(h.Gam, G * m + m, m, 0);
+    k = 0;
+    const int rc = ricadi::radi_sweep(G, m, nb, ps.data(), h.Gh, h.Gam, stt.rhs, res_reltol, left, &k, resv.data(), h.Cf);
+    if (c->sw.timing) tph[3] += tk.lap();
+    if (rc == RICADI_OK) return true;
+    c->radi_shift_hist.push_back(ps[0]);
+    stt.breakdown = true;
+    return false;
+  }
+
+  // 5., 6.: the k kept steps into the factor, the panel and the histories
+  void sweep_combine() {
+    const int K = G * m, km = k * m;
+    HIPCHK(hipMemcpyAsync(dCf.p, h.Cf, sizeof(double) * K * (km + mp), hipMemcpyHostToDevice, st));
+    launch_radi_sweep_combine(st, nv, G, m, nb, k, c->sweep_u.p, (size_t)c->n * ldv, ldv, dP.p + m, K + m, dCf.p, dRU.p,
+                              c->Z.p, c->zld, c->zc);
+    uzero = false;
+    ++sweeps;
+    c->zc += km;
+    for (int j = 0; j < k; ++j) {
+      c->radi_shift_hist.push_back(ps[j]);
+      c->adi_res_hist.push_back(resv[j]);
+      if (verbose)
+        fprintf(stderr, "[ricadi] RADI step %3d: shift %10.3e%s rel residual %9.3e (sweep %d of %d solves, gmres its %d)\n",
+                stt.steps + j + 1, ps[j], !gen ? "" : sweeps == 1 ? " (first)" : listed ? " (fallback)" : " (generated)",
+                resv[j], sweeps, G, its);
+    }
+    stt.steps += k;
+    stt.res = resv[k - 1];
+  }
+
+  // 7. the CholQR2 of the group of Z the sweep kept (its last min(k, 127 / m) blocks, read where they lie in c->Z,
+  //    BEFORE any recompression) and the reduction H = Q^T [cal A Q | cal E Q | R | U | B], H, R and the QR's flag
+  //    fetched: the sweep's SECOND host synchronisation (the Householder repeat where the flag is raised);
+  // 8. ricadi::radi_next_shifts_dominant: up to min(Gw, steps left) shifts for the next sweep into ps, in acceptance
+  //    order.  A refused selection makes the next sweep ONE step with the list's next entry (fall_back).
+  // Returns the solves of the next sweep.
+  int select_sweep() {
+    const int cq = std::min(k, 127 / m) * m;
+    const double* dZg = c->Z.p + (c->zc - cq);
+    issue_selection(dZg, cq);
+    HIPCHK(hipStreamSynchronize(st));
+    repeat_selection_if_flagged(dZg, cq);
+    if (c->sw.timing) tph[5] += tk.lap();
+    int kept = 0, nsel = 0;
+    listed = fall_back(ricadi::radi_next_shifts_dominant(cq, m, nb, h.H, h.R, std::min(Gw, max_steps - stt.steps),
+                                                         psn.data(), crit.data(), &nsel, &kept),
+                       kept, &ps[0]);
+    if (!listed) std::copy(psn.begin(), psn.begin() + nsel, ps.begin());
+    if (c->sw.timing) tph[6] += tk.lap();
+    return listed ? 1 : nsel;
+  }
+
+  // the statistics closed, the gain U + old out
+  RadiStats finish(double* dK_out) {
+    stt.gmres_iters = c->total_iters - it0;
+    stt.escalations = c->escalations - esc0;
+    c->radi_sweep_info[2] = (int)stt.shift_solves;
+    if (dK_out && !stt.breakdown) {
+      launch_copy_cols(st, nv, nb, dRU.p, mp, m, dK_out, nb, 0, 1.0);
+      if (dOld) launch_axpby(st, (size_t)nv * nb, 1.0, dOld, 1.0, dK_out);
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return stt;
+  }
+};
+
+static RadiStats ric_radi_run(ricadi_ctx* c, const double* shifts, int ns, const double* dB, int nb, const double* dW,
+                              int mw, const double* dOld, int max_steps, double res_reltol, int compress_cols,
+                              bool project_w, bool verbose, double* dK_out) {
+  RadiRun run(c, shifts, ns, dB, nb, mw, dOld, max_steps, res_reltol, compress_cols, verbose);
+  run.prepare(dW, project_w);
+  if (run.Gw > 1) run.run_sweeps();
+  else run.run_steps();
+  return run.finish(dK_out);
 }

@@ -9,8 +9,8 @@
    against the model (tests/golden/radi_sweep_shift_model.npz, written by tests/radi_sweep_shift_model.py);
 4. width 1 with the setting on: the bits of ``'hamiltonian-dominant'``;
 5. wide factors (33 columns at width 3, 58 at width 2);  6. the 128-column limit (16 columns at width 8);
-7. forced fallbacks;  8. a run stopped by the residual inside a sweep;  9. the contract;
-10. the two-step DRE sweep.
+7. forced fallbacks, and the borrowed per-shift entries a sequential call shares with a sweep;
+8. a run stopped by the residual inside a sweep;  9. the contract;  10. the two-step DRE sweep.
 
 tests/test_radi_sweep_shifts_cpu.py holds the model and the host entry; it has to pass for these to mean anything.
 """
@@ -170,7 +170,8 @@ def test_reduce_group_exact_on_small_integers_and_the_existing_entries_bits(ctx_
 
 
 # ------------------------------------------------------------------------------------------------ the whole solves
-def run(ctx, f, width, fallback=None, max_steps=200, tol=TOL, sweep_shifts=True, mode="hamiltonian-dominant"):
+def run(ctx, f, width, fallback=None, max_steps=200, tol=TOL, sweep_shifts=True, mode="hamiltonian-dominant",
+        compress_cols=0):
     """One RADI call with generated sweep shifts (mode, setting and width are restored): dict(Z, K, info, ms, fallbacks,
     kept, res, widths, swi)."""
     fb = [sm.initial_shift(f["calA"], f["calE"])] if fallback is None else list(fallback)
@@ -178,7 +179,8 @@ def run(ctx, f, width, fallback=None, max_steps=200, tol=TOL, sweep_shifts=True,
     set_before = ctx.set_radi_sweep_shifts(sweep_shifts)
     width_before = ctx.set_radi_sweep_width(width)
     try:
-        Z, K, info = ctx.ric_radi(fb, f["B"], f["W"], oldB=f["old"], max_steps=max_steps, res_reltol=tol)
+        Z, K, info = ctx.ric_radi(fb, f["B"], f["W"], oldB=f["old"], max_steps=max_steps, res_reltol=tol,
+                                  compress_cols=compress_cols)
     finally:
         ctx.set_radi_sweep_width(width_before)
         ctx.set_radi_sweep_shifts(set_before)
@@ -355,6 +357,30 @@ def test_forced_fallbacks():
         r3 = run(ctx, f, 4, fallback=fb)
         assert r3["fallbacks"] == 0 and np.array_equal(r3["ms"], free["ms"]) and np.array_equal(r3["K"], free["K"])
         assert ctx.cache_entries() == n1
+
+
+def test_sequential_and_sweep_calls_share_their_borrowed_entries():
+    """A sequential call with generated shifts borrows the first of the per-shift entries a generated sweep borrows.
+    N = 8 steady on one context: sequential DOMINANT, sweeps of 4, and both once more -- each repeat gives the bits of
+    its first run, whichever form rebuilt the shared entry in between, and the cache holds what the first call left.
+    (No recompression inside the calls: a recompressed factor's bits are those of the GEMM's atomics.)"""
+    f = ssm.case_form("steady", 8)
+    nocomp = 200 * f["W"].shape[1] + 1
+    with _lib.Context(0) as ctx:
+        ctx.set_operator(f["calA"], f["calE"], f["J"])
+        assert ctx.nv == 450
+        runs, entries = [], []
+        for width in (1, 4, 1, 4):
+            runs.append(run(ctx, f, width, sweep_shifts=width > 1, compress_cols=nocomp))
+            entries.append(ctx.cache_entries())
+        print("steps %s, sweep widths %s, cache entries %s" % ([len(r["ms"]) for r in runs],
+                                                               [r["widths"].tolist() for r in runs], entries))
+        assert len(runs[0]["widths"]) == 0 and runs[1]["widths"].max() > 1 and runs[1]["swi"]["width"] == 4
+        for first, again in ((0, 2), (1, 3)):
+            for k in ("K", "ms", "res"):
+                assert np.array_equal(runs[again][k], runs[first][k]), (first, again, k)
+            assert runs[again]["recompressions"] == runs[first]["recompressions"] == 0
+        assert entries[1:] == entries[:1] * 3
 
 
 # ------------------------------------------------------------------------- 8. the residual rule inside a sweep

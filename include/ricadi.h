@@ -183,7 +183,8 @@ int ricadi_synchronize(ricadi_ctx* ctx);
  *    per-shift cache (child levels included), the child level, the low-rank
  *    term (q = 0), the resident factor, the workspace sizes, the recycled
  *    right-hand sides and their solutions, and everything a reporter says "of
- *    the last call" (ADI residual history and stop rule, RADI shift history,
+ *    the last call" (ADI residual history and stop rule, Newton history and
+ *    stop rule, RADI shift history,
  *    fallbacks, sweep info and widths, the probes' last-call counters, the
  *    kernel forms of ricadi_setup_info): asked right after the call, a
  *    reporter answers as a fresh context's does.
@@ -415,6 +416,26 @@ int ricadi_ric_newtonadi_dev(ricadi_ctx* ctx, const double* shifts, int nshifts,
                              const double* dB, int nb, const double* dW, int mw,
                              const double* dZ0, int c0, const double* dOldB,
                              const ricadi_adi_params* prm, int* c_out, double* stats_out);
+/* Both entries of a1 return RICADI_EINVAL before anything is launched for nwtn_max_steps < 1 and adi_max_steps < 1
+ * (ABI 413; a loop that never ran used to answer with the factor an earlier call had left in the context), as for
+ * bad widths, a NULL panel and a shift >= 0.  After a refused call the resident factor, the histories and every
+ * other reporter answer as before it.
+ *
+ * ricadi_newton_history (ABI 413): one row of six doubles per Newton step of the most recent ricadi_ric_newtonadi(_dev)
+ * call of the context, row k-1 for step k:
+ *   [upd_abs = ||Z_k Z_k^T - Z_{k-1} Z_{k-1}^T||_F, upd_rel = upd_abs / ||Z_k Z_k^T||_F, ADI steps of the step,
+ *    columns of the raw ADI factor before the step's recompression, columns kept, ||Z_k Z_k^T||_F].
+ * *n_out = number of steps; at most `cap` ROWS (6 * cap doubles) are copied to `out` (may be NULL with cap = 0).
+ * Always recorded (six doubles per step); on a sharded context after rank 0's decision has gone round, so every
+ * rank holds rank 0's row.  The last row's first two entries are stats_out[1] and stats_out[2] of the call.
+ * RICADI_ESTATE before any Newton call.
+ * ricadi_newton_stop_rule: the rule that ended that call.  Where both tolerances are met at one step it reports
+ * RICADI_NEWTON_STOP_ABSTOL, the first test of `upd_abs < nwtn_upd_abstol || upd_rel < nwtn_upd_reltol`.        */
+#define RICADI_NEWTON_STOP_MAX_STEPS 0   /* nwtn_max_steps reached                                              */
+#define RICADI_NEWTON_STOP_ABSTOL 1      /* update norm below nwtn_upd_abstol                                   */
+#define RICADI_NEWTON_STOP_RELTOL 2      /* relative update norm below nwtn_upd_reltol                          */
+int ricadi_newton_history(ricadi_ctx* ctx, double* out, int cap, int* n_out);
+int ricadi_newton_stop_rule(ricadi_ctx* ctx, int* rule_out);
 
 /* ---- a1r: low-rank RADI for the projected Riccati equation (Benner, Bujanovic, Kuerschner, Saak, Numer. Math.
  * 2018; pru.proj_alg_ric_radi; no reference counterpart) -------------------------------------------------------
@@ -807,6 +828,27 @@ int ricadi_arnoldi_probe_read_dev(ricadi_ctx* ctx, int what, int slot, double* d
  * Q_out: NV x c or NULL.  The "QR" of the reference's compress_Zsvd comment
  * (/root/reference/optcont_main.py:133-134) and of the Newton update norm.      */
 int ricadi_qr(ricadi_ctx* ctx, const double* Z, int c, double* Q_out, double* R_out);
+
+/* The Newton-Kleinman loop's update norm, called as the loop calls it (ABI 413, for tests):
+ *   *upd_out = ||Z1 Z1^T - Z0 Z0^T||_F,   *x1_out = ||Z1 Z1^T||_F
+ * from R of the block QR of [Z1, Z0] (no panel of which holds columns of both factors) as ||R S R^T||_F,
+ * S = diag(I_k1, -I_k0) -- the Gram matrices of the factors are never formed, so an update 1e-10 below x1 keeps
+ * about four digits.  dZ1 NV x k1 and dZ0 NV x k0 are DEVICE panels, row-major with leading dimension = width and
+ * only read; dZ0 may be NULL with k0 = 0; either output may be NULL.  k1 + k0 may exceed NV (two full-rank iterates
+ * of a small operator): the NV x NV matrix [Z1, Z0] S [Z1, Z0]^T is then the smaller one and is formed as it stands,
+ * to the same accuracy -- block Gram-Schmidt has nothing left to orthogonalise against once the columns have used up
+ * the NV dimensions.
+ * A dimension-only context (ricadi_set_dims) is enough.
+ * Width limit: k1 + k0 <= RICADI_MAX_UPD_COLS.  The block QR itself has no fixed bound -- its kernels walk the
+ * columns in panels of at most 128 and their grids grow with the width in 32- or 64-column tiles, far below the
+ * grid limits; the scratch pool serves any size the device can allocate -- so the bound is the workspace: five
+ * (k1 + k0)^2 arrays of doubles (R, its two transposes and the product on the device, the product again on the
+ * host), 0.67 GB at 4096 columns, beside two NV x (k1 + k0) panels.
+ * RICADI_EINVAL before anything is launched, outputs untouched: k1 < 1, k0 < 0, a NULL panel with a positive width,
+ * k1 + k0 above the limit.  RICADI_ESTATE on a context without dimensions.                                        */
+#define RICADI_MAX_UPD_COLS 4096
+int ricadi_diff_zzt_fnorm_dev(ricadi_ctx* ctx, const double* dZ1, int k1, const double* dZ0, int k0,
+                              double* upd_out, double* x1_out);
 
 /* K7: the pencil of the operator projected onto a dense basis (the Ritz values behind ms='auto'):
  * HA = Q^T (cal A - U V^T) Q,  HE = Q^T cal E Q  (k x k row-major; the low-rank term if one is set).

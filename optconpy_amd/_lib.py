@@ -20,10 +20,12 @@ RICADI_ENOCONV = -3
 RICADI_STOP_MAX_STEPS, RICADI_STOP_NEWZ, RICADI_STOP_RES = 0, 1, 2      # ricadi_adi_stop_rule (include/ricadi.h)
 RICADI_RADI_SHIFTS_CYCLE, RICADI_RADI_SHIFTS_HAMILTONIAN = 0, 1          # ricadi_set_radi_shifts
 RICADI_RADI_SHIFTS_HAMILTONIAN_DOMINANT = 2
+RICADI_NEWTON_STOP_MAX_STEPS, RICADI_NEWTON_STOP_ABSTOL, RICADI_NEWTON_STOP_RELTOL = 0, 1, 2   # ricadi_newton_stop_rule
 MAX_M = 128
+MAX_UPD_COLS = 4096                                                     # ricadi_diff_zzt_fnorm_dev: k1 + k0
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 412
+ABI_VERSION = 413
 
 
 class RicadiOpts(C.Structure):
@@ -59,6 +61,9 @@ SIGNATURES = {
     "ricadi_set_adi_res_history": (C.c_int, [_vp, C.c_int]),
     "ricadi_adi_stop_rule": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "ricadi_adi_res_launches": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "ricadi_newton_history": (C.c_int, [_vp, _dp, C.c_int, C.POINTER(C.c_int)]),
+    "ricadi_newton_stop_rule": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "ricadi_diff_zzt_fnorm_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _dp, _dp]),
     "ricadi_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "ricadi_destroy": (C.c_int, [_vp]),
     "ricadi_set_opts": (C.c_int, [_vp, C.POINTER(RicadiOpts)]),
@@ -598,6 +603,36 @@ class Context:
         _chk(self._lib.ricadi_adi_stop_rule(self._h, C.byref(r)))
         return self.STOP_RULES[r.value]
 
+    NEWTON_STOP_RULES = ("max_steps", "abstol", "reltol")
+
+    def newton_history(self, cap=None):
+        """``ricadi_newton_history``: one row ``[upd_abs, upd_rel, ADI steps, raw columns, columns kept,
+        ||Z_new Z_new^T||_F]`` per Newton step of the last Newton call.  ``cap``: copy at most that many rows;
+        returns ``(rows, steps of the call)`` then."""
+        n = C.c_int(0)
+        _chk(self._lib.ricadi_newton_history(self._h, None, 0, C.byref(n)))
+        rows = n.value if cap is None else int(cap)
+        out = np.full((max(rows, 1), 6), np.nan)
+        _chk(self._lib.ricadi_newton_history(self._h, _d(out), rows, C.byref(n)))
+        hist = out[:min(rows, n.value)].copy()
+        return hist if cap is None else (hist, n.value)
+
+    def newton_stopped_by(self):
+        """``ricadi_newton_stop_rule`` of the last Newton call: ``'abstol'``, ``'reltol'`` or ``'max_steps'``
+        (``'abstol'`` where both tolerances were met at one step)."""
+        r = C.c_int(0)
+        _chk(self._lib.ricadi_newton_stop_rule(self._h, C.byref(r)))
+        return self.NEWTON_STOP_RULES[r.value]
+
+    def diff_zzt_fnorm_dev(self, z1_ptr, k1, z0_ptr, k0, want=(True, True)):
+        """``ricadi_diff_zzt_fnorm_dev``: ``(||Z1 Z1^T - Z0 Z0^T||_F, ||Z1 Z1^T||_F)`` of two device panels (row-major,
+        leading dimension = width; ``z0_ptr`` None with ``k0 = 0``), as the Newton loop forms them.  ``want``: which of
+        the two outputs to pass (the other pointer is NULL and its value comes back as NaN)."""
+        upd, x1 = C.c_double(np.nan), C.c_double(np.nan)
+        _chk(self._lib.ricadi_diff_zzt_fnorm_dev(self._h, z1_ptr, int(k1), z0_ptr, int(k0),
+                                                 C.byref(upd) if want[0] else None, C.byref(x1) if want[1] else None))
+        return upd.value, x1.value
+
     def lyap_adi(self, shifts, W, prm, fetch=True):
         W = as_panel(W, self.nv)
         m = W.shape[1]
@@ -619,7 +654,10 @@ class Context:
         _warn_nonconverged(info)
         return Z, info
 
-    def ric_newtonadi(self, shifts, B, W, prm, Z0=None, oldB=None, fetch=True):
+    def ric_newtonadi(self, shifts, B, W, prm, Z0=None, oldB=None, fetch=True, upd_hist=False):
+        """``upd_hist=True`` adds ``info['upd_hist']`` (:meth:`newton_history` of this call) and
+        ``info['nwtn_stopped_by']``.  They come on request only: without them every value of ``info`` is a number or a
+        string, and callers convert the dict wholesale on that footing (``tests/context_battery.py`` does)."""
         B = as_panel(B, self.nv)
         W = as_panel(W, self.nv)
         sh = np.ascontiguousarray(shifts, dtype=np.float64)
@@ -650,6 +688,8 @@ class Context:
                     gmres_nonconverged=int(stats[6]), gmres_worst_relres=stats[7],
                     lyap_res_fro=stats[8], lyap_rhs_fro=stats[9], storage_escalations=int(stats[10]),
                     adi_sweeps=int(stats[11]), adi_stopped_by=self.adi_stopped_by())
+        if upd_hist:
+            info.update(upd_hist=self.newton_history(), nwtn_stopped_by=self.newton_stopped_by())
         _warn_nonconverged(info)
         return Z, info
 
@@ -657,9 +697,10 @@ class Context:
         """Copy the context's resident factor (NV x c, packed) into a device buffer."""
         _chk(self._lib.ricadi_factor_get_dev(self._h, z_ptr, int(c)))
 
-    def ric_newtonadi_dev(self, shifts, B_t, W_t, prm, Z0_t=None, old_t=None):
+    def ric_newtonadi_dev(self, shifts, B_t, W_t, prm, Z0_t=None, old_t=None, upd_hist=False):
         """``ricadi_ric_newtonadi_dev``: every panel is a torch CUDA tensor (float64, contiguous, NV rows);
-        the new iterate comes back as a fresh NV x c CUDA tensor.  No PCIe traffic."""
+        the new iterate comes back as a fresh NV x c CUDA tensor.  No PCIe traffic.  ``upd_hist``: as
+        :meth:`ric_newtonadi`."""
         import torch
         sh = np.ascontiguousarray(shifts, dtype=np.float64)
         for t in (B_t, W_t, Z0_t, old_t):
@@ -684,6 +725,8 @@ class Context:
                     gmres_nonconverged=int(stats[6]), gmres_worst_relres=stats[7],
                     lyap_res_fro=stats[8], lyap_rhs_fro=stats[9], storage_escalations=int(stats[10]),
                     adi_sweeps=int(stats[11]), adi_stopped_by=self.adi_stopped_by())
+        if upd_hist:
+            info.update(upd_hist=self.newton_history(), nwtn_stopped_by=self.newton_stopped_by())
         _warn_nonconverged(info)
         return Zt, info
 

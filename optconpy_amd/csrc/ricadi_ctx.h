@@ -361,6 +361,12 @@ struct ricadi_ctx {
   DArr<double> res_pan, res_part, res_gram;
   std::vector<double> adi_res_hist;
   int adi_stop_rule = 0;
+  // Newton-Kleinman driver (solver_newton.inl), of the last call: six doubles per step -- update norm, relative
+  // update, ADI steps, raw and kept columns, ||Z_new Z_new^T||_F -- and the rule that ended it (ricadi_newton_history,
+  // ricadi_newton_stop_rule)
+  bool newton_ran = false;
+  std::vector<double> newton_hist;
+  int newton_stop_rule = 0;
   bool adi_ran = false, adi_res_record = false;
   double* h_res = nullptr;    // pinned host copy of res_gram (h_res_cap doubles)
   size_t h_res_cap = 0;

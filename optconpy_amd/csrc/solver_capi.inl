@@ -112,7 +112,7 @@ static void factor_download(ricadi_ctx* c, double* Z_out) {
 extern "C" {
 
 const char* ricadi_last_error(void) { return ricadi::g_err.c_str(); }
-int ricadi_version(void) { return 412; }
+int ricadi_version(void) { return 413; }
 int ricadi_sizeof_opts(void) { return (int)sizeof(ricadi_opts); }
 int ricadi_sizeof_adi_params(void) { return (int)sizeof(ricadi_adi_params); }
 // field types in declaration order (d = double, i = int); keep in step with include/ricadi.h
@@ -269,6 +269,9 @@ static void forget_operator(ricadi_ctx* c) {
   c->adi_ran = false;
   c->adi_res_hist.clear();
   c->adi_stop_rule = 0;
+  c->newton_ran = false;
+  c->newton_hist.clear();
+  c->newton_stop_rule = 0;
   c->radi_ran = false;
   c->radi_shift_hist.clear();
   c->radi_fallbacks = 0;
@@ -827,6 +830,22 @@ int ricadi_qr(ricadi_ctx* c, const double* Z, int cz, double* Q_out, double* R_o
   API_END
 }
 
+// The Newton loop's update norm on device panels (diff_zzt_fnorm as ric_newtonadi_run calls it), for tests
+int ricadi_diff_zzt_fnorm_dev(ricadi_ctx* c, const double* dZ1, int k1, const double* dZ0, int k0, double* upd_out,
+                              double* x1_out) {
+  REQUIRE(c && c->nv > 0, RICADI_ESTATE, "set the operator (or the dimensions) first");
+  REQUIRE(k1 >= 1 && k0 >= 0, RICADI_EINVAL, "k1 >= 1 and k0 >= 0 required");
+  REQUIRE(dZ1 && (dZ0 || k0 == 0), RICADI_EINVAL, "NULL panel");
+  REQUIRE(k0 <= RICADI_MAX_UPD_COLS && k1 <= RICADI_MAX_UPD_COLS - k0, RICADI_EINVAL,
+          "k1 + k0 <= RICADI_MAX_UPD_COLS (4096) required");
+  API_BEGIN_ON(c)
+  double x1 = 0.0;
+  const double upd = diff_zzt_fnorm(c, dZ1, k1, k0 > 0 ? dZ0 : nullptr, k0, &x1);
+  if (upd_out) *upd_out = upd;
+  if (x1_out) *x1_out = x1;
+  API_END
+}
+
 // H_A = Q^T (cal A - U V^T) Q, H_E = Q^T cal E Q on device panels; the low-rank term through the dense form of
 // the same kernel (Q^T U, Q^T V), so H is bitwise reproducible with it as well
 static void project_pencil_dev(ricadi_ctx* c, const double* dQ, int k, double* dHA, double* dHE) {
@@ -1031,15 +1050,40 @@ int ricadi_adi_stop_rule(ricadi_ctx* c, int* rule_out) {
   return RICADI_OK;
 }
 
-int ricadi_ric_newtonadi(ricadi_ctx* c, const double* shifts, int ns, const double* B, int nb,
-                         const double* W, int mw, const double* Z0, int c0, const double* oldB,
-                         const ricadi_adi_params* prm, double* Z_out, int zcap, int* c_out,
-                         double* stats_out) {
+int ricadi_newton_history(ricadi_ctx* c, double* out, int cap, int* n_out) {
+  REQUIRE(c && n_out && cap >= 0 && (out || cap == 0), RICADI_EINVAL, "bad argument");
+  REQUIRE(c->newton_ran, RICADI_ESTATE, "no Newton iteration has run on this context");
+  const int n = (int)(c->newton_hist.size() / 6);
+  *n_out = n;
+  for (int i = 0; i < 6 * std::min(n, cap); ++i) out[i] = c->newton_hist[i];
+  return RICADI_OK;
+}
+int ricadi_newton_stop_rule(ricadi_ctx* c, int* rule_out) {
+  REQUIRE(c && rule_out, RICADI_EINVAL, "NULL argument");
+  REQUIRE(c->newton_ran, RICADI_ESTATE, "no Newton iteration has run on this context");
+  *rule_out = c->newton_stop_rule;
+  return RICADI_OK;
+}
+
+// the checks both Newton entries make before anything is launched
+static int check_newton(const ricadi_ctx* c, const double* shifts, int ns, const void* B, int nb, const void* W, int mw,
+                        const void* Z0, int c0, const ricadi_adi_params* prm) {
   REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
   REQUIRE(shifts && ns > 0 && B && W && prm, RICADI_EINVAL, "bad argument");
   REQUIRE(nb >= 1 && nb <= 64 && mw >= 1 && mw + nb <= RICADI_MAX_M, RICADI_EINVAL, "bad widths");
   REQUIRE(c0 == 0 || Z0, RICADI_EINVAL, "Z0 is NULL");
+  // a loop that never runs would answer with the factor an earlier call left in the context
+  REQUIRE(prm->nwtn_max_steps >= 1, RICADI_EINVAL, "nwtn_max_steps must be positive");
+  REQUIRE(prm->adi_max_steps >= 1, RICADI_EINVAL, "adi_max_steps must be positive");
   for (int i = 0; i < ns; ++i) REQUIRE(shifts[i] < 0.0, RICADI_EINVAL, "ADI shifts must be negative");
+  return RICADI_OK;
+}
+
+int ricadi_ric_newtonadi(ricadi_ctx* c, const double* shifts, int ns, const double* B, int nb,
+                         const double* W, int mw, const double* Z0, int c0, const double* oldB,
+                         const ricadi_adi_params* prm, double* Z_out, int zcap, int* c_out,
+                         double* stats_out) {
+  if (int rc = check_newton(c, shifts, ns, B, nb, W, mw, Z0, c0, prm)) return rc;
   API_BEGIN_ON(c)
   hipStream_t st = c->st;
   const int nv = c->nv;
@@ -1069,11 +1113,7 @@ int ricadi_ric_newtonadi(ricadi_ctx* c, const double* shifts, int ns, const doub
 int ricadi_ric_newtonadi_dev(ricadi_ctx* c, const double* shifts, int ns, const double* dB, int nb,
                              const double* dW, int mw, const double* dZ0, int c0, const double* dOldB,
                              const ricadi_adi_params* prm, int* c_out, double* stats_out) {
-  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
-  REQUIRE(shifts && ns > 0 && dB && dW && prm, RICADI_EINVAL, "bad argument");
-  REQUIRE(nb >= 1 && nb <= 64 && mw >= 1 && mw + nb <= RICADI_MAX_M, RICADI_EINVAL, "bad widths");
-  REQUIRE(c0 == 0 || dZ0, RICADI_EINVAL, "Z0 is NULL");
-  for (int i = 0; i < ns; ++i) REQUIRE(shifts[i] < 0.0, RICADI_EINVAL, "ADI shifts must be negative");
+  if (int rc = check_newton(c, shifts, ns, dB, nb, dW, mw, dZ0, c0, prm)) return rc;
   API_BEGIN_ON(c)
   ric_newtonadi_run(c, shifts, ns, dB, nb, dW, mw, dZ0, c0, dOldB, prm, stats_out);
   if (c_out) *c_out = c->zc;

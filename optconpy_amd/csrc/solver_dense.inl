@@ -409,8 +409,36 @@ static int compress_dev(ricadi_ctx* c, const double* dZ, int cz, int ldz, double
   return compress_gram_exec(c, main_exec(c), dZ, cz, ldz, thresh, kmax, thresh_relative, dOut, sv_host);
 }
 
-// || Z1 Z1^T - Z0 Z0^T ||_F  via an LQ factorisation of [Z1, Z0]^T (Householder,
-// rocSOLVER) -- no squaring, so updates far below 1e-8 relative are resolved.
+// More columns than rows (k1 + k0 > nv: two full-rank iterates of a small operator): D S D^T is itself the smaller
+// matrix, nv x nv, and is formed as it stands -- the entries cancel at u ||D||_F^2, the level the QR route reaches.
+// The QR route cannot serve here: once the columns have used up the nv dimensions, a panel is nothing after the
+// projection, the Householder tree returns unit columns for it that lie in the span of the earlier ones, and block
+// Gram-Schmidt against a Q that is not orthonormal no longer projects -- R S R^T then has another norm than D S D^T
+// (nv = 1, 100 + 100 columns: 534 for 3.4; found by tests/test_gpu_newton_steps.py).
+static double diff_zzt_fnorm_wide(ricadi_ctx* c, const double* D, int k1, int k0, double* x1norm) {
+  hipStream_t st = c->st;
+  const int kk = k1 + k0, nv = c->nv;
+  TArr<double> Dt(c->pool, (size_t)kk * nv), Dts(c->pool, (size_t)kk * nv), T(c->pool, (size_t)nv * nv);
+  std::vector<double> Th((size_t)nv * nv);
+  launch_transpose(st, nv, kk, D, kk, Dt.p, nv);
+  auto fro_of = [&](double sneg) {
+    // (S D^T)^T D^T = D S D^T, the rows of D^T that belong to Z0 scaled by sneg
+    launch_copy_cols(st, k1, nv, Dt.p, nv, 0, Dts.p, nv, 0, 1.0);
+    if (k0 > 0) launch_copy_cols(st, k0, nv, Dt.p + (size_t)k1 * nv, nv, 0, Dts.p + (size_t)k1 * nv, nv, 0, sneg);
+    HIPCHK(hipMemsetAsync(T.p, 0, sizeof(double) * nv * nv, st));
+    launch_gemm_tn(st, kk, nv, nv, Dts.p, nv, Dt.p, nv, T.p, nv);
+    HIPCHK(hipMemcpyAsync(Th.data(), T.p, sizeof(double) * nv * nv, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    double f = 0.0;
+    for (double v : Th) f += v * v;
+    return std::sqrt(f);
+  };
+  if (x1norm) *x1norm = fro_of(0.0);
+  return fro_of(-1.0);
+}
+
+// || Z1 Z1^T - Z0 Z0^T ||_F  via a QR factorisation of [Z1, Z0] (block_qr_dev) -- no squaring, so updates far below
+// 1e-8 relative are resolved.  With more columns than rows: diff_zzt_fnorm_wide.
 static double diff_zzt_fnorm(ricadi_ctx* c, const double* dZ1, int k1, const double* dZ0, int k0,
                              double* x1norm) {
   // D = [Z1, Z0] = Q R  (Householder TSQR panels, no squaring of the condition
@@ -418,10 +446,12 @@ static double diff_zzt_fnorm(ricadi_ctx* c, const double* dZ1, int k1, const dou
   // is that of the small matrix R S R^T -- updates far below 1e-8 are resolved.
   hipStream_t st = c->st;
   const int kk = k1 + k0, nv = c->nv;
-  TArr<double> D(c->pool, (size_t)nv * kk), Q(c->pool, (size_t)nv * kk), R(c->pool, (size_t)kk * kk),
-      Rt(c->pool, (size_t)kk * kk), Rts(c->pool, (size_t)kk * kk), T(c->pool, (size_t)kk * kk);
+  TArr<double> D(c->pool, (size_t)nv * kk);
   launch_copy_cols(st, nv, k1, dZ1, k1, 0, D.p, kk, 0, 1.0);
   if (k0 > 0) launch_copy_cols(st, nv, k0, dZ0, k0, 0, D.p, kk, k1, 1.0);
+  if (kk > nv) return diff_zzt_fnorm_wide(c, D.p, k1, k0, x1norm);
+  TArr<double> Q(c->pool, (size_t)nv * kk), R(c->pool, (size_t)kk * kk), Rt(c->pool, (size_t)kk * kk),
+      Rts(c->pool, (size_t)kk * kk), T(c->pool, (size_t)kk * kk);
   // panels never hold columns of both factors: Z1 ~ Z0 at convergence, and near-duplicate columns inside one
   // panel would send the factorisation to the Householder fallback
   block_qr_dev(c, D.p, kk, nv, kk, Q.p, R.p, k1);

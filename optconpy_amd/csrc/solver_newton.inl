@@ -46,6 +46,10 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
   const long esc0 = c->escalations;
   double worst = 0.0, last_res = 0.0, last_rhs = 0.0;
   int steps = 0;
+  // "of the last call": one row per step below (ricadi_newton_history), the rule that ends the loop
+  c->newton_hist.clear();
+  c->newton_stop_rule = RICADI_NEWTON_STOP_MAX_STEPS;
+  c->newton_ran = true;
   for (steps = 1; steps <= prm->nwtn_max_steps; ++steps) {
     int m = mw;
     Tick tkn;
@@ -97,10 +101,15 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
     upd = diff_zzt_fnorm(c, Znew.p, knew, zk, kk, &x1);
     updrel = x1 > 0.0 ? upd / x1 : 0.0;
     {
-      double dec[2] = {upd, updrel};       // the stopping decision is rank 0's
-      values_of_rank0(c, dec, 2);
+      double dec[3] = {upd, updrel, x1};   // the stopping decision is rank 0's
+      values_of_rank0(c, dec, 3);
       upd = dec[0];
       updrel = dec[1];
+      x1 = dec[2];
+    }
+    {
+      const double row[6] = {upd, updrel, (double)s.steps, (double)zraw, (double)knew, x1};
+      c->newton_hist.insert(c->newton_hist.end(), row, row + 6);
     }
     if (c->sw.timing) {
       c->t_updnorm += tkc.lap();
@@ -117,7 +126,11 @@ static void ric_newtonadi_run(ricadi_ctx* c, const double* shifts, int ns, const
     Zown.swap(Znew);
     zk = Zown.p;
     kk = knew;
-    if (upd < prm->nwtn_upd_abstol || updrel < prm->nwtn_upd_reltol) break;
+    if (upd < prm->nwtn_upd_abstol || updrel < prm->nwtn_upd_reltol) {
+      // both at one step: the first test of the || is reported
+      c->newton_stop_rule = upd < prm->nwtn_upd_abstol ? RICADI_NEWTON_STOP_ABSTOL : RICADI_NEWTON_STOP_RELTOL;
+      break;
+    }
   }
   if (steps > prm->nwtn_max_steps) steps = prm->nwtn_max_steps;
   if (stats_out) {

@@ -204,7 +204,7 @@ def names(sections=SECTIONS):
     out = []
     if "direct" in sections:
         out += ["rep0.setup_info", "rep0.cache_entries", "rep0.adi_res_history", "rep0.adi_stopped_by",
-                "rep0.radi_shift_history", "rep0.radi_sweep_info", "rep0.radi_sweep_widths", "rep0.recycle_guess_rank"]
+                "rep0.newton_history", "rep0.newton_stopped_by", "rep0.radi_shift_history", "rep0.radi_sweep_info", "rep0.radi_sweep_widths", "rep0.recycle_guess_rank"]
         for m in (5, 16):
             out += ["spmm.m%d" % m, "precond_apply.m%d" % m]
         for m in (16, 5):
@@ -227,8 +227,8 @@ def names(sections=SECTIONS):
 
 
 def reporters(ctx, op, inp=None):
-    """What the reporters say right now (the ``rep0.*`` outputs): ``setup_info``, ``cache_entries``, the ADI's and
-    RADI's "of the last call" entries, and the rank of the recycled guess for a 16-column panel at depth 0 (0
+    """What the reporters say right now (the ``rep0.*`` outputs): ``setup_info``, ``cache_entries``, the ADI's, the
+    Newton driver's and RADI's "of the last call" entries, and the rank of the recycled guess for a 16-column panel at depth 0 (0
     expected).  An exception is recorded as its type and message."""
     inp = inputs(op, 0) if inp is None else inp
     G = len(so.SHIFTS)
@@ -237,6 +237,8 @@ def reporters(ctx, op, inp=None):
     out["rep0.cache_entries"] = _reporter(ctx.cache_entries)
     out["rep0.adi_res_history"] = _reporter(ctx.adi_res_history)
     out["rep0.adi_stopped_by"] = _reporter(ctx.adi_stopped_by)
+    out["rep0.newton_history"] = _reporter(ctx.newton_history)
+    out["rep0.newton_stopped_by"] = _reporter(ctx.newton_stopped_by)
     out["rep0.radi_shift_history"] = _reporter(ctx.radi_shift_history)
     out["rep0.radi_sweep_info"] = _reporter(ctx.radi_sweep_info)
     out["rep0.radi_sweep_widths"] = _reporter(ctx.radi_sweep_widths)

@@ -348,6 +348,35 @@ int ricadi_adi_stop_rule(ricadi_ctx* ctx, int* rule_out);
  * for the right-hand side of the step form; 0 while neither the rule nor the history is on), for tests.          */
 int ricadi_adi_res_launches(ricadi_ctx* ctx, int64_t* n_out);
 
+/* ---- low-rank ADI with complex-conjugate shift pairs (exports added under the same ABI number) --
+ * ricadi_lyap_adi_cplx:  ricadi_lyap_adi -- same conventions for W, Z_out, c_out, stats_out -- for a list whose entry i
+ *   is the real shift shifts_re[i] where shifts_im[i] == 0 and else the PAIR (p, conj p), p = shifts_re[i] + i
+ *   shifts_im[i].  A pair is the real-arithmetic step of Benner, Kuerschner and Saak (2013): one complex solve, two real
+ *   blocks of Z, a real residual factor behind it.  It counts as two steps (stats_out[0], adi_max_steps, the residual
+ *   history: both entries of a pair hold the residual behind the pair) and as one shift solve (stats_out[3]); it is
+ *   never split -- with one step left before adi_max_steps and a pair due the iteration ends one step short with
+ *   RICADI_STOP_MAX_STEPS, and the rules are read after a pair's second block.  A low-rank term of the context is
+ *   applied around the complex solve (Sherman-Morrison-Woodbury; a numerically singular capacitance matrix is an error).
+ *   Step form only: with a pair in the list prm->sweep_width is not used (the Cauchy recombination of the sweep form is
+ *   real).  With every shifts_im[i] == 0 the call IS ricadi_lyap_adi(ctx, shifts_re, ...), sweep form included.
+ *   RICADI_EINVAL: a shift that is not finite or has shifts_re[i] >= 0; with a pair in the list also m + q > 128 (q the
+ *   width of the low-rank term) and a context with an exchange (ricadi_set_exchange: sharded, or a forced one).
+ * ricadi_adi_pair_blocks_dev:  the blocks kernel of the pair step alone, for tests.  dX: ng groups of n x mc complex
+ *   solutions (device, 16-byte aligned, group stride n mc complex; n = NV + NP, only the first NV rows of a group are
+ *   read), real column j < m of the step in complex column j % mc of group j / mc.  With delta = ar / ai, gam = 2
+ *   sqrt(-ar):  V1 = Re X + delta Im X  to dV1 (NV x m, contiguous),  gam V1  to columns zc .. zc + m of dZ (leading
+ *   dimension ldz >= zc + 2 m),  gam sqrt(delta^2 + 1) Im X  to the m columns behind; norms2_out[2] (host): the squared
+ *   Frobenius norms of the two blocks, summed in a fixed order.
+ * ricadi_adi_pair_info:  of the last ricadi_lyap_adi_cplx call: [pair entries solved, lockstep iterations of their
+ *   complex GMRES (per solve the slowest group's, refinement included), Woodbury refinement passes, complex solves
+ *   that missed their tolerance].  All zero after a call without pairs.                                           */
+int ricadi_lyap_adi_cplx(ricadi_ctx* ctx, const double* shifts_re, const double* shifts_im, int nshifts,
+                         const double* W, int m, const ricadi_adi_params* prm, double* Z_out, int* c_out,
+                         double* stats_out);
+int ricadi_adi_pair_blocks_dev(ricadi_ctx* ctx, int ng, int mc, int m, double ar, double ai, const double* dX,
+                               double* dZ, int ldz, int zc, double* dV1, double* norms2_out);
+int ricadi_adi_pair_info(ricadi_ctx* ctx, int64_t out[4]);
+
 /* ---- a1: Newton-Kleinman ADI for the projected Riccati equation -------
  * pru.proj_alg_ric_newtonadi (/root/reference/optcont_main.py:488-492,
  * /root/reference/solve_dae_ric.py:152-159).  B is NV x nb dense, W NV x mw,

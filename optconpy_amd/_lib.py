@@ -80,6 +80,11 @@ SIGNATURES = {
                                      C.POINTER(C.c_int), _dp]),
     "ricadi_lyap_adi": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.POINTER(RicadiAdiParams),
                                   _dp, C.POINTER(C.c_int), _dp]),
+    "ricadi_lyap_adi_cplx": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, C.c_int, C.POINTER(RicadiAdiParams),
+                                       _dp, C.POINTER(C.c_int), _dp]),
+    "ricadi_adi_pair_blocks_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp, _vp,
+                                             C.c_int, C.c_int, _vp, _dp]),
+    "ricadi_adi_pair_info": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "ricadi_ric_newtonadi": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp,
                                        C.c_int, _dp, C.POINTER(RicadiAdiParams), _dp, C.c_int,
                                        C.POINTER(C.c_int), _dp]),
@@ -634,16 +639,26 @@ class Context:
         return upd.value, x1.value
 
     def lyap_adi(self, shifts, W, prm, fetch=True):
+        """``ricadi_lyap_adi``; a list with a complex entry -- one number ``p`` with ``Re p < 0`` that stands for the
+        pair ``(p, conj p)``, DESIGN.md 3g -- goes through ``ricadi_lyap_adi_cplx`` and adds ``info['pair_info']``
+        (:meth:`adi_pair_info`)."""
         W = as_panel(W, self.nv)
         m = W.shape[1]
-        sh = np.ascontiguousarray(shifts, dtype=np.float64)
+        shc = np.asarray(shifts)
+        pairs = np.iscomplexobj(shc) and bool(np.any(shc.imag != 0.0))
+        sh = np.ascontiguousarray(shc.real, dtype=np.float64)
         cap = prm.adi_max_steps * m
         Z = np.empty((self.nv, cap)) if fetch else None
         cc = C.c_int(0)
         stats = np.zeros(8)
         self._zdev = None
-        _chk(self._lib.ricadi_lyap_adi(self._h, _d(sh), sh.size, _d(W), m, C.byref(prm),
-                                       None if Z is None else _d(Z), C.byref(cc), _d(stats)))
+        if pairs:
+            shi = np.ascontiguousarray(shc.imag, dtype=np.float64)
+            _chk(self._lib.ricadi_lyap_adi_cplx(self._h, _d(sh), _d(shi), sh.size, _d(W), m, C.byref(prm),
+                                                None if Z is None else _d(Z), C.byref(cc), _d(stats)))
+        else:
+            _chk(self._lib.ricadi_lyap_adi(self._h, _d(sh), sh.size, _d(W), m, C.byref(prm),
+                                           None if Z is None else _d(Z), C.byref(cc), _d(stats)))
         c = cc.value
         if fetch:
             Z = Z.ravel()[:self.nv * c].reshape(self.nv, c)
@@ -651,8 +666,40 @@ class Context:
                     shift_solves=int(stats[3]), res_fro=stats[4], cols=c,
                     gmres_nonconverged=int(stats[5]), gmres_worst_relres=stats[6],
                     storage_escalations=int(stats[7]), adi_stopped_by=self.adi_stopped_by())
+        if pairs:
+            info["pair_info"] = self.adi_pair_info()
         _warn_nonconverged(info)
         return Z, info
+
+    def lyap_adi_cplx(self, shifts_re, shifts_im, W, prm):
+        """``ricadi_lyap_adi_cplx`` as it is, for tests: returns ``(Z, stats[8], columns)``."""
+        W = as_panel(W, self.nv)
+        m = W.shape[1]
+        sr = np.ascontiguousarray(shifts_re, dtype=np.float64)
+        si = np.ascontiguousarray(shifts_im, dtype=np.float64)
+        Z = np.empty((self.nv, prm.adi_max_steps * m))
+        cc = C.c_int(0)
+        stats = np.zeros(8)
+        self._zdev = None
+        _chk(self._lib.ricadi_lyap_adi_cplx(self._h, _d(sr), _d(si), sr.size, _d(W), m, C.byref(prm), _d(Z),
+                                            C.byref(cc), _d(stats)))
+        return Z.ravel()[:self.nv * cc.value].reshape(self.nv, cc.value), stats, cc.value
+
+    def adi_pair_info(self):
+        """``ricadi_adi_pair_info`` of the last ``ricadi_lyap_adi_cplx`` call: ``[pairs solved, lockstep iterations of
+        the complex GMRES, Woodbury refinement passes, complex solves that missed the tolerance]``."""
+        out = (C.c_int64 * 4)()
+        _chk(self._lib.ricadi_adi_pair_info(self._h, out))
+        return [int(v) for v in out]
+
+    def adi_pair_blocks_dev(self, ng, mc, m, p, x_ptr, z_ptr, ldz, zc, v1_ptr):
+        """``ricadi_adi_pair_blocks_dev``: the blocks kernel of the pair step at ``p`` on device panels; returns the two
+        squared block norms."""
+        out = np.zeros(2)
+        p = complex(p)
+        _chk(self._lib.ricadi_adi_pair_blocks_dev(self._h, int(ng), int(mc), int(m), p.real, p.imag, x_ptr, z_ptr,
+                                                  int(ldz), int(zc), v1_ptr, _d(out)))
+        return out
 
     def ric_newtonadi(self, shifts, B, W, prm, Z0=None, oldB=None, fetch=True, upd_hist=False):
         """``upd_hist=True`` adds ``info['upd_hist']`` (:meth:`newton_history` of this call) and
@@ -1309,6 +1356,15 @@ Context.lqg_balance_dev = _lqg_balance_dev
 
 # ---- complex shifts (include/ricadi.h, "saddle systems at COMPLEX shifts") --------------------
 MAX_MC = 8               # widest complex panel
+ADI_PAIR_ROWS = 32       # velocity rows per workgroup of the pair step's kernels (PAIR_ROWS of ricadi_cplx.hip)
+
+
+def adi_pair_groups(width):
+    """How the pair step of the ADI packs ``width`` real columns (``m``, plus ``q`` with a low-rank term):
+    ``(ng, mc)`` -- ``ceil(width / 8)`` groups of ``ceil(width / ng)`` complex columns, real column ``j`` in complex
+    column ``j % mc`` of group ``j // mc``."""
+    ng = -(-int(width) // MAX_MC)
+    return ng, -(-int(width) // ng)
 
 
 def _cplx_ptr(t, shape=None):

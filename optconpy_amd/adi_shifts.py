@@ -61,10 +61,65 @@ def _ratio(c, p):
     return np.abs((c - p) / (c + p))
 
 
+def _merge_complex(cands, rtol=MERGE_RTOL):
+    """Candidates with a complex entry: every one in the closed upper half plane (a pair is held by its member with
+    ``Im > 0``), sorted by magnitude, then phase; one within ``rtol`` (relative distance) of a kept one is dropped."""
+    c = np.asarray(cands, dtype=complex)
+    c = np.where(c.imag < 0, c.conj(), c)
+    c = c[np.lexsort((np.angle(c), np.abs(c)))]
+    out = []
+    for x in c:
+        if all(abs(x - y) > rtol * abs(y) for y in out):
+            out.append(x)
+    return np.asarray(out, dtype=complex)
+
+
+def _pair_ratio(t, p):
+    """``|(t - p)/(t + p)|`` for a real ``p``, ``|(t - p)(t - conj p) / ((t + p)(t + conj p))|`` for a pair."""
+    r = np.abs((t - p) / (t + p))
+    return r if p.imag == 0.0 else r * np.abs((t - p.conjugate()) / (t + p.conjugate()))
+
+
+def _penzl_select_pairs(cands, num):
+    """:func:`penzl_select` for candidates off the real axis: a complex candidate stands for its conjugate pair, the
+    min-max and the running products are taken over the conjugate-symmetric set of test points with the pair factor,
+    and a pair counts as two of ``num`` (with one left, the best real candidate is taken, if there is one).  Returns
+    floats and -- for the pairs -- complex numbers with a positive imaginary part, in the order of the picks."""
+    c = _merge_complex(cands)
+    if c.size == 0 or num < 1:
+        return []
+    t = np.concatenate([c, c[c.imag != 0.0].conj()])
+    cost = np.where(c.imag != 0.0, 2, 1)
+    picks, count = [], 0
+    prod = np.ones(t.size)
+    taken = np.zeros(c.size, dtype=bool)
+    while count < num:
+        ok = ~taken & (cost <= num - count)
+        if not ok.any():
+            break
+        if not picks:
+            score = np.array([-_pair_ratio(t, p).max() for p in c])     # the first minimises the worst ratio
+        else:
+            score = prod[:c.size]
+            if score[ok].max() == 0.0:
+                break
+        i = int(np.flatnonzero(ok)[np.argmax(score[ok])])
+        taken[i] = True
+        picks.append(complex(c[i]) if c[i].imag != 0.0 else float(c[i].real))
+        count += int(cost[i])
+        prod = prod * _pair_ratio(t, c[i])
+    return picks
+
+
 def penzl_select(cands, num):
     """Penzl's greedy selection of ``num`` shifts among negative real candidates (merged within 1 % first):
     the first minimises ``max_c |(c - p)/(c + p)|``, each further one is the candidate where the running product
-    ``prod_i |(c - p_i)/(c + p_i)|`` is largest.  Returns the picks in the order they were made."""
+    ``prod_i |(c - p_i)/(c + p_i)|`` is largest.  Returns the picks in the order they were made.  Candidates with a
+    complex entry (``candidates(..., keep_complex=True)``) are selected as conjugate pairs:
+    :func:`_penzl_select_pairs`."""
+    if np.iscomplexobj(cands) and np.any(np.asarray(cands).imag != 0.0):
+        return _penzl_select_pairs(cands, num)
+    cands = np.real(cands)
     c = _merge(cands)
     if c.size == 0 or num < 1:
         return []
@@ -147,17 +202,29 @@ def basis(Qraw, R, max_dim=MAX_BASIS, rtol=BASIS_RTOL):
     return Qraw @ U[:, :keep]
 
 
-def candidates(HA, HE):
-    """``-|lambda|`` for the finite, nonzero generalised eigenvalues of ``(HA, HE)``."""
+COMPLEX_RTOL = 1e-3   # keep_complex: a Ritz value with |Im| above this fraction of its modulus stays complex
+
+
+def candidates(HA, HE, keep_complex=False):
+    """``-|lambda|`` for the finite, nonzero generalised eigenvalues of ``(HA, HE)``.  ``keep_complex``: a stable
+    one with ``|Im lambda| > 1e-3 |lambda|`` is kept as ``Re lambda + i |Im lambda|`` (it stands for its conjugate
+    pair), the others as ``-|lambda|``; the array is complex then."""
     lam = sla.eigvals(HA, HE)
     lam = lam[np.isfinite(lam)]
     c = -np.abs(lam)
+    if keep_complex:
+        off = (np.abs(lam.imag) > COMPLEX_RTOL * np.abs(lam)) & (lam.real < 0)
+        c = np.where(off, lam.real + 1j * np.abs(lam.imag), c.astype(complex))
+        return c[c.real < 0]
     return c[c < 0]
 
 
-def auto_shifts(ctx, W, num=8, warm_steps=2, default=None):
+def auto_shifts(ctx, W, num=8, warm_steps=2, default=None, keep_complex=False):
     """Shifts for the ADI on the operator of ``ctx`` (its low-rank term included) with right-hand side
-    factor ``W`` (NV x m): a :class:`ShiftList` of distinct negative reals, at most ``num`` of them."""
+    factor ``W`` (NV x m): a :class:`ShiftList` of distinct negative reals, at most ``num`` of them.
+    ``keep_complex``: Ritz values off the real axis are candidates as they are and the list may hold complex entries,
+    one per conjugate pair, each counted as two of ``num``; such a list is returned in the order of the picks
+    (:func:`admissible_order` serves the Cauchy windows of the sweep form, which takes no pairs)."""
     W = _lib.as_panel(W, ctx.nv)
     p0 = initial_shift(ctx.diag_ratio)
     W0 = _project_w(ctx, W)
@@ -179,14 +246,16 @@ def auto_shifts(ctx, W, num=8, warm_steps=2, default=None):
     cands = np.zeros(0)
     if Q.shape[1] > 0:
         HA, HE = ctx.project_pencil(Q)
-        cands = candidates(HA, HE)
+        cands = candidates(HA, HE, keep_complex=keep_complex)
     if cands.size == 0:
         from .proj_ric_utils import DEFAULT_MS
         out = ShiftList(DEFAULT_MS if default is None else default)
         fallback = True
     else:
-        out = ShiftList(admissible_order(penzl_select(cands, num)))
+        picks = penzl_select(cands, num)
+        out = ShiftList(picks if any(isinstance(p, complex) for p in picks) else admissible_order(picks))
         fallback = False
-    out.info = dict(candidates=int(_merge(cands).size), warm_solves=int(solves), fallback=fallback,
+    ncand = _merge_complex(cands).size if np.iscomplexobj(cands) else _merge(cands).size
+    out.info = dict(candidates=int(ncand), warm_solves=int(solves), fallback=fallback,
                     basis_dim=int(Q.shape[1]), p0=p0)
     return out

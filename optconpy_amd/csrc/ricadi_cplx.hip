@@ -453,4 +453,97 @@ void launch_cplx_gmres_backsolve(hipStream_t st, const GroupTab& gt, const Group
   hipLaunchKernelGGL(cplx_gmres_backsolve_kernel, dim3(gt.ng), dim3(64), 0, st, gt, ks, mc, restart, Hm, gv, y, gsy);
 }
 
+// ---------------------------------------------------------------------------
+// K6c: the streaming kernels of the complex-conjugate pair step of the Lyapunov ADI.  The m'
+// real columns of a step -- the residual factor W and, with a low-rank term, U beside it -- travel as ng groups of mc
+// complex columns: real column j is complex column j % mc of group j / mc.
+// ---------------------------------------------------------------------------
+constexpr int PAIR_ROWS = 32;   // rows per workgroup of both kernels
+int adi_pair_rows() { return PAIR_ROWS; }
+int adi_pair_num_blocks(int nv) { return std::max(1, (nv + PAIR_ROWS - 1) / PAIR_ROWS); }
+
+// R_g (nv x mc complex, group stride gsr doubles) <- columns g mc .. of [W (nv x m), U (nv x q)]: imaginary parts zero,
+// columns behind m + q zero.  One 16-byte store per complex entry.
+__global__ __launch_bounds__(256) void adi_pair_pack_kernel(int nv, int m, int q, int ng, int mc,
+                                                            const double* __restrict__ W, const double* __restrict__ U,
+                                                            double* __restrict__ R, size_t gsr) {
+  const int wide = ng * mc;
+  const size_t total = (size_t)nv * wide;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    const size_t row = idx / wide;
+    const int j = (int)(idx % wide), grp = j / mc, cc = j % mc;
+    double v = 0.0;
+    if (j < m) v = W[row * m + j];
+    else if (j < m + q) v = U[row * q + (j - m)];
+    *reinterpret_cast<double2*>(R + (size_t)grp * gsr + (row * mc + cc) * 2) = make_double2(v, 0.0);
+  }
+}
+void launch_adi_pair_pack(hipStream_t st, int nv, int m, int q, int ng, int mc, const double* W, const double* U,
+                          double* R, size_t gsr) {
+  if (nv <= 0 || ng <= 0) return;
+  const size_t total = (size_t)nv * ng * mc;
+  const int grid = (int)std::min<size_t>((total + 255) / 256, 4096);
+  hipLaunchKernelGGL(adi_pair_pack_kernel, dim3(grid), dim3(256), 0, st, nv, m, q, ng, mc, W, U, R, gsr);
+}
+
+// The two real blocks of a pair step from the solution groups X_g (rows x mc complex, group stride gsx doubles; the
+// first nv rows are read, the pressure rows behind them never): per velocity row and column j < m, with x = X[row][j],
+//   v1 = Re x + delta Im x,   Z[row][zc + j] = gam v1,   Z[row][zc + m + j] = gam2 Im x,   V1[row][j] = v1
+// (gam = 2 sqrt(-a), gam2 = gam sqrt(delta^2 + 1), delta = a / b).  A workgroup owns PAIR_ROWS rows; thread t takes the
+// entries t, t + 256, .. of its tile in row-major order (one 16-byte load each) and sums the squares of what it wrote;
+// the 256 sums are added pairwise in LDS in a fixed tree, partial[2 blk], partial[2 blk + 1] are the workgroup's shares
+// of the two squared Frobenius norms.
+__global__ __launch_bounds__(256) void adi_pair_blocks_kernel(int nv, int m, int mc, double delta, double gam,
+                                                              double gam2, const double* __restrict__ X, size_t gsx,
+                                                              double* __restrict__ Z, int zld, int zc,
+                                                              double* __restrict__ V1, double* __restrict__ partial) {
+  __shared__ double s1[256], s2[256];
+  const int r0 = blockIdx.x * PAIR_ROWS, m2 = 2 * mc;
+  const int rows = min(PAIR_ROWS, nv - r0);
+  double a1 = 0.0, a2 = 0.0;
+  for (int idx = threadIdx.x; idx < rows * m; idx += 256) {
+    const size_t row = (size_t)(r0 + idx / m);
+    const int j = idx % m, grp = j / mc, cc = j % mc;
+    const double2 x = *reinterpret_cast<const double2*>(X + (size_t)grp * gsx + row * m2 + 2 * cc);
+    const double v1 = fma(delta, x.y, x.x);
+    const double z1 = gam * v1, z2 = gam2 * x.y;
+    Z[row * zld + zc + j] = z1;
+    Z[row * zld + zc + m + j] = z2;
+    V1[row * m + j] = v1;
+    a1 = fma(z1, z1, a1);
+    a2 = fma(z2, z2, a2);
+  }
+  s1[threadIdx.x] = a1;
+  s2[threadIdx.x] = a2;
+  __syncthreads();
+  for (int w = 128; w >= 1; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      s1[threadIdx.x] += s1[threadIdx.x + w];
+      s2[threadIdx.x] += s2[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    partial[2 * blockIdx.x] = s1[0];
+    partial[2 * blockIdx.x + 1] = s2[0];
+  }
+}
+// out[k] = sum over the workgroups, in workgroup order, of partial[2 blk + k]  (k < 2; the pattern of cplx_reduce_kernel)
+__global__ __launch_bounds__(64) void adi_pair_reduce_kernel(int nblk, const double* __restrict__ partial,
+                                                             double* __restrict__ out) {
+  if (threadIdx.x >= 2) return;
+  double sum = 0.0;
+  for (int b = 0; b < nblk; ++b) sum += partial[2 * b + threadIdx.x];
+  out[threadIdx.x] = sum;
+}
+void launch_adi_pair_blocks(hipStream_t st, int nv, int m, int mc, double delta, double gam, double gam2,
+                            const double* X, size_t gsx, double* Z, int zld, int zc, double* V1, double* partial,
+                            double* norms2) {
+  if (nv <= 0 || m <= 0) return;
+  const int nblk = adi_pair_num_blocks(nv);
+  hipLaunchKernelGGL(adi_pair_blocks_kernel, dim3(nblk), dim3(256), 0, st, nv, m, mc, delta, gam, gam2, X, gsx, Z, zld,
+                     zc, V1, partial);
+  hipLaunchKernelGGL(adi_pair_reduce_kernel, dim3(1), dim3(64), 0, st, nblk, partial, norms2);
+}
+
 }  // namespace ricadi

@@ -433,6 +433,13 @@ struct ricadi_ctx {
     DArr<double> V, Zb, w, r, b;
     DArr<double> partial, h1, h2, hout, nrm2, scale, Hm, cs, sn, gv, y, bnorm, resid;
   } cw;
+  // pair step of the Lyapunov ADI (solver_adi_pairs.inl): the packed right-hand side groups and
+  // their solutions, the refinement's pair of the same, S(p)^-1 U as one complex panel, V^T X and the embedded Woodbury
+  // coefficients per group, the norm partials and the two block norms; of the last ricadi_lyap_adi_cplx call: pairs
+  // solved, lockstep iterations of the complex GMRES, Woodbury refinement passes, complex solves that missed the
+  // tolerance (ricadi_adi_pair_info)
+  DArr<double> pair_rhs, pair_x, pair_rhs2, pair_d, pair_xu, pair_t, pair_m, pair_part, pair_nrm;
+  int64_t pair_info[4] = {0, 0, 0, 0};
   // factor
   DArr<double> Z;
   int zc = 0, zld = 0;

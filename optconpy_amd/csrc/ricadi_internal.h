@@ -681,6 +681,18 @@ void launch_cplx_gmres_hess(hipStream_t st, const GroupTab& gt, int mc, int j, i
 void launch_cplx_gmres_backsolve(hipStream_t st, const GroupTab& gt, const GroupInts& ks, int mc, int restart,
                                  const double* Hm, const double* gv, double* y, size_t gsy);
 
+// K6c: the pair step of the Lyapunov ADI (ricadi_cplx.hip).  Real column j of a step's panel is
+// complex column j % mc of group j / mc.  pack: R_g <- [W, U] with zero imaginary parts and zero padding columns
+// (U == NULL with q = 0).  blocks: Z[:, zc .. zc + 2m) <- [gam V1, gam2 Im X], V1 = Re X + delta Im X (nv x m,
+// contiguous), norms2[0..2) the squared Frobenius norms of the two blocks; partial: 2 adi_pair_num_blocks(nv) doubles.
+int adi_pair_rows();
+int adi_pair_num_blocks(int nv);
+void launch_adi_pair_pack(hipStream_t st, int nv, int m, int q, int ng, int mc, const double* W, const double* U,
+                          double* R, size_t gsr);
+void launch_adi_pair_blocks(hipStream_t st, int nv, int m, int mc, double delta, double gam, double gam2,
+                            const double* X, size_t gsx, double* Z, int zld, int zc, double* V1, double* partial,
+                            double* norms2);
+
 void set_error(const std::string& msg);
 
 }  // namespace ricadi

@@ -25,3 +25,4 @@ namespace ricadi {
 #include "solver_capi_probe.inl"   // the tests' probes
 #include "solver_capi_timing.inl"  // the benchmark's timers
 #include "solver_cplx.inl"         // complex shifts: product, CGS2 step, lockstep flexible GMRES, their entry points
+#include "solver_adi_pairs.inl"    // low-rank ADI with complex-conjugate shift pairs (step form), its entry points

@@ -632,6 +632,47 @@ static int adi_recycle_depth(const ricadi_ctx* c) {
   return e ? std::max(0, std::min(8, atoi(e))) : (c->n <= 200000 ? 5 : 3);
 }
 
+// What the step form fetches for the residual rule: res_gram holds W^T W before and after a step (2 m^2 doubles), `hg`
+// is its pinned host copy.  Launches ||W_0^T W_0|| of the iteration; it is fetched in the first step's synchronisation.
+static double* adi_res_begin(ricadi_ctx* c, const double* dW, int m) {
+  c->res_part.ensure(gram_fixed_partial_len(c->nv, m));
+  c->res_gram.ensure((size_t)2 * m * m);
+  double* hg = res_host(c, (size_t)2 * m * m);
+  launch_gram_fixed(c->st, c->nv, m, dW, m, c->res_part.p, c->res_gram.p);
+  c->res_launches += 2;
+  return hg;
+}
+// ... W^T W behind a step into the second half, both halves to `hg` (queued: the step's synchronisation fetches them)
+static void adi_res_fetch(ricadi_ctx* c, const double* dW, int m, double* hg) {
+  const int mm = m * m;
+  launch_gram_fixed(c->st, c->nv, m, dW, m, c->res_part.p, c->res_gram.p + mm);
+  c->res_launches += 2;
+  HIPCHK(hipMemcpyAsync(hg, c->res_gram.p, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, c->st));
+}
+
+// One step at the real shift p: S(p) [V; *] = [W; 0], W <- W - 2 p E V, Z <- [Z, sqrt(-2p) V] at column c->zc (which the
+// caller advances).  n2: the block's squared Frobenius norm; with `hg` the Gram matrices of adi_res_fetch are in it when
+// the step returns (one synchronisation for both).
+static GmresResult adi_real_step(ricadi_ctx* c, double p, double* dW, int m, double* hg, double& n2) {
+  hipStream_t st = c->st;
+  ShiftData* sd = get_shift(c, p, 1.0);
+  load_rhs(c, dW, m, c->bvec.p);
+  GmresResult r = gmres_solve(c, sd, c->bvec.p, c->xs.p, m, true, nullptr);
+  // W <- W - 2 p E V
+  launch_spmm(st, c->nv, c->E.rp.p, c->E.ci.p, c->E.v.p, c->xs.p, m, nullptr, dW, m, dW, m,
+              -2.0 * p, 1.0, nullptr, m);
+  // Z <- [Z, sqrt(-2p) V]
+  launch_copy_cols(st, c->nv, m, c->xs.p, m, 0, c->Z.p, c->zld, c->zc, std::sqrt(-2.0 * p));
+  col_norms2(c, c->xs.p, c->nv, m, c->nrm2.p);
+  HIPCHK(hipMemcpyAsync(c->h_resid, c->nrm2.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+  if (hg) adi_res_fetch(c, dW, m, hg);
+  HIPCHK(hipStreamSynchronize(st));
+  n2 = 0.0;
+  for (int j = 0; j < m; ++j) n2 += c->h_resid[j];
+  n2 *= -2.0 * p;
+  return r;
+}
+
 // Step form: one shift solve per step, S(p) [V; *] = [W; 0], then W <- W - 2 p E V and Z <- [Z, sqrt(-2p) V].
 // dW: NV x m device panel (overwritten by the final residual factor); the blocks are appended to c->Z (ld = c->zld)
 // starting at column c->zc.  Tries the sweep form first where sweep_width asks for it.  Both rules of AdiStop end the
@@ -647,7 +688,6 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
   c->adi_ran = true;
   if (prm.sweep_width > 1 && lyap_adi_sweeps_dev(c, shifts, ns, dW, m, prm, stt)) return stt;
   stt = AdiStats();
-  hipStream_t st = c->st;
   ensure_work(c, m);
   // per-shift data of the whole shift cycle (and of the projection) up front: the coarse
   // inverses then come out of one batched factorisation instead of one at a time
@@ -658,19 +698,11 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
   // is launched here and fetched in the first step's synchronisation.
   AdiStop stop(ns, prm.adi_newZ_reltol, prm.adi_res_reltol, prm.adi_max_steps, adi_res_wanted(c, prm));
   const int mm = m * m;
-  double* hg = nullptr;
-  if (stop.res_on) {
-    c->res_part.ensure(gram_fixed_partial_len(c->nv, m));
-    c->res_gram.ensure((size_t)2 * mm);
-    hg = res_host(c, (size_t)2 * mm);
-    launch_gram_fixed(st, c->nv, m, dW, m, c->res_part.p, c->res_gram.p);
-    c->res_launches += 2;
-  }
+  double* hg = stop.res_on ? adi_res_begin(c, dW, m) : nullptr;
   for (int step = 1; step <= prm.adi_max_steps; ++step) {
     const double p = shifts[(step - 1) % ns];
-    ShiftData* sd = get_shift(c, p, 1.0);
-    load_rhs(c, dW, m, c->bvec.p);
-    GmresResult r = gmres_solve(c, sd, c->bvec.p, c->xs.p, m, true, nullptr);
+    double n2 = 0.0, wf = 0.0;
+    GmresResult r = adi_real_step(c, p, dW, m, hg, n2);
     if (!r.converged) {
       stt.nonconverged++;
       stt.worst_relres = std::max(stt.worst_relres, r.max_relres);
@@ -679,22 +711,6 @@ static AdiStats lyap_adi_dev(ricadi_ctx* c, const double* shifts, int ns, double
                 step, p, r.max_relres, r.iters);
     }
     stt.shift_solves++;
-    // W <- W - 2 p E V
-    launch_spmm(st, c->nv, c->E.rp.p, c->E.ci.p, c->E.v.p, c->xs.p, m, nullptr, dW, m, dW, m,
-                -2.0 * p, 1.0, nullptr, m);
-    // Z <- [Z, sqrt(-2p) V]
-    launch_copy_cols(st, c->nv, m, c->xs.p, m, 0, c->Z.p, c->zld, c->zc, std::sqrt(-2.0 * p));
-    double n2 = 0.0, wf = 0.0;
-    col_norms2(c, c->xs.p, c->nv, m, c->nrm2.p);
-    HIPCHK(hipMemcpyAsync(c->h_resid, c->nrm2.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
-    if (stop.res_on) {
-      launch_gram_fixed(st, c->nv, m, dW, m, c->res_part.p, c->res_gram.p + mm);
-      c->res_launches += 2;
-      HIPCHK(hipMemcpyAsync(hg, c->res_gram.p, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    for (int j = 0; j < m; ++j) n2 += c->h_resid[j];
-    n2 *= -2.0 * p;
     if (stop.res_on) {
       if (stop.res_rhs < 0.0) stop.res_rhs = gram_block_fro(hg, m, m, 0);
       wf = gram_block_fro(hg + mm, m, m, 0);

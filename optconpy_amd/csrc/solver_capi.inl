@@ -987,12 +987,10 @@ int ricadi_lqg_balance_dev(ricadi_ctx* c, const double* dZc, int kc, const doubl
   API_END
 }
 
-int ricadi_lyap_adi(ricadi_ctx* c, const double* shifts, int ns, const double* W, int m,
-                    const ricadi_adi_params* prm, double* Z_out, int* c_out, double* stats_out) {
-  if (int rc = check_panel(c, m)) return rc;
-  REQUIRE(shifts && ns > 0 && W && prm, RICADI_EINVAL, "bad argument");
-  for (int i = 0; i < ns; ++i) REQUIRE(shifts[i] < 0.0, RICADI_EINVAL, "ADI shifts must be negative");
-  REQUIRE(prm->adi_max_steps > 0, RICADI_EINVAL, "adi_max_steps must be positive");
+// What ricadi_lyap_adi and ricadi_lyap_adi_cplx share behind their argument checks: the factor reserved, W uploaded,
+// `run(dW)` -- the driver, which returns its AdiStats --, the outputs.
+static int lyap_adi_entry(ricadi_ctx* c, const double* W, int m, const ricadi_adi_params* prm, double* Z_out, int* c_out,
+                          double* stats_out, const std::function<AdiStats(double*)>& run) {
   API_BEGIN_ON(c)
   ensure_work(c, m);
   const long esc0 = c->escalations;
@@ -1002,7 +1000,7 @@ int ricadi_lyap_adi(ricadi_ctx* c, const double* shifts, int ns, const double* W
   HIPCHK(hipMemcpyAsync(dW.p, W, sizeof(double) * c->nv * m, hipMemcpyHostToDevice, c->st));
   if (c->sw.timing) c->t_setup = c->t_solve = c->t_recomb = c->t_compress = c->t_proj = c->t_cyc = c->t_iter = c->t_guess = 0;
   Tick tka;
-  AdiStats s = lyap_adi_dev(c, shifts, ns, dW.p, m, *prm);
+  AdiStats s = run(dW.p);
   if (c->sw.timing) {
     (void)hipStreamSynchronize(c->st);
     fprintf(stderr, "[ricadi timing] lyap_adi: total %.1f ms = setup %.1f + projection %.1f + solves %.1f (Arnoldi iterations %.1f, "
@@ -1023,6 +1021,16 @@ int ricadi_lyap_adi(ricadi_ctx* c, const double* shifts, int ns, const double* W
     stats_out[7] = (double)(c->escalations - esc0);
   }
   API_END
+}
+
+int ricadi_lyap_adi(ricadi_ctx* c, const double* shifts, int ns, const double* W, int m,
+                    const ricadi_adi_params* prm, double* Z_out, int* c_out, double* stats_out) {
+  if (int rc = check_panel(c, m)) return rc;
+  REQUIRE(shifts && ns > 0 && W && prm, RICADI_EINVAL, "bad argument");
+  for (int i = 0; i < ns; ++i) REQUIRE(shifts[i] < 0.0, RICADI_EINVAL, "ADI shifts must be negative");
+  REQUIRE(prm->adi_max_steps > 0, RICADI_EINVAL, "adi_max_steps must be positive");
+  return lyap_adi_entry(c, W, m, prm, Z_out, c_out, stats_out,
+                        [&](double* dW) { return lyap_adi_dev(c, shifts, ns, dW, m, *prm); });
 }
 
 int ricadi_adi_res_history(ricadi_ctx* c, double* out, int cap, int* n_out) {

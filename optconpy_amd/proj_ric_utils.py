@@ -133,19 +133,48 @@ def _orient(amat, mmat, transposed):
 
 
 def _is_auto(ms):
-    return isinstance(ms, str) and ms == "auto"
+    return isinstance(ms, str) and ms in ("auto", "auto-complex")
+
+
+def _has_pairs(ms):
+    return any(isinstance(p, complex) for p in ms)
 
 
 def _shifts(d):
-    """The shift list of an ``adi_dict``: ``DEFAULT_MS`` without ``'ms'``, the string ``'auto'`` as is (the
-    caller generates the list, :func:`_auto_shifts`), else a list of negative reals."""
+    """The shift list of an ``adi_dict``: ``DEFAULT_MS`` without ``'ms'``, the strings ``'auto'`` and
+    ``'auto-complex'`` as they are (the caller generates the list, :func:`_auto_shifts`), else a list of negative
+    reals -- or, with a complex entry in it, of negative reals (``float``) and complex numbers with a negative real
+    part (``complex``), each of which stands for the pair ``(p, conj p)``; an entry immediately followed by its exact
+    conjugate is that one pair."""
     ms = d.get("ms", DEFAULT_MS)
     if _is_auto(ms):
-        return "auto"
+        return ms
     ms = list(ms)
-    if any((not np.isreal(p)) or p >= 0 for p in ms):
+    if all(np.isreal(p) for p in ms):
+        if any(p >= 0 for p in ms):
+            raise ValueError("ADI shifts must be negative real numbers")
+        return [float(np.real(p)) for p in ms]
+    out, i = [], 0
+    while i < len(ms):
+        p = complex(ms[i])
+        if not (np.isfinite(p.real) and np.isfinite(p.imag) and p.real < 0):
+            raise ValueError("ADI shifts must be negative real numbers")
+        if p.imag == 0.0:
+            out.append(p.real)
+        else:
+            out.append(p)
+            if i + 1 < len(ms) and complex(ms[i + 1]) == p.conjugate():
+                i += 1
+        i += 1
+    return out
+
+
+def _real_shifts(d):
+    """:func:`_shifts` for the iterations that take real shifts only (Newton-ADI, RADI)."""
+    ms = _shifts(d)
+    if ms == "auto-complex" or (not _is_auto(ms) and _has_pairs(ms)):
         raise ValueError("ADI shifts must be negative real numbers")
-    return [float(p) for p in ms]
+    return ms
 
 
 def _broadcast_shifts(ms):
@@ -170,12 +199,14 @@ def _broadcast_shifts(ms):
     return out
 
 
-def _auto_shifts(ctx, d, W):
+def _auto_shifts(ctx, d, W, keep_complex=False):
     """``ms='auto'``: shifts from the operator of ``ctx`` as it stands (low-rank term included) and the
-    right-hand side factor ``W``; ``adi_dict['num_shifts']`` / ``['shift_warm_steps']``."""
+    right-hand side factor ``W``; ``adi_dict['num_shifts']`` / ``['shift_warm_steps']``.  ``keep_complex``
+    (``ms='auto-complex'``): Ritz values off the real axis stay complex and are selected as pairs."""
     ms = adi_shifts.auto_shifts(ctx, W, num=int(d.get("num_shifts", 8)),
-                                warm_steps=int(d.get("shift_warm_steps", 2)), default=DEFAULT_MS)
-    return _broadcast_shifts(ms)
+                                warm_steps=int(d.get("shift_warm_steps", 2)), default=DEFAULT_MS,
+                                keep_complex=keep_complex)
+    return ms if _has_pairs(ms) else _broadcast_shifts(ms)
 
 
 def solve_proj_lyap_stein(amat=None, mmat=None, jmat=None, wmat=None,
@@ -186,6 +217,11 @@ def solve_proj_lyap_stein(amat=None, mmat=None, jmat=None, wmat=None,
     ``F = amat - umat*vmat``; ``transposed=True`` swaps the roles
     (``F X M^T + M X F^T``).  Signature and ``['zfac']`` return as at
     ``tests/test_units_compfacres_compress.py:62-64``.
+
+    ``adi_dict['ms']`` may hold complex entries with a negative real part: each stands for the conjugate pair
+    ``(p, conj p)`` and is one complex solve and two steps (DESIGN.md 3g; step form, ``umat`` / ``vmat`` included);
+    ``ms='auto-complex'`` generates such a list.  The call then also returns ``['ms']`` (the list as parsed, one
+    entry per pair) and ``['pair_info']`` (``Context.adi_pair_info``).
     """
     d = nwtn_adi_dict if adi_dict is None else adi_dict
     d = {} if d is None else d
@@ -209,8 +245,10 @@ def solve_proj_lyap_stein(amat=None, mmat=None, jmat=None, wmat=None,
             raise ValueError("right-hand side factor wider than {0} columns".format(_lib.MAX_M))
         ms = _shifts(d)
         if _is_auto(ms):
-            ms = _auto_shifts(ctx, d, W)
+            ms = _auto_shifts(ctx, d, W, keep_complex=ms == "auto-complex")
             out["ms"], out["shift_info"] = list(ms), dict(ms.info)
+        elif _has_pairs(ms):
+            out["ms"] = list(ms)          # as parsed: one complex entry per pair
         backend.ensure_exchange(ctx, W.shape[1], len(ms))
         if d.get("device_resident", False):
             # the factor stays in HBM (DeviceFactor): NV x (steps m) doubles need not cross PCIe to form a gain
@@ -267,7 +305,7 @@ def proj_alg_ric_newtonadi(mmat=None, amat=None, jmat=None, bmat=None,
         # throughput of one shift-solve at a time on one GPU.  ``sweep_width=1`` in the
         # dict restores the step-by-step recurrence of the reference.
         prm.sweep_width = 16
-    ms = _shifts(d)
+    ms = _real_shifts(d)
     sinfo = None
     if _is_auto(ms):
         ms = _newton_auto_shifts(ctx, d, calE, bmat, wmat, z0, mtxoldb)
@@ -357,9 +395,9 @@ def proj_alg_ric_radi(mmat=None, amat=None, jmat=None, bmat=None, wmat=None, z0=
     sinfo = None
     if generated:
         fb = d.get("ms_fallback")
-        ms = [adi_shifts.initial_shift(ctx.diag_ratio)] if fb is None else _shifts(dict(ms=list(fb)))
+        ms = [adi_shifts.initial_shift(ctx.diag_ratio)] if fb is None else _real_shifts(dict(ms=list(fb)))
     else:
-        ms = _shifts(d)
+        ms = _real_shifts(d)
         if _is_auto(ms):
             ms = _newton_auto_shifts(ctx, d, calE, bmat, wmat, None, mtxoldb)
             sinfo = dict(ms.info)

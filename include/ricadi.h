@@ -369,13 +369,30 @@ int ricadi_adi_res_launches(ricadi_ctx* ctx, int64_t* n_out);
  *   Frobenius norms of the two blocks, summed in a fixed order.
  * ricadi_adi_pair_info:  of the last ricadi_lyap_adi_cplx call: [pair entries solved, lockstep iterations of their
  *   complex GMRES (per solve the slowest group's, refinement included), Woodbury refinement passes, complex solves
- *   that missed their tolerance].  All zero after a call without pairs.                                           */
+ *   that missed their tolerance].  All zero after a call without pairs.
+ * ricadi_adi_pair_solve_dev (ABI 414, for tests):  the complex solve of ONE pair entry at p = ar + i ai, as the driver
+ *   runs it on the context's operator and low-rank term (width q): the proxy shift's setup, [W, U] packed into ng groups
+ *   of mc complex columns ((ng, mc) of m + q columns), the lockstep solve, with q > 0 the Sherman-Morrison-Woodbury
+ *   correction and -- a column's true residual above 10 gmres_tol -- its one refinement pass.  No projection of W, no
+ *   blocks kernel, no update of W or Z, no stopping bookkeeping; ricadi_adi_pair_info keeps what it held.  dW: NV x m
+ *   (device, read only).  what_mask: 1  dRhs (ng groups of NV x mc complex, 16-byte aligned) <- the packed right-hand
+ *   sides, written by the pack kernel itself;  2  dRaw (2 ng groups of n x mc complex, n = NV + NP) <- with q > 0 the
+ *   groups as first solved, before any correction, and behind them, where the refinement ran, its uncorrected D;
+ *   4  dX (ng groups of n x mc complex) <- the final groups;  8  stop behind the pack (no solve).  A pointer whose bit
+ *   is not set may be NULL.  report[8] (host): ng, mc, lockstep iterations, refinement ran (0 / 1), the largest true
+ *   relative residual of W's columns before the refinement, the same after it (equal where it did not run), converged
+ *   (0 / 1: after <= 10 gmres_tol with q > 0, every column at gmres_tol with q = 0), the smallest pivot modulus of the
+ *   capacitance LU over max |cap_ij| (NaN with q = 0).  RICADI_EINVAL as ricadi_adi_pair_blocks_dev, m + q > 128, an
+ *   exchange: the outputs stay untouched.  A numerically singular capacitance matrix is RICADI_EHIP with report[0 .. 2]
+ *   and report[7] filled.                                                                                          */
 int ricadi_lyap_adi_cplx(ricadi_ctx* ctx, const double* shifts_re, const double* shifts_im, int nshifts,
                          const double* W, int m, const ricadi_adi_params* prm, double* Z_out, int* c_out,
                          double* stats_out);
 int ricadi_adi_pair_blocks_dev(ricadi_ctx* ctx, int ng, int mc, int m, double ar, double ai, const double* dX,
                                double* dZ, int ldz, int zc, double* dV1, double* norms2_out);
 int ricadi_adi_pair_info(ricadi_ctx* ctx, int64_t out[4]);
+int ricadi_adi_pair_solve_dev(ricadi_ctx* ctx, double ar, double ai, const double* dW, int m, int what_mask,
+                              double* dRaw, double* dX, double* dRhs, double* report);
 
 /* ---- a1: Newton-Kleinman ADI for the projected Riccati equation -------
  * pru.proj_alg_ric_newtonadi (/root/reference/optcont_main.py:488-492,

@@ -25,7 +25,7 @@ MAX_M = 128
 MAX_UPD_COLS = 4096                                                     # ricadi_diff_zzt_fnorm_dev: k1 + k0
 # ricadi_version() this mirror was written for: the stats arrays' lengths and the meaning of their slots
 # are part of the ABI and are not covered by the struct handshake below
-ABI_VERSION = 413
+ABI_VERSION = 414
 
 
 class RicadiOpts(C.Structure):
@@ -85,6 +85,7 @@ SIGNATURES = {
     "ricadi_adi_pair_blocks_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp, _vp,
                                              C.c_int, C.c_int, _vp, _dp]),
     "ricadi_adi_pair_info": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "ricadi_adi_pair_solve_dev": (C.c_int, [_vp, C.c_double, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _dp]),
     "ricadi_ric_newtonadi": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp,
                                        C.c_int, _dp, C.POINTER(RicadiAdiParams), _dp, C.c_int,
                                        C.POINTER(C.c_int), _dp]),
@@ -699,6 +700,29 @@ class Context:
         p = complex(p)
         _chk(self._lib.ricadi_adi_pair_blocks_dev(self._h, int(ng), int(mc), int(m), p.real, p.imag, x_ptr, z_ptr,
                                                   int(ldz), int(zc), v1_ptr, _d(out)))
+        return out
+
+    PAIR_SOLVE_RHS, PAIR_SOLVE_RAW, PAIR_SOLVE_X, PAIR_SOLVE_PACK_ONLY = 1, 2, 4, 8
+    PAIR_SOLVE_REPORT = ("ng", "mc", "iters", "refined", "worst_before", "worst_after", "converged", "min_pivot_rel")
+
+    def adi_pair_solve_dev(self, p, w_ptr, m, what_mask=0, raw_ptr=None, x_ptr=None, rhs_ptr=None):
+        """``ricadi_adi_pair_solve_dev``: the complex solve of one pair entry at ``p`` for the device panel ``W``
+        (``nv x m``), as the driver runs it, with the outputs ``what_mask`` asks for (``PAIR_SOLVE_*``) copied to the
+        device buffers.  Returns the report as a dict (``PAIR_SOLVE_REPORT``); when the call fails the report filled so
+        far is ``self.pair_solve_report`` (``None`` after a refusal, which writes nothing)."""
+        rep = np.full(8, -1.0)
+        p = complex(p)
+        self.pair_solve_report = None
+        rc = self._lib.ricadi_adi_pair_solve_dev(self._h, p.real, p.imag, w_ptr, int(m), int(what_mask), raw_ptr, x_ptr,
+                                                 rhs_ptr, _d(rep))
+        out = dict(zip(self.PAIR_SOLVE_REPORT, rep.tolist()))
+        for k in ("ng", "mc", "iters"):
+            out[k] = int(out[k])
+        for k in ("refined", "converged"):
+            out[k] = bool(out[k])
+        if rc != 0 and rep[0] >= 0:
+            self.pair_solve_report = out
+        _chk(rc)
         return out
 
     def ric_newtonadi(self, shifts, B, W, prm, Z0=None, oldB=None, fetch=True, upd_hist=False):

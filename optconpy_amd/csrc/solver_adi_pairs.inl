@@ -11,58 +11,9 @@
 #include <complex>
 #include <cstdint>
 
+#include "pair_smw.h"              // the host arithmetic of PairSolve: grouping, index map, capacitance LU, embedding
+
 namespace {
-
-using cdbl = std::complex<double>;
-
-// LU with partial pivoting of the q x q matrix `a` (row-major) in place; false: a pivot below 1e-13 max |a_ij|
-bool pair_lu(std::vector<cdbl>& a, std::vector<int>& piv, int q) {
-  double scale = 0.0;
-  for (const cdbl& v : a) scale = std::max(scale, std::abs(v));
-  piv.assign(q, 0);
-  for (int k = 0; k < q; ++k) {
-    int pk = k;
-    for (int i = k + 1; i < q; ++i)
-      if (std::abs(a[(size_t)i * q + k]) > std::abs(a[(size_t)pk * q + k])) pk = i;
-    piv[k] = pk;
-    if (pk != k)
-      for (int j = 0; j < q; ++j) std::swap(a[(size_t)k * q + j], a[(size_t)pk * q + j]);
-    const cdbl d = a[(size_t)k * q + k];
-    if (!(std::abs(d) >= 1e-13 * scale) || scale == 0.0) return false;
-    for (int i = k + 1; i < q; ++i) {
-      const cdbl f = a[(size_t)i * q + k] / d;
-      a[(size_t)i * q + k] = f;
-      for (int j = k + 1; j < q; ++j) a[(size_t)i * q + j] -= f * a[(size_t)k * q + j];
-    }
-  }
-  return true;
-}
-// y (q x w, row-major) <- a^-1 y with the factors of pair_lu
-void pair_lu_solve(const std::vector<cdbl>& a, const std::vector<int>& piv, int q, std::vector<cdbl>& y, int w) {
-  for (int k = 0; k < q; ++k)
-    if (piv[k] != k)
-      for (int j = 0; j < w; ++j) std::swap(y[(size_t)k * w + j], y[(size_t)piv[k] * w + j]);
-  for (int k = 0; k < q; ++k)
-    for (int i = k + 1; i < q; ++i)
-      for (int j = 0; j < w; ++j) y[(size_t)i * w + j] -= a[(size_t)i * q + k] * y[(size_t)k * w + j];
-  for (int k = q - 1; k >= 0; --k)
-    for (int j = 0; j < w; ++j) {
-      cdbl sacc = y[(size_t)k * w + j];
-      for (int l = k + 1; l < q; ++l) sacc -= a[(size_t)k * q + l] * y[(size_t)l * w + j];
-      y[(size_t)k * w + j] = sacc / a[(size_t)k * q + k];
-    }
-}
-
-// The scalars of a pair step
-struct PairCoefs {
-  double delta, gam, gam2;
-  PairCoefs(double a, double b) {
-    delta = a / b;
-    gam = 2.0 * std::sqrt(-a);
-    const double d2 = delta * delta;
-    gam2 = gam * std::sqrt(d2 + 1.0);
-  }
-};
 
 // The complex solve of a pair step on the operator of the context, low-rank term included:
 //   (S(p) - [U; 0] [V; 0]^T) [X; *] = [W; 0]
@@ -73,7 +24,9 @@ struct PairCoefs {
 // columns -- complex product plus low-rank term -- decides on ONE refinement pass (a column above 10 gmres_tol).
 struct PairSolve {
   ricadi_ctx* const c;
-  const int m, q, mp, ng, mc, m2, n, nv;
+  const int m, q, mp;
+  const PairGroups pg;            // the grouping of the mp columns and the index map (pair_smw.h)
+  const int ng, mc, m2, n, nv;
   const size_t gs, gsr;           // group strides of the solution panels (n rows) and of the packed right-hand sides (nv)
   const GroupTab all;
   CplxCoefs cf{};
@@ -83,15 +36,20 @@ struct PairSolve {
   bool converged = true;          // of the last solve: every column of W met its bar
   double worst = 0.0;             // ... the largest true relative residual
   int iters = 0;                  // ... lockstep iterations (the slowest group's), refinement included
+  // for ricadi_adi_pair_solve_dev (the driver reads none of them): whether the refinement pass ran, the largest
+  // residual before it (`worst` is the one after it), the smallest pivot of the capacitance LU over max |cap_ij|, and
+  // where to copy the groups as first solved -- ng gs doubles, the refinement's uncorrected D behind them
+  bool refined = false;
+  double worst_before = 0.0, min_pivot_rel = NAN;
+  double* raw_out = nullptr;
 
-  static int groups_of(int mp) { return (mp + 7) / 8; }
   PairSolve(ricadi_ctx* ctx, int m_)
-      : c(ctx), m(m_), q(std::max(ctx->q, 0)), mp(m_ + q), ng(groups_of(mp)), mc((mp + ng - 1) / ng), m2(2 * mc),
+      : c(ctx), m(m_), q(std::max(ctx->q, 0)), mp(m_ + q), pg(mp), ng(pg.ng), mc(pg.mc), m2(2 * mc),
         n(ctx->n), nv(ctx->nv), gs((size_t)ctx->n * m2), gsr((size_t)ctx->nv * m2), all(all_groups(ng)) {
     c->pair_rhs.ensure(gsr * ng);
     c->pair_x.ensure(gs * ng);
     if (q > 0) {
-      c->pair_rhs2.ensure(gsr * ng);
+      c->pair_rhs2.ensure(gs * ng);
       c->pair_d.ensure(gs * ng);
       c->pair_xu.ensure((size_t)n * 2 * q);
       c->pair_t.ensure((size_t)ng * q * m2);
@@ -109,22 +67,16 @@ struct PairSolve {
     HIPCHK(hipMemcpyAsync(ht.data(), c->pair_t.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
-  cdbl t_at(int k, int j) const {   // (V^T D)[k][column j of the step's panel]
-    const double* t = ht.data() + ((size_t)(j / mc) * q + k) * m2 + 2 * (j % mc);
-    return cdbl(t[0], t[1]);
-  }
 
   // capacitance I - V^T X_U from the solutions in pair_x, factorised; X_U as one complex panel (n x q) in pair_xu
   void capacitance() {
     hipStream_t st = c->st;
     vt(c->pair_x.p);
-    cap.assign((size_t)q * q, cdbl(0.0, 0.0));
-    for (int k = 0; k < q; ++k)
-      for (int l = 0; l < q; ++l) cap[(size_t)k * q + l] = (k == l ? 1.0 : 0.0) - t_at(k, m + l);
-    if (!pair_lu(cap, piv, q))
+    pair_capacitance(ht.data(), pg, m, q, cap);
+    if (!pair_lu(cap, piv, q, &min_pivot_rel))
       throw HipError{"ADI pair step: the capacitance matrix I - V^T S(p)^-1 U of the low-rank term is numerically singular"};
     for (int g = 0; g < ng; ++g) {
-      const int j0 = std::max(m, g * mc), j1 = std::min(mp, (g + 1) * mc);
+      const auto [j0, j1] = pg.u_range(g, m, mp);
       if (j0 < j1)
         launch_copy_cols(st, n, 2 * (j1 - j0), c->pair_x.p + g * gs, m2, 2 * (j0 - g * mc), c->pair_xu.p, 2 * q,
                          2 * (j0 - m), 1.0);
@@ -135,21 +87,9 @@ struct PairSolve {
   void woodbury(double* D) {
     hipStream_t st = c->st;
     vt(D);
-    y.assign((size_t)q * m, cdbl(0.0, 0.0));
-    for (int k = 0; k < q; ++k)
-      for (int j = 0; j < m; ++j) y[(size_t)k * m + j] = t_at(k, j);
+    pair_vtw(ht.data(), pg, m, q, y);
     pair_lu_solve(cap, piv, q, y, m);
-    // complex y (q x m) as the real 2q x m2 matrix of every group: [[re, im], [-im, re]] per entry
-    hm.assign((size_t)ng * 2 * q * m2, 0.0);
-    for (int k = 0; k < q; ++k)
-      for (int j = 0; j < m; ++j) {
-        const cdbl v = y[(size_t)k * m + j];
-        double* g0 = hm.data() + (size_t)(j / mc) * 2 * q * m2 + 2 * (j % mc);
-        g0[(size_t)(2 * k) * m2] = v.real();
-        g0[(size_t)(2 * k) * m2 + 1] = v.imag();
-        g0[(size_t)(2 * k + 1) * m2] = -v.imag();
-        g0[(size_t)(2 * k + 1) * m2 + 1] = v.real();
-      }
+    pair_embed(y, pg, m, q, hm);     // complex y (q x m) as the real 2q x m2 matrix of every group
     HIPCHK(hipMemcpyAsync(c->pair_m.p, hm.data(), sizeof(double) * hm.size(), hipMemcpyHostToDevice, st));
     launch_gemm_nn_bp(st, all, n, 2 * q, m2, same_ptr((const double*)c->pair_xu.p), 2 * q, c->pair_m.p, m2,
                       (size_t)2 * q * m2, D, m2, gs, 1.0, 1.0);
@@ -180,7 +120,8 @@ struct PairSolve {
     norms2(k.r.p, n, gs);
     double w = 0.0;
     for (int j = 0; j < m; ++j) {
-      const double b2 = bn2[(size_t)(j / mc) * 16 + 2 * (j % mc)], r2 = h16[(size_t)(j / mc) * 16 + 2 * (j % mc)];
+      const size_t at = (size_t)pg.group_of(j) * 16 + 2 * pg.col_of(j);
+      const double b2 = bn2[at], r2 = h16[at];
       const double rr = b2 > 0.0 ? std::sqrt(r2 / b2) : 0.0;
       w = std::isfinite(rr) ? std::max(w, rr) : INFINITY;
     }
@@ -199,35 +140,44 @@ struct PairSolve {
     launch_adi_pair_pack(st, nv, m, q, ng, mc, dW, q > 0 ? c->U.p : nullptr, c->pair_rhs.p, gsr);
     const CplxResult r = cplx_solve(c, ng, cf, c->pair_rhs.p, gsr, mc, c->pair_x.p);
     iters = *std::max_element(r.iters.begin(), r.iters.end());
+    refined = false;
     if (q == 0) {
       converged = r.converged;
       worst = 0.0;
-      for (int j = 0; j < m; ++j) worst = std::max(worst, r.relres[(size_t)(j / mc) * mc + j % mc]);
+      for (int j = 0; j < m; ++j) worst = std::max(worst, r.relres[(size_t)pg.group_of(j) * mc + pg.col_of(j)]);
+      worst_before = worst;
       return;
     }
+    if (raw_out) HIPCHK(hipMemcpyAsync(raw_out, c->pair_x.p, sizeof(double) * gs * ng, hipMemcpyDeviceToDevice, st));
     norms2(c->pair_rhs.p, nv, gsr);
     bn2 = h16;
     capacitance();
     woodbury(c->pair_x.p);
-    worst = residual();
+    worst = worst_before = residual();
     if (worst > 10.0 * tol) {
+      refined = true;
       // one pass on the residual equation: S(p) D = r for the columns of W (those of U are zeroed), corrected alike
       ++c->pair_info[2];
       ricadi_ctx::CplxWork& k = c->cw;
+      // The right-hand side is the whole residual, pressure rows included: J (X_W + X_U y) carries the solves'
+      // pressure residuals times the same y as the velocity rows do, and a pass on the velocity rows alone leaves
+      // that share where it is.
+      HIPCHK(hipMemcpyAsync(c->pair_rhs2.p, k.r.p, sizeof(double) * gs * ng, hipMemcpyDeviceToDevice, st));
       for (int g = 0; g < ng; ++g) {
-        double* rg = c->pair_rhs2.p + g * gsr;
-        HIPCHK(hipMemcpyAsync(rg, k.r.p + g * gs, sizeof(double) * gsr, hipMemcpyDeviceToDevice, st));
-        const int c0 = std::min(mc, std::max(0, m - g * mc));
+        const int c0 = pg.w_cols(g, m);
         if (c0 < mc)
-          HIPCHK(hipMemset2DAsync(rg + 2 * c0, sizeof(double) * m2, 0, sizeof(double) * 2 * (mc - c0), nv, st));
+          HIPCHK(hipMemset2DAsync(c->pair_rhs2.p + g * gs + 2 * c0, sizeof(double) * m2, 0,
+                                  sizeof(double) * 2 * (mc - c0), n, st));
       }
       CplxResult r2;
       {
         Restore<double> keep_tol(c->opts.gmres_tol);
         c->opts.gmres_tol = std::min(0.5, std::max(1e-14, 0.5 * tol / worst));
-        r2 = cplx_solve(c, ng, cf, c->pair_rhs2.p, gsr, mc, c->pair_d.p);
+        r2 = cplx_solve(c, ng, cf, c->pair_rhs2.p, gs, mc, c->pair_d.p, n);
       }
       iters += *std::max_element(r2.iters.begin(), r2.iters.end());
+      if (raw_out)
+        HIPCHK(hipMemcpyAsync(raw_out + gs * ng, c->pair_d.p, sizeof(double) * gs * ng, hipMemcpyDeviceToDevice, st));
       woodbury(c->pair_d.p);
       launch_cplx_axpby(st, all, gs, m2, 1.0, c->pair_x.p, gs, 1.0, nullptr, c->pair_d.p, gs, c->pair_x.p, gs);
       worst = residual();
@@ -393,6 +343,59 @@ int ricadi_adi_pair_blocks_dev(ricadi_ctx* c, int ng, int mc, int m, double ar, 
                          c->pair_part.p, c->pair_nrm.p);
   HIPCHK(hipMemcpyAsync(norms2_out, c->pair_nrm.p, sizeof(double) * 2, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
+  API_END
+}
+
+int ricadi_adi_pair_solve_dev(ricadi_ctx* c, double ar, double ai, const double* dW, int m, int what_mask, double* dRaw,
+                              double* dX, double* dRhs, double* report) {
+  REQUIRE(c && c->has_op, RICADI_ESTATE, "set the operator first");
+  REQUIRE(std::isfinite(ar) && std::isfinite(ai) && ar < 0.0 && ai != 0.0, RICADI_EINVAL,
+          "a pair needs a finite shift with Re < 0 and Im != 0");
+  REQUIRE(dW && report, RICADI_EINVAL, "NULL argument");
+  REQUIRE(m >= 1 && m + std::max(c->q, 0) <= RICADI_MAX_M, RICADI_EINVAL,
+          "pair solve: m >= 1 and panel width plus low-rank width at most 128 required");
+  REQUIRE(what_mask >= 0 && what_mask < 16, RICADI_EINVAL, "what_mask has four bits");
+  REQUIRE(!(what_mask & 1) || (dRhs && ((uintptr_t)dRhs & 15) == 0), RICADI_EINVAL, "dRhs must be 16-byte aligned");
+  REQUIRE(!(what_mask & 2) || dRaw, RICADI_EINVAL, "NULL dRaw");
+  REQUIRE(!(what_mask & 4) || dX, RICADI_EINVAL, "NULL dX");
+  REQUIRE(!sharded(c), RICADI_EINVAL, "complex shift pairs are not taken on a context with an exchange (ricadi_set_exchange)");
+  API_BEGIN_ON(c)
+  hipStream_t st = c->st;
+  int64_t keep_info[4];
+  std::copy(c->pair_info, c->pair_info + 4, keep_info);
+  ensure_work(c, m);
+  PairSolve ps(c, m);
+  std::fill(report, report + 8, 0.0);
+  report[0] = ps.ng;
+  report[1] = ps.mc;
+  report[7] = NAN;
+  // the pack kernel straight into the caller's groups: what it writes beside them shows there
+  if (what_mask & 1)
+    launch_adi_pair_pack(st, ps.nv, m, ps.q, ps.ng, ps.mc, dW, ps.q > 0 ? c->U.p : nullptr, dRhs, ps.gsr);
+  if (!(what_mask & 8)) {
+    const double proxy = cplx_proxy(ar, ai);
+    setup_and_project(c, &proxy, 1, false, nullptr, m);
+    if ((what_mask & 2) && ps.q > 0) ps.raw_out = dRaw;
+    try {
+      ps.solve(ar, ai, dW);
+    } catch (...) {
+      std::copy(keep_info, keep_info + 4, c->pair_info);
+      report[2] = ps.iters;
+      report[7] = ps.min_pivot_rel;
+      (void)hipStreamSynchronize(st);
+      throw;
+    }
+    std::copy(keep_info, keep_info + 4, c->pair_info);
+    report[2] = ps.iters;
+    report[3] = ps.refined ? 1.0 : 0.0;
+    report[4] = ps.worst_before;
+    report[5] = ps.worst;
+    report[6] = ps.converged ? 1.0 : 0.0;
+    report[7] = ps.min_pivot_rel;
+    if (what_mask & 4)
+      HIPCHK(hipMemcpyAsync(dX, c->pair_x.p, sizeof(double) * ps.gs * ps.ng, hipMemcpyDeviceToDevice, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
   API_END
 }
 

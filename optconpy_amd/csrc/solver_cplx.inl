@@ -167,10 +167,14 @@ void cplx_cycle_end_launches(ricadi_ctx* c, const CplxCycle& cy, const GroupTab&
 }
 
 // S(alpha_g, beta_g) X_g = [R_g; 0] for ng groups in lockstep: flexible GMRES(restart) from zero, Z_j kept in FP64.
-CplxResult cplx_solve(ricadi_ctx* c, int ng, const CplxCoefs& cf, const double* dR, size_t gsr, int mc, double* dX) {
+// R_g has rhs_rows rows (default: the nv velocity rows; n for a right-hand side with a pressure part, as the residual
+// equation of the pair step's refinement has).
+CplxResult cplx_solve(ricadi_ctx* c, int ng, const CplxCoefs& cf, const double* dR, size_t gsr, int mc, double* dX,
+                      int rhs_rows = -1) {
   hipStream_t st = c->st;
   const int m2 = 2 * mc, n = c->n, restart = c->opts.gmres_restart, maxit = c->opts.gmres_maxit;
   const double tol = c->opts.gmres_tol;
+  const size_t rows = rhs_rows < 0 ? (size_t)c->nv : (size_t)rhs_rows;
   CplxPrecond pc(c, ng, cf, m2);
   cplx_ensure_work(c, ng, restart + 1, true);
   c->cprobe = ricadi_ctx::CplxProbe();   // the workspace of a probe cycle in flight is the solve's now
@@ -182,7 +186,7 @@ CplxResult cplx_solve(ricadi_ctx* c, int ng, const CplxCoefs& cf, const double* 
   // b_g = [R_g; 0], x_g = 0, r_g = b_g
   HIPCHK(hipMemsetAsync(k.b.p, 0, sizeof(double) * gs * ng, st));
   for (int g = 0; g < ng; ++g)
-    HIPCHK(hipMemcpyAsync(k.b.p + g * gs, dR + g * gsr, sizeof(double) * c->nv * m2, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(k.b.p + g * gs, dR + g * gsr, sizeof(double) * rows * m2, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemsetAsync(dX, 0, sizeof(double) * gs * ng, st));
   HIPCHK(hipMemcpyAsync(k.r.p, k.b.p, sizeof(double) * gs * ng, hipMemcpyDeviceToDevice, st));
   std::vector<double> h16((size_t)ng * 16), h8((size_t)ng * 8), bn((size_t)ng * 8, 0.0);

@@ -237,3 +237,173 @@ def test_twin_matches_the_model_step():
     Z1, Z2, V1, n2 = apm.blocks_twin(X, mdl.nv, m, p)
     assert np.array_equal(np.hstack([Z1, Z2]), out["Z"])
     assert np.allclose(n2, [np.sum(Z1 ** 2), np.sum(Z2 ** 2)], rtol=1e-15)
+
+
+# ------------------------------------------------------------------------------------------------ the Woodbury solve
+# what tests/test_gpu_adi_pair_solve.py rests on
+LADDER_OPS = ("unsym", "nv33_np1", "nv65_np24", "fe3")
+LADDER_DELTAS = (1e-1, 1e-2, 1e-3)
+LADDER_TOL, LADDER_ETA, LADDER_Q, LADDER_M = 1e-8, 1e-3, 3, (3, 9)
+FIRST_BLOCK_TOL = 0.266
+
+
+def ladder_of(name):
+    """(operator, p, [(delta, U2, V)]) of the refinement ladder on ``name``: ``a = -sqrt(min max |lambda|)`` of the
+    operator's projected pencil."""
+    op, mdl, _ = model_of(name, False)
+    lam = np.abs(mdl.pencil_eigs())
+    lam = lam[np.isfinite(lam)]
+    a = -float(np.sqrt(lam.min() * lam.max()))
+    p, rungs = apm.refinement_ladder(op, a, LADDER_ETA, LADDER_DELTAS, LADDER_Q, seed=130)
+    return op, p, rungs
+
+
+def ladder_rhs(op, m):
+    return np.random.default_rng(200 + m).standard_normal((op.nv, m))
+
+
+def first_block_list(name="fe3"):
+    op, mdl, ms = model_of(name, False)
+    return op, mdl, [complex(ms[0].real, 20.0 * ms[0].imag)]
+
+
+def steps_pinned(ref, tol):
+    """Whether the model's stopping step is safe from rounding: of the entry that stopped the run (both blocks of a
+    pair) the smallest ``rel_newZ`` lies a factor 2 below ``tol``, and the entry before it a factor 2 above."""
+    r = ref["rel_newZ"]
+    if ref["rule"] != "newZ":
+        return False
+    k = 2 if (len(r) >= 2 and ref["last_is_pair"]) else 1
+    return bool(r[-k:].min() <= tol / 2 and (len(r) == k or r[-k - 1] >= 2 * tol))
+
+
+def _random_groups(m, q, nv, n, seed):
+    rng = np.random.default_rng(seed)
+    ng, mc = apm.groups(m + q)
+    X = rng.standard_normal((ng, n, mc)) + 1j * rng.standard_normal((ng, n, mc))
+    for j in range(m + q, ng * mc):
+        X[j // mc, :, j % mc] = 0.0
+    V = 0.2 * rng.standard_normal((nv, q))
+    return X, V
+
+
+@pytest.fixture(scope="module")
+def smw_probe(tmp_path_factory):
+    import test_pair_smw_cpu as tps
+    return tps._build(tmp_path_factory.mktemp("pair_smw_twin"), [])
+
+
+@pytest.mark.parametrize("m,q", [s for s in apm.PAIR_SOLVE_SHAPES if s[1] > 0])
+def test_woodbury_bound_holds_a_second_evaluation_and_sees_the_faults(smw_probe, m, q):
+    """A second float64 evaluation of the twin -- rows in reversed order, the header's LU and embedding through the
+    probe -- stays at or below 0.5 of ``woodbury_bound``; every seeded fault that applies at the shape exceeds 1."""
+    nv, n = 37, 45
+    X, V = _random_groups(m, q, nv, n, 10 * m + q)
+    ng, mc = apm.groups(m + q)
+    ref = apm.woodbury_twin(X, V, m, q)
+    bound = apm.woodbury_bound(X, V, m, q)
+    at = apm._maps(m, q)
+    wcols = np.zeros((ng, n, mc), dtype=bool)
+    for g, cc in at[:m]:
+        wcols[g, :, cc] = True
+    assert np.all(bound[wcols] > 0) and np.all(bound[~wcols] == 0)
+    assert np.array_equal(ref[~wcols], X[~wcols])
+    # second evaluation: V^T X with the rows reversed, then the header
+    T = np.einsum("vk,gvc->gkc", V[::-1], X[:, :nv][:, ::-1])
+    ht = np.zeros((ng, q, 2 * mc))
+    ht[:, :, 0::2], ht[:, :, 1::2] = T.real, T.imag
+    cap, ok, low, y, hm = smw_probe.smw(m, q, ht)
+    assert ok
+    XU = np.stack([X[g, :, cc] for g, cc in at[m:]], axis=1)
+    xr = np.ascontiguousarray(XU).view(np.float64)
+    second = X.copy()
+    for g in range(ng):
+        second[g] += np.ascontiguousarray(xr[::-1] @ hm[g]).view(np.complex128)[::-1]
+    ratio = float(np.max(np.abs(second - ref)[wcols] / bound[wcols]))
+    print("[pair solve] model m %d q %d | second evaluation / bound | %.3e | 0.5" % (m, q, ratio))
+    assert ratio <= 0.5 and np.array_equal(second[~wcols], X[~wcols])
+    for fault in apm.WOODBURY_FAULTS:
+        if not apm.fault_applies(fault, m, q, n, nv):
+            continue
+        bad = apm.woodbury_twin(X, V, m, q, fault=fault)
+        d = np.abs(bad - ref)
+        worst = float(np.max(np.where(bound > 0, d / np.where(bound > 0, bound, 1.0), np.where(d > 0, np.inf, 0.0))))
+        print("[pair solve] model m %d q %d | fault %s / bound | %.3e | > 1" % (m, q, fault, worst))
+        assert worst > 1.0, (fault, m, q)
+    # the two-pass twin: a second evaluation holds, the uncorrected D does not
+    D = 1e-6 * _random_groups(m, q, nv, n, 77)[0]
+    for g, cc in at[m:]:
+        D[g, :, cc] = 0.0
+    ref2, bound2 = apm.woodbury_twin(X, V, m, q, Draw=D), apm.woodbury_bound(X, V, m, q, Draw=D)
+    rev = apm.woodbury_twin(X[:, ::-1][:, list(range(n - nv, n)) + list(range(n - nv))], V[::-1], m, q,
+                            Draw=D[:, ::-1][:, list(range(n - nv, n)) + list(range(n - nv))])
+    back = rev[:, list(range(nv, n)) + list(range(nv))][:, ::-1]
+    assert float(np.max(np.abs(back - ref2)[wcols] / bound2[wcols])) <= 0.5
+    bad = apm.woodbury_twin(X, V, m, q, fault="refine_raw", Draw=D)
+    assert float(np.max(np.abs(bad - ref2)[wcols] / bound2[wcols])) > 1.0
+    which = [s for s in apm.PAIR_SOLVE_SHAPES if apm.fault_applies("straddle", *s)]
+    assert which == [(5, 6), (2, 16)]
+    which = [s for s in apm.PAIR_SOLVE_SHAPES if apm.fault_applies("group_of_m", *s)]
+    assert which == [(5, 6), (2, 16), (17, 7)]
+
+
+@pytest.mark.parametrize("name", LOWRANK)
+def test_no_refinement_is_due_on_the_lowrank_operators(name):
+    """The model's amplification stays at or below 8 along the whole run on every LOWRANK operator (9 is where a
+    column could reach 10 tol): the driver test asserts ``pair_info[2] == 0`` on all of them, none is exempt."""
+    op, mdl, ms = model_of(name, True)
+    out = mdl.run(ms, op.W, max_steps=300, newZ_reltol=1e-12, woodbury=True)
+    a = out["amplification"]
+    print("[adi pairs] %s | amplification: first %.2f, largest %.2f at pair %d of %d" %
+          (name, a[0], a.max(), int(a.argmax()), a.size))
+    assert a.size == out["pairs"] and a.max() <= 8.0
+
+
+@pytest.mark.parametrize("name", LADDER_OPS)
+def test_the_ladder_makes_the_refinement_due(name):
+    """At delta = 1e-3 the model's amplification is at least 100 on every column (the solves' residuals, at most tol,
+    then exceed 10 tol unless they are a factor 10 better than asked) and the closed-loop reference is good to
+    tol / 100; the imaginary part of the capacitance matrix stays below its delta real part."""
+    op, p, rungs = ladder_of(name)
+    assert p.real < 0 < p.imag and abs(p.imag / p.real + LADDER_ETA) < 1e-15
+    for delta, U2, V in rungs:
+        mdl = apm.PairsModel(*op.ops, U=U2, V=V)
+        for m in LADDER_M:
+            W = ladder_rhs(op, m)
+            amp = apm.amplification(mdl, p, W)
+            S = mdl.saddle(mdl.A, p)
+            x = mdl._solve(S, W)
+            rhs = np.zeros_like(x)
+            rhs[:op.nv] = W
+            rr = float(np.max(np.linalg.norm(S @ x - rhs, axis=0) / np.linalg.norm(W, axis=0)))
+            XU = mdl._solve(mdl.saddle(mdl.A0, p), U2)[:op.nv]
+            cap = np.eye(LADDER_Q) - V.T @ XU
+            smin = float(np.linalg.svd(cap, compute_uv=False)[-1])
+            print("[pair solve] ladder %s delta %g m %d | min amplification %.3g | reference residual %.2e | "
+                  "sigma_min(cap) %.2e | max |Im cap| %.2e" % (name, delta, m, amp.min(), rr, smin,
+                                                               np.abs(cap.imag).max()))
+            assert rr <= LADDER_TOL / 100
+            assert np.allclose(cap.real, delta * np.eye(LADDER_Q), atol=1e-9) and smin >= delta / 2
+            if delta == 1e-3:
+                assert amp.min() >= 100.0
+
+
+def test_a_rule_that_fires_on_the_first_block_only_model():
+    """fe3 with the first recipe pair's imaginary part times 20 and ``adi_newZ_reltol = 0.266``: the model's relative
+    block norms are 1.0, 0.99 and 0.101, 0.701 -- the rule fires on the second pair's first block alone, a factor 2.6
+    from the tolerance on either side --, and both blocks are kept."""
+    op, mdl, lst = first_block_list()
+    out = mdl.run(lst, op.W, max_steps=300, newZ_reltol=FIRST_BLOCK_TOL)
+    r = out["rel_newZ"]
+    print("[adi pairs] fe3 | first-block rule | rel_newZ %s" % r)
+    assert (out["steps"], out["pairs"], out["rule"]) == (4, 2, "newZ") and out["Z"].shape[1] == 4 * op.W.shape[1]
+    assert np.allclose(r, [1.0, 0.99, 0.101, 0.701], rtol=0.05)
+    assert r[2] < FIRST_BLOCK_TOL / 2 and r[3] > 2 * FIRST_BLOCK_TOL
+
+
+def test_signature_of_the_pair_solve_entry():
+    hdr = open(os.path.join(ROOT, "include", "ricadi.h")).read()
+    res, args = _lib.SIGNATURES["ricadi_adi_pair_solve_dev"]
+    decl = re.search(r"\bint\s+ricadi_adi_pair_solve_dev\s*\(([^;]*)\)\s*;", hdr)
+    assert decl is not None and len(decl.group(1).split(",")) == len(args) == 10
+    assert len(_lib.Context.PAIR_SOLVE_REPORT) == 8

@@ -15,7 +15,8 @@ import adi_pairs_model as apm
 import small_ops as so
 from optconpy_amd import _lib
 from optconpy_amd import proj_ric_utils as pru
-from test_adi_pairs_cpu import KERNEL_M, KERNEL_NV, KERNEL_P, LOWRANK, PLAIN, model_of
+from test_adi_pairs_cpu import (FIRST_BLOCK_TOL, KERNEL_M, KERNEL_NV, KERNEL_P, LOWRANK, PLAIN, first_block_list, model_of,
+                                steps_pinned)
 
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(np.float64).eps
@@ -152,7 +153,10 @@ def _driver_case(name, lowrank, W=None, tag=""):
           (who, info["adi_steps"], ref["steps"], info["shift_solves"], info.get("pair_info"), info["adi_stopped_by"]))
     ok = _say(who, "Z Z^T vs dense", so.rel(Z @ Z.T, X), LYAP_TOL)
     assert ok
-    assert abs(info["adi_steps"] - ref["steps"]) <= 2, (info["adi_steps"], ref["steps"])
+    # the model's step count exactly where its stopping step is a factor 2 clear of the tolerance on both sides
+    pinned = steps_pinned(ref, TIGHT["adi_newZ_reltol"])
+    print("[adi pairs] %s | step count held to the model's %s" % (who, "exactly" if pinned else "+- 2"))
+    assert abs(info["adi_steps"] - ref["steps"]) <= (0 if pinned else 2), (info["adi_steps"], ref["steps"])
     assert info["cols"] == info["adi_steps"] * m == Z.shape[1]
     assert info["gmres_nonconverged"] == 0
     if any(isinstance(p, complex) for p in ms):
@@ -160,6 +164,16 @@ def _driver_case(name, lowrank, W=None, tag=""):
         assert info["pair_info"][0] == pairs and info["pair_info"][3] == 0
         assert info["shift_solves"] == info["adi_steps"] - pairs
         assert info["pair_info"][1] >= pairs
+        if lowrank:
+            # no refinement pass where the model's amplification stays at or below 8 along its own run (9 is where a
+            # column could reach 10 gmres_tol; tests/test_adi_pairs_cpu.py asserts it for every LOWRANK operator)
+            amp = float(ref["amplification"].max())
+            print("[adi pairs] %s | largest model amplification %.2f, refinement passes %d" %
+                  (who, amp, info["pair_info"][2]))
+            if amp <= 8.0:
+                assert info["pair_info"][2] == 0, info["pair_info"]
+        else:
+            assert info["pair_info"][2] == 0
     else:
         assert "pair_info" not in info and info["shift_solves"] == info["adi_steps"]
     return info
@@ -217,6 +231,25 @@ def test_stopping_and_history():
         assert info["adi_stopped_by"] == "res" and ref["rule"] == "res"
         assert abs(info["adi_steps"] - ref["steps"]) <= 2 and info["cols"] == info["adi_steps"] * op.W.shape[1]
         assert ctx.adi_res_history()[-1] <= 1e-6
+
+
+def test_a_rule_that_fires_on_a_pairs_first_block_keeps_both_blocks():
+    """fe3, the first recipe pair with its imaginary part times 20, ``adi_newZ_reltol = 0.266``: the model's relative
+    block norms are 1.0, 0.99 and 0.101, 0.701 (tests/test_adi_pairs_cpu.py), so the rule fires on the second pair's
+    first block and not on its second.  The run ends with rule newZ behind that pair, both of its blocks in Z."""
+    op, mdl, lst = first_block_list()
+    m = op.W.shape[1]
+    with _context(op) as ctx:
+        Z, info = ctx.lyap_adi(lst, op.W, _lib.adi_params(dict(adi_max_steps=300, adi_newZ_reltol=FIRST_BLOCK_TOL)))
+    with _context(op) as ctx:
+        Z4, info4 = ctx.lyap_adi(lst, op.W, _lib.adi_params(dict(adi_max_steps=4, adi_newZ_reltol=0.0)))
+    print("[adi pairs] fe3 | first-block rule | steps %d cols %d pair_info %s stopped by %s" %
+          (info["adi_steps"], info["cols"], info["pair_info"], info["adi_stopped_by"]))
+    assert info["adi_stopped_by"] == "newZ" and info["adi_steps"] == 4 and info["cols"] == 4 * m == Z.shape[1]
+    assert info["pair_info"][0] == 2
+    assert info4["adi_stopped_by"] == "max_steps" and info4["cols"] == 4 * m
+    assert np.array_equal(Z, Z4[:, :4 * m])
+    assert np.all(np.any(Z[:, 2 * m:] != 0.0, axis=0)), "a block of the second pair is missing"
 
 
 def test_recompression_inside_the_iteration():
@@ -328,8 +361,11 @@ def test_dropin_takes_complex_lists_and_auto_complex():
     assert sum(2 if isinstance(p, complex) else 1 for p in outc["ms"]) <= 8
     assert _say("fe3", "drop-in, auto-complex", so.rel(outc["zfac"] @ outc["zfac"].T, X), LYAP_TOL)
     auto1 = pru.solve_proj_lyap_stein(adi_dict=dict(TIGHT, ms="auto"), **kw)
-    # (the same list up to the last bits: the projected pencil behind it is summed with atomics, in an order that
-    # varies from call to call -- eps-level changes of a pencil of order <= 128, far below the 1e-8 asked here)
+    # (the same list up to the last bits: the projected pencil itself is summed in a fixed order -- ricadi_project.hip
+    # has no atomics, test_gpu_adi_shifts.py asserts it bitwise --, but the Gram matrices of ctx.qr behind the basis it
+    # is projected on come from gemm_tn, which adds its slices with atomics in an order that varies from call to
+    # call, and the recycling ring starts the second call's solves from the first call's solutions: eps-level changes
+    # of a pencil of order <= 128, far below the 1e-8 asked here)
     assert len(auto1["ms"]) == len(auto0["ms"]) and all(type(p) is float for p in auto1["ms"])
     assert np.allclose(auto1["ms"], auto0["ms"], rtol=1e-8, atol=0.0) and "pair_info" not in auto1
     assert abs(auto1["adi_steps"] - auto0["adi_steps"]) <= 1

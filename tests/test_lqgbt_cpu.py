@@ -131,7 +131,7 @@ def test_header_exports_abi_and_signatures():
     assert "ABI 412" in hdr
     assert "cal A = A, cal E = M" in hdr                      # the orientation the device entry expects
     lib = _lib.load()
-    assert lib.ricadi_version() == _lib.ABI_VERSION == 413
+    assert lib.ricadi_version() == _lib.ABI_VERSION == 414
     ip, dp, vp = C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p
     sig = {"ricadi_cross_gram_dev": [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp],
            "ricadi_project_pencil_twosided_dev": [vp, vp, vp, C.c_int, vp, vp],

@@ -282,7 +282,7 @@ def test_header_exports_abi_and_signatures():
     assert float(re.search(r"#define RICADI_RADI_SWEEP_PIVOT (\S+)", hdr).group(1)) == swm.PIVOT
     assert float(re.search(r"#define RICADI_RADI_RANK_TOL (\S+)", hdr).group(1)) == sm.RANK_TOL
     lib = _lib.load()
-    assert lib.ricadi_version() == _lib.ABI_VERSION == 413
+    assert lib.ricadi_version() == _lib.ABI_VERSION == 414
     ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
     sig = {"ricadi_set_radi_sweep_shifts": [C.c_void_p, C.c_int],
            "ricadi_radi_sweep_widths": [C.c_void_p, None, C.c_int, ip],
